@@ -10,6 +10,12 @@ parallel); the timed region is bracketed by barriers and the max over ranks is
 reported.  Weights are synthetic (random init of the architecture, seeded) --
 there are no checkpoints offline.
 
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs:
+set up, W warm-up steps, K timed steps, the output dump if --dump-outputs is
+given, the result line.  --full adds every other leg after the timed steps (the
+evented roofline pass, this run's PMC passes, the library and text-in paths, the
+CPU baselines, the north-star probes); the --no-* switches trim it.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -45,6 +51,13 @@ def parse():
     p.add_argument("--seq", type=int, default=512)
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--model-dir", default=os.environ.get("EMB_MODEL_DIR", "/tmp/emb_models"))
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every other leg: the evented per-kernel / roofline pass, "
+                        "the PMC passes, the library and encode paths, the CPU baselines and the probes "
+                        "(each can be dropped again with its --no-* switch); off: the headline alone")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write what the last timed step computed (the caller's embedding rows, float32) to "
+                        "DIR/embeddings.npy (DIR/embeddings_rank<r>.npy per rank when --gpus > 1)")
     p.add_argument("--cpu-baseline-sentences", type=int, default=24)
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-profile", action="store_true", help="disable live per-kernel event timing")
@@ -63,7 +76,24 @@ def parse():
     p.add_argument("--dry-step", action="store_true",
                    help="CPU stub in place of the forward (no GPU, gloo): tests the launch / timing / reporting "
                         "skeleton, never a measurement")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.dump_outputs and a.dry_step:
+        p.error("--dump-outputs: the --dry-step stub computes nothing to dump")
+    if not a.full:
+        # a plain run: the headline's timed steps only
+        a.no_profile = a.no_pmc = a.no_library = a.no_encode = a.no_cpu_baseline = a.no_probes = True
+    return a
+
+
+def dump_outputs(out_dir, name, arr):
+    """--dump-outputs: one array a caller of the timed path receives, as
+    out_dir/<name>.npy in float32 (whole: the embedding rows of a batch are far
+    below the 64 MB a dump may hold)."""
+    import numpy as np
+    arr = np.ascontiguousarray(arr, dtype=np.float32)
+    assert arr.nbytes <= 64 << 20, arr.nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def launch_ranks(a):
@@ -524,7 +554,13 @@ def run_inproc(a):
     for _ in range(max(a.warmup, 1)):
         e = m.forward_batch(ids)
     assert np.all(np.isfinite(e)) and np.allclose(np.linalg.norm(e, axis=1), 1.0, atol=1e-3)
-    el = timed_steps(lambda: m.forward_batch(ids), a.steps, lambda: None)
+    last = [e]
+
+    def step():
+        last[0] = m.forward_batch(ids)
+    el = timed_steps(step, a.steps, lambda: None)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, "embeddings", last[0])
     per = m.device_last_call()
     busy = [p[0] for p in per if p[1] > 0]
     flop = a.inproc_batch * flop_per_sentence(hp, a.seq)
@@ -628,7 +664,6 @@ def main():
     for _ in range(a.warmup):
         step()
     sync()
-    e = fwd.check()
 
     red_dev = dev if (dist is not None and dist.get_backend() == "nccl") else "cpu"
     # timed region (the metric): graph replay of the forward, no per-kernel events
@@ -636,7 +671,12 @@ def main():
         lib.bertx_set_profiling(model.ctx, 0)
     rank_elapsed = []
     elapsed = timed_steps(step, a.steps, sync, dist, red_dev, per_rank=rank_elapsed)
-    # roofline pass: the same K steps again, launched eagerly with a HIP event
+    # what the last timed step left in the caller's rows (checked here, after the
+    # timed region, so that --warmup 0 has something to check)
+    e = fwd.check()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, "embeddings" if world == 1 else f"embeddings_rank{rank}", e)
+    # --full, roofline pass: the same K steps again, launched eagerly with a HIP event
     # pair around every kernel on the launch stream (per-kernel averages)
     stats = []
     profiled = lib is not None and not a.no_profile
@@ -724,9 +764,11 @@ def main():
         # step / step time: at C3 the path is MFMA-bound (AI ~1e5 FLOP/B), so this is
         # NOT an HBM-roofline figure -- see probes.q4_0_hbm and roofline.traffic
         "compulsory_gbps": round(alg_bytes / (ms_per_step * 1e-3) / 1e9, 2),
-        "timing": "value: K graph-replayed forwards (no events); roofline/kernels: a second pass of K eager "
-                  "forwards with HIP events around every kernel"
-                  + (f" ({prof_elapsed / a.steps * 1e3:.3f} ms/step)" if profiled else ""),
+        "timing": "value: K graph-replayed forwards (no events)"
+                  + (f"; roofline/kernels: a second pass of K eager forwards with HIP events around every kernel "
+                     f"({prof_elapsed / a.steps * 1e3:.3f} ms/step)" if profiled
+                     else "; no roofline/kernels pass (--full without --no-profile runs it)"),
+        "full": a.full,
         "roofline": roofline,
         "kernels": kernels,
         # every rank's own rate over the same timed region (value uses the max time)

@@ -18,9 +18,9 @@ if [ -n "$STAMPS" ]; then
 fi
 summ() { python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], d['value'], {k: round(v['avg_us'], 1) for k, v in d['kernels'].items()})" "$@"; }
 for r in 1 2; do
-  BERT_LIB=$LIB_A step 300 python -u bench.py --no-cpu-baseline --no-probes --no-library > $OUT/bench_a$r.log 2>&1 || { tail -20 $OUT/bench_a$r.log; exit 1; }
+  BERT_LIB=$LIB_A step 300 python -u bench.py --full --no-cpu-baseline --no-probes --no-library > $OUT/bench_a$r.log 2>&1 || { tail -20 $OUT/bench_a$r.log; exit 1; }
   summ $OUT/bench_a$r.log A | tee -a $OUT/ab.log
-  step 300 python -u bench.py --no-cpu-baseline --no-probes --no-library > $OUT/bench_b$r.log 2>&1 || { tail -20 $OUT/bench_b$r.log; exit 1; }
+  step 300 python -u bench.py --full --no-cpu-baseline --no-probes --no-library > $OUT/bench_b$r.log 2>&1 || { tail -20 $OUT/bench_b$r.log; exit 1; }
   summ $OUT/bench_b$r.log B | tee -a $OUT/ab.log
 done
 echo ab-ok

@@ -9,7 +9,7 @@ mkdir -p $OUT
 for r in 1 2; do
   for v in $VALS; do
     lg=$OUT/run_${v//\//_}_${r}.log
-    env $VAR=$v timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-probes --no-library ${BENCH_ARGS:-} > $lg 2>&1 || { tail -20 $lg; exit 1; }
+    env $VAR=$v timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-probes --no-library ${BENCH_ARGS:-} > $lg 2>&1 || { tail -20 $lg; exit 1; }
     python3 - "$lg" "$VAR=$v" <<'PY' | tee -a $OUT/ab.log
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -23,7 +23,7 @@ if has smoke; then
   tail -1 $OUT/smoke.log
 fi
 if has bench; then
-  step 400 python -u bench.py ${BENCH_ARGS:-} > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
+  step 400 python -u bench.py --full ${BENCH_ARGS:-} > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
   tail -c 600 $OUT/bench.log
 fi
 if has prof; then

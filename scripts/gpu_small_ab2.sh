@@ -17,7 +17,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   env $ON_ENV timeout -k 10 600 python -u -m pytest -x -q --timeout 300 --timeout-method thread -m gpu ${ON_TESTS:-tests/test_gpu_forward.py} > $OUT/t_forward_on.log 2>&1 || { tail -30 $OUT/t_forward_on.log; exit 1; }
   tail -1 $OUT/t_forward_on.log
 fi
-B="--no-cpu-baseline --no-library --no-pmc --no-encode --steps 20"
+B="--full --no-cpu-baseline --no-library --no-pmc --no-encode --steps 20"
 for i in $(seq 1 ${ROUNDS:-2}); do
   step 300 python bench.py $B > $OUT/bench_off$i.log 2>&1 || { tail -20 $OUT/bench_off$i.log; exit 1; }
   env $ON_ENV timeout -k 10 300 python bench.py $B > $OUT/bench_on$i.log 2>&1 || { tail -20 $OUT/bench_on$i.log; exit 1; }

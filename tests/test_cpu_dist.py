@@ -130,6 +130,36 @@ def test_bench_gpus_2_starts_two_ranks():
     assert abs(res["value"] - 128 * 1e3 / res["ms_per_step"]) / res["value"] < 1e-3
 
 
+EXTRA_LEGS = ("no_profile", "no_pmc", "no_library", "no_encode", "no_cpu_baseline", "no_probes")
+
+
+def test_plain_run_switches_every_extra_leg_off(monkeypatch):
+    """Without --full the run is the headline alone: every other leg (evented pass,
+    PMC, library and encode paths, CPU baselines, probes) is off; --full turns them
+    all on, and a --no-* switch still drops its own leg."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert all(getattr(a, k) for k in EXTRA_LEGS)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not any(getattr(a, k) for k in EXTRA_LEGS)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-pmc"])
+    a = bench.parse()
+    assert [k for k in EXTRA_LEGS if getattr(a, k)] == ["no_pmc"]
+
+
+def test_dump_outputs_writes_float32_npy(tmp_path):
+    import bench
+    x = np.random.default_rng(0).standard_normal((6, 16))          # float64, non-contiguous view below
+    d = str(tmp_path / "new" / "dir")
+    bench.dump_outputs(d, "embeddings", x[::2])
+    got = np.load(os.path.join(d, "embeddings.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, x[::2].astype(np.float32))
+    assert os.listdir(d) == ["embeddings.npy"]
+
+
 def test_bench_refuses_world_mismatch():
     """A rank whose WORLD_SIZE disagrees with --gpus stops before any work."""
     import subprocess
