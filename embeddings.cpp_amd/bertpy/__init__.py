@@ -93,6 +93,17 @@ def load_lib(path=None):
     L.bertx_test_gemm_ran.argtypes = []
     L.bertx_test_gemm_f32.restype = c_i32
     L.bertx_test_gemm_f32.argtypes = [c_i32, c_i32, vp, vp, c_i32, vp, c_i32, vp, vp]
+    try:   # (the activation mode and its hooks: absent from older BERT_LIB builds)
+        L.bertx_load_from_file.restype = vp
+        L.bertx_load_from_file.argtypes = [ctypes.c_char_p, c_i32]
+        L.bertx_activation_mode.restype = c_i32
+        L.bertx_activation_mode.argtypes = [vp]
+        L.bertx_test_quantize_act.restype = c_i32
+        L.bertx_test_quantize_act.argtypes = [c_i32, c_i32, c_i32, vp, vp, vp, vp]
+        L.bertx_test_gemm_q8.restype = c_i32
+        L.bertx_test_gemm_q8.argtypes = [c_i32, c_i32, c_i32, vp, vp, c_i32, vp, c_i32, vp, vp]
+    except AttributeError:
+        pass
     L.bertx_bench_gemm.restype = c_i32
     L.bertx_bench_gemm.argtypes = [c_i32] * 7 + [c_f32p]
     L.bertx_bench_attention.restype = c_i32
@@ -119,9 +130,19 @@ class BertModel:
 
     N_THREADS = 6   # sample_dylib.py:7
 
-    def __init__(self, fname, lib=None):
+    ACT_MODES = {"f16": 0, "q8": 1}
+
+    def __init__(self, fname, lib=None, act=None):
+        """act: None = the plain ABI call (the mode comes from BERT_ACT, default f16);
+        "f16" / "q8" = bertx_load_from_file with that activation mode ("q8": the
+        reference's q8-activation arithmetic, quantized files only)."""
         self.lib = lib or load_lib()
-        self.ctx = self.lib.bert_load_from_file(fname.encode("utf-8"))
+        if act is None:
+            self.ctx = self.lib.bert_load_from_file(fname.encode("utf-8"))
+        else:
+            if act not in self.ACT_MODES:
+                raise ValueError("act must be None, 'f16' or 'q8', not %r" % (act,))
+            self.ctx = self.lib.bertx_load_from_file(fname.encode("utf-8"), self.ACT_MODES[act])
         if not self.ctx:
             raise RuntimeError("bert_load_from_file failed for " + fname)
         self.n_embd = self.lib.bert_n_embd(self.ctx)
@@ -131,6 +152,11 @@ class BertModel:
         if getattr(self, "ctx", None):
             self.lib.bert_free(self.ctx)
             self.ctx = None
+
+    @property
+    def activation_mode(self):
+        """The activation mode the context runs: 0 = f16, 1 = the reference's q8."""
+        return int(self.lib.bertx_activation_mode(self.ctx))
 
     def encode(self, sentences, batch_size=16):
         input_is_string = isinstance(sentences, str)

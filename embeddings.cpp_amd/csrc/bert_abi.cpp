@@ -84,6 +84,7 @@ struct bert_ctx {
     emb::Vocab vocab;
     std::vector<std::unique_ptr<Device>> devices;
     bool host_only = false;
+    int act_mode = 0;   // the activation mode the context runs (bertx_activation_mode)
     // routing state of run_forward: the cost of the work routed to each replica and
     // not yet finished, and the rotation that breaks ties between equal loads
     std::mutex route_mu;
@@ -365,8 +366,13 @@ bool bert_params_parse(int argc, char **argv, bert_params &params)
 // All HIP calls of the load run on this thread, one replica after another; the
 // weight uploads still overlap (async copies from one page-locked image on each
 // replica's stream).  DESIGN §11 has the round-5 abort this replaces.
-static bert_ctx *load_context(const char *fname)
+// act_mode: 0 (f16 activations) or 1 (the reference's q8 activations, bert_hip.h).
+static bert_ctx *load_context(const char *fname, int act_mode)
 {
+    if (act_mode != 0 && act_mode != 1) {
+        emb::errorf("bertx_load_from_file: act_mode %d is not an activation mode (0 = f16, 1 = q8)\n", act_mode);
+        return nullptr;
+    }
     emb::infof("bert_load_from_file: loading model from '%s' - please wait ...\n", fname);
     if (emb::fault_inject("load")) throw std::runtime_error("BERT_FAULT_INJECT=load");
     emb::HostModel m;
@@ -381,6 +387,10 @@ static bert_ctx *load_context(const char *fname)
     std::unique_ptr<bert_ctx> ctx(new bert_ctx);
     ctx->hp = m.hp;
     ctx->vocab.build(m.vocab);
+    ctx->act_mode = emb::act_mode_effective(m.hp.ftype, act_mode);
+    if (act_mode == 1 && ctx->act_mode == 0)
+        emb::infof("bert_load_from_file: q8 activations asked for a file of ftype %d: the reference has no q8 "
+                   "arithmetic for f16 / f32 files, running the default mode\n", m.hp.ftype);
     const char *ho = std::getenv("BERT_HOST_ONLY");
     const bool host_only = ho && *ho && std::strcmp(ho, "0") != 0;
     if (host_only) {
@@ -390,7 +400,7 @@ static bert_ctx *load_context(const char *fname)
     }
     const std::vector<int> devs = parse_device_list(emb::hip_device_count());
     // the host half of the load, once for all replicas: repack into one image
-    if (!emb::build_model_image(m, img, err, !devs.empty())) {
+    if (!emb::build_model_image(m, img, err, !devs.empty(), ctx->act_mode)) {
         emb::errorf("bert_load_from_file: %s\n", err.c_str());
         return nullptr;
     }
@@ -431,13 +441,16 @@ static bert_ctx *load_context(const char *fname)
     if (m.hp.ftype == emb::FMT_F32)
         emb::infof("bert_load_from_file: f32 file: f32 activations x f32 weights on the f32 MFMA chain "
                    "(as the reference multiplies them, bert.cpp:499-503)\n");
+    if (ctx->act_mode == 1)
+        emb::infof("bert_load_from_file: q8 activations: every projection re-quantizes its input per 32-block and "
+                   "takes integer block dots (as the reference, bert.cpp:995)\n");
     return ctx.release();
 }
 
-struct bert_ctx *bert_load_from_file(const char *fname)
+static bert_ctx *load_guarded(const char *fname, int act_mode)
 {
     try {
-        return load_context(fname);
+        return load_context(fname, act_mode);
     } catch (const std::bad_alloc &) {
         emb::errorf("bert_load_from_file: out of host memory\n");
     } catch (const std::exception &ex) {
@@ -447,6 +460,26 @@ struct bert_ctx *bert_load_from_file(const char *fname)
     }
     return nullptr;
 }
+
+// The reference's entry point has no mode argument: its unmodified clients choose
+// with the environment, BERT_ACT=f16|q8, read at every load (unset: f16).
+struct bert_ctx *bert_load_from_file(const char *fname)
+{
+    const char *ea = std::getenv("BERT_ACT");
+    int act_mode = 0;
+    if (ea && *ea && std::strcmp(ea, "f16") != 0) {
+        if (std::strcmp(ea, "q8") != 0) {
+            emb::errorf("bert_load_from_file: BERT_ACT='%s' is not an activation mode (f16 or q8)\n", ea);
+            return nullptr;
+        }
+        act_mode = 1;
+    }
+    return load_guarded(fname, act_mode);
+}
+
+struct bert_ctx *bertx_load_from_file(const char *fname, int32_t act_mode) { return load_guarded(fname, act_mode); }
+
+int32_t bertx_activation_mode(struct bert_ctx *ctx) { return ctx->act_mode; }
 
 void bert_free(bert_ctx *ctx) { delete ctx; }
 

@@ -59,6 +59,28 @@ __device__ __forceinline__ uint32_t and_or_vs(uint32_t x, uint32_t vmask, uint32
     return r;
 }
 
+// a * b and a + b, each rounded on its own: the operations carry no contraction
+// permission, so the compiler never fuses them into an FMA (it does fuse __fmul_rn
+// into __fadd_rn).  For the chains that reproduce the reference's f32 roundings.
+__device__ __forceinline__ float mul_rn(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+// The era's fp16 tables (GELU, exp), built on the host with libm at load
+// (model_file.cpp era_tables) and indexed by the f16 bit pattern of the input:
+// T(f16(x)), bit for bit the table ggml held (the f32 and q8-activation chains).
+__device__ __forceinline__ float era_table(const uint16_t *__restrict__ tab, float v)
+{
+    return (float)as_h(tab[__builtin_bit_cast(uint16_t, (h16)v)]);
+}
+
 // ggml-era GELU (tanh form) on an f16-rounded input, result rounded to f16 --
 // the value ggml's GGML_GELU_FP16 table holds (bert.cpp:1063).  Evaluated as
 // 0.5 x (1 + tanh(u)) = x / (1 + exp(-2u)), well inside f16 rounding.

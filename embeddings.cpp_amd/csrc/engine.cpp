@@ -221,7 +221,7 @@ ModelImage::~ModelImage()
     if (pinned_) (void)hipHostFree(pinned_);
 }
 
-bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bool pin)
+bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bool pin, int act_mode)
 {
     try {
         const HParams &hp = m.hp;
@@ -240,6 +240,9 @@ bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bo
         // f32 files run the f32 chain (f32.hip) on the file's own f32 rows; the other
         // formats the lane-order layout of the MFMA f16 GEMMs
         img.f32 = img.wfmt == FMT_F32;
+        // activation mode 1 (quantized files): the same lane-order weights under the
+        // q8-activation chain (q8act.hip)
+        img.q8 = act_mode_effective(img.wfmt, act_mode) == 1;
         std::vector<Piece> pieces;
         pieces.reserve(16 + 24 * (size_t)hp.n_layer);
         auto add = [&](Piece &&p) -> size_t { pieces.push_back(std::move(p)); return pieces.size() - 1; };
@@ -262,9 +265,9 @@ bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bo
         img.word = table(m.word);
         img.type = table(m.ttype);
         img.pos = table(m.pos);
-        // f32 chain: the era's fp16 GELU and exp tables, built on the host (libm) as
-        // ggml built them, indexed on the device by the f16 bits of the input
-        if (img.f32) {
+        // f32 and q8 chains: the era's fp16 GELU and exp tables, built on the host (libm)
+        // as ggml built them, indexed on the device by the f16 bits of the input
+        if (img.f32 || img.q8) {
             std::vector<uint16_t> tg, te;
             era_tables(tg, te);
             Piece pg, pe;
@@ -310,11 +313,16 @@ bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bo
             x.o = linear({&L.o_w});
             x.up = linear({&L.i_w});
             x.down = linear({&L.o2_w});
-            // the LN in front of QKV: the previous layer's output LN, or the embedding LN
-            const HostTensor &gq = l ? m.layers[(size_t)l - 1].ln_out_w : m.ln_e_w;
-            const HostTensor &bq = l ? m.layers[(size_t)l - 1].ln_out_b : m.ln_e_b;
-            fold({&L.q_w, &L.k_w, &L.v_w}, {&L.q_b, &L.k_b, &L.v_b}, gq, bq, x.c1q, x.c2q);
-            fold({&L.i_w}, {&L.i_b}, L.ln_att_w, L.ln_att_b, x.c1u, x.c2u);
+            if (img.q8) {
+                // LayerNorm is a kernel of its own in this chain: the raw biases, no fold
+                x.bq = rows32({&L.q_b, &L.k_b, &L.v_b}); x.bu = vec(L.i_b);
+            } else {
+                // the LN in front of QKV: the previous layer's output LN, or the embedding LN
+                const HostTensor &gq = l ? m.layers[(size_t)l - 1].ln_out_w : m.ln_e_w;
+                const HostTensor &bq = l ? m.layers[(size_t)l - 1].ln_out_b : m.ln_e_b;
+                fold({&L.q_w, &L.k_w, &L.v_w}, {&L.q_b, &L.k_b, &L.v_b}, gq, bq, x.c1q, x.c2q);
+                fold({&L.i_w}, {&L.i_b}, L.ln_att_w, L.ln_att_b, x.c1u, x.c2u);
+            }
             x.bo = vec(L.o_b); x.bdown = vec(L.o2_b);
             x.l1w = vec(L.ln_att_w); x.l1b = vec(L.ln_att_b); x.l2w = vec(L.ln_out_w); x.l2b = vec(L.ln_out_b);
         }
@@ -439,6 +447,7 @@ void Device::bind(const ModelImage &img)
 {
     wfmt_ = img.wfmt;
     f32_ = img.f32;
+    q8_ = img.q8;
     auto P = [&](size_t i) -> void * {
         return (i == ModelImage::kNone || img.len[i] == 0) ? nullptr : (void *)(arena_ + img.off[i]);
     };
@@ -448,7 +457,7 @@ void Device::bind(const ModelImage &img)
         r.qs = P(x.q); r.d = (const uint16_t *)P(x.d); r.m = (const uint16_t *)P(x.m);
         return r;
     };
-    if (f32_) {
+    if (f32_ || q8_) {
         gelu_tab_ = (const uint16_t *)P(img.gelu);
         exp_tab_ = (const uint16_t *)P(img.exp);
     }
@@ -478,6 +487,7 @@ void Device::bind(const ModelImage &img)
         }
         D.qkv = mk_lin(x.qkv); D.o = mk_lin(x.o); D.up = mk_lin(x.up); D.down = mk_lin(x.down);
         D.b_o = (float *)P(x.bo); D.b_down = (float *)P(x.bdown);
+        D.b_qkv = (const float *)P(x.bq); D.b_up = (const float *)P(x.bu);   // (q8 chain; else absent)
         D.c1_qkv = (float *)P(x.c1q); D.c2_qkv = (float *)P(x.c2q); D.c1_up = (float *)P(x.c1u); D.c2_up = (float *)P(x.c2u);
         D.ln1_w = (float *)P(x.l1w); D.ln1_b = (float *)P(x.l1b); D.ln2_w = (float *)P(x.l2w); D.ln2_b = (float *)P(x.l2b);
     }
@@ -500,12 +510,15 @@ bool Device::reserve(int64_t tokens, int64_t seqs, int max_len)
     const int64_t d = hp_.n_embd, f = hp_.n_intermediate;
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
-    // f16 chain: Z, QKV, ATT, FFN f16 + statistics; f32 chain: X, Z, QKV, ATT, FFN f32
-    const int64_t r16 = f32_ ? 0 : rows, r32 = f32_ ? rows : 0;
+    // f16 chain: Z, QKV, ATT, FFN f16 + statistics; f32 and q8 chains: X, Z, QKV, ATT,
+    // FFN f32; q8 chain: the int8 input of a projection, its block scales and sums
+    const bool c32 = f32_ || q8_;
+    const int64_t r16 = c32 ? 0 : rows, r32 = c32 ? rows : 0, rq = q8_ ? rows : 0, kq = std::max(d, f);
     const size_t o_st = take(r16 * 8), o_z = take(r16 * d * 2), o_part = take(r16 * (d / 32) * 8);
     const size_t o_qkv = take(r16 * 3 * d * 2), o_att = take(r16 * d * 2), o_ffn = take(r16 * f * 2);
     const size_t o_x32 = take(r32 * d * 4), o_z32 = take(r32 * d * 4), o_qkv32 = take(r32 * 3 * d * 4);
     const size_t o_att32 = take(r32 * d * 4), o_ffn32 = take(r32 * f * 4);
+    const size_t o_xq = take(rq * kq), o_xd = take(rq * (kq / 32) * 4), o_xs = take(rq * (kq / 32) * 4);
     const size_t o_ids = take(rows * 4), o_cu = take((ns + 1) * 4), o_out = take(ns * d * 4);
     const size_t o_pool = take((size_t)np * d * 4);
     drop_graphs();   // captured graphs hold the old workspace pointers
@@ -526,6 +539,7 @@ bool Device::reserve(int64_t tokens, int64_t seqs, int max_len)
     pool_part_ = (float *)(ws_ + o_pool);
     x32_ = (float *)(ws_ + o_x32); z32_ = (float *)(ws_ + o_z32); qkv32_ = (float *)(ws_ + o_qkv32);
     att32_ = (float *)(ws_ + o_att32); ffn32_ = (float *)(ws_ + o_ffn32);
+    xq_ = (int8_t *)(ws_ + o_xq); xd_ = (float *)(ws_ + o_xd); xs_ = (float *)(ws_ + o_xs);
     HIP_OK(hipHostMalloc((void **)&h_ids_, nt * 4, hipHostMallocDefault));
     HIP_OK(hipHostMalloc((void **)&h_cu_, (ns + 1) * 4, hipHostMallocDefault));
     HIP_OK(hipHostMalloc((void **)&h_out_, ns * d * 4, hipHostMallocDefault));
@@ -654,6 +668,7 @@ int Device::launch_all(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, in
                        hipStream_t s, bool check)
 {
     if (f32_) return launch_all_f32(d_ids, d_cu, n_seqs, max_len, T, d_out, s);
+    if (q8_) return launch_all_q8(d_ids, d_cu, n_seqs, max_len, T, d_out, s);
     const int d = hp_.n_embd, f = hp_.n_intermediate;
     const int M = gemm_rows(T);   // GEMM rows: T padded to whole tiles
     const double t = (double)T;
@@ -806,6 +821,61 @@ int Device::launch_all_f32(const int32_t *d_ids, const int32_t *d_cu, int n_seqs
     }
     begin(K_POOL_L2, s, ev);
     launch_f32_pool(x32_, d_cu, n_seqs, d, d_out, s);
+    end(K_POOL_L2, s, ev, t * d * 4.0 + (double)n_seqs * d * 4.0);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        errorf("libbert: kernel launch failed: %s\n", hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
+}
+
+// The q8-activation chain (q4_0 / q4_1 / q8_0 files in activation mode 1): the f32
+// chain above with every projection in the reference's block arithmetic -- its
+// input re-quantized to q8_0 / q8_1 (bert.cpp:995 through ggml), then the integer
+// block GEMM (q8act.hip).  The quantize launch is timed inside its projection's class.
+int Device::launch_all_q8(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out,
+                          hipStream_t s)
+{
+    const int d = hp_.n_embd, f = hp_.n_intermediate;
+    const int M = gemm_rows(T);
+    const double t = (double)T;
+    const int kind = wfmt_ == FMT_Q4_1 ? 1 : 0;   // q8_1 activations for q4_1 weights, else q8_0
+    hipEvent_t ev;
+    // Y = epi(quantize(X) W^T): rows T <= row < M (tile padding) enter as zeros
+    auto proj = [&](const DevWeight &W, const float *X, const float *bias, int epi, const float *res, float *Y) {
+        if (launch_q8_quantize(X, T, M, W.K, kind, xq_, xd_, xs_, s)) return -1;
+        return launch_q8_gemm(W, xq_, xd_, xs_, M, bias, epi, res, Y, s, gelu_tab_);
+    };
+    begin(K_EMBED_LN, s, ev);
+    launch_f32_embed_ln(word_, type_, pos_, ln_e_w_, ln_e_b_, d_ids, d_cu, n_seqs, max_len, d, x32_, s, true);
+    end(K_EMBED_LN, s, ev, t * (4.0 + 3.0 * d * 4.0 + 4.0 * d));
+    for (int l = 0; l < hp_.n_layer; ++l) {
+        const DevLayer &L = layers_[(size_t)l];
+        begin(K_GEMM_QKV, s, ev);
+        if (proj(L.qkv, x32_, L.b_qkv, 0, nullptr, qkv32_)) return -1;
+        end(K_GEMM_QKV, s, ev, 2.0 * t * 3.0 * d * d);
+        begin(K_ATTENTION, s, ev);
+        if (launch_f32_attention(qkv32_, d_cu, n_seqs, max_len, hp_.n_head, d, att32_, s, exp_tab_, true)) return -1;
+        end(K_ATTENTION, s, ev, att_flop_);
+        begin(K_GEMM_O, s, ev);
+        if (proj(L.o, att32_, L.b_o, 2, x32_, z32_)) return -1;
+        end(K_GEMM_O, s, ev, 2.0 * t * d * d);
+        begin(K_LN_STATS, s, ev);
+        launch_f32_ln(z32_, M, d, L.ln1_w, L.ln1_b, s, true);
+        end(K_LN_STATS, s, ev, (double)M * d * 8.0);
+        begin(K_GEMM_FFN_UP, s, ev);
+        if (proj(L.up, z32_, L.b_up, 1, nullptr, ffn32_)) return -1;
+        end(K_GEMM_FFN_UP, s, ev, 2.0 * t * d * f);
+        begin(K_GEMM_FFN_DOWN, s, ev);
+        if (proj(L.down, ffn32_, L.b_down, 2, z32_, x32_)) return -1;
+        end(K_GEMM_FFN_DOWN, s, ev, 2.0 * t * d * f);
+        begin(K_LN_STATS, s, ev);
+        launch_f32_ln(x32_, M, d, L.ln2_w, L.ln2_b, s, true);
+        end(K_LN_STATS, s, ev, (double)M * d * 8.0);
+    }
+    begin(K_POOL_L2, s, ev);
+    launch_f32_pool(x32_, d_cu, n_seqs, d, d_out, s, true);
     end(K_POOL_L2, s, ev, t * d * 4.0 + (double)n_seqs * d * 4.0);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -1047,6 +1117,71 @@ extern "C" int32_t bertx_test_gemm_f32(int32_t N, int32_t K, const float *w, con
     const uint16_t *dg = (const uint16_t *)B.up(tg.data(), tg.size() * 2, 0);
     if (B.bad) return -1;
     if (launch_f32_gemm(dx, Mp, dw, N, K, db, epi, dr, dout, nullptr, dg) != 0) return -1;
+    HIP_RC(hipGetLastError());
+    HIP_RC(hipDeviceSynchronize());
+    HIP_RC(hipMemcpy(out, dout, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// q8-activation chain (q8act.hip): the activation quantizer on host buffers; the
+// device's block-major scale planes [K/32][Mp] come back as [M][K/32]
+extern "C" int32_t bertx_test_quantize_act(int32_t kind, int32_t M, int32_t K, const float *x, int8_t *q, float *d,
+                                           float *s)
+{
+    using namespace emb;
+    if ((kind != 0 && kind != 1) || M <= 0 || K <= 0 || K % 32 || !x || !q || !d || (kind == 1 && !s) ||
+        hip_device_count() == 0)
+        return -1;
+    const int Mp = (int)align_up((size_t)M, 64), nb = K / 32;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const float *dx = (const float *)B.up(x, (size_t)M * K * 4, 0);
+    int8_t *dq = (int8_t *)B.up(nullptr, 0, (size_t)Mp * K);
+    float *dd = (float *)B.up(nullptr, 0, (size_t)Mp * nb * 4), *ds = (float *)B.up(nullptr, 0, (size_t)Mp * nb * 4);
+    if (B.bad) return -1;
+    if (launch_q8_quantize(dx, M, Mp, K, kind, dq, dd, ds, nullptr) != 0) return -1;
+    HIP_RC(hipGetLastError());
+    HIP_RC(hipDeviceSynchronize());
+    HIP_RC(hipMemcpy(q, dq, (size_t)M * K, hipMemcpyDeviceToHost));
+    std::vector<float> pl((size_t)Mp * nb);
+    for (int pass = 0; pass < (kind == 1 ? 2 : 1); ++pass) {
+        HIP_RC(hipMemcpy(pl.data(), pass ? ds : dd, pl.size() * 4, hipMemcpyDeviceToHost));
+        float *o = pass ? s : d;
+        for (int r = 0; r < M; ++r)
+            for (int b = 0; b < nb; ++b) o[(size_t)r * nb + b] = pl[(size_t)b * Mp + r];
+    }
+    return 0;
+}
+
+// q8-activation chain: one projection as the forward runs it (quantize, then the
+// block-integer GEMM): x f32 [M][K], res / out f32 [M][N]
+extern "C" int32_t bertx_test_gemm_q8(int32_t fmt, int32_t N, int32_t K, const void *w_rows, const float *bias,
+                                      int32_t M, const float *x, int32_t epi, const float *res, float *out)
+{
+    using namespace emb;
+    if ((fmt != FMT_Q4_0 && fmt != FMT_Q4_1 && fmt != FMT_Q8_0) || K <= 0 || K % 64 || N <= 0 || N % 32 || M <= 0 ||
+        epi < 0 || epi > 2 || (epi == 2 && !res) || !w_rows || !bias || !x || !out || hip_device_count() == 0)
+        return -1;
+    const int Mp = gemm_rows(M), nb = K / 32;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    HostTensor t;
+    DevWeight W;
+    if (!hook_weight(fmt, N, K, w_rows, t, W, B)) return -1;
+    const float *db = (const float *)B.up(bias, (size_t)N * 4, 0);
+    const float *dx = (const float *)B.up(x, (size_t)M * K * 4, 0);
+    const float *dr = epi == 2 ? (const float *)B.up(res, (size_t)M * N * 4, (size_t)Mp * N * 4) : nullptr;
+    float *dout = (float *)B.up(nullptr, 0, (size_t)Mp * N * 4);
+    int8_t *dq = (int8_t *)B.up(nullptr, 0, (size_t)Mp * K);
+    float *dd = (float *)B.up(nullptr, 0, (size_t)Mp * nb * 4), *ds = (float *)B.up(nullptr, 0, (size_t)Mp * nb * 4);
+    std::vector<uint16_t> tg, te;
+    era_tables(tg, te);
+    const uint16_t *dg = (const uint16_t *)B.up(tg.data(), tg.size() * 2, 0);
+    if (B.bad) return -1;
+    if (launch_q8_quantize(dx, M, Mp, K, fmt == FMT_Q4_1 ? 1 : 0, dq, dd, ds, nullptr) != 0) return -1;
+    if (launch_q8_gemm(W, dq, dd, ds, Mp, db, epi, dr, dout, nullptr, dg) != 0) return -1;
     HIP_RC(hipGetLastError());
     HIP_RC(hipDeviceSynchronize());
     HIP_RC(hipMemcpy(out, dout, (size_t)M * N * 4, hipMemcpyDeviceToHost));

@@ -36,7 +36,8 @@ struct DevLayer {
     float *c1_qkv = nullptr, *c2_qkv = nullptr, *c1_up = nullptr, *c2_up = nullptr;
     float *ln1_w = nullptr, *ln1_b = nullptr, *ln2_w = nullptr, *ln2_b = nullptr;
     // f32 files (the f32 chain, f32.hip): weights as the file rows [N][K] f32, QKV
-    // fused [3d][d] with its bias [3d]
+    // fused [3d][d] with its bias [3d]; the q8-activation chain uses the two biases
+    // with the lane-order weights above
     const float *w32_qkv = nullptr, *w32_o = nullptr, *w32_up = nullptr, *w32_down = nullptr;
     const float *b_qkv = nullptr, *b_up = nullptr;
 };
@@ -80,6 +81,7 @@ struct ModelImage {
     HParams hp;
     int wfmt = FMT_F16;
     bool f32 = false;
+    bool q8 = false;   // activation mode 1 on a q4_0 / q4_1 / q8_0 file: the q8-activation chain (q8act.hip)
     Tab word, type, pos;
     size_t gelu = kNone, exp = kNone, lnw = kNone, lnb = kNone;
     std::vector<Layer> layers;
@@ -95,15 +97,24 @@ struct ModelImage {
     ModelImage &operator=(const ModelImage &) = delete;
 
 private:
-    friend bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bool pin);
+    friend bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bool pin, int act_mode);
     std::vector<uint8_t> host_;       // pageable image (when pinning failed or no device)
     uint8_t *pinned_ = nullptr;       // page-locked image (hipHostMalloc): async uploads
 };
 
 // Host work of a load, once per context: checks the shape, repacks every plane
 // and concatenates them into the image (page-locked when `pin`).  False with a
-// message in err; never throws (a bad_alloc becomes false).
-bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bool pin);
+// message in err; never throws (a bad_alloc becomes false).  act_mode 1 (the
+// reference's q8 activations, quantized files only: act_mode_effective): the
+// image carries the raw QKV / FFN-up biases and the era tables, as for f32 files,
+// and no LN-fold constants.
+bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bool pin, int act_mode = 0);
+// The activation mode a file of format `ftype` runs when `act_mode` is asked for:
+// 1 only for q4_0 / q4_1 / q8_0 (f16 and f32 files have no q8 arithmetic in the reference).
+inline int act_mode_effective(int ftype, int act_mode)
+{
+    return act_mode == 1 && (ftype == FMT_Q4_0 || ftype == FMT_Q4_1 || ftype == FMT_Q8_0) ? 1 : 0;
+}
 
 class Device {
 public:
@@ -181,6 +192,8 @@ private:
                    hipStream_t s, bool check);
     int launch_all_f32(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out,
                        hipStream_t s);
+    int launch_all_q8(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out,
+                      hipStream_t s);
     void drop_graphs();
     void bind(const ModelImage &img);   // device pointers of the image's planes
     bool uploading_ = false;
@@ -202,7 +215,8 @@ private:
     std::vector<DevLayer> layers_;
     int wfmt_ = FMT_F16;
     bool f32_ = false;              // ftype 0 file: the f32 chain (f32.hip)
-    const uint16_t *gelu_tab_ = nullptr, *exp_tab_ = nullptr;   // f32 chain: the era's fp16 tables (host-built)
+    bool q8_ = false;               // activation mode 1: the q8-activation chain (q8act.hip + f32.hip)
+    const uint16_t *gelu_tab_ = nullptr, *exp_tab_ = nullptr;   // f32 / q8 chains: the era's fp16 tables (host-built)
 
     // workspace
     int64_t cap_tokens_ = 0, cap_seqs_ = 0, cap_pool_ = 0;   // cap_pool_: pool partial rows (seqs x chunks)
@@ -215,7 +229,9 @@ private:
     float2 *part_ = nullptr;        // [d/32][rows] group partials of the residual GEMMs
     int64_t rows_ = 0;              // workspace rows (part_ stride)
     uint16_t *qkv_ = nullptr, *att_ = nullptr, *ffn_ = nullptr;
-    float *x32_ = nullptr, *z32_ = nullptr, *qkv32_ = nullptr, *att32_ = nullptr, *ffn32_ = nullptr;   // f32 chain
+    float *x32_ = nullptr, *z32_ = nullptr, *qkv32_ = nullptr, *att32_ = nullptr, *ffn32_ = nullptr;   // f32 / q8 chains
+    int8_t *xq_ = nullptr;          // q8 chain: the quantized input of the next projection [rows][max(d, f)]
+    float *xd_ = nullptr, *xs_ = nullptr;   // ... its block scales and q8_1 sums [max(d, f) / 32][M]
     int32_t *d_ids_ = nullptr, *d_cu_ = nullptr;
     float *d_out_ = nullptr;
     float *pool_part_ = nullptr;

@@ -33,6 +33,9 @@ constexpr int F32_MAXC = 4;   // float4 chunks per lane: d <= 1024
 
 // ggml_norm (mean and centred variance summed in f64, eps 1e-5) then * gamma +
 // beta (bert.cpp:977-984), of one row held as lane chunks c = 4 lane + 256 k.
+// EXACT (the q8-activation chain): y * scale, * gamma, + beta as three operations the
+// compiler cannot contract (mul_rn / add_rn), the oracle's roundings bit for bit.
+template <bool EXACT>
 __device__ __forceinline__ void ln_row(f32x4 (&v)[F32_MAXC], int d, int lane, const float *__restrict__ g,
                                        const float *__restrict__ b)
 {
@@ -63,12 +66,15 @@ __device__ __forceinline__ void ln_row(f32x4 (&v)[F32_MAXC], int d, int lane, co
             // ggml_norm's y = c * scale, then ggml_mul (gamma) and ggml_add (beta):
             // three rounded ops, no contraction (bert.cpp:977-984, 1051-1055)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[k][e] = __fadd_rn(__fmul_rn(gg[e], __fmul_rn(v[k][e], scale)), bb[e]);
+            for (int e = 0; e < 4; ++e)
+                v[k][e] = EXACT ? add_rn(mul_rn(gg[e], mul_rn(v[k][e], scale)), bb[e])
+                                : __fadd_rn(__fmul_rn(gg[e], __fmul_rn(v[k][e], scale)), bb[e]);
         }
     }
 }
 
 // One wave per token row: x = LN(pos[i] + (type[0] + word[id])) (bert.cpp:963-984).
+template <bool EXACT>
 __global__ __launch_bounds__(256) void f32_embed_ln_kernel(DevTable word, DevTable type, DevTable pos,
                                                            const float *__restrict__ ln_w,
                                                            const float *__restrict__ ln_b,
@@ -90,7 +96,7 @@ __global__ __launch_bounds__(256) void f32_embed_ln_kernel(DevTable word, DevTab
             for (int e = 0; e < 4; ++e) v[k][e] = p[e] + (ty[e] + w[e]);
         }
     }
-    ln_row(v, d, lane, ln_w, ln_b);
+    ln_row<EXACT>(v, d, lane, ln_w, ln_b);
 #pragma unroll
     for (int k = 0; k < F32_MAXC; ++k) {
         const int c = 4 * lane + 256 * k;
@@ -99,6 +105,7 @@ __global__ __launch_bounds__(256) void f32_embed_ln_kernel(DevTable word, DevTab
 }
 
 // In-place LayerNorm of rows [0, rows) (bert.cpp:1048-1056, 1074-1082).
+template <bool EXACT>
 __global__ __launch_bounds__(256) void f32_ln_kernel(float *__restrict__ x, int rows, int d,
                                                      const float *__restrict__ g, const float *__restrict__ b)
 {
@@ -110,7 +117,7 @@ __global__ __launch_bounds__(256) void f32_ln_kernel(float *__restrict__ x, int 
         const int c = 4 * lane + 256 * k;
         if (c < d) v[k] = *(const f32x4 *)(x + (size_t)t * d + c);
     }
-    ln_row(v, d, lane, g, b);
+    ln_row<EXACT>(v, d, lane, g, b);
 #pragma unroll
     for (int k = 0; k < F32_MAXC; ++k) {
         const int c = 4 * lane + 256 * k;
@@ -119,14 +126,6 @@ __global__ __launch_bounds__(256) void f32_ln_kernel(float *__restrict__ x, int 
 }
 
 // ---------------------------------------------------------------- GEMM
-
-// The era's fp16 tables (GELU, exp), built on the host with libm at load
-// (model_file.cpp era_tables) and indexed by the f16 bit pattern of the input:
-// T(f16(x)), bit for bit the table ggml held.
-__device__ __forceinline__ float era_table(const uint16_t *__restrict__ tab, float v)
-{
-    return (float)as_h(tab[__builtin_bit_cast(uint16_t, (h16)v)]);
-}
 
 // Y[m][n] = epi(sum_k X[m][k] W[n][k]) on 64 x 32 tiles, 4 waves of 32 x 16
 // (2 v_mfma_f32_16x16x4_f32 tiles each), K in steps of 32 through LDS (rows
@@ -209,7 +208,18 @@ __global__ __launch_bounds__(256) void f32_gemm_kernel(const float *__restrict__
 // 1/sum; bert.cpp:1018-1025), then P V (bert.cpp:1027-1036).  16 lanes per
 // query row; K / V in 64-key tiles through LDS.  Padded keys do not exist here
 // (packed sentences); the reference's mask makes theirs contribute exactly 0.
-template <int DH>
+// ERA (the q8-activation chain): both dot products in ggml_vec_dot_f32's own order
+// (oracle dot_f32: eight lanes i & 7 of rounded multiply-adds, no FMA, a pairwise
+// horizontal sum), the keys of P V all in the lanes as in a batch padded to a
+// multiple of eight (padded keys add exact zeros) -- there every f32 rounding
+// difference is re-quantized by the next projection and amplified by the layers.
+__device__ __forceinline__ float era_lanes_sum(const float (&a)[8])
+{
+    return add_rn(add_rn(add_rn(a[0], a[1]), add_rn(a[2], a[3])),
+                     add_rn(add_rn(a[4], a[5]), add_rn(a[6], a[7])));
+}
+
+template <int DH, bool ERA>
 __global__ __launch_bounds__(256) void f32_attention_kernel(const float *__restrict__ qkv, const int32_t *__restrict__ cu,
                                                             int d, int s_stride, float scale, float *__restrict__ out,
                                                             const uint16_t *__restrict__ exp_tab)
@@ -238,8 +248,16 @@ __global__ __launch_bounds__(256) void f32_attention_kernel(const float *__restr
         for (int j = 0; j < 4; ++j) {
             const int kk = l16 + 16 * j;
             float a = 0.f;
+            if (ERA) {
+                float la[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                for (int e = 0; e < DH; e += 8)
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) la[u] = add_rn(la[u], mul_rn(kv[kk][e + u], qs[qi][e + u]));
+                a = era_lanes_sum(la);
+            } else {
 #pragma unroll 8
-            for (int e = 0; e < DH; ++e) a = fmaf(kv[kk][e], qs[qi][e], a);
+                for (int e = 0; e < DH; ++e) a = fmaf(kv[kk][e], qs[qi][e], a);
+            }
             if (k0 + kk < len) S[qi * s_stride + k0 + kk] = a * scale;
         }
     }
@@ -261,8 +279,13 @@ __global__ __launch_bounds__(256) void f32_attention_kernel(const float *__restr
     for (int k = l16; k < len; k += 16) row[k] *= inv;
     constexpr int NE = DH / 16;
     float o_acc[NE];
+    float o_la[ERA ? NE : 1][8];   // ERA: lane (key & 7) sums of each output
 #pragma unroll
     for (int j = 0; j < NE; ++j) o_acc[j] = 0.f;
+#pragma unroll
+    for (int j = 0; j < (ERA ? NE : 1); ++j)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) o_la[j][u] = 0.f;
     for (int k0 = 0; k0 < len; k0 += 64) {
         __syncthreads();   // row updates visible; previous V tile consumed
         for (int i = tid; i < 64 * DH; i += 256) {
@@ -271,11 +294,30 @@ __global__ __launch_bounds__(256) void f32_attention_kernel(const float *__restr
         }
         __syncthreads();
         const int kn = min(64, len - k0);
-        for (int kk = 0; kk < kn; ++kk) {
-            const float p = row[k0 + kk];
+        if (ERA) {
+            // (rows past kn of the tile are zero-filled and their p is not read)
+            for (int kk = 0; kk < kn; kk += 8)
 #pragma unroll
-            for (int j = 0; j < NE; ++j) o_acc[j] = fmaf(p, kv[kk][l16 + 16 * j], o_acc[j]);
+                for (int u = 0; u < 8; ++u) {
+                    const float p = kk + u < kn ? row[k0 + kk + u] : 0.f;
+#pragma unroll
+                    for (int j = 0; j < NE; ++j)
+                        o_la[j][u] = add_rn(o_la[j][u], mul_rn(kv[kk + u][l16 + 16 * j], p));
+                }
+        } else {
+            for (int kk = 0; kk < kn; ++kk) {
+                const float p = row[k0 + kk];
+#pragma unroll
+                for (int j = 0; j < NE; ++j) o_acc[j] = fmaf(p, kv[kk][l16 + 16 * j], o_acc[j]);
+            }
         }
+    }
+    if (ERA) {
+#pragma unroll
+        for (int j = 0; j < NE; ++j) o_acc[j] = era_lanes_sum(o_la[j]);
+        // every LDS read retired before the stores (the drain scripts/check_drain.py asks of
+        // each attention kernel; the compiler's own partial counts are right but not that form)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     if (q0 + qi < len)
 #pragma unroll
@@ -286,6 +328,7 @@ __global__ __launch_bounds__(256) void f32_attention_kernel(const float *__restr
 
 // out[b] = (sum_i x[i] * (1/len)) / ||.||  (bert.cpp:1087-1095), one workgroup
 // per sentence, a thread per column; the norm's sum of squares in f64.
+template <bool ERA>
 __global__ __launch_bounds__(256) void f32_pool_kernel(const float *__restrict__ x, const int32_t *__restrict__ cu,
                                                        int d, float *__restrict__ out)
 {
@@ -299,7 +342,15 @@ __global__ __launch_bounds__(256) void f32_pool_kernel(const float *__restrict__
     for (int j = 0; j < 4; ++j) {
         const int c = tid + 256 * j;
         float a = 0.f;
-        if (c < d) {
+        if (c < d && ERA) {
+            // ggml_vec_dot_f32's order over the tokens (lanes i & 7, as in a padded batch)
+            float la[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            for (int i = 0; i < len; i += 8)
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    if (i + u < len) la[u] = add_rn(la[u], mul_rn(x[(size_t)(start + i + u) * d + c], wt));
+            a = era_lanes_sum(la);
+        } else if (c < d) {
             // (unrolled: eight loads in flight; the fmaf chain keeps its token order)
 #pragma unroll 8
             for (int i = 0; i < len; ++i) a = fmaf(x[(size_t)(start + i) * d + c], wt, a);
@@ -322,14 +373,18 @@ __global__ __launch_bounds__(256) void f32_pool_kernel(const float *__restrict__
 
 void launch_f32_embed_ln(const DevTable &word, const DevTable &type, const DevTable &pos, const float *ln_w,
                          const float *ln_b, const int32_t *ids, const int32_t *cu, int32_t n_seqs, int32_t max_len,
-                         int32_t d, float *x, hipStream_t s)
+                         int32_t d, float *x, hipStream_t s, bool exact)
 {
-    f32_embed_ln_kernel<<<dim3((max_len + 3) / 4, n_seqs), 256, 0, s>>>(word, type, pos, ln_w, ln_b, ids, cu, d, x);
+    const dim3 g((max_len + 3) / 4, n_seqs);
+    if (exact) f32_embed_ln_kernel<true><<<g, 256, 0, s>>>(word, type, pos, ln_w, ln_b, ids, cu, d, x);
+    else f32_embed_ln_kernel<false><<<g, 256, 0, s>>>(word, type, pos, ln_w, ln_b, ids, cu, d, x);
 }
 
-void launch_f32_ln(float *x, int32_t rows, int32_t d, const float *g, const float *b, hipStream_t s)
+void launch_f32_ln(float *x, int32_t rows, int32_t d, const float *g, const float *b, hipStream_t s, bool exact)
 {
-    if (rows > 0) f32_ln_kernel<<<(rows + 3) / 4, 256, 0, s>>>(x, rows, d, g, b);
+    if (rows <= 0) return;
+    if (exact) f32_ln_kernel<true><<<(rows + 3) / 4, 256, 0, s>>>(x, rows, d, g, b);
+    else f32_ln_kernel<false><<<(rows + 3) / 4, 256, 0, s>>>(x, rows, d, g, b);
 }
 
 int launch_f32_gemm(const float *X, int32_t M, const float *W, int32_t N, int32_t K, const float *bias, int32_t epi,
@@ -363,7 +418,7 @@ static size_t device_lds_limit()
 }
 
 int launch_f32_attention(const float *qkv, const int32_t *cu, int32_t n_seqs, int32_t max_len, int32_t n_head,
-                         int32_t d, float *out, hipStream_t s, const uint16_t *exp_tab)
+                         int32_t d, float *out, hipStream_t s, const uint16_t *exp_tab, bool era_order)
 {
     const int dh = d / n_head;
     if (d % n_head || (dh != 32 && dh != 64) || max_len <= 0 || !exp_tab) return -1;
@@ -374,14 +429,21 @@ int launch_f32_attention(const float *qkv, const int32_t *cu, int32_t n_seqs, in
     if (lds > device_lds_limit()) return -1;
     const dim3 g((max_len + 15) / 16, n_head, n_seqs);
     const float scale = 1.0f / sqrtf((float)dh);
-    if (dh == 64) f32_attention_kernel<64><<<g, 256, lds, s>>>(qkv, cu, d, s_stride, scale, out, exp_tab);
-    else f32_attention_kernel<32><<<g, 256, lds, s>>>(qkv, cu, d, s_stride, scale, out, exp_tab);
+    if (era_order) {
+        if (dh == 64) f32_attention_kernel<64, true><<<g, 256, lds, s>>>(qkv, cu, d, s_stride, scale, out, exp_tab);
+        else f32_attention_kernel<32, true><<<g, 256, lds, s>>>(qkv, cu, d, s_stride, scale, out, exp_tab);
+        return 0;
+    }
+    if (dh == 64) f32_attention_kernel<64, false><<<g, 256, lds, s>>>(qkv, cu, d, s_stride, scale, out, exp_tab);
+    else f32_attention_kernel<32, false><<<g, 256, lds, s>>>(qkv, cu, d, s_stride, scale, out, exp_tab);
     return 0;
 }
 
-void launch_f32_pool(const float *x, const int32_t *cu, int32_t n_seqs, int32_t d, float *out, hipStream_t s)
+void launch_f32_pool(const float *x, const int32_t *cu, int32_t n_seqs, int32_t d, float *out, hipStream_t s,
+                     bool era_order)
 {
-    f32_pool_kernel<<<n_seqs, 256, 0, s>>>(x, cu, d, out);
+    if (era_order) f32_pool_kernel<true><<<n_seqs, 256, 0, s>>>(x, cu, d, out);
+    else f32_pool_kernel<false><<<n_seqs, 256, 0, s>>>(x, cu, d, out);
 }
 
 }  // namespace emb

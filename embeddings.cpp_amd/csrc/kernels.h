@@ -142,9 +142,12 @@ void launch_pool_l2(const uint16_t *z, const float2 *stats, const float *ln_w, c
 // x = LN(pos + (type + word)) with gamma/beta (bert.cpp:963-984).
 void launch_f32_embed_ln(const DevTable &word, const DevTable &type, const DevTable &pos, const float *ln_w,
                          const float *ln_b, const int32_t *ids, const int32_t *cu, int32_t n_seqs, int32_t max_len,
-                         int32_t d, float *x, hipStream_t s);
-// In-place LayerNorm of rows [0, rows) (ggml_norm, f64 sums, eps 1e-5).
-void launch_f32_ln(float *x, int32_t rows, int32_t d, const float *g, const float *b, hipStream_t s);
+                         int32_t d, float *x, hipStream_t s, bool exact = false);
+// In-place LayerNorm of rows [0, rows) (ggml_norm, f64 sums, eps 1e-5).  exact (both
+// LayerNorm launchers; the q8-activation chain): scale, gamma and beta as three
+// operations the compiler cannot contract, the reference's roundings bit for bit.
+void launch_f32_ln(float *x, int32_t rows, int32_t d, const float *g, const float *b, hipStream_t s,
+                   bool exact = false);
 // Y[M][N] = epi(X[M][K] W[N][K]^T): 0 bias + acc, 1 era GELU(bias + acc) through the
 // f16-indexed table gelu_tab [65536] (host_common.h era_tables, uploaded to the
 // device), 2 (bias + acc) + res.  M % 64 == 0, K % 32 == 0; returns -1 otherwise.
@@ -153,10 +156,32 @@ int launch_f32_gemm(const float *X, int32_t M, const float *W, int32_t N, int32_
 // Per (sentence, head) softmax(Q K^T / sqrt(dh)) V with the era's fp16-table exp
 // (exp_tab [65536] on the device), qkv f32 [T][3d] -> out f32 [T][d]; dh 32 or 64
 // and the 16 score rows of max_len keys within the device's LDS, else -1.
+// era_order (the q8-activation chain): Q K^T and P V summed in ggml_vec_dot_f32's own
+// order (eight lanes, rounded multiply and add, pairwise horizontal sum).
 int launch_f32_attention(const float *qkv, const int32_t *cu, int32_t n_seqs, int32_t max_len, int32_t n_head,
-                         int32_t d, float *out, hipStream_t s, const uint16_t *exp_tab);
-// out[b] = mean_{i<len} x[start + i] / ||.|| (bert.cpp:1087-1095).
-void launch_f32_pool(const float *x, const int32_t *cu, int32_t n_seqs, int32_t d, float *out, hipStream_t s);
+                         int32_t d, float *out, hipStream_t s, const uint16_t *exp_tab, bool era_order = false);
+// out[b] = mean_{i<len} x[start + i] / ||.|| (bert.cpp:1087-1095); era_order: the token
+// sum in ggml_vec_dot_f32's order.
+void launch_f32_pool(const float *x, const int32_t *cu, int32_t n_seqs, int32_t d, float *out, hipStream_t s,
+                     bool era_order = false);
+
+// ---- the q8-activation chain (q4_0 / q4_1 / q8_0 files in activation mode 1, q8act.hip):
+// the f32 chain's kernels around projections in the reference's block arithmetic ----
+// ggml's activation quantizer (era_quantize_row_q8_0 / _q8_1): X f32 [>= T][K] ->
+// q int8 [M][K], d f32 [K/32][M] (kind 0, q8_0: the f16-rounded scale as f32; kind 1,
+// q8_1: the f32 scale) and, kind 1, s f32 [K/32][M] = (float)(sum q) * d.  Rows
+// T <= row < M (tile padding) are quantized as zeros and never read.  M % 64 == 0,
+// K % 32 == 0; returns -1 otherwise.
+int launch_q8_quantize(const float *X, int32_t T, int32_t M, int32_t K, int32_t kind, int8_t *q, float *d, float *s,
+                       hipStream_t st);
+// Y f32 [M][N] = epi(sum over blocks b, ascending, of (wd xd) (float)sumi [+ wm xs]) with
+// the exact integer block dot sumi on the i8 matrix cores; W in the lane-order layout
+// above (q4_0 / q4_1 / q8_0), xq / xd / xs as launch_q8_quantize wrote them for the
+// same M (q8_1 for q4_1 weights, else q8_0).  epi as launch_f32_gemm.  Returns -1 for
+// an unsupported format or shape.
+int launch_q8_gemm(const DevWeight &W, const int8_t *xq, const float *xd, const float *xs, int32_t M,
+                   const float *bias, int32_t epi, const float *res, float *Y, hipStream_t s,
+                   const uint16_t *gelu_tab);
 
 // Diagnostics: *cnt += number of non-finite values in p[0..n) (f32, or f16 if f16).
 void launch_count_nonfinite(const void *p, size_t n, int f16, unsigned *cnt, hipStream_t s);

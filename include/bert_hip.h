@@ -17,6 +17,21 @@
 extern "C" {
 #endif
 
+/*
+ * bert_load_from_file with an activation mode.  0: f16 activations into the
+ * matrix cores, the default path (it tracks the f32-activation arithmetic).  1:
+ * the reference's own arithmetic for q4_0 / q4_1 / q8_0 files: every projection
+ * re-quantizes its input rows to q8_0 / q8_1 per 32-element block and takes
+ * integer block dots (ggml through bert.cpp:995-1016, 1040, 1059, 1066), for
+ * embeddings comparable with a CPU deployment of the reference; slower.  f16 and
+ * f32 files have no q8 arithmetic in the reference: mode 1 loads them in mode 0.
+ * Any other act_mode returns NULL.  The plain bert_load_from_file takes its mode
+ * from the environment, BERT_ACT=f16|q8 (unset: f16; anything else: NULL).
+ * bertx_activation_mode: the mode the context actually runs.
+ */
+BERT_API struct bert_ctx *bertx_load_from_file(const char *fname, int32_t act_mode);
+BERT_API int32_t bertx_activation_mode(struct bert_ctx *ctx);
+
 /* Number of GPUs the context drives, and the HIP ordinal of slot i. */
 BERT_API int32_t bertx_num_devices(struct bert_ctx *ctx);
 BERT_API int32_t bertx_device_ordinal(struct bert_ctx *ctx, int32_t slot);
@@ -149,6 +164,23 @@ BERT_API int32_t bertx_test_gemm_ran(void);
  */
 BERT_API int32_t bertx_test_gemm_f32(int32_t N, int32_t K, const float *w, const float *bias, int32_t M,
                                      const float *x, int32_t epi, const float *res, float *out);
+
+/*
+ * The q8-activation mode's two kernels (activation mode 1 above).
+ * bertx_test_quantize_act: ggml's activation quantizer on x f32 [M][K] (K % 32 ==
+ * 0): q int8 [M][K], d f32 [M][K/32] and, kind 1, s f32 [M][K/32].  kind 0 = q8_0
+ * (d = the f16-rounded scale as f32, the value the dot uses; s may be NULL), kind 1
+ * = q8_1 (d = the f32 scale, s = (float)(sum q) * d).
+ * bertx_test_gemm_q8: one projection as the forward runs it, the quantizer (q8_1
+ * for fmt 3, else q8_0) and then the block-integer GEMM: fmt 2, 3 or 8, w_rows as
+ * bertx_test_gemm, x f32 [M][K] (K % 64 == 0), out f32 [M][N] (N % 32 == 0) =
+ * epi(sum over blocks, ascending, of (wd xd) (float)sumi [+ wm xs]), epi as
+ * bertx_test_gemm_f32 (res f32 [M][N]).  Return 0 or -1.
+ */
+BERT_API int32_t bertx_test_quantize_act(int32_t kind, int32_t M, int32_t K, const float *x, int8_t *q, float *d,
+                                         float *s);
+BERT_API int32_t bertx_test_gemm_q8(int32_t fmt, int32_t N, int32_t K, const void *w_rows, const float *bias,
+                                    int32_t M, const float *x, int32_t epi, const float *res, float *out);
 
 /*
  * GEMM micro-benchmark on random operands (device 0): average device time of

@@ -8,9 +8,11 @@ the same weights by f16 activations.  At C4 dims (bge-large-en-v1.5, q4_1, 24
 layers, "sharp" weights) with the Q/K spread swept over 0.02 / 0.03 / 0.05, this
 records per sentence the cosines
 
-    hip_vs_q8   HIP (libbert)            vs oracle, reference arithmetic (q8 activations)
-    hip_vs_f32  HIP                      vs oracle with f32 activations (diagnostic switch)
-    q8_vs_f32   oracle (q8 activations)  vs oracle (f32 activations)
+    hip_vs_q8    HIP (libbert, default mode) vs oracle, reference arithmetic (q8 activations)
+    hip_vs_f32   HIP (default mode)          vs oracle with f32 activations (diagnostic switch)
+    q8_vs_f32    oracle (q8 activations)     vs oracle (f32 activations)
+    hipq8_vs_q8  HIP in the q8-activation mode (BertModel(act="q8"), csrc/q8act.hip) vs oracle
+    hipq8_vs_f32 HIP in the q8-activation mode vs oracle with f32 activations
 
 one JSON line per (qk_std, statistic) into --out.  Runs on the GPU box (libbert
 needs a gfx950 device); the oracle is the checker, timed nowhere.
@@ -60,11 +62,15 @@ def main():
             m = bertpy.BertModel(path)
             hip = m.forward_batch(ids)
             del m
+            m = bertpy.BertModel(path, act="q8")
+            hipq8 = m.forward_batch(ids)
+            del m
             o = oracle_lib.Oracle(path)
             q8 = np.concatenate([o.forward_batch([x], n_threads=a.threads) for x in ids])
             f32 = np.concatenate([o.forward_batch([x], n_threads=a.threads, activations="f32") for x in ids])
             del o
-            rows = {"hip_vs_q8": cos(hip, q8), "hip_vs_f32": cos(hip, f32), "q8_vs_f32": cos(q8, f32)}
+            rows = {"hip_vs_q8": cos(hip, q8), "hip_vs_f32": cos(hip, f32), "q8_vs_f32": cos(q8, f32),
+                    "hipq8_vs_q8": cos(hipq8, q8), "hipq8_vs_f32": cos(hipq8, f32)}
             for k, c in rows.items():
                 rec = {"arch": a.arch, "ftype": a.ftype, "qk_std": qk, "stat": k, "min_cos": float(np.min(c)),
                        "per_sentence": {str(L): round(float(v), 7) for L, v in zip(lens, c)}}
