@@ -104,6 +104,21 @@ def load_lib(path=None):
         L.bertx_test_gemm_q8.argtypes = [c_i32, c_i32, c_i32, vp, vp, c_i32, vp, c_i32, vp, vp]
     except AttributeError:
         pass
+    try:   # (pooling modes and per-token output: absent from older BERT_LIB builds)
+        L.bertx_set_pooling.restype = c_i32
+        L.bertx_set_pooling.argtypes = [vp, c_i32]
+        L.bertx_pooling.restype = c_i32
+        L.bertx_pooling.argtypes = [vp]
+        L.bertx_set_cls_pruning.restype = c_i32
+        L.bertx_set_cls_pruning.argtypes = [vp, c_i32]
+        L.bertx_forward_tokens.restype = c_i32
+        L.bertx_forward_tokens.argtypes = [vp, c_i32, ctypes.POINTER(c_i32p), c_i32p, ctypes.POINTER(c_f32p)]
+        L.bertx_forward_tokens_device.restype = c_i32
+        L.bertx_forward_tokens_device.argtypes = [vp, c_i32, vp, vp, c_i32, c_i32, c_i32, vp, vp]
+        L.bertx_test_attention_cls.restype = c_i32
+        L.bertx_test_attention_cls.argtypes = [vp, vp, c_i32, c_i32, c_i32, vp]
+    except AttributeError:
+        pass
     L.bertx_bench_gemm.restype = c_i32
     L.bertx_bench_gemm.argtypes = [c_i32] * 7 + [c_f32p]
     L.bertx_bench_attention.restype = c_i32
@@ -157,6 +172,43 @@ class BertModel:
     def activation_mode(self):
         """The activation mode the context runs: 0 = f16, 1 = the reference's q8."""
         return int(self.lib.bertx_activation_mode(self.ctx))
+
+    POOL_MODES = {"mean": 0, "cls": 1}
+
+    @property
+    def pooling(self):
+        """The pooling mode of the sentence embeddings: "mean" (default) or "cls"."""
+        v = int(self.lib.bertx_pooling(self.ctx))
+        return next(k for k, x in self.POOL_MODES.items() if x == v)
+
+    def set_pooling(self, mode):
+        """"mean": masked mean of the final rows; "cls": the first token's row; both L2-normalised."""
+        if mode not in self.POOL_MODES:
+            raise ValueError("pooling must be 'mean' or 'cls', not %r" % (mode,))
+        if self.lib.bertx_set_pooling(self.ctx, self.POOL_MODES[mode]) != 0:
+            raise RuntimeError("bertx_set_pooling failed")
+
+    def set_cls_pruning(self, on):
+        """Whether CLS pooling runs the last layer on the sentences' first rows only (default on)."""
+        self.lib.bertx_set_cls_pruning(self.ctx, 1 if on else 0)
+
+    def forward_tokens(self, ids_list):
+        """Per-token final hidden states (un-normalised): a list of [len][n_embd] f32 arrays."""
+        n = len(ids_list)
+        lens = np.fromiter((len(x) for x in ids_list), np.int32, n)
+        flat = (np.concatenate(ids_list) if n else np.zeros(0)).astype(np.int32, copy=False)
+        flat = np.ascontiguousarray(flat)
+        out = np.zeros((int(lens.sum()), self.n_embd), np.float32)
+        offs = np.zeros(n, np.uintp)
+        if n > 1:
+            np.cumsum(lens[:-1], out=offs[1:])
+        tp = (flat.ctypes.data + 4 * offs).astype(np.uintp)
+        op = (out.ctypes.data + out.strides[0] * offs).astype(np.uintp)
+        rc = self.lib.bertx_forward_tokens(self.ctx, n, tp.ctypes.data_as(ctypes.POINTER(c_i32p)), _as_i32p(lens),
+                                           op.ctypes.data_as(ctypes.POINTER(c_f32p)))
+        if rc != 0:
+            raise RuntimeError("bertx_forward_tokens failed (%d)" % rc)
+        return [out[int(o):int(o) + int(l)] for o, l in zip(offs, lens)]
 
     def encode(self, sentences, batch_size=16):
         input_is_string = isinstance(sentences, str)

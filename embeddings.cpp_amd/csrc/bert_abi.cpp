@@ -85,6 +85,7 @@ struct bert_ctx {
     std::vector<std::unique_ptr<Device>> devices;
     bool host_only = false;
     int act_mode = 0;   // the activation mode the context runs (bertx_activation_mode)
+    int pool = 0;       // BERTX_POOL_MEAN / BERTX_POOL_CLS (bertx_set_pooling), mirrored on every replica
     // routing state of run_forward: the cost of the work routed to each replica and
     // not yet finished, and the rotation that breaks ties between equal loads
     std::mutex route_mu;
@@ -449,8 +450,20 @@ static bert_ctx *load_context(const char *fname, int act_mode)
 
 static bert_ctx *load_guarded(const char *fname, int act_mode)
 {
+    // the initial pooling mode, BERT_POOL=mean|cls, read at every load (unset: mean)
+    const char *ep = std::getenv("BERT_POOL");
+    int pool = BERTX_POOL_MEAN;
+    if (ep && *ep && std::strcmp(ep, "mean") != 0) {
+        if (std::strcmp(ep, "cls") != 0) {
+            emb::errorf("bert_load_from_file: BERT_POOL='%s' is not a pooling mode (mean or cls)\n", ep);
+            return nullptr;
+        }
+        pool = BERTX_POOL_CLS;
+    }
     try {
-        return load_context(fname, act_mode);
+        bert_ctx *ctx = load_context(fname, act_mode);
+        if (ctx && pool != BERTX_POOL_MEAN) bertx_set_pooling(ctx, pool);
+        return ctx;
     } catch (const std::bad_alloc &) {
         emb::errorf("bert_load_from_file: out of host memory\n");
     } catch (const std::exception &ex) {
@@ -604,6 +617,98 @@ int32_t bertx_forward_device(struct bert_ctx *ctx, int32_t slot, const int32_t *
     std::lock_guard<std::mutex> lk(D.mutex());
     emb::DeviceGuard g(D.ordinal());
     return D.forward(d_ids, d_cu, n_seqs, max_len, total_tokens, d_out, stream ? (hipStream_t)stream : D.stream());
+}
+
+int32_t bertx_set_pooling(struct bert_ctx *ctx, int32_t pool)
+{
+    if (!ctx || (pool != BERTX_POOL_MEAN && pool != BERTX_POOL_CLS)) return -1;
+    // under each replica's mutex: no forward of that replica is being launched; the
+    // mode is part of a captured graph's key, so graphs of the other mode stay unreachable
+    for (auto &d : ctx->devices) {
+        std::lock_guard<std::mutex> lk(d->mutex());
+        d->set_pooling(pool);
+    }
+    ctx->pool = pool;
+    return 0;
+}
+
+int32_t bertx_pooling(struct bert_ctx *ctx) { return ctx ? ctx->pool : -1; }
+
+int32_t bertx_set_cls_pruning(struct bert_ctx *ctx, int32_t on)
+{
+    if (!ctx) return -1;
+    for (auto &d : ctx->devices) {
+        std::lock_guard<std::mutex> lk(d->mutex());
+        d->set_cls_pruning(on != 0);
+    }
+    return 0;
+}
+
+int32_t bertx_forward_tokens_device(struct bert_ctx *ctx, int32_t slot, const int32_t *d_ids, const int32_t *d_cu,
+                                    int32_t n_seqs, int32_t max_len, int32_t total_tokens, float *d_out, void *stream)
+{
+    if (slot < 0 || slot >= (int32_t)ctx->devices.size()) return -1;
+    if (max_len > ctx->hp.n_max_tokens || max_len <= 0) return -4;
+    Device &D = *ctx->devices[(size_t)slot];
+    std::lock_guard<std::mutex> lk(D.mutex());
+    emb::DeviceGuard g(D.ordinal());
+    return D.forward(d_ids, d_cu, n_seqs, max_len, total_tokens, d_out, stream ? (hipStream_t)stream : D.stream(), -1.0,
+                     true);
+}
+
+int32_t bertx_forward_tokens(struct bert_ctx *ctx, int32_t n, bert_vocab_id **batch_tokens, int32_t *n_tokens,
+                             float **out)
+{
+    if (!ctx || n < 0 || (n > 0 && (!batch_tokens || !n_tokens || !out))) return -1;
+    if (ctx->devices.empty()) {
+        emb::errorf("libbert: no HIP device in this context (BERT_HOST_ONLY); forward unavailable\n");
+        return -1;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (n_tokens[i] > ctx->hp.n_max_tokens) {
+            emb::errorf("Too many tokens, maximum is %d\n", ctx->hp.n_max_tokens);
+            return -4;
+        }
+        if (n_tokens[i] <= 0) return -1;
+    }
+    if (n == 0) return 0;
+    // the whole call on the least-loaded replica, in chunks the workspace holds
+    int dv = 0;
+    double cost = 0.0;
+    for (int i = 0; i < n; ++i) cost += sentence_cost(ctx->hp, n_tokens[i]);
+    {
+        std::lock_guard<std::mutex> lk(ctx->route_mu);
+        for (int i = 1; i < (int)ctx->devices.size(); ++i)
+            if (ctx->inflight[(size_t)i] < ctx->inflight[(size_t)dv]) dv = i;
+        ctx->inflight[(size_t)dv] += cost;
+    }
+    int rc = 0;
+    try {
+        Device &D = *ctx->devices[(size_t)dv];
+        std::lock_guard<std::mutex> lk(D.mutex());
+        std::vector<const int32_t *> tp;
+        std::vector<int32_t> lp;
+        std::vector<float *> op;
+        int i = 0;
+        while (i < n && rc == 0) {
+            tp.clear(); lp.clear(); op.clear();
+            int64_t tok = 0;
+            while (i < n && (tp.empty() || (tok + n_tokens[i] <= kChunkTokens && (int)tp.size() < kChunkSeqs))) {
+                tp.push_back(batch_tokens[i]); lp.push_back(n_tokens[i]); op.push_back(out[i]);
+                tok += n_tokens[i++];
+            }
+            rc = D.forward_host(tp.data(), lp.data(), (int)tp.size(), op.data(), true);
+        }
+    } catch (...) {
+        rc = -1;
+    }
+    {
+        std::lock_guard<std::mutex> lk(ctx->route_mu);
+        ctx->inflight[(size_t)dv] -= cost;
+        if (ctx->inflight[(size_t)dv] < 0.5) ctx->inflight[(size_t)dv] = 0.0;
+    }
+    if (rc != 0) emb::errorf("libbert: forward failed (%d)\n", rc);
+    return rc;
 }
 
 void bertx_set_profiling(struct bert_ctx *ctx, int32_t on)

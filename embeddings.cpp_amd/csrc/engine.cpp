@@ -424,6 +424,7 @@ Device::~Device()
     for (auto e : free_events_) (void)hipEventDestroy(e);
     if (arena_) (void)hipFree(arena_);
     if (ws_) (void)hipFree(ws_);
+    if (tok_out_) (void)hipFree(tok_out_);
     if (h_ids_) (void)hipHostFree(h_ids_);
     if (h_cu_) (void)hipHostFree(h_cu_);
     if (h_out_) (void)hipHostFree(h_out_);
@@ -521,6 +522,11 @@ bool Device::reserve(int64_t tokens, int64_t seqs, int max_len)
     const size_t o_xq = take(rq * kq), o_xd = take(rq * (kq / 32) * 4), o_xs = take(rq * (kq / 32) * 4);
     const size_t o_ids = take(rows * 4), o_cu = take((ns + 1) * 4), o_out = take(ns * d * 4);
     const size_t o_pool = take((size_t)np * d * 4);
+    // the pruned last layer of CLS pooling (f16 chain): one row per sentence, padded
+    // to whole GEMM tiles as the token rows are
+    const int64_t rows_c = ns + GEMM_BM + 256, rc16 = c32 ? 0 : rows_c;
+    const size_t o_stc = take(rc16 * 8), o_zc = take(rc16 * d * 2), o_partc = take(rc16 * (d / 32) * 8);
+    const size_t o_attc = take(rc16 * d * 2), o_ffnc = take(rc16 * f * 2);
     drop_graphs();   // captured graphs hold the old workspace pointers
     if (ws_) { (void)hipFree(ws_); ws_ = nullptr; }
     if (h_ids_) { (void)hipHostFree(h_ids_); h_ids_ = nullptr; }
@@ -537,6 +543,9 @@ bool Device::reserve(int64_t tokens, int64_t seqs, int max_len)
     qkv_ = (uint16_t *)(ws_ + o_qkv); att_ = (uint16_t *)(ws_ + o_att); ffn_ = (uint16_t *)(ws_ + o_ffn);
     d_ids_ = (int32_t *)(ws_ + o_ids); d_cu_ = (int32_t *)(ws_ + o_cu); d_out_ = (float *)(ws_ + o_out);
     pool_part_ = (float *)(ws_ + o_pool);
+    stc_ = (float2 *)(ws_ + o_stc); zc_ = (uint16_t *)(ws_ + o_zc); partc_ = (float2 *)(ws_ + o_partc);
+    attc_ = (uint16_t *)(ws_ + o_attc); ffnc_ = (uint16_t *)(ws_ + o_ffnc);
+    rows_c_ = rows_c;
     x32_ = (float *)(ws_ + o_x32); z32_ = (float *)(ws_ + o_z32); qkv32_ = (float *)(ws_ + o_qkv32);
     att32_ = (float *)(ws_ + o_att32); ffn32_ = (float *)(ws_ + o_ffn32);
     xq_ = (int8_t *)(ws_ + o_xq); xd_ = (float *)(ws_ + o_xd); xs_ = (float *)(ws_ + o_xs);
@@ -605,8 +614,9 @@ void Device::drop_graphs()
 }
 
 int Device::forward(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out,
-                    hipStream_t s, double len2_sum)
+                    hipStream_t s, double len2_sum, bool tokens)
 {
+    out_mode_ = tokens ? OUT_TOKENS : pool_ != 1 ? OUT_MEAN : (prune_ && !f32_ && !q8_) ? OUT_CLS_PRUNED : OUT_CLS;
     // attention work for the per-kernel stats: exact from the host's lengths when
     // known, else T max_len (exact for equal lengths, an upper bound otherwise)
     att_flop_ = 4.0 * hp_.n_embd * (len2_sum >= 0 ? len2_sum : (double)T * max_len);
@@ -628,7 +638,7 @@ int Device::forward_ordered(const int32_t *d_ids, const int32_t *d_cu, int n_seq
     static const bool graphs_env = [] { const char *e = std::getenv("BERT_GRAPHS"); return !(e && *e == '0'); }();
     if (profiling_ || check || !use_graphs_ || !graphs_env || s == nullptr)
         return launch_all(d_ids, d_cu, n_seqs, max_len, T, d_out, s, check);
-    const GraphKey key{d_ids, d_cu, d_out, s, n_seqs, max_len, T};
+    const GraphKey key{d_ids, d_cu, d_out, s, n_seqs, max_len, T, out_mode_};
     for (auto &g : graphs_)
         if (g.key == key) return hipGraphLaunch(g.exec, s) == hipSuccess ? 0 : -1;
     // a shape seen for the first time runs eagerly (one-off batches never pay
@@ -723,6 +733,56 @@ int Device::launch_all(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, in
         end(K_GEMM_QKV, s, ev, 2.0 * t * 3.0 * d * d);
         chk("gemm_qkv", l, qkv_, (size_t)T * 3 * d, 1);
 
+        if (out_mode_ == OUT_CLS_PRUNED && l + 1 == hp_.n_layer) {
+            // CLS pooling reads one row per sentence of this layer: attention of the
+            // sentences' first rows only (its launch gathers their residual rows into
+            // zc_ / stc_), then the rest of the layer on Mc compact rows, wired as
+            // the full layer below
+            const int Mc = gemm_rows(n_seqs);
+            const double tc = (double)n_seqs;
+            const bool fold_c = fold_env && gemm_fold_ok(L.up, Mc, G);
+            begin(K_ATTENTION, s, ev);
+            if (launch_attention_cls(qkv_, d_cu, n_seqs, hp_.n_head, d, Mc, attc_, z_, st_, zc_, stc_, s) != 0) return -1;
+            end(K_ATTENTION, s, ev, 4.0 * d * t);   // one query per sentence: 4 d len FLOP each
+            chk("attention_cls", l, attc_, (size_t)Mc * d, 1);
+            chk("gather_cls", l, zc_, (size_t)Mc * d, 1);
+
+            LnFold c1;
+            c1.res_stats = stc_; c1.res_g = gz; c1.res_b = bz;
+            c1.g_next = L.ln1_w; c1.part = partc_; c1.part_stride = (int32_t)rows_c_;
+            begin(K_GEMM_O, s, ev);
+            if (launch_gemm(L.o, attc_, Mc, L.b_o, EPI_BIAS_RES, zc_, zc_, s, c1) != 0) return -1;
+            end(K_GEMM_O, s, ev, 2.0 * tc * d * d);
+            chk("gemm_o_cls", l, zc_, (size_t)Mc * d, 1);
+            LnFold cu_in;
+            if (fold_c) {
+                cu_in.in_part = partc_; cu_in.in_part_stride = (int32_t)rows_c_; cu_in.in_G = G; cu_in.st_out = stc_;
+            } else {
+                begin(K_LN_STATS, s, ev);
+                if (launch_ln_stats(partc_, G, (int32_t)rows_c_, Mc, d, stc_, s) != 0) return -1;
+                end(K_LN_STATS, s, ev, (double)Mc * (G + 1) * 8.0);
+                cu_in.in_stats = stc_;
+            }
+            gz = L.ln1_w; bz = L.ln1_b;
+            cu_in.c1 = L.c1_up;
+            begin(K_GEMM_FFN_UP, s, ev);
+            if (launch_gemm(L.up, zc_, Mc, L.c2_up, EPI_BIAS_GELU_F16, nullptr, ffnc_, s, cu_in) != 0) return -1;
+            end(K_GEMM_FFN_UP, s, ev, 2.0 * tc * d * f);
+            chk("gemm_up_cls", l, ffnc_, (size_t)Mc * f, 1);
+            LnFold c2;
+            c2.res_stats = stc_; c2.res_g = gz; c2.res_b = bz;
+            c2.g_next = L.ln2_w; c2.part = partc_; c2.part_stride = (int32_t)rows_c_;
+            begin(K_GEMM_FFN_DOWN, s, ev);
+            if (launch_gemm(L.down, ffnc_, Mc, L.b_down, EPI_BIAS_RES, zc_, zc_, s, c2) != 0) return -1;
+            end(K_GEMM_FFN_DOWN, s, ev, 2.0 * tc * d * f);
+            chk("gemm_down_cls", l, zc_, (size_t)Mc * d, 1);
+            begin(K_LN_STATS, s, ev);
+            if (launch_ln_stats(partc_, G, (int32_t)rows_c_, Mc, d, stc_, s) != 0) return -1;
+            end(K_LN_STATS, s, ev, (double)Mc * (G + 1) * 8.0);
+            gz = L.ln2_w; bz = L.ln2_b;
+            break;
+        }
+
         begin(K_ATTENTION, s, ev);
         launch_attention(qkv_, d_cu, n_seqs, max_len, hp_.n_head, d, att_, s);
         end(K_ATTENTION, s, ev, att_flop);
@@ -770,14 +830,41 @@ int Device::launch_all(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, in
         gz = L.ln2_w; bz = L.ln2_b;
     }
     begin(K_POOL_L2, s, ev);
-    launch_pool_l2(z_, st_, gz, bz, d_cu, n_seqs, max_len, d, pool_part_, d_out, s);
-    end(K_POOL_L2, s, ev, t * d * 2.0 + t * 8.0 + (double)n_seqs * d * 4.0);
-    chk("pool_l2", -1, d_out, (size_t)n_seqs * d, 0);
+    if (out_mode_ == OUT_MEAN) {
+        launch_pool_l2(z_, st_, gz, bz, d_cu, n_seqs, max_len, d, pool_part_, d_out, s);
+        end(K_POOL_L2, s, ev, t * d * 2.0 + t * 8.0 + (double)n_seqs * d * 4.0);
+    } else if (out_mode_ == OUT_TOKENS) {
+        launch_tokens_f32(z_, st_, gz, bz, T, d, d_out, s);
+        end(K_POOL_L2, s, ev, t * d * 6.0 + t * 8.0);
+    } else {
+        // the sentences' first rows: of the compact last layer, or of the full one
+        if (out_mode_ == OUT_CLS_PRUNED) launch_cls_l2(zc_, stc_, gz, bz, nullptr, n_seqs, d, d_out, s);
+        else launch_cls_l2(z_, st_, gz, bz, d_cu, n_seqs, d, d_out, s);
+        end(K_POOL_L2, s, ev, (double)n_seqs * (d * 6.0 + 8.0));
+    }
+    chk("pool_l2", -1, d_out, (out_mode_ == OUT_TOKENS ? (size_t)T : (size_t)n_seqs) * d, 0);
     if (cnt) (void)hipFree(cnt);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         errorf("libbert: kernel launch failed: %s\n", hipGetErrorString(e));
         return -1;
+    }
+    return 0;
+}
+
+// The CLS / per-token output stage of the f32 and q8 chains: x32_ holds the final
+// LayerNorm output, so CLS is a gather + normalise and the token output a copy.
+int Device::launch_f32_out(const int32_t *d_cu, int n_seqs, int T, float *d_out, hipStream_t s)
+{
+    const int d = hp_.n_embd;
+    hipEvent_t ev;
+    begin(K_POOL_L2, s, ev);
+    if (out_mode_ == OUT_TOKENS) {
+        if (hipMemcpyAsync(d_out, x32_, sizeof(float) * (size_t)T * d, hipMemcpyDeviceToDevice, s) != hipSuccess) return -1;
+        end(K_POOL_L2, s, ev, (double)T * d * 8.0);
+    } else {
+        launch_f32_cls(x32_, d_cu, n_seqs, d, d_out, s);
+        end(K_POOL_L2, s, ev, (double)n_seqs * d * 8.0);
     }
     return 0;
 }
@@ -819,9 +906,13 @@ int Device::launch_all_f32(const int32_t *d_ids, const int32_t *d_cu, int n_seqs
         launch_f32_ln(x32_, M, d, L.ln2_w, L.ln2_b, s);
         end(K_LN_STATS, s, ev, (double)M * d * 8.0);
     }
-    begin(K_POOL_L2, s, ev);
-    launch_f32_pool(x32_, d_cu, n_seqs, d, d_out, s);
-    end(K_POOL_L2, s, ev, t * d * 4.0 + (double)n_seqs * d * 4.0);
+    if (out_mode_ != OUT_MEAN) {
+        if (launch_f32_out(d_cu, n_seqs, T, d_out, s) != 0) return -1;
+    } else {
+        begin(K_POOL_L2, s, ev);
+        launch_f32_pool(x32_, d_cu, n_seqs, d, d_out, s);
+        end(K_POOL_L2, s, ev, t * d * 4.0 + (double)n_seqs * d * 4.0);
+    }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         errorf("libbert: kernel launch failed: %s\n", hipGetErrorString(e));
@@ -874,9 +965,13 @@ int Device::launch_all_q8(const int32_t *d_ids, const int32_t *d_cu, int n_seqs,
         launch_f32_ln(x32_, M, d, L.ln2_w, L.ln2_b, s, true);
         end(K_LN_STATS, s, ev, (double)M * d * 8.0);
     }
-    begin(K_POOL_L2, s, ev);
-    launch_f32_pool(x32_, d_cu, n_seqs, d, d_out, s, true);
-    end(K_POOL_L2, s, ev, t * d * 4.0 + (double)n_seqs * d * 4.0);
+    if (out_mode_ != OUT_MEAN) {
+        if (launch_f32_out(d_cu, n_seqs, T, d_out, s) != 0) return -1;
+    } else {
+        begin(K_POOL_L2, s, ev);
+        launch_f32_pool(x32_, d_cu, n_seqs, d, d_out, s, true);
+        end(K_POOL_L2, s, ev, t * d * 4.0 + (double)n_seqs * d * 4.0);
+    }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         errorf("libbert: kernel launch failed: %s\n", hipGetErrorString(e));
@@ -885,7 +980,7 @@ int Device::launch_all_q8(const int32_t *d_ids, const int32_t *d_cu, int n_seqs,
     return 0;
 }
 
-int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int n, float *const *out)
+int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int n, float *const *out, bool tok_out)
 {
     if (!ok_) return -3;
     if (n <= 0) return 0;
@@ -908,9 +1003,29 @@ int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int 
     }
     HIP_RC(hipMemcpyAsync(d_ids_, h_ids_, sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, stream_));
     HIP_RC(hipMemcpyAsync(d_cu_, h_cu_, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice, stream_));
+    const size_t d = (size_t)hp_.n_embd;
+    if (tok_out) {
+        // per-token output: a device buffer of its own, grown on demand, and plain
+        // copies into the caller's buffers (not a hot path)
+        if (T > cap_tok_out_) {
+            HIP_RC(hipStreamSynchronize(stream_));
+            if (tok_out_) { (void)hipFree(tok_out_); tok_out_ = nullptr; }
+            cap_tok_out_ = 0;
+            drop_graphs();   // captured token forwards hold the old pointer
+            const int64_t cap = (int64_t)align_up((size_t)T, 4096);
+            HIP_RC(hipMalloc((void **)&tok_out_, sizeof(float) * d * (size_t)cap));
+            cap_tok_out_ = cap;
+        }
+        const int rc = forward(d_ids_, d_cu_, n, max_len, (int)T, tok_out_, stream_, len2, true);
+        if (rc != 0) return rc;
+        HIP_RC(hipStreamSynchronize(stream_));
+        for (int i = 0; i < n; ++i)
+            HIP_RC(hipMemcpy(out[i], tok_out_ + d * (size_t)h_cu_[i], sizeof(float) * d * (size_t)lens[i],
+                             hipMemcpyDeviceToHost));
+        return 0;
+    }
     const int rc = forward(d_ids_, d_cu_, n, max_len, (int)T, d_out_, stream_, len2);
     if (rc != 0) return rc;
-    const size_t d = (size_t)hp_.n_embd;
     HIP_RC(hipMemcpyAsync(h_out_, d_out_, sizeof(float) * d * (size_t)n, hipMemcpyDeviceToHost, stream_));
     HIP_RC(hipStreamSynchronize(stream_));
     for (int i = 0; i < n; ++i) std::memcpy(out[i], h_out_ + d * (size_t)i, sizeof(float) * d);
@@ -1339,5 +1454,39 @@ extern "C" int32_t bertx_test_attention(const uint16_t *qkv, const int32_t *cu, 
     HIP_RC(hipDeviceSynchronize());
     HIP_RC(hipMemcpy(out, dout, T * d * 2, hipMemcpyDeviceToHost));
     for (void *p : {(void *)dq, (void *)dcu, (void *)dout}) (void)hipFree(p);
+    return 0;
+}
+
+// The single-query attention of the pruned last layer (attention_cls.hip) on host
+// buffers: out f16 [n_seqs][d], row b = the attention output of token cu[b].
+extern "C" int32_t bertx_test_attention_cls(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head,
+                                            int32_t d, uint16_t *out)
+{
+    using namespace emb;
+    if (!qkv || !cu || !out || n_seqs <= 0 || n_head <= 0 || d % n_head || hip_device_count() == 0) return -1;
+    const int dh = d / n_head;
+    if (dh != 64 && dh != 32) return -1;
+    for (int i = 0; i < n_seqs; ++i)
+        if (cu[i + 1] < cu[i]) return -1;
+    const size_t T = (size_t)cu[n_seqs];
+    const int Mc = gemm_rows(n_seqs);
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const uint16_t *dq = (const uint16_t *)B.up(qkv, T * 3 * d * 2, 0);
+    const int32_t *dcu = (const int32_t *)B.up(cu, ((size_t)n_seqs + 1) * 4, 0);
+    uint16_t *dout = (uint16_t *)B.up(nullptr, 0, (size_t)Mc * d * 2);
+    if (B.bad) return -1;
+    // the output starts as NaN bits, so the zeros of the padding rows are the kernel's
+    HIP_RC(hipMemset(dout, 0xff, (size_t)Mc * d * 2));
+    if (launch_attention_cls(dq, dcu, n_seqs, n_head, d, Mc, dout, nullptr, nullptr, nullptr, nullptr, nullptr) != 0)
+        return -1;
+    HIP_RC(hipGetLastError());
+    HIP_RC(hipDeviceSynchronize());
+    std::vector<uint16_t> h((size_t)Mc * d);
+    HIP_RC(hipMemcpy(h.data(), dout, h.size() * 2, hipMemcpyDeviceToHost));
+    for (size_t i = (size_t)n_seqs * d; i < h.size(); ++i)
+        if (h[i] != 0) return -5;   // a padding row the kernel did not clear
+    std::memcpy(out, h.data(), (size_t)n_seqs * d * 2);
     return 0;
 }

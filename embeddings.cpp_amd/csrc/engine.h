@@ -144,12 +144,21 @@ public:
     // overlap in the workspace.
     // len2_sum: sum of the squared sentence lengths when the caller knows them
     // (attention FLOP of the per-kernel stats), else -1.
+    // tokens: d_out is float[total_tokens][n_embd] and receives every token's final
+    // LayerNorm output (un-normalised) instead of the pooled sentence embeddings.
     int forward(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int total_tokens, float *d_out,
-                hipStream_t s, double len2_sum = -1.0);
+                hipStream_t s, double len2_sum = -1.0, bool tokens = false);
 
     // Host-driven forward: packs tokens, H2D, forward, D2H, synchronous.
-    // tokens[i] has lens[i] ids; out[i] receives n_embd floats.
-    int forward_host(const int32_t *const *tokens, const int32_t *lens, int n, float *const *out);
+    // tokens[i] has lens[i] ids; out[i] receives n_embd floats, or with tok_out
+    // lens[i] x n_embd floats (the per-token output).
+    int forward_host(const int32_t *const *tokens, const int32_t *lens, int n, float *const *out, bool tok_out = false);
+
+    // Pooling of the sentence embeddings (bert_hip.h): BERTX_POOL_MEAN / BERTX_POOL_CLS,
+    // and whether CLS pooling runs the last layer on the sentences' first rows only
+    // (f16 chain).  Both are part of a captured graph's key.  Call under mutex().
+    void set_pooling(int pool) { pool_ = pool; }
+    void set_cls_pruning(bool on) { prune_ = on; }
 
     // profiling
     void set_profiling(bool on) { profiling_ = on; }
@@ -177,12 +186,15 @@ private:
         const void *ids, *cu, *out;
         hipStream_t s;
         int n_seqs, max_len, T;
+        int mode;   // OutMode: a graph of one pooling mode is never replayed for another
         bool operator==(const GraphKey &o) const
         {
             return ids == o.ids && cu == o.cu && out == o.out && s == o.s && n_seqs == o.n_seqs &&
-                   max_len == o.max_len && T == o.T;
+                   max_len == o.max_len && T == o.T && mode == o.mode;
         }
     };
+    // what the launch sequence ends in (and, for CLS, how its last layer runs)
+    enum OutMode : int { OUT_MEAN = 0, OUT_CLS, OUT_CLS_PRUNED, OUT_TOKENS };
     struct GraphEntry { GraphKey key; hipGraphExec_t exec; };
     int forward_ordered(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out,
                         hipStream_t s);
@@ -194,6 +206,7 @@ private:
                        hipStream_t s);
     int launch_all_q8(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out,
                       hipStream_t s);
+    int launch_f32_out(const int32_t *d_cu, int n_seqs, int T, float *d_out, hipStream_t s);
     void drop_graphs();
     void bind(const ModelImage &img);   // device pointers of the image's planes
     bool uploading_ = false;
@@ -235,6 +248,15 @@ private:
     int32_t *d_ids_ = nullptr, *d_cu_ = nullptr;
     float *d_out_ = nullptr;
     float *pool_part_ = nullptr;
+    // the pruned last layer of CLS pooling (f16 chain): compact rows, one per sentence
+    uint16_t *zc_ = nullptr, *attc_ = nullptr, *ffnc_ = nullptr;
+    float2 *stc_ = nullptr, *partc_ = nullptr;
+    int64_t rows_c_ = 0;            // compact workspace rows (partc_ stride)
+    float *tok_out_ = nullptr;      // per-token output staging of forward_host [cap_tok_out_][d], grown on demand
+    int64_t cap_tok_out_ = 0;
+    int pool_ = 0;                  // BERTX_POOL_MEAN / BERTX_POOL_CLS
+    bool prune_ = true;
+    int out_mode_ = OUT_MEAN;       // of the forward being launched
     int32_t *h_ids_ = nullptr, *h_cu_ = nullptr;   // pinned staging
     float *h_out_ = nullptr;
 

@@ -369,7 +369,40 @@ __global__ __launch_bounds__(256) void f32_pool_kernel(const float *__restrict__
     }
 }
 
+// [CLS] pooling: out[b] = x[cu[b]] / ||.||, the norm's sum of squares in f64 as the
+// mean pool above takes it; a thread per column.
+__global__ __launch_bounds__(256) void f32_cls_kernel(const float *__restrict__ x, const int32_t *__restrict__ cu,
+                                                      int d, float *__restrict__ out)
+{
+    __shared__ double red[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float *row = x + (size_t)cu[b] * d;
+    float e[4];
+    double ss = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = tid + 256 * j;
+        const float a = c < d ? row[c] : 0.f;
+        e[j] = a;
+        ss += (double)(a * a);
+    }
+    ss = wave_sum_d(ss);
+    if ((tid & 63) == 0) red[tid >> 6] = ss;
+    __syncthreads();
+    const float nrm = sqrtf((float)((red[0] + red[1]) + (red[2] + red[3])));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = tid + 256 * j;
+        if (c < d) out[(size_t)b * d + c] = e[j] / nrm;
+    }
+}
+
 }  // namespace
+
+void launch_f32_cls(const float *x, const int32_t *cu, int32_t n_seqs, int32_t d, float *out, hipStream_t s)
+{
+    f32_cls_kernel<<<n_seqs, 256, 0, s>>>(x, cu, d, out);
+}
 
 void launch_f32_embed_ln(const DevTable &word, const DevTable &type, const DevTable &pos, const float *ln_w,
                          const float *ln_b, const int32_t *ids, const int32_t *cu, int32_t n_seqs, int32_t max_len,

@@ -138,6 +138,24 @@ int32_t pool_chunks(int32_t max_len);
 void launch_pool_l2(const uint16_t *z, const float2 *stats, const float *ln_w, const float *ln_b, const int32_t *cu,
                     int32_t n_seqs, int32_t max_len, int32_t d, float *partial, float *out, hipStream_t s);
 
+// [CLS] pooling: out[b] = LN(y[row]) / ||.|| of the sentence's first token, from z
+// and the row statistics (the expression of the mean pool, per token).  row =
+// cu[b], or b when cu is null (the compact rows of the pruned last layer).
+void launch_cls_l2(const uint16_t *z, const float2 *stats, const float *ln_w, const float *ln_b, const int32_t *cu,
+                   int32_t n_seqs, int32_t d, float *out, hipStream_t s);
+// Per-token output: out[t] = LN(y[t]) as f32 for rows t < T (un-normalised).
+void launch_tokens_f32(const uint16_t *z, const float2 *stats, const float *ln_w, const float *ln_b, int32_t T,
+                       int32_t d, float *out, hipStream_t s);
+
+// The pruned last layer under [CLS] pooling (attention_cls.hip): per (sentence,
+// head) the one query of row cu[b] against the sentence's own keys, f32 scores,
+// softmax and P V, f16 into the compact attc [Mc][d] (row b).  With z (else null)
+// the same launch gathers the residual of the compact rows, zc[b] = z[cu[b]] and
+// stc[b] = st[cu[b]]; rows n_seqs <= row < Mc of attc, zc and stc are written as
+// zeros.  dh 32 or 64, any sentence length; returns -1 otherwise.
+int launch_attention_cls(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head, int32_t d, int32_t Mc,
+                         uint16_t *attc, const uint16_t *z, const float2 *st, uint16_t *zc, float2 *stc, hipStream_t s);
+
 // ---- the f32 chain (ftype 0 files, f32.hip): every activation f32 [rows][width] ----
 // x = LN(pos + (type + word)) with gamma/beta (bert.cpp:963-984).
 void launch_f32_embed_ln(const DevTable &word, const DevTable &type, const DevTable &pos, const float *ln_w,
@@ -164,6 +182,8 @@ int launch_f32_attention(const float *qkv, const int32_t *cu, int32_t n_seqs, in
 // sum in ggml_vec_dot_f32's order.
 void launch_f32_pool(const float *x, const int32_t *cu, int32_t n_seqs, int32_t d, float *out, hipStream_t s,
                      bool era_order = false);
+// [CLS] pooling of the f32 / q8 chains: out[b] = x[cu[b]] / ||.|| (x holds the final LayerNorm output).
+void launch_f32_cls(const float *x, const int32_t *cu, int32_t n_seqs, int32_t d, float *out, hipStream_t s);
 
 // ---- the q8-activation chain (q4_0 / q4_1 / q8_0 files in activation mode 1, q8act.hip):
 // the f32 chain's kernels around projections in the reference's block arithmetic ----

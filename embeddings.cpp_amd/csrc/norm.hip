@@ -7,6 +7,7 @@
 #include "kernels.h"
 #include "table_read.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
@@ -277,6 +278,60 @@ __global__ __launch_bounds__(256) void pool_one_kernel(const h16 *__restrict__ z
     pool_normalize<false>(cs, d, n_chunks, out + (size_t)b * d);
 }
 
+// [CLS] pooling: LN(y[row]) of the sentence's first token by the LN-fold expression
+// of pool_chunk_sum (r z - r mean gamma + beta), divided by its L2 norm as
+// pool_normalize divides.  row = cu[b], or b for compact rows (cu null); d <= 1024.
+__global__ __launch_bounds__(256) void cls_l2_kernel(const h16 *__restrict__ z, const float2 *__restrict__ stats,
+                                                     const float *__restrict__ lw, const float *__restrict__ lb,
+                                                     const int32_t *__restrict__ cu, int d, float *__restrict__ out)
+{
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int row = cu ? cu[b] : b;
+    const float2 st = stats[row];
+    const float r = st.y, t0 = -st.x * st.y;
+    float e[4];
+    float ss = 0.f;
+    int ne = 0;
+    for (int c = tid; c < d; c += 256) {
+        const float v = fmaf(r, (float)z[(size_t)row * d + c], fmaf(t0, lw[c], lb[c]));
+        e[ne++] = v;
+        ss += v * v;
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) red[w] = ss;
+    __syncthreads();
+    const float nrm = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
+    ne = 0;
+    for (int c = tid; c < d; c += 256) out[(size_t)b * d + c] = e[ne++] / nrm;
+}
+
+// per-token output: the same expression for every row, eight columns per thread
+__global__ __launch_bounds__(256) void tokens_f32_kernel(const h16 *__restrict__ z, const float2 *__restrict__ stats,
+                                                         const float *__restrict__ lw, const float *__restrict__ lb,
+                                                         int T, int d, float *__restrict__ out)
+{
+    const int G = d / 8;
+    const size_t n = (size_t)T * G;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const size_t t = i / G;
+        const int c = 8 * (int)(i % G);
+        const h16x8 y = *(const h16x8 *)(z + t * d + c);
+        const float2 st = stats[t];
+        const float r = st.y, t0 = -st.x * st.y;
+        const f32x4 w0 = *(const f32x4 *)(lw + c), w1 = *(const f32x4 *)(lw + c + 4);
+        const f32x4 b0 = *(const f32x4 *)(lb + c), b1 = *(const f32x4 *)(lb + c + 4);
+        f32x4 o0, o1;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            o0[e] = fmaf(r, (float)y[e], fmaf(t0, w0[e], b0[e]));
+            o1[e] = fmaf(r, (float)y[4 + e], fmaf(t0, w1[e], b1[e]));
+        }
+        *(f32x4 *)(out + t * d + c) = o0;
+        *(f32x4 *)(out + t * d + c + 4) = o1;
+    }
+}
+
 // diagnostics (BERT_CHECK_FINITE): count non-finite values of a buffer
 __global__ void count_nonfinite_kernel(const void *p, size_t n, int f16, unsigned *cnt)
 {
@@ -348,6 +403,20 @@ void launch_pool_l2(const uint16_t *z, const float2 *stats, const float *ln_w, c
     }
     pool_partial_kernel<<<dim3(nc, n_seqs), 256, 0, s>>>((const h16 *)z, stats, ln_w, ln_b, cu, d, nc, partial);
     pool_final_kernel<<<n_seqs, 256, 0, s>>>(partial, d, nc, out);
+}
+
+void launch_cls_l2(const uint16_t *z, const float2 *stats, const float *ln_w, const float *ln_b, const int32_t *cu,
+                   int32_t n_seqs, int32_t d, float *out, hipStream_t s)
+{
+    cls_l2_kernel<<<n_seqs, 256, 0, s>>>((const h16 *)z, stats, ln_w, ln_b, cu, d, out);
+}
+
+void launch_tokens_f32(const uint16_t *z, const float2 *stats, const float *ln_w, const float *ln_b, int32_t T,
+                       int32_t d, float *out, hipStream_t s)
+{
+    const size_t n = (size_t)T * (d / 8);
+    const int nb = (int)std::min<size_t>((n + 255) / 256, 4096);
+    tokens_f32_kernel<<<nb, 256, 0, s>>>((const h16 *)z, stats, ln_w, ln_b, T, d, out);
 }
 
 }  // namespace emb

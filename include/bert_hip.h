@@ -51,6 +51,42 @@ BERT_API int32_t bertx_forward_device(struct bert_ctx *ctx, int32_t slot,
                                       int32_t n_seqs, int32_t max_len, int32_t total_tokens,
                                       float *d_out, void *stream);
 
+/*
+ * Pooling of the sentence embeddings, a per-context runtime setting that every
+ * entry producing them follows (bert_encode, bert_encode_batch, bert_forward,
+ * bert_forward_batch, bert_forward_fake_batch, bertx_forward_device) on every
+ * replica.  MEAN (the default; bert.cpp:1087-1095): masked mean of the final
+ * LayerNorm rows, divided by its L2 norm.  CLS: the final LayerNorm row of the
+ * sentence's first token, divided by its L2 norm (how the BGE family is trained and
+ * published).  Output sizes never change.  bertx_set_pooling returns 0, or -1 for
+ * an unknown mode (nothing changes).  bert_load_from_file and bertx_load_from_file
+ * take the initial mode from the environment, BERT_POOL=mean|cls (unset: mean;
+ * anything else: NULL).  Tokenizer-only contexts accept and report the mode.
+ *
+ * bertx_set_cls_pruning (default 1): under CLS pooling the f16-activation chain
+ * runs the last layer's attention, O-proj and FFN on the sentences' first rows only
+ * (one row per sentence is ever read); 0 runs the full layer (A/B and tests).  The
+ * f32 and q8-activation chains always run the full layer.  Returns 0.
+ */
+enum { BERTX_POOL_MEAN = 0, BERTX_POOL_CLS = 1 };
+BERT_API int32_t bertx_set_pooling(struct bert_ctx *ctx, int32_t pool);
+BERT_API int32_t bertx_pooling(struct bert_ctx *ctx);
+BERT_API int32_t bertx_set_cls_pruning(struct bert_ctx *ctx, int32_t on);
+
+/*
+ * Per-token output: the final LayerNorm row of every token, un-normalised f32,
+ * whatever the pooling mode.  Host form: out[i] receives float[n_tokens[i]][n_embd];
+ * the refusals of bert_forward_batch (an input longer than n_max_tokens, a
+ * tokenizer-only context: a message, outputs untouched) with a negative return;
+ * the whole call runs on the least-loaded replica.  Device form: as
+ * bertx_forward_device with d_out float[total_tokens][n_embd], rows packed as d_ids.
+ */
+BERT_API int32_t bertx_forward_tokens(struct bert_ctx *ctx, int32_t n, bert_vocab_id **batch_tokens,
+                                      int32_t *n_tokens, float **out);
+BERT_API int32_t bertx_forward_tokens_device(struct bert_ctx *ctx, int32_t slot, const int32_t *d_ids,
+                                             const int32_t *d_cu, int32_t n_seqs, int32_t max_len,
+                                             int32_t total_tokens, float *d_out, void *stream);
+
 /* Make sure the workspace of `slot` can hold total_tokens (so a timed region
  * never allocates).  Returns 0 or a negative error. */
 BERT_API int32_t bertx_reserve(struct bert_ctx *ctx, int32_t slot, int32_t total_tokens, int32_t n_seqs);
@@ -212,6 +248,16 @@ BERT_API int32_t bertx_bench_attention(int32_t n_seqs, int32_t len, int32_t n_he
  */
 BERT_API int32_t bertx_test_attention(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head,
                                       int32_t d, int32_t variant, uint16_t *out);
+
+/*
+ * Parity hook of the pruned last layer's attention (CLS pooling; host buffers,
+ * device 0): qkv and cu as bertx_test_attention, out f16 [n_seqs][d], row b = the
+ * attention output of the sentence's first token (row cu[b]) over the sentence's
+ * own keys.  dh 32 or 64, any sentence length.  -5: the kernel left a padding row
+ * of its compact output unwritten.
+ */
+BERT_API int32_t bertx_test_attention_cls(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head,
+                                          int32_t d, uint16_t *out);
 
 /*
  * The tokenization stage of bert_encode_batch on its own (bert.cpp:1402-1406 runs
