@@ -200,13 +200,29 @@ private:
                         hipStream_t s);
     void order_after_last(hipStream_t s);   // stream s waits for the last forward (any stream)
     void mark_done(hipStream_t s);          // records the completion event of a forward on s
+    // The launch schedules (forward.cpp): launch_all runs the replica's chain through
+    // a Launcher (timed launches, the optional finite check, the closing error report).
+    struct Launcher;
+    // The rows a layer tail of the f16 chain runs on: all the packed tokens, or the
+    // compact rows (one per sentence) of the pruned last layer under CLS pooling.
+    struct RowSet {
+        int M;                      // GEMM rows (whole tiles)
+        double flop_rows;           // rows that count as work
+        size_t valid;               // rows the finite check reads
+        uint16_t *z;
+        float2 *st, *part;
+        int32_t part_stride;
+        uint16_t *att, *ffn;
+        bool fold;                  // the statistics fold applies (gemm_fold_ok on these rows)
+        bool last;                  // the last layer: its statistics feed the output stage
+        const char *tag;            // suffix of the kernel names in the finite check
+        LnFold input(bool fold_in, int G, const float *c1) const;
+    };
     int launch_all(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out,
                    hipStream_t s, bool check);
-    int launch_all_f32(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out,
-                       hipStream_t s);
-    int launch_all_q8(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out,
-                      hipStream_t s);
-    int launch_f32_out(const int32_t *d_cu, int n_seqs, int T, float *d_out, hipStream_t s);
+    int chain_f16(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out);
+    int layer_tail(Launcher &run, const DevLayer &L, int l, const RowSet &r, const float *&gz, const float *&bz);
+    int chain_32(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out);
     void drop_graphs();
     void bind(const ModelImage &img);   // device pointers of the image's planes
     bool uploading_ = false;

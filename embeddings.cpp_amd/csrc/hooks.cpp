@@ -1,0 +1,464 @@
+// Per-kernel parity hooks and micro-benchmarks (bert_hip.h bertx_test_* /
+// bertx_bench_*): one launch on device 0 over host buffers.  Test infrastructure
+// inside the library; the forward never calls these.
+#include "bert_hip.h"
+#include "engine.h"
+#include "hip_check.h"
+#include "repack.h"
+
+#include <algorithm>
+#include <cstring>
+
+namespace emb {
+namespace {
+
+// Device buffers of one hook call, freed together.
+struct HookBufs {
+    std::vector<void *> p;
+    bool bad = false;
+    void *up(const void *h, size_t bytes, size_t alloc)
+    {
+        void *d = nullptr;
+        alloc = std::max<size_t>(std::max(alloc, bytes), 16);
+        if (hipMalloc(&d, alloc) != hipSuccess) { bad = true; return nullptr; }
+        p.push_back(d);
+        if (hipMemset(d, 0, alloc) != hipSuccess) bad = true;
+        if (h && bytes && hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) bad = true;
+        return d;
+    }
+    ~HookBufs() { for (void *d : p) (void)hipFree(d); }
+};
+
+// The two events of a device-timed bench loop.
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    hipError_t create()
+    {
+        const hipError_t e = hipEventCreate(&a);
+        return e != hipSuccess ? e : hipEventCreate(&b);
+    }
+    ~EventPair()
+    {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+
+// A per-thread test switch (g_gemm_cfg, g_att_variant) set for a scope.
+struct ScopedSet {
+    int &var;
+    const int prev;
+    ScopedSet(int &v, int value) : var(v), prev(v) { var = value; }
+    ~ScopedSet() { var = prev; }
+    ScopedSet(const ScopedSet &) = delete;
+    ScopedSet &operator=(const ScopedSet &) = delete;
+};
+
+// The weight of a hook call in the device layout; t keeps the file-format rows.
+bool hook_weight(int32_t fmt, int32_t N, int32_t K, const void *w_rows, HostTensor &t, DevWeight &W, HookBufs &B)
+{
+    t.fmt = fmt; t.ne0 = K; t.ne1 = N;
+    t.bytes.assign((const uint8_t *)w_rows, (const uint8_t *)w_rows + fmt_row_bytes(fmt, K) * (size_t)N);
+    Piece q, dd, mm;
+    repack_linear({&t}, fmt, q, dd, mm, W.N, W.K);
+    W.fmt = fmt == FMT_F32 ? FMT_F16 : fmt;
+    W.kx = fmt == FMT_F32 ? W.K / 2 : 0;
+    W.qs = B.up(q.bytes.data(), q.bytes.size(), 0);
+    W.d = (const uint16_t *)(dd.bytes.empty() ? nullptr : B.up(dd.bytes.data(), dd.bytes.size(), 0));
+    W.m = (const uint16_t *)(mm.bytes.empty() ? nullptr : B.up(mm.bytes.data(), mm.bytes.size(), 0));
+    return !B.bad;
+}
+
+HostTensor vec_tensor(const float *v, int n)
+{
+    HostTensor t;
+    t.fmt = FMT_F32; t.ne0 = n; t.ne1 = 1;
+    t.bytes.assign((const uint8_t *)v, (const uint8_t *)(v + n));
+    return t;
+}
+
+}  // namespace
+}  // namespace emb
+
+extern "C" int32_t bertx_test_gemm(int32_t fmt, int32_t N, int32_t K, const void *w_rows, const float *bias,
+                                   int32_t M, const uint16_t *x, int32_t epi, const void *res, void *out,
+                                   int32_t cfg)
+{
+    return bertx_test_gemm_ln(fmt, N, K, w_rows, bias, M, x, nullptr, nullptr, nullptr, epi, (const uint16_t *)res,
+                              nullptr, nullptr, nullptr, nullptr, (uint16_t *)out, nullptr, cfg);
+}
+
+extern "C" int32_t bertx_test_gemm_fold(int32_t fmt, int32_t N, int32_t K, const void *w_rows, const float *bias,
+                                        int32_t M, const uint16_t *x, const float *part, const float *in_g,
+                                        const float *in_b, int32_t epi, uint16_t *out, float *st_out,
+                                        float *st_kernel, int32_t cfg)
+{
+    using namespace emb;
+    if (!fmt_valid(fmt) || K % 64 || N % 32 || M <= 0 || (epi != 0 && epi != 1) || !part || !in_g || !in_b ||
+        hip_device_count() == 0)
+        return -1;
+    const int Mp = (int)align_up((size_t)M, GEMM_BM), G = K / 32;   // (X columns: K for every format)
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    HostTensor t;
+    DevWeight W;
+    if (!hook_weight(fmt, N, K, w_rows, t, W, B)) return -1;
+    ScopedSet tile(g_gemm_cfg, cfg);
+    if (!gemm_fold_ok(W, Mp, G)) return -2;
+    const HostTensor hb = vec_tensor(bias, N), hg = vec_tensor(in_g, K), hbt = vec_tensor(in_b, K);
+    Piece c1, c2;
+    fold_ln({&t}, {&hb}, hg, hbt, c1, c2, fmt == FMT_F32);
+    LnFold ln;
+    // partials [G][M] on the host -> [G][Mp] on the device (stride Mp)
+    std::vector<float> hp((size_t)G * Mp * 2, 0.f);
+    for (int g = 0; g < G; ++g) std::memcpy(&hp[(size_t)g * Mp * 2], part + (size_t)g * M * 2, (size_t)M * 8);
+    ln.in_part = (const float2 *)B.up(hp.data(), hp.size() * 4, 0);
+    ln.in_part_stride = Mp;
+    ln.in_G = G;
+    ln.st_out = (float2 *)B.up(nullptr, 0, (size_t)Mp * 8);
+    ln.c1 = (const float *)B.up(c1.bytes.data(), c1.bytes.size(), 0);
+    const float *dbias = (const float *)B.up(c2.bytes.data(), c2.bytes.size(), 0);
+    void *dx = B.up(x, (size_t)M * K * 2, (size_t)Mp * K * 2);
+    void *dout = B.up(nullptr, 0, (size_t)Mp * N * 2);
+    if (B.bad) return -1;
+    const int rc = launch_gemm(W, (const uint16_t *)dx, Mp, dbias, epi, nullptr, dout, nullptr, ln);
+    if (rc != 0) return rc;
+    HIP_RC(hipGetLastError());
+    HIP_RC(hipDeviceSynchronize());
+    HIP_RC(hipMemcpy(out, dout, (size_t)M * N * 2, hipMemcpyDeviceToHost));
+    if (st_out) HIP_RC(hipMemcpy(st_out, ln.st_out, (size_t)M * 8, hipMemcpyDeviceToHost));
+    if (st_kernel) {
+        // the same partials through the statistics kernel (the launch form)
+        float2 *dk = (float2 *)B.up(nullptr, 0, (size_t)Mp * 8);
+        if (B.bad || launch_ln_stats(ln.in_part, G, Mp, Mp, 32 * G, dk, nullptr) != 0) return -1;
+        HIP_RC(hipDeviceSynchronize());
+        HIP_RC(hipMemcpy(st_kernel, dk, (size_t)M * 8, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+extern "C" int32_t bertx_test_gemm_ln(int32_t fmt, int32_t N, int32_t K, const void *w_rows, const float *bias,
+                                      int32_t M, const uint16_t *x, const float *in_stats, const float *in_g,
+                                      const float *in_b, int32_t epi, const uint16_t *res, const float *res_stats,
+                                      const float *res_g, const float *res_b, const float *g_next, uint16_t *out,
+                                      float *st_out, int32_t cfg)
+{
+    using namespace emb;
+    if (!fmt_valid(fmt) || K % 64 || N % 32 || M <= 0 || epi < 0 || epi > 2 || hip_device_count() == 0) return -1;
+    if (g_next && N > 1024) return -1;   // the statistics kernel combines at most 32 partials per row
+    if ((in_stats && (!in_g || !in_b || epi == EPI_BIAS_RES)) || (epi == EPI_BIAS_RES && !res) ||
+        (res_stats && (!res_g || !res_b)) || (g_next && epi != EPI_BIAS_RES))
+        return -1;
+    const int Mp = (int)align_up((size_t)M, GEMM_BM);
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    HostTensor t;
+    DevWeight W;
+    if (!hook_weight(fmt, N, K, w_rows, t, W, B)) return -1;
+    LnFold ln;
+    const float *dbias = (const float *)B.up(bias, (size_t)N * 4, 0);
+    if (in_stats) {
+        // the LN fold of the input: c1 = W gamma, c2 = bias + W beta
+        const HostTensor hb = vec_tensor(bias, N), hg = vec_tensor(in_g, K), hbt = vec_tensor(in_b, K);
+        Piece c1, c2;
+        fold_ln({&t}, {&hb}, hg, hbt, c1, c2, fmt == FMT_F32);
+        ln.in_stats = (const float2 *)B.up(in_stats, (size_t)M * 8, (size_t)Mp * 8);
+        ln.c1 = (const float *)B.up(c1.bytes.data(), c1.bytes.size(), 0);
+        dbias = (const float *)B.up(c2.bytes.data(), c2.bytes.size(), 0);
+    }
+    void *dx = B.up(x, (size_t)M * K * 2, (size_t)Mp * K * 2);
+    void *dout = B.up(nullptr, 0, (size_t)Mp * N * 2);
+    float2 *dst = nullptr;
+    if (epi == EPI_BIAS_RES) {
+        B.up(nullptr, 0, 0);
+        void *dr = B.up(res, (size_t)M * N * 2, (size_t)Mp * N * 2);
+        dout = dr;   // in place, as the forward runs it
+        if (res_stats) {
+            ln.res_stats = (const float2 *)B.up(res_stats, (size_t)M * 8, (size_t)Mp * 8);
+            ln.res_g = (const float *)B.up(res_g, (size_t)N * 4, 0);
+            ln.res_b = (const float *)B.up(res_b, (size_t)N * 4, 0);
+        }
+        if (g_next) {
+            ln.g_next = (const float *)B.up(g_next, (size_t)N * 4, 0);
+            ln.part = (float2 *)B.up(nullptr, 0, (size_t)Mp * (N / 32) * 8);
+            ln.part_stride = Mp;
+            dst = (float2 *)B.up(nullptr, 0, (size_t)Mp * 8);
+        }
+    }
+    if (B.bad) return -1;
+    ScopedSet tile(g_gemm_cfg, cfg);
+    const int rc = launch_gemm(W, (const uint16_t *)dx, Mp, dbias, epi, dout, dout, nullptr, ln);
+    if (rc != 0) return rc;
+    if (dst && launch_ln_stats(ln.part, N / 32, Mp, Mp, N, dst, nullptr) != 0) return -1;
+    HIP_RC(hipGetLastError());
+    HIP_RC(hipDeviceSynchronize());
+    HIP_RC(hipMemcpy(out, dout, (size_t)M * N * 2, hipMemcpyDeviceToHost));
+    if (dst && st_out) HIP_RC(hipMemcpy(st_out, dst, (size_t)M * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int32_t bertx_test_gemm_ran(void) { return emb::g_gemm_ran; }
+
+// f32 chain GEMM (f32.hip) on host buffers: w f32 [N][K], x f32 [M][K], res/out f32 [M][N]
+extern "C" int32_t bertx_test_gemm_f32(int32_t N, int32_t K, const float *w, const float *bias, int32_t M,
+                                       const float *x, int32_t epi, const float *res, float *out)
+{
+    using namespace emb;
+    if (N <= 0 || K % 32 || K <= 0 || M <= 0 || epi < 0 || epi > 2 || (epi == 2 && !res) || hip_device_count() == 0)
+        return -1;
+    const int Mp = (int)align_up((size_t)M, 64);
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const float *dw = (const float *)B.up(w, (size_t)N * K * 4, 0);
+    const float *db = (const float *)B.up(bias, (size_t)N * 4, 0);
+    const float *dx = (const float *)B.up(x, (size_t)M * K * 4, (size_t)Mp * K * 4);
+    const float *dr = epi == 2 ? (const float *)B.up(res, (size_t)M * N * 4, (size_t)Mp * N * 4) : nullptr;
+    float *dout = (float *)B.up(nullptr, 0, (size_t)Mp * N * 4);
+    std::vector<uint16_t> tg, te;
+    era_tables(tg, te);
+    const uint16_t *dg = (const uint16_t *)B.up(tg.data(), tg.size() * 2, 0);
+    if (B.bad) return -1;
+    if (launch_f32_gemm(dx, Mp, dw, N, K, db, epi, dr, dout, nullptr, dg) != 0) return -1;
+    HIP_RC(hipGetLastError());
+    HIP_RC(hipDeviceSynchronize());
+    HIP_RC(hipMemcpy(out, dout, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// q8-activation chain (q8act.hip): the activation quantizer on host buffers; the
+// device's block-major scale planes [K/32][Mp] come back as [M][K/32]
+extern "C" int32_t bertx_test_quantize_act(int32_t kind, int32_t M, int32_t K, const float *x, int8_t *q, float *d,
+                                           float *s)
+{
+    using namespace emb;
+    if ((kind != 0 && kind != 1) || M <= 0 || K <= 0 || K % 32 || !x || !q || !d || (kind == 1 && !s) ||
+        hip_device_count() == 0)
+        return -1;
+    const int Mp = (int)align_up((size_t)M, 64), nb = K / 32;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const float *dx = (const float *)B.up(x, (size_t)M * K * 4, 0);
+    int8_t *dq = (int8_t *)B.up(nullptr, 0, (size_t)Mp * K);
+    float *dd = (float *)B.up(nullptr, 0, (size_t)Mp * nb * 4), *ds = (float *)B.up(nullptr, 0, (size_t)Mp * nb * 4);
+    if (B.bad) return -1;
+    if (launch_q8_quantize(dx, M, Mp, K, kind, dq, dd, ds, nullptr) != 0) return -1;
+    HIP_RC(hipGetLastError());
+    HIP_RC(hipDeviceSynchronize());
+    HIP_RC(hipMemcpy(q, dq, (size_t)M * K, hipMemcpyDeviceToHost));
+    std::vector<float> pl((size_t)Mp * nb);
+    for (int pass = 0; pass < (kind == 1 ? 2 : 1); ++pass) {
+        HIP_RC(hipMemcpy(pl.data(), pass ? ds : dd, pl.size() * 4, hipMemcpyDeviceToHost));
+        float *o = pass ? s : d;
+        for (int r = 0; r < M; ++r)
+            for (int b = 0; b < nb; ++b) o[(size_t)r * nb + b] = pl[(size_t)b * Mp + r];
+    }
+    return 0;
+}
+
+// q8-activation chain: one projection as the forward runs it (quantize, then the
+// block-integer GEMM): x f32 [M][K], res / out f32 [M][N]
+extern "C" int32_t bertx_test_gemm_q8(int32_t fmt, int32_t N, int32_t K, const void *w_rows, const float *bias,
+                                      int32_t M, const float *x, int32_t epi, const float *res, float *out)
+{
+    using namespace emb;
+    if ((fmt != FMT_Q4_0 && fmt != FMT_Q4_1 && fmt != FMT_Q8_0) || K <= 0 || K % 64 || N <= 0 || N % 32 || M <= 0 ||
+        epi < 0 || epi > 2 || (epi == 2 && !res) || !w_rows || !bias || !x || !out || hip_device_count() == 0)
+        return -1;
+    const int Mp = gemm_rows(M), nb = K / 32;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    HostTensor t;
+    DevWeight W;
+    if (!hook_weight(fmt, N, K, w_rows, t, W, B)) return -1;
+    const float *db = (const float *)B.up(bias, (size_t)N * 4, 0);
+    const float *dx = (const float *)B.up(x, (size_t)M * K * 4, 0);
+    const float *dr = epi == 2 ? (const float *)B.up(res, (size_t)M * N * 4, (size_t)Mp * N * 4) : nullptr;
+    float *dout = (float *)B.up(nullptr, 0, (size_t)Mp * N * 4);
+    int8_t *dq = (int8_t *)B.up(nullptr, 0, (size_t)Mp * K);
+    float *dd = (float *)B.up(nullptr, 0, (size_t)Mp * nb * 4), *ds = (float *)B.up(nullptr, 0, (size_t)Mp * nb * 4);
+    std::vector<uint16_t> tg, te;
+    era_tables(tg, te);
+    const uint16_t *dg = (const uint16_t *)B.up(tg.data(), tg.size() * 2, 0);
+    if (B.bad) return -1;
+    if (launch_q8_quantize(dx, M, Mp, K, fmt == FMT_Q4_1 ? 1 : 0, dq, dd, ds, nullptr) != 0) return -1;
+    if (launch_q8_gemm(W, dq, dd, ds, Mp, db, epi, dr, dout, nullptr, dg) != 0) return -1;
+    HIP_RC(hipGetLastError());
+    HIP_RC(hipDeviceSynchronize());
+    HIP_RC(hipMemcpy(out, dout, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// GEMM micro-benchmark (bert_hip.h): device-timed launches on random operands,
+// in the forward's own forms (LN fold on the input of epi 0/1; residual with
+// its LN, the next gamma and the partial statistics for epi 2)
+// ---------------------------------------------------------------------------
+extern "C" int32_t bertx_bench_gemm(int32_t fmt, int32_t N, int32_t K, int32_t M, int32_t epi, int32_t cfg,
+                                    int32_t iters, float *avg_us)
+{
+    using namespace emb;
+    if (!fmt_valid(fmt) || K % 64 || N % 32 || M <= 0 || iters <= 0 || epi < 0 || epi > 2 ||
+        hip_device_count() == 0)
+        return -1;
+    const int Mp = (int)align_up((size_t)M, GEMM_BM);
+    uint32_t st = 12345u;
+    auto rnd = [&]() { st = st * 1664525u + 1013904223u; return (st >> 8) / 16777216.0f; };
+    // random weights in the file format, quantized by the native quantizer's rows
+    std::vector<float> wrow((size_t)K);
+    std::vector<uint8_t> rows(fmt_row_bytes(fmt, K) * (size_t)N);
+    for (int n = 0; n < N; ++n) {
+        for (auto &v : wrow) v = (rnd() - 0.5f) * 0.1f;
+        quantize_row(fmt, wrow.data(), rows.data() + fmt_row_bytes(fmt, K) * (size_t)n, K);
+    }
+    std::vector<uint16_t> hx((size_t)Mp * K);
+    for (auto &v : hx) v = f32_to_f16(rnd() - 0.5f);
+    std::vector<float> hb((size_t)N), hg((size_t)std::max(N, K)), hbt((size_t)std::max(N, K)), hs((size_t)Mp * 2);
+    for (auto &v : hb) v = (rnd() - 0.5f) * 0.1f;
+    for (auto &v : hg) v = 1.0f + (rnd() - 0.5f) * 0.2f;
+    for (auto &v : hbt) v = (rnd() - 0.5f) * 0.1f;
+    for (size_t i = 0; i < hs.size(); i += 2) { hs[i] = 0.01f; hs[i + 1] = 1.0f + rnd() * 0.1f; }
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    HostTensor t;
+    DevWeight W;
+    if (!hook_weight(fmt, N, K, rows.data(), t, W, B)) return -1;
+    LnFold ln;
+    const float *dbias = (const float *)B.up(hb.data(), hb.size() * 4, 0);
+    void *dx = B.up(hx.data(), hx.size() * 2, 0);
+    void *dout = B.up(nullptr, 0, (size_t)Mp * N * 2);
+    const bool plain = cfg & 0x100;   // A/B: the same GEMM without the LN fold
+    cfg &= 0xff;
+    if (plain) {
+    } else if (epi == EPI_BIAS_RES) {
+        ln.res_stats = (const float2 *)B.up(hs.data(), hs.size() * 4, 0);
+        ln.res_g = (const float *)B.up(hg.data(), (size_t)N * 4, 0);
+        ln.res_b = (const float *)B.up(hbt.data(), (size_t)N * 4, 0);
+        ln.g_next = ln.res_g;
+        ln.part = (float2 *)B.up(nullptr, 0, (size_t)Mp * (N / 32) * 8);
+        ln.part_stride = Mp;
+    } else {
+        ln.in_stats = (const float2 *)B.up(hs.data(), hs.size() * 4, 0);
+        ln.c1 = (const float *)B.up(hg.data(), (size_t)N * 4, 0);
+    }
+    if (B.bad) return -1;
+    ScopedSet tile(g_gemm_cfg, cfg);
+    int lrc = 0;
+    auto launch = [&]() { lrc |= launch_gemm(W, (const uint16_t *)dx, Mp, dbias, epi, dout, dout, nullptr, ln); };
+    for (int i = 0; i < 3; ++i) launch();
+    if (lrc != 0) return -1;
+    EventPair ev;
+    HIP_RC(ev.create());
+    HIP_RC(hipEventRecord(ev.a, nullptr));
+    for (int i = 0; i < iters; ++i) launch();
+    HIP_RC(hipEventRecord(ev.b, nullptr));
+    HIP_RC(hipEventSynchronize(ev.b));
+    float ms = 0.f;
+    HIP_RC(hipEventElapsedTime(&ms, ev.a, ev.b));
+    *avg_us = ms * 1000.0f / (float)iters;
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---------------------------------------------------------------------------
+// attention micro-benchmark (bert_hip.h): n_seqs sentences of `len` tokens,
+// random Q/K/V, device-timed launches of variant `variant`
+// ---------------------------------------------------------------------------
+extern "C" int32_t bertx_bench_attention(int32_t n_seqs, int32_t len, int32_t n_head, int32_t dh, int32_t variant,
+                                         int32_t iters, float *avg_us)
+{
+    using namespace emb;
+    if (n_seqs <= 0 || len <= 0 || iters <= 0 || hip_device_count() == 0) return -1;
+    const int d = n_head * dh;
+    const size_t T = (size_t)n_seqs * len, rows = T + 256;
+    std::vector<uint16_t> hq(rows * 3 * d);
+    uint32_t st = 777u;
+    for (auto &v : hq) { st = st * 1664525u + 1013904223u; v = f32_to_f16(((st >> 8) / 16777216.0f - 0.5f) * 2.0f); }
+    std::vector<int32_t> hcu((size_t)n_seqs + 1);
+    for (int i = 0; i <= n_seqs; ++i) hcu[(size_t)i] = i * len;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const uint16_t *dq = (const uint16_t *)B.up(hq.data(), hq.size() * 2, 0);
+    const int32_t *dcu = (const int32_t *)B.up(hcu.data(), hcu.size() * 4, 0);
+    uint16_t *dout = (uint16_t *)B.up(nullptr, 0, rows * d * 2);
+    if (B.bad) return -1;
+    ScopedSet var(g_att_variant, variant);
+    for (int i = 0; i < 3; ++i) launch_attention(dq, dcu, n_seqs, len, n_head, d, dout, nullptr);
+    EventPair ev;
+    HIP_RC(ev.create());
+    HIP_RC(hipEventRecord(ev.a, nullptr));
+    for (int i = 0; i < iters; ++i) launch_attention(dq, dcu, n_seqs, len, n_head, d, dout, nullptr);
+    HIP_RC(hipEventRecord(ev.b, nullptr));
+    HIP_RC(hipEventSynchronize(ev.b));
+    float ms = 0.f;
+    HIP_RC(hipEventElapsedTime(&ms, ev.a, ev.b));
+    *avg_us = ms * 1000.f / (float)iters;
+    return 0;
+}
+
+extern "C" int32_t bertx_test_attention(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head,
+                                        int32_t d, int32_t variant, uint16_t *out)
+{
+    using namespace emb;
+    if (n_seqs <= 0 || n_head <= 0 || d % n_head || hip_device_count() == 0) return -1;
+    const int dh = d / n_head;
+    if (dh != 64 && dh != 32) return -1;
+    int max_len = 0;
+    for (int i = 0; i < n_seqs; ++i) {
+        if (cu[i + 1] < cu[i]) return -1;
+        max_len = std::max(max_len, cu[i + 1] - cu[i]);
+    }
+    const size_t T = (size_t)cu[n_seqs];
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const uint16_t *dq = (const uint16_t *)B.up(qkv, T * 3 * d * 2, (T + 64) * 3 * d * 2);
+    const int32_t *dcu = (const int32_t *)B.up(cu, ((size_t)n_seqs + 1) * 4, 0);
+    uint16_t *dout = (uint16_t *)B.up(nullptr, 0, (T + 64) * d * 2);
+    if (B.bad) return -1;
+    ScopedSet var(g_att_variant, variant);
+    // variant -1: the streaming kernel, reached by claiming a length past the LDS form
+    launch_attention(dq, dcu, n_seqs, variant == -1 ? ATT_LDS_MAX + 1 : max_len, n_head, d, dout, nullptr);
+    HIP_RC(hipDeviceSynchronize());
+    HIP_RC(hipMemcpy(out, dout, T * d * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The single-query attention of the pruned last layer (attention_cls.hip) on host
+// buffers: out f16 [n_seqs][d], row b = the attention output of token cu[b].
+extern "C" int32_t bertx_test_attention_cls(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head,
+                                            int32_t d, uint16_t *out)
+{
+    using namespace emb;
+    if (!qkv || !cu || !out || n_seqs <= 0 || n_head <= 0 || d % n_head || hip_device_count() == 0) return -1;
+    const int dh = d / n_head;
+    if (dh != 64 && dh != 32) return -1;
+    for (int i = 0; i < n_seqs; ++i)
+        if (cu[i + 1] < cu[i]) return -1;
+    const size_t T = (size_t)cu[n_seqs];
+    const int Mc = gemm_rows(n_seqs);
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const uint16_t *dq = (const uint16_t *)B.up(qkv, T * 3 * d * 2, 0);
+    const int32_t *dcu = (const int32_t *)B.up(cu, ((size_t)n_seqs + 1) * 4, 0);
+    uint16_t *dout = (uint16_t *)B.up(nullptr, 0, (size_t)Mc * d * 2);
+    if (B.bad) return -1;
+    // the output starts as NaN bits, so the zeros of the padding rows are the kernel's
+    HIP_RC(hipMemset(dout, 0xff, (size_t)Mc * d * 2));
+    if (launch_attention_cls(dq, dcu, n_seqs, n_head, d, Mc, dout, nullptr, nullptr, nullptr, nullptr, nullptr) != 0)
+        return -1;
+    HIP_RC(hipGetLastError());
+    HIP_RC(hipDeviceSynchronize());
+    std::vector<uint16_t> h((size_t)Mc * d);
+    HIP_RC(hipMemcpy(h.data(), dout, h.size() * 2, hipMemcpyDeviceToHost));
+    for (size_t i = (size_t)n_seqs * d; i < h.size(); ++i)
+        if (h[i] != 0) return -5;   // a padding row the kernel did not clear
+    std::memcpy(out, h.data(), (size_t)n_seqs * d * 2);
+    return 0;
+}

@@ -1,6 +1,6 @@
 // Device-side data layouts and kernel launchers (HIP, gfx950).
 //
-// HBM layout of one model replica (built by engine.cpp at load):
+// HBM layout of one model replica (built by repack.cpp and engine.cpp build_model_image at load):
 //   linear weights [N][K] ("lane order", gemm.hip): per K-step (64 k = quant
 //            blocks 2ks, 2ks+1) and 32-feature group, 64 lane records; lane
 //            l = 16g + f holds the four 16x16x32 A fragments u = 2a + s
@@ -42,7 +42,7 @@ struct DevWeight {
     int32_t fmt = 0;   // FMT_F16, FMT_Q4_0, FMT_Q4_1, FMT_Q8_0
     int32_t N = 0, K = 0;
     int32_t kx = 0;    // 0: X has K columns; else X has kx = K/2 columns, read twice
-                       // (f32 files: [hi | lo] f16 weight rows, engine.cpp)
+                       // (f32 files: [hi | lo] f16 weight rows, repack.cpp repack_linear_f32)
     const void *qs = nullptr;       // values / nibbles / int8, lane order
     const uint16_t *d = nullptr;    // f16 scales
     const uint16_t *m = nullptr;    // f16 mins (q4_1)

@@ -117,6 +117,109 @@ def test_loader_quantizer_under_sanitizers(harness, tmp_path, lib, tiny):
     assert r.returncode == 5 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr
 
 
+BLOCK_BYTES = {0: 128, 1: 64, 2: 18, 3: 20, 8: 34}   # per 32 elements, by file format (ggml type id)
+
+
+def _file_rows(fmt, rows, N, K):
+    """File-format rows [N][K] -> (codes [N][K], d [N][K/32] f16 bits, m likewise or None,
+    w [N][K] f32 as dequantized): codes are f16 bits (f16), nibbles (q4_0 / q4_1: element
+    e < 16 the low nibble of byte e, else the high nibble of byte e - 16) or int8 (q8_0)."""
+    b = np.frombuffer(rows, np.uint8).reshape(N, K // 32, BLOCK_BYTES[fmt])
+    if fmt == 1:
+        codes = b.reshape(N, -1).view(np.uint16)
+        return codes, None, None, codes.view(np.float16).astype(np.float32)
+    d = np.ascontiguousarray(b[:, :, 0:2]).view(np.uint16)[:, :, 0]
+    df = d.view(np.float16).astype(np.float32)[:, :, None]
+    if fmt == 8:
+        q = np.ascontiguousarray(b[:, :, 2:]).view(np.int8)
+        return q.reshape(N, K), d, None, (q.astype(np.float32) * df).reshape(N, K)
+    nib = b[:, :, (4 if fmt == 3 else 2):]
+    q = np.concatenate([nib & 15, nib >> 4], axis=2)
+    if fmt == 2:
+        return q.reshape(N, K), d, None, ((q.astype(np.float32) - 8) * df).reshape(N, K)
+    m = np.ascontiguousarray(b[:, :, 2:4]).view(np.uint16)[:, :, 0]
+    mf = m.view(np.float16).astype(np.float32)[:, :, None]
+    return q.reshape(N, K), d, m, (q.astype(np.float32) * df + mf).reshape(N, K)
+
+
+def _lane_order(fmt, codes, d, m):
+    """The lane-order layout as the top of kernels.h describes it: per K-step ks (64 k:
+    blocks 2ks, 2ks + 1) and 32-feature group grp, 64 lane records; lane 16g + f holds the
+    fragments u = 2a + s = feature 32grp + 16a + f, block 2ks + s, elements 8g .. 8g + 7."""
+    N, K = codes.shape
+    x = codes.reshape(N // 32, 2, 16, K // 64, 2, 4, 8)          # grp a f ks s g i
+    x = x.transpose(3, 0, 5, 2, 1, 4, 6).reshape(K // 64, N // 32, 64, 4, 8)   # ks grp lane u i
+    if fmt == 1:
+        qs = x.astype("<u2").tobytes()                           # 64 B per lane
+    elif fmt == 8:                                               # 8 B per u: e0 e2 e1 e3 per 4-group, ^ 0x80
+        y = x.reshape(x.shape[:-1] + (2, 4))[..., [0, 2, 1, 3]]
+        qs = (y.astype(np.int8).view(np.uint8) ^ 0x80).tobytes()
+    else:                                                        # one word per u: element i at bit 4(i/2) + 16(i%2)
+        sh = np.array([4 * (i // 2) + 16 * (i % 2) for i in range(8)], np.uint32)
+        qs = np.bitwise_or.reduce(x.astype(np.uint32) << sh, axis=-1).astype("<u4").tobytes()
+
+    def plane(p):                                                # f16 [ks][grp][f][u]
+        if p is None:
+            return b""
+        y = p.reshape(N // 32, 2, 16, K // 64, 2).transpose(3, 0, 2, 1, 4)
+        return np.ascontiguousarray(y).astype("<u2").tobytes()
+    return qs, plane(d), plane(m)
+
+
+def test_repack_under_sanitizers(harness, tmp_path):
+    """The weight layout code (repack.cpp) under ASan + UBSan over the tiny64 files in all
+    five formats (every table, every layer's linear weights and LN folds), and the dump of
+    one weight against restatements that share no code with it.  tiny64 (n_embd 64) has
+    one K-step, so the harness dumps its synthetic [64][128] weight: two 32-feature groups,
+    two K-steps, two parts.  The qs / d / m planes are compared byte for byte with
+    _lane_order.  c1 / c2 are compared for exact f32 equality: the restatement adds the
+    float64 products in the loop's own left-to-right order (np.cumsum) and makes the same
+    double -> float casts, so not even the last bit is free (a pairwise np.dot would need
+    a 1-ulp allowance for sums that land next to a rounding boundary)."""
+    exe = os.path.join(harness, "host_harness")
+    files = {ft: os.path.join(GOLDEN, "tiny64", f"ggml-model-{ft}.bin") for ft in ("f32", "f16")}
+    for name, it in (("q4_0", 2), ("q4_1", 3), ("q8_0", 8)):
+        files[name] = str(tmp_path / f"{name}.bin")
+        run(exe, "quant", files["f16"], files[name], it)
+    for name, path in files.items():
+        dump = tmp_path / f"{name}.repack"
+        fmt, N, K = map(int, run(exe, "repack", path, dump).split())
+        data = open(dump, "rb").read()
+        hdr = np.frombuffer(data, "<i4", 8)
+        assert (hdr[0], hdr[1]) == (fmt, N) and N >= 64 and hdr[2] >= 128, hdr
+        Kf = int(hdr[2])                                         # K of the file rows (f32 files: K = 2 Kf)
+        o = 32
+
+        def take(n):
+            nonlocal o
+            o += n
+            return data[o - n:o]
+        rows = take(N * (Kf // 32) * BLOCK_BYTES[fmt])
+        gamma, beta, bias = (np.frombuffer(take(4 * n), "<f4").astype(np.float64) for n in (Kf, Kf, N))
+        qs, dpl, mpl, c1, c2 = (take(int(n)) for n in hdr[3:8])
+        assert o == len(data)
+        if fmt == 0:
+            # f32 files: rows [hi | lo] of f16 pairs along a doubled K, hi = f16(w), lo = f16(w - hi)
+            w = np.frombuffer(rows, "<f4").reshape(N, Kf)
+            hi = w.astype(np.float16)
+            lo = (w - hi.astype(np.float32)).astype(np.float16)
+            assert K == 2 * Kf
+            want = _lane_order(1, np.concatenate([hi, lo], axis=1).view(np.uint16), None, None)
+            wq = w.astype(np.float64)                            # the fold takes the f32 value itself
+        else:
+            assert K == Kf
+            codes, d, m, w = _file_rows(fmt, rows, N, Kf)
+            want = _lane_order(fmt, codes, d, m)
+            wq = w.astype(np.float16).astype(np.float64)         # rounded once to f16, as the GEMM multiplies it
+        assert (qs, dpl, mpl) == want, name
+        assert len(dpl) == (0 if fmt in (0, 1) else N * (Kf // 32) * 2) and (len(mpl) > 0) == (fmt == 3)
+        s1 = np.cumsum(wq * gamma, axis=1)[:, -1].astype(np.float32)
+        s2 = np.cumsum(wq * beta, axis=1)[:, -1].astype(np.float32)
+        s2 = (s2.astype(np.float64) + bias).astype(np.float32)
+        assert np.array_equal(np.frombuffer(c1, "<f4"), s1), name
+        assert np.array_equal(np.frombuffer(c2, "<f4"), s2), name
+
+
 def test_converter_under_sanitizers(harness, tmp_path):
     ref32 = os.path.join(GOLDEN, "tiny32", "ggml-model-f32.bin")
     hp, vocab, tens = _parse_model_file(ref32)

@@ -91,7 +91,7 @@ def test_batch_composition_invariance(quant_models):
 
 
 def test_stats_fold_forward_bitwise(quant_models, tmp_path):
-    """The small-batch statistics fold (engine.cpp: QKV / FFN-up combine their input's
+    """The small-batch statistics fold (forward.cpp chain_f16: QKV / FFN-up combine their input's
     LN statistics from the residual GEMM's partials; 2 n_layer - 1 fewer ln_stats
     launches) gives the bits of the launch form end to end.  The switch
     is a process-wide static (BERT_STATS_FOLD), so each form runs in its own
@@ -260,7 +260,7 @@ def test_bge_base_q4_0_full_size(tmp_path):
                                          ("bge-large-en-v1.5", "q4_1")])
 def test_graph_replay_bitwise(tmp_path, arch, ftype):
     """A batch runs eagerly on first use, is captured into a HIP graph on its second
-    and replayed on its third (engine.cpp forward_ordered): all three give the same
+    and replayed on its third (forward.cpp forward_ordered): all three give the same
     bits on ragged lengths whose packed rows end mid-tile (tile padding rows carry
     stale values from earlier forwards, which valid rows never read)."""
     hp = bertpy.ARCHS[arch]
@@ -599,3 +599,73 @@ def test_load_free_cycles_multi_replica(quant_models, monkeypatch):
         assert m.lib.bertx_num_devices(m.ctx) == 4
         assert np.array_equal(m.forward_batch(ids), want)
         del m
+
+
+def _gemm_rows(T):
+    """kernels.h gemm_rows: packed rows padded to whole GEMM tiles."""
+    a = 256 if T >= 4096 else 64
+    return (T + a - 1) // a * a
+
+
+SCHEDULE_CASES = [("q4_0", None, "mean"), ("q4_0", None, "cls_pruned"), ("q4_0", None, "cls"), ("q4_0", None, "tokens"),
+                  ("f32", None, "mean"), ("f32", None, "cls"), ("q4_0", "q8", "mean"), ("q4_0", "q8", "tokens")]
+
+
+@pytest.mark.parametrize("fmt,act,out", SCHEDULE_CASES, ids=["-".join(str(x) for x in c) for c in SCHEDULE_CASES])
+def test_launch_schedule_per_class(quant_models, fmt, act, out):
+    """The shape of the launch schedule (forward.cpp), not its numbers: with profiling on
+    (every launch between two events, no graph) one forward of ragged lengths
+    [5, 17, 32, 60] gives, per kernel class, the launch count and the work figure
+    (FLOP or bytes) of bertx_kernel_stats.  Expected, per chain:
+      f16 chain: embed, per layer QKV / attention / O-proj / FFN-up / FFN-down, and the
+        ln_stats launches the statistics fold leaves (small batches: only the last one,
+        for the output stage; BERT_STATS_FOLD=0: two per layer), then one output launch.
+        Pruned CLS: the last layer's attention is one query per sentence (4 d len FLOP)
+        and its tail runs on gemm_rows(n_seqs) compact rows (FLOP of n_seqs rows).
+      f32 and q8 chains: the same classes with a LayerNorm launch (class ln_stats) after
+        each residual GEMM; the q8 chain's quantize launches are timed inside their
+        projection's class, so the counts are those of the f32 chain."""
+    m = bertpy.BertModel(quant_models[("tiny64", fmt)], act=act)
+    _, _, d, f, _, L, _ = m.hparams()
+    lens = [5, 17, 32, 60]
+    ids = ragged_ids(690, lens)
+    T, n = sum(lens), len(lens)
+    M, Mc, G = _gemm_rows(T), _gemm_rows(n), d // 32
+    att = 4.0 * d * sum(x * x for x in lens)
+    if out.startswith("cls"):
+        m.set_pooling("cls")
+        m.set_cls_pruning(out == "cls_pruned")
+    m.lib.bertx_set_profiling(m.ctx, 1)
+    m.lib.bertx_reset_stats(m.ctx)
+    if out == "tokens":
+        m.forward_tokens(ids)
+    else:
+        m.forward_batch(ids)
+    got = {s["name"]: (s["launches"], s["work"]) for s in m.kernel_stats()}
+    m.lib.bertx_set_profiling(m.ctx, 0)
+    want = {"gemm_qkv": (L, L * 2.0 * T * 3 * d * d), "attention": (L, L * att),
+            "gemm_attn_out": (L, L * 2.0 * T * d * d), "gemm_ffn_up": (L, L * 2.0 * T * d * f),
+            "gemm_ffn_down": (L, L * 2.0 * T * d * f)}
+    if fmt == "f32" or act == "q8":
+        want["embed_ln"] = (1, T * (4.0 + 3 * d * 4 + 4 * d))
+        want["ln_stats"] = (2 * L, 2 * L * M * d * 8.0)
+        want["pool_l2"] = (1, {"mean": T * d * 4.0 + n * d * 4.0, "cls": n * d * 8.0, "tokens": T * d * 8.0}[out])
+    else:
+        fold = os.environ.get("BERT_STATS_FOLD", "1")[:1] != "0"   # tiny64 at 64 / 128 rows has the LDS for it
+        full = L - 1 if out == "cls_pruned" else L               # layers that run on all the rows
+        st, st_c = M * (G + 1) * 8.0, Mc * (G + 1) * 8.0
+        want["embed_ln"] = (1, T * (4.0 + 3 * d * 2 + 2 * d + 8))
+        if out == "cls_pruned":
+            want["attention"] = (L, full * att + 4.0 * d * T)
+            want["gemm_attn_out"] = (L, 2.0 * d * d * (full * T + n))
+            want["gemm_ffn_up"] = want["gemm_ffn_down"] = (L, 2.0 * d * f * (full * T + n))
+            want["ln_stats"] = (1, st_c) if fold else (2 * L, 2 * full * st + 2 * st_c)
+        else:
+            want["ln_stats"] = (1, st) if fold else (2 * L, 2 * L * st)
+        want["pool_l2"] = (1, {"mean": T * d * 2.0 + T * 8.0 + n * d * 4.0, "tokens": T * d * 6.0 + T * 8.0,
+                               "cls": n * (d * 6.0 + 8.0), "cls_pruned": n * (d * 6.0 + 8.0)}[out])
+    print(fmt, act, out, got)
+    assert set(got) == set(want)
+    for k, (launches, work) in want.items():
+        assert got[k][0] == launches, (k, got[k], want[k])
+        assert abs(got[k][1] - work) <= 1e-12 * work, (k, got[k], want[k])
