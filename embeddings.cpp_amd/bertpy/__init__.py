@@ -119,6 +119,19 @@ def load_lib(path=None):
         L.bertx_test_attention_cls.argtypes = [vp, vp, c_i32, c_i32, c_i32, vp]
     except AttributeError:
         pass
+    try:   # (the row-kernel parity hooks: absent from older BERT_LIB builds)
+        L.bertx_test_embed_ln.restype = c_i32
+        L.bertx_test_embed_ln.argtypes = [c_i32] * 7 + [vp] * 7 + [c_i32, c_i32, vp, vp, c_i32]
+        L.bertx_test_ln_stats.restype = c_i32
+        L.bertx_test_ln_stats.argtypes = [vp, c_i32, c_i32, c_i32, c_i32, vp, c_i32]
+        L.bertx_test_pool.restype = c_i32
+        L.bertx_test_pool.argtypes = [c_i32, vp, vp, vp, vp, vp, c_i32, c_i32, c_i32, c_i32, vp, c_i32]
+        L.bertx_test_f32_rows.restype = c_i32
+        L.bertx_test_f32_rows.argtypes = [c_i32, vp, vp, c_i32, c_i32, vp, vp, c_i32, vp, c_i32]
+        L.bertx_test_attention_f32.restype = c_i32
+        L.bertx_test_attention_f32.argtypes = [vp, vp, c_i32, c_i32, c_i32, c_i32, c_i32, vp, c_i32]
+    except AttributeError:
+        pass
     L.bertx_bench_gemm.restype = c_i32
     L.bertx_bench_gemm.argtypes = [c_i32] * 7 + [c_f32p]
     L.bertx_bench_attention.restype = c_i32

@@ -462,3 +462,201 @@ extern "C" int32_t bertx_test_attention_cls(const uint16_t *qkv, const int32_t *
     std::memcpy(out, h.data(), (size_t)n_seqs * d * 2);
     return 0;
 }
+
+// ---------------------------------------------------------------------------
+// Row-kernel parity hooks (norm.hip, f32.hip, table_read.h): one launch over host
+// buffers.  The caller's output buffers (out_rows rows, at least the rows the
+// kernel writes) are uploaded before the launch and copied back whole after it,
+// so a sentinel the caller put there shows which rows the kernel touched.  -1: bad
+// arguments or the launcher's own refusal; -3: the launch was refused by the
+// runtime (hipGetLastError); -4: the synchronise after it reported an error.
+// ---------------------------------------------------------------------------
+namespace emb {
+namespace {
+
+// launch error / execution error of the launch just made
+int hook_finish()
+{
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) {
+        errorf("libbert: test hook: launch refused: %s\n", hipGetErrorString(le));
+        return -3;
+    }
+    const hipError_t se = hipDeviceSynchronize();
+    if (se != hipSuccess) {
+        errorf("libbert: test hook: synchronise failed: %s\n", hipGetErrorString(se));
+        return -4;
+    }
+    return 0;
+}
+
+// cu[0] == 0, ascending, every sentence of 1 .. max_len tokens
+bool hook_cu_ok(const int32_t *cu, int32_t n_seqs, int32_t max_len)
+{
+    if (!cu || n_seqs <= 0 || max_len <= 0 || cu[0] != 0) return false;
+    for (int i = 0; i < n_seqs; ++i)
+        if (cu[i + 1] <= cu[i] || cu[i + 1] - cu[i] > max_len) return false;
+    return true;
+}
+
+// An embedding table from its file-format rows, through repack_table as the engine loads it.
+bool hook_table(int32_t fmt, int32_t rows, int32_t cols, const void *bytes, DevTable &T, HookBufs &B)
+{
+    HostTensor t;
+    t.fmt = fmt; t.ne0 = cols; t.ne1 = rows;
+    t.bytes.assign((const uint8_t *)bytes, (const uint8_t *)bytes + fmt_row_bytes(fmt, cols) * (size_t)rows);
+    Piece q, dd, mm;
+    repack_table(t, q, dd, mm);
+    T.fmt = fmt; T.rows = rows; T.cols = cols;
+    T.qs = B.up(q.bytes.data(), q.bytes.size(), 0);
+    T.d = (const uint16_t *)(dd.bytes.empty() ? nullptr : B.up(dd.bytes.data(), dd.bytes.size(), 0));
+    T.m = (const uint16_t *)(mm.bytes.empty() ? nullptr : B.up(mm.bytes.data(), mm.bytes.size(), 0));
+    return !B.bad;
+}
+
+bool hook_width_ok(int32_t d) { return d >= 64 && d <= 1024 && d % 64 == 0; }
+
+}  // namespace
+}  // namespace emb
+
+extern "C" int32_t bertx_test_embed_ln(int32_t mode, int32_t fmt_word, int32_t fmt_type, int32_t fmt_pos,
+                                       int32_t rows_word, int32_t rows_pos, int32_t d, const void *word_rows,
+                                       const void *type_rows, const void *pos_rows, const float *ln_w,
+                                       const float *ln_b, const int32_t *ids, const int32_t *cu, int32_t n_seqs,
+                                       int32_t max_len, void *out, float *stats, int32_t out_rows)
+{
+    using namespace emb;
+    if (mode < 0 || mode > 2 || !fmt_valid(fmt_word) || !fmt_valid(fmt_type) || !fmt_valid(fmt_pos) ||
+        rows_word <= 0 || rows_pos <= 0 || !hook_width_ok(d) || !word_rows || !type_rows || !pos_rows || !ln_w ||
+        !ln_b || !ids || !out || (mode == 0 && !stats) || !hook_cu_ok(cu, n_seqs, max_len) || max_len > rows_pos ||
+        hip_device_count() == 0)
+        return -1;
+    const int T = cu[n_seqs];
+    if (out_rows < T) return -1;
+    for (int t = 0; t < T; ++t)
+        if (ids[t] < 0 || ids[t] >= rows_word) return -1;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    DevTable word, type, pos;
+    if (!hook_table(fmt_word, rows_word, d, word_rows, word, B) || !hook_table(fmt_type, 2, d, type_rows, type, B) ||
+        !hook_table(fmt_pos, rows_pos, d, pos_rows, pos, B))
+        return -1;
+    const float *dg = (const float *)B.up(ln_w, (size_t)d * 4, 0), *db = (const float *)B.up(ln_b, (size_t)d * 4, 0);
+    const int32_t *dids = (const int32_t *)B.up(ids, (size_t)T * 4, 0);
+    const int32_t *dcu = (const int32_t *)B.up(cu, ((size_t)n_seqs + 1) * 4, 0);
+    const size_t ob = (size_t)out_rows * d * (mode == 0 ? 2 : 4);
+    void *dout = B.up(out, ob, 0);
+    float2 *dst = mode == 0 ? (float2 *)B.up(stats, (size_t)out_rows * 8, 0) : nullptr;
+    if (B.bad) return -1;
+    if (mode == 0) launch_embed_ln(word, type, pos, dg, dids, dcu, n_seqs, max_len, d, (uint16_t *)dout, dst, nullptr);
+    else launch_f32_embed_ln(word, type, pos, dg, db, dids, dcu, n_seqs, max_len, d, (float *)dout, nullptr, mode == 2);
+    if (const int rc = hook_finish()) return rc;
+    HIP_RC(hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost));
+    if (dst) HIP_RC(hipMemcpy(stats, dst, (size_t)out_rows * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int32_t bertx_test_ln_stats(const float *part, int32_t G, int32_t stride, int32_t rows, int32_t d,
+                                       float *stats, int32_t stats_rows)
+{
+    using namespace emb;
+    if (!part || !stats || G <= 0 || G > 64 || rows <= 0 || stride < rows || stats_rows < rows ||
+        hip_device_count() == 0)
+        return -1;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const float2 *dp = (const float2 *)B.up(part, (size_t)G * stride * 8, 0);
+    float2 *dst = (float2 *)B.up(stats, (size_t)stats_rows * 8, 0);
+    if (B.bad) return -1;
+    const int lrc = launch_ln_stats(dp, G, stride, rows, d, dst, nullptr);
+    if (const int rc = hook_finish()) return rc;
+    HIP_RC(hipMemcpy(stats, dst, (size_t)stats_rows * 8, hipMemcpyDeviceToHost));
+    return lrc;
+}
+
+extern "C" int32_t bertx_test_pool(int32_t kind, const uint16_t *z, const float *stats, const float *ln_w,
+                                   const float *ln_b, const int32_t *cu, int32_t n_seqs, int32_t max_len, int32_t T,
+                                   int32_t d, float *out, int32_t out_rows)
+{
+    using namespace emb;
+    if (kind < 0 || kind > 3 || !z || !stats || !ln_w || !ln_b || !out || T <= 0 || !hook_width_ok(d) ||
+        hip_device_count() == 0)
+        return -1;
+    if (kind == 0 || kind == 1) {
+        if (!hook_cu_ok(cu, n_seqs, kind == 0 ? max_len : T) || cu[n_seqs] > T) return -1;
+    }
+    if (kind == 2 && (n_seqs <= 0 || n_seqs > T)) return -1;
+    if (out_rows < (kind == 3 ? T : n_seqs)) return -1;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const uint16_t *dz = (const uint16_t *)B.up(z, (size_t)T * d * 2, 0);
+    const float2 *dst = (const float2 *)B.up(stats, (size_t)T * 8, 0);
+    const float *dg = (const float *)B.up(ln_w, (size_t)d * 4, 0), *db = (const float *)B.up(ln_b, (size_t)d * 4, 0);
+    const int32_t *dcu = kind < 2 ? (const int32_t *)B.up(cu, ((size_t)n_seqs + 1) * 4, 0) : nullptr;
+    float *dout = (float *)B.up(out, (size_t)out_rows * d * 4, 0);
+    float *dpart = kind == 0 ? (float *)B.up(nullptr, 0, (size_t)n_seqs * pool_chunks(max_len) * d * 4) : nullptr;
+    if (B.bad) return -1;
+    if (kind == 0) launch_pool_l2(dz, dst, dg, db, dcu, n_seqs, max_len, d, dpart, dout, nullptr);
+    else if (kind == 3) launch_tokens_f32(dz, dst, dg, db, T, d, dout, nullptr);
+    else launch_cls_l2(dz, dst, dg, db, dcu, n_seqs, d, dout, nullptr);
+    if (const int rc = hook_finish()) return rc;
+    HIP_RC(hipMemcpy(out, dout, (size_t)out_rows * d * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int32_t bertx_test_f32_rows(int32_t kind, const float *x, const int32_t *cu, int32_t n, int32_t d,
+                                       const float *g, const float *b, int32_t flag, float *out, int32_t out_rows)
+{
+    using namespace emb;
+    if (kind < 0 || kind > 2 || !x || !out || n <= 0 || out_rows < n || !hook_width_ok(d) ||
+        (kind == 0 && (!g || !b)) || hip_device_count() == 0)
+        return -1;
+    if (kind != 0 && !hook_cu_ok(cu, n, INT32_MAX)) return -1;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    float *dout = (float *)B.up(out, (size_t)out_rows * d * 4, 0);
+    if (kind == 0) {
+        // in place over the first n rows of the caller's buffer
+        const float *dg = (const float *)B.up(g, (size_t)d * 4, 0), *db = (const float *)B.up(b, (size_t)d * 4, 0);
+        if (B.bad) return -1;
+        HIP_RC(hipMemcpy(dout, x, (size_t)n * d * 4, hipMemcpyHostToDevice));
+        launch_f32_ln(dout, n, d, dg, db, nullptr, flag != 0);
+    } else {
+        const float *dx = (const float *)B.up(x, (size_t)cu[n] * d * 4, 0);
+        const int32_t *dcu = (const int32_t *)B.up(cu, ((size_t)n + 1) * 4, 0);
+        if (B.bad) return -1;
+        if (kind == 1) launch_f32_pool(dx, dcu, n, d, dout, nullptr, flag != 0);
+        else launch_f32_cls(dx, dcu, n, d, dout, nullptr);
+    }
+    if (const int rc = hook_finish()) return rc;
+    HIP_RC(hipMemcpy(out, dout, (size_t)out_rows * d * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int32_t bertx_test_attention_f32(const float *qkv, const int32_t *cu, int32_t n_seqs, int32_t max_len,
+                                            int32_t n_head, int32_t d, int32_t era, float *out, int32_t out_rows)
+{
+    using namespace emb;
+    if (!qkv || !out || n_head <= 0 || d <= 0 || d % n_head || !hook_cu_ok(cu, n_seqs, max_len) ||
+        out_rows < cu[n_seqs] || hip_device_count() == 0)
+        return -1;
+    const size_t T = (size_t)cu[n_seqs];
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const float *dq = (const float *)B.up(qkv, T * 3 * d * 4, 0);
+    const int32_t *dcu = (const int32_t *)B.up(cu, ((size_t)n_seqs + 1) * 4, 0);
+    float *dout = (float *)B.up(out, (size_t)out_rows * d * 4, 0);
+    std::vector<uint16_t> tg, te;
+    era_tables(tg, te);
+    const uint16_t *de = (const uint16_t *)B.up(te.data(), te.size() * 2, 0);
+    if (B.bad) return -1;
+    const int lrc = launch_f32_attention(dq, dcu, n_seqs, max_len, n_head, d, dout, nullptr, de, era != 0);
+    if (const int rc = hook_finish()) return rc;
+    HIP_RC(hipMemcpy(out, dout, (size_t)out_rows * d * 4, hipMemcpyDeviceToHost));
+    return lrc;
+}

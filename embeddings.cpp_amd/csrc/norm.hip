@@ -44,6 +44,18 @@ __device__ __forceinline__ float sum32(float v)
     return v;
 }
 
+// f16(a * b) with the f32 product rounded first, then rounded to f16.  The empty asm hides
+// the product from instruction selection: left alone, the compiler turned 14 of a lane's
+// 32 products of the q8_0 instantiation (and of no other) into v_fma_mixlo/hi_f16, one
+// fused multiply-convert with a single rounding, so about one z in 2^13 (an f32 product on
+// an f16 tie) differed by an f16 ulp with the tables' format.
+__device__ __forceinline__ h16 f16_of_product(float a, float b)
+{
+    float p = a * b;
+    asm("" : "+v"(p));
+    return (h16)p;
+}
+
 // resident waves per SIMD the register budget is held to (no spills at these)
 constexpr int emb_occ(int tf) { return tf == FMT_Q4_0 || tf == FMT_F16 ? 8 : tf < 0 ? 4 : 6; }
 
@@ -92,8 +104,8 @@ __global__ __launch_bounds__(256, emb_occ(TF)) void embed_ln_kernel(DevTable wor
             h16x8 zh;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                zh[e] = (h16)(v[8 * q + e] * g0[e]);
-                zh[4 + e] = (h16)(v[8 * q + 4 + e] * g1[e]);
+                zh[e] = f16_of_product(v[8 * q + e], g0[e]);
+                zh[4 + e] = f16_of_product(v[8 * q + 4 + e], g1[e]);
             }
             dst[q] = zh;                            // the stream as z = y * gamma (kernels.h LN fold)
         }

@@ -260,6 +260,54 @@ BERT_API int32_t bertx_test_attention_cls(const uint16_t *qkv, const int32_t *cu
                                           int32_t d, uint16_t *out);
 
 /*
+ * Parity hooks of the memory-bound row kernels (norm.hip, f32.hip and their table
+ * readers; host buffers, device 0, one launch each).  Common rules: every output
+ * buffer has out_rows rows (at least the rows the kernel writes), is uploaded
+ * before the launch and copied back whole after it, so rows the caller pre-filled
+ * with a sentinel show whether the kernel touched them.  Returns 0; -1 for bad
+ * arguments or the launcher's own refusal (outputs still copied back); -3 when the
+ * runtime refused the launch; -4 when the synchronise after it reported an error.
+ * cu: int32 [n_seqs + 1] token offsets, cu[0] = 0, every sentence of 1 .. max_len
+ * tokens; widths d % 64 == 0, 64 <= d <= 1024.
+ *
+ * bertx_test_embed_ln: the three embedding tables as file-format rows (word
+ * [rows_word][d] in fmt_word, type [2][d], pos [rows_pos][d]; formats may differ),
+ * repacked as at load.  mode 0: the f16 chain's kernel, out f16 [out_rows][d] = z =
+ * f16((pos[i] + (type[0] + word[id])) * ln_w) and stats f32 [out_rows][2] = (mean,
+ * 1/sigma) of the f32 sum.  mode 1 / 2: the f32 chain's kernel (2: its exact form),
+ * out f32 [out_rows][d] = LayerNorm of the sum; stats unused.
+ *
+ * bertx_test_ln_stats: part f32 pairs [G][stride] -> stats f32 [stats_rows][2] for
+ * rows < rows; the launcher's return value (-1: refused, nothing launched).
+ *
+ * bertx_test_pool: z f16 [T][d] with stats f32 [T][2] (the LN fold's stream).  kind
+ * 0: mean pool + L2 (max_len picks the one- or two-launch form), out [out_rows][d],
+ * rows < n_seqs; 1: [CLS] pool of rows cu[b]; 2: [CLS] pool of the compact rows b
+ * (cu unused); 3: per-token LN output, rows < T.
+ *
+ * bertx_test_f32_rows: the f32 chain.  kind 0: LayerNorm of x [n][d] (flag: exact),
+ * out [out_rows][d] rows < n; 1: mean pool of x [cu[n]][d] over n sentences (flag:
+ * the era summation order); 2: [CLS] pool.  g, b: gamma, beta (kind 0).
+ *
+ * bertx_test_attention_f32: qkv f32 [T][3d] -> out f32 [out_rows][d], rows < T; era:
+ * the era summation order.  Returns launch_f32_attention's value (-1: refused).
+ */
+BERT_API int32_t bertx_test_embed_ln(int32_t mode, int32_t fmt_word, int32_t fmt_type, int32_t fmt_pos,
+                                     int32_t rows_word, int32_t rows_pos, int32_t d, const void *word_rows,
+                                     const void *type_rows, const void *pos_rows, const float *ln_w,
+                                     const float *ln_b, const int32_t *ids, const int32_t *cu, int32_t n_seqs,
+                                     int32_t max_len, void *out, float *stats, int32_t out_rows);
+BERT_API int32_t bertx_test_ln_stats(const float *part, int32_t G, int32_t stride, int32_t rows, int32_t d,
+                                     float *stats, int32_t stats_rows);
+BERT_API int32_t bertx_test_pool(int32_t kind, const uint16_t *z, const float *stats, const float *ln_w,
+                                 const float *ln_b, const int32_t *cu, int32_t n_seqs, int32_t max_len, int32_t T,
+                                 int32_t d, float *out, int32_t out_rows);
+BERT_API int32_t bertx_test_f32_rows(int32_t kind, const float *x, const int32_t *cu, int32_t n, int32_t d,
+                                     const float *g, const float *b, int32_t flag, float *out, int32_t out_rows);
+BERT_API int32_t bertx_test_attention_f32(const float *qkv, const int32_t *cu, int32_t n_seqs, int32_t max_len,
+                                          int32_t n_head, int32_t d, int32_t era, float *out, int32_t out_rows);
+
+/*
  * The tokenization stage of bert_encode_batch on its own (bert.cpp:1402-1406 runs
  * it sequentially; here on n_threads threads of the library's persistent pool):
  * texts[i] -> ids[i * n_max .. + min(n_tokens[i], n_max)), n_tokens[i] =
