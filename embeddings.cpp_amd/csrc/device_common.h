@@ -199,6 +199,15 @@ __device__ __forceinline__ float2 ln_row_stats(const float2 (&p)[MAXG], int G, i
     return float2{mean, __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(__fdiv_rn(m2, (float)d), 1e-5f)))};
 }
 
+// XCD-aware bijective remap of workgroup b of nb: workgroups are dealt to the 8
+// XCDs round-robin; this gives each XCD a contiguous run of logical ids, so
+// neighbouring ids share one XCD's L2.
+__device__ __forceinline__ int xcd_block(int b, int nb)
+{
+    const int xcd = b & 7, qq = nb >> 3, rr = nb & 7;
+    return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (b >> 3);
+}
+
 __device__ __forceinline__ void lds_barrier()
 {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -286,10 +286,9 @@ __device__ __forceinline__ void gemmz_body(char *__restrict__ smem, const int b,
     ZSTAMP(0, __builtin_amdgcn_s_memtime());
     // XCD-aware bijective remap: consecutive tiles (same token panel) land on one
     // XCD's L2 (workgroups are dealt to the 8 XCDs round-robin)
-    const int xcd = b & 7, qq = nTiles >> 3, rr = nTiles & 7;
     // (round 6 measured panel-group and snake orders of the tiles inside an XCD's
     // share: within noise, and without the remap -13 %; profiles/r06_gemm_raster_ab.log)
-    const int t = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (b >> 3);
+    const int t = xcd_block(b, nTiles);
     const int m0 = (t / nN) * BM, n0 = (t % nN) * BN;
     const int K = W.K, N = W.N, KS = K / ZK;
     const int KX = W.kx ? W.kx : K, KSX = KX / ZK;   // X columns (f32 hi/lo weights: K = 2 KX)
