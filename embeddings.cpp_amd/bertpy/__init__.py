@@ -132,6 +132,34 @@ def load_lib(path=None):
         L.bertx_test_attention_f32.argtypes = [vp, vp, c_i32, c_i32, c_i32, c_i32, c_i32, vp, c_i32]
     except AttributeError:
         pass
+    try:   # (the embedding index: absent from older BERT_LIB builds)
+        L.bertx_index_create.restype = vp
+        L.bertx_index_create.argtypes = [vp, c_i32, c_i32]
+        L.bertx_index_free.restype = None
+        L.bertx_index_free.argtypes = [vp]
+        for fn in (L.bertx_index_clear, L.bertx_index_size, L.bertx_index_capacity, L.bertx_index_dim):
+            fn.restype = c_i32
+            fn.argtypes = [vp]
+        L.bertx_index_add.restype = c_i32
+        L.bertx_index_add.argtypes = [vp, vp, c_i32]
+        L.bertx_index_add_device.restype = c_i32
+        L.bertx_index_add_device.argtypes = [vp, vp, c_i32, vp]
+        L.bertx_index_rows.restype = c_i32
+        L.bertx_index_rows.argtypes = [vp, c_i32, c_i32, vp]
+        L.bertx_index_search.restype = c_i32
+        L.bertx_index_search.argtypes = [vp, vp, c_i32, c_i32, vp, vp]
+        L.bertx_index_search_device.restype = c_i32
+        L.bertx_index_search_device.argtypes = [vp, vp, c_i32, c_i32, vp, vp, vp]
+        L.bertx_index_add_texts.restype = c_i32
+        L.bertx_index_add_texts.argtypes = [vp, vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p)]
+        L.bertx_index_search_texts.restype = c_i32
+        L.bertx_index_search_texts.argtypes = [vp, vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p), c_i32, vp, vp]
+        L.bertx_bench_search.restype = c_i32
+        L.bertx_bench_search.argtypes = [c_i32] * 5 + [c_f32p]
+        L.bertx_bench_search_add_rate.restype = c_i32
+        L.bertx_bench_search_add_rate.argtypes = [c_i32, c_i32, ctypes.POINTER(ctypes.c_double)]
+    except AttributeError:
+        pass
     L.bertx_bench_gemm.restype = c_i32
     L.bertx_bench_gemm.argtypes = [c_i32] * 7 + [c_f32p]
     L.bertx_bench_attention.restype = c_i32
@@ -304,6 +332,89 @@ class BertModel:
             out.append({"name": name.value.decode(), "launches": launches.value, "ms": ms.value,
                         "work": work.value, "work_is_flops": bool(flops.value)})
             i += 1
+        return out
+
+
+class BertIndex:
+    """A device-resident embedding index with fused top-k search (bertx_index_*): rows of
+    the model's n_embd, stored as f16 on GPU `slot` of the model's context; ids are the
+    insertion order.  Scores are dot products (cosines, for the model's unit rows)."""
+
+    def __init__(self, model, capacity, slot=0):
+        self.model = model
+        self.lib = model.lib
+        self.idx = self.lib.bertx_index_create(model.ctx, slot, capacity)
+        if not self.idx:
+            raise RuntimeError("bertx_index_create failed")
+        self.dim = int(self.lib.bertx_index_dim(self.idx))
+        self.capacity = int(self.lib.bertx_index_capacity(self.idx))
+
+    def __del__(self):
+        if getattr(self, "idx", None):
+            self.lib.bertx_index_free(self.idx)
+            self.idx = None
+
+    def __len__(self):
+        return int(self.lib.bertx_index_size(self.idx))
+
+    def clear(self):
+        self.lib.bertx_index_clear(self.idx)
+
+    def _rows(self, a):
+        a = np.ascontiguousarray(np.asarray(a, np.float32))
+        if a.ndim == 1:
+            a = a[None, :]
+        if a.ndim != 2 or a.shape[1] != self.dim:
+            raise ValueError("expected rows of width %d, got shape %r" % (self.dim, a.shape))
+        return a
+
+    @staticmethod
+    def _texts(texts):
+        arr = (ctypes.c_char_p * len(texts))()
+        for j, s in enumerate(texts):
+            arr[j] = s.encode("utf-8") if isinstance(s, str) else s
+        return arr
+
+    def add(self, rows):
+        """Append f32 rows [n][dim]; returns the id of the first one."""
+        a = self._rows(rows)
+        rc = self.lib.bertx_index_add(self.idx, a.ctypes.data, a.shape[0])
+        if rc < 0:
+            raise RuntimeError("bertx_index_add failed (%d)" % rc)
+        return rc
+
+    def add_texts(self, texts):
+        """Encode (the model's pooling mode) and append; returns the id of the first new row."""
+        rc = self.lib.bertx_index_add_texts(self.idx, self.model.ctx, self.model.N_THREADS, len(texts),
+                                            self._texts(texts))
+        if rc < 0:
+            raise RuntimeError("bertx_index_add_texts failed (%d)" % rc)
+        return rc
+
+    def search(self, queries, k):
+        """(scores f32 [B][k], ids i32 [B][k]) of the k best rows per query, best first."""
+        q = self._rows(queries)
+        scores = np.zeros((q.shape[0], k), np.float32)
+        ids = np.zeros((q.shape[0], k), np.int32)
+        rc = self.lib.bertx_index_search(self.idx, q.ctypes.data, q.shape[0], k, scores.ctypes.data, ids.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_index_search failed (%d)" % rc)
+        return scores, ids
+
+    def search_texts(self, texts, k):
+        scores = np.zeros((len(texts), k), np.float32)
+        ids = np.zeros((len(texts), k), np.int32)
+        rc = self.lib.bertx_index_search_texts(self.idx, self.model.ctx, self.model.N_THREADS, len(texts),
+                                               self._texts(texts), k, scores.ctypes.data, ids.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_index_search_texts failed (%d)" % rc)
+        return scores, ids
+
+    def rows(self, first, n):
+        """The stored rows first .. first + n - 1: the exact f16 values as f32 [n][dim]."""
+        out = np.zeros((n, self.dim), np.float32)
+        if n and self.lib.bertx_index_rows(self.idx, first, n, out.ctypes.data) != 0:
+            raise RuntimeError("bertx_index_rows failed")
         return out
 
 

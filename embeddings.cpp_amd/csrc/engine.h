@@ -13,6 +13,8 @@
 #include <string>
 #include <vector>
 
+struct bertx_index;
+
 namespace emb {
 
 enum KClass : int32_t {
@@ -296,5 +298,10 @@ private:
 
 // HIP device count (0 when no runtime / no GPU); never throws.
 int hip_device_count();
+
+// An embedding index (index.cpp, bert_hip.h bertx_index_*) of `capacity` rows of width
+// d on device `ordinal`, without a context (bertx_index_create, the search bench).
+// NULL after a message.
+::bertx_index *index_create_on(int ordinal, int d, int64_t capacity);
 
 }  // namespace emb

@@ -401,6 +401,103 @@ extern "C" int32_t bertx_bench_attention(int32_t n_seqs, int32_t len, int32_t n_
     return 0;
 }
 
+namespace emb {
+namespace {
+
+struct IndexHolder {
+    bertx_index *ix = nullptr;
+    ~IndexHolder() { bertx_index_free(ix); }
+};
+
+// An index of N unit rows on device 0, filled by device-form adds of kFill rows from
+// a staging buffer of hashed values, all on stream s; fill_ms (if not null): the adds' device time.
+constexpr int64_t kFill = 65536;
+int bench_index(int32_t d, int32_t N, HookBufs &B, IndexHolder &H, hipStream_t s, float *fill_ms)
+{
+    H.ix = index_create_on(0, d, N);
+    if (!H.ix) return -1;
+    const int64_t chunk = std::min<int64_t>(kFill, N);
+    float *rows = (float *)B.up(nullptr, 0, (size_t)chunk * d * 4);
+    if (B.bad) return -1;
+    EventPair ev;
+    HIP_RC(ev.create());
+    float total = 0.f;
+    for (int64_t i = 0; i < N; i += chunk) {
+        const int64_t m = std::min<int64_t>(chunk, N - i);
+        if (launch_unit_rows(rows, m, d, 12345u + (uint32_t)i, s) != 0) return -1;
+        HIP_RC(hipEventRecord(ev.a, s));
+        if (bertx_index_add_device(H.ix, rows, (int32_t)m, s) < 0) return -1;
+        HIP_RC(hipEventRecord(ev.b, s));
+        HIP_RC(hipEventSynchronize(ev.b));
+        float ms = 0.f;
+        HIP_RC(hipEventElapsedTime(&ms, ev.a, ev.b));
+        total += ms;
+    }
+    if (fill_ms) *fill_ms = total;
+    return 0;
+}
+
+}  // namespace
+}  // namespace emb
+
+namespace emb {
+namespace {
+struct StreamHolder {
+    hipStream_t s = nullptr;
+    ~StreamHolder()
+    {
+        if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+    }
+};
+}  // namespace
+}  // namespace emb
+
+extern "C" int32_t bertx_bench_search(int32_t d, int32_t N, int32_t B, int32_t k, int32_t iters, float *avg_us)
+{
+    using namespace emb;
+    if (N <= 0 || B <= 0 || iters <= 0 || !avg_us || hip_device_count() == 0) return -1;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs bufs;
+    IndexHolder H;
+    StreamHolder S;   // destroyed (after a synchronise) before the index and the buffers
+    HIP_RC(hipStreamCreateWithFlags(&S.s, hipStreamNonBlocking));
+    if (bench_index(d, N, bufs, H, S.s, nullptr) != 0) return -1;
+    float *q = (float *)bufs.up(nullptr, 0, (size_t)B * d * 4);
+    float *sc = (float *)bufs.up(nullptr, 0, (size_t)B * 128 * 4);
+    int32_t *id = (int32_t *)bufs.up(nullptr, 0, (size_t)B * 128 * 4);
+    if (bufs.bad || launch_unit_rows(q, B, d, 777u, S.s) != 0) return -1;
+    for (int i = 0; i < 3; ++i)
+        if (bertx_index_search_device(H.ix, q, B, k, sc, id, S.s) != 0) return -1;
+    EventPair ev;
+    HIP_RC(ev.create());
+    HIP_RC(hipEventRecord(ev.a, S.s));
+    for (int i = 0; i < iters; ++i)
+        if (bertx_index_search_device(H.ix, q, B, k, sc, id, S.s) != 0) return -1;
+    HIP_RC(hipEventRecord(ev.b, S.s));
+    HIP_RC(hipEventSynchronize(ev.b));
+    float ms = 0.f;
+    HIP_RC(hipEventElapsedTime(&ms, ev.a, ev.b));
+    *avg_us = ms * 1000.f / (float)iters;
+    return 0;
+}
+
+extern "C" int32_t bertx_bench_search_add_rate(int32_t d, int32_t N, double *add_rows_per_s)
+{
+    using namespace emb;
+    if (N <= 0 || !add_rows_per_s || hip_device_count() == 0) return -1;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs bufs;
+    IndexHolder H;
+    StreamHolder S;
+    HIP_RC(hipStreamCreateWithFlags(&S.s, hipStreamNonBlocking));
+    float ms = 0.f;
+    if (bench_index(d, N, bufs, H, S.s, &ms) != 0 || ms <= 0.f) return -1;
+    *add_rows_per_s = (double)N / (ms * 1e-3);
+    return 0;
+}
+
 extern "C" int32_t bertx_test_attention(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head,
                                         int32_t d, int32_t variant, uint16_t *out)
 {

@@ -1,0 +1,346 @@
+// Fused top-k search over a device-resident f16 embedding index (bertx_index_*,
+// bert_hip.h).  One streaming pass over the stored rows:
+// the scores of up to 64 queries are taken on v_mfma_f32_16x16x32_f16 straight from
+// the rows' HBM image (fragment order, below) and the k best of a workgroup's row
+// range are kept in LDS, so no [B][N] score matrix ever exists.  A second small
+// kernel merges the workgroups' lists.
+//
+// Stored layout ("fragment order", the A operand of the MFMA as it sits in HBM):
+// rows in groups of 16, a group's d / 32 blocks consecutive, a block = 16 rows x
+// 32 k = 1 KiB; lane 16g + f of a block holds row f, elements 8g .. 8g + 7 (16 B).
+// One global_load_dwordx4 per wave is one contiguous block and goes to the MFMA
+// without touching LDS.
+//
+// Arithmetic of one (query, row) score: both operands f16 (round to nearest even),
+// the d / 32 MFMAs of the row's group in ascending k into an f32 accumulator that
+// starts at 0.  Every tile of every launch runs that same sequence, so a score
+// depends on neither the row's position, the row count nor the other queries.
+#include "device_common.h"
+#include "kernels.h"
+
+#include <algorithm>
+
+namespace emb {
+namespace {
+
+constexpr int kThreads = 256;          // 4 waves: each streams its own contiguous run of 16-row groups
+constexpr int kUnitsAhead = 8;         // prefetch ring: 8 units of 2 blocks = 16 KiB in flight per wave
+constexpr int kLdsBudget = 160 * 1024; // LDS of one CU (a single workgroup may use all of it)
+
+// (score, id) order of the results: higher score first, equal scores by ascending
+// id.  Empty slots are (-inf, -1): the unsigned compare puts id -1 behind every row.
+__device__ __forceinline__ bool better(float as, int32_t ai, float bs, int32_t bi)
+{
+    return as > bs || (as == bs && (uint32_t)ai < (uint32_t)bi);
+}
+
+struct Hit { float s; int32_t id; };
+
+// Inserts (cs, ci) into the descending list of k <= 128 entries, by one whole wave
+// (lane l holds entries l and l + 64).  Entries the candidate beats move down by
+// one, the last one drops out; a candidate that beats none changes nothing.  The
+// reads of every lane precede the writes (one wave, LDS operations in order).
+__device__ __forceinline__ void list_insert(Hit *list, int k, float cs, int32_t ci, int lane)
+{
+    const int j0 = lane, j1 = lane + 64;
+    Hit e0{0.f, 0}, e1{0.f, 0};
+    if (j0 < k) e0 = list[j0];
+    if (j1 < k) e1 = list[j1];
+    const bool b0 = j0 < k && better(e0.s, e0.id, cs, ci);
+    const bool b1 = j1 < k && better(e1.s, e1.id, cs, ci);
+    const int pos = __popcll(__ballot(b0)) + __popcll(__ballot(b1));
+    if (pos >= k) return;
+    if (j0 < k && !b0 && j0 + 1 < k) list[j0 + 1] = e0;
+    if (j1 < k && !b1 && j1 + 1 < k) list[j1 + 1] = e1;
+    if (lane == (pos & 63)) list[pos] = Hit{cs, ci};
+}
+
+// Offers this lane's (s, id) (when `valid`) to the list: candidates that beat the
+// current k-th entry are inserted one by one, lowest lane first.  The final list is
+// the k best of everything offered whatever the order of the offers, because
+// `better` is a total order.
+__device__ __forceinline__ void list_offer(Hit *list, int k, float s, int32_t id, bool valid, int lane)
+{
+    const Hit th = list[k - 1];
+    unsigned long long mask = __ballot(valid && better(s, id, th.s, th.id));
+    while (mask) {
+        const int l = __builtin_ctzll(mask);
+        mask &= mask - 1;
+        list_insert(list, k, __shfl(s, l, 64), __shfl(id, l, 64), lane);
+    }
+}
+
+// LDS of the search kernel for QT query tiles (16 queries each): the queries' B
+// fragments, the running lists, the score tile of one step, the step's group ids.
+__host__ __device__ inline size_t search_lds_bytes(int QT, int d, int k)
+{
+    return (size_t)QT * 16 * ((size_t)d * 2 + (size_t)k * 8 + 64 * 4) + 16;
+}
+
+// Workgroup b walks the 16-row groups [b * per, (b + 1) * per), per % 4 == 0: wave w
+// streams the contiguous quarter w of them, one group per step.  After a group's
+// d / 32 blocks the wave's 16 x (16 QT) scores go to the LDS score tile; then wave w
+// offers the step's 64 rows to the lists of queries w, w + 4, ... (one lane per row).
+// Rows >= n_rows (the unfilled part of the last group, and the groups a range has
+// past the end) are never offered.  partial: [query][P][k].
+template <int QT>
+__global__ __launch_bounds__(kThreads) void search_kernel(const h16x8 *__restrict__ corpus,
+                                                          const float *__restrict__ queries, int nq, int d,
+                                                          int n_rows, int k, int per, Hit *__restrict__ partial)
+{
+    extern __shared__ uint4 smem[];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int KB = d >> 5, nq16 = QT * 16;
+    h16x8 *qf = (h16x8 *)smem;                                  // [QT][KB][64]
+    Hit *lists = (Hit *)(qf + (size_t)QT * KB * 64);            // [nq16][k]
+    float *tile = (float *)(lists + (size_t)nq16 * k);          // [nq16][64]
+    int *gb = (int *)(tile + nq16 * 64);                        // [4]
+
+    // the queries as f16 B fragments: lane 16g + c of block (t, kb) holds query
+    // 16t + c, elements 32kb + 8g .. + 7; queries past nq are zeros
+    const int chunks = d >> 3;
+    for (int i = tid; i < nq16 * chunks; i += kThreads) {
+        const int q = i / chunks, c = i - q * chunks;
+        h16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (q < nq) {
+            const float4 a = *(const float4 *)(queries + (size_t)q * d + 8 * c);
+            const float4 b = *(const float4 *)(queries + (size_t)q * d + 8 * c + 4);
+            v = h16x8{(h16)a.x, (h16)a.y, (h16)a.z, (h16)a.w, (h16)b.x, (h16)b.y, (h16)b.z, (h16)b.w};
+        }
+        qf[((size_t)(q >> 4) * KB + (c >> 2)) * 64 + 16 * (c & 3) + (q & 15)] = v;
+    }
+    for (int i = tid; i < nq16 * k; i += kThreads) lists[i] = Hit{-INFINITY, -1};
+    lds_barrier();
+
+    // wave-uniform stream position in scalar registers: block index -> one base
+    // address per load, the lane's 16 B at base + 16 lane
+    const int ws = __builtin_amdgcn_readfirstlane(w);
+    const int steps = per >> 2;
+    const int g0 = blockIdx.x * per + ws * steps;                 // this wave's first group
+    const int last_blk = max((n_rows + 15) >> 4, 1) * KB - 1;     // loads stay inside the filled groups
+    const int blk0 = g0 * KB;
+    const int U = steps * (KB >> 1);                              // units of 2 blocks; the same for all waves
+    auto load = [&](int blk) { return (corpus + (size_t)min(blk, last_blk) * 64)[lane]; };
+
+    // the ring is filled and refilled in the order it is consumed (the scheduling
+    // barriers keep the compiler from reordering the loads), so a unit's two loads
+    // are always the oldest ones outstanding
+    h16x8 ring[kUnitsAhead][2];
+#pragma unroll
+    for (int j = 0; j < kUnitsAhead; ++j) {
+        ring[j][0] = load(blk0 + 2 * j);
+        ring[j][1] = load(blk0 + 2 * j + 1);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    f32x4 acc[QT];
+#pragma unroll
+    for (int t = 0; t < QT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    int kb = 0, g = g0;
+    const int nqv = min(nq, nq16);
+    for (int u0 = 0; u0 < U; u0 += kUnitsAhead) {
+#pragma unroll
+        for (int j = 0; j < kUnitsAhead; ++j) {
+            const int u = u0 + j;
+            if (u >= U) goto done;   // uniform over the workgroup; no path re-enters the ring out of order
+            {
+                const h16x8 a0 = ring[j][0], a1 = ring[j][1];
+#pragma unroll
+                for (int t = 0; t < QT; ++t) {
+                    const h16x8 b0 = qf[((size_t)t * KB + kb) * 64 + lane];
+                    const h16x8 b1 = qf[((size_t)t * KB + kb + 1) * 64 + lane];
+                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, b0, acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b1, acc[t], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                ring[j][0] = load(blk0 + 2 * (u + kUnitsAhead));
+                ring[j][1] = load(blk0 + 2 * (u + kUnitsAhead) + 1);
+                __builtin_amdgcn_sched_barrier(0);
+                kb += 2;
+                if (kb == KB) {
+                    // accumulator register r of lane l: row 4 (l >> 4) + r of the group, query l & 15 of tile t
+#pragma unroll
+                    for (int t = 0; t < QT; ++t) {
+                        *(f32x4 *)&tile[(16 * t + (lane & 15)) * 64 + 16 * w + 4 * (lane >> 4)] = acc[t];
+                        acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    }
+                    if (lane == 0) gb[w] = g;
+                    lds_barrier();
+                    const int64_t row = (int64_t)gb[lane >> 4] * 16 + (lane & 15);
+                    const bool valid = row < n_rows;
+                    for (int q = w; q < nqv; q += 4)
+                        list_offer(lists + (size_t)q * k, k, tile[q * 64 + lane], (int32_t)row, valid, lane);
+                    lds_barrier();
+                    kb = 0;
+                    ++g;
+                }
+            }
+        }
+    }
+done:
+    const int P = gridDim.x;
+    for (int i = tid; i < nqv * k; i += kThreads) {
+        const int q = i / k, j = i - q * k;
+        partial[((size_t)q * P + blockIdx.x) * k + j] = lists[i];
+    }
+}
+
+// One workgroup per query: wave w folds the partial lists w, w + 4, ... into its own
+// LDS list (the next list's entries are loaded while the current one is offered),
+// wave 0 then folds the other three waves' lists into its own and writes the result.
+__global__ __launch_bounds__(kThreads) void search_merge_kernel(const Hit *__restrict__ partial, int P, int k,
+                                                                float *__restrict__ scores,
+                                                                int32_t *__restrict__ ids)
+{
+    __shared__ Hit lists[4][128];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, q = blockIdx.x;
+    Hit *mine = lists[w];
+    for (int j = lane; j < 128; j += 64) mine[j] = Hit{-INFINITY, -1};
+    const Hit *src = partial + (size_t)q * P * k;
+    const Hit none{-INFINITY, -1};
+    Hit n0 = none, n1 = none;
+    if (w < P) {
+        if (lane < k) n0 = src[(size_t)w * k + lane];
+        if (lane + 64 < k) n1 = src[(size_t)w * k + lane + 64];
+    }
+    for (int p = w; p < P; p += 4) {
+        const Hit e0 = n0, e1 = n1;
+        n0 = none; n1 = none;
+        if (p + 4 < P) {
+            if (lane < k) n0 = src[(size_t)(p + 4) * k + lane];
+            if (lane + 64 < k) n1 = src[(size_t)(p + 4) * k + lane + 64];
+        }
+        list_offer(mine, k, e0.s, e0.id, lane < k && e0.id >= 0, lane);
+        list_offer(mine, k, e1.s, e1.id, lane + 64 < k && e1.id >= 0, lane);
+    }
+    lds_barrier();
+    if (w == 0) {
+        for (int o = 1; o < 4; ++o) {
+            const Hit e0 = lists[o][lane], e1 = lists[o][lane + 64];
+            list_offer(mine, k, e0.s, e0.id, lane < k && e0.id >= 0, lane);
+            list_offer(mine, k, e1.s, e1.id, lane + 64 < k && e1.id >= 0, lane);
+        }
+        for (int j = lane; j < k; j += 64) {
+            const Hit e = mine[j];
+            scores[(size_t)q * k + j] = e.s;
+            ids[(size_t)q * k + j] = e.id;
+        }
+    }
+}
+
+// rows f32 [n][d] -> f16 (round to nearest even) into fragment order at rows
+// first .. first + n - 1; one thread per 8 elements (one 16-B store).
+__global__ __launch_bounds__(kThreads) void index_add_kernel(const float *__restrict__ rows, int64_t n, int d,
+                                                             int64_t first, h16x8 *__restrict__ corpus)
+{
+    const int chunks = d >> 3, KB = d >> 5;
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n * chunks) return;
+    const int64_t r = i / chunks;
+    const int c = (int)(i - r * chunks);
+    const float4 a = *(const float4 *)(rows + r * d + 8 * c);
+    const float4 b = *(const float4 *)(rows + r * d + 8 * c + 4);
+    const int64_t row = first + r;
+    corpus[((row >> 4) * KB + (c >> 2)) * 64 + 16 * (c & 3) + (row & 15)] =
+        h16x8{(h16)a.x, (h16)a.y, (h16)a.z, (h16)a.w, (h16)b.x, (h16)b.y, (h16)b.z, (h16)b.w};
+}
+
+// Benchmark data: row r of out [n][d] = a unit vector of hashed values in [-1, 1); one wave per row.
+__global__ __launch_bounds__(kThreads) void unit_rows_kernel(float *__restrict__ out, int64_t n, int d, uint32_t seed)
+{
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const int lane = threadIdx.x & 63;
+    float ss = 0.f;
+    for (int c = lane; c < d; c += 64) {
+        uint32_t h = (uint32_t)(r * d + c) * 2654435761u + seed;
+        h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
+        const float v = (float)(h >> 8) * (1.0f / 8388608.0f) - 1.0f;
+        out[r * d + c] = v;
+        ss += v * v;
+    }
+    const float inv = 1.0f / sqrtf(wave_sum(ss));
+    for (int c = lane; c < d; c += 64) out[r * d + c] *= inv;
+}
+
+template <int QT>
+hipError_t allow_lds()
+{
+    return hipFuncSetAttribute((const void *)search_kernel<QT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               kLdsBudget);
+}
+
+}  // namespace
+
+int search_prepare_device()
+{
+    hipError_t e = allow_lds<1>();
+    if (e == hipSuccess) e = allow_lds<2>();
+    if (e == hipSuccess) e = allow_lds<3>();
+    if (e == hipSuccess) e = allow_lds<4>();
+    return e == hipSuccess ? 0 : -1;
+}
+
+int search_group_queries(int d, int k)
+{
+    int QT = 4;
+    while (QT > 1 && search_lds_bytes(QT, d, k) > (size_t)kLdsBudget) --QT;
+    return 16 * QT;
+}
+
+int64_t search_max_workgroups(int64_t capacity_rows)
+{
+    const int64_t groups = (capacity_rows + 15) / 16;
+    return std::max<int64_t>(1, std::min<int64_t>(2 * (int64_t)device_cu_count(), (groups + 3) / 4));
+}
+
+int launch_index_add(const float *d_rows, int64_t n, int d, int64_t first, void *corpus, hipStream_t s)
+{
+    if (n <= 0 || d % 64 || d < 64 || d > 1024) return -1;
+    const int64_t blocks = (n * (d / 8) + kThreads - 1) / kThreads;
+    if (blocks > 0x7fffffff) return -1;
+    index_add_kernel<<<(unsigned)blocks, kThreads, 0, s>>>(d_rows, n, d, first, (h16x8 *)corpus);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_search(const void *corpus, int64_t n_rows, int d, const float *d_queries, int B, int k, void *scratch,
+                  float *d_scores, int32_t *d_ids, hipStream_t s)
+{
+    if (B < 1 || k < 1 || k > 128 || d % 64 || d < 64 || d > 1024 || n_rows < 0 || n_rows > 0x7ffffff0) return -1;
+    const int QG = search_group_queries(d, k);
+    if (search_lds_bytes(1, d, k) > (size_t)kLdsBudget) return -1;
+    // the row ranges: P workgroups of `per` groups each, per % 4 == 0 (one group per wave and step)
+    const int64_t groups = std::max<int64_t>(1, (n_rows + 15) / 16);
+    const int cus = device_cu_count();
+    // block indices are 32-bit in the kernel, the ranges' overhang and the prefetch included
+    if ((groups + 8 * (int64_t)cus + 8) * (d / 32) + 4 * kUnitsAhead > 0x7fffffffll) return -1;
+    for (int b0 = 0; b0 < B; b0 += QG) {
+        const int nq = std::min(QG, B - b0), QT = (nq + 15) / 16;
+        const size_t lds = search_lds_bytes(QT, d, k);
+        const int64_t wg_per_cu = std::min<int64_t>(2, (int64_t)kLdsBudget / (int64_t)lds);
+        int64_t P = std::max<int64_t>(1, std::min<int64_t>(wg_per_cu * cus, (groups + 3) / 4));
+        const int64_t per = ((groups + P - 1) / P + 3) / 4 * 4;
+        P = (groups + per - 1) / per;
+        const h16x8 *C = (const h16x8 *)corpus;
+        const float *Q = d_queries + (size_t)b0 * d;
+        Hit *part = (Hit *)scratch;
+        switch (QT) {
+        case 1: search_kernel<1><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, (int)n_rows, k, (int)per, part); break;
+        case 2: search_kernel<2><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, (int)n_rows, k, (int)per, part); break;
+        case 3: search_kernel<3><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, (int)n_rows, k, (int)per, part); break;
+        default: search_kernel<4><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, (int)n_rows, k, (int)per, part); break;
+        }
+        if (hipGetLastError() != hipSuccess) return -3;
+        search_merge_kernel<<<nq, kThreads, 0, s>>>(part, (int)P, k, d_scores + (size_t)b0 * k, d_ids + (size_t)b0 * k);
+        if (hipGetLastError() != hipSuccess) return -3;
+    }
+    return 0;
+}
+
+int launch_unit_rows(float *d_out, int64_t n, int d, uint32_t seed, hipStream_t s)
+{
+    if (n <= 0 || d <= 0) return -1;
+    unit_rows_kernel<<<(unsigned)((n + 3) / 4), kThreads, 0, s>>>(d_out, n, d, seed);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // namespace emb

@@ -318,6 +318,80 @@ BERT_API int32_t bertx_test_attention_f32(const float *qkv, const int32_t *cu, i
 BERT_API int32_t bertx_tokenize_batch(struct bert_ctx *ctx, int32_t n_threads, int32_t n_inputs, const char **texts,
                                       int32_t n_max, int32_t *ids, int32_t *n_tokens);
 
+/*
+ * Embedding index: an append-only matrix of rows x n_embd embeddings resident in the
+ * HBM of one of the context's GPUs, stored as f16, with a fused top-k search (what
+ * the reference's sample clients do on the host after bert_encode_batch,
+ * examples/sample_dylib.py:84-94).  Row ids are int32 insertion order from 0.
+ *
+ * bertx_index_create: an index of fixed capacity on GPU `slot`, or NULL after a
+ * message (bad slot, capacity < 1, allocation failure, a tokenizer-only context).
+ * Its width is the context's n_embd.  The index keeps only the device ordinal and
+ * the width: it may outlive the context.  Its buffers never move.
+ * bertx_index_clear sets the row count back to 0.
+ *
+ * bertx_index_add / _add_device: rows float[n][d] (host / device, the layout
+ * bertx_forward_device writes) are rounded to f16, nearest even, and appended; the
+ * id of the first new row is returned, or a negative error with nothing changed (-2:
+ * size + n > capacity).  bertx_index_rows: the stored values of rows first ..
+ * first + n - 1, the exact f16 values widened to f32, into out float[n][d].
+ *
+ * bertx_index_search / _search_device: for each of the B queries float[B][d], the k
+ * highest scores into scores float[B][k] with their row ids into ids int32[B][k].
+ * A score is the dot product of the f16-rounded query with the stored f16 row,
+ * accumulated in f32 (for the library's unit-length embeddings: the cosine, within
+ * 2^-10).  Scores descend; equal scores come by ascending id; with fewer than k
+ * rows the remaining slots are (-inf, -1).  1 <= k <= 128, B >= 1; anything else
+ * returns a negative error and leaves the outputs untouched.  The score of a
+ * (query, row) pair does not depend on the row's id, the row count or the other
+ * queries of the call, bit for bit.
+ *
+ * The device forms take device pointers on the index's GPU and a hipStream_t (NULL:
+ * the index's own stream); they are asynchronous, allocate nothing and never
+ * synchronise, so they can be captured into a HIP graph.  A search sees the rows
+ * added by the calls made before it.  Calls on one stream are ordered by the stream;
+ * on different streams each operation waits on the device for the previous one's
+ * completion event (a stream being captured waits for and records nothing outside
+ * its graph).  Host calls on one index are serialised; the caller's current HIP
+ * device is left as it was.
+ *
+ * The text forms encode with bert_encode_batch (the context's pooling mode) and
+ * then add or search; if the encoder refuses an input (longer than n_max_tokens)
+ * the whole call fails (-4) with nothing added.  The context's n_embd must be the
+ * index's width.
+ *
+ * Not provided: an index sharded over several GPUs, deleting rows, saving and
+ * loading, f32 storage.
+ */
+struct bertx_index;
+BERT_API struct bertx_index *bertx_index_create(struct bert_ctx *ctx, int32_t slot, int32_t capacity_rows);
+BERT_API void bertx_index_free(struct bertx_index *idx);
+BERT_API int32_t bertx_index_clear(struct bertx_index *idx);
+BERT_API int32_t bertx_index_size(struct bertx_index *idx);
+BERT_API int32_t bertx_index_capacity(struct bertx_index *idx);
+BERT_API int32_t bertx_index_dim(struct bertx_index *idx);
+BERT_API int32_t bertx_index_add(struct bertx_index *idx, const float *rows, int32_t n);
+BERT_API int32_t bertx_index_add_device(struct bertx_index *idx, const float *d_rows, int32_t n, void *stream);
+BERT_API int32_t bertx_index_rows(struct bertx_index *idx, int32_t first, int32_t n, float *out);
+BERT_API int32_t bertx_index_search(struct bertx_index *idx, const float *queries, int32_t B, int32_t k,
+                                    float *scores, int32_t *ids);
+BERT_API int32_t bertx_index_search_device(struct bertx_index *idx, const float *d_queries, int32_t B, int32_t k,
+                                           float *d_scores, int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_index_add_texts(struct bertx_index *idx, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                       const char **texts);
+BERT_API int32_t bertx_index_search_texts(struct bertx_index *idx, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                          const char **texts, int32_t k, float *scores, int32_t *ids);
+
+/*
+ * Search micro-benchmark (device 0, no context): an index of N random unit rows of
+ * width d, B random unit queries; average device time of `iters` calls of
+ * bertx_index_search_device for the k best, after 3 warm-up calls.
+ * bertx_bench_search_add_rate: rows per second of bertx_index_add_device filling an
+ * index of N rows from device rows, 65,536 rows per call (device time).
+ */
+BERT_API int32_t bertx_bench_search(int32_t d, int32_t N, int32_t B, int32_t k, int32_t iters, float *avg_us);
+BERT_API int32_t bertx_bench_search_add_rate(int32_t d, int32_t N, double *add_rows_per_s);
+
 BERT_API const char *bertx_version(void);
 
 #ifdef __cplusplus
