@@ -132,6 +132,13 @@ def load_lib(path=None):
         L.bertx_test_attention_f32.argtypes = [vp, vp, c_i32, c_i32, c_i32, c_i32, c_i32, vp, c_i32]
     except AttributeError:
         pass
+    try:   # (which attention kernel ran, the CLS gather hook: absent from older BERT_LIB builds)
+        L.bertx_test_attention_ran.restype = c_i32
+        L.bertx_test_attention_ran.argtypes = []
+        L.bertx_test_attention_cls_gather.restype = c_i32
+        L.bertx_test_attention_cls_gather.argtypes = [vp, vp, c_i32, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp]
+    except AttributeError:
+        pass
     try:   # (the embedding index: absent from older BERT_LIB builds)
         L.bertx_index_create.restype = vp
         L.bertx_index_create.argtypes = [vp, c_i32, c_i32]

@@ -657,6 +657,7 @@ __global__ __launch_bounds__(512, 4) void attention_pp_kernel(const h16 *__restr
 }
 
 thread_local int g_att_variant = 0;   // benches only (bertx_bench_attention), per calling thread
+thread_local int g_att_ran = -1;      // the AttKernel of the calling thread's last launch_attention
 
 // an A/B switch of the environment: on unless set to a value starting with 0
 static bool env_on(const char *name)
@@ -693,7 +694,9 @@ void launch_attention(const uint16_t *qkv_, const int32_t *cu, int32_t n_seqs, i
     const float sl2 = (1.0f / sqrtf((float)dh)) * 1.4426950408889634f;
     const h16 *qkv = (const h16 *)qkv_;
     h16 *out = (h16 *)out_;
-    switch (choose_attention(dh, max_len, g_att_variant)) {
+    const AttKernel kernel = choose_attention(dh, max_len, g_att_variant);
+    g_att_ran = (int)kernel;
+    switch (kernel) {
     case AttKernel::Short:
         if (n_items > 0) attention_short_kernel<<<n_items, 128, 0, s>>>(qkv, cu, d, n_head, sl2, out);
         break;

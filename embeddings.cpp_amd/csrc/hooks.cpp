@@ -498,68 +498,6 @@ extern "C" int32_t bertx_bench_search_add_rate(int32_t d, int32_t N, double *add
     return 0;
 }
 
-extern "C" int32_t bertx_test_attention(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head,
-                                        int32_t d, int32_t variant, uint16_t *out)
-{
-    using namespace emb;
-    if (n_seqs <= 0 || n_head <= 0 || d % n_head || hip_device_count() == 0) return -1;
-    const int dh = d / n_head;
-    if (dh != 64 && dh != 32) return -1;
-    int max_len = 0;
-    for (int i = 0; i < n_seqs; ++i) {
-        if (cu[i + 1] < cu[i]) return -1;
-        max_len = std::max(max_len, cu[i + 1] - cu[i]);
-    }
-    const size_t T = (size_t)cu[n_seqs];
-    DeviceGuard guard(0);
-    HIP_RC(guard.status());
-    HookBufs B;
-    const uint16_t *dq = (const uint16_t *)B.up(qkv, T * 3 * d * 2, (T + 64) * 3 * d * 2);
-    const int32_t *dcu = (const int32_t *)B.up(cu, ((size_t)n_seqs + 1) * 4, 0);
-    uint16_t *dout = (uint16_t *)B.up(nullptr, 0, (T + 64) * d * 2);
-    if (B.bad) return -1;
-    ScopedSet var(g_att_variant, variant);
-    // variant -1: the streaming kernel, reached by claiming a length past the LDS form
-    launch_attention(dq, dcu, n_seqs, variant == -1 ? ATT_LDS_MAX + 1 : max_len, n_head, d, dout, nullptr);
-    HIP_RC(hipDeviceSynchronize());
-    HIP_RC(hipMemcpy(out, dout, T * d * 2, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// The single-query attention of the pruned last layer (attention_cls.hip) on host
-// buffers: out f16 [n_seqs][d], row b = the attention output of token cu[b].
-extern "C" int32_t bertx_test_attention_cls(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head,
-                                            int32_t d, uint16_t *out)
-{
-    using namespace emb;
-    if (!qkv || !cu || !out || n_seqs <= 0 || n_head <= 0 || d % n_head || hip_device_count() == 0) return -1;
-    const int dh = d / n_head;
-    if (dh != 64 && dh != 32) return -1;
-    for (int i = 0; i < n_seqs; ++i)
-        if (cu[i + 1] < cu[i]) return -1;
-    const size_t T = (size_t)cu[n_seqs];
-    const int Mc = gemm_rows(n_seqs);
-    DeviceGuard guard(0);
-    HIP_RC(guard.status());
-    HookBufs B;
-    const uint16_t *dq = (const uint16_t *)B.up(qkv, T * 3 * d * 2, 0);
-    const int32_t *dcu = (const int32_t *)B.up(cu, ((size_t)n_seqs + 1) * 4, 0);
-    uint16_t *dout = (uint16_t *)B.up(nullptr, 0, (size_t)Mc * d * 2);
-    if (B.bad) return -1;
-    // the output starts as NaN bits, so the zeros of the padding rows are the kernel's
-    HIP_RC(hipMemset(dout, 0xff, (size_t)Mc * d * 2));
-    if (launch_attention_cls(dq, dcu, n_seqs, n_head, d, Mc, dout, nullptr, nullptr, nullptr, nullptr, nullptr) != 0)
-        return -1;
-    HIP_RC(hipGetLastError());
-    HIP_RC(hipDeviceSynchronize());
-    std::vector<uint16_t> h((size_t)Mc * d);
-    HIP_RC(hipMemcpy(h.data(), dout, h.size() * 2, hipMemcpyDeviceToHost));
-    for (size_t i = (size_t)n_seqs * d; i < h.size(); ++i)
-        if (h[i] != 0) return -5;   // a padding row the kernel did not clear
-    std::memcpy(out, h.data(), (size_t)n_seqs * d * 2);
-    return 0;
-}
-
 // ---------------------------------------------------------------------------
 // Row-kernel parity hooks (norm.hip, f32.hip, table_read.h): one launch over host
 // buffers.  The caller's output buffers (out_rows rows, at least the rows the
@@ -756,4 +694,109 @@ extern "C" int32_t bertx_test_attention_f32(const float *qkv, const int32_t *cu,
     if (const int rc = hook_finish()) return rc;
     HIP_RC(hipMemcpy(out, dout, (size_t)out_rows * d * 4, hipMemcpyDeviceToHost));
     return lrc;
+}
+
+// ---------------------------------------------------------------------------
+// The f16 attention kernels (attention.hip, attention_cls.hip).  Every output
+// buffer starts as NaN bits (0xffff), so a row the kernel did not write, and a
+// write past the rows it owns, both show.
+// ---------------------------------------------------------------------------
+extern "C" int32_t bertx_test_attention(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head,
+                                        int32_t d, int32_t variant, uint16_t *out)
+{
+    using namespace emb;
+    if (!qkv || !cu || !out || n_seqs <= 0 || n_head <= 0 || d % n_head || hip_device_count() == 0) return -1;
+    const int dh = d / n_head;
+    if (dh != 64 && dh != 32) return -1;
+    int max_len = 0;
+    for (int i = 0; i < n_seqs; ++i) {
+        if (cu[i + 1] < cu[i]) return -1;
+        max_len = std::max(max_len, cu[i + 1] - cu[i]);
+    }
+    const size_t T = (size_t)cu[n_seqs];
+    // Rows behind the T packed ones.  qkv: the widest over-read of any kernel
+    // launched here is the streaming kernel's, which loads the Q rows of all ATT_QT
+    // queries of a tile that holds one query of the last sentence before it masks
+    // them, so up to row T + ATT_QT - 2; every other kernel clamps its rows to the
+    // sentence (min(row, len - 1)).  The forward's workspace has GEMM_BM + 256 spare
+    // rows for the same read.  out: as many sentinel rows, which no kernel may touch.
+    constexpr size_t PAD = ATT_QT;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const uint16_t *dq = (const uint16_t *)B.up(qkv, T * 3 * d * 2, (T + PAD) * 3 * d * 2);
+    const int32_t *dcu = (const int32_t *)B.up(cu, ((size_t)n_seqs + 1) * 4, 0);
+    uint16_t *dout = (uint16_t *)B.up(nullptr, 0, (T + PAD) * d * 2);
+    if (B.bad) return -1;
+    HIP_RC(hipMemset(dout, 0xff, (T + PAD) * d * 2));
+    ScopedSet var(g_att_variant, variant);
+    // variant -1: the streaming kernel, reached by claiming a length past the LDS form
+    launch_attention(dq, dcu, n_seqs, variant == -1 ? std::max(max_len, ATT_LDS_MAX + 1) : max_len, n_head, d, dout,
+                     nullptr);
+    if (const int rc = hook_finish()) return rc;
+    HIP_RC(hipMemcpy(out, dout, T * d * 2, hipMemcpyDeviceToHost));
+    std::vector<uint16_t> pad(PAD * d);
+    HIP_RC(hipMemcpy(pad.data(), dout + T * d, pad.size() * 2, hipMemcpyDeviceToHost));
+    for (const uint16_t v : pad)
+        if (v != 0xffff) return -5;   // a store past the last sentence
+    return 0;
+}
+
+extern "C" int32_t bertx_test_attention_ran(void) { return emb::g_att_ran; }
+
+extern "C" int32_t bertx_test_attention_cls_gather(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs,
+                                                   int32_t n_head, int32_t d, int32_t Mc, uint16_t *out,
+                                                   const uint16_t *z, const float *st, uint16_t *zc, float *stc)
+{
+    using namespace emb;
+    if (!qkv || !cu || !out || n_seqs <= 0 || Mc < n_seqs || n_head <= 0 || d % n_head || hip_device_count() == 0)
+        return -1;
+    if ((z != nullptr) != (st != nullptr) || (z != nullptr) != (zc != nullptr) || (z != nullptr) != (stc != nullptr))
+        return -1;
+    const int dh = d / n_head;
+    if (dh != 64 && dh != 32) return -1;
+    for (int i = 0; i < n_seqs; ++i)
+        if (cu[i + 1] < cu[i]) return -1;
+    const size_t T = (size_t)cu[n_seqs];
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const uint16_t *dq = (const uint16_t *)B.up(qkv, T * 3 * d * 2, 0);
+    const int32_t *dcu = (const int32_t *)B.up(cu, ((size_t)n_seqs + 1) * 4, 0);
+    uint16_t *dout = (uint16_t *)B.up(nullptr, 0, (size_t)Mc * d * 2);
+    const uint16_t *dz = z ? (const uint16_t *)B.up(z, T * d * 2, 0) : nullptr;
+    const float2 *dst = z ? (const float2 *)B.up(st, T * 8, 0) : nullptr;
+    uint16_t *dzc = z ? (uint16_t *)B.up(nullptr, 0, (size_t)Mc * d * 2) : nullptr;
+    float2 *dstc = z ? (float2 *)B.up(nullptr, 0, (size_t)Mc * 8) : nullptr;
+    if (B.bad) return -1;
+    // the compact buffers start as NaN bits, so the zeros of the padding rows are the kernel's
+    HIP_RC(hipMemset(dout, 0xff, (size_t)Mc * d * 2));
+    if (z) {
+        HIP_RC(hipMemset(dzc, 0xff, (size_t)Mc * d * 2));
+        HIP_RC(hipMemset(dstc, 0xff, (size_t)Mc * 8));
+    }
+    if (launch_attention_cls(dq, dcu, n_seqs, n_head, d, Mc, dout, dz, dst, dzc, dstc, nullptr) != 0) return -1;
+    if (const int rc = hook_finish()) return rc;
+    HIP_RC(hipMemcpy(out, dout, (size_t)Mc * d * 2, hipMemcpyDeviceToHost));
+    if (z) {
+        HIP_RC(hipMemcpy(zc, dzc, (size_t)Mc * d * 2, hipMemcpyDeviceToHost));
+        HIP_RC(hipMemcpy(stc, dstc, (size_t)Mc * 8, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+extern "C" int32_t bertx_test_attention_cls(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head,
+                                            int32_t d, uint16_t *out)
+{
+    using namespace emb;
+    if (!out || n_seqs <= 0 || d <= 0) return -1;
+    const int Mc = gemm_rows(n_seqs);
+    std::vector<uint16_t> h((size_t)Mc * d);
+    if (const int rc = bertx_test_attention_cls_gather(qkv, cu, n_seqs, n_head, d, Mc, h.data(), nullptr, nullptr,
+                                                       nullptr, nullptr))
+        return rc;
+    for (size_t i = (size_t)n_seqs * d; i < h.size(); ++i)
+        if (h[i] != 0) return -5;   // a padding row the kernel did not clear
+    std::memcpy(out, h.data(), (size_t)n_seqs * d * 2);
+    return 0;
 }

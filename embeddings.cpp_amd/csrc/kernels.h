@@ -126,6 +126,9 @@ int launch_ln_stats(const float2 *part, int32_t G, int32_t stride, int32_t rows,
 
 // Benches only: attention kernel variant (bertx_bench_attention).
 extern thread_local int g_att_variant;
+// The kernel the calling thread's last launch_attention chose (attention.hip AttKernel:
+// 0 short, 1 pp, 2 lds3, 3 lds<32>, 4 streaming; -1 before the first launch).
+extern thread_local int g_att_ran;
 
 // Per (sentence, head) softmax(Q K^T / sqrt(dh)) V over the sentence's own keys.
 void launch_attention(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t max_len, int32_t n_head,

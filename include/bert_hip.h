@@ -244,10 +244,21 @@ BERT_API int32_t bertx_bench_attention(int32_t n_seqs, int32_t len, int32_t n_he
  * QKV GEMM writes it (packed tokens of n_seqs sentences, cu[n_seqs + 1] the
  * token offsets), out f16 [T][d] = per (sentence, head) softmax(Q K^T / sqrt(dh)) V
  * over the sentence's own keys (bert.cpp:1018-1036).  variant as
- * bertx_bench_attention; -1 = the streaming kernel (sentences > 512).
+ * bertx_bench_attention; -1 = the streaming kernel (sentences > 512), which a batch
+ * holding such a sentence takes by itself.  The device output starts as NaN bits
+ * (0xffff) with ATT_QT spare rows behind it, so a row the kernel left unwritten comes
+ * back as NaN.  Returns 0; -1 bad arguments; -3 the runtime refused the launch; -4
+ * the synchronise after it reported an error; -5 a spare row behind row T was
+ * written.
  */
 BERT_API int32_t bertx_test_attention(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head,
                                       int32_t d, int32_t variant, uint16_t *out);
+
+/* The kernel the calling thread's last attention launch ran: 0 attention_short,
+ * 1 attention_pp, 2 attention_lds3, 3 attention_lds<32>, 4 the streaming kernel
+ * (-1: none yet).  BERT_ATT_PP=0 / BERT_ATT_SHORT=0 in the environment take variant
+ * 0 off the first two. */
+BERT_API int32_t bertx_test_attention_ran(void);
 
 /*
  * Parity hook of the pruned last layer's attention (CLS pooling; host buffers,
@@ -258,6 +269,18 @@ BERT_API int32_t bertx_test_attention(const uint16_t *qkv, const int32_t *cu, in
  */
 BERT_API int32_t bertx_test_attention_cls(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head,
                                           int32_t d, uint16_t *out);
+
+/*
+ * The same launch with its residual gather, on Mc >= n_seqs compact rows: out f16
+ * [Mc][d] comes back whole.  With z f16 [T][d] and st f32 [T][2] (all four of z, st,
+ * zc, stc, or none): zc f16 [Mc][d] and stc f32 [Mc][2] come back whole too, zc[b] =
+ * z[cu[b]], stc[b] = st[cu[b]].  All three device buffers start as NaN bits (0xff
+ * bytes), so the zeros of rows n_seqs <= row < Mc are the kernel's.  Returns as
+ * bertx_test_attention (no -5: the caller sees every row).
+ */
+BERT_API int32_t bertx_test_attention_cls_gather(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs,
+                                                 int32_t n_head, int32_t d, int32_t Mc, uint16_t *out,
+                                                 const uint16_t *z, const float *st, uint16_t *zc, float *stc);
 
 /*
  * Parity hooks of the memory-bound row kernels (norm.hip, f32.hip and their table
