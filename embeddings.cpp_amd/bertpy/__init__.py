@@ -89,6 +89,17 @@ def load_lib(path=None):
         L.bertx_test_gemm_fold.argtypes = [c_i32, c_i32, c_i32, vp, vp, c_i32, vp, vp, vp, vp, c_i32, vp, vp, vp, c_i32]
     except AttributeError:
         pass
+    try:   # (the launched-row-count forms: absent from older BERT_LIB builds)
+        L.bertx_test_gemm_rows.restype = c_i32
+        L.bertx_test_gemm_rows.argtypes = ([c_i32, c_i32, c_i32, vp, vp, c_i32, c_i32, vp, vp, vp, vp, c_i32] +
+                                           [vp] * 5 + [c_i32, vp, vp, vp, c_i32])
+        L.bertx_test_gemm_fold_rows.restype = c_i32
+        L.bertx_test_gemm_fold_rows.argtypes = [c_i32, c_i32, c_i32, vp, vp, c_i32, c_i32, vp, vp, vp, vp, c_i32, vp, vp,
+                                                vp, c_i32]
+        L.bertx_test_cu_count.restype = c_i32
+        L.bertx_test_cu_count.argtypes = []
+    except AttributeError:
+        pass
     L.bertx_test_gemm_ran.restype = c_i32
     L.bertx_test_gemm_ran.argtypes = []
     L.bertx_test_gemm_f32.restype = c_i32

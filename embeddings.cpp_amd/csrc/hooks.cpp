@@ -7,6 +7,7 @@
 #include "repack.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 namespace emb {
@@ -26,8 +27,66 @@ struct HookBufs {
         if (h && bytes && hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) bad = true;
         return d;
     }
+    // the same with every byte the host does not give set to 0xFF (NaN bits): a
+    // buffer the kernel writes, so an element it left alone and a store behind the
+    // rows it owns both show
+    void *up_ff(const void *h, size_t bytes, size_t alloc)
+    {
+        void *d = up(nullptr, 0, std::max(alloc, bytes));
+        if (!d) return nullptr;
+        if (hipMemset(d, 0xff, std::max<size_t>(std::max(alloc, bytes), 16)) != hipSuccess) bad = true;
+        if (h && bytes && hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) bad = true;
+        return d;
+    }
     ~HookBufs() { for (void *d : p) (void)hipFree(d); }
 };
+
+// Rows behind the launched ones of every buffer a GEMM hook's kernels write (one
+// 64-row tile), 0xFF before the launch and checked after it.
+constexpr int HOOK_GUARD = 64;
+
+// 0 when `bytes` device bytes at d still hold 0xFF, -5 when one was written, -1 on a copy error
+int guard_intact(const void *d, size_t bytes)
+{
+    std::vector<uint8_t> h(bytes);
+    if (hipMemcpy(h.data(), d, bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    for (const uint8_t v : h)
+        if (v != 0xff) return -5;
+    return 0;
+}
+
+// Pad rows of a hook's inputs (rows M .. rows - 1, computed and stored as the
+// forward's are): finite, non-zero, magnitudes in [0.25, 1.25) with both signs.
+struct PadFill {
+    uint32_t st = 2463534242u;
+    float next()
+    {
+        st = st * 1664525u + 1013904223u;
+        const float v = 0.25f + (float)(st >> 8) / 16777216.0f;
+        return (st & 0x80u) ? -v : v;
+    }
+};
+
+// f16 rows [M][cols] of the host (may be null with M == 0) -> [rows][cols] with the pad rows filled
+std::vector<uint16_t> padded_h16(const uint16_t *h, int M, int rows, int cols, PadFill &pf)
+{
+    std::vector<uint16_t> v((size_t)rows * cols);
+    if (h && M > 0) std::memcpy(v.data(), h, (size_t)M * cols * 2);
+    for (size_t i = (size_t)M * cols; i < v.size(); ++i) v[i] = f32_to_f16(pf.next());
+    return v;
+}
+
+// (mean, 1/sigma) pairs [M] -> [rows], pad rows (mean, 1/sigma) with 1/sigma > 0
+std::vector<float> padded_stats(const float *h, int M, int rows, PadFill &pf)
+{
+    std::vector<float> v((size_t)rows * 2);
+    std::memcpy(v.data(), h, (size_t)M * 8);
+    for (int r = M; r < rows; ++r) {
+        v[2 * (size_t)r] = pf.next();
+        v[2 * (size_t)r + 1] = 0.5f + std::fabs(pf.next());
+    }
+    return v;
+}
 
 // The two events of a device-timed bench loop.
 struct EventPair {
@@ -88,16 +147,47 @@ extern "C" int32_t bertx_test_gemm(int32_t fmt, int32_t N, int32_t K, const void
                               nullptr, nullptr, nullptr, nullptr, (uint16_t *)out, nullptr, cfg);
 }
 
+extern "C" int32_t bertx_test_cu_count(void)
+{
+    using namespace emb;
+    if (hip_device_count() == 0) return -1;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    return device_cu_count();
+}
+
+// the M-row forms: the launch padded to the 256-row tile, the first M rows returned
 extern "C" int32_t bertx_test_gemm_fold(int32_t fmt, int32_t N, int32_t K, const void *w_rows, const float *bias,
                                         int32_t M, const uint16_t *x, const float *part, const float *in_g,
                                         const float *in_b, int32_t epi, uint16_t *out, float *st_out,
                                         float *st_kernel, int32_t cfg)
 {
     using namespace emb;
-    if (!fmt_valid(fmt) || K % 64 || N % 32 || M <= 0 || (epi != 0 && epi != 1) || !part || !in_g || !in_b ||
-        hip_device_count() == 0)
+    if (M <= 0 || N <= 0 || !out) return -1;
+    const int rows = (int)align_up((size_t)M, GEMM_BM);
+    std::vector<uint16_t> o((size_t)rows * N);
+    std::vector<float> s((size_t)rows * 2), sk((size_t)rows * 2);
+    const int rc = bertx_test_gemm_fold_rows(fmt, N, K, w_rows, bias, M, rows, x, part, in_g, in_b, epi, o.data(),
+                                             s.data(), st_kernel ? sk.data() : nullptr, cfg);
+    if (rc != 0) return rc;
+    std::memcpy(out, o.data(), (size_t)M * N * 2);
+    if (st_out) std::memcpy(st_out, s.data(), (size_t)M * 8);
+    if (st_kernel) std::memcpy(st_kernel, sk.data(), (size_t)M * 8);
+    return 0;
+}
+
+extern "C" int32_t bertx_test_gemm_fold_rows(int32_t fmt, int32_t N, int32_t K, const void *w_rows,
+                                             const float *bias, int32_t M, int32_t rows, const uint16_t *x,
+                                             const float *part, const float *in_g, const float *in_b, int32_t epi,
+                                             uint16_t *out, float *st_out, float *st_kernel, int32_t cfg)
+{
+    using namespace emb;
+    if (!fmt_valid(fmt) || K % 64 || N % 32 || M <= 0 || rows < M || rows % 64 || (epi != 0 && epi != 1) || !part ||
+        !in_g || !in_b || !x || !out || hip_device_count() == 0)
         return -1;
-    const int Mp = (int)align_up((size_t)M, GEMM_BM), G = K / 32;   // (X columns: K for every format)
+    const int Mp = rows, G = K / 32;   // (X columns: K for every format)
+    const int PS = Mp + HOOK_GUARD;     // rows of the guarded [row] buffers
+    PadFill pf;
     DeviceGuard guard(0);
     HIP_RC(guard.status());
     HookBufs B;
@@ -111,29 +201,41 @@ extern "C" int32_t bertx_test_gemm_fold(int32_t fmt, int32_t N, int32_t K, const
     fold_ln({&t}, {&hb}, hg, hbt, c1, c2, fmt == FMT_F32);
     LnFold ln;
     // partials [G][M] on the host -> [G][Mp] on the device (stride Mp)
-    std::vector<float> hp((size_t)G * Mp * 2, 0.f);
-    for (int g = 0; g < G; ++g) std::memcpy(&hp[(size_t)g * Mp * 2], part + (size_t)g * M * 2, (size_t)M * 8);
+    // (the pad rows: a sum and a positive sum of squared deviations)
+    std::vector<float> hp((size_t)G * Mp * 2);
+    for (int g = 0; g < G; ++g) {
+        float *row = &hp[(size_t)g * Mp * 2];
+        std::memcpy(row, part + (size_t)g * M * 2, (size_t)M * 8);
+        for (int r = M; r < Mp; ++r) {
+            row[2 * r] = 32.0f * pf.next();
+            row[2 * r + 1] = 16.0f + 16.0f * std::fabs(pf.next());
+        }
+    }
     ln.in_part = (const float2 *)B.up(hp.data(), hp.size() * 4, 0);
     ln.in_part_stride = Mp;
     ln.in_G = G;
-    ln.st_out = (float2 *)B.up(nullptr, 0, (size_t)Mp * 8);
+    ln.st_out = (float2 *)B.up_ff(nullptr, 0, (size_t)PS * 8);
     ln.c1 = (const float *)B.up(c1.bytes.data(), c1.bytes.size(), 0);
     const float *dbias = (const float *)B.up(c2.bytes.data(), c2.bytes.size(), 0);
-    void *dx = B.up(x, (size_t)M * K * 2, (size_t)Mp * K * 2);
-    void *dout = B.up(nullptr, 0, (size_t)Mp * N * 2);
+    const std::vector<uint16_t> hx = padded_h16(x, M, Mp, K, pf);
+    void *dx = B.up(hx.data(), hx.size() * 2, 0);
+    void *dout = B.up_ff(nullptr, 0, (size_t)PS * N * 2);
     if (B.bad) return -1;
     const int rc = launch_gemm(W, (const uint16_t *)dx, Mp, dbias, epi, nullptr, dout, nullptr, ln);
     if (rc != 0) return rc;
     HIP_RC(hipGetLastError());
     HIP_RC(hipDeviceSynchronize());
-    HIP_RC(hipMemcpy(out, dout, (size_t)M * N * 2, hipMemcpyDeviceToHost));
-    if (st_out) HIP_RC(hipMemcpy(st_out, ln.st_out, (size_t)M * 8, hipMemcpyDeviceToHost));
+    HIP_RC(hipMemcpy(out, dout, (size_t)Mp * N * 2, hipMemcpyDeviceToHost));
+    if (st_out) HIP_RC(hipMemcpy(st_out, ln.st_out, (size_t)Mp * 8, hipMemcpyDeviceToHost));
+    if (const int g = guard_intact((const uint16_t *)dout + (size_t)Mp * N, (size_t)HOOK_GUARD * N * 2)) return g;
+    if (const int g = guard_intact(ln.st_out + Mp, (size_t)HOOK_GUARD * 8)) return g;
     if (st_kernel) {
         // the same partials through the statistics kernel (the launch form)
-        float2 *dk = (float2 *)B.up(nullptr, 0, (size_t)Mp * 8);
+        float2 *dk = (float2 *)B.up_ff(nullptr, 0, (size_t)PS * 8);
         if (B.bad || launch_ln_stats(ln.in_part, G, Mp, Mp, 32 * G, dk, nullptr) != 0) return -1;
         HIP_RC(hipDeviceSynchronize());
-        HIP_RC(hipMemcpy(st_kernel, dk, (size_t)M * 8, hipMemcpyDeviceToHost));
+        HIP_RC(hipMemcpy(st_kernel, dk, (size_t)Mp * 8, hipMemcpyDeviceToHost));
+        if (const int g = guard_intact(dk + Mp, (size_t)HOOK_GUARD * 8)) return g;
     }
     return 0;
 }
@@ -145,12 +247,36 @@ extern "C" int32_t bertx_test_gemm_ln(int32_t fmt, int32_t N, int32_t K, const v
                                       float *st_out, int32_t cfg)
 {
     using namespace emb;
-    if (!fmt_valid(fmt) || K % 64 || N % 32 || M <= 0 || epi < 0 || epi > 2 || hip_device_count() == 0) return -1;
+    if (M <= 0 || N <= 0 || !out) return -1;
+    const int rows = (int)align_up((size_t)M, GEMM_BM);
+    std::vector<uint16_t> o((size_t)rows * N);
+    std::vector<float> s((size_t)rows * 2);
+    const int rc = bertx_test_gemm_rows(fmt, N, K, w_rows, bias, M, rows, x, in_stats, in_g, in_b, epi, res, res_stats,
+                                        res_g, res_b, g_next, 0, o.data(), st_out ? s.data() : nullptr, nullptr, cfg);
+    if (rc != 0) return rc;
+    std::memcpy(out, o.data(), (size_t)M * N * 2);
+    if (st_out && g_next) std::memcpy(st_out, s.data(), (size_t)M * 8);
+    return 0;
+}
+
+extern "C" int32_t bertx_test_gemm_rows(int32_t fmt, int32_t N, int32_t K, const void *w_rows, const float *bias,
+                                        int32_t M, int32_t rows, const uint16_t *x, const float *in_stats,
+                                        const float *in_g, const float *in_b, int32_t epi, const uint16_t *res,
+                                        const float *res_stats, const float *res_g, const float *res_b,
+                                        const float *g_next, int32_t out_of_place, uint16_t *out, float *st_out,
+                                        float *part_out, int32_t cfg)
+{
+    using namespace emb;
+    if (!fmt_valid(fmt) || K % 64 || N % 32 || M <= 0 || rows < M || rows % 64 || epi < 0 || epi > 2 || !x || !out ||
+        hip_device_count() == 0)
+        return -1;
     if (g_next && N > 1024) return -1;   // the statistics kernel combines at most 32 partials per row
     if ((in_stats && (!in_g || !in_b || epi == EPI_BIAS_RES)) || (epi == EPI_BIAS_RES && !res) ||
         (res_stats && (!res_g || !res_b)) || (g_next && epi != EPI_BIAS_RES))
         return -1;
-    const int Mp = (int)align_up((size_t)M, GEMM_BM);
+    const int Mp = rows;
+    const int PS = Mp + HOOK_GUARD;   // rows of the guarded [row] buffers (and the partials' stride)
+    PadFill pf;
     DeviceGuard guard(0);
     HIP_RC(guard.status());
     HookBufs B;
@@ -164,39 +290,66 @@ extern "C" int32_t bertx_test_gemm_ln(int32_t fmt, int32_t N, int32_t K, const v
         const HostTensor hb = vec_tensor(bias, N), hg = vec_tensor(in_g, K), hbt = vec_tensor(in_b, K);
         Piece c1, c2;
         fold_ln({&t}, {&hb}, hg, hbt, c1, c2, fmt == FMT_F32);
-        ln.in_stats = (const float2 *)B.up(in_stats, (size_t)M * 8, (size_t)Mp * 8);
+        const std::vector<float> hs = padded_stats(in_stats, M, Mp, pf);
+        ln.in_stats = (const float2 *)B.up(hs.data(), hs.size() * 4, 0);
         ln.c1 = (const float *)B.up(c1.bytes.data(), c1.bytes.size(), 0);
         dbias = (const float *)B.up(c2.bytes.data(), c2.bytes.size(), 0);
     }
-    void *dx = B.up(x, (size_t)M * K * 2, (size_t)Mp * K * 2);
-    void *dout = B.up(nullptr, 0, (size_t)Mp * N * 2);
+    const std::vector<uint16_t> hx = padded_h16(x, M, Mp, K, pf);
+    void *dx = B.up(hx.data(), hx.size() * 2, 0);
+    void *dout = nullptr;
+    const void *dres = nullptr;
     float2 *dst = nullptr;
+    const int NG = N / 32;
     if (epi == EPI_BIAS_RES) {
-        B.up(nullptr, 0, 0);
-        void *dr = B.up(res, (size_t)M * N * 2, (size_t)Mp * N * 2);
-        dout = dr;   // in place, as the forward runs it
+        const std::vector<uint16_t> hr = padded_h16(res, M, Mp, N, pf);
+        if (out_of_place) {
+            dres = B.up(hr.data(), hr.size() * 2, 0);
+            dout = B.up_ff(nullptr, 0, (size_t)PS * N * 2);
+        } else {
+            // in place, as the forward runs it
+            dout = B.up_ff(hr.data(), hr.size() * 2, (size_t)PS * N * 2);
+            dres = dout;
+        }
         if (res_stats) {
-            ln.res_stats = (const float2 *)B.up(res_stats, (size_t)M * 8, (size_t)Mp * 8);
+            const std::vector<float> hs = padded_stats(res_stats, M, Mp, pf);
+            ln.res_stats = (const float2 *)B.up(hs.data(), hs.size() * 4, 0);
             ln.res_g = (const float *)B.up(res_g, (size_t)N * 4, 0);
             ln.res_b = (const float *)B.up(res_b, (size_t)N * 4, 0);
         }
         if (g_next) {
             ln.g_next = (const float *)B.up(g_next, (size_t)N * 4, 0);
-            ln.part = (float2 *)B.up(nullptr, 0, (size_t)Mp * (N / 32) * 8);
-            ln.part_stride = Mp;
-            dst = (float2 *)B.up(nullptr, 0, (size_t)Mp * 8);
+            ln.part = (float2 *)B.up_ff(nullptr, 0, (size_t)PS * NG * 8);
+            ln.part_stride = PS;
+            dst = (float2 *)B.up_ff(nullptr, 0, (size_t)PS * 8);
         }
+    } else {
+        dout = B.up_ff(nullptr, 0, (size_t)PS * N * 2);
     }
     if (B.bad) return -1;
     ScopedSet tile(g_gemm_cfg, cfg);
-    const int rc = launch_gemm(W, (const uint16_t *)dx, Mp, dbias, epi, dout, dout, nullptr, ln);
+    const int rc = launch_gemm(W, (const uint16_t *)dx, Mp, dbias, epi, dres, dout, nullptr, ln);
     if (rc != 0) return rc;
-    if (dst && launch_ln_stats(ln.part, N / 32, Mp, Mp, N, dst, nullptr) != 0) return -1;
     HIP_RC(hipGetLastError());
     HIP_RC(hipDeviceSynchronize());
-    HIP_RC(hipMemcpy(out, dout, (size_t)M * N * 2, hipMemcpyDeviceToHost));
-    if (dst && st_out) HIP_RC(hipMemcpy(st_out, dst, (size_t)M * 8, hipMemcpyDeviceToHost));
-    return 0;
+    if (dst) {
+        // the partials as the epilogue left them: every group's guard rows, then the copy
+        std::vector<float> hp((size_t)PS * NG * 2);
+        HIP_RC(hipMemcpy(hp.data(), ln.part, hp.size() * 4, hipMemcpyDeviceToHost));
+        for (int g = 0; g < NG; ++g) {
+            const uint8_t *gb = (const uint8_t *)&hp[((size_t)g * PS + Mp) * 2];
+            for (size_t i = 0; i < (size_t)HOOK_GUARD * 8; ++i)
+                if (gb[i] != 0xff) return -5;
+            if (part_out) std::memcpy(part_out + (size_t)g * Mp * 2, &hp[(size_t)g * PS * 2], (size_t)Mp * 8);
+        }
+        if (launch_ln_stats(ln.part, NG, PS, Mp, N, dst, nullptr) != 0) return -1;
+        HIP_RC(hipGetLastError());
+        HIP_RC(hipDeviceSynchronize());
+        if (st_out) HIP_RC(hipMemcpy(st_out, dst, (size_t)Mp * 8, hipMemcpyDeviceToHost));
+        if (const int g = guard_intact(dst + Mp, (size_t)HOOK_GUARD * 8)) return g;
+    }
+    HIP_RC(hipMemcpy(out, dout, (size_t)Mp * N * 2, hipMemcpyDeviceToHost));
+    return guard_intact((const uint16_t *)dout + (size_t)Mp * N, (size_t)HOOK_GUARD * N * 2);
 }
 
 extern "C" int32_t bertx_test_gemm_ran(void) { return emb::g_gemm_ran; }

@@ -187,6 +187,39 @@ BERT_API int32_t bertx_test_gemm_fold(int32_t fmt, int32_t N, int32_t K, const v
                                       const float *in_b, int32_t epi, uint16_t *out, float *st_out, float *st_kernel,
                                       int32_t cfg);
 
+/*
+ * The two hooks above with the launched row count given: `rows` (a multiple of 64,
+ * rows >= M) is the M that launch_gemm gets, so the 64-, 128-, 192- and 320-row
+ * launches of the small-batch forward and the tile fallbacks can be reached
+ * (bertx_test_gemm_ln and bertx_test_gemm_fold are these with rows = M rounded up
+ * to 256, returning the first M rows).  Rows M .. rows-1 of x, res, the statistics
+ * and the partials are filled by the hook with finite non-zero values and are
+ * computed and stored like any other row.  out [rows][N], st_out [rows] (and
+ * st_kernel [rows]) come back whole; every buffer the kernels write starts as 0xFF
+ * bytes (NaN bits; the in-place residual as the residual), so an element left
+ * unwritten shows, and carries 64 guard rows behind row `rows`.
+ * bertx_test_gemm_rows: part_out (or NULL), float pairs [N/32][rows]: the per-group
+ * (sum, squared deviations from the group mean) the g_next form's epilogue wrote;
+ * out_of_place != 0 gives the epi-2 forms an output buffer of their own (res is
+ * read, out is written), 0 runs them in place as the forward does.
+ * Return 0; -1 bad arguments or a runtime error; -2 (fold) no fold form for the
+ * shape; -5 a guard row behind row `rows` of a written buffer was stored to.
+ */
+BERT_API int32_t bertx_test_gemm_rows(int32_t fmt, int32_t N, int32_t K, const void *w_rows, const float *bias,
+                                      int32_t M, int32_t rows, const uint16_t *x, const float *in_stats,
+                                      const float *in_g, const float *in_b, int32_t epi, const uint16_t *res,
+                                      const float *res_stats, const float *res_g, const float *res_b,
+                                      const float *g_next, int32_t out_of_place, uint16_t *out, float *st_out,
+                                      float *part_out, int32_t cfg);
+BERT_API int32_t bertx_test_gemm_fold_rows(int32_t fmt, int32_t N, int32_t K, const void *w_rows,
+                                           const float *bias, int32_t M, int32_t rows, const uint16_t *x,
+                                           const float *part, const float *in_g, const float *in_b, int32_t epi,
+                                           uint16_t *out, float *st_out, float *st_kernel, int32_t cfg);
+
+/* Compute units of device 0 as the GEMM launch code counts them (tile heuristic,
+ * persistent grids); -1 without a device. */
+BERT_API int32_t bertx_test_cu_count(void);
+
 /* The tile config the calling thread's last GEMM launch dispatched (after the
  * fallbacks above), so a test can assert which kernel it exercised. */
 BERT_API int32_t bertx_test_gemm_ran(void);

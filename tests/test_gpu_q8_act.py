@@ -21,6 +21,7 @@ import pytest
 
 import bertpy
 import oracle_lib
+from gemm_refs import parse_blocks
 from test_gpu_kernels import BLOCK, era_gelu_table, weight_rows
 
 pytestmark = pytest.mark.gpu
@@ -55,24 +56,6 @@ def quantize_act_np(X, kind):
         return q.reshape(M, K), d.astype(np.float16).astype(np.float32), None
     s = q.sum(axis=2, dtype=np.int32).astype(np.float32) * d
     return q.reshape(M, K), d, s.astype(np.float32)
-
-
-def parse_blocks(fmt, wb, N, K):
-    """The file blocks of a weight [N][K]: integer values wq [N][K/32][32] as the block dot
-    uses them (nibble - 8, nibble, byte), f16 scales wd and mins wm as float64 [N][K/32]."""
-    nb = K // 32
-    raw = np.frombuffer(wb, np.uint8).reshape(N, nb, BLOCK[fmt])
-    wd = raw[:, :, 0:2].copy().view(np.float16)[:, :, 0].astype(np.float64)
-    wm = np.zeros((N, nb))
-    if fmt == 8:
-        wq = raw[:, :, 2:].copy().view(np.int8).astype(np.int64)
-    else:
-        o = 4 if fmt == 3 else 2
-        if fmt == 3:
-            wm = raw[:, :, 2:4].copy().view(np.float16)[:, :, 0].astype(np.float64)
-        nib = raw[:, :, o:]
-        wq = np.concatenate([nib & 15, nib >> 4], axis=2).astype(np.int64) - (8 if fmt == 2 else 0)
-    return wq, wd, wm
 
 
 def block_terms(fmt, wb, N, K, X):
