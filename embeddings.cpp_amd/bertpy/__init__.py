@@ -178,6 +178,28 @@ def load_lib(path=None):
         L.bertx_bench_search_add_rate.argtypes = [c_i32, c_i32, ctypes.POINTER(ctypes.c_double)]
     except AttributeError:
         pass
+    try:   # (cross-encoder reranking: absent from older BERT_LIB builds)
+        L.bertx_convert_hf_head.restype = c_i32
+        L.bertx_convert_hf_head.argtypes = [ctypes.c_char_p, ctypes.c_char_p, c_i32]
+        L.bertx_n_labels.restype = c_i32
+        L.bertx_n_labels.argtypes = [vp]
+        L.bertx_tokenize_pair.restype = c_i32
+        L.bertx_tokenize_pair.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, c_i32, vp, vp, c_i32p, c_i32]
+        L.bertx_forward_device_ex.restype = c_i32
+        L.bertx_forward_device_ex.argtypes = [vp, c_i32, vp, vp, vp, c_i32, c_i32, c_i32, c_i32, vp, vp]
+        L.bertx_score_ids.restype = c_i32
+        L.bertx_score_ids.argtypes = [vp, c_i32, vp, vp, vp, vp]
+        L.bertx_score_pairs.restype = c_i32
+        L.bertx_score_pairs.argtypes = [vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p),
+                                        ctypes.POINTER(ctypes.c_char_p), c_i32, vp]
+        L.bertx_rerank.restype = c_i32
+        L.bertx_rerank.argtypes = [vp, c_i32, ctypes.c_char_p, c_i32, ctypes.POINTER(ctypes.c_char_p), c_i32, vp]
+        L.bertx_test_head.restype = c_i32
+        L.bertx_test_head.argtypes = [vp, c_i32, c_i32, vp, vp, vp, vp, c_i32, vp, c_i32]
+        L.bertx_test_embed_ln_types.restype = c_i32
+        L.bertx_test_embed_ln_types.argtypes = [c_i32] * 7 + [vp] * 8 + [c_i32, c_i32, vp, vp, c_i32]
+    except AttributeError:
+        pass
     L.bertx_bench_gemm.restype = c_i32
     L.bertx_bench_gemm.argtypes = [c_i32] * 7 + [c_f32p]
     L.bertx_bench_attention.restype = c_i32
@@ -321,6 +343,82 @@ class BertModel:
         self.lib.bert_forward(self.ctx, self.N_THREADS, _as_i32p(a), len(a), _as_f32p(out))
         return out
 
+    # -- cross-encoder reranking (bert_hip.h) --
+    OUT_POOLED, OUT_TOKENS, OUT_LOGITS = 0, 1, 2
+
+    @property
+    def n_labels(self):
+        """Logits per pair of the file's classification head; 0: the file has none."""
+        return int(self.lib.bertx_n_labels(self.ctx))
+
+    @staticmethod
+    def _bytes(s):
+        return s.encode("utf-8") if isinstance(s, str) else s
+
+    def tokenize_pair(self, a, b, truncate=True, n_max=None):
+        """(ids, types) of [CLS] a [SEP] b [SEP]; a pair over n_max without `truncate` raises
+        ValueError carrying the full token count."""
+        n_max = self.n_max_tokens if n_max is None else n_max
+        ids, types = np.zeros(max(n_max, 1), np.int32), np.zeros(max(n_max, 1), np.int32)
+        n = c_i32(0)
+        rc = self.lib.bertx_tokenize_pair(self.ctx, self._bytes(a), self._bytes(b), 1 if truncate else 0,
+                                          ids.ctypes.data, types.ctypes.data, ctypes.byref(n), n_max)
+        if rc == -4:
+            raise ValueError("pair of %d tokens, maximum is %d" % (n.value, n_max))
+        if rc != 0:
+            raise RuntimeError("bertx_tokenize_pair failed (%d)" % rc)
+        return ids[:n.value].copy(), types[:n.value].copy()
+
+    def score_ids(self, ids_list, types_list, fill=0.0):
+        """Raw logits f32 [n][n_labels] of pre-tokenised pairs."""
+        n = len(ids_list)
+        lens = np.fromiter((len(x) for x in ids_list), np.int32, n)
+        ids = [np.ascontiguousarray(np.asarray(x, np.int32)) for x in ids_list]
+        types = [np.ascontiguousarray(np.asarray(x, np.int32)) for x in types_list]
+        ip = np.array([x.ctypes.data for x in ids], np.uintp)
+        tp = np.array([x.ctypes.data for x in types], np.uintp)
+        out = np.full((n, max(self.n_labels, 1)), fill, np.float32)
+        rc = self.lib.bertx_score_ids(self.ctx, n, ip.ctypes.data, tp.ctypes.data, lens.ctypes.data, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_score_ids failed (%d)" % rc)
+        return out
+
+    def score_pairs(self, pairs, truncate=True):
+        """Raw logits f32 [n][n_labels] of (a, b) text pairs (no sigmoid / softmax applied)."""
+        n = len(pairs)
+        ta, tb = (ctypes.c_char_p * n)(), (ctypes.c_char_p * n)()
+        for j, (a, b) in enumerate(pairs):
+            ta[j], tb[j] = self._bytes(a), self._bytes(b)
+        out = np.zeros((n, max(self.n_labels, 1)), np.float32)
+        rc = self.lib.bertx_score_pairs(self.ctx, self.N_THREADS, n, ta, tb, 1 if truncate else 0, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_score_pairs failed (%d)" % rc)
+        return out
+
+    def rerank_logits(self, query, docs, truncate=True):
+        """bertx_rerank: logits f32 [n_docs][n_labels] of (query, doc) pairs."""
+        n = len(docs)
+        td = (ctypes.c_char_p * n)()
+        for j, s in enumerate(docs):
+            td[j] = self._bytes(s)
+        out = np.zeros((n, max(self.n_labels, 1)), np.float32)
+        rc = self.lib.bertx_rerank(self.ctx, self.N_THREADS, self._bytes(query), n, td, 1 if truncate else 0,
+                                   out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_rerank failed (%d)" % rc)
+        return out
+
+    def rerank(self, query, docs, top_k=None):
+        """[(index, logit)] of docs by descending first-label logit (equal logits by index), the best top_k."""
+        lg = self.rerank_logits(query, docs)[:, 0]
+        order = np.argsort(-lg, kind="stable")
+        return [(int(i), float(lg[i])) for i in order[:top_k]]
+
+    def forward_device_ex(self, slot, d_ids, d_types, d_cu, n_seqs, max_len, total_tokens, out_kind, d_out, stream):
+        """bertx_forward_device_ex on raw device addresses (ints; d_types 0 / None: all type 0)."""
+        return int(self.lib.bertx_forward_device_ex(self.ctx, slot, d_ids, d_types or None, d_cu, n_seqs, max_len,
+                                                    total_tokens, out_kind, d_out, stream or None))
+
     def device_last_call(self):
         """Per GPU of the context: (wall ms, sentences, tokens) of the last host-driven call."""
         out = []
@@ -440,8 +538,13 @@ class BertIndex:
 # model files in the reference format
 # ---------------------------------------------------------------------------
 
-def tensor_names(n_layer):
-    """Tensor names and roles in converter order (convert-to-ggml.py iterates state_dict)."""
+HEAD_NAMES = [("pooler.dense.weight", "dd"), ("pooler.dense.bias", "d"), ("classifier.weight", "cd"),
+              ("classifier.bias", "c")]
+
+
+def tensor_names(n_layer, head=False):
+    """Tensor names and roles in converter order (convert-to-ggml.py iterates state_dict);
+    head: followed by the four records of a classification head."""
     names = [("embeddings.word_embeddings.weight", "word"), ("embeddings.position_embeddings.weight", "pos"),
              ("embeddings.token_type_embeddings.weight", "type"), ("embeddings.LayerNorm.weight", "ln_w"),
              ("embeddings.LayerNorm.bias", "ln_b")]
@@ -455,13 +558,47 @@ def tensor_names(n_layer):
                   (p + "intermediate.dense.weight", "fd"), (p + "intermediate.dense.bias", "f"),
                   (p + "output.dense.weight", "df"), (p + "output.dense.bias", "d"),
                   (p + "output.LayerNorm.weight", "ln_w"), (p + "output.LayerNorm.bias", "ln_b")]
-    return names
+    return names + (HEAD_NAMES if head else [])
 
 
-def write_model(path, hp, vocab, tensors, ftype):
+def _write_tensor(f, name, a, ftype):
+    """One record.  classifier.weight: f32 in every ftype and 2-D [n_labels][d] also for one label."""
+    a = np.asarray(a, np.float32)
+    if name == "classifier.weight":
+        a = a.reshape(-1, a.shape[-1])
+    nd = a.ndim
+    if ftype == 1 and name.endswith(".weight") and nd == 2 and name != "classifier.weight":
+        data, lt = a.astype(np.float16), 1
+    else:
+        data, lt = a, 0
+    nb = name.encode("utf-8")
+    f.write(struct.pack("<3i", nd, len(nb), lt))
+    for i in range(nd):
+        f.write(struct.pack("<i", a.shape[nd - 1 - i]))
+    f.write(nb)
+    f.write(np.ascontiguousarray(data).tobytes())
+
+
+def append_head(src, dst, tensors):
+    """Copy the f32 / f16 model file src to dst followed by the four head records from tensors
+    (pooler.dense.weight [d][d], pooler.dense.bias [d], classifier.weight [n_labels][d],
+    classifier.bias [n_labels]); quantize the result with bertx_quantize_file for the q formats."""
+    with open(src, "rb") as f:
+        raw = f.read()
+    ftype = struct.unpack_from("<i", raw, 4 + 6 * 4)[0]
+    assert ftype in (0, 1), "append_head needs an f32 or f16 file"
+    with open(dst, "wb") as f:
+        f.write(raw)
+        for name, _ in HEAD_NAMES:
+            _write_tensor(f, name, tensors[name], ftype)
+    return dst
+
+
+def write_model(path, hp, vocab, tensors, ftype, head=False):
     """hp: dict n_vocab,n_max_tokens,n_embd,n_intermediate,n_head,n_layer; tensors: name -> f32 array
     (torch Linear layout [out][in]).  ftype 0 (f32) or 1 (f16): 2-D '*weight' tensors stored f16
-    like convert-to-ggml.py:96-101; everything else f32."""
+    like convert-to-ggml.py:96-101; everything else f32.  head: the four head records follow
+    (classifier.weight stays f32)."""
     assert ftype in (0, 1)
     with open(path, "wb") as f:
         f.write(struct.pack("<I", 0x67676D6C))
@@ -471,19 +608,8 @@ def write_model(path, hp, vocab, tensors, ftype):
             b = w.encode("utf-8")
             f.write(struct.pack("<i", len(b)))
             f.write(b)
-        for name, _ in tensor_names(hp["n_layer"]):
-            a = np.asarray(tensors[name], np.float32)
-            nd = a.ndim
-            if ftype == 1 and name.endswith(".weight") and nd == 2:
-                data, lt = a.astype(np.float16), 1
-            else:
-                data, lt = a, 0
-            nb = name.encode("utf-8")
-            f.write(struct.pack("<3i", nd, len(nb), lt))
-            for i in range(nd):
-                f.write(struct.pack("<i", a.shape[nd - 1 - i]))
-            f.write(nb)
-            f.write(np.ascontiguousarray(data).tobytes())
+        for name, _ in tensor_names(hp["n_layer"], head):
+            _write_tensor(f, name, tensors[name], ftype)
 
 
 ARCHS = {

@@ -86,6 +86,7 @@ struct bert_ctx {
     bool host_only = false;
     int act_mode = 0;   // the activation mode the context runs (bertx_activation_mode)
     int pool = 0;       // BERTX_POOL_MEAN / BERTX_POOL_CLS (bertx_set_pooling), mirrored on every replica
+    int n_labels = 0;   // logits per sentence of the file's classification head; 0: none (bertx_n_labels)
     // routing state of run_forward: the cost of the work routed to each replica and
     // not yet finished, and the rotation that breaks ties between equal loads
     std::mutex route_mu;
@@ -153,7 +154,10 @@ double sentence_cost(const emb::HParams &hp, int L)
 // sentences in chunks of <= kChunkTokens on its persistent worker thread (the
 // caller runs one share itself).  Results are independent of the routing and the
 // split: every kernel computes a sentence from its own tokens only.
-int run_forward(bert_ctx *ctx, const int32_t *const *toks, const int32_t *lens, float *const *outs, int n)
+// types (or null) ride along with the ids; logits: outs[i] receives the n_labels raw
+// logits of the file's head instead of an embedding (-6 without a head).
+int run_forward(bert_ctx *ctx, const int32_t *const *toks, const int32_t *lens, float *const *outs, int n,
+                const int32_t *const *types = nullptr, bool logits = false)
 {
     if (ctx->devices.empty()) {
         emb::errorf("libbert: no HIP device in this context (BERT_HOST_ONLY); forward unavailable\n");
@@ -205,20 +209,22 @@ int run_forward(bert_ctx *ctx, const int32_t *const *toks, const int32_t *lens, 
                 D.set_last_call(ms, (int)mine.size(), toks);
             }
         } stamp{D, t0, mine, toks_done};
-        std::vector<const int32_t *> tp;
+        std::vector<const int32_t *> tp, yp;
         std::vector<int32_t> lp;
         std::vector<float *> op;
         size_t i = 0;
         while (i < mine.size()) {
-            tp.clear(); lp.clear(); op.clear();
+            tp.clear(); lp.clear(); op.clear(); yp.clear();
             int64_t tok = 0;
             while (i < mine.size() && (tp.empty() || (tok + lens[mine[i]] <= kChunkTokens &&
                                                        (int)tp.size() < kChunkSeqs))) {
                 const int idx = mine[i++];
                 tp.push_back(toks[idx]); lp.push_back(lens[idx]); op.push_back(outs[idx]);
+                if (types) yp.push_back(types[idx]);
                 tok += lens[idx];
             }
-            const int rc = D.forward_host(tp.data(), lp.data(), (int)tp.size(), op.data());
+            const int rc = D.forward_host(tp.data(), lp.data(), (int)tp.size(), op.data(), false,
+                                          types ? yp.data() : nullptr, logits);
             if (rc != 0) { rcs[(size_t)dv] = rc; return; }
             toks_done += tok;
         }
@@ -389,6 +395,7 @@ static bert_ctx *load_context(const char *fname, int act_mode)
     ctx->hp = m.hp;
     ctx->vocab.build(m.vocab);
     ctx->act_mode = emb::act_mode_effective(m.hp.ftype, act_mode);
+    ctx->n_labels = m.n_labels;
     if (act_mode == 1 && ctx->act_mode == 0)
         emb::infof("bert_load_from_file: q8 activations asked for a file of ftype %d: the reference has no q8 "
                    "arithmetic for f16 / f32 files, running the default mode\n", m.hp.ftype);
@@ -770,6 +777,153 @@ int32_t bertx_quantize_file(const char *fin, const char *fout, int32_t itype)
 int32_t bertx_convert_hf(const char *dir_model, const char *fname_out, int32_t ftype)
 {
     return emb::convert_hf_dir(dir_model, fname_out, ftype);
+}
+
+int32_t bertx_convert_hf_head(const char *dir_model, const char *fname_out, int32_t ftype)
+{
+    return emb::convert_hf_dir(dir_model, fname_out, ftype, true);
+}
+
+int32_t bertx_n_labels(struct bert_ctx *ctx) { return ctx ? ctx->n_labels : 0; }
+
+int32_t bertx_forward_device_ex(struct bert_ctx *ctx, int32_t slot, const int32_t *d_ids, const int32_t *d_types,
+                                const int32_t *d_cu, int32_t n_seqs, int32_t max_len, int32_t total_tokens,
+                                int32_t out_kind, float *d_out, void *stream)
+{
+    if (slot < 0 || slot >= (int32_t)ctx->devices.size()) return -1;
+    if (out_kind != BERTX_OUT_POOLED && out_kind != BERTX_OUT_TOKENS && out_kind != BERTX_OUT_LOGITS) return -1;
+    if (out_kind == BERTX_OUT_LOGITS && ctx->n_labels <= 0) return -6;
+    if (max_len > ctx->hp.n_max_tokens || max_len <= 0) return -4;
+    Device &D = *ctx->devices[(size_t)slot];
+    std::lock_guard<std::mutex> lk(D.mutex());
+    emb::DeviceGuard g(D.ordinal());
+    return D.forward_ex(d_ids, d_types, d_cu, n_seqs, max_len, total_tokens, out_kind, d_out,
+                        stream ? (hipStream_t)stream : D.stream());
+}
+
+int32_t bertx_tokenize_pair(struct bert_ctx *ctx, const char *text_a, const char *text_b, int32_t truncate,
+                            bert_vocab_id *ids, int32_t *types, int32_t *n_tokens, int32_t n_max)
+{
+    if (!ctx || !text_a || !text_b || !ids || !types || !n_tokens || n_max < 3) return -1;
+    try {
+        thread_local std::vector<int32_t> pa, pb;
+        ctx->vocab.pieces(text_a, pa);
+        ctx->vocab.pieces(text_b, pb);
+        const int32_t rc = emb::Vocab::pair_layout(pa.data(), (int32_t)pa.size(), pb.data(), (int32_t)pb.size(),
+                                                   truncate != 0, n_max, ids, types, n_tokens);
+        if (rc == -4) emb::errorf("Too many tokens, maximum is %d\n", n_max);
+        return rc;
+    } catch (...) {
+        emb::errorf("libbert: tokenization failed\n");
+        return -1;
+    }
+}
+
+// The refusals the three scoring entries share, before any work: -1 bad arguments, -6
+// a file without a head, -1 (after the usual message) a tokenizer-only context.
+static int32_t score_refusal(struct bert_ctx *ctx, int32_t n, bool ptrs_ok, const float *logits)
+{
+    if (!ctx || n < 0 || (n > 0 && (!ptrs_ok || !logits))) return -1;
+    if (ctx->n_labels <= 0) {
+        emb::errorf("libbert: this model file has no classification head (pooler.dense.* + classifier.*)\n");
+        return -6;
+    }
+    if (ctx->devices.empty()) {
+        emb::errorf("libbert: no HIP device in this context (BERT_HOST_ONLY); forward unavailable\n");
+        return -1;
+    }
+    return 0;
+}
+
+int32_t bertx_score_ids(struct bert_ctx *ctx, int32_t n, bert_vocab_id **ids, int32_t **types, int32_t *n_tokens,
+                        float *logits)
+{
+    if (const int32_t rc = score_refusal(ctx, n, ids && types && n_tokens, logits)) return rc;
+    for (int i = 0; i < n; ++i) {
+        if (n_tokens[i] > ctx->hp.n_max_tokens) {
+            emb::errorf("Too many tokens, maximum is %d\n", ctx->hp.n_max_tokens);
+            return -4;
+        }
+        if (n_tokens[i] <= 0 || !ids[i] || !types[i]) return -1;
+        for (int t = 0; t < n_tokens[i]; ++t)
+            if (types[i][t] != 0 && types[i][t] != 1) {
+                emb::errorf("libbert: token type %d of input %d is not 0 or 1\n", types[i][t], i);
+                return -1;
+            }
+    }
+    if (n == 0) return 0;
+    try {
+        // results in staging rows first: a failed call leaves the caller's logits untouched
+        const size_t nl = (size_t)ctx->n_labels;
+        std::vector<float> stage((size_t)n * nl);
+        std::vector<float *> op((size_t)n);
+        for (int i = 0; i < n; ++i) op[(size_t)i] = stage.data() + nl * (size_t)i;
+        const int rc = run_forward(ctx, ids, n_tokens, op.data(), n, types, true);
+        if (rc != 0) return rc;
+        std::memcpy(logits, stage.data(), stage.size() * sizeof(float));
+        return 0;
+    } catch (...) {
+        emb::errorf("libbert: scoring failed\n");
+        return -1;
+    }
+}
+
+// n pairs: texts_a[i] (or the one query's pieces, tokenised once) against texts_b[i]
+static int32_t score_texts(struct bert_ctx *ctx, int32_t n_threads, int32_t n, const char *query,
+                           const char *const *texts_a, const char *const *texts_b, int32_t truncate, float *logits)
+{
+    if (n == 0) return 0;
+    try {
+        const int32_t N = ctx->hp.n_max_tokens;
+        std::vector<int32_t> ids((size_t)n * N), types((size_t)n * N), lens((size_t)n), rcs((size_t)n, 0), qp;
+        if (query) ctx->vocab.pieces(query, qp);
+        emb::TaskPool::instance().run(((int64_t)n + 7) / 8, n_threads > 0 ? n_threads : 1, [&](int64_t blk) {
+            thread_local std::vector<int32_t> pa, pb;
+            const int e = (int)std::min<int64_t>(n, 8 * blk + 8);
+            for (int i = (int)(8 * blk); i < e; ++i) {
+                if (!query) ctx->vocab.pieces(texts_a[i], pa);
+                ctx->vocab.pieces(texts_b[i], pb);
+                const std::vector<int32_t> &A = query ? qp : pa;
+                rcs[(size_t)i] = emb::Vocab::pair_layout(A.data(), (int32_t)A.size(), pb.data(), (int32_t)pb.size(),
+                                                         truncate != 0, N, ids.data() + (size_t)i * N,
+                                                         types.data() + (size_t)i * N, &lens[(size_t)i]);
+            }
+        });
+        for (int i = 0; i < n; ++i)
+            if (rcs[(size_t)i] != 0) {
+                if (rcs[(size_t)i] == -4) emb::errorf("Too many tokens, maximum is %d\n", N);
+                return rcs[(size_t)i];
+            }
+        std::vector<int32_t *> ip((size_t)n), tp((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            ip[(size_t)i] = ids.data() + (size_t)i * N;
+            tp[(size_t)i] = types.data() + (size_t)i * N;
+        }
+        return bertx_score_ids(ctx, n, ip.data(), tp.data(), lens.data(), logits);
+    } catch (const std::exception &ex) {
+        emb::errorf("libbert: tokenization failed: %s\n", ex.what());
+    } catch (...) {
+        emb::errorf("libbert: tokenization failed\n");
+    }
+    return -1;
+}
+
+int32_t bertx_score_pairs(struct bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts_a,
+                          const char **texts_b, int32_t truncate, float *logits)
+{
+    if (const int32_t rc = score_refusal(ctx, n, texts_a && texts_b, logits)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (!texts_a[i] || !texts_b[i]) return -1;
+    return score_texts(ctx, n_threads, n, nullptr, texts_a, texts_b, truncate, logits);
+}
+
+int32_t bertx_rerank(struct bert_ctx *ctx, int32_t n_threads, const char *query, int32_t n_docs, const char **docs,
+                     int32_t truncate, float *logits)
+{
+    if (const int32_t rc = score_refusal(ctx, n_docs, query && docs, logits)) return rc;
+    for (int i = 0; i < n_docs; ++i)
+        if (!docs[i]) return -1;
+    return score_texts(ctx, n_threads, n_docs, query, nullptr, docs, truncate, logits);
 }
 
 int32_t bertx_tokenize_batch(struct bert_ctx *ctx, int32_t n_threads, int32_t n_inputs, const char **texts,

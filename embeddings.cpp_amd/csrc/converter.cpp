@@ -283,7 +283,7 @@ template <typename T> void put(std::string &o, const T &v) { o.append((const cha
 
 }  // namespace
 
-int convert_hf_dir(const std::string &dir, const std::string &fname_out, int ftype)
+int convert_hf_dir(const std::string &dir, const std::string &fname_out, int ftype, bool head)
 {
     if (ftype < 0 || ftype > 1) {
         errorf("Invalid ftype: %d\n", ftype);
@@ -389,6 +389,43 @@ int convert_hf_dir(const std::string &dir, const std::string &fname_out, int fty
             for (float v : t.data) put(o, f32_to_f16(v));
         else
             o.append((const char *)t.data.data(), t.data.size() * 4);
+    }
+    if (head) {
+        // the four head records behind the reference's bytes: the pooler (the base model's,
+        // "bert." already dropped) and the un-prefixed classifier of BertForSequenceClassification
+        const char *need[] = {"pooler.dense.weight", "pooler.dense.bias", "classifier.weight", "classifier.bias"};
+        for (const char *n : need)
+            if (!byname.count(n)) {
+                errorf("convert: --head: checkpoint lacks tensor '%s' (not a BertForSequenceClassification "
+                       "checkpoint with a pooler)\n", n);
+                return 1;
+            }
+        const int64_t d = hp[2];
+        const StTensor &pw = *byname["pooler.dense.weight"], &pb = *byname["pooler.dense.bias"];
+        const StTensor &cw = *byname["classifier.weight"], &cb = *byname["classifier.bias"];
+        const int64_t nl = (int64_t)cb.data.size();
+        if ((int64_t)pw.data.size() != d * d || (int64_t)pb.data.size() != d || nl < 1 || nl > kMaxLabels ||
+            (int64_t)cw.data.size() != nl * d) {
+            errorf("convert: --head: pooler / classifier shapes do not fit hidden_size %d and 1 .. %d labels\n",
+                   (int)d, kMaxLabels);
+            return 1;
+        }
+        auto rec = [&](const char *n, const StTensor &t, int nd, int64_t e0, int64_t e1, bool half) {
+            put(o, (int32_t)nd);
+            put(o, (int32_t)std::strlen(n));
+            put(o, (int32_t)(half ? 1 : 0));
+            put(o, (int32_t)e0);
+            if (nd == 2) put(o, (int32_t)e1);
+            o += n;
+            if (half)
+                for (float v : t.data) put(o, f32_to_f16(v));
+            else
+                o.append((const char *)t.data.data(), t.data.size() * 4);
+        };
+        rec(need[0], pw, 2, d, d, ftype == 1);
+        rec(need[1], pb, 1, d, 1, false);
+        rec(need[2], cw, 2, d, nl, false);   // f32 in every ftype, 2-D also for one label
+        rec(need[3], cb, 1, nl, 1, false);
     }
     FILE *f = std::fopen(fname_out.c_str(), "wb");
     if (!f) {

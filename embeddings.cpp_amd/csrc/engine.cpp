@@ -110,6 +110,14 @@ bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bo
             }
             return add(std::move(p));
         };
+        // the head, one f32 form for every chain: the pooler rows dequantized once
+        if (m.n_labels > 0) {
+            img.n_labels = m.n_labels;
+            img.head_wp = rows32({&m.pool_w});
+            img.head_bp = vec(m.pool_b);
+            img.head_wc = vec(m.cls_w);
+            img.head_bc = vec(m.cls_b);
+        }
         img.layers.assign((size_t)hp.n_layer, ModelImage::Layer());
         for (int l = 0; l < hp.n_layer; ++l) {
             const HostLayer &L = m.layers[(size_t)l];
@@ -246,6 +254,7 @@ Device::~Device()
     if (tok_out_) (void)hipFree(tok_out_);
     if (h_ids_) (void)hipHostFree(h_ids_);
     if (h_cu_) (void)hipHostFree(h_cu_);
+    if (h_types_) (void)hipHostFree(h_types_);
     if (h_out_) (void)hipHostFree(h_out_);
     if (done_ev_) (void)hipEventDestroy(done_ev_);
     if (stream_) (void)hipStreamDestroy(stream_);
@@ -286,6 +295,9 @@ void Device::bind(const ModelImage &img)
     pos_ = mk_table(img.pos);
     ln_e_w_ = (float *)P(img.lnw);
     ln_e_b_ = (float *)P(img.lnb);
+    n_labels_ = img.n_labels;
+    head_wp_ = (const float *)P(img.head_wp); head_bp_ = (const float *)P(img.head_bp);
+    head_wc_ = (const float *)P(img.head_wc); head_bc_ = (const float *)P(img.head_bc);
     auto mk_lin = [&](const ModelImage::Lin &x) {
         DevWeight w;
         w.fmt = wfmt_ == FMT_F32 ? FMT_F16 : wfmt_; w.N = x.N; w.K = x.K;
@@ -339,6 +351,9 @@ bool Device::reserve(int64_t tokens, int64_t seqs, int max_len)
     const size_t o_att32 = take(r32 * d * 4), o_ffn32 = take(r32 * f * 4);
     const size_t o_xq = take(rq * kq), o_xd = take(rq * (kq / 32) * 4), o_xs = take(rq * (kq / 32) * 4);
     const size_t o_ids = take(rows * 4), o_cu = take((ns + 1) * 4), o_out = take(ns * d * 4);
+    const size_t o_types = take(rows * 4);
+    const int64_t rh = n_labels_ > 0 ? ns : 0;   // the head's two row buffers
+    const size_t o_hx = take(rh * d * 4), o_hp = take(rh * d * 4);
     const size_t o_pool = take((size_t)np * d * 4);
     // the pruned last layer of CLS pooling (f16 chain): one row per sentence, padded
     // to whole GEMM tiles as the token rows are
@@ -350,6 +365,7 @@ bool Device::reserve(int64_t tokens, int64_t seqs, int max_len)
     if (h_ids_) { (void)hipHostFree(h_ids_); h_ids_ = nullptr; }
     if (h_cu_) { (void)hipHostFree(h_cu_); h_cu_ = nullptr; }
     if (h_out_) { (void)hipHostFree(h_out_); h_out_ = nullptr; }
+    if (h_types_) { (void)hipHostFree(h_types_); h_types_ = nullptr; }
     cap_tokens_ = cap_seqs_ = cap_pool_ = 0;
     HIP_OK(hipMalloc((void **)&ws_, off));
     // on the replica's own (non-blocking) stream: a null-stream memset would not
@@ -361,6 +377,8 @@ bool Device::reserve(int64_t tokens, int64_t seqs, int max_len)
     qkv_ = (uint16_t *)(ws_ + o_qkv); att_ = (uint16_t *)(ws_ + o_att); ffn_ = (uint16_t *)(ws_ + o_ffn);
     d_ids_ = (int32_t *)(ws_ + o_ids); d_cu_ = (int32_t *)(ws_ + o_cu); d_out_ = (float *)(ws_ + o_out);
     pool_part_ = (float *)(ws_ + o_pool);
+    d_types_ = (int32_t *)(ws_ + o_types);
+    head_x_ = (float *)(ws_ + o_hx); head_p_ = (float *)(ws_ + o_hp);
     stc_ = (float2 *)(ws_ + o_stc); zc_ = (uint16_t *)(ws_ + o_zc); partc_ = (float2 *)(ws_ + o_partc);
     attc_ = (uint16_t *)(ws_ + o_attc); ffnc_ = (uint16_t *)(ws_ + o_ffnc);
     rows_c_ = rows_c;
@@ -369,6 +387,7 @@ bool Device::reserve(int64_t tokens, int64_t seqs, int max_len)
     xq_ = (int8_t *)(ws_ + o_xq); xd_ = (float *)(ws_ + o_xd); xs_ = (float *)(ws_ + o_xs);
     HIP_OK(hipHostMalloc((void **)&h_ids_, nt * 4, hipHostMallocDefault));
     HIP_OK(hipHostMalloc((void **)&h_cu_, (ns + 1) * 4, hipHostMallocDefault));
+    HIP_OK(hipHostMalloc((void **)&h_types_, nt * 4, hipHostMallocDefault));
     HIP_OK(hipHostMalloc((void **)&h_out_, ns * d * 4, hipHostMallocDefault));
     cap_tokens_ = nt;
     cap_seqs_ = ns;

@@ -86,6 +86,10 @@ struct ModelImage {
     bool q8 = false;   // activation mode 1 on a q4_0 / q4_1 / q8_0 file: the q8-activation chain (q8act.hip)
     Tab word, type, pos;
     size_t gelu = kNone, exp = kNone, lnw = kNone, lnb = kNone;
+    // the classification head (files that carry one): the pooler rows dequantized to
+    // f32 [d][d], its bias, the classifier rows f32 [n_labels][d] and bias
+    size_t head_wp = kNone, head_bp = kNone, head_wc = kNone, head_bc = kNone;
+    int n_labels = 0;
     std::vector<Layer> layers;
     // piece i: bytes [off[i], off[i] + len[i]) of the image (len 0: absent plane)
     std::vector<size_t> off, len;
@@ -149,12 +153,28 @@ public:
     // tokens: d_out is float[total_tokens][n_embd] and receives every token's final
     // LayerNorm output (un-normalised) instead of the pooled sentence embeddings.
     int forward(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int total_tokens, float *d_out,
-                hipStream_t s, double len2_sum = -1.0, bool tokens = false);
+                hipStream_t s, double len2_sum = -1.0, bool tokens = false)
+    {
+        return forward_ex(d_ids, nullptr, d_cu, n_seqs, max_len, total_tokens, tokens ? KIND_TOKENS : KIND_POOLED, d_out,
+                          s, len2_sum);
+    }
+    // The same with token types and the kind of output (bert_hip.h BERTX_OUT_*).
+    // d_types: int32[total_tokens] on this GPU, every value 0 or 1 (trusted), or null
+    // for all 0.  KIND_LOGITS: d_out is float[n_seqs][n_labels], the raw logits of the
+    // file's classification head on each sentence's [CLS] row; -6 without a head.  The
+    // f16 chain runs the last layer on the compact rows when CLS pruning is on.
+    enum OutKind : int { KIND_POOLED = 0, KIND_TOKENS = 1, KIND_LOGITS = 2 };
+    int forward_ex(const int32_t *d_ids, const int32_t *d_types, const int32_t *d_cu, int n_seqs, int max_len,
+                   int total_tokens, int out_kind, float *d_out, hipStream_t s, double len2_sum = -1.0);
+    int n_labels() const { return n_labels_; }
 
     // Host-driven forward: packs tokens, H2D, forward, D2H, synchronous.
     // tokens[i] has lens[i] ids; out[i] receives n_embd floats, or with tok_out
-    // lens[i] x n_embd floats (the per-token output).
-    int forward_host(const int32_t *const *tokens, const int32_t *lens, int n, float *const *out, bool tok_out = false);
+    // lens[i] x n_embd floats (the per-token output).  types (or null: all 0): the
+    // token type ids, types[i] beside tokens[i].  logits: out[i] receives the
+    // n_labels logits of sentence i instead.
+    int forward_host(const int32_t *const *tokens, const int32_t *lens, int n, float *const *out, bool tok_out = false,
+                     const int32_t *const *types = nullptr, bool logits = false);
 
     // Pooling of the sentence embeddings (bert_hip.h): BERTX_POOL_MEAN / BERTX_POOL_CLS,
     // and whether CLS pooling runs the last layer on the sentences' first rows only
@@ -189,14 +209,16 @@ private:
         hipStream_t s;
         int n_seqs, max_len, T;
         int mode;   // OutMode: a graph of one pooling mode is never replayed for another
+        const void *types;   // the token types pointer (null: all 0) is baked into the embedding launch
         bool operator==(const GraphKey &o) const
         {
             return ids == o.ids && cu == o.cu && out == o.out && s == o.s && n_seqs == o.n_seqs &&
-                   max_len == o.max_len && T == o.T && mode == o.mode;
+                   max_len == o.max_len && T == o.T && mode == o.mode && types == o.types;
         }
     };
-    // what the launch sequence ends in (and, for CLS, how its last layer runs)
-    enum OutMode : int { OUT_MEAN = 0, OUT_CLS, OUT_CLS_PRUNED, OUT_TOKENS };
+    // what the launch sequence ends in (and, for CLS and the logits, how its last layer runs)
+    enum OutMode : int { OUT_MEAN = 0, OUT_CLS, OUT_CLS_PRUNED, OUT_TOKENS, OUT_LOGITS, OUT_LOGITS_PRUNED };
+    bool pruned_last() const { return out_mode_ == OUT_CLS_PRUNED || out_mode_ == OUT_LOGITS_PRUNED; }
     struct GraphEntry { GraphKey key; hipGraphExec_t exec; };
     int forward_ordered(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out,
                         hipStream_t s);
@@ -224,6 +246,7 @@ private:
                    hipStream_t s, bool check);
     int chain_f16(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out);
     int layer_tail(Launcher &run, const DevLayer &L, int l, const RowSet &r, const float *&gz, const float *&bz);
+    int head(Launcher &run, int n_seqs, float *d_out);
     int chain_32(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out);
     void drop_graphs();
     void bind(const ModelImage &img);   // device pointers of the image's planes
@@ -248,6 +271,9 @@ private:
     bool f32_ = false;              // ftype 0 file: the f32 chain (f32.hip)
     bool q8_ = false;               // activation mode 1: the q8-activation chain (q8act.hip + f32.hip)
     const uint16_t *gelu_tab_ = nullptr, *exp_tab_ = nullptr;   // f32 / q8 chains: the era's fp16 tables (host-built)
+    // the classification head, f32 (null / 0: the file has none)
+    const float *head_wp_ = nullptr, *head_bp_ = nullptr, *head_wc_ = nullptr, *head_bc_ = nullptr;
+    int n_labels_ = 0;
 
     // workspace
     int64_t cap_tokens_ = 0, cap_seqs_ = 0, cap_pool_ = 0;   // cap_pool_: pool partial rows (seqs x chunks)
@@ -263,8 +289,9 @@ private:
     float *x32_ = nullptr, *z32_ = nullptr, *qkv32_ = nullptr, *att32_ = nullptr, *ffn32_ = nullptr;   // f32 / q8 chains
     int8_t *xq_ = nullptr;          // q8 chain: the quantized input of the next projection [rows][max(d, f)]
     float *xd_ = nullptr, *xs_ = nullptr;   // ... its block scales and q8_1 sums [max(d, f) / 32][M]
-    int32_t *d_ids_ = nullptr, *d_cu_ = nullptr;
+    int32_t *d_ids_ = nullptr, *d_cu_ = nullptr, *d_types_ = nullptr;
     float *d_out_ = nullptr;
+    float *head_x_ = nullptr, *head_p_ = nullptr;   // the head's [CLS] rows and pooler output [seqs][d] (files with a head)
     float *pool_part_ = nullptr;
     // the pruned last layer of CLS pooling (f16 chain): compact rows, one per sentence
     uint16_t *zc_ = nullptr, *attc_ = nullptr, *ffnc_ = nullptr;
@@ -275,7 +302,8 @@ private:
     int pool_ = 0;                  // BERTX_POOL_MEAN / BERTX_POOL_CLS
     bool prune_ = true;
     int out_mode_ = OUT_MEAN;       // of the forward being launched
-    int32_t *h_ids_ = nullptr, *h_cu_ = nullptr;   // pinned staging
+    const int32_t *types_ = nullptr;   // ... and its token types (null: all 0)
+    int32_t *h_ids_ = nullptr, *h_cu_ = nullptr, *h_types_ = nullptr;   // pinned staging
     float *h_out_ = nullptr;
 
     // HIP graphs of the launch sequence (cleared when the workspace moves)

@@ -73,12 +73,14 @@ __device__ __forceinline__ void ln_row(f32x4 (&v)[F32_MAXC], int d, int lane, co
     }
 }
 
-// One wave per token row: x = LN(pos[i] + (type[0] + word[id])) (bert.cpp:963-984).
-template <bool EXACT>
+// One wave per token row: x = LN(pos[i] + (type[ty] + word[id])) (bert.cpp:963-984), ty =
+// types[t] (in {0, 1}, trusted) with TY, else row 0 as before the types existed.
+template <bool EXACT, bool TY>
 __global__ __launch_bounds__(256) void f32_embed_ln_kernel(DevTable word, DevTable type, DevTable pos,
                                                            const float *__restrict__ ln_w,
                                                            const float *__restrict__ ln_b,
                                                            const int32_t *__restrict__ ids,
+                                                           const int32_t *__restrict__ types,
                                                            const int32_t *__restrict__ cu, int d, float *__restrict__ x)
 {
     const int b = blockIdx.y, lane = threadIdx.x & 63;
@@ -86,12 +88,14 @@ __global__ __launch_bounds__(256) void f32_embed_ln_kernel(DevTable word, DevTab
     const int start = cu[b], len = cu[b + 1] - start;
     if (i >= len) return;   // whole waves
     const int t = start + i, id = ids[t];
+    int tr = 0;
+    if constexpr (TY) tr = types[t];
     f32x4 v[F32_MAXC];
 #pragma unroll
     for (int k = 0; k < F32_MAXC; ++k) {
         const int c = 4 * lane + 256 * k;
         if (c < d) {
-            const f32x4 w = table4(word, id, c), ty = table4(type, 0, c), p = table4(pos, i, c);
+            const f32x4 w = table4(word, id, c), ty = table4(type, TY ? tr : 0, c), p = table4(pos, i, c);
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[k][e] = p[e] + (ty[e] + w[e]);
         }
@@ -406,11 +410,16 @@ void launch_f32_cls(const float *x, const int32_t *cu, int32_t n_seqs, int32_t d
 
 void launch_f32_embed_ln(const DevTable &word, const DevTable &type, const DevTable &pos, const float *ln_w,
                          const float *ln_b, const int32_t *ids, const int32_t *cu, int32_t n_seqs, int32_t max_len,
-                         int32_t d, float *x, hipStream_t s, bool exact)
+                         int32_t d, float *x, hipStream_t s, bool exact, const int32_t *types)
 {
     const dim3 g((max_len + 3) / 4, n_seqs);
-    if (exact) f32_embed_ln_kernel<true><<<g, 256, 0, s>>>(word, type, pos, ln_w, ln_b, ids, cu, d, x);
-    else f32_embed_ln_kernel<false><<<g, 256, 0, s>>>(word, type, pos, ln_w, ln_b, ids, cu, d, x);
+    if (types) {
+        if (exact) f32_embed_ln_kernel<true, true><<<g, 256, 0, s>>>(word, type, pos, ln_w, ln_b, ids, types, cu, d, x);
+        else f32_embed_ln_kernel<false, true><<<g, 256, 0, s>>>(word, type, pos, ln_w, ln_b, ids, types, cu, d, x);
+        return;
+    }
+    if (exact) f32_embed_ln_kernel<true, false><<<g, 256, 0, s>>>(word, type, pos, ln_w, ln_b, ids, nullptr, cu, d, x);
+    else f32_embed_ln_kernel<false, false><<<g, 256, 0, s>>>(word, type, pos, ln_w, ln_b, ids, nullptr, cu, d, x);
 }
 
 void launch_f32_ln(float *x, int32_t rows, int32_t d, const float *g, const float *b, hipStream_t s, bool exact)

@@ -76,10 +76,17 @@ struct Device::Launcher {
     }
 };
 
-int Device::forward(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out,
-                    hipStream_t s, double len2_sum, bool tokens)
+int Device::forward_ex(const int32_t *d_ids, const int32_t *d_types, const int32_t *d_cu, int n_seqs, int max_len, int T,
+                       int out_kind, float *d_out, hipStream_t s, double len2_sum)
 {
-    out_mode_ = tokens ? OUT_TOKENS : pool_ != 1 ? OUT_MEAN : (prune_ && !f32_ && !q8_) ? OUT_CLS_PRUNED : OUT_CLS;
+    if (out_kind != KIND_POOLED && out_kind != KIND_TOKENS && out_kind != KIND_LOGITS) return -1;
+    if (out_kind == KIND_LOGITS && n_labels_ <= 0) return -6;
+    const bool can_prune = prune_ && !f32_ && !q8_;
+    out_mode_ = out_kind == KIND_TOKENS   ? OUT_TOKENS
+                : out_kind == KIND_LOGITS ? (can_prune ? OUT_LOGITS_PRUNED : OUT_LOGITS)
+                : pool_ != 1              ? OUT_MEAN
+                                          : can_prune ? OUT_CLS_PRUNED : OUT_CLS;
+    types_ = d_types;
     // attention work for the per-kernel stats: exact from the host's lengths when
     // known, else T max_len (exact for equal lengths, an upper bound otherwise)
     att_flop_ = 4.0 * hp_.n_embd * (len2_sum >= 0 ? len2_sum : (double)T * max_len);
@@ -100,7 +107,7 @@ int Device::forward_ordered(const int32_t *d_ids, const int32_t *d_cu, int n_seq
     static const bool graphs_env = [] { const char *e = std::getenv("BERT_GRAPHS"); return !(e && *e == '0'); }();
     if (profiling_ || check || !use_graphs_ || !graphs_env || s == nullptr)
         return launch_all(d_ids, d_cu, n_seqs, max_len, T, d_out, s, check);
-    const GraphKey key{d_ids, d_cu, d_out, s, n_seqs, max_len, T, out_mode_};
+    const GraphKey key{d_ids, d_cu, d_out, s, n_seqs, max_len, T, out_mode_, types_};
     for (auto &g : graphs_)
         if (g.key == key) return hipGraphLaunch(g.exec, s) == hipSuccess ? 0 : -1;
     // a shape seen for the first time runs eagerly (one-off batches never pay
@@ -158,7 +165,7 @@ int Device::chain_f16(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, 
     const size_t Td = (size_t)T * d;
 
     run.run(K_EMBED_LN, t * (4.0 + 3.0 * d * 2.0 + 2.0 * d + 8.0),
-            [&] { launch_embed_ln(word_, type_, pos_, ln_e_w_, d_ids, d_cu, n_seqs, max_len, d, z_, st_, s); },
+            [&] { launch_embed_ln(word_, type_, pos_, ln_e_w_, d_ids, d_cu, n_seqs, max_len, d, z_, st_, s, types_); },
             Out{"embed_ln", "", -1, z_, Td});
     // z_ holds the stream as z = y * gamma of the LN in front of the next
     // projection, st_ its (mean, 1/sigma) (kernels.h LN fold); (gz, bz) is that LN
@@ -186,8 +193,8 @@ int Device::chain_f16(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, 
                      Out{"gemm_qkv", "", l, qkv_, Td * 3}))
             return -1;
 
-        if (out_mode_ == OUT_CLS_PRUNED && last) {
-            // CLS pooling reads one row per sentence of this layer: attention of the
+        if (pruned_last() && last) {
+            // CLS pooling and the head read one row per sentence of this layer: attention of the
             // sentences' first rows only (its launch gathers their residual rows into
             // zc_ / stc_), then the rest of the layer on Mc compact rows
             const int Mc = gemm_rows(n_seqs);
@@ -205,6 +212,14 @@ int Device::chain_f16(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, 
         if (layer_tail(run, L, l, r, gz, bz) != 0) return -1;
     }
 
+    if (out_mode_ == OUT_LOGITS || out_mode_ == OUT_LOGITS_PRUNED) {
+        // the head's [CLS] rows: of the compact last layer, or of the full one
+        run.run(K_POOL_L2, (double)n_seqs * (d * 6.0 + 8.0), [&] {
+            if (out_mode_ == OUT_LOGITS_PRUNED) launch_head_gather(zc_, stc_, gz, bz, nullptr, n_seqs, d, head_x_, s);
+            else launch_head_gather(z_, st_, gz, bz, d_cu, n_seqs, d, head_x_, s);
+        }, Out{"head_gather", "", -1, head_x_, (size_t)n_seqs * d, 0});
+        return head(run, n_seqs, d_out);
+    }
     const Out out{"pool_l2", "", -1, d_out, (out_mode_ == OUT_TOKENS ? (size_t)T : (size_t)n_seqs) * d, 0};
     if (out_mode_ == OUT_MEAN) {
         run.run(K_POOL_L2, t * d * 2.0 + t * 8.0 + (double)n_seqs * d * 4.0,
@@ -219,6 +234,19 @@ int Device::chain_f16(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, 
         }, out);
     }
     return 0;
+}
+
+// The classification head on head_x_ (the sentences' final-LayerNorm [CLS] rows): the
+// pooler GEMM + tanh and the classifier (head.hip), timed in the output-stage class.
+// Work: the bytes of the pooler rows, read once per 16 sentences.
+int Device::head(Launcher &run, int n_seqs, float *d_out)
+{
+    const int d = hp_.n_embd;
+    const double tiles = (double)((n_seqs + 15) / 16);
+    const bool ok = run.run(K_POOL_L2, tiles * d * d * 4.0 + (double)n_seqs * d * 12.0, [&] {
+        return launch_head(head_x_, n_seqs, d, head_wp_, head_bp_, head_wc_, head_bc_, n_labels_, head_p_, d_out, run.s);
+    }, Launcher::Out{"head", "", -1, d_out, (size_t)n_seqs * n_labels_, 0});
+    return ok ? 0 : -1;
 }
 
 // The LN side of a projection that reads the rows' stream (c1 = W gamma): with the
@@ -308,7 +336,7 @@ int Device::chain_32(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, i
         run.run(K_LN_STATS, (double)M * d * 8.0, [&] { launch_f32_ln(x, M, d, g, b, s, exact); }, Out{"ln", "", l, x, Td, 0});
     };
     run.run(K_EMBED_LN, t * (4.0 + 3.0 * d * 4.0 + 4.0 * d), [&] {
-        launch_f32_embed_ln(word_, type_, pos_, ln_e_w_, ln_e_b_, d_ids, d_cu, n_seqs, max_len, d, x32_, s, exact);
+        launch_f32_embed_ln(word_, type_, pos_, ln_e_w_, ln_e_b_, d_ids, d_cu, n_seqs, max_len, d, x32_, s, exact, types_);
     }, Out{"embed_ln", "", -1, x32_, Td, 0});
     for (int l = 0; l < hp_.n_layer; ++l) {
         const DevLayer &L = layers_[(size_t)l];
@@ -326,6 +354,11 @@ int Device::chain_32(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, i
     // x32_ holds the final LayerNorm output: the mean pool; CLS, a gather + normalise;
     // the token output, a copy
     bool ok;
+    if (out_mode_ == OUT_LOGITS) {
+        run.run(K_POOL_L2, (double)n_seqs * d * 8.0, [&] { launch_head_gather_f32(x32_, d_cu, n_seqs, d, head_x_, s); },
+                Out{"head_gather", "", -1, head_x_, nd, 0});
+        return head(run, n_seqs, d_out);
+    }
     if (out_mode_ == OUT_MEAN)
         ok = run.run(K_POOL_L2, t * d * 4.0 + (double)n_seqs * d * 4.0,
                      [&] { launch_f32_pool(x32_, d_cu, n_seqs, d, d_out, s, exact); }, Out{"pool_l2", "", -1, d_out, nd, 0});
@@ -338,9 +371,11 @@ int Device::chain_32(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, i
     return ok ? 0 : -1;
 }
 
-int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int n, float *const *out, bool tok_out)
+int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int n, float *const *out, bool tok_out,
+                         const int32_t *const *types, bool logits)
 {
     if (!ok_) return -3;
+    if (logits && n_labels_ <= 0) return -6;
     if (n <= 0) return 0;
     int64_t T = 0;
     int max_len = 0;
@@ -361,6 +396,11 @@ int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int 
     }
     HIP_RC(hipMemcpyAsync(d_ids_, h_ids_, sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, stream_));
     HIP_RC(hipMemcpyAsync(d_cu_, h_cu_, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice, stream_));
+    if (types) {
+        for (int i = 0; i < n; ++i) std::memcpy(h_types_ + h_cu_[i], types[i], sizeof(int32_t) * (size_t)lens[i]);
+        HIP_RC(hipMemcpyAsync(d_types_, h_types_, sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, stream_));
+    }
+    const int32_t *dty = types ? d_types_ : nullptr;
     const size_t d = (size_t)hp_.n_embd;
     if (tok_out) {
         // per-token output: a device buffer of its own, grown on demand, and plain
@@ -374,7 +414,7 @@ int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int 
             HIP_RC(hipMalloc((void **)&tok_out_, sizeof(float) * d * (size_t)cap));
             cap_tok_out_ = cap;
         }
-        const int rc = forward(d_ids_, d_cu_, n, max_len, (int)T, tok_out_, stream_, len2, true);
+        const int rc = forward_ex(d_ids_, dty, d_cu_, n, max_len, (int)T, KIND_TOKENS, tok_out_, stream_, len2);
         if (rc != 0) return rc;
         HIP_RC(hipStreamSynchronize(stream_));
         for (int i = 0; i < n; ++i)
@@ -382,11 +422,13 @@ int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int 
                              hipMemcpyDeviceToHost));
         return 0;
     }
-    const int rc = forward(d_ids_, d_cu_, n, max_len, (int)T, d_out_, stream_, len2);
+    // (the staging rows are n_embd wide; the logits, n_labels <= 16 per sentence, fit in them)
+    const size_t w = logits ? (size_t)n_labels_ : d;
+    const int rc = forward_ex(d_ids_, dty, d_cu_, n, max_len, (int)T, logits ? KIND_LOGITS : KIND_POOLED, d_out_, stream_, len2);
     if (rc != 0) return rc;
-    HIP_RC(hipMemcpyAsync(h_out_, d_out_, sizeof(float) * d * (size_t)n, hipMemcpyDeviceToHost, stream_));
+    HIP_RC(hipMemcpyAsync(h_out_, d_out_, sizeof(float) * w * (size_t)n, hipMemcpyDeviceToHost, stream_));
     HIP_RC(hipStreamSynchronize(stream_));
-    for (int i = 0; i < n; ++i) std::memcpy(out[i], h_out_ + d * (size_t)i, sizeof(float) * d);
+    for (int i = 0; i < n; ++i) std::memcpy(out[i], h_out_ + w * (size_t)i, sizeof(float) * w);
     return 0;
 }
 

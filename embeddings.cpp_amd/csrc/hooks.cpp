@@ -713,6 +713,17 @@ extern "C" int32_t bertx_test_embed_ln(int32_t mode, int32_t fmt_word, int32_t f
                                        const float *ln_b, const int32_t *ids, const int32_t *cu, int32_t n_seqs,
                                        int32_t max_len, void *out, float *stats, int32_t out_rows)
 {
+    return bertx_test_embed_ln_types(mode, fmt_word, fmt_type, fmt_pos, rows_word, rows_pos, d, word_rows, type_rows,
+                                     pos_rows, ln_w, ln_b, ids, nullptr, cu, n_seqs, max_len, out, stats, out_rows);
+}
+
+extern "C" int32_t bertx_test_embed_ln_types(int32_t mode, int32_t fmt_word, int32_t fmt_type, int32_t fmt_pos,
+                                             int32_t rows_word, int32_t rows_pos, int32_t d, const void *word_rows,
+                                             const void *type_rows, const void *pos_rows, const float *ln_w,
+                                             const float *ln_b, const int32_t *ids, const int32_t *types,
+                                             const int32_t *cu, int32_t n_seqs, int32_t max_len, void *out,
+                                             float *stats, int32_t out_rows)
+{
     using namespace emb;
     if (mode < 0 || mode > 2 || !fmt_valid(fmt_word) || !fmt_valid(fmt_type) || !fmt_valid(fmt_pos) ||
         rows_word <= 0 || rows_pos <= 0 || !hook_width_ok(d) || !word_rows || !type_rows || !pos_rows || !ln_w ||
@@ -722,7 +733,7 @@ extern "C" int32_t bertx_test_embed_ln(int32_t mode, int32_t fmt_word, int32_t f
     const int T = cu[n_seqs];
     if (out_rows < T) return -1;
     for (int t = 0; t < T; ++t)
-        if (ids[t] < 0 || ids[t] >= rows_word) return -1;
+        if (ids[t] < 0 || ids[t] >= rows_word || (types && types[t] != 0 && types[t] != 1)) return -1;
     DeviceGuard guard(0);
     HIP_RC(guard.status());
     HookBufs B;
@@ -733,15 +744,49 @@ extern "C" int32_t bertx_test_embed_ln(int32_t mode, int32_t fmt_word, int32_t f
     const float *dg = (const float *)B.up(ln_w, (size_t)d * 4, 0), *db = (const float *)B.up(ln_b, (size_t)d * 4, 0);
     const int32_t *dids = (const int32_t *)B.up(ids, (size_t)T * 4, 0);
     const int32_t *dcu = (const int32_t *)B.up(cu, ((size_t)n_seqs + 1) * 4, 0);
+    const int32_t *dty = types ? (const int32_t *)B.up(types, (size_t)T * 4, 0) : nullptr;
     const size_t ob = (size_t)out_rows * d * (mode == 0 ? 2 : 4);
     void *dout = B.up(out, ob, 0);
     float2 *dst = mode == 0 ? (float2 *)B.up(stats, (size_t)out_rows * 8, 0) : nullptr;
     if (B.bad) return -1;
-    if (mode == 0) launch_embed_ln(word, type, pos, dg, dids, dcu, n_seqs, max_len, d, (uint16_t *)dout, dst, nullptr);
-    else launch_f32_embed_ln(word, type, pos, dg, db, dids, dcu, n_seqs, max_len, d, (float *)dout, nullptr, mode == 2);
+    if (mode == 0) launch_embed_ln(word, type, pos, dg, dids, dcu, n_seqs, max_len, d, (uint16_t *)dout, dst, nullptr, dty);
+    else launch_f32_embed_ln(word, type, pos, dg, db, dids, dcu, n_seqs, max_len, d, (float *)dout, nullptr, mode == 2, dty);
     if (const int rc = hook_finish()) return rc;
     HIP_RC(hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost));
     if (dst) HIP_RC(hipMemcpy(stats, dst, (size_t)out_rows * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int32_t bertx_test_head(const float *x, int32_t n, int32_t d, const float *wp, const float *bp,
+                                   const float *wc, const float *bc, int32_t n_labels, float *out, int32_t out_rows)
+{
+    using namespace emb;
+    if (!x || !wp || !bp || !wc || !bc || !out || n <= 0 || out_rows < n || !hook_width_ok(d) || n_labels < 1 ||
+        n_labels > HEAD_MAX_LABELS || hip_device_count() == 0)
+        return -1;
+    constexpr size_t GUARD = 16;   // rows of NaN bits behind the caller's out_rows
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const float *dx = (const float *)B.up(x, (size_t)n * d * 4, 0);
+    const float *dwp = (const float *)B.up(wp, (size_t)d * d * 4, 0), *dbp = (const float *)B.up(bp, (size_t)d * 4, 0);
+    const float *dwc = (const float *)B.up(wc, (size_t)n_labels * d * 4, 0);
+    const float *dbc = (const float *)B.up(bc, (size_t)n_labels * 4, 0);
+    const size_t ob = (size_t)out_rows * n_labels * 4, gb = GUARD * n_labels * 4;
+    float *dout = (float *)B.up(out, ob, ob + gb);
+    float *dp = (float *)B.up(nullptr, 0, ((size_t)n + GUARD) * d * 4);
+    if (B.bad) return -1;
+    HIP_RC(hipMemset((char *)dout + ob, 0xff, gb));
+    HIP_RC(hipMemset(dp, 0xff, ((size_t)n + GUARD) * d * 4));
+    const int lrc = launch_head(dx, n, d, dwp, dbp, dwc, dbc, n_labels, dp, dout, nullptr);
+    if (const int rc = hook_finish()) return rc;
+    if (lrc != 0) return -1;
+    HIP_RC(hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> g1(GUARD * n_labels), g2(GUARD * d);
+    HIP_RC(hipMemcpy(g1.data(), (char *)dout + ob, gb, hipMemcpyDeviceToHost));
+    HIP_RC(hipMemcpy(g2.data(), dp + (size_t)n * d, GUARD * d * 4, hipMemcpyDeviceToHost));
+    for (const uint32_t v : g1) if (v != 0xffffffffu) return -5;
+    for (const uint32_t v : g2) if (v != 0xffffffffu) return -5;   // the pooler stored past row n
     return 0;
 }
 

@@ -29,7 +29,15 @@ inline size_t fmt_block_bytes(int f)
     }
 }
 
-inline size_t fmt_row_bytes(int f, int64_t k) { return fmt_block_bytes(f) * (size_t)(k / QK); }
+constexpr int kMaxLabels = 16;  // classifier rows a model file may carry
+
+// (f32 / f16 rows of any length: the classifier's bias has n_labels elements)
+inline size_t fmt_row_bytes(int f, int64_t k)
+{
+    if (f == FMT_F32) return (size_t)k * 4;
+    if (f == FMT_F16) return (size_t)k * 2;
+    return fmt_block_bytes(f) * (size_t)(k / QK);
+}
 
 // IEEE binary16 conversions, round-to-nearest-even (the rounding numpy's
 // astype(float16) in convert-to-ggml.py and F16C use).
@@ -60,6 +68,10 @@ struct HostModel {
     std::vector<std::string> vocab;
     HostTensor word, ttype, pos, ln_e_w, ln_e_b;
     std::vector<HostLayer> layers;
+    // the optional classification head (all four records or none): pooler.dense
+    // [d][d] in the header ftype + bias, classifier [n_labels][d] f32 + bias
+    HostTensor pool_w, pool_b, cls_w, cls_b;
+    int32_t n_labels = 0;           // 0: the file has no head
     size_t total_bytes = 0;
     int n_tensors = 0;
 };
@@ -84,7 +96,9 @@ void quantize_row(int fmt, const float *x, uint8_t *dst, int64_t k);
 
 // Native quantizer (mirrors models/quantize.cpp:27-268; itype 2, 3, or 8).
 int quantize_file(const char *in, const char *out, int itype, bool verbose);
-// HF directory (config.json, vocab.txt, model.safetensors) -> model file (converter.cpp)
-int convert_hf_dir(const std::string &dir, const std::string &fname_out, int ftype);
+// HF directory (config.json, vocab.txt, model.safetensors) -> model file (converter.cpp);
+// head: followed by the four head records (pooler.dense.*, classifier.*), refused
+// when the checkpoint lacks either
+int convert_hf_dir(const std::string &dir, const std::string &fname_out, int ftype, bool head = false);
 
 }  // namespace emb

@@ -112,11 +112,13 @@ bool gemm_fold_ok(const DevWeight &W, int32_t M, int32_t G);
 // CU count of the calling thread's current HIP device (cached per ordinal).
 int device_cu_count();
 
-// z = f16((pos[i] + (type[0] + word[id])) * gamma) and the (mean, 1/sigma) of
-// the f32 sum, for every valid token (bert.cpp:963-984).
+// z = f16((pos[i] + (type[ty] + word[id])) * gamma) and the (mean, 1/sigma) of
+// the f32 sum, for every valid token (bert.cpp:963-984).  types (both embedding
+// launchers): int32 [T] token type ids packed as ids, every value 0 or 1 (trusted:
+// the table has two rows), ty = types[t]; null: ty = 0, the kernel without the load.
 void launch_embed_ln(const DevTable &word, const DevTable &type, const DevTable &pos, const float *ln_w,
                      const int32_t *ids, const int32_t *cu, int32_t n_seqs, int32_t max_len, int32_t d, uint16_t *z,
-                     float2 *stats, hipStream_t s);
+                     float2 *stats, hipStream_t s, const int32_t *types = nullptr);
 
 // stats[t] = (mean, 1/sqrt(var + 1e-5)) of rows t < rows from the G = d/32 group
 // partials part[g * stride + t] a residual GEMM wrote (ggml_norm, bert.cpp:1048-1056).
@@ -163,7 +165,7 @@ int launch_attention_cls(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs,
 // x = LN(pos + (type + word)) with gamma/beta (bert.cpp:963-984).
 void launch_f32_embed_ln(const DevTable &word, const DevTable &type, const DevTable &pos, const float *ln_w,
                          const float *ln_b, const int32_t *ids, const int32_t *cu, int32_t n_seqs, int32_t max_len,
-                         int32_t d, float *x, hipStream_t s, bool exact = false);
+                         int32_t d, float *x, hipStream_t s, bool exact = false, const int32_t *types = nullptr);
 // In-place LayerNorm of rows [0, rows) (ggml_norm, f64 sums, eps 1e-5).  exact (both
 // LayerNorm launchers; the q8-activation chain): scale, gamma and beta as three
 // operations the compiler cannot contract, the reference's roundings bit for bit.
@@ -230,6 +232,26 @@ int launch_search(const void *corpus, int64_t n_rows, int d, const float *d_quer
                   float *d_scores, int32_t *d_ids, hipStream_t s);
 // Benches: out f32 [n][d] (device) = unit rows of hashed values.
 int launch_unit_rows(float *d_out, int64_t n, int d, uint32_t seed, hipStream_t s);
+
+// ---- the classification head (head.hip): pooler dense + tanh + classifier on the
+// sentences' [CLS] rows, all f32, one form for the three chains ----
+constexpr int HEAD_MAX_LABELS = 16;
+// x f32 [n_seqs][d] = the final-LayerNorm row of each sentence's first token, not
+// normalised.  f16 chain: LN(y[row]) by the LN-fold expression of launch_cls_l2 /
+// launch_tokens_f32 from z and the row statistics, row = cu[b], or b when cu is null
+// (the compact rows of the pruned last layer).  f32 / q8 chains: row cu[b] of x32.
+void launch_head_gather(const uint16_t *z, const float2 *stats, const float *ln_w, const float *ln_b, const int32_t *cu,
+                        int32_t n_seqs, int32_t d, float *x, hipStream_t s);
+void launch_head_gather_f32(const float *x32, const int32_t *cu, int32_t n_seqs, int32_t d, float *x, hipStream_t s);
+// logits f32 [n_seqs][n_labels] = wc tanh(x wp^T + bp) + bc: wp f32 [d][d] (rows =
+// output features), wc f32 [n_labels][d]; p f32 [n_seqs][d] receives the pooler
+// output.  Two launches: the pooler GEMM on v_mfma_f32_16x16x4_f32 over (16 feature,
+// 16 sentence) tiles (wp is read once per 16 sentences), then one wave per sentence
+// for the classifier.  Every sum runs in an order fixed by d alone, so a sentence's
+// logits do not depend on n_seqs, its row or the other rows, bit for bit.
+// d % 64 == 0, d <= 1024, 1 <= n_labels <= HEAD_MAX_LABELS; returns -1 otherwise.
+int launch_head(const float *x, int32_t n_seqs, int32_t d, const float *wp, const float *bp, const float *wc,
+                const float *bc, int32_t n_labels, float *p, float *logits, hipStream_t s);
 
 // Diagnostics: *cnt += number of non-finite values in p[0..n) (f32, or f16 if f16).
 void launch_count_nonfinite(const void *p, size_t n, int f16, unsigned *cnt, hipStream_t s);

@@ -137,6 +137,11 @@ HostTensor *slot(HostModel &m, const std::string &name, int32_t &e0, int32_t &e1
     vec = true; e1 = 1;
     if (name == "embeddings.LayerNorm.weight") { e0 = d; return &m.ln_e_w; }
     if (name == "embeddings.LayerNorm.bias") { e0 = d; return &m.ln_e_b; }
+    // the optional head; e1 = -1: the classifier's row count is the file's (n_labels)
+    if (name == "pooler.dense.bias") { e0 = d; return &m.pool_b; }
+    if (name == "classifier.bias") { e0 = -1; return &m.cls_b; }
+    if (name == "pooler.dense.weight") { vec = false; e0 = d; e1 = d; return &m.pool_w; }
+    if (name == "classifier.weight") { vec = false; e0 = d; e1 = -1; return &m.cls_w; }
     static const std::string pre = "encoder.layer.";
     if (name.compare(0, pre.size(), pre) != 0) return nullptr;
     size_t pos = pre.size(), end = name.find('.', pos);
@@ -219,10 +224,14 @@ bool load_model_file(const char *path, HostModel &m, std::string &err, bool verb
         bool vec = false;
         HostTensor *t = slot(m, name, e0, e1, vec);
         if (!t) { err = "unknown tensor '" + name + "' in model file"; return false; }
+        // the classifier: [d][n_labels] (always 2-D) and [n_labels], 1 <= n_labels <= kMaxLabels
+        const bool cls_w = t == &m.cls_w, cls_b = t == &m.cls_b;
+        if (cls_w && n_dims == 2 && ne[1] >= 1 && ne[1] <= kMaxLabels) e1 = ne[1];
+        if (cls_b && ne[0] >= 1 && ne[0] <= kMaxLabels) e0 = ne[0];
         if (ne[0] != e0 || ne[1] != e1) { err = "tensor '" + name + "' has wrong shape in model file"; return false; }
         if (!fmt_valid(fmt)) { err = "unknown ftype " + std::to_string(fmt) + " in model file"; return false; }
-        if (vec && fmt != FMT_F32) { err = "tensor '" + name + "' must be f32"; return false; }
-        if (!vec && fmt != m.hp.ftype) {
+        if ((vec || cls_w) && fmt != FMT_F32) { err = "tensor '" + name + "' must be f32"; return false; }
+        if (!vec && !cls_w && fmt != m.hp.ftype) {
             err = "tensor '" + name + "' has wrong size in model file";
             return false;
         }
@@ -246,6 +255,17 @@ bool load_model_file(const char *path, HostModel &m, std::string &err, bool verb
                                    &L.i_b, &L.o2_b, &L.ln_att_w, &L.ln_att_b, &L.ln_out_w, &L.ln_out_b};
         for (const HostTensor *t : all)
             if (!t->present()) { err = "missing tensor in encoder.layer." + std::to_string(l); return false; }
+    }
+    const int n_head_recs = (int)m.pool_w.present() + m.pool_b.present() + m.cls_w.present() + m.cls_b.present();
+    if (n_head_recs != 0 && n_head_recs != 4) {
+        err = "incomplete classification head: pooler.dense.weight, pooler.dense.bias, classifier.weight and "
+              "classifier.bias come together or not at all";
+        return false;
+    }
+    if (n_head_recs == 4) {
+        if (m.cls_b.ne0 != m.cls_w.ne1) { err = "classifier.bias does not match classifier.weight"; return false; }
+        m.n_labels = m.cls_w.ne1;
+        if (verbose) std::printf("bert_load_from_file: n_labels = %d\n", m.n_labels);
     }
     if (verbose)
         std::printf("bert_load_from_file: model size = %8.2f MB / num tensors = %d\n",
@@ -340,7 +360,9 @@ int quantize_file(const char *in, const char *out, int itype, bool verbose)
         if (h3[0] < 1 || h3[0] > 2 || !fi.read(ne, 4 * (size_t)h3[0]) || h3[1] <= 0 || h3[1] > 4096) return 1;
         std::string name((size_t)h3[1], '\0');
         if (!fi.read(&name[0], (size_t)h3[1])) return 1;
-        const bool q = h3[0] == 2 && name.size() >= 6 && name.compare(name.size() - 6, 6, "weight") == 0;
+        // (the classifier stays f32 in every ftype: copied through)
+        const bool q = name != "classifier.weight" && h3[0] == 2 && name.size() >= 6 &&
+                       name.compare(name.size() - 6, 6, "weight") == 0;
         if (!fmt_valid(h3[2])) return 1;
         std::vector<uint8_t> src(fmt_row_bytes(h3[2], ne[0]) * (size_t)ne[1]);
         if (!fi.read(src.data(), src.size())) return 1;

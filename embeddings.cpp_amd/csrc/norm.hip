@@ -59,9 +59,12 @@ __device__ __forceinline__ h16 f16_of_product(float a, float b)
 // resident waves per SIMD the register budget is held to (no spills at these)
 constexpr int emb_occ(int tf) { return tf == FMT_Q4_0 || tf == FMT_F16 ? 8 : tf < 0 ? 4 : 6; }
 
-template <int TF>
+// TY: token t reads row types[t] of the type table (values in {0, 1}, trusted); without
+// it every token reads row 0, by the same instructions as before the types existed.
+template <int TF, bool TY>
 __global__ __launch_bounds__(256, emb_occ(TF)) void embed_ln_kernel(DevTable word, DevTable type, DevTable pos,
                                                        const float *__restrict__ ln_w, const int32_t *__restrict__ ids,
+                                                       const int32_t *__restrict__ types,
                                                        const int32_t *__restrict__ cu, int d, h16 *__restrict__ z,
                                                        float2 *__restrict__ stats)
 {
@@ -74,11 +77,12 @@ __global__ __launch_bounds__(256, emb_occ(TF)) void embed_ln_kernel(DevTable wor
     float v[32];
     float s = 0.f;
     if (act) {
-        // pos + (type[0] + word[id]) in the reference's operand order (bert.cpp:968-973), f32
+        // pos + (type[ty] + word[id]) in the reference's operand order (bert.cpp:968-973), f32
         // (one table at a time into a 32-value temporary: 64 live values, not 128)
         float tmp[32];
         emb_table32<TF>(word, ids[t], l32, v);
-        emb_table32<TF>(type, 0, l32, tmp);
+        if constexpr (TY) emb_table32<TF>(type, types[t], l32, tmp);
+        else emb_table32<TF>(type, 0, l32, tmp);
 #pragma unroll
         for (int e = 0; e < 32; ++e) v[e] = tmp[e] + v[e];
         emb_table32<TF>(pos, i, l32, tmp);
@@ -358,11 +362,15 @@ void launch_count_nonfinite(const void *p, size_t n, int f16, unsigned *cnt, hip
 
 void launch_embed_ln(const DevTable &word, const DevTable &type, const DevTable &pos, const float *ln_w,
                      const int32_t *ids, const int32_t *cu, int32_t n_seqs, int32_t max_len, int32_t d, uint16_t *z,
-                     float2 *stats, hipStream_t s)
+                     float2 *stats, hipStream_t s, const int32_t *types)
 {
     dim3 grid((max_len + 7) / 8, n_seqs);
     const int f = word.fmt == type.fmt && word.fmt == pos.fmt ? word.fmt : -1;
-#define EMB_LAUNCH(TF) embed_ln_kernel<TF><<<grid, 256, 0, s>>>(word, type, pos, ln_w, ids, cu, d, (h16 *)z, stats)
+#define EMB_LAUNCH(TF)                                                                                              \
+    do {                                                                                                            \
+        if (types) embed_ln_kernel<TF, true><<<grid, 256, 0, s>>>(word, type, pos, ln_w, ids, types, cu, d, (h16 *)z, stats); \
+        else embed_ln_kernel<TF, false><<<grid, 256, 0, s>>>(word, type, pos, ln_w, ids, nullptr, cu, d, (h16 *)z, stats);    \
+    } while (0)
     switch (f) {
     case FMT_F32: EMB_LAUNCH(FMT_F32); break;
     case FMT_F16: EMB_LAUNCH(FMT_F16); break;

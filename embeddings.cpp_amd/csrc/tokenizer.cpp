@@ -4,6 +4,7 @@
 #include "tokenizer.h"
 
 #include <algorithm>
+#include <climits>
 #include <cstring>
 #include <vector>
 #include <utility>
@@ -321,6 +322,53 @@ int32_t Vocab::tokenize(const char *text, int32_t n_max_tokens, int32_t *out, in
     }
     emit(102);
     return t;
+}
+
+void Vocab::pieces(const char *text, std::vector<int32_t> &out) const
+{
+    // every id consumes at least one byte of the text, so strlen + 2 holds them all;
+    // the loop covers a text that proves otherwise
+    size_t cap = std::strlen(text) + 2;
+    for (;;) {
+        out.resize(cap);
+        const int32_t n = tokenize(text, INT32_MAX, out.data(), (int32_t)std::min<size_t>(cap, INT32_MAX));
+        if ((size_t)n <= cap) {
+            out.erase(out.begin() + (n - 1), out.end());   // [SEP] and the unused tail
+            out.erase(out.begin());                        // [CLS]
+            return;
+        }
+        cap = (size_t)n;
+    }
+}
+
+int32_t Vocab::pair_layout(const int32_t *pa, int32_t la, const int32_t *pb, int32_t lb, bool truncate, int32_t n_max,
+                           int32_t *ids, int32_t *types, int32_t *n_tokens)
+{
+    if (n_max < 3) return -1;
+    const int64_t m = (int64_t)n_max - 3;
+    int64_t ka = la, kb = lb;
+    if (ka + kb > m) {
+        if (!truncate) {
+            *n_tokens = (int32_t)std::min<int64_t>(ka + kb + 3, INT32_MAX);
+            return -4;
+        }
+        const int64_t sh = std::min(ka, kb);
+        if (2 * sh <= m) {
+            (ka <= kb ? kb : ka) = m - sh;
+        } else {
+            ka = (m + 1) / 2;
+            kb = m / 2;
+        }
+    }
+    int32_t t = 0;
+    auto put = [&](int32_t id, int32_t ty) { ids[t] = id; types[t] = ty; ++t; };
+    put(101, 0);
+    for (int64_t i = 0; i < ka; ++i) put(pa[i], 0);
+    put(102, 0);
+    for (int64_t i = 0; i < kb; ++i) put(pb[i], 1);
+    put(102, 1);
+    *n_tokens = t;
+    return 0;
 }
 
 }  // namespace emb

@@ -21,6 +21,20 @@ public:
     // the first `cap` are stored.
     int32_t tokenize(const char *text, int32_t n_max_tokens, int32_t *out, int32_t cap) const;
 
+    // The WordPiece ids of `text` alone: what tokenize gives with no token limit,
+    // without its [CLS] and [SEP].
+    void pieces(const char *text, std::vector<int32_t> &out) const;
+
+    // One (A, B) pair as a cross-encoder reads it: [CLS] A [SEP] B [SEP] with token
+    // types 0 for [CLS] A [SEP] and 1 for B [SEP] (an empty B keeps its [SEP]).  The
+    // pieces share the budget m = n_max - 3.  Over budget without `truncate`: -4, with
+    // *n_tokens the full count and nothing stored.  With it, HF's longest_first in
+    // closed form, s the shorter side: 2 s <= m keeps it whole and m - s of the longer;
+    // else A keeps ceil(m / 2) and B floor(m / 2); tokens drop from the end of a side.
+    // Returns 0 with *n_tokens ids and types stored (at most n_max); -1 for n_max < 3.
+    static int32_t pair_layout(const int32_t *pa, int32_t la, const int32_t *pb, int32_t lb, bool truncate,
+                               int32_t n_max, int32_t *ids, int32_t *types, int32_t *n_tokens);
+
     // bert_vocab_id_to_token semantics (bert.cpp:121-134).
     const char *id_to_token(int32_t id) const;
 

@@ -3,6 +3,8 @@
 // writes dir-model/ggml-model-{f32,f16}.bin, or dir-model/ggml-model.bin when
 // ftype is omitted (the script's fname_out before the argument is parsed).
 // Reads only a local directory: there is no hub download.
+//   convert dir-model ftype --head   a BertForSequenceClassification checkpoint (a
+// cross-encoder reranker): the same file followed by the pooler and classifier records.
 #include "bert_hip.h"
 
 #include <cstdio>
@@ -27,7 +29,9 @@ int main(int argc, char **argv)
         }
         out = dir + (ftype == 0 ? "/ggml-model-f32.bin" : "/ggml-model-f16.bin");
     }
-    if (bertx_convert_hf(dir.c_str(), out.c_str(), ftype) != 0) return 1;
+    const bool head = argc > 3 && std::string(argv[3]) == "--head";
+    if ((head ? bertx_convert_hf_head(dir.c_str(), out.c_str(), ftype) : bertx_convert_hf(dir.c_str(), out.c_str(), ftype)) != 0)
+        return 1;
     std::printf("Done. Output file: %s\n\n", out.c_str());
     return 0;
 }

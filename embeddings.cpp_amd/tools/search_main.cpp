@@ -2,12 +2,17 @@
 // corpus, then print the k closest texts of every query) with the corpus resident on
 // the GPU and the search fused there (bertx_index_*).
 //
-// usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads]
+// usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-r RERANK_MODEL [-c N]]
 // One text per line of CORPUS.txt; queries from stdin, one per line, `q` or EOF ends.
 // Per hit one line: rank<TAB>id<TAB>score<TAB>text.
+// -r: a second stage.  Per query the N best of the index (default 4 k, at most the
+// index's 128) are re-scored as (query, text) pairs by the cross-encoder RERANK_MODEL
+// (a model file with a classification head, bertx_rerank) and the k best of those are
+// printed, ordered by the reranker's first-label logit, which is the printed score.
 #include "bert.h"
 #include "bert_hip.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,18 +23,22 @@
 
 int main(int argc, char **argv)
 {
-    const char *model = nullptr, *corpus = nullptr;
-    int k = 3, threads = 4;
+    const char *model = nullptr, *corpus = nullptr, *rerank = nullptr;
+    int k = 3, threads = 4, cand = 0;
     for (int i = 1; i < argc; ++i) {
         const bool has = i + 1 < argc;
         if (!std::strcmp(argv[i], "-m") && has) model = argv[++i];
         else if (!std::strcmp(argv[i], "-f") && has) corpus = argv[++i];
         else if (!std::strcmp(argv[i], "-k") && has) k = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "-t") && has) threads = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "-r") && has) rerank = argv[++i];
+        else if (!std::strcmp(argv[i], "-c") && has) cand = std::atoi(argv[++i]);
         else { model = nullptr; break; }
     }
-    if (!model || !corpus || k < 1 || k > 128 || threads < 1) {
-        std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads]\n", argv[0]);
+    if (rerank && cand == 0) cand = std::min(128, 4 * k);
+    if (!model || !corpus || k < 1 || k > 128 || threads < 1 || (rerank ? cand < k || cand > 128 : cand != 0)) {
+        std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads] "
+                             "[-r RERANK_MODEL [-c N (k..128, default 4 k)]]\n", argv[0]);
         return 2;
     }
     std::vector<std::string> texts;
@@ -53,8 +62,19 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "search: cannot load '%s'\n", model);
         return 1;
     }
+    bert_ctx *rctx = nullptr;
+    if (rerank) {
+        rctx = bert_load_from_file(rerank);
+        if (!rctx || bertx_n_labels(rctx) < 1) {
+            std::fprintf(stderr, "search: '%s' %s\n", rerank, rctx ? "has no classification head" : "cannot be loaded");
+            if (rctx) bert_free(rctx);
+            bert_free(ctx);
+            return 1;
+        }
+    }
     bertx_index *idx = bertx_index_create(ctx, 0, (int32_t)texts.size());
     if (!idx) {
+        if (rctx) bert_free(rctx);
         bert_free(ctx);
         return 1;
     }
@@ -68,23 +88,51 @@ int main(int argc, char **argv)
             rc = 1;
         }
     }
-    std::vector<float> scores((size_t)k);
-    std::vector<int32_t> ids((size_t)k);
+    const int kq = rerank ? cand : k;   // what the index is asked for
+    std::vector<float> scores((size_t)kq);
+    std::vector<int32_t> ids((size_t)kq);
     for (std::string q; rc == 0 && std::getline(std::cin, q);) {
         if (!q.empty() && q.back() == '\r') q.pop_back();
         if (q == "q") break;
         if (q.empty()) continue;
         const char *qp = q.c_str();
-        if (bertx_index_search_texts(idx, ctx, threads, 1, &qp, k, scores.data(), ids.data()) != 0) {
+        if (bertx_index_search_texts(idx, ctx, threads, 1, &qp, kq, scores.data(), ids.data()) != 0) {
             std::fprintf(stderr, "search: query failed\n");
             rc = 1;
             break;
+        }
+        if (rctx) {
+            // the candidates re-scored as (query, text) pairs; the k best by the first logit,
+            // equal logits in the index's order
+            int n = 0;
+            while (n < kq && ids[(size_t)n] >= 0) ++n;
+            const int nl = bertx_n_labels(rctx);
+            std::vector<const char *> docs((size_t)n);
+            for (int j = 0; j < n; ++j) docs[(size_t)j] = texts[(size_t)ids[(size_t)j]].c_str();
+            std::vector<float> logits((size_t)n * nl);
+            if (n && bertx_rerank(rctx, threads, qp, n, docs.data(), 1, logits.data()) != 0) {
+                std::fprintf(stderr, "search: reranking failed\n");
+                rc = 1;
+                break;
+            }
+            std::vector<int> ord((size_t)n);
+            for (int j = 0; j < n; ++j) ord[(size_t)j] = j;
+            std::stable_sort(ord.begin(), ord.end(),
+                             [&](int a, int b) { return logits[(size_t)a * nl] > logits[(size_t)b * nl]; });
+            for (int j = 0; j < k && j < n; ++j) {
+                const int c = ord[(size_t)j];
+                std::printf("%d\t%d\t%.4f\t%s\n", j + 1, ids[(size_t)c], logits[(size_t)c * nl],
+                            texts[(size_t)ids[(size_t)c]].c_str());
+            }
+            std::fflush(stdout);
+            continue;
         }
         for (int j = 0; j < k && ids[(size_t)j] >= 0; ++j)
             std::printf("%d\t%d\t%.4f\t%s\n", j + 1, ids[(size_t)j], scores[(size_t)j], texts[(size_t)ids[(size_t)j]].c_str());
         std::fflush(stdout);
     }
     bertx_index_free(idx);
+    if (rctx) bert_free(rctx);
     bert_free(ctx);
     return rc;
 }

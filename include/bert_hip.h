@@ -439,6 +439,85 @@ BERT_API int32_t bertx_index_search_texts(struct bertx_index *idx, struct bert_c
                                           const char **texts, int32_t k, float *scores, int32_t *ids);
 
 /*
+ * Cross-encoder reranking: token types and a classification head.
+ *
+ * Model file.  Four optional records behind the encoder's: pooler.dense.weight
+ * [d][d] in the header ftype (the quantizer quantizes it), pooler.dense.bias [d] f32,
+ * classifier.weight ne = {d, n_labels}, always 2-D and f32 in every ftype (the
+ * quantizer copies it through), classifier.bias [n_labels] f32; 1 <= n_labels <= 16.
+ * All four or none: a partial head is a load error.  A file without them loads and
+ * runs as before.  bertx_convert_hf_head is bertx_convert_hf followed by the four
+ * records, from a BertForSequenceClassification directory (pooler.dense.* or
+ * bert.pooler.dense.*, un-prefixed classifier.*); it refuses (message, non-zero) a
+ * checkpoint without a classifier or a pooler.  bertx_n_labels: the head's label
+ * count, 0 for a file without one; works on tokenizer-only contexts.
+ *
+ * bertx_tokenize_pair: one (A, B) pair as [CLS] A [SEP] B [SEP], types 0 for [CLS] A
+ * [SEP] and 1 for B [SEP] (an empty B keeps its [SEP]).  The WordPiece ids of each
+ * text are bert_tokenize's for that text alone.  The pieces share m = n_max - 3.
+ * truncate 0: a pair over budget is refused ("Too many tokens"), -4, *n_tokens the
+ * full count, ids / types untouched.  truncate 1: Hugging Face's longest_first in
+ * closed form; with s the shorter side, 2 s <= m keeps it whole and m - s pieces of
+ * the longer, otherwise A keeps ceil(m / 2) and B floor(m / 2); pieces drop from the
+ * end of a side.  Returns 0 with *n_tokens <= n_max ids and types stored; -1 for bad
+ * arguments (n_max < 3).  Works on tokenizer-only contexts.
+ *
+ * bertx_forward_device_ex: bertx_forward_device with token types and a named output.
+ * d_types: int32[total_tokens] on that GPU, packed as d_ids, or NULL for all 0 (then
+ * POOLED and TOKENS give the bits of bertx_forward_device and
+ * bertx_forward_tokens_device).  The device entry trusts every type to be 0 or 1:
+ * the type table has two rows and another value reads outside it; the host entries
+ * below check.  BERTX_OUT_LOGITS writes float[n_seqs][n_labels], the raw logits
+ * classifier(tanh(pooler(final LayerNorm row of [CLS]))): no sigmoid or softmax is
+ * applied.  Under the f16-activation chain with CLS pruning on (bertx_set_cls_pruning)
+ * the last layer runs on the sentences' first rows only, whatever the pooling mode.
+ * A sentence's logits depend on its own ids and types only, bit for bit: not on its
+ * place in the batch, the other sentences or n_seqs.  Returns as bertx_forward_device;
+ * -6 for LOGITS on a file without a head, -1 for an unknown out_kind.
+ *
+ * Host entries (routing, chunking and replicas as bert_forward_batch; outputs at the
+ * caller's indices; on any refusal a message, a negative return and logits
+ * untouched): bertx_score_ids takes pre-tokenised pairs (types outside {0, 1}: -1; an
+ * input over n_max_tokens: -4) into logits float[n][n_labels]; bertx_score_pairs
+ * tokenises texts_a[i] / texts_b[i] with bertx_tokenize_pair's rule at n_max_tokens
+ * on n_threads threads of the library's pool; bertx_rerank is bertx_score_pairs with
+ * the query as every A, tokenised once.  -6 for a file without a head.
+ */
+enum { BERTX_OUT_POOLED = 0, BERTX_OUT_TOKENS = 1, BERTX_OUT_LOGITS = 2 };
+BERT_API int32_t bertx_convert_hf_head(const char *dir_model, const char *fname_out, int32_t ftype);
+BERT_API int32_t bertx_n_labels(struct bert_ctx *ctx);
+BERT_API int32_t bertx_tokenize_pair(struct bert_ctx *ctx, const char *text_a, const char *text_b, int32_t truncate,
+                                     bert_vocab_id *ids, int32_t *types, int32_t *n_tokens, int32_t n_max);
+BERT_API int32_t bertx_forward_device_ex(struct bert_ctx *ctx, int32_t slot, const int32_t *d_ids,
+                                         const int32_t *d_types, const int32_t *d_cu, int32_t n_seqs, int32_t max_len,
+                                         int32_t total_tokens, int32_t out_kind, float *d_out, void *stream);
+BERT_API int32_t bertx_score_ids(struct bert_ctx *ctx, int32_t n, bert_vocab_id **ids, int32_t **types,
+                                 int32_t *n_tokens, float *logits);
+BERT_API int32_t bertx_score_pairs(struct bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts_a,
+                                   const char **texts_b, int32_t truncate, float *logits);
+BERT_API int32_t bertx_rerank(struct bert_ctx *ctx, int32_t n_threads, const char *query, int32_t n_docs,
+                              const char **docs, int32_t truncate, float *logits);
+
+/*
+ * Parity hooks of the head and of the typed embedding kernels (host buffers, device
+ * 0; the rules of the row-kernel hooks above).  bertx_test_head: x f32 [n][d] (the
+ * [CLS] rows), wp f32 [d][d], bp [d], wc f32 [n_labels][d], bc [n_labels] -> out f32
+ * [out_rows][n_labels], rows < n = wc tanh(x wp^T + bp) + bc as the forward computes
+ * it.  The device output starts as the caller's bytes (pre-fill NaN bits: rows n ..
+ * out_rows - 1 must come back untouched) with guard rows of NaN bits behind it; -5: a
+ * guard row was written.  bertx_test_embed_ln_types: bertx_test_embed_ln with types
+ * int32 [T] (values 0 or 1, checked), or NULL for the kernel without types.
+ */
+BERT_API int32_t bertx_test_head(const float *x, int32_t n, int32_t d, const float *wp, const float *bp,
+                                 const float *wc, const float *bc, int32_t n_labels, float *out, int32_t out_rows);
+BERT_API int32_t bertx_test_embed_ln_types(int32_t mode, int32_t fmt_word, int32_t fmt_type, int32_t fmt_pos,
+                                           int32_t rows_word, int32_t rows_pos, int32_t d, const void *word_rows,
+                                           const void *type_rows, const void *pos_rows, const float *ln_w,
+                                           const float *ln_b, const int32_t *ids, const int32_t *types,
+                                           const int32_t *cu, int32_t n_seqs, int32_t max_len, void *out,
+                                           float *stats, int32_t out_rows);
+
+/*
  * Search micro-benchmark (device 0, no context): an index of N random unit rows of
  * width d, B random unit queries; average device time of `iters` calls of
  * bertx_index_search_device for the k best, after 3 warm-up calls.
