@@ -153,6 +153,12 @@ def load_lib(path=None):
     try:   # (the embedding index: absent from older BERT_LIB builds)
         L.bertx_index_create.restype = vp
         L.bertx_index_create.argtypes = [vp, c_i32, c_i32]
+        L.bertx_index_create_ex.restype = vp
+        L.bertx_index_create_ex.argtypes = [vp, c_i32, c_i32, c_i32]
+        L.bertx_index_storage.restype = c_i32
+        L.bertx_index_storage.argtypes = [vp]
+        L.bertx_index_rows_i8.restype = c_i32
+        L.bertx_index_rows_i8.argtypes = [vp, c_i32, c_i32, vp, vp]
         L.bertx_index_free.restype = None
         L.bertx_index_free.argtypes = [vp]
         for fn in (L.bertx_index_clear, L.bertx_index_size, L.bertx_index_capacity, L.bertx_index_dim):
@@ -176,6 +182,10 @@ def load_lib(path=None):
         L.bertx_bench_search.argtypes = [c_i32] * 5 + [c_f32p]
         L.bertx_bench_search_add_rate.restype = c_i32
         L.bertx_bench_search_add_rate.argtypes = [c_i32, c_i32, ctypes.POINTER(ctypes.c_double)]
+        L.bertx_bench_search_ex.restype = c_i32
+        L.bertx_bench_search_ex.argtypes = [c_i32] * 6 + [c_f32p]
+        L.bertx_bench_search_add_rate_ex.restype = c_i32
+        L.bertx_bench_search_add_rate_ex.argtypes = [c_i32, c_i32, c_i32, ctypes.POINTER(ctypes.c_double)]
     except AttributeError:
         pass
     try:   # (cross-encoder reranking: absent from older BERT_LIB builds)
@@ -453,15 +463,22 @@ class BertModel:
 
 class BertIndex:
     """A device-resident embedding index with fused top-k search (bertx_index_*): rows of
-    the model's n_embd, stored as f16 on GPU `slot` of the model's context; ids are the
-    insertion order.  Scores are dot products (cosines, for the model's unit rows)."""
+    the model's n_embd, stored as f16 (storage="f16") or as int8 with one f32 scale per
+    row (storage="int8", half the bytes) on GPU `slot` of the model's context; ids are
+    the insertion order.  Scores are dot products (cosines, for the model's unit rows);
+    bert_hip.h gives the arithmetic of both kinds."""
 
-    def __init__(self, model, capacity, slot=0):
+    STORAGE = {"f16": 0, "int8": 1}
+
+    def __init__(self, model, capacity, slot=0, storage="f16"):
+        if storage not in self.STORAGE:
+            raise ValueError("storage must be 'f16' or 'int8', got %r" % (storage,))
         self.model = model
         self.lib = model.lib
-        self.idx = self.lib.bertx_index_create(model.ctx, slot, capacity)
+        self.storage = storage
+        self.idx = self.lib.bertx_index_create_ex(model.ctx, slot, capacity, self.STORAGE[storage])
         if not self.idx:
-            raise RuntimeError("bertx_index_create failed")
+            raise RuntimeError("bertx_index_create_ex failed")
         self.dim = int(self.lib.bertx_index_dim(self.idx))
         self.capacity = int(self.lib.bertx_index_capacity(self.idx))
 
@@ -527,11 +544,20 @@ class BertIndex:
         return scores, ids
 
     def rows(self, first, n):
-        """The stored rows first .. first + n - 1: the exact f16 values as f32 [n][dim]."""
+        """The stored rows first .. first + n - 1 as f32 [n][dim]: the exact f16 values, or
+        the dequantized q * scale of an int8 index."""
         out = np.zeros((n, self.dim), np.float32)
         if n and self.lib.bertx_index_rows(self.idx, first, n, out.ctypes.data) != 0:
             raise RuntimeError("bertx_index_rows failed")
         return out
+
+    def rows_i8(self, first, n):
+        """(q int8 [n][dim], scale f32 [n]): the stored bytes and scales of an int8 index."""
+        q = np.zeros((n, self.dim), np.int8)
+        scale = np.zeros(n, np.float32)
+        if n and self.lib.bertx_index_rows_i8(self.idx, first, n, q.ctypes.data, scale.ctypes.data) != 0:
+            raise RuntimeError("bertx_index_rows_i8 failed")
+        return q, scale
 
 
 # ---------------------------------------------------------------------------

@@ -328,8 +328,8 @@ private:
 int hip_device_count();
 
 // An embedding index (index.cpp, bert_hip.h bertx_index_*) of `capacity` rows of width
-// d on device `ordinal`, without a context (bertx_index_create, the search bench).
-// NULL after a message.
-::bertx_index *index_create_on(int ordinal, int d, int64_t capacity);
+// d on device `ordinal`, stored as BERTX_INDEX_F16 or _I8, without a context
+// (bertx_index_create_ex, the search bench).  NULL after a message.
+::bertx_index *index_create_on(int ordinal, int d, int64_t capacity, int storage);
 
 }  // namespace emb

@@ -565,9 +565,9 @@ struct IndexHolder {
 // An index of N unit rows on device 0, filled by device-form adds of kFill rows from
 // a staging buffer of hashed values, all on stream s; fill_ms (if not null): the adds' device time.
 constexpr int64_t kFill = 65536;
-int bench_index(int32_t d, int32_t N, HookBufs &B, IndexHolder &H, hipStream_t s, float *fill_ms)
+int bench_index(int32_t d, int32_t N, int32_t storage, HookBufs &B, IndexHolder &H, hipStream_t s, float *fill_ms)
 {
-    H.ix = index_create_on(0, d, N);
+    H.ix = index_create_on(0, d, N, storage);
     if (!H.ix) return -1;
     const int64_t chunk = std::min<int64_t>(kFill, N);
     float *rows = (float *)B.up(nullptr, 0, (size_t)chunk * d * 4);
@@ -607,6 +607,12 @@ struct StreamHolder {
 
 extern "C" int32_t bertx_bench_search(int32_t d, int32_t N, int32_t B, int32_t k, int32_t iters, float *avg_us)
 {
+    return bertx_bench_search_ex(d, N, B, k, BERTX_INDEX_F16, iters, avg_us);
+}
+
+extern "C" int32_t bertx_bench_search_ex(int32_t d, int32_t N, int32_t B, int32_t k, int32_t storage, int32_t iters,
+                                         float *avg_us)
+{
     using namespace emb;
     if (N <= 0 || B <= 0 || iters <= 0 || !avg_us || hip_device_count() == 0) return -1;
     DeviceGuard guard(0);
@@ -615,7 +621,7 @@ extern "C" int32_t bertx_bench_search(int32_t d, int32_t N, int32_t B, int32_t k
     IndexHolder H;
     StreamHolder S;   // destroyed (after a synchronise) before the index and the buffers
     HIP_RC(hipStreamCreateWithFlags(&S.s, hipStreamNonBlocking));
-    if (bench_index(d, N, bufs, H, S.s, nullptr) != 0) return -1;
+    if (bench_index(d, N, storage, bufs, H, S.s, nullptr) != 0) return -1;
     float *q = (float *)bufs.up(nullptr, 0, (size_t)B * d * 4);
     float *sc = (float *)bufs.up(nullptr, 0, (size_t)B * 128 * 4);
     int32_t *id = (int32_t *)bufs.up(nullptr, 0, (size_t)B * 128 * 4);
@@ -637,6 +643,11 @@ extern "C" int32_t bertx_bench_search(int32_t d, int32_t N, int32_t B, int32_t k
 
 extern "C" int32_t bertx_bench_search_add_rate(int32_t d, int32_t N, double *add_rows_per_s)
 {
+    return bertx_bench_search_add_rate_ex(d, N, BERTX_INDEX_F16, add_rows_per_s);
+}
+
+extern "C" int32_t bertx_bench_search_add_rate_ex(int32_t d, int32_t N, int32_t storage, double *add_rows_per_s)
+{
     using namespace emb;
     if (N <= 0 || !add_rows_per_s || hip_device_count() == 0) return -1;
     DeviceGuard guard(0);
@@ -646,7 +657,7 @@ extern "C" int32_t bertx_bench_search_add_rate(int32_t d, int32_t N, double *add
     StreamHolder S;
     HIP_RC(hipStreamCreateWithFlags(&S.s, hipStreamNonBlocking));
     float ms = 0.f;
-    if (bench_index(d, N, bufs, H, S.s, &ms) != 0 || ms <= 0.f) return -1;
+    if (bench_index(d, N, storage, bufs, H, S.s, &ms) != 0 || ms <= 0.f) return -1;
     *add_rows_per_s = (double)N / (ms * 1e-3);
     return 0;
 }

@@ -1,7 +1,7 @@
 // The device-resident embedding index (bert_hip.h bertx_index_*): an append-only
-// matrix of f16 rows in HBM in the search kernel's fragment order (kernels.h), the
-// fused top-k search over it, and the text forms on top of bert_encode_batch.
-// After creation an index knows only its device ordinal and its width.
+// matrix of f16 or int8 rows in HBM in the search kernel's fragment order (kernels.h),
+// the fused top-k search over it, and the text forms on top of bert_encode_batch.
+// After creation an index knows only its device ordinal, its width and its storage.
 #include "bert.h"
 #include "bert_hip.h"
 
@@ -19,8 +19,10 @@
 struct bertx_index {
     int ordinal = 0;
     int d = 0;
+    int storage = BERTX_INDEX_F16;
     int64_t cap = 0, n = 0;
-    void *rows = nullptr;        // f16, ceil(cap / 16) groups in fragment order
+    void *rows = nullptr;        // f16 or int8, ceil(cap / 16) groups in fragment order
+    float *scales = nullptr;     // int8: one per row of the padded capacity
     void *scratch = nullptr;     // partial lists of one search launch
     // staging of the host forms, kStage rows or queries at a time
     float *st_rows = nullptr, *st_scores = nullptr;
@@ -37,6 +39,7 @@ struct bertx_index {
         emb::DeviceGuard g(ordinal);
         if (stream) (void)hipStreamSynchronize(stream);
         if (rows) (void)hipFree(rows);
+        if (scales) (void)hipFree(scales);
         if (scratch) (void)hipFree(scratch);
         if (st_rows) (void)hipFree(st_rows);
         if (st_scores) (void)hipFree(st_scores);
@@ -88,7 +91,7 @@ int32_t add_device_locked(bertx_index &ix, const float *d_rows, int32_t n, hipSt
     }
     {
         Ordered o(ix, s);
-        const int rc = launch_index_add(d_rows, n, ix.d, ix.n, ix.rows, s);
+        const int rc = launch_index_add(d_rows, n, ix.d, ix.n, ix.storage, ix.rows, ix.scales, s);
         if (rc != 0) return rc;
     }
     const int32_t first = (int32_t)ix.n;
@@ -101,13 +104,17 @@ int32_t search_device_locked(bertx_index &ix, const float *d_q, int32_t B, int32
 {
     if (!d_q || !d_scores || !d_ids || B < 1 || k < 1 || k > kMaxK) return -1;
     Ordered o(ix, s);
-    return launch_search(ix.rows, ix.n, ix.d, d_q, B, k, ix.scratch, d_scores, d_ids, s);
+    return launch_search(ix.rows, ix.scales, ix.storage, ix.n, ix.d, d_q, B, k, ix.scratch, d_scores, d_ids, s);
 }
 
 }  // namespace
 
-bertx_index *index_create_on(int ordinal, int d, int64_t capacity)
+bertx_index *index_create_on(int ordinal, int d, int64_t capacity, int storage)
 {
+    if (storage != BERTX_INDEX_F16 && storage != BERTX_INDEX_I8) {
+        errorf("bertx_index_create: storage %d is neither BERTX_INDEX_F16 (0) nor BERTX_INDEX_I8 (1)\n", storage);
+        return nullptr;
+    }
     if (capacity < 1 || capacity > 0x7ffffff0ll) {
         errorf("bertx_index_create: capacity %lld is not in 1 .. 2^31 - 16\n", (long long)capacity);
         return nullptr;
@@ -126,11 +133,14 @@ bertx_index *index_create_on(int ordinal, int d, int64_t capacity)
     ix->ordinal = ordinal;
     ix->d = d;
     ix->cap = capacity;
-    const size_t row_bytes = (size_t)((capacity + 15) / 16) * 16 * (size_t)d * 2;
+    ix->storage = storage;
+    const size_t padded = (size_t)((capacity + 15) / 16) * 16;
+    const size_t row_bytes = padded * (size_t)d * (storage == BERTX_INDEX_I8 ? 1 : 2);
     const size_t scratch_bytes = (size_t)64 * (size_t)search_max_workgroups(capacity) * kMaxK * 8;
     const bool ok = search_prepare_device() == 0 && hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&ix->done, hipEventDisableTiming) == hipSuccess &&
                     hipMalloc(&ix->rows, row_bytes) == hipSuccess && hipMalloc(&ix->scratch, scratch_bytes) == hipSuccess &&
+                    (storage != BERTX_INDEX_I8 || hipMalloc((void **)&ix->scales, padded * 4) == hipSuccess) &&
                     hipMalloc((void **)&ix->st_rows, (size_t)kStage * d * 4) == hipSuccess &&
                     hipMalloc((void **)&ix->st_scores, (size_t)kStage * kMaxK * 4) == hipSuccess &&
                     hipMalloc((void **)&ix->st_ids, (size_t)kStage * kMaxK * 4) == hipSuccess;
@@ -152,8 +162,17 @@ extern "C" {
 
 struct bertx_index *bertx_index_create(struct bert_ctx *ctx, int32_t slot, int32_t capacity_rows)
 {
+    return bertx_index_create_ex(ctx, slot, capacity_rows, BERTX_INDEX_F16);
+}
+
+struct bertx_index *bertx_index_create_ex(struct bert_ctx *ctx, int32_t slot, int32_t capacity_rows, int32_t storage)
+{
     if (!ctx) {
         emb::errorf("bertx_index_create: no context\n");
+        return nullptr;
+    }
+    if (storage != BERTX_INDEX_F16 && storage != BERTX_INDEX_I8) {
+        emb::errorf("bertx_index_create: storage %d is neither BERTX_INDEX_F16 (0) nor BERTX_INDEX_I8 (1)\n", storage);
         return nullptr;
     }
     if (bertx_num_devices(ctx) == 0) {
@@ -165,7 +184,7 @@ struct bertx_index *bertx_index_create(struct bert_ctx *ctx, int32_t slot, int32
         emb::errorf("bertx_index_create: slot %d is not one of the context's %d device(s)\n", slot, bertx_num_devices(ctx));
         return nullptr;
     }
-    return emb::index_create_on(ordinal, bert_n_embd(ctx), capacity_rows);
+    return emb::index_create_on(ordinal, bert_n_embd(ctx), capacity_rows, storage);
 }
 
 void bertx_index_free(struct bertx_index *idx) { delete idx; }
@@ -187,6 +206,7 @@ int32_t bertx_index_size(struct bertx_index *idx)
 
 int32_t bertx_index_capacity(struct bertx_index *idx) { return idx ? (int32_t)idx->cap : -1; }
 int32_t bertx_index_dim(struct bertx_index *idx) { return idx ? idx->d : -1; }
+int32_t bertx_index_storage(struct bertx_index *idx) { return idx ? idx->storage : -1; }
 
 int32_t bertx_index_add_device(struct bertx_index *idx, const float *d_rows, int32_t n, void *stream)
 {
@@ -224,6 +244,30 @@ int32_t bertx_index_add(struct bertx_index *idx, const float *rows, int32_t n)
     return (int32_t)n0;
 }
 
+// The int8 image of rows first .. first + n - 1 (idx locked, the range checked) out of
+// i8 fragment order: q int8 [n][d], scale f32 [n].
+static int32_t read_rows_i8(struct bertx_index *idx, int32_t first, int32_t n, std::vector<int8_t> &q,
+                            std::vector<float> &scale)
+{
+    const int d = idx->d, KB = d / 64;
+    const int64_t g0 = first / 16, g1 = ((int64_t)first + n + 15) / 16;
+    const size_t group_bytes = (size_t)16 * d;
+    std::vector<int8_t> raw((size_t)(g1 - g0) * group_bytes);
+    q.resize((size_t)n * d);
+    scale.resize((size_t)n);
+    if (idx->any) HIP_RC(hipEventSynchronize(idx->done));
+    HIP_RC(hipMemcpy(raw.data(), (const int8_t *)idx->rows + (size_t)g0 * group_bytes, raw.size(), hipMemcpyDeviceToHost));
+    HIP_RC(hipMemcpy(scale.data(), idx->scales + first, (size_t)n * 4, hipMemcpyDeviceToHost));
+    for (int64_t r = first; r < (int64_t)first + n; ++r) {
+        const int8_t *grp = raw.data() + (size_t)(r / 16 - g0) * group_bytes;
+        int8_t *o = q.data() + (size_t)(r - first) * d;
+        for (int kb = 0; kb < KB; ++kb)
+            for (int g = 0; g < 4; ++g)
+                std::memcpy(o + 64 * kb + 16 * g, grp + ((size_t)kb * 64 + 16 * g + (r & 15)) * 16, 16);
+    }
+    return 0;
+}
+
 int32_t bertx_index_rows(struct bertx_index *idx, int32_t first, int32_t n, float *out)
 {
     if (!idx || !out || first < 0 || n < 1) return -1;
@@ -232,6 +276,15 @@ int32_t bertx_index_rows(struct bertx_index *idx, int32_t first, int32_t n, floa
     DeviceGuard g(idx->ordinal);
     HIP_RC(g.status());
     try {
+        if (idx->storage == BERTX_INDEX_I8) {
+            std::vector<int8_t> q;
+            std::vector<float> scale;
+            const int32_t rc = read_rows_i8(idx, first, n, q, scale);
+            if (rc != 0) return rc;
+            for (size_t r = 0; r < (size_t)n; ++r)
+                for (int i = 0; i < idx->d; ++i) out[r * idx->d + i] = (float)q[r * idx->d + i] * scale[r];
+            return 0;
+        }
         const int d = idx->d, KB = d / 32;
         const int64_t g0 = first / 16, g1 = ((int64_t)first + n + 15) / 16;
         const size_t group_halfs = (size_t)16 * d;
@@ -249,6 +302,28 @@ int32_t bertx_index_rows(struct bertx_index *idx, int32_t first, int32_t n, floa
         }
     } catch (const std::bad_alloc &) {
         emb::errorf("bertx_index_rows: out of host memory\n");
+        return -1;
+    }
+    return 0;
+}
+
+int32_t bertx_index_rows_i8(struct bertx_index *idx, int32_t first, int32_t n, int8_t *q, float *scale)
+{
+    if (!idx || !q || !scale || first < 0 || n < 1) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (idx->storage != BERTX_INDEX_I8 || (int64_t)first + n > idx->n) return -1;
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    try {
+        // the caller's outputs are written only once both copies have succeeded
+        std::vector<int8_t> hq;
+        std::vector<float> hs;
+        const int32_t rc = read_rows_i8(idx, first, n, hq, hs);
+        if (rc != 0) return rc;
+        std::memcpy(q, hq.data(), hq.size());
+        std::memcpy(scale, hs.data(), hs.size() * 4);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_index_rows_i8: out of host memory\n");
         return -1;
     }
     return 0;

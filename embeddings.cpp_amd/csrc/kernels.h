@@ -208,28 +208,36 @@ int launch_q8_gemm(const DevWeight &W, const int8_t *xq, const float *xd, const 
                    const float *bias, int32_t epi, const float *res, float *Y, hipStream_t s,
                    const uint16_t *gelu_tab);
 
-// ---- the embedding index (search.hip, index.cpp): rows f16 in fragment order, groups
-// of 16 rows, a group's d / 32 blocks of 16 rows x 32 k = 1 KiB consecutive, lane
-// 16g + f of a block = row f, elements 8g .. 8g + 7 ----
+// ---- the embedding index (search.hip, index.cpp): rows in fragment order, groups of
+// 16 rows, a group's blocks of 1 KiB consecutive.  SEARCH_F16: a block = 16 rows x 32 k,
+// lane 16g + f = row f, elements 8g .. 8g + 7.  SEARCH_I8: a block = 16 rows x 64 k,
+// lane 16g + f = row f, bytes 16g .. 16g + 15, and a second buffer of one f32 scale per
+// row (the arithmetic: bert_hip.h, search.hip quantize_row_i8 / score_i8) ----
+enum { SEARCH_F16 = 0, SEARCH_I8 = 1 };   // = BERTX_INDEX_F16 / _I8
 // Once per process and device (the calling thread's current one) before the first
-// launch_search: lets the search kernel use the CU's whole LDS.  Returns 0 or -1.
+// launch_search: lets the search kernels use the CU's whole LDS.  Returns 0 or -1.
 int search_prepare_device();
 // Queries one search launch takes at width d and list length k (16, 32, 48 or 64:
-// what the queries' fragments, the lists and the score tile leave room for in LDS).
-int search_group_queries(int d, int k);
+// what the queries' fragments, the lists and the score tile leave room for in LDS;
+// always 64 for SEARCH_I8, whose queries take d + 4 bytes).
+int search_group_queries(int d, int k, int storage);
 // The most workgroups a search over an index of this capacity uses (current device);
 // the scratch of launch_search holds 64 * that * 128 (score, id) pairs of 8 B.
 int64_t search_max_workgroups(int64_t capacity_rows);
-// Converts rows f32 [n][d] (device) to f16, round to nearest even, into rows first ..
-// first + n - 1 of the index image.  d % 64 == 0, 64 <= d <= 1024; returns -1 otherwise.
-int launch_index_add(const float *d_rows, int64_t n, int d, int64_t first, void *corpus, hipStream_t s);
-// scores f32 [B][k], ids i32 [B][k]: per query the k highest dot products of the
-// f16-rounded query with rows < n_rows, descending, equal scores by ascending id,
-// (-inf, -1) where the index has fewer than k rows.  One streaming kernel and one
-// merge kernel per group of search_group_queries queries.  1 <= k <= 128, B >= 1;
-// returns -1 for bad arguments (nothing launched), -3 when a launch was refused.
-int launch_search(const void *corpus, int64_t n_rows, int d, const float *d_queries, int B, int k, void *scratch,
-                  float *d_scores, int32_t *d_ids, hipStream_t s);
+// Converts rows f32 [n][d] (device) into rows first .. first + n - 1 of the index image:
+// to f16, round to nearest even, or to int8 with the rows' scales into scales[first ..].
+// d % 64 == 0, 64 <= d <= 1024; returns -1 otherwise.
+int launch_index_add(const float *d_rows, int64_t n, int d, int64_t first, int storage, void *corpus, float *scales,
+                     hipStream_t s);
+// scores f32 [B][k], ids i32 [B][k]: per query the k highest scores over rows < n_rows
+// (f16: the dot product of the f16-rounded query with the row; int8: the query quantized
+// as the rows are, score_i8), descending, equal scores by ascending id, (-inf, -1) where
+// the index has fewer than k rows.  One streaming kernel and one merge kernel per group
+// of search_group_queries queries.  scales: the int8 rows' scales (not read for f16).
+// 1 <= k <= 128, B >= 1; returns -1 for bad arguments (nothing launched), -3 when a
+// launch was refused.
+int launch_search(const void *corpus, const float *scales, int storage, int64_t n_rows, int d, const float *d_queries,
+                  int B, int k, void *scratch, float *d_scores, int32_t *d_ids, hipStream_t s);
 // Benches: out f32 [n][d] (device) = unit rows of hashed values.
 int launch_unit_rows(float *d_out, int64_t n, int d, uint32_t seed, hipStream_t s);
 

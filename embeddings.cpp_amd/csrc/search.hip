@@ -15,6 +15,13 @@
 // the d / 32 MFMAs of the row's group in ascending k into an f32 accumulator that
 // starts at 0.  Every tile of every launch runs that same sequence, so a score
 // depends on neither the row's position, the row count nor the other queries.
+//
+// int8 storage (BERTX_INDEX_I8) is the same kernel over another Store:
+// "i8 fragment order" is the A operand of v_mfma_i32_16x16x64_i8, a block = 16 rows x
+// 64 k = 1 KiB, lane 16g + f = row f, bytes 16g .. 16g + 15, a group's d / 64 blocks
+// consecutive, and one f32 scale per row in a second buffer.  quantize_row_i8 is the
+// one quantizer of stored rows and queries; a score is the exact i32 sum of the byte
+// products times the two scales (score_i8), so it is order-free as well.
 #include "device_common.h"
 #include "kernels.h"
 
@@ -23,9 +30,80 @@
 namespace emb {
 namespace {
 
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
 constexpr int kThreads = 256;          // 4 waves: each streams its own contiguous run of 16-row groups
 constexpr int kUnitsAhead = 8;         // prefetch ring: 8 units of 2 blocks = 16 KiB in flight per wave
+constexpr int kRingBlocks = 2 * kUnitsAhead;   // int8: 16 units of 1 block
 constexpr int kLdsBudget = 160 * 1024; // LDS of one CU (a single workgroup may use all of it)
+
+// What differs between the storage kinds: the 16-B lane fragment of a 1-KiB block, the
+// k a block covers, the accumulator, the blocks of one ring unit (a group's block count
+// is a multiple of it: d / 32 is even, d / 64 may be odd and may be 1) and the bytes a
+// query takes in LDS.
+template <int ST> struct Store;
+template <> struct Store<SEARCH_F16> {
+    typedef h16x8 Block;
+    typedef f32x4 Acc;
+    static constexpr int kShift = 5, kUnit = 2;
+    __host__ __device__ static constexpr size_t query_bytes(int d) { return (size_t)d * 2; }
+};
+template <> struct Store<SEARCH_I8> {
+    typedef i32x4 Block;
+    typedef i32x4 Acc;
+    static constexpr int kShift = 6, kUnit = 1;
+    __host__ __device__ static constexpr size_t query_bytes(int d) { return (size_t)d + 4; }   // bytes + the scale
+};
+
+__device__ __forceinline__ f32x4 mma(h16x8 a, h16x8 b, f32x4 c)
+{
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ i32x4 mma(i32x4 a, i32x4 b, i32x4 c)
+{
+    return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
+}
+
+// The int8 quantizer of stored rows and of queries, one wave per row x f32 [d]: lane
+// c < d / 16 takes elements 16c .. 16c + 15 and returns their 16 bytes (element 16c + j
+// in byte j), the other lanes return zeros; every lane gets the row's scale.
+//   amax = max |x_i|;  amax == 0: scale 0, every q 0;  else inv = 127 / amax,
+//   q_i = clamp(rint(x_i * inv), -127, 127) (nearest even), scale = amax / 127,
+// each operation rounded once to f32.  Non-finite input: the clamp still holds (a NaN
+// product becomes -127), the values are unspecified.
+__device__ __forceinline__ i32x4 quantize_row_i8(const float *__restrict__ x, int d, int lane, float &scale)
+{
+    float v[16];
+    const bool on = lane < (d >> 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float4 a = {0.f, 0.f, 0.f, 0.f};
+        if (on) a = *(const float4 *)(x + 16 * lane + 4 * j);
+        v[4 * j] = a.x; v[4 * j + 1] = a.y; v[4 * j + 2] = a.z; v[4 * j + 3] = a.w;
+    }
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(v[i]));
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    i32x4 out = {0, 0, 0, 0};
+    scale = 0.f;
+    if (!(amax > 0.f)) return out;
+    const float inv = __fdiv_rn(127.0f, amax);
+    scale = __fdiv_rn(amax, 127.0f);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const float r = fminf(fmaxf(rintf(__fmul_rn(v[i], inv)), -127.0f), 127.0f);
+        out[i >> 2] |= ((int)r & 0xff) << (8 * (i & 3));
+    }
+    return out;
+}
+
+// The int8 score: the i32 sum is exact in f32 (|isum| <= 127 * 127 * 1024 < 2^24).
+__device__ __forceinline__ float score_i8(int isum, float scale_q, float scale_row)
+{
+    return __fmul_rn((float)isum, __fmul_rn(scale_q, scale_row));
+}
 
 // (score, id) order of the results: higher score first, equal scores by ascending
 // id.  Empty slots are (-inf, -1): the unsigned compare puts id -1 behind every row.
@@ -72,9 +150,14 @@ __device__ __forceinline__ void list_offer(Hit *list, int k, float s, int32_t id
 
 // LDS of the search kernel for QT query tiles (16 queries each): the queries' B
 // fragments, the running lists, the score tile of one step, the step's group ids.
+template <int ST>
 __host__ __device__ inline size_t search_lds_bytes(int QT, int d, int k)
 {
-    return (size_t)QT * 16 * ((size_t)d * 2 + (size_t)k * 8 + 64 * 4) + 16;
+    return (size_t)QT * 16 * (Store<ST>::query_bytes(d) + (size_t)k * 8 + 64 * 4) + 16;
+}
+inline size_t search_lds_bytes(int storage, int QT, int d, int k)
+{
+    return storage == SEARCH_I8 ? search_lds_bytes<SEARCH_I8>(QT, d, k) : search_lds_bytes<SEARCH_F16>(QT, d, k);
 }
 
 // Workgroup b walks the 16-row groups [b * per, (b + 1) * per), per % 4 == 0: wave w
@@ -83,31 +166,52 @@ __host__ __device__ inline size_t search_lds_bytes(int QT, int d, int k)
 // offers the step's 64 rows to the lists of queries w, w + 4, ... (one lane per row).
 // Rows >= n_rows (the unfilled part of the last group, and the groups a range has
 // past the end) are never offered.  partial: [query][P][k].
-template <int QT>
-__global__ __launch_bounds__(kThreads) void search_kernel(const h16x8 *__restrict__ corpus,
+// int8: row_scale f32 [rows]; a row's scale is read only for rows < n_rows, one group
+// ahead of its use, and the group's i32 sums become scores (score_i8) on their way to
+// the score tile.  f16: row_scale is not used.
+template <int QT, int ST>
+__global__ __launch_bounds__(kThreads) void search_kernel(const typename Store<ST>::Block *__restrict__ corpus,
                                                           const float *__restrict__ queries, int nq, int d,
-                                                          int n_rows, int k, int per, Hit *__restrict__ partial)
+                                                          int n_rows, int k, int per, Hit *__restrict__ partial,
+                                                          const float *__restrict__ row_scale)
 {
+    typedef Store<ST> S;
+    typedef typename S::Block Block;
+    typedef typename S::Acc Acc;
     extern __shared__ uint4 smem[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int KB = d >> 5, nq16 = QT * 16;
-    h16x8 *qf = (h16x8 *)smem;                                  // [QT][KB][64]
+    const int KB = d >> S::kShift, nq16 = QT * 16;
+    Block *qf = (Block *)smem;                                  // [QT][KB][64]
     Hit *lists = (Hit *)(qf + (size_t)QT * KB * 64);            // [nq16][k]
     float *tile = (float *)(lists + (size_t)nq16 * k);          // [nq16][64]
     int *gb = (int *)(tile + nq16 * 64);                        // [4]
+    float *qscale = (float *)(gb + 4);                          // int8: [nq16]
 
-    // the queries as f16 B fragments: lane 16g + c of block (t, kb) holds query
-    // 16t + c, elements 32kb + 8g .. + 7; queries past nq are zeros
-    const int chunks = d >> 3;
-    for (int i = tid; i < nq16 * chunks; i += kThreads) {
-        const int q = i / chunks, c = i - q * chunks;
-        h16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (q < nq) {
-            const float4 a = *(const float4 *)(queries + (size_t)q * d + 8 * c);
-            const float4 b = *(const float4 *)(queries + (size_t)q * d + 8 * c + 4);
-            v = h16x8{(h16)a.x, (h16)a.y, (h16)a.z, (h16)a.w, (h16)b.x, (h16)b.y, (h16)b.z, (h16)b.w};
+    if constexpr (ST == SEARCH_F16) {
+        // the queries as f16 B fragments: lane 16g + c of block (t, kb) holds query
+        // 16t + c, elements 32kb + 8g .. + 7; queries past nq are zeros
+        const int chunks = d >> 3;
+        for (int i = tid; i < nq16 * chunks; i += kThreads) {
+            const int q = i / chunks, c = i - q * chunks;
+            h16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (q < nq) {
+                const float4 a = *(const float4 *)(queries + (size_t)q * d + 8 * c);
+                const float4 b = *(const float4 *)(queries + (size_t)q * d + 8 * c + 4);
+                v = h16x8{(h16)a.x, (h16)a.y, (h16)a.z, (h16)a.w, (h16)b.x, (h16)b.y, (h16)b.z, (h16)b.w};
+            }
+            qf[((size_t)(q >> 4) * KB + (c >> 2)) * 64 + 16 * (c & 3) + (q & 15)] = v;
         }
-        qf[((size_t)(q >> 4) * KB + (c >> 2)) * 64 + 16 * (c & 3) + (q & 15)] = v;
+    } else {
+        // the queries quantized as the rows are, one wave per query: lane 16g + c of
+        // block (t, kb) holds query 16t + c, bytes 64kb + 16g .. + 15, the same byte -> k
+        // map as a stored block; queries past nq are zeros with scale 0
+        for (int q = w; q < nq16; q += 4) {
+            float sc = 0.f;
+            i32x4 v = {0, 0, 0, 0};
+            if (q < nq) v = quantize_row_i8(queries + (size_t)q * d, d, lane, sc);
+            if (lane < (d >> 4)) qf[((size_t)(q >> 4) * KB + (lane >> 2)) * 64 + 16 * (lane & 3) + (q & 15)] = v;
+            if (lane == 0) qscale[q] = sc;
+        }
     }
     for (int i = tid; i < nq16 * k; i += kThreads) lists[i] = Hit{-INFINITY, -1};
     lds_barrier();
@@ -119,50 +223,103 @@ __global__ __launch_bounds__(kThreads) void search_kernel(const h16x8 *__restric
     const int g0 = blockIdx.x * per + ws * steps;                 // this wave's first group
     const int last_blk = max((n_rows + 15) >> 4, 1) * KB - 1;     // loads stay inside the filled groups
     const int blk0 = g0 * KB;
-    const int U = steps * (KB >> 1);                              // units of 2 blocks; the same for all waves
+    constexpr int UB = S::kUnit, NU = kRingBlocks / UB;           // blocks per unit, units in the ring
+    const int U = steps * (UB == 2 ? KB >> 1 : KB);               // units; the same for all waves
     auto load = [&](int blk) { return (corpus + (size_t)min(blk, last_blk) * 64)[lane]; };
+    // int8: the scales of group grp's 16 rows, zeros for rows >= n_rows.  The address is
+    // wave-uniform and the scales do not change during a search, so they come through
+    // the scalar cache (constant address space) and never enter the vector-memory
+    // counter that paces the ring.
+    typedef const __attribute__((address_space(4))) float *ScalePtr;
+    const ScalePtr scale_c = (ScalePtr)(uintptr_t)row_scale;
+    auto load_scales = [&](int grp, float (&o)[16]) {
+        const int64_t r0 = (int64_t)grp * 16;
+        if (r0 + 16 <= n_rows) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o[i] = scale_c[r0 + i];
+        } else {
+            // the index's last, partly filled group (once per launch) and the groups
+            // past it: one lane per row, then broadcast
+            float v = 0.f;
+            if (r0 + (lane & 15) < n_rows) v = row_scale[r0 + (lane & 15)];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), i));
+        }
+    };
 
     // the ring is filled and refilled in the order it is consumed (the scheduling
-    // barriers keep the compiler from reordering the loads), so a unit's two loads
+    // barriers keep the compiler from reordering the loads), so a unit's loads
     // are always the oldest ones outstanding
-    h16x8 ring[kUnitsAhead][2];
+    Block ring[NU][UB];
 #pragma unroll
-    for (int j = 0; j < kUnitsAhead; ++j) {
-        ring[j][0] = load(blk0 + 2 * j);
-        ring[j][1] = load(blk0 + 2 * j + 1);
+    for (int j = 0; j < NU; ++j) {
+        ring[j][0] = load(blk0 + UB * j);
+        if constexpr (UB == 2) ring[j][1] = load(blk0 + UB * j + 1);
         __builtin_amdgcn_sched_barrier(0);
     }
-    f32x4 acc[QT];
+    int hmask[4];                                                 // int8: all ones where lane >> 4 == h
 #pragma unroll
-    for (int t = 0; t < QT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int h = 0; h < 4; ++h) hmask[h] = -(int)((lane >> 4) == h);
+    float rs[16] = {};                                            // int8: the scales of group g, loaded a group ahead
+    if constexpr (ST == SEARCH_I8) {
+        if (U > 0) load_scales(g0, rs);
+    }
+    Acc acc[QT];
+#pragma unroll
+    for (int t = 0; t < QT; ++t) acc[t] = Acc{0, 0, 0, 0};
     int kb = 0, g = g0;
     const int nqv = min(nq, nq16);
-    for (int u0 = 0; u0 < U; u0 += kUnitsAhead) {
+    for (int u0 = 0; u0 < U; u0 += NU) {
 #pragma unroll
-        for (int j = 0; j < kUnitsAhead; ++j) {
+        for (int j = 0; j < NU; ++j) {
             const int u = u0 + j;
             if (u >= U) goto done;   // uniform over the workgroup; no path re-enters the ring out of order
             {
-                const h16x8 a0 = ring[j][0], a1 = ring[j][1];
+                const Block a0 = ring[j][0], a1 = ring[j][UB - 1];
 #pragma unroll
                 for (int t = 0; t < QT; ++t) {
-                    const h16x8 b0 = qf[((size_t)t * KB + kb) * 64 + lane];
-                    const h16x8 b1 = qf[((size_t)t * KB + kb + 1) * 64 + lane];
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, b0, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b1, acc[t], 0, 0, 0);
+                    const Block b0 = qf[((size_t)t * KB + kb) * 64 + lane];
+                    if constexpr (UB == 2) {
+                        const Block b1 = qf[((size_t)t * KB + kb + 1) * 64 + lane];
+                        acc[t] = mma(a0, b0, acc[t]);
+                        acc[t] = mma(a1, b1, acc[t]);
+                    } else {
+                        acc[t] = mma(a0, b0, acc[t]);
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                ring[j][0] = load(blk0 + 2 * (u + kUnitsAhead));
-                ring[j][1] = load(blk0 + 2 * (u + kUnitsAhead) + 1);
+                ring[j][0] = load(blk0 + UB * (u + NU));
+                if constexpr (UB == 2) ring[j][1] = load(blk0 + UB * (u + NU) + 1);
                 __builtin_amdgcn_sched_barrier(0);
-                kb += 2;
+                kb += UB;
                 if (kb == KB) {
-                    // accumulator register r of lane l: row 4 (l >> 4) + r of the group, query l & 15 of tile t
+                    // accumulator register r of lane l: row 4 (l >> 4) + r of the group, query l & 15 of tile t.
+                    // int8: this lane's four row scales out of the group's 16 uniform ones, by bit
+                    // masks (selects here compiled to exec-mask branches)
+                    float rrow[4] = {};
+                    if constexpr (ST == SEARCH_I8) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            int b = 0;
+#pragma unroll
+                            for (int h = 0; h < 4; ++h) b |= __float_as_int(rs[4 * h + r]) & hmask[h];
+                            rrow[r] = __int_as_float(b);
+                        }
+                    }
 #pragma unroll
                     for (int t = 0; t < QT; ++t) {
-                        *(f32x4 *)&tile[(16 * t + (lane & 15)) * 64 + 16 * w + 4 * (lane >> 4)] = acc[t];
-                        acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+                        f32x4 sc;
+                        if constexpr (ST == SEARCH_F16) {
+                            sc = acc[t];
+                        } else {
+                            const float qs = qscale[16 * t + (lane & 15)];
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) sc[r] = score_i8(acc[t][r], qs, rrow[r]);
+                        }
+                        *(f32x4 *)&tile[(16 * t + (lane & 15)) * 64 + 16 * w + 4 * (lane >> 4)] = sc;
+                        acc[t] = Acc{0, 0, 0, 0};
                     }
+                    if constexpr (ST == SEARCH_I8) load_scales(g + 1, rs);
                     if (lane == 0) gb[w] = g;
                     lds_barrier();
                     const int64_t row = (int64_t)gb[lane >> 4] * 16 + (lane & 15);
@@ -244,6 +401,24 @@ __global__ __launch_bounds__(kThreads) void index_add_kernel(const float *__rest
         h16x8{(h16)a.x, (h16)a.y, (h16)a.z, (h16)a.w, (h16)b.x, (h16)b.y, (h16)b.z, (h16)b.w};
 }
 
+// rows f32 [n][d] -> int8 (quantize_row_i8) into i8 fragment order at rows first ..
+// first + n - 1 with their scales; one wave per row, one 16-B store per 16 elements.
+// A row touches only its own 16 B of each block and its own scale, so rows may
+// start and end inside a group.
+__global__ __launch_bounds__(kThreads) void index_add_i8_kernel(const float *__restrict__ rows, int64_t n, int d,
+                                                                int64_t first, i32x4 *__restrict__ corpus,
+                                                                float *__restrict__ scales)
+{
+    const int lane = threadIdx.x & 63, KB = d >> 6;
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    float sc;
+    const i32x4 v = quantize_row_i8(rows + r * d, d, lane, sc);
+    const int64_t row = first + r;
+    if (lane < (d >> 4)) corpus[((row >> 4) * KB + (lane >> 2)) * 64 + 16 * (lane & 3) + (row & 15)] = v;
+    if (lane == 0) scales[row] = sc;
+}
+
 // Benchmark data: row r of out [n][d] = a unit vector of hashed values in [-1, 1); one wave per row.
 __global__ __launch_bounds__(kThreads) void unit_rows_kernel(float *__restrict__ out, int64_t n, int d, uint32_t seed)
 {
@@ -262,28 +437,56 @@ __global__ __launch_bounds__(kThreads) void unit_rows_kernel(float *__restrict__
     for (int c = lane; c < d; c += 64) out[r * d + c] *= inv;
 }
 
-template <int QT>
+template <int QT, int ST>
 hipError_t allow_lds()
 {
-    return hipFuncSetAttribute((const void *)search_kernel<QT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    return hipFuncSetAttribute((const void *)search_kernel<QT, ST>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                kLdsBudget);
+}
+
+template <int ST>
+hipError_t allow_lds_all()
+{
+    hipError_t e = allow_lds<1, ST>();
+    if (e == hipSuccess) e = allow_lds<2, ST>();
+    if (e == hipSuccess) e = allow_lds<3, ST>();
+    if (e == hipSuccess) e = allow_lds<4, ST>();
+    return e;
+}
+
+// One group of nq <= 64 queries: the streaming kernel over P row ranges, then the merge.
+template <int ST>
+int launch_group(const void *corpus, const float *row_scale, const float *Q, int nq, int d, int n_rows, int k,
+                 int per, int P, Hit *part, float *d_scores, int32_t *d_ids, hipStream_t s)
+{
+    typedef typename Store<ST>::Block Block;
+    const int QT = (nq + 15) / 16;
+    const size_t lds = search_lds_bytes<ST>(QT, d, k);
+    const Block *C = (const Block *)corpus;
+    switch (QT) {
+    case 1: search_kernel<1, ST><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, n_rows, k, per, part, row_scale); break;
+    case 2: search_kernel<2, ST><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, n_rows, k, per, part, row_scale); break;
+    case 3: search_kernel<3, ST><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, n_rows, k, per, part, row_scale); break;
+    default: search_kernel<4, ST><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, n_rows, k, per, part, row_scale); break;
+    }
+    if (hipGetLastError() != hipSuccess) return -3;
+    search_merge_kernel<<<nq, kThreads, 0, s>>>(part, P, k, d_scores, d_ids);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 }  // namespace
 
 int search_prepare_device()
 {
-    hipError_t e = allow_lds<1>();
-    if (e == hipSuccess) e = allow_lds<2>();
-    if (e == hipSuccess) e = allow_lds<3>();
-    if (e == hipSuccess) e = allow_lds<4>();
+    hipError_t e = allow_lds_all<SEARCH_F16>();
+    if (e == hipSuccess) e = allow_lds_all<SEARCH_I8>();
     return e == hipSuccess ? 0 : -1;
 }
 
-int search_group_queries(int d, int k)
+int search_group_queries(int d, int k, int storage)
 {
     int QT = 4;
-    while (QT > 1 && search_lds_bytes(QT, d, k) > (size_t)kLdsBudget) --QT;
+    while (QT > 1 && search_lds_bytes(storage, QT, d, k) > (size_t)kLdsBudget) --QT;
     return 16 * QT;
 }
 
@@ -293,45 +496,51 @@ int64_t search_max_workgroups(int64_t capacity_rows)
     return std::max<int64_t>(1, std::min<int64_t>(2 * (int64_t)device_cu_count(), (groups + 3) / 4));
 }
 
-int launch_index_add(const float *d_rows, int64_t n, int d, int64_t first, void *corpus, hipStream_t s)
+int launch_index_add(const float *d_rows, int64_t n, int d, int64_t first, int storage, void *corpus, float *scales,
+                     hipStream_t s)
 {
     if (n <= 0 || d % 64 || d < 64 || d > 1024) return -1;
+    if (storage == SEARCH_I8) {
+        if (!scales) return -1;
+        index_add_i8_kernel<<<(unsigned)((n + 3) / 4), kThreads, 0, s>>>(d_rows, n, d, first, (i32x4 *)corpus, scales);
+        return hipGetLastError() == hipSuccess ? 0 : -3;
+    }
+    if (storage != SEARCH_F16) return -1;
     const int64_t blocks = (n * (d / 8) + kThreads - 1) / kThreads;
     if (blocks > 0x7fffffff) return -1;
     index_add_kernel<<<(unsigned)blocks, kThreads, 0, s>>>(d_rows, n, d, first, (h16x8 *)corpus);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-int launch_search(const void *corpus, int64_t n_rows, int d, const float *d_queries, int B, int k, void *scratch,
-                  float *d_scores, int32_t *d_ids, hipStream_t s)
+int launch_search(const void *corpus, const float *scales, int storage, int64_t n_rows, int d, const float *d_queries,
+                  int B, int k, void *scratch, float *d_scores, int32_t *d_ids, hipStream_t s)
 {
     if (B < 1 || k < 1 || k > 128 || d % 64 || d < 64 || d > 1024 || n_rows < 0 || n_rows > 0x7ffffff0) return -1;
-    const int QG = search_group_queries(d, k);
-    if (search_lds_bytes(1, d, k) > (size_t)kLdsBudget) return -1;
+    if ((storage != SEARCH_F16 && storage != SEARCH_I8) || (storage == SEARCH_I8 && !scales)) return -1;
+    const int QG = search_group_queries(d, k, storage);
+    if (search_lds_bytes(storage, 1, d, k) > (size_t)kLdsBudget) return -1;
     // the row ranges: P workgroups of `per` groups each, per % 4 == 0 (one group per wave and step)
     const int64_t groups = std::max<int64_t>(1, (n_rows + 15) / 16);
     const int cus = device_cu_count();
     // block indices are 32-bit in the kernel, the ranges' overhang and the prefetch included
+    // (counted in f16 blocks, d / 32 per group; int8 has half as many)
     if ((groups + 8 * (int64_t)cus + 8) * (d / 32) + 4 * kUnitsAhead > 0x7fffffffll) return -1;
     for (int b0 = 0; b0 < B; b0 += QG) {
         const int nq = std::min(QG, B - b0), QT = (nq + 15) / 16;
-        const size_t lds = search_lds_bytes(QT, d, k);
+        const size_t lds = search_lds_bytes(storage, QT, d, k);
         const int64_t wg_per_cu = std::min<int64_t>(2, (int64_t)kLdsBudget / (int64_t)lds);
         int64_t P = std::max<int64_t>(1, std::min<int64_t>(wg_per_cu * cus, (groups + 3) / 4));
         const int64_t per = ((groups + P - 1) / P + 3) / 4 * 4;
         P = (groups + per - 1) / per;
-        const h16x8 *C = (const h16x8 *)corpus;
         const float *Q = d_queries + (size_t)b0 * d;
-        Hit *part = (Hit *)scratch;
-        switch (QT) {
-        case 1: search_kernel<1><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, (int)n_rows, k, (int)per, part); break;
-        case 2: search_kernel<2><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, (int)n_rows, k, (int)per, part); break;
-        case 3: search_kernel<3><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, (int)n_rows, k, (int)per, part); break;
-        default: search_kernel<4><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, (int)n_rows, k, (int)per, part); break;
-        }
-        if (hipGetLastError() != hipSuccess) return -3;
-        search_merge_kernel<<<nq, kThreads, 0, s>>>(part, (int)P, k, d_scores + (size_t)b0 * k, d_ids + (size_t)b0 * k);
-        if (hipGetLastError() != hipSuccess) return -3;
+        float *S = d_scores + (size_t)b0 * k;
+        int32_t *I = d_ids + (size_t)b0 * k;
+        const int rc = storage == SEARCH_I8
+                           ? launch_group<SEARCH_I8>(corpus, scales, Q, nq, d, (int)n_rows, k, (int)per, (int)P,
+                                                     (Hit *)scratch, S, I, s)
+                           : launch_group<SEARCH_F16>(corpus, nullptr, Q, nq, d, (int)n_rows, k, (int)per, (int)P,
+                                                      (Hit *)scratch, S, I, s);
+        if (rc != 0) return rc;
     }
     return 0;
 }

@@ -2,9 +2,11 @@
 // corpus, then print the k closest texts of every query) with the corpus resident on
 // the GPU and the search fused there (bertx_index_*).
 //
-// usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-r RERANK_MODEL [-c N]]
+// usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8] [-r RERANK_MODEL [-c N]]
 // One text per line of CORPUS.txt; queries from stdin, one per line, `q` or EOF ends.
 // Per hit one line: rank<TAB>id<TAB>score<TAB>text.
+// -s: how the index stores its rows (bertx_index_create_ex): f16, the default, or int8
+// with one scale per row, half the bytes and a less precise first stage.
 // -r: a second stage.  Per query the N best of the index (default 4 k, at most the
 // index's 128) are re-scored as (query, text) pairs by the cross-encoder RERANK_MODEL
 // (a model file with a classification head, bertx_rerank) and the k best of those are
@@ -24,20 +26,22 @@
 int main(int argc, char **argv)
 {
     const char *model = nullptr, *corpus = nullptr, *rerank = nullptr;
-    int k = 3, threads = 4, cand = 0;
+    int k = 3, threads = 4, cand = 0, storage = BERTX_INDEX_F16;
     for (int i = 1; i < argc; ++i) {
         const bool has = i + 1 < argc;
         if (!std::strcmp(argv[i], "-m") && has) model = argv[++i];
         else if (!std::strcmp(argv[i], "-f") && has) corpus = argv[++i];
         else if (!std::strcmp(argv[i], "-k") && has) k = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "-t") && has) threads = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "-s") && has && !std::strcmp(argv[i + 1], "f16")) { storage = BERTX_INDEX_F16; ++i; }
+        else if (!std::strcmp(argv[i], "-s") && has && !std::strcmp(argv[i + 1], "int8")) { storage = BERTX_INDEX_I8; ++i; }
         else if (!std::strcmp(argv[i], "-r") && has) rerank = argv[++i];
         else if (!std::strcmp(argv[i], "-c") && has) cand = std::atoi(argv[++i]);
         else { model = nullptr; break; }
     }
     if (rerank && cand == 0) cand = std::min(128, 4 * k);
     if (!model || !corpus || k < 1 || k > 128 || threads < 1 || (rerank ? cand < k || cand > 128 : cand != 0)) {
-        std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads] "
+        std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads] [-s f16|int8] "
                              "[-r RERANK_MODEL [-c N (k..128, default 4 k)]]\n", argv[0]);
         return 2;
     }
@@ -72,7 +76,7 @@ int main(int argc, char **argv)
             return 1;
         }
     }
-    bertx_index *idx = bertx_index_create(ctx, 0, (int32_t)texts.size());
+    bertx_index *idx = bertx_index_create_ex(ctx, 0, (int32_t)texts.size(), storage);
     if (!idx) {
         if (rctx) bert_free(rctx);
         bert_free(ctx);

@@ -416,11 +416,39 @@ BERT_API int32_t bertx_tokenize_batch(struct bert_ctx *ctx, int32_t n_threads, i
  * the whole call fails (-4) with nothing added.  The context's n_embd must be the
  * index's width.
  *
+ * Storage kinds.  bertx_index_create_ex takes the kind: BERTX_INDEX_F16 (0) is exactly
+ * bertx_index_create, everything above; BERTX_INDEX_I8 (1) stores a row as d int8 values
+ * and one f32 scale, half the bytes; any other value returns NULL after a message.
+ * bertx_index_storage returns the kind, -1 for NULL.  Every other entry follows the
+ * index's kind with the same signature, refusals, ordering rules and capturability.
+ * The int8 arithmetic, each named operation rounded once to f32 (IEEE, nearest even),
+ * one quantizer for stored rows and for queries:
+ *   amax = max_i |x_i|;  amax == 0: scale = 0 and every q_i = 0;  otherwise
+ *   inv = 127 / amax,  q_i = clamp(rint(x_i * inv), -127, 127) (rint: nearest even),
+ *   scale = amax / 127;
+ *   score(query, row) = (float)isum * (scale_query * scale_row),  isum = sum_i qq_i qr_i
+ * in int32, which is exact (|isum| <= 127 * 127 * 1024 < 2^24) and does not depend on
+ * the order of the sum.  So the score of a (query, row) pair depends on that query and
+ * that row only, bit for bit, with no accumulation-order caveat; ordering and fill are
+ * as above.  Non-finite inputs give unspecified values within the clamp.  Against the
+ * f32 dot of the unquantized vectors x (scale s_x) and y (scale s_y):
+ *   |x.y - score| <= (s_y |x|_1 + s_x |y|_1) / 2 + d s_x s_y / 4
+ * plus the two roundings of the final multiplies.  bertx_index_rows on an int8 index
+ * returns the dequantized values (float)q * scale (one f32 multiply);
+ * bertx_index_rows_i8 returns the stored bytes q int8[n][d] and scales float[n] of rows
+ * first .. first + n - 1, or -1 on an f16 index or a bad range with the outputs
+ * untouched.
+ *
  * Not provided: an index sharded over several GPUs, deleting rows, saving and
- * loading, f32 storage.
+ * loading, f32 storage, f16 queries against int8 rows, 4-bit or binary storage,
+ * rescoring against f16 copies.
  */
+enum { BERTX_INDEX_F16 = 0, BERTX_INDEX_I8 = 1 };
 struct bertx_index;
 BERT_API struct bertx_index *bertx_index_create(struct bert_ctx *ctx, int32_t slot, int32_t capacity_rows);
+BERT_API struct bertx_index *bertx_index_create_ex(struct bert_ctx *ctx, int32_t slot, int32_t capacity_rows,
+                                                   int32_t storage);
+BERT_API int32_t bertx_index_storage(struct bertx_index *idx);
 BERT_API void bertx_index_free(struct bertx_index *idx);
 BERT_API int32_t bertx_index_clear(struct bertx_index *idx);
 BERT_API int32_t bertx_index_size(struct bertx_index *idx);
@@ -429,6 +457,7 @@ BERT_API int32_t bertx_index_dim(struct bertx_index *idx);
 BERT_API int32_t bertx_index_add(struct bertx_index *idx, const float *rows, int32_t n);
 BERT_API int32_t bertx_index_add_device(struct bertx_index *idx, const float *d_rows, int32_t n, void *stream);
 BERT_API int32_t bertx_index_rows(struct bertx_index *idx, int32_t first, int32_t n, float *out);
+BERT_API int32_t bertx_index_rows_i8(struct bertx_index *idx, int32_t first, int32_t n, int8_t *q, float *scale);
 BERT_API int32_t bertx_index_search(struct bertx_index *idx, const float *queries, int32_t B, int32_t k,
                                     float *scores, int32_t *ids);
 BERT_API int32_t bertx_index_search_device(struct bertx_index *idx, const float *d_queries, int32_t B, int32_t k,
@@ -523,9 +552,13 @@ BERT_API int32_t bertx_test_embed_ln_types(int32_t mode, int32_t fmt_word, int32
  * bertx_index_search_device for the k best, after 3 warm-up calls.
  * bertx_bench_search_add_rate: rows per second of bertx_index_add_device filling an
  * index of N rows from device rows, 65,536 rows per call (device time).
+ * The _ex forms take the index's storage kind; the plain forms are BERTX_INDEX_F16.
  */
 BERT_API int32_t bertx_bench_search(int32_t d, int32_t N, int32_t B, int32_t k, int32_t iters, float *avg_us);
 BERT_API int32_t bertx_bench_search_add_rate(int32_t d, int32_t N, double *add_rows_per_s);
+BERT_API int32_t bertx_bench_search_ex(int32_t d, int32_t N, int32_t B, int32_t k, int32_t storage, int32_t iters,
+                                       float *avg_us);
+BERT_API int32_t bertx_bench_search_add_rate_ex(int32_t d, int32_t N, int32_t storage, double *add_rows_per_s);
 
 BERT_API const char *bertx_version(void);
 
