@@ -210,6 +210,38 @@ def load_lib(path=None):
         L.bertx_test_embed_ln_types.argtypes = [c_i32] * 7 + [vp] * 8 + [c_i32, c_i32, vp, vp, c_i32]
     except AttributeError:
         pass
+    try:   # (the token store of late interaction: absent from older BERT_LIB builds)
+        c_i64 = ctypes.c_int64
+        L.bertx_mvindex_create.restype = vp
+        L.bertx_mvindex_create.argtypes = [vp, c_i32, c_i32, c_i32, c_i64]
+        L.bertx_mvindex_free.restype = None
+        L.bertx_mvindex_free.argtypes = [vp]
+        for fn in (L.bertx_mvindex_clear, L.bertx_mvindex_docs, L.bertx_mvindex_capacity_docs, L.bertx_mvindex_dim):
+            fn.restype = c_i32
+            fn.argtypes = [vp]
+        for fn in (L.bertx_mvindex_token_slots, L.bertx_mvindex_capacity_token_slots):
+            fn.restype = c_i64
+            fn.argtypes = [vp]
+        L.bertx_mvindex_add.restype = c_i32
+        L.bertx_mvindex_add.argtypes = [vp, vp, vp, c_i32]
+        L.bertx_mvindex_add_device.restype = c_i32
+        L.bertx_mvindex_add_device.argtypes = [vp, vp, vp, c_i32, vp]
+        L.bertx_mvindex_doc_len.restype = c_i32
+        L.bertx_mvindex_doc_len.argtypes = [vp, c_i32]
+        L.bertx_mvindex_doc.restype = c_i32
+        L.bertx_mvindex_doc.argtypes = [vp, c_i32, vp]
+        L.bertx_mvindex_score.restype = c_i32
+        L.bertx_mvindex_score.argtypes = [vp, vp, c_i32, vp, c_i32, vp]
+        L.bertx_mvindex_score_device.restype = c_i32
+        L.bertx_mvindex_score_device.argtypes = [vp, vp, c_i32, vp, c_i32, vp, vp]
+        L.bertx_mvindex_add_texts.restype = c_i32
+        L.bertx_mvindex_add_texts.argtypes = [vp, vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p)]
+        L.bertx_mvindex_score_text.restype = c_i32
+        L.bertx_mvindex_score_text.argtypes = [vp, vp, ctypes.c_char_p, vp, c_i32, vp]
+        L.bertx_bench_maxsim.restype = c_i32
+        L.bertx_bench_maxsim.argtypes = [c_i32] * 6 + [c_f32p]
+    except AttributeError:
+        pass
     L.bertx_bench_gemm.restype = c_i32
     L.bertx_bench_gemm.argtypes = [c_i32] * 7 + [c_f32p]
     L.bertx_bench_attention.restype = c_i32
@@ -558,6 +590,122 @@ class BertIndex:
         if n and self.lib.bertx_index_rows_i8(self.idx, first, n, q.ctypes.data, scale.ctypes.data) != 0:
             raise RuntimeError("bertx_index_rows_i8 failed")
         return q, scale
+
+
+class BertTokenIndex:
+    """A device-resident token store with a fused MaxSim scorer (bertx_mvindex_*): late
+    interaction.  Documents are [len][width] token vectors, stored as unit-length f16
+    rows on GPU `slot` of the model's context; ids are the insertion order.  A query of
+    up to 64 token vectors scores a document as sum_i max_j <q_i, c_j>; bert_hip.h gives
+    the arithmetic.  width None: the model's n_embd (what the text forms need)."""
+
+    MAX_QUERY_TOKENS = 64
+
+    def __init__(self, model, capacity_docs, capacity_token_slots, slot=0, width=None):
+        self.model = model
+        self.lib = model.lib
+        self.mv = self.lib.bertx_mvindex_create(model.ctx, slot, model.n_embd if width is None else width,
+                                                capacity_docs, capacity_token_slots)
+        if not self.mv:
+            raise RuntimeError("bertx_mvindex_create failed")
+        self.dim = int(self.lib.bertx_mvindex_dim(self.mv))
+        self.capacity_docs = int(self.lib.bertx_mvindex_capacity_docs(self.mv))
+        self.capacity_token_slots = int(self.lib.bertx_mvindex_capacity_token_slots(self.mv))
+
+    def __del__(self):
+        if getattr(self, "mv", None):
+            self.lib.bertx_mvindex_free(self.mv)
+            self.mv = None
+
+    def __len__(self):
+        return int(self.lib.bertx_mvindex_docs(self.mv))
+
+    @property
+    def token_slots(self):
+        """Token slots in use: 16 ceil(len / 16) per document."""
+        return int(self.lib.bertx_mvindex_token_slots(self.mv))
+
+    def clear(self):
+        self.lib.bertx_mvindex_clear(self.mv)
+
+    def _tokens(self, a):
+        a = np.ascontiguousarray(np.asarray(a, np.float32))
+        if a.ndim == 1:
+            a = a[None, :]
+        if a.ndim != 2 or a.shape[1] != self.dim:
+            raise ValueError("expected token rows of width %d, got shape %r" % (self.dim, a.shape))
+        return a
+
+    @staticmethod
+    def _ids(ids):
+        return None if ids is None else np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
+
+    def add(self, docs):
+        """Append documents, a list of [len][width] f32 arrays; returns the id of the first one."""
+        docs = [self._tokens(d) for d in docs]
+        lens = np.fromiter((len(d) for d in docs), np.int32, len(docs))
+        rows = np.ascontiguousarray(np.concatenate(docs)) if docs else np.zeros((0, self.dim), np.float32)
+        rc = self.lib.bertx_mvindex_add(self.mv, rows.ctypes.data, lens.ctypes.data, len(docs))
+        if rc < 0:
+            raise RuntimeError("bertx_mvindex_add failed (%d)" % rc)
+        return rc
+
+    def add_texts(self, texts):
+        """One document per text: its per-token final hidden states; returns the first new id."""
+        rc = self.lib.bertx_mvindex_add_texts(self.mv, self.model.ctx, self.model.N_THREADS, len(texts),
+                                              BertIndex._texts(texts))
+        if rc < 0:
+            raise RuntimeError("bertx_mvindex_add_texts failed (%d)" % rc)
+        return rc
+
+    def doc_len(self, i):
+        return int(self.lib.bertx_mvindex_doc_len(self.mv, i))
+
+    def doc(self, i):
+        """The stored rows of document i as f32 [len][width]: the exact f16 values."""
+        n = self.doc_len(i)
+        if n < 1:
+            raise IndexError("no document %d" % i)
+        out = np.zeros((n, self.dim), np.float32)
+        if self.lib.bertx_mvindex_doc(self.mv, i, out.ctypes.data) != 0:
+            raise RuntimeError("bertx_mvindex_doc failed")
+        return out
+
+    def _out(self, ids):
+        n = len(self) if ids is None else len(ids)
+        return n, np.zeros(n, np.float32)
+
+    def score(self, q, ids=None):
+        """MaxSim scores f32 [n] of the query tokens q [Lq][width] against the documents
+        `ids` (None: every document); an id that is not a document scores -inf."""
+        q, ids = self._tokens(q), self._ids(ids)
+        n, out = self._out(ids)
+        if n == 0:
+            return out
+        rc = self.lib.bertx_mvindex_score(self.mv, q.ctypes.data, q.shape[0], None if ids is None else ids.ctypes.data,
+                                          n, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_mvindex_score failed (%d)" % rc)
+        return out
+
+    def score_text(self, query, ids=None):
+        ids = self._ids(ids)
+        n, out = self._out(ids)
+        if n == 0:
+            return out
+        rc = self.lib.bertx_mvindex_score_text(self.mv, self.model.ctx, BertModel._bytes(query),
+                                               None if ids is None else ids.ctypes.data, n, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_mvindex_score_text failed (%d)" % rc)
+        return out
+
+    def rerank(self, query, ids, top_k=None):
+        """(ids, scores) of the candidates by descending MaxSim score, equal scores by
+        ascending id, the best top_k.  query: a text, or token rows [Lq][width]."""
+        ids = self._ids(ids)
+        sc = self.score_text(query, ids) if isinstance(query, (str, bytes)) else self.score(query, ids)
+        order = np.lexsort((ids, -sc.astype(np.float64)))[:top_k]
+        return ids[order], sc[order]
 
 
 # ---------------------------------------------------------------------------

@@ -14,6 +14,7 @@
 #include <vector>
 
 struct bertx_index;
+struct bertx_mvindex;
 
 namespace emb {
 
@@ -331,5 +332,10 @@ int hip_device_count();
 // d on device `ordinal`, stored as BERTX_INDEX_F16 or _I8, without a context
 // (bertx_index_create_ex, the search bench).  NULL after a message.
 ::bertx_index *index_create_on(int ordinal, int d, int64_t capacity, int storage);
+
+// A token store (mvindex.cpp, bert_hip.h bertx_mvindex_*) of width w for cap_docs
+// documents in cap_slots token slots on device `ordinal`, without a context
+// (bertx_mvindex_create, the MaxSim bench).  NULL after a message.
+::bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t cap_slots);
 
 }  // namespace emb

@@ -241,6 +241,24 @@ int launch_search(const void *corpus, const float *scales, int storage, int64_t 
 // Benches: out f32 [n][d] (device) = unit rows of hashed values.
 int launch_unit_rows(float *d_out, int64_t n, int d, uint32_t seed, hipStream_t s);
 
+// ---- the token store of late interaction (maxsim.hip, mvindex.cpp): documents of len
+// token rows in the SEARCH_F16 fragment order, every document on a group boundary, and
+// a device table of int32 pairs (first group, len) per document (the arithmetic:
+// bert_hip.h, maxsim.hip pack_row_f16) ----
+// Once per process and device before the first launch_maxsim (the LDS attribute).
+int maxsim_prepare_device();
+// Source rows t0 .. t0 + count - 1 of one add call, d_rows = row t0, f32 [count][w], each
+// normalised to unit length, rounded to f16 and written to its slot.  d_src_off int32
+// [n_new]: the first source row of the call's i-th document (ascending from 0);
+// d_table: the (first group, len) pairs of those n_new documents.  -1: bad arguments.
+int launch_mv_pack(const float *d_rows, int64_t t0, int64_t count, int w, const int32_t *d_src_off,
+                   const void *d_table, int n_new, void *store, hipStream_t s);
+// d_out[c] = sum_{i < Lq} max_{j < len} sim(q_i, row j of document id), id = d_ids[c] (or c
+// when d_ids is null), for c < n; -inf for an id outside [0, n_docs).  d_q f32 [Lq][w]
+// is normalised as the rows are.  1 <= Lq <= 64, n >= 1; -1 otherwise, -3: launch refused.
+int launch_maxsim(const void *store, const void *d_table, int n_docs, int w, const float *d_q, int Lq,
+                  const int32_t *d_ids, int n, float *d_out, hipStream_t s);
+
 // ---- the classification head (head.hip): pooler dense + tanh + classifier on the
 // sentences' [CLS] rows, all f32, one form for the three chains ----
 constexpr int HEAD_MAX_LABELS = 16;

@@ -1,0 +1,271 @@
+// Late interaction (ColBERT's MaxSim) over a device-resident token store
+// (bertx_mvindex_*, bert_hip.h; mvindex.cpp).
+//
+// Store: documents of len >= 1 token vectors of width w in the f16 fragment order of
+// the embedding index (search.hip): 16-row groups, a group's w / 32 blocks of 1 KiB
+// consecutive, lane 16g + f of a block = row f, elements 8g .. 8g + 7.  Every document
+// starts on a group boundary and takes ceil(len / 16) groups; a table of
+// (first group, len) per document says where.  The slots of a document's last group
+// past len are never written and may hold anything.
+//
+// pack_row_f16 is the one normaliser of stored rows and of queries:
+//   ss = sum x_i^2 in f32 (order below, a function of w alone); ss == 0: zeros; else
+//   rinv = 1 / sqrt(ss) (two correctly rounded f32 operations), v_i = f16(x_i * rinv).
+//
+// score(doc) = sum_{i < Lq} max_{j < len} sim(q_i, c_j): sim is the search kernel's
+// arithmetic (both operands f16, the w / 32 MFMAs of the row's group in ascending k,
+// an f32 accumulator from 0), the max is exact, the sum over i is f32 in an order
+// fixed by Lq alone.  One wave scores one whole document, so a score depends on the
+// query and the document's own rows only, bit for bit.
+#include "device_common.h"
+#include "kernels.h"
+
+#include <algorithm>
+
+namespace emb {
+namespace {
+
+constexpr int kThreads = 256;      // 4 waves, each scores whole documents on its own
+constexpr int kRingUnits = 4;      // prefetch ring per wave: 4 units of 2 blocks = 8 KiB in flight
+constexpr int kLdsBudget = 160 * 1024;
+
+// One wave normalises row x f32 [w]: lane l takes the 8-element chunks l and l + 64
+// (w / 8 <= 128 chunks).  Sum of squares: each lane adds its chunks' squares in element
+// order into one f32 (lanes without a chunk hold 0), then the xor butterfly of
+// wave_sum; the order depends on w only.  out[j] = chunk l + 64 j as f16, zeros for a
+// chunk the row does not have and for a row whose sum of squares is 0.
+__device__ __forceinline__ void pack_row_f16(const float *__restrict__ x, int w, int lane, h16x8 (&out)[2])
+{
+    const int chunks = w >> 3;
+    float v[2][8];
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int c = lane + 64 * j;
+        float4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
+        if (c < chunks) {
+            a = *(const float4 *)(x + 8 * c);
+            b = *(const float4 *)(x + 8 * c + 4);
+        }
+        v[j][0] = a.x; v[j][1] = a.y; v[j][2] = a.z; v[j][3] = a.w;
+        v[j][4] = b.x; v[j][5] = b.y; v[j][6] = b.z; v[j][7] = b.w;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ss = __fadd_rn(ss, __fmul_rn(v[j][i], v[j][i]));
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) ss = __fadd_rn(ss, __shfl_xor(ss, o, 64));
+    const float rinv = ss > 0.f ? __fdiv_rn(1.0f, __fsqrt_rn(ss)) : 0.f;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) out[j][i] = ss > 0.f ? (h16)__fmul_rn(v[j][i], rinv) : (h16)0.0f;
+}
+
+// Where chunk c (elements 8c .. 8c + 7) of row `row` sits in an image of KB = w / 32
+// blocks per group, in h16x8 units: the A fragment of a stored row and the B fragment
+// of a query alike.
+__device__ __forceinline__ size_t frag_index(int64_t row, int c, int KB)
+{
+    return (size_t)((row >> 4) * KB + (c >> 2)) * 64 + 16 * (c & 3) + (int)(row & 15);
+}
+
+// Source rows t0 .. t0 + count - 1 of one add call (rows = row t0) into their slots; one
+// wave per row.  src_off[i] (i < n_new, ascending, src_off[0] = 0) is the first source
+// row of the call's i-th document, table[i] = (first group, len) of it: row t belongs
+// to the last document whose src_off is <= t and goes to slot 16 first + (t - src_off).
+__global__ __launch_bounds__(kThreads) void mv_pack_kernel(const float *__restrict__ rows, int64_t t0, int64_t count,
+                                                           int w, const int32_t *__restrict__ src_off,
+                                                           const int2 *__restrict__ table, int n_new,
+                                                           h16x8 *__restrict__ store)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= count) return;
+    const int64_t t = t0 + r;
+    int lo = 0, hi = n_new - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((int64_t)src_off[mid] <= t) lo = mid; else hi = mid - 1;
+    }
+    const int2 e = table[lo];
+    const int64_t j = t - src_off[lo];
+    if (j >= e.y) return;   // (never: the host sizes count by the lens)
+    h16x8 v[2];
+    pack_row_f16(rows + (size_t)r * w, w, lane, v);
+    const int64_t slot = (int64_t)e.x * 16 + j;
+    const int chunks = w >> 3, KB = w >> 5;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int c = lane + 64 * k;
+        if (c < chunks) store[frag_index(slot, c, KB)] = v[k];
+    }
+}
+
+__host__ __device__ inline size_t maxsim_lds_bytes(int QT, int w) { return (size_t)QT * 16 * w * 2; }
+
+// Persistent workgroups.  Prologue: the Lq query rows normalised (pack_row_f16, one wave
+// per row) into B fragments in LDS, lane 16g + c of block (t, kb) = query 16t + c,
+// elements 32kb + 8g .. + 7; queries Lq .. 16 QT - 1 are zeros.  Then wave v of the
+// grid takes candidates v, v + waves, ...: no barrier and no cross-wave step follows
+// the prologue.  Per candidate: the document's ceil(len / 16) w / 32 blocks stream
+// through a register ring of kRingUnits units of 2 blocks (loads past the document's
+// last block re-read that block); after a group's last block accumulator register r
+// of lane 16g + c is (row 4g + r of the group, query c): rows >= len become -inf and
+// the four fold into the lane's running maxima, which start at -inf.  After the
+// document two shuffles per tile fold the four g, lane c adds its columns c, 16 + c,
+// ... (a padded column adds +0), a 16-lane butterfly adds the lanes, lane 0 stores.
+// An id outside [0, n_docs) gets -inf and touches nothing else.
+template <int QT>
+__global__ __launch_bounds__(kThreads) void maxsim_kernel(const h16x8 *__restrict__ store,
+                                                          const int2 *__restrict__ table, int n_docs,
+                                                          const float *__restrict__ q, int Lq, int w,
+                                                          const int32_t *__restrict__ ids, int n,
+                                                          float *__restrict__ out)
+{
+    extern __shared__ uint4 smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int KB = w >> 5, chunks = w >> 3;
+    h16x8 *qf = (h16x8 *)smem;                                    // [QT][KB][64]
+
+    for (int i = wv; i < QT * 16; i += 4) {
+        h16x8 v[2] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
+        if (i < Lq) pack_row_f16(q + (size_t)i * w, w, lane, v);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = lane + 64 * k;
+            if (c < chunks) qf[frag_index(i, c, KB)] = v[k];
+        }
+    }
+    lds_barrier();
+
+    const int ws = __builtin_amdgcn_readfirstlane(wv);
+    const int stride = (int)gridDim.x * 4;
+    constexpr int NU = kRingUnits;
+    const int g4 = lane >> 4;
+    for (int c = (int)blockIdx.x * 4 + ws; c < n; c += stride) {
+        const int id = __builtin_amdgcn_readfirstlane(ids ? ids[c] : c);
+        if ((unsigned)id >= (unsigned)n_docs) {
+            if (lane == 0) out[c] = -INFINITY;
+            continue;
+        }
+        const int2 e = table[id];
+        const int first = __builtin_amdgcn_readfirstlane(e.x), len = __builtin_amdgcn_readfirstlane(e.y);
+        const int U = ((len + 15) >> 4) * (KB >> 1);              // units of 2 blocks; KB is even
+        const int last_blk = 2 * U - 1;
+        const h16x8 *base = store + (size_t)first * KB * 64;
+        auto load = [&](int blk) { return (base + (size_t)min(blk, last_blk) * 64)[lane]; };
+
+        // the ring is filled and refilled in the order it is consumed (search.hip)
+        h16x8 ring[NU][2];
+#pragma unroll
+        for (int j = 0; j < NU; ++j) {
+            ring[j][0] = load(2 * j);
+            ring[j][1] = load(2 * j + 1);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        f32x4 acc[QT];
+        float mx[QT];
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {
+            acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+            mx[t] = -INFINITY;
+        }
+        int kb = 0, row0 = 4 * g4;                                // row0: this lane's first row of the group, in the document
+        for (int u0 = 0; u0 < U; u0 += NU) {
+#pragma unroll
+            for (int j = 0; j < NU; ++j) {
+                const int u = u0 + j;
+                if (u >= U) goto done;   // wave-uniform; no path re-enters the ring out of order
+                {
+                    const h16x8 a0 = ring[j][0], a1 = ring[j][1];
+#pragma unroll
+                    for (int t = 0; t < QT; ++t) {
+                        const h16x8 b0 = qf[((size_t)t * KB + kb) * 64 + lane];
+                        const h16x8 b1 = qf[((size_t)t * KB + kb + 1) * 64 + lane];
+                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, b0, acc[t], 0, 0, 0);
+                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b1, acc[t], 0, 0, 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    ring[j][0] = load(2 * (u + NU));
+                    ring[j][1] = load(2 * (u + NU) + 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                    kb += 2;
+                    if (kb == KB) {
+#pragma unroll
+                        for (int t = 0; t < QT; ++t) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) mx[t] = fmaxf(mx[t], row0 + r < len ? acc[t][r] : -INFINITY);
+                            acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+                        }
+                        kb = 0;
+                        row0 += 16;
+                    }
+                }
+            }
+        }
+    done:
+        float s = 0.f;
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {
+            float m = mx[t];
+            m = fmaxf(m, __shfl_xor(m, 16, 64));
+            m = fmaxf(m, __shfl_xor(m, 32, 64));
+            s = __fadd_rn(s, 16 * t + (lane & 15) < Lq ? m : 0.f);
+        }
+#pragma unroll
+        for (int o = 8; o >= 1; o >>= 1) s = __fadd_rn(s, __shfl_xor(s, o, 64));
+        if (lane == 0) out[c] = s;
+    }
+}
+
+template <int QT>
+hipError_t allow_lds()
+{
+    return hipFuncSetAttribute((const void *)maxsim_kernel<QT>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
+}
+
+}  // namespace
+
+int maxsim_prepare_device()
+{
+    hipError_t e = allow_lds<1>();
+    if (e == hipSuccess) e = allow_lds<2>();
+    if (e == hipSuccess) e = allow_lds<3>();
+    if (e == hipSuccess) e = allow_lds<4>();
+    return e == hipSuccess ? 0 : -1;
+}
+
+int launch_mv_pack(const float *d_rows, int64_t t0, int64_t count, int w, const int32_t *d_src_off,
+                   const void *d_table, int n_new, void *store, hipStream_t s)
+{
+    if (count <= 0 || n_new < 1 || w % 64 || w < 64 || w > 1024) return -1;
+    const int64_t blocks = (count + 3) / 4;
+    if (blocks > 0x7fffffff) return -1;
+    mv_pack_kernel<<<(unsigned)blocks, kThreads, 0, s>>>(d_rows, t0, count, w, d_src_off, (const int2 *)d_table, n_new,
+                                                         (h16x8 *)store);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_maxsim(const void *store, const void *d_table, int n_docs, int w, const float *d_q, int Lq,
+                  const int32_t *d_ids, int n, float *d_out, hipStream_t s)
+{
+    // (the candidate index advances by at most 4 * 4 * CUs per step, in int32)
+    if (Lq < 1 || Lq > 64 || n < 1 || n > 0x7fff0000 || n_docs < 0 || w % 64 || w < 64 || w > 1024) return -1;
+    const int QT = (Lq + 15) / 16;
+    const size_t lds = maxsim_lds_bytes(QT, w);
+    if (lds > (size_t)kLdsBudget) return -1;
+    // as many workgroups per CU as the LDS holds, at most 4 (16 waves of 8 KiB in flight)
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (int64_t)kLdsBudget / (int64_t)lds));
+    const int64_t P = std::max<int64_t>(1, std::min<int64_t>(per_cu * device_cu_count(), ((int64_t)n + 3) / 4));
+    const h16x8 *S = (const h16x8 *)store;
+    const int2 *T = (const int2 *)d_table;
+    switch (QT) {
+    case 1: maxsim_kernel<1><<<(unsigned)P, kThreads, lds, s>>>(S, T, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
+    case 2: maxsim_kernel<2><<<(unsigned)P, kThreads, lds, s>>>(S, T, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
+    case 3: maxsim_kernel<3><<<(unsigned)P, kThreads, lds, s>>>(S, T, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
+    default: maxsim_kernel<4><<<(unsigned)P, kThreads, lds, s>>>(S, T, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // namespace emb

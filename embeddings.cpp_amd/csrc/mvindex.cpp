@@ -1,0 +1,633 @@
+// The token store of late interaction (bert_hip.h bertx_mvindex_*): an append-only set
+// of documents, each a run of unit-length f16 token rows in the search kernel's fragment
+// order (kernels.h, maxsim.hip), the fused MaxSim scorer over it, and the text forms on
+// top of the per-token forward.  After creation a store knows only its device ordinal
+// and its width.  The ordering rules are the embedding index's (index.cpp).
+#include "bert.h"
+#include "bert_hip.h"
+
+#include "engine.h"
+#include "hip_check.h"
+
+#include <algorithm>
+#include <cstring>
+#include <limits>
+#include <mutex>
+#include <new>
+#include <vector>
+
+struct bertx_mvindex {
+    int ordinal = 0;
+    int w = 0;
+    int64_t cap_docs = 0, cap_slots = 0;   // as given at creation
+    int64_t n_docs = 0, used_slots = 0;    // used_slots: whole groups, 16 per group
+    void *store = nullptr;                 // f16, ceil(cap_slots / 16) groups in fragment order
+    int32_t *table = nullptr;              // device: (first group, len) per document
+    int32_t *src_off = nullptr;            // device: per document, its first source row in the add call that brought it
+    // page-locked host images of both, written per add at the new documents' own entries
+    // (an entry is rewritten only after a clear, which waits for the device first)
+    int32_t *h_table = nullptr, *h_src = nullptr;
+    // staging of the host forms
+    float *st_rows = nullptr, *st_q = nullptr, *st_out = nullptr;
+    int32_t *st_ids = nullptr, *st_tok = nullptr;
+    hipStream_t stream = nullptr;
+    hipEvent_t done = nullptr;             // completion of the last device operation on the store
+    hipStream_t last_stream = nullptr;
+    bool any = false;
+    std::mutex mu;
+    ~bertx_mvindex()
+    {
+        emb::DeviceGuard g(ordinal);
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (any && done) (void)hipEventSynchronize(done);
+        for (void *p : {store, (void *)table, (void *)src_off, (void *)st_rows, (void *)st_q, (void *)st_out,
+                        (void *)st_ids, (void *)st_tok})
+            if (p) (void)hipFree(p);
+        if (h_table) (void)hipHostFree(h_table);
+        if (h_src) (void)hipHostFree(h_src);
+        if (done) (void)hipEventDestroy(done);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace emb {
+namespace {
+
+constexpr int kStageRows = 2048;    // token rows per staged chunk of the host add
+constexpr int kStageIds = 65536;    // candidates per staged chunk of the host score
+constexpr int kMaxLq = 64;
+constexpr int64_t kChunkTokens = 1 << 17;   // per device forward of add_texts, as run_forward chunks
+constexpr int kChunkSeqs = 4096;
+
+bool capturing(hipStream_t s)
+{
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return st != hipStreamCaptureStatusNone;
+}
+
+// Orders an operation on `s` after the store's previous one and records it as the new
+// previous one (index.cpp Ordered; a capturing stream waits for and records nothing).
+struct Ordered {
+    bertx_mvindex &mv;
+    hipStream_t s;
+    const bool cap;
+    Ordered(bertx_mvindex &m, hipStream_t st) : mv(m), s(st), cap(capturing(st))
+    {
+        if (!cap && mv.any && mv.last_stream != s) (void)hipStreamWaitEvent(s, mv.done, 0);
+    }
+    ~Ordered()
+    {
+        if (cap) return;
+        (void)hipEventRecord(mv.done, s);
+        mv.last_stream = s;
+        mv.any = true;
+    }
+};
+
+// The first half of an add: checks the lens and both capacities and writes the new
+// documents' entries into the host images.  Returns 0 with *T the source rows and
+// *slots the slots they take; -1 / -2 as bertx_mvindex_add.
+int32_t plan_add(bertx_mvindex &mv, const int32_t *lens, int32_t n, int64_t *T, int64_t *slots)
+{
+    if (!lens || n < 1) return -1;
+    int64_t t = 0, g = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        if (lens[i] < 1) {
+            errorf("bertx_mvindex_add: document %d has %d tokens\n", i, lens[i]);
+            return -1;
+        }
+        t += lens[i];
+        g += (lens[i] + 15) / 16;
+    }
+    if (mv.n_docs + n > mv.cap_docs || mv.used_slots + 16 * g > mv.cap_slots) {
+        errorf("bertx_mvindex_add: %d documents of %lld token slots do not fit (%lld of %lld documents, %lld of %lld "
+               "slots used)\n", n, (long long)(16 * g), (long long)mv.n_docs, (long long)mv.cap_docs,
+               (long long)mv.used_slots, (long long)mv.cap_slots);
+        return -2;
+    }
+    if (t > 0x7fffffffll) return -1;   // source rows are indexed in int32 (src_off)
+    int64_t grp = mv.used_slots / 16, off = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const int64_t id = mv.n_docs + i;
+        mv.h_table[2 * id] = (int32_t)grp;
+        mv.h_table[2 * id + 1] = lens[i];
+        mv.h_src[id] = (int32_t)off;
+        grp += (lens[i] + 15) / 16;
+        off += lens[i];
+    }
+    *T = t;
+    *slots = 16 * g;
+    return 0;
+}
+
+// The new documents' entries to the device (asynchronous, from page-locked memory).
+int32_t upload_entries(bertx_mvindex &mv, int32_t n, hipStream_t s)
+{
+    const int64_t id = mv.n_docs;
+    HIP_RC(hipMemcpyAsync(mv.table + 2 * id, mv.h_table + 2 * id, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIP_RC(hipMemcpyAsync(mv.src_off + id, mv.h_src + id, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    return 0;
+}
+
+int32_t pack(bertx_mvindex &mv, const float *d_rows, int64_t t0, int64_t count, int32_t n, hipStream_t s)
+{
+    return launch_mv_pack(d_rows, t0, count, mv.w, mv.src_off + mv.n_docs, mv.table + 2 * mv.n_docs, n, mv.store, s);
+}
+
+int32_t commit(bertx_mvindex &mv, int32_t n, int64_t slots)
+{
+    const int32_t first = (int32_t)mv.n_docs;
+    mv.n_docs += n;
+    mv.used_slots += slots;
+    return first;
+}
+
+int32_t add_device_locked(bertx_mvindex &mv, const float *d_rows, const int32_t *lens, int32_t n, hipStream_t s)
+{
+    if (!d_rows) return -1;
+    int64_t T = 0, slots = 0;
+    int32_t rc = plan_add(mv, lens, n, &T, &slots);
+    if (rc != 0) return rc;
+    {
+        Ordered o(mv, s);
+        rc = upload_entries(mv, n, s);
+        if (rc == 0) rc = pack(mv, d_rows, 0, T, n, s);
+    }
+    if (rc != 0) {
+        (void)hipStreamSynchronize(s);   // the entries may be rewritten by the next add
+        return rc;
+    }
+    return commit(mv, n, slots);
+}
+
+int32_t score_device_locked(bertx_mvindex &mv, const float *d_q, int32_t Lq, const int32_t *d_ids, int32_t n,
+                            float *d_out, hipStream_t s)
+{
+    if (!d_q || !d_out || Lq < 1 || Lq > kMaxLq || n < 1) return -1;
+    Ordered o(mv, s);
+    return launch_maxsim(mv.store, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s);
+}
+
+// The query already on the device (mv.st_q or a caller's buffer on the store's stream):
+// scores of the host ids (or of all documents) into the host out, which is written
+// only when every chunk succeeded.
+int32_t score_host_ids(bertx_mvindex &mv, const float *d_q, int32_t Lq, const int32_t *ids, int32_t n, float *out)
+{
+    std::vector<float> hs((size_t)n);
+    std::vector<int32_t> all;
+    if (!ids) {
+        all.resize((size_t)n);
+        for (int32_t i = 0; i < n; ++i) all[(size_t)i] = i;
+        ids = all.data();
+    }
+    for (int32_t i = 0; i < n; i += kStageIds) {
+        const int32_t m = std::min(kStageIds, n - i);
+        HIP_RC(hipMemcpyAsync(mv.st_ids, ids + i, (size_t)m * 4, hipMemcpyHostToDevice, mv.stream));
+        const int32_t rc = score_device_locked(mv, d_q, Lq, mv.st_ids, m, mv.st_out, mv.stream);
+        if (rc != 0) return rc;
+        HIP_RC(hipMemcpyAsync(hs.data() + i, mv.st_out, (size_t)m * 4, hipMemcpyDeviceToHost, mv.stream));
+        HIP_RC(hipStreamSynchronize(mv.stream));
+    }
+    std::memcpy(out, hs.data(), hs.size() * 4);
+    return 0;
+}
+
+// The context's replica on the store's GPU, or -1.
+int32_t slot_on(struct bert_ctx *ctx, int ordinal)
+{
+    for (int32_t s = 0; s < bertx_num_devices(ctx); ++s)
+        if (bertx_device_ordinal(ctx, s) == ordinal) return s;
+    return -1;
+}
+
+int32_t text_ctx_ok(bertx_mvindex *mv, struct bert_ctx *ctx, const char *who, int32_t *slot)
+{
+    if (!mv || !ctx) return -1;
+    if (bertx_num_devices(ctx) == 0 || bert_n_embd(ctx) != mv->w) {
+        errorf("%s: the context cannot produce token rows of width %d\n", who, mv->w);
+        return -1;
+    }
+    *slot = slot_on(ctx, mv->ordinal);
+    if (*slot < 0) {
+        errorf("%s: the context has no replica on the store's device %d\n", who, mv->ordinal);
+        return -1;
+    }
+    return 0;
+}
+
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+}  // namespace
+
+bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t cap_slots)
+{
+    if (w % 64 || w < 64 || w > 1024) {
+        errorf("bertx_mvindex_create: width %d is not a multiple of 64 in 64 .. 1024\n", w);
+        return nullptr;
+    }
+    if (cap_docs < 1 || cap_docs > 0x7ffffff0ll || cap_slots < 16 || cap_slots > (0x7ffffff0ll << 4)) {
+        errorf("bertx_mvindex_create: capacity of %lld documents / %lld token slots is not in 1 .. 2^31 - 16 / "
+               "16 .. 2^35 - 256\n", (long long)cap_docs, (long long)cap_slots);
+        return nullptr;
+    }
+    DeviceGuard g(ordinal);
+    if (!g.ok()) {
+        errorf("bertx_mvindex_create: cannot select device %d\n", ordinal);
+        return nullptr;
+    }
+    bertx_mvindex *mv = new (std::nothrow) bertx_mvindex();
+    if (!mv) return nullptr;
+    mv->ordinal = ordinal;
+    mv->w = w;
+    mv->cap_docs = cap_docs;
+    mv->cap_slots = cap_slots;
+    const size_t store_bytes = (size_t)((cap_slots + 15) / 16) * 16 * (size_t)w * 2;
+    const bool ok = maxsim_prepare_device() == 0 &&
+                    hipStreamCreateWithFlags(&mv->stream, hipStreamNonBlocking) == hipSuccess &&
+                    hipEventCreateWithFlags(&mv->done, hipEventDisableTiming) == hipSuccess &&
+                    hipMalloc(&mv->store, store_bytes) == hipSuccess &&
+                    hipMalloc((void **)&mv->table, (size_t)cap_docs * 8) == hipSuccess &&
+                    hipMalloc((void **)&mv->src_off, (size_t)cap_docs * 4) == hipSuccess &&
+                    hipHostMalloc((void **)&mv->h_table, (size_t)cap_docs * 8, hipHostMallocDefault) == hipSuccess &&
+                    hipHostMalloc((void **)&mv->h_src, (size_t)cap_docs * 4, hipHostMallocDefault) == hipSuccess &&
+                    hipMalloc((void **)&mv->st_rows, (size_t)kStageRows * w * 4) == hipSuccess &&
+                    hipMalloc((void **)&mv->st_q, (size_t)kMaxLq * w * 4) == hipSuccess &&
+                    hipMalloc((void **)&mv->st_out, (size_t)kStageIds * 4) == hipSuccess &&
+                    hipMalloc((void **)&mv->st_ids, (size_t)kStageIds * 4) == hipSuccess &&
+                    hipMalloc((void **)&mv->st_tok, (size_t)(kMaxLq + 2) * 4) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        errorf("bertx_mvindex_create: device %d could not allocate %zu bytes of token rows (+ %lld table entries)\n",
+               ordinal, store_bytes, (long long)cap_docs);
+        delete mv;
+        return nullptr;
+    }
+    return mv;
+}
+
+}  // namespace emb
+
+using emb::DeviceGuard;
+
+extern "C" {
+
+struct bertx_mvindex *bertx_mvindex_create(struct bert_ctx *ctx, int32_t slot, int32_t width, int32_t capacity_docs,
+                                           int64_t capacity_token_slots)
+{
+    if (!ctx) {
+        emb::errorf("bertx_mvindex_create: no context\n");
+        return nullptr;
+    }
+    if (bertx_num_devices(ctx) == 0) {
+        emb::errorf("bertx_mvindex_create: tokenizer-only context (BERT_HOST_ONLY): no device to hold a token store\n");
+        return nullptr;
+    }
+    const int ordinal = bertx_device_ordinal(ctx, slot);
+    if (ordinal < 0) {
+        emb::errorf("bertx_mvindex_create: slot %d is not one of the context's %d device(s)\n", slot,
+                    bertx_num_devices(ctx));
+        return nullptr;
+    }
+    return emb::mvindex_create_on(ordinal, width, capacity_docs, capacity_token_slots);
+}
+
+void bertx_mvindex_free(struct bertx_mvindex *mv) { delete mv; }
+
+int32_t bertx_mvindex_clear(struct bertx_mvindex *mv)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    // the host images' entries are about to be reused: no copy of them may be in flight
+    if (mv->any) HIP_RC(hipEventSynchronize(mv->done));
+    mv->n_docs = 0;
+    mv->used_slots = 0;
+    return 0;
+}
+
+int32_t bertx_mvindex_docs(struct bertx_mvindex *mv)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    return (int32_t)mv->n_docs;
+}
+
+int64_t bertx_mvindex_token_slots(struct bertx_mvindex *mv)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    return mv->used_slots;
+}
+
+int32_t bertx_mvindex_capacity_docs(struct bertx_mvindex *mv) { return mv ? (int32_t)mv->cap_docs : -1; }
+int64_t bertx_mvindex_capacity_token_slots(struct bertx_mvindex *mv) { return mv ? mv->cap_slots : -1; }
+int32_t bertx_mvindex_dim(struct bertx_mvindex *mv) { return mv ? mv->w : -1; }
+
+int32_t bertx_mvindex_add_device(struct bertx_mvindex *mv, const float *d_rows, const int32_t *lens, int32_t n,
+                                 void *stream)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    return emb::add_device_locked(*mv, d_rows, lens, n, stream ? (hipStream_t)stream : mv->stream);
+}
+
+int32_t bertx_mvindex_add(struct bertx_mvindex *mv, const float *rows, const int32_t *lens, int32_t n)
+{
+    if (!mv || !rows) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    int64_t T = 0, slots = 0;
+    int32_t rc = emb::plan_add(*mv, lens, n, &T, &slots);
+    if (rc != 0) return rc;
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    {
+        emb::Ordered o(*mv, mv->stream);
+        rc = emb::upload_entries(*mv, n, mv->stream);
+        for (int64_t t = 0; t < T && rc == 0; t += emb::kStageRows) {
+            const int64_t m = std::min<int64_t>(emb::kStageRows, T - t);
+            if (hipMemcpyAsync(mv->st_rows, rows + (size_t)t * mv->w, (size_t)m * mv->w * 4, hipMemcpyHostToDevice,
+                               mv->stream) != hipSuccess)
+                rc = -1;
+            if (rc == 0) rc = emb::pack(*mv, mv->st_rows, t, m, n, mv->stream);
+            if (rc == 0 && hipStreamSynchronize(mv->stream) != hipSuccess) rc = -1;   // the staging buffer is reused
+        }
+    }
+    if (rc != 0) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(mv->stream);
+        emb::errorf("bertx_mvindex_add: device %d failed while adding (%d)\n", mv->ordinal, rc);
+        return rc;
+    }
+    return emb::commit(*mv, n, slots);
+}
+
+int32_t bertx_mvindex_doc_len(struct bertx_mvindex *mv, int32_t id)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    if (id < 0 || id >= mv->n_docs) return -1;
+    return mv->h_table[2 * (size_t)id + 1];
+}
+
+int32_t bertx_mvindex_doc(struct bertx_mvindex *mv, int32_t id, float *out)
+{
+    if (!mv || !out) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    if (id < 0 || id >= mv->n_docs) return -1;
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    try {
+        const int w = mv->w, KB = w / 32;
+        const int64_t first = mv->h_table[2 * (size_t)id], len = mv->h_table[2 * (size_t)id + 1];
+        const size_t group_halfs = (size_t)16 * w;
+        std::vector<uint16_t> raw((size_t)((len + 15) / 16) * group_halfs);
+        if (mv->any) HIP_RC(hipEventSynchronize(mv->done));
+        HIP_RC(hipMemcpy(raw.data(), (const uint16_t *)mv->store + (size_t)first * group_halfs, raw.size() * 2,
+                         hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < len; ++r) {
+            const uint16_t *grp = raw.data() + (size_t)(r / 16) * group_halfs;
+            float *o = out + (size_t)r * w;
+            for (int kb = 0; kb < KB; ++kb)
+                for (int q = 0; q < 4; ++q)
+                    for (int j = 0; j < 8; ++j)
+                        o[32 * kb + 8 * q + j] = emb::f16_to_f32(grp[((size_t)kb * 64 + 16 * q + (r & 15)) * 8 + j]);
+        }
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_mvindex_doc: out of host memory\n");
+        return -1;
+    }
+    return 0;
+}
+
+int32_t bertx_mvindex_score_device(struct bertx_mvindex *mv, const float *d_q, int32_t Lq, const int32_t *d_ids,
+                                   int32_t n, float *d_out, void *stream)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    return emb::score_device_locked(*mv, d_q, Lq, d_ids, n, d_out, stream ? (hipStream_t)stream : mv->stream);
+}
+
+int32_t bertx_mvindex_score(struct bertx_mvindex *mv, const float *q, int32_t Lq, const int32_t *ids, int32_t n,
+                            float *out)
+{
+    if (!mv || !q || !out || Lq < 1 || Lq > emb::kMaxLq || n < 1) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    try {
+        HIP_RC(hipMemcpyAsync(mv->st_q, q, (size_t)Lq * mv->w * 4, hipMemcpyHostToDevice, mv->stream));
+        return emb::score_host_ids(*mv, mv->st_q, Lq, ids, n, out);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_mvindex_score: out of host memory\n");
+        return -1;
+    }
+}
+
+int32_t bertx_mvindex_add_texts(struct bertx_mvindex *mv, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                const char **texts)
+{
+    int32_t slot = -1;
+    if (!texts || n < 1) return -1;
+    if (emb::text_ctx_ok(mv, ctx, "bertx_mvindex_add_texts", &slot) != 0) return -1;
+    try {
+        const int32_t n_max = bert_n_max_tokens(ctx);
+        std::vector<int32_t> ids((size_t)n * n_max), lens((size_t)n);
+        if (bertx_tokenize_batch(ctx, n_threads, n, texts, n_max, ids.data(), lens.data()) != 0) return -1;
+        for (int32_t i = 0; i < n; ++i)
+            if (lens[(size_t)i] > n_max) {
+                emb::errorf("Too many tokens, maximum is %d\n", n_max);
+                emb::errorf("bertx_mvindex_add_texts: text %d has %d tokens; nothing was added\n", i, lens[(size_t)i]);
+                return -4;
+            }
+        std::lock_guard<std::mutex> lk(mv->mu);
+        int64_t T = 0, slots = 0;
+        int32_t rc = emb::plan_add(*mv, lens.data(), n, &T, &slots);
+        if (rc != 0) return rc;
+        DeviceGuard g(mv->ordinal);
+        HIP_RC(g.status());
+        // chunks of whole texts as run_forward cuts them; each chunk's token rows go from
+        // the forward's device output straight into the pack kernel on the store's stream
+        std::vector<int32_t> flat, cu;
+        emb::DevBuf d_ids, d_cu, d_rows;
+        int64_t cap_tok = 0, cap_seq = 0;
+        {
+            emb::Ordered o(*mv, mv->stream);
+            rc = emb::upload_entries(*mv, n, mv->stream);
+            int32_t i = 0;
+            int64_t t0 = 0;
+            while (i < n && rc == 0) {
+                flat.clear();
+                cu.assign(1, 0);
+                int max_len = 0;
+                while (i < n && (cu.size() == 1 || ((int64_t)flat.size() + lens[(size_t)i] <= emb::kChunkTokens &&
+                                                    (int)cu.size() - 1 < emb::kChunkSeqs))) {
+                    const int32_t *p = ids.data() + (size_t)i * n_max;
+                    flat.insert(flat.end(), p, p + lens[(size_t)i]);
+                    cu.push_back((int32_t)flat.size());
+                    max_len = std::max(max_len, (int)lens[(size_t)i]);
+                    ++i;
+                }
+                const int64_t tok = (int64_t)flat.size(), seqs = (int64_t)cu.size() - 1;
+                if (tok > cap_tok || seqs > cap_seq) {
+                    HIP_RC(hipStreamSynchronize(mv->stream));
+                    for (emb::DevBuf *b : {&d_ids, &d_cu, &d_rows})
+                        if (b->p) { (void)hipFree(b->p); b->p = nullptr; }
+                    cap_tok = std::max(tok, cap_tok);
+                    cap_seq = std::max(seqs, cap_seq);
+                    HIP_RC(hipMalloc(&d_ids.p, (size_t)cap_tok * 4));
+                    HIP_RC(hipMalloc(&d_cu.p, (size_t)(cap_seq + 1) * 4));
+                    HIP_RC(hipMalloc(&d_rows.p, (size_t)cap_tok * mv->w * 4));
+                }
+                if (bertx_reserve(ctx, slot, (int32_t)tok, (int32_t)seqs) != 0) { rc = -1; break; }
+                HIP_RC(hipMemcpyAsync(d_ids.p, flat.data(), (size_t)tok * 4, hipMemcpyHostToDevice, mv->stream));
+                HIP_RC(hipMemcpyAsync(d_cu.p, cu.data(), (size_t)(seqs + 1) * 4, hipMemcpyHostToDevice, mv->stream));
+                rc = bertx_forward_tokens_device(ctx, slot, (const int32_t *)d_ids.p, (const int32_t *)d_cu.p,
+                                                 (int32_t)seqs, max_len, (int32_t)tok, (float *)d_rows.p, mv->stream);
+                if (rc == 0) rc = emb::pack(*mv, (const float *)d_rows.p, t0, tok, n, mv->stream);
+                // the chunk's host and device buffers are reused by the next one
+                if (rc == 0 && hipStreamSynchronize(mv->stream) != hipSuccess) rc = -1;
+                t0 += tok;
+            }
+        }
+        if (rc != 0) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(mv->stream);
+            emb::errorf("bertx_mvindex_add_texts: device %d failed while adding (%d)\n", mv->ordinal, rc);
+            return rc < 0 ? rc : -1;
+        }
+        return emb::commit(*mv, n, slots);
+    } catch (const std::exception &ex) {
+        emb::errorf("bertx_mvindex_add_texts: %s\n", ex.what());
+        return -1;
+    }
+}
+
+int32_t bertx_mvindex_score_text(struct bertx_mvindex *mv, struct bert_ctx *ctx, const char *query, const int32_t *ids,
+                                 int32_t n, float *out)
+{
+    int32_t slot = -1;
+    if (!query || !out || n < 1) return -1;
+    if (emb::text_ctx_ok(mv, ctx, "bertx_mvindex_score_text", &slot) != 0) return -1;
+    try {
+        const int32_t n_max = bert_n_max_tokens(ctx);
+        std::vector<int32_t> tok((size_t)n_max + 2);
+        int32_t L = 0;
+        bert_tokenize(ctx, query, tok.data(), &L, n_max);
+        if (L > n_max || L > emb::kMaxLq) {
+            emb::errorf("bertx_mvindex_score_text: the query has %d tokens, maximum is %d\n", L,
+                        std::min<int32_t>(n_max, emb::kMaxLq));
+            return -4;
+        }
+        if (L < 1) return -1;
+        std::lock_guard<std::mutex> lk(mv->mu);
+        DeviceGuard g(mv->ordinal);
+        HIP_RC(g.status());
+        // ids [L] and cu {0, L} in one staging buffer, the token rows into the query staging
+        std::vector<int32_t> h((size_t)emb::kMaxLq + 2, 0);
+        std::memcpy(h.data(), tok.data(), (size_t)L * 4);
+        h[(size_t)emb::kMaxLq] = 0;
+        h[(size_t)emb::kMaxLq + 1] = L;
+        if (bertx_reserve(ctx, slot, L, 1) != 0) return -1;
+        int32_t rc = 0;
+        {
+            emb::Ordered o(*mv, mv->stream);
+            HIP_RC(hipMemcpyAsync(mv->st_tok, h.data(), h.size() * 4, hipMemcpyHostToDevice, mv->stream));
+            HIP_RC(hipStreamSynchronize(mv->stream));   // h is pageable and leaves scope
+            rc = bertx_forward_tokens_device(ctx, slot, mv->st_tok, mv->st_tok + emb::kMaxLq, 1, L, L, mv->st_q,
+                                             mv->stream);
+        }
+        if (rc != 0) return rc < 0 ? rc : -1;
+        return emb::score_host_ids(*mv, mv->st_q, L, ids, n, out);
+    } catch (const std::exception &ex) {
+        emb::errorf("bertx_mvindex_score_text: %s\n", ex.what());
+        return -1;
+    }
+}
+
+// MaxSim micro-benchmark (bert_hip.h): device 0, no context.
+int32_t bertx_bench_maxsim(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t iters,
+                           float *avg_us)
+{
+    using namespace emb;
+    if (n_docs < 1 || doc_len < 0 || doc_len > 4096 || n_cand < 1 || iters < 1 || !avg_us || hip_device_count() == 0)
+        return -1;
+    try {
+        // ragged (doc_len 0): 16 .. 512 tokens by a hash of the id
+        std::vector<int32_t> lens((size_t)n_docs), ids((size_t)n_cand);
+        int64_t slots = 0;
+        for (int32_t i = 0; i < n_docs; ++i) {
+            uint32_t h = (uint32_t)i * 2654435761u + 99u;
+            h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
+            lens[(size_t)i] = doc_len ? doc_len : 16 + (int32_t)(h % 497u);
+            slots += (lens[(size_t)i] + 15) / 16 * 16;
+        }
+        for (int32_t c = 0; c < n_cand; ++c) ids[(size_t)c] = (int32_t)(((uint64_t)c * 2654435761ull + 12345ull) % (uint64_t)n_docs);
+        DeviceGuard guard(0);
+        HIP_RC(guard.status());
+        struct Holder {
+            bertx_mvindex *mv = nullptr;
+            hipStream_t s = nullptr;
+            hipEvent_t a = nullptr, b = nullptr;
+            DevBuf rows, q, id, out;
+            ~Holder()
+            {
+                if (s) (void)hipStreamSynchronize(s);
+                if (a) (void)hipEventDestroy(a);
+                if (b) (void)hipEventDestroy(b);
+                if (s) (void)hipStreamDestroy(s);
+                bertx_mvindex_free(mv);
+            }
+        } H;
+        H.mv = mvindex_create_on(0, w, n_docs, slots);
+        if (!H.mv) return -1;
+        HIP_RC(hipStreamCreateWithFlags(&H.s, hipStreamNonBlocking));
+        HIP_RC(hipEventCreate(&H.a));
+        HIP_RC(hipEventCreate(&H.b));
+        constexpr int64_t kFillRows = 1 << 18;
+        HIP_RC(hipMalloc(&H.rows.p, (size_t)(kFillRows + 4096) * w * 4));
+        HIP_RC(hipMalloc(&H.q.p, (size_t)kMaxLq * w * 4));
+        HIP_RC(hipMalloc(&H.id.p, (size_t)n_cand * 4));
+        HIP_RC(hipMalloc(&H.out.p, (size_t)n_cand * 4));
+        for (int32_t i = 0; i < n_docs;) {
+            int32_t j = i;
+            int64_t rows = 0;
+            while (j < n_docs && (j == i || rows + lens[(size_t)j] <= kFillRows)) rows += lens[(size_t)j++];
+            if (launch_unit_rows((float *)H.rows.p, rows, w, 12345u + (uint32_t)i, H.s) != 0) return -1;
+            if (bertx_mvindex_add_device(H.mv, (const float *)H.rows.p, lens.data() + i, j - i, H.s) < 0) return -1;
+            HIP_RC(hipStreamSynchronize(H.s));   // the fill buffer is reused
+            i = j;
+        }
+        if (Lq < 1 || Lq > kMaxLq || launch_unit_rows((float *)H.q.p, Lq, w, 777u, H.s) != 0) return -1;
+        HIP_RC(hipMemcpyAsync(H.id.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, H.s));
+        HIP_RC(hipStreamSynchronize(H.s));
+        auto run = [&] {
+            return bertx_mvindex_score_device(H.mv, (const float *)H.q.p, Lq, (const int32_t *)H.id.p, n_cand,
+                                              (float *)H.out.p, H.s);
+        };
+        for (int i = 0; i < 3; ++i)
+            if (run() != 0) return -1;
+        HIP_RC(hipEventRecord(H.a, H.s));
+        for (int i = 0; i < iters; ++i)
+            if (run() != 0) return -1;
+        HIP_RC(hipEventRecord(H.b, H.s));
+        HIP_RC(hipEventSynchronize(H.b));
+        float ms = 0.f;
+        HIP_RC(hipEventElapsedTime(&ms, H.a, H.b));
+        *avg_us = ms * 1000.f / (float)iters;
+        return 0;
+    } catch (const std::exception &ex) {
+        emb::errorf("bertx_bench_maxsim: %s\n", ex.what());
+        return -1;
+    }
+}
+
+}  // extern "C"

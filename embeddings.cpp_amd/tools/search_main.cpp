@@ -2,7 +2,7 @@
 // corpus, then print the k closest texts of every query) with the corpus resident on
 // the GPU and the search fused there (bertx_index_*).
 //
-// usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8] [-r RERANK_MODEL [-c N]]
+// usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8] [-r RERANK_MODEL [-c N] | -l [-c N]]
 // One text per line of CORPUS.txt; queries from stdin, one per line, `q` or EOF ends.
 // Per hit one line: rank<TAB>id<TAB>score<TAB>text.
 // -s: how the index stores its rows (bertx_index_create_ex): f16, the default, or int8
@@ -11,6 +11,10 @@
 // index's 128) are re-scored as (query, text) pairs by the cross-encoder RERANK_MODEL
 // (a model file with a classification head, bertx_rerank) and the k best of those are
 // printed, ordered by the reranker's first-label logit, which is the printed score.
+// -l: late interaction as the second stage, instead of -r.  While indexing, every text's
+// per-token vectors go into a token store beside the index (bertx_mvindex_*); per query
+// the N best of the index are re-scored by MaxSim and the k best of those are printed,
+// ordered by that score (equal scores by ascending id), which is the printed score.
 #include "bert.h"
 #include "bert_hip.h"
 
@@ -27,6 +31,7 @@ int main(int argc, char **argv)
 {
     const char *model = nullptr, *corpus = nullptr, *rerank = nullptr;
     int k = 3, threads = 4, cand = 0, storage = BERTX_INDEX_F16;
+    bool late = false;
     for (int i = 1; i < argc; ++i) {
         const bool has = i + 1 < argc;
         if (!std::strcmp(argv[i], "-m") && has) model = argv[++i];
@@ -37,12 +42,15 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "-s") && has && !std::strcmp(argv[i + 1], "int8")) { storage = BERTX_INDEX_I8; ++i; }
         else if (!std::strcmp(argv[i], "-r") && has) rerank = argv[++i];
         else if (!std::strcmp(argv[i], "-c") && has) cand = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "-l")) late = true;
         else { model = nullptr; break; }
     }
-    if (rerank && cand == 0) cand = std::min(128, 4 * k);
-    if (!model || !corpus || k < 1 || k > 128 || threads < 1 || (rerank ? cand < k || cand > 128 : cand != 0)) {
+    const bool second = rerank || late;
+    if (second && cand == 0) cand = std::min(128, 4 * k);
+    if (!model || !corpus || k < 1 || k > 128 || threads < 1 || (rerank && late) ||
+        (second ? cand < k || cand > 128 : cand != 0)) {
         std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads] [-s f16|int8] "
-                             "[-r RERANK_MODEL [-c N (k..128, default 4 k)]]\n", argv[0]);
+                             "[-r RERANK_MODEL [-c N (k..128, default 4 k)] | -l [-c N]]\n", argv[0]);
         return 2;
     }
     std::vector<std::string> texts;
@@ -82,6 +90,24 @@ int main(int argc, char **argv)
         bert_free(ctx);
         return 1;
     }
+    bertx_mvindex *mv = nullptr;
+    if (late) {
+        // the store's size: every text's token count, as bert_tokenize counts it
+        const int32_t n_max = bert_n_max_tokens(ctx);
+        std::vector<bert_vocab_id> tok((size_t)n_max);
+        int64_t slots = 0;
+        for (const std::string &t : texts) {
+            int32_t n = 0;
+            bert_tokenize(ctx, t.c_str(), tok.data(), &n, n_max);
+            slots += (std::max(n, 1) + 15) / 16 * 16;
+        }
+        mv = bertx_mvindex_create(ctx, 0, bert_n_embd(ctx), (int32_t)texts.size(), slots);
+        if (!mv) {
+            bertx_index_free(idx);
+            bert_free(ctx);
+            return 1;
+        }
+    }
     int rc = 0;
     // the corpus in batches (one encoder call each)
     for (size_t i = 0; i < texts.size() && rc == 0; i += 256) {
@@ -90,9 +116,12 @@ int main(int argc, char **argv)
         if (bertx_index_add_texts(idx, ctx, threads, (int32_t)p.size(), p.data()) < 0) {
             std::fprintf(stderr, "search: indexing failed at text %zu\n", i);
             rc = 1;
+        } else if (mv && bertx_mvindex_add_texts(mv, ctx, threads, (int32_t)p.size(), p.data()) < 0) {
+            std::fprintf(stderr, "search: token indexing failed at text %zu\n", i);
+            rc = 1;
         }
     }
-    const int kq = rerank ? cand : k;   // what the index is asked for
+    const int kq = second ? cand : k;   // what the index is asked for
     std::vector<float> scores((size_t)kq);
     std::vector<int32_t> ids((size_t)kq);
     for (std::string q; rc == 0 && std::getline(std::cin, q);) {
@@ -104,6 +133,26 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "search: query failed\n");
             rc = 1;
             break;
+        }
+        if (mv) {
+            // the candidates re-scored by MaxSim (a -1 fill slot scores -inf and sorts last)
+            std::vector<float> ms((size_t)kq);
+            if (bertx_mvindex_score_text(mv, ctx, qp, ids.data(), kq, ms.data()) != 0) {
+                std::fprintf(stderr, "search: late-interaction scoring failed\n");
+                rc = 1;
+                break;
+            }
+            std::vector<int> ord((size_t)kq);
+            for (int j = 0; j < kq; ++j) ord[(size_t)j] = j;
+            std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) {
+                return ms[(size_t)a] > ms[(size_t)b] || (ms[(size_t)a] == ms[(size_t)b] && ids[(size_t)a] < ids[(size_t)b]);
+            });
+            for (int j = 0; j < k && ids[(size_t)ord[(size_t)j]] >= 0; ++j) {
+                const int c = ord[(size_t)j];
+                std::printf("%d\t%d\t%.4f\t%s\n", j + 1, ids[(size_t)c], ms[(size_t)c], texts[(size_t)ids[(size_t)c]].c_str());
+            }
+            std::fflush(stdout);
+            continue;
         }
         if (rctx) {
             // the candidates re-scored as (query, text) pairs; the k best by the first logit,
@@ -135,6 +184,7 @@ int main(int argc, char **argv)
             std::printf("%d\t%d\t%.4f\t%s\n", j + 1, ids[(size_t)j], scores[(size_t)j], texts[(size_t)ids[(size_t)j]].c_str());
         std::fflush(stdout);
     }
+    bertx_mvindex_free(mv);
     bertx_index_free(idx);
     if (rctx) bert_free(rctx);
     bert_free(ctx);

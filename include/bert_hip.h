@@ -468,6 +468,105 @@ BERT_API int32_t bertx_index_search_texts(struct bertx_index *idx, struct bert_c
                                           const char **texts, int32_t k, float *scores, int32_t *ids);
 
 /*
+ * Token store: late interaction (ColBERT's MaxSim) over per-token vectors.  An
+ * append-only set of documents resident in the HBM of one of the context's GPUs; a
+ * document is len >= 1 token vectors of the store's width, each stored as a unit-length
+ * f16 row; a query of Lq <= 64 token vectors scores a list of documents in one launch.
+ * Document ids are int32 insertion order from 0.  The conventions are the embedding
+ * index's: plain C types, a message and a negative return on refusal with the outputs
+ * untouched, the caller's HIP device left as it was, host calls on one store
+ * serialised, and the stream ordering rules of the index (above) word for word.
+ *
+ * bertx_mvindex_create: a store of `width` (a multiple of 64 in 64 .. 1024; it need not
+ * be n_embd, so a caller can store vectors it projected itself) on GPU `slot`, for at
+ * most capacity_docs documents in at most capacity_token_slots token slots, or NULL
+ * after a message (bad slot, width or capacity, allocation failure, a tokenizer-only
+ * context).  A document of len tokens takes 16 ceil(len / 16) slots: every document
+ * starts on a 16-row group of the search kernel's f16 fragment order.  The store keeps
+ * only the device ordinal and the width: it may outlive the context.  Its buffers never
+ * move.  _clear sets both counts back to 0; _docs and _token_slots return what is used.
+ *
+ * The arithmetic, one normaliser for stored rows and for queries, every named operation
+ * rounded once to f32 (IEEE, nearest even):
+ *   ss = sum_i x_i * x_i, summed in an order that depends on the width only;
+ *   ss == 0: the row is stored as zeros;  otherwise rinv = 1 / sqrt(ss) (sqrt, then the
+ *   division) and v_i = f16(x_i * rinv), nearest even;
+ *   sim(q, c) = the f16 search score of the embedding index: both operands f16, products
+ *   accumulated in f32 from 0 in ascending blocks of 32 elements;
+ *   score(doc) = sum_{i < Lq} max_{j < len} sim(q_i, c_j): the max is exact, the sum over
+ *   i is f32 in an order that depends on Lq only.
+ * The slots of a document's last group past len are never counted, whatever they hold
+ * (a similarity can be negative, so they count as -inf, not 0).  A document's score
+ * depends on the query and on that document's rows only, bit for bit: not on its id,
+ * the other documents, the candidate list, its length or its order.  Against the exact
+ * value v = x_i / |x| a stored element is within |v| (2^-11 + (w + 8) 2^-24) + 2^-24;
+ * against the exact MaxSim of the stored f16 values a score is within
+ * Lq (2 w + Lq) 2^-24.
+ *
+ * bertx_mvindex_add / _add_device: n documents, their token rows float[T][width]
+ * consecutive (host / device), T = sum lens, with lens int32[n] always on the host;
+ * returns the id of the first new document, or a negative error with nothing changed
+ * (-2: over either capacity; -1: a len < 1 or bad arguments).  One call of several
+ * documents stores the bits that one call per document stores.  _doc_len: a document's
+ * len (-1: no such id).  _doc: its stored f16 values widened, into out float[len][width].
+ *
+ * bertx_mvindex_score / _score_device: out[c] = score(document ids[c]) for c < n; ids
+ * NULL: document c (pass n = _docs for all).  An id outside [0, docs) scores -inf and
+ * disturbs nothing else, so the id output of bertx_index_search with its -1 fill slots
+ * can be passed unchanged.  Only out[0 .. n) is written.  The host form refuses (-1) Lq
+ * outside 1 .. 64 and n < 1.  The device form takes device pointers on the store's GPU
+ * and a hipStream_t (NULL: the store's own stream); it is asynchronous, allocates
+ * nothing and never synchronises, so it can be captured into a HIP graph (a captured
+ * score keeps the document count of its capture).  The add forms are asynchronous on
+ * the stream but are not meant for capture.
+ *
+ * The text forms need width == n_embd and a replica of the context on the store's GPU
+ * (-1 otherwise).  _add_texts tokenises with bert_tokenize's rule, runs the per-token
+ * forward (bertx_forward_tokens_device) on the store's GPU in chunks of at most 2^17
+ * tokens and 4,096 texts, and packs the final hidden states from the forward's device
+ * output: one document per text, len = the text's token count ([CLS] and [SEP]
+ * included).  An input over n_max_tokens fails the whole call (-4) with nothing added.
+ * _score_text does the same for one query; a query over 64 tokens (or over
+ * n_max_tokens) fails with -4.
+ *
+ * bertx_bench_maxsim (device 0, no context): a store of n_docs documents of doc_len
+ * random unit rows each (doc_len 0: ragged, 16 .. 512 by a hash of the id), a random
+ * query of Lq rows, n_cand candidate ids spread over the store by a multiplicative
+ * hash; average device time of `iters` calls of bertx_mvindex_score_device after 3
+ * warm-up calls.
+ *
+ * Not provided: a ColBERT `linear` projection record with its [Q] / [D] markers, [MASK]
+ * query augmentation and punctuation skiplist (the free width lets a caller add vectors
+ * it projected itself through _add / _add_device); int8 token storage; a full-scan fused
+ * top-k; several queries per call; sharding over GPUs; deleting, saving and loading.
+ */
+struct bertx_mvindex;
+BERT_API struct bertx_mvindex *bertx_mvindex_create(struct bert_ctx *ctx, int32_t slot, int32_t width,
+                                                    int32_t capacity_docs, int64_t capacity_token_slots);
+BERT_API void bertx_mvindex_free(struct bertx_mvindex *mv);
+BERT_API int32_t bertx_mvindex_clear(struct bertx_mvindex *mv);
+BERT_API int32_t bertx_mvindex_docs(struct bertx_mvindex *mv);
+BERT_API int64_t bertx_mvindex_token_slots(struct bertx_mvindex *mv);
+BERT_API int32_t bertx_mvindex_capacity_docs(struct bertx_mvindex *mv);
+BERT_API int64_t bertx_mvindex_capacity_token_slots(struct bertx_mvindex *mv);
+BERT_API int32_t bertx_mvindex_dim(struct bertx_mvindex *mv);
+BERT_API int32_t bertx_mvindex_add(struct bertx_mvindex *mv, const float *rows, const int32_t *lens, int32_t n);
+BERT_API int32_t bertx_mvindex_add_device(struct bertx_mvindex *mv, const float *d_rows, const int32_t *lens, int32_t n,
+                                          void *stream);
+BERT_API int32_t bertx_mvindex_doc_len(struct bertx_mvindex *mv, int32_t id);
+BERT_API int32_t bertx_mvindex_doc(struct bertx_mvindex *mv, int32_t id, float *out);
+BERT_API int32_t bertx_mvindex_score(struct bertx_mvindex *mv, const float *q, int32_t Lq, const int32_t *ids, int32_t n,
+                                     float *out);
+BERT_API int32_t bertx_mvindex_score_device(struct bertx_mvindex *mv, const float *d_q, int32_t Lq, const int32_t *d_ids,
+                                            int32_t n, float *d_out, void *stream);
+BERT_API int32_t bertx_mvindex_add_texts(struct bertx_mvindex *mv, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                         const char **texts);
+BERT_API int32_t bertx_mvindex_score_text(struct bertx_mvindex *mv, struct bert_ctx *ctx, const char *query,
+                                          const int32_t *ids, int32_t n, float *out);
+BERT_API int32_t bertx_bench_maxsim(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand,
+                                    int32_t iters, float *avg_us);
+
+/*
  * Cross-encoder reranking: token types and a classification head.
  *
  * Model file.  Four optional records behind the encoder's: pooler.dense.weight
