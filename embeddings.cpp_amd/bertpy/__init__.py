@@ -242,6 +242,28 @@ def load_lib(path=None):
         L.bertx_bench_maxsim.argtypes = [c_i32] * 6 + [c_f32p]
     except AttributeError:
         pass
+    try:   # (ColBERT checkpoints: the projection record and its entries; absent from older BERT_LIB builds)
+        L.bertx_convert_hf_colbert.restype = c_i32
+        L.bertx_convert_hf_colbert.argtypes = [ctypes.c_char_p, ctypes.c_char_p, c_i32]
+        for fn in (L.bertx_proj_dim, L.bertx_proj_width):
+            fn.restype = c_i32
+            fn.argtypes = [vp]
+        L.bertx_tokenize_colbert.restype = c_i32
+        L.bertx_tokenize_colbert.argtypes = [vp, ctypes.c_char_p, c_i32, c_i32, vp, vp, c_i32p]
+        L.bertx_forward_project_device.restype = c_i32
+        L.bertx_forward_project_device.argtypes = [vp, c_i32, vp, vp, vp, c_i32, c_i32, c_i32, vp, c_i32, vp, vp]
+        L.bertx_forward_project.restype = c_i32
+        L.bertx_forward_project.argtypes = [vp, c_i32, ctypes.POINTER(c_i32p), c_i32p, ctypes.POINTER(c_f32p)]
+        L.bertx_mvindex_add_texts_colbert.restype = c_i32
+        L.bertx_mvindex_add_texts_colbert.argtypes = [vp, vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p), c_i32]
+        L.bertx_mvindex_score_text_colbert.restype = c_i32
+        L.bertx_mvindex_score_text_colbert.argtypes = [vp, vp, ctypes.c_char_p, c_i32, vp, c_i32, vp]
+        L.bertx_test_project.restype = c_i32
+        L.bertx_test_project.argtypes = [c_i32, vp, vp, vp, vp, c_i32, c_i32, vp, c_i32, vp, c_i32, vp, c_i32]
+        L.bertx_bench_project.restype = c_i32
+        L.bertx_bench_project.argtypes = [c_i32] * 4 + [c_f32p]
+    except AttributeError:
+        pass
     L.bertx_bench_gemm.restype = c_i32
     L.bertx_bench_gemm.argtypes = [c_i32] * 7 + [c_f32p]
     L.bertx_bench_attention.restype = c_i32
@@ -315,23 +337,52 @@ class BertModel:
         """Whether CLS pooling runs the last layer on the sentences' first rows only (default on)."""
         self.lib.bertx_set_cls_pruning(self.ctx, 1 if on else 0)
 
-    def forward_tokens(self, ids_list):
-        """Per-token final hidden states (un-normalised): a list of [len][n_embd] f32 arrays."""
+    def _forward_rows(self, fn, name, ids_list, width):
         n = len(ids_list)
         lens = np.fromiter((len(x) for x in ids_list), np.int32, n)
         flat = (np.concatenate(ids_list) if n else np.zeros(0)).astype(np.int32, copy=False)
         flat = np.ascontiguousarray(flat)
-        out = np.zeros((int(lens.sum()), self.n_embd), np.float32)
+        out = np.zeros((int(lens.sum()), width), np.float32)
         offs = np.zeros(n, np.uintp)
         if n > 1:
             np.cumsum(lens[:-1], out=offs[1:])
         tp = (flat.ctypes.data + 4 * offs).astype(np.uintp)
         op = (out.ctypes.data + out.strides[0] * offs).astype(np.uintp)
-        rc = self.lib.bertx_forward_tokens(self.ctx, n, tp.ctypes.data_as(ctypes.POINTER(c_i32p)), _as_i32p(lens),
-                                           op.ctypes.data_as(ctypes.POINTER(c_f32p)))
+        rc = fn(self.ctx, n, tp.ctypes.data_as(ctypes.POINTER(c_i32p)), _as_i32p(lens),
+                op.ctypes.data_as(ctypes.POINTER(c_f32p)))
         if rc != 0:
-            raise RuntimeError("bertx_forward_tokens failed (%d)" % rc)
+            raise RuntimeError("%s failed (%d)" % (name, rc))
         return [out[int(o):int(o) + int(l)] for o, l in zip(offs, lens)]
+
+    def forward_tokens(self, ids_list):
+        """Per-token final hidden states (un-normalised): a list of [len][n_embd] f32 arrays."""
+        return self._forward_rows(self.lib.bertx_forward_tokens, "bertx_forward_tokens", ids_list, self.n_embd)
+
+    # -- ColBERT checkpoints: files with a linear.weight record --
+    @property
+    def proj_dim(self):
+        """Rows of the file's ColBERT projection, 0 for a file without one."""
+        return int(self.lib.bertx_proj_dim(self.ctx))
+
+    @property
+    def proj_width(self):
+        """Width of every projected row, 64 ceil(proj_dim / 64): a legal BertTokenIndex width."""
+        return int(self.lib.bertx_proj_width(self.ctx))
+
+    def tokenize_colbert(self, text, kind, maxlen):
+        """(ids, keep) of a query ("query" / 0: [CLS] [Q] pieces [SEP] and [MASK] up to maxlen) or a
+        document ("doc" / 1: [CLS] [D] pieces [SEP], keep 0 on punctuation tokens)."""
+        kind = {"query": 0, "doc": 1}.get(kind, kind)
+        ids, keep, n = np.zeros(max(maxlen, 1), np.int32), np.zeros(max(maxlen, 1), np.int32), c_i32(0)
+        rc = self.lib.bertx_tokenize_colbert(self.ctx, self._bytes(text), kind, maxlen, ids.ctypes.data, keep.ctypes.data,
+                                             ctypes.byref(n))
+        if rc != 0:
+            raise ValueError("bertx_tokenize_colbert failed (%d)" % rc)
+        return ids[:n.value].copy(), keep[:n.value].copy()
+
+    def forward_project(self, ids_list):
+        """Per-token unit-length projected rows: a list of [len][proj_width] f32 arrays."""
+        return self._forward_rows(self.lib.bertx_forward_project, "bertx_forward_project", ids_list, self.proj_width)
 
     def encode(self, sentences, batch_size=16):
         input_is_string = isinstance(sentences, str)
@@ -650,12 +701,18 @@ class BertTokenIndex:
             raise RuntimeError("bertx_mvindex_add failed (%d)" % rc)
         return rc
 
-    def add_texts(self, texts):
-        """One document per text: its per-token final hidden states; returns the first new id."""
-        rc = self.lib.bertx_mvindex_add_texts(self.mv, self.model.ctx, self.model.N_THREADS, len(texts),
-                                              BertIndex._texts(texts))
+    def add_texts(self, texts, colbert=None):
+        """One document per text: its per-token final hidden states; returns the first new id.
+        colbert=doc_maxlen (a model with a projection record, a store of its proj_width): the
+        projected rows of the text as a ColBERT document, punctuation rows dropped."""
+        if colbert is not None:
+            rc = self.lib.bertx_mvindex_add_texts_colbert(self.mv, self.model.ctx, self.model.N_THREADS, len(texts),
+                                                          BertIndex._texts(texts), colbert)
+        else:
+            rc = self.lib.bertx_mvindex_add_texts(self.mv, self.model.ctx, self.model.N_THREADS, len(texts),
+                                                  BertIndex._texts(texts))
         if rc < 0:
-            raise RuntimeError("bertx_mvindex_add_texts failed (%d)" % rc)
+            raise RuntimeError("bertx_mvindex_add_texts%s failed (%d)" % ("_colbert" if colbert is not None else "", rc))
         return rc
 
     def doc_len(self, i):
@@ -688,15 +745,20 @@ class BertTokenIndex:
             raise RuntimeError("bertx_mvindex_score failed (%d)" % rc)
         return out
 
-    def score_text(self, query, ids=None):
+    def score_text(self, query, ids=None, colbert=None):
+        """colbert=query_maxlen (at most 64): the query as a ColBERT query, [MASK]-augmented."""
         ids = self._ids(ids)
         n, out = self._out(ids)
         if n == 0:
             return out
-        rc = self.lib.bertx_mvindex_score_text(self.mv, self.model.ctx, BertModel._bytes(query),
-                                               None if ids is None else ids.ctypes.data, n, out.ctypes.data)
+        ip = None if ids is None else ids.ctypes.data
+        if colbert is not None:
+            rc = self.lib.bertx_mvindex_score_text_colbert(self.mv, self.model.ctx, BertModel._bytes(query), colbert, ip, n,
+                                                           out.ctypes.data)
+        else:
+            rc = self.lib.bertx_mvindex_score_text(self.mv, self.model.ctx, BertModel._bytes(query), ip, n, out.ctypes.data)
         if rc != 0:
-            raise RuntimeError("bertx_mvindex_score_text failed (%d)" % rc)
+            raise RuntimeError("bertx_mvindex_score_text%s failed (%d)" % ("_colbert" if colbert is not None else "", rc))
         return out
 
     def rerank(self, query, ids, top_k=None):
@@ -765,6 +827,20 @@ def append_head(src, dst, tensors):
         f.write(raw)
         for name, _ in HEAD_NAMES:
             _write_tensor(f, name, tensors[name], ftype)
+    return dst
+
+
+def append_projection(src, dst, W):
+    """Copy the f32 / f16 model file src to dst followed by the ColBERT projection record
+    linear.weight from W [dim][n_embd] (dim % 32 == 0, 32 .. 256; no bias); quantize the result
+    with bertx_quantize_file for the q formats."""
+    with open(src, "rb") as f:
+        raw = f.read()
+    ftype = struct.unpack_from("<i", raw, 4 + 6 * 4)[0]
+    assert ftype in (0, 1), "append_projection needs an f32 or f16 file"
+    with open(dst, "wb") as f:
+        f.write(raw)
+        _write_tensor(f, "linear.weight", np.asarray(W, np.float32), ftype)
     return dst
 
 

@@ -87,6 +87,7 @@ struct bert_ctx {
     int act_mode = 0;   // the activation mode the context runs (bertx_activation_mode)
     int pool = 0;       // BERTX_POOL_MEAN / BERTX_POOL_CLS (bertx_set_pooling), mirrored on every replica
     int n_labels = 0;   // logits per sentence of the file's classification head; 0: none (bertx_n_labels)
+    int proj_dim = 0;   // rows of the file's ColBERT projection; 0: none (bertx_proj_dim)
     // routing state of run_forward: the cost of the work routed to each replica and
     // not yet finished, and the rotation that breaks ties between equal loads
     std::mutex route_mu;
@@ -396,6 +397,7 @@ static bert_ctx *load_context(const char *fname, int act_mode)
     ctx->vocab.build(m.vocab);
     ctx->act_mode = emb::act_mode_effective(m.hp.ftype, act_mode);
     ctx->n_labels = m.n_labels;
+    ctx->proj_dim = m.proj_dim;
     if (act_mode == 1 && ctx->act_mode == 0)
         emb::infof("bert_load_from_file: q8 activations asked for a file of ftype %d: the reference has no q8 "
                    "arithmetic for f16 / f32 files, running the default mode\n", m.hp.ftype);
@@ -663,10 +665,15 @@ int32_t bertx_forward_tokens_device(struct bert_ctx *ctx, int32_t slot, const in
                      true);
 }
 
-int32_t bertx_forward_tokens(struct bert_ctx *ctx, int32_t n, bert_vocab_id **batch_tokens, int32_t *n_tokens,
-                             float **out)
+// The per-token host forms: every token's final-LayerNorm row, or (proj) its projection.
+static int32_t forward_rows(struct bert_ctx *ctx, int32_t n, bert_vocab_id **batch_tokens, int32_t *n_tokens,
+                            float **out, bool proj)
 {
     if (!ctx || n < 0 || (n > 0 && (!batch_tokens || !n_tokens || !out))) return -1;
+    if (proj && ctx->proj_dim <= 0) {
+        emb::errorf("libbert: this model file has no projection (linear.weight)\n");
+        return -6;
+    }
     if (ctx->devices.empty()) {
         emb::errorf("libbert: no HIP device in this context (BERT_HOST_ONLY); forward unavailable\n");
         return -1;
@@ -704,7 +711,7 @@ int32_t bertx_forward_tokens(struct bert_ctx *ctx, int32_t n, bert_vocab_id **ba
                 tp.push_back(batch_tokens[i]); lp.push_back(n_tokens[i]); op.push_back(out[i]);
                 tok += n_tokens[i++];
             }
-            rc = D.forward_host(tp.data(), lp.data(), (int)tp.size(), op.data(), true);
+            rc = D.forward_host(tp.data(), lp.data(), (int)tp.size(), op.data(), true, nullptr, false, proj);
         }
     } catch (...) {
         rc = -1;
@@ -716,6 +723,58 @@ int32_t bertx_forward_tokens(struct bert_ctx *ctx, int32_t n, bert_vocab_id **ba
     }
     if (rc != 0) emb::errorf("libbert: forward failed (%d)\n", rc);
     return rc;
+}
+
+int32_t bertx_forward_tokens(struct bert_ctx *ctx, int32_t n, bert_vocab_id **batch_tokens, int32_t *n_tokens,
+                             float **out)
+{
+    return forward_rows(ctx, n, batch_tokens, n_tokens, out, false);
+}
+
+int32_t bertx_forward_project(struct bert_ctx *ctx, int32_t n, bert_vocab_id **batch_tokens, int32_t *n_tokens,
+                              float **out)
+{
+    return forward_rows(ctx, n, batch_tokens, n_tokens, out, true);
+}
+
+int32_t bertx_proj_dim(struct bert_ctx *ctx) { return ctx ? ctx->proj_dim : 0; }
+int32_t bertx_proj_width(struct bert_ctx *ctx) { return ctx ? emb::proj_width_of(ctx->proj_dim) : 0; }
+
+int32_t bertx_forward_project_device(struct bert_ctx *ctx, int32_t slot, const int32_t *d_ids, const int32_t *d_types,
+                                     const int32_t *d_cu, int32_t n_seqs, int32_t max_len, int32_t total_tokens,
+                                     const int32_t *d_rows, int32_t n_rows, float *d_out, void *stream)
+{
+    if (!ctx || slot < 0 || slot >= (int32_t)ctx->devices.size() || (d_rows && n_rows < 0)) return -1;
+    if (ctx->proj_dim <= 0) return -6;
+    if (max_len > ctx->hp.n_max_tokens || max_len <= 0) return -4;
+    Device &D = *ctx->devices[(size_t)slot];
+    std::lock_guard<std::mutex> lk(D.mutex());
+    emb::DeviceGuard g(D.ordinal());
+    return D.forward_ex(d_ids, d_types, d_cu, n_seqs, max_len, total_tokens, Device::KIND_PROJ, d_out,
+                        stream ? (hipStream_t)stream : D.stream(), -1.0, d_rows, n_rows);
+}
+
+int32_t bertx_tokenize_colbert(struct bert_ctx *ctx, const char *text, int32_t kind, int32_t maxlen, bert_vocab_id *ids,
+                               int32_t *keep, int32_t *n_tokens)
+{
+    if (!ctx || !text || !ids || !keep || !n_tokens || (kind != 0 && kind != 1)) return -1;
+    if (maxlen < 4 || maxlen > ctx->hp.n_max_tokens) return -1;
+    try {
+        thread_local std::vector<int32_t> p;
+        ctx->vocab.pieces(text, p);
+        const int32_t t = ctx->vocab.colbert_layout(p.data(), (int32_t)p.size(), kind, maxlen, ids, keep);
+        if (t < 0) return -1;
+        *n_tokens = t;
+        return 0;
+    } catch (...) {
+        emb::errorf("libbert: tokenization failed\n");
+        return -1;
+    }
+}
+
+int32_t bertx_convert_hf_colbert(const char *dir_model, const char *fname_out, int32_t ftype)
+{
+    return emb::convert_hf_dir(dir_model, fname_out, ftype, false, true);
 }
 
 void bertx_set_profiling(struct bert_ctx *ctx, int32_t on)
@@ -791,8 +850,13 @@ int32_t bertx_forward_device_ex(struct bert_ctx *ctx, int32_t slot, const int32_
                                 int32_t out_kind, float *d_out, void *stream)
 {
     if (slot < 0 || slot >= (int32_t)ctx->devices.size()) return -1;
-    if (out_kind != BERTX_OUT_POOLED && out_kind != BERTX_OUT_TOKENS && out_kind != BERTX_OUT_LOGITS) return -1;
+    if (out_kind != BERTX_OUT_POOLED && out_kind != BERTX_OUT_TOKENS && out_kind != BERTX_OUT_LOGITS &&
+        out_kind != BERTX_OUT_PROJ)
+        return -1;
     if (out_kind == BERTX_OUT_LOGITS && ctx->n_labels <= 0) return -6;
+    // (a file without the projection record has no fourth output kind: -1 as before the
+    // record existed; the entries that exist only for the projection answer -6)
+    if (out_kind == BERTX_OUT_PROJ && ctx->proj_dim <= 0) return -1;
     if (max_len > ctx->hp.n_max_tokens || max_len <= 0) return -4;
     Device &D = *ctx->devices[(size_t)slot];
     std::lock_guard<std::mutex> lk(D.mutex());

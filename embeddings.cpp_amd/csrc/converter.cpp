@@ -283,7 +283,7 @@ template <typename T> void put(std::string &o, const T &v) { o.append((const cha
 
 }  // namespace
 
-int convert_hf_dir(const std::string &dir, const std::string &fname_out, int ftype, bool head)
+int convert_hf_dir(const std::string &dir, const std::string &fname_out, int ftype, bool head, bool colbert)
 {
     if (ftype < 0 || ftype > 1) {
         errorf("Invalid ftype: %d\n", ftype);
@@ -426,6 +426,48 @@ int convert_hf_dir(const std::string &dir, const std::string &fname_out, int fty
         rec(need[1], pb, 1, d, 1, false);
         rec(need[2], cw, 2, d, nl, false);   // f32 in every ftype, 2-D also for one label
         rec(need[3], cb, 1, nl, 1, false);
+    }
+    if (colbert) {
+        // the projection record behind everything else: HF_ColBERT's un-prefixed linear
+        // [dim][hidden], which has no bias
+        const int64_t d = hp[2];
+        const auto it = raw.find("linear.weight");
+        if (it == raw.end()) {
+            errorf("convert: --colbert: checkpoint lacks tensor 'linear.weight' (not an HF_ColBERT checkpoint)\n");
+            return 1;
+        }
+        if (raw.count("linear.bias")) {
+            errorf("convert: --colbert: checkpoint has a 'linear.bias'; ColBERT's projection has none and the model "
+                   "file has no record for one\n");
+            return 1;
+        }
+        const StTensor &w = it->second;
+        const int64_t dim = w.shape.size() == 2 ? w.shape[0] : 0;
+        if (w.shape.size() != 2 || w.shape[1] != d || (int64_t)w.data.size() != dim * d || dim % 32 != 0 ||
+            dim < kProjMinDim || dim > kProjMaxDim) {
+            errorf("convert: --colbert: linear.weight does not fit [dim][%d] with dim a multiple of 32 in %d .. %d\n",
+                   (int)d, kProjMinDim, kProjMaxDim);
+            return 1;
+        }
+        const char *n = "linear.weight";
+        put(o, (int32_t)2);
+        put(o, (int32_t)std::strlen(n));
+        put(o, (int32_t)(ftype == 1 ? 1 : 0));
+        put(o, (int32_t)d);
+        put(o, (int32_t)dim);
+        o += n;
+        if (ftype == 1)
+            for (float v : w.data) put(o, f32_to_f16(v));
+        else
+            o.append((const char *)w.data.data(), w.data.size() * 4);
+        // ColBERT's own settings file, where the checkpoint has one
+        JVal meta;
+        if (read_file(dir + "/artifact.metadata", s) && parse_json(s, meta)) {
+            const JVal *a = meta.get("attend_to_mask_tokens");
+            if (a && a->kind == JVal::BOOL && !a->b)
+                infof("convert: --colbert: this checkpoint was trained with attend_to_mask_tokens = false; this "
+                      "library's query [MASK] rows are ordinary attention keys\n");
+        }
     }
     FILE *f = std::fopen(fname_out.c_str(), "wb");
     if (!f) {

@@ -34,6 +34,18 @@ ModelImage::~ModelImage()
     if (pinned_) (void)hipHostFree(pinned_);
 }
 
+void build_proj_image(const float *W, int dim, int d, std::vector<uint8_t> &bytes)
+{
+    const int width = proj_width_of(dim), NT = width / 16;
+    bytes.assign((size_t)width * d * 2, 0);   // (f16 +0: the padding rows)
+    uint16_t *o = (uint16_t *)bytes.data();
+    for (int j = 0; j < dim; ++j)
+        for (int k = 0; k < d; ++k) {
+            const int kb = k / 32, g = (k % 32) / 8, e = k % 8, t = j / 16, f = j % 16;
+            o[(((size_t)kb * NT + t) * 64 + 16 * g + f) * 8 + e] = f32_to_f16(W[(size_t)j * d + k]);
+        }
+}
+
 bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bool pin, int act_mode)
 {
     try {
@@ -117,6 +129,17 @@ bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bo
             img.head_bp = vec(m.pool_b);
             img.head_wc = vec(m.cls_w);
             img.head_bc = vec(m.cls_b);
+        }
+        // the projection, one f16 image for every chain: the library's own dequantized rows
+        if (m.proj_dim > 0) {
+            std::vector<float> w32((size_t)m.proj_dim * d);
+            for (int r = 0; r < m.proj_dim; ++r)
+                dequant_row(m.proj_w.fmt, m.proj_w.bytes.data() + fmt_row_bytes(m.proj_w.fmt, d) * r,
+                            w32.data() + (size_t)r * d, d);
+            Piece p;
+            build_proj_image(w32.data(), m.proj_dim, d, p.bytes);
+            img.proj_dim = m.proj_dim;
+            img.proj = add(std::move(p));
         }
         img.layers.assign((size_t)hp.n_layer, ModelImage::Layer());
         for (int l = 0; l < hp.n_layer; ++l) {
@@ -298,6 +321,8 @@ void Device::bind(const ModelImage &img)
     n_labels_ = img.n_labels;
     head_wp_ = (const float *)P(img.head_wp); head_bp_ = (const float *)P(img.head_bp);
     head_wc_ = (const float *)P(img.head_wc); head_bc_ = (const float *)P(img.head_bc);
+    proj_dim_ = img.proj_dim;
+    proj_w_ = P(img.proj);
     auto mk_lin = [&](const ModelImage::Lin &x) {
         DevWeight w;
         w.fmt = wfmt_ == FMT_F32 ? FMT_F16 : wfmt_; w.N = x.N; w.K = x.K;

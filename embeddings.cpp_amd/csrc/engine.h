@@ -91,6 +91,9 @@ struct ModelImage {
     // f32 [d][d], its bias, the classifier rows f32 [n_labels][d] and bias
     size_t head_wp = kNone, head_bp = kNone, head_wc = kNone, head_bc = kNone;
     int n_labels = 0;
+    // the ColBERT projection (files that carry one): build_proj_image of the dequantized rows
+    size_t proj = kNone;
+    int proj_dim = 0;
     std::vector<Layer> layers;
     // piece i: bytes [off[i], off[i] + len[i]) of the image (len 0: absent plane)
     std::vector<size_t> off, len;
@@ -116,6 +119,11 @@ private:
 // image carries the raw QKV / FFN-up biases and the era tables, as for f32 files,
 // and no LN-fold constants.
 bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bool pin, int act_mode = 0);
+// The projector's weight image (project.hip, kernels.h launch_project): W f32 [dim][d]
+// rounded to f16, nearest even, zero-padded to width = 64 ceil(dim / 64) rows, in the
+// SEARCH_F16 block order: block (kb, t) of 16 features x 32 k at (kb * width / 16 + t)
+// KiB, lane 16g + f = feature 16t + f, elements 32kb + 8g .. + 7.
+void build_proj_image(const float *W, int dim, int d, std::vector<uint8_t> &bytes);
 // The activation mode a file of format `ftype` runs when `act_mode` is asked for:
 // 1 only for q4_0 / q4_1 / q8_0 (f16 and f32 files have no q8 arithmetic in the reference).
 inline int act_mode_effective(int ftype, int act_mode)
@@ -164,18 +172,26 @@ public:
     // for all 0.  KIND_LOGITS: d_out is float[n_seqs][n_labels], the raw logits of the
     // file's classification head on each sentence's [CLS] row; -6 without a head.  The
     // f16 chain runs the last layer on the compact rows when CLS pruning is on.
-    enum OutKind : int { KIND_POOLED = 0, KIND_TOKENS = 1, KIND_LOGITS = 2 };
+    // KIND_PROJ: d_out is float[n_rows][proj_width], row i the unit-length ColBERT
+    // projection of token d_rows[i] (d_rows int32 [n_rows] on this GPU, every value in
+    // [0, total_tokens), trusted), or with d_rows null float[total_tokens][proj_width],
+    // every token in order; -6 on a file without the record.  Never pruned.
+    enum OutKind : int { KIND_POOLED = 0, KIND_TOKENS = 1, KIND_LOGITS = 2, KIND_PROJ = 3 };
     int forward_ex(const int32_t *d_ids, const int32_t *d_types, const int32_t *d_cu, int n_seqs, int max_len,
-                   int total_tokens, int out_kind, float *d_out, hipStream_t s, double len2_sum = -1.0);
+                   int total_tokens, int out_kind, float *d_out, hipStream_t s, double len2_sum = -1.0,
+                   const int32_t *d_rows = nullptr, int n_rows = 0);
     int n_labels() const { return n_labels_; }
+    int proj_dim() const { return proj_dim_; }
+    int proj_width() const { return proj_width_of(proj_dim_); }
 
     // Host-driven forward: packs tokens, H2D, forward, D2H, synchronous.
     // tokens[i] has lens[i] ids; out[i] receives n_embd floats, or with tok_out
     // lens[i] x n_embd floats (the per-token output).  types (or null: all 0): the
     // token type ids, types[i] beside tokens[i].  logits: out[i] receives the
-    // n_labels logits of sentence i instead.
+    // n_labels logits of sentence i instead.  proj (with tok_out): out[i] receives
+    // lens[i] x proj_width floats, the projected rows (KIND_PROJ).
     int forward_host(const int32_t *const *tokens, const int32_t *lens, int n, float *const *out, bool tok_out = false,
-                     const int32_t *const *types = nullptr, bool logits = false);
+                     const int32_t *const *types = nullptr, bool logits = false, bool proj = false);
 
     // Pooling of the sentence embeddings (bert_hip.h): BERTX_POOL_MEAN / BERTX_POOL_CLS,
     // and whether CLS pooling runs the last layer on the sentences' first rows only
@@ -211,14 +227,17 @@ private:
         int n_seqs, max_len, T;
         int mode;   // OutMode: a graph of one pooling mode is never replayed for another
         const void *types;   // the token types pointer (null: all 0) is baked into the embedding launch
+        const void *rows;    // OUT_PROJ: the row map (null: every token) and its length
+        int n_rows;
         bool operator==(const GraphKey &o) const
         {
             return ids == o.ids && cu == o.cu && out == o.out && s == o.s && n_seqs == o.n_seqs &&
-                   max_len == o.max_len && T == o.T && mode == o.mode && types == o.types;
+                   max_len == o.max_len && T == o.T && mode == o.mode && types == o.types && rows == o.rows &&
+                   n_rows == o.n_rows;
         }
     };
     // what the launch sequence ends in (and, for CLS and the logits, how its last layer runs)
-    enum OutMode : int { OUT_MEAN = 0, OUT_CLS, OUT_CLS_PRUNED, OUT_TOKENS, OUT_LOGITS, OUT_LOGITS_PRUNED };
+    enum OutMode : int { OUT_MEAN = 0, OUT_CLS, OUT_CLS_PRUNED, OUT_TOKENS, OUT_LOGITS, OUT_LOGITS_PRUNED, OUT_PROJ };
     bool pruned_last() const { return out_mode_ == OUT_CLS_PRUNED || out_mode_ == OUT_LOGITS_PRUNED; }
     struct GraphEntry { GraphKey key; hipGraphExec_t exec; };
     int forward_ordered(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out,
@@ -275,6 +294,8 @@ private:
     // the classification head, f32 (null / 0: the file has none)
     const float *head_wp_ = nullptr, *head_bp_ = nullptr, *head_wc_ = nullptr, *head_bc_ = nullptr;
     int n_labels_ = 0;
+    const void *proj_w_ = nullptr;   // the projector's weight image (null / 0: the file has none)
+    int proj_dim_ = 0;
 
     // workspace
     int64_t cap_tokens_ = 0, cap_seqs_ = 0, cap_pool_ = 0;   // cap_pool_: pool partial rows (seqs x chunks)
@@ -298,12 +319,14 @@ private:
     uint16_t *zc_ = nullptr, *attc_ = nullptr, *ffnc_ = nullptr;
     float2 *stc_ = nullptr, *partc_ = nullptr;
     int64_t rows_c_ = 0;            // compact workspace rows (partc_ stride)
-    float *tok_out_ = nullptr;      // per-token output staging of forward_host [cap_tok_out_][d], grown on demand
+    float *tok_out_ = nullptr;      // per-token output staging of forward_host [cap_tok_out_][max(d, proj_width)], grown on demand
     int64_t cap_tok_out_ = 0;
     int pool_ = 0;                  // BERTX_POOL_MEAN / BERTX_POOL_CLS
     bool prune_ = true;
     int out_mode_ = OUT_MEAN;       // of the forward being launched
     const int32_t *types_ = nullptr;   // ... and its token types (null: all 0)
+    const int32_t *map_ = nullptr;     // ... and, OUT_PROJ, its row map (null: every token) of n_map_ rows
+    int n_map_ = 0;
     int32_t *h_ids_ = nullptr, *h_cu_ = nullptr, *h_types_ = nullptr;   // pinned staging
     float *h_out_ = nullptr;
 

@@ -77,12 +77,18 @@ struct Device::Launcher {
 };
 
 int Device::forward_ex(const int32_t *d_ids, const int32_t *d_types, const int32_t *d_cu, int n_seqs, int max_len, int T,
-                       int out_kind, float *d_out, hipStream_t s, double len2_sum)
+                       int out_kind, float *d_out, hipStream_t s, double len2_sum, const int32_t *d_rows, int n_rows)
 {
-    if (out_kind != KIND_POOLED && out_kind != KIND_TOKENS && out_kind != KIND_LOGITS) return -1;
+    if (out_kind != KIND_POOLED && out_kind != KIND_TOKENS && out_kind != KIND_LOGITS && out_kind != KIND_PROJ) return -1;
     if (out_kind == KIND_LOGITS && n_labels_ <= 0) return -6;
+    if (out_kind == KIND_PROJ && proj_dim_ <= 0) return -6;
+    const bool mapped = out_kind == KIND_PROJ && d_rows != nullptr;
+    if (mapped && n_rows < 0) return -1;
+    map_ = mapped ? d_rows : nullptr;
+    n_map_ = mapped ? n_rows : 0;
     const bool can_prune = prune_ && !f32_ && !q8_;
     out_mode_ = out_kind == KIND_TOKENS   ? OUT_TOKENS
+                : out_kind == KIND_PROJ   ? OUT_PROJ
                 : out_kind == KIND_LOGITS ? (can_prune ? OUT_LOGITS_PRUNED : OUT_LOGITS)
                 : pool_ != 1              ? OUT_MEAN
                                           : can_prune ? OUT_CLS_PRUNED : OUT_CLS;
@@ -107,7 +113,7 @@ int Device::forward_ordered(const int32_t *d_ids, const int32_t *d_cu, int n_seq
     static const bool graphs_env = [] { const char *e = std::getenv("BERT_GRAPHS"); return !(e && *e == '0'); }();
     if (profiling_ || check || !use_graphs_ || !graphs_env || s == nullptr)
         return launch_all(d_ids, d_cu, n_seqs, max_len, T, d_out, s, check);
-    const GraphKey key{d_ids, d_cu, d_out, s, n_seqs, max_len, T, out_mode_, types_};
+    const GraphKey key{d_ids, d_cu, d_out, s, n_seqs, max_len, T, out_mode_, types_, map_, n_map_};
     for (auto &g : graphs_)
         if (g.key == key) return hipGraphLaunch(g.exec, s) == hipSuccess ? 0 : -1;
     // a shape seen for the first time runs eagerly (one-off batches never pay
@@ -219,6 +225,16 @@ int Device::chain_f16(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, 
             else launch_head_gather(z_, st_, gz, bz, d_cu, n_seqs, d, head_x_, s);
         }, Out{"head_gather", "", -1, head_x_, (size_t)n_seqs * d, 0});
         return head(run, n_seqs, d_out);
+    }
+    if (out_mode_ == OUT_PROJ) {
+        // the projector reads z and the statistics as the token output does and writes
+        // proj_width floats per mapped row (a row map of 0 rows: nothing to do)
+        const int n_out = map_ ? n_map_ : T, width = proj_width();
+        if (n_out == 0) return 0;
+        const bool ok = run.run(K_POOL_L2, (double)n_out * (d * 2.0 + 8.0 + width * 4.0), [&] {
+            return launch_project(z_, st_, gz, bz, nullptr, d, proj_w_, proj_dim_, map_, n_out, d_out, s);
+        }, Out{"project", "", -1, d_out, (size_t)n_out * width, 0});
+        return ok ? 0 : -1;
     }
     const Out out{"pool_l2", "", -1, d_out, (out_mode_ == OUT_TOKENS ? (size_t)T : (size_t)n_seqs) * d, 0};
     if (out_mode_ == OUT_MEAN) {
@@ -359,6 +375,14 @@ int Device::chain_32(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, i
                 Out{"head_gather", "", -1, head_x_, nd, 0});
         return head(run, n_seqs, d_out);
     }
+    if (out_mode_ == OUT_PROJ) {
+        const int n_out = map_ ? n_map_ : T, width = proj_width();
+        if (n_out == 0) return 0;
+        ok = run.run(K_POOL_L2, (double)n_out * (d * 4.0 + width * 4.0), [&] {
+            return launch_project(nullptr, nullptr, nullptr, nullptr, x32_, d, proj_w_, proj_dim_, map_, n_out, d_out, s);
+        }, Out{"project", "", -1, d_out, (size_t)n_out * width, 0});
+        return ok ? 0 : -1;
+    }
     if (out_mode_ == OUT_MEAN)
         ok = run.run(K_POOL_L2, t * d * 4.0 + (double)n_seqs * d * 4.0,
                      [&] { launch_f32_pool(x32_, d_cu, n_seqs, d, d_out, s, exact); }, Out{"pool_l2", "", -1, d_out, nd, 0});
@@ -372,10 +396,11 @@ int Device::chain_32(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, i
 }
 
 int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int n, float *const *out, bool tok_out,
-                         const int32_t *const *types, bool logits)
+                         const int32_t *const *types, bool logits, bool proj)
 {
     if (!ok_) return -3;
     if (logits && n_labels_ <= 0) return -6;
+    if (proj && proj_dim_ <= 0) return -6;
     if (n <= 0) return 0;
     int64_t T = 0;
     int max_len = 0;
@@ -411,14 +436,16 @@ int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int 
             cap_tok_out_ = 0;
             drop_graphs();   // captured token forwards hold the old pointer
             const int64_t cap = (int64_t)align_up((size_t)T, 4096);
-            HIP_RC(hipMalloc((void **)&tok_out_, sizeof(float) * d * (size_t)cap));
+            HIP_RC(hipMalloc((void **)&tok_out_, sizeof(float) * std::max(d, (size_t)proj_width()) * (size_t)cap));
             cap_tok_out_ = cap;
         }
-        const int rc = forward_ex(d_ids_, dty, d_cu_, n, max_len, (int)T, KIND_TOKENS, tok_out_, stream_, len2);
+        const size_t tw = proj ? (size_t)proj_width() : d;   // floats per row of this output
+        const int rc = forward_ex(d_ids_, dty, d_cu_, n, max_len, (int)T, proj ? KIND_PROJ : KIND_TOKENS, tok_out_, stream_,
+                                  len2);
         if (rc != 0) return rc;
         HIP_RC(hipStreamSynchronize(stream_));
         for (int i = 0; i < n; ++i)
-            HIP_RC(hipMemcpy(out[i], tok_out_ + d * (size_t)h_cu_[i], sizeof(float) * d * (size_t)lens[i],
+            HIP_RC(hipMemcpy(out[i], tok_out_ + tw * (size_t)h_cu_[i], sizeof(float) * tw * (size_t)lens[i],
                              hipMemcpyDeviceToHost));
         return 0;
     }

@@ -1009,3 +1009,108 @@ extern "C" int32_t bertx_test_attention_cls(const uint16_t *qkv, const int32_t *
     std::memcpy(out, h.data(), (size_t)n_seqs * d * 2);
     return 0;
 }
+
+extern "C" int32_t bertx_test_project(int32_t mode, const void *src, const float *stats, const float *g, const float *b,
+                                      int32_t T, int32_t d, const float *W, int32_t dim, const int32_t *rows,
+                                      int32_t n_out, float *out, int32_t out_rows)
+{
+    using namespace emb;
+    if ((mode != 0 && mode != 1) || !src || (mode == 0 && (!stats || !g || !b)) || !W || !out || T <= 0 ||
+        !hook_width_ok(d) || dim % 32 || dim < kProjMinDim || dim > kProjMaxDim || hip_device_count() == 0)
+        return -1;
+    if (!rows) n_out = T;
+    if (n_out <= 0 || out_rows < n_out) return -1;
+    for (int i = 0; rows && i < n_out; ++i)
+        if (rows[i] < 0 || rows[i] >= T) return -1;
+    constexpr size_t GUARD = 16;   // rows of NaN bits behind the caller's out_rows
+    const size_t width = (size_t)proj_width_of(dim);
+    std::vector<uint8_t> img;
+    build_proj_image(W, dim, d, img);
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const void *dsrc = B.up(src, (size_t)T * d * (mode == 0 ? 2 : 4), 0);
+    const float2 *dst = mode == 0 ? (const float2 *)B.up(stats, (size_t)T * 8, 0) : nullptr;
+    const float *dg = mode == 0 ? (const float *)B.up(g, (size_t)d * 4, 0) : nullptr;
+    const float *db = mode == 0 ? (const float *)B.up(b, (size_t)d * 4, 0) : nullptr;
+    const void *dw = B.up(img.data(), img.size(), 0);
+    const int32_t *dr = rows ? (const int32_t *)B.up(rows, (size_t)n_out * 4, 0) : nullptr;
+    const size_t ob = (size_t)out_rows * width * 4, gb = GUARD * width * 4;
+    float *dout = (float *)B.up(out, ob, ob + gb);
+    if (B.bad) return -1;
+    HIP_RC(hipMemset((char *)dout + ob, 0xff, gb));
+    const int lrc = mode == 0 ? launch_project((const uint16_t *)dsrc, dst, dg, db, nullptr, d, dw, dim, dr, n_out, dout, nullptr)
+                              : launch_project(nullptr, nullptr, nullptr, nullptr, (const float *)dsrc, d, dw, dim, dr, n_out,
+                                               dout, nullptr);
+    if (const int rc = hook_finish()) return rc;
+    if (lrc != 0) return -1;
+    HIP_RC(hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> gd(GUARD * width);
+    HIP_RC(hipMemcpy(gd.data(), (char *)dout + ob, gb, hipMemcpyDeviceToHost));
+    for (const uint32_t v : gd) if (v != 0xffffffffu) return -5;
+    return 0;
+}
+
+// Projector micro-benchmark (bert_hip.h): device 0, no context, the f16-chain form.
+extern "C" int32_t bertx_bench_project(int32_t d, int32_t dim, int32_t T, int32_t iters, float *avg_us)
+{
+    using namespace emb;
+    if (!hook_width_ok(d) || dim % 32 || dim < kProjMinDim || dim > kProjMaxDim || T < 1 || iters < 1 || !avg_us ||
+        hip_device_count() == 0)
+        return -1;
+    try {
+        // hashed operands: z in about [-2, 2), statistics near (0, 1), gamma near 1, W about 1 / sqrt(d)
+        auto h01 = [](uint32_t x) {
+            x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+            return (float)(x >> 8) * (1.0f / 16777216.0f);
+        };
+        const size_t width = (size_t)proj_width_of(dim);
+        std::vector<uint16_t> z((size_t)T * d);
+        for (size_t i = 0; i < z.size(); ++i) z[i] = f32_to_f16(4.0f * h01((uint32_t)i + 1u) - 2.0f);
+        std::vector<float> st((size_t)T * 2), gam((size_t)d), bet((size_t)d), W((size_t)dim * d);
+        for (int t = 0; t < T; ++t) { st[2 * (size_t)t] = 0.1f * h01(77u + (uint32_t)t); st[2 * (size_t)t + 1] = 0.5f + h01(991u + (uint32_t)t); }
+        for (int k = 0; k < d; ++k) { gam[(size_t)k] = 0.75f + 0.5f * h01(5u + (uint32_t)k); bet[(size_t)k] = 0.2f * h01(3001u + (uint32_t)k) - 0.1f; }
+        const float ws = 2.0f / std::sqrt((float)d);
+        for (size_t i = 0; i < W.size(); ++i) W[i] = ws * (h01(0x9e3779b9u + (uint32_t)i) - 0.5f);
+        std::vector<uint8_t> img;
+        build_proj_image(W.data(), dim, d, img);
+        DeviceGuard guard(0);
+        HIP_RC(guard.status());
+        HookBufs B;
+        const uint16_t *dz = (const uint16_t *)B.up(z.data(), z.size() * 2, 0);
+        const float2 *dst = (const float2 *)B.up(st.data(), st.size() * 4, 0);
+        const float *dg = (const float *)B.up(gam.data(), gam.size() * 4, 0), *db = (const float *)B.up(bet.data(), bet.size() * 4, 0);
+        const void *dw = B.up(img.data(), img.size(), 0);
+        float *dout = (float *)B.up(nullptr, 0, (size_t)T * width * 4);
+        if (B.bad) return -1;
+        struct Ev {
+            hipStream_t s = nullptr;
+            hipEvent_t a = nullptr, b = nullptr;
+            ~Ev()
+            {
+                if (s) (void)hipStreamSynchronize(s);
+                if (a) (void)hipEventDestroy(a);
+                if (b) (void)hipEventDestroy(b);
+                if (s) (void)hipStreamDestroy(s);
+            }
+        } E;
+        HIP_RC(hipStreamCreateWithFlags(&E.s, hipStreamNonBlocking));
+        HIP_RC(hipEventCreate(&E.a));
+        HIP_RC(hipEventCreate(&E.b));
+        auto run = [&] { return launch_project(dz, dst, dg, db, nullptr, d, dw, dim, nullptr, T, dout, E.s); };
+        for (int i = 0; i < 3; ++i)
+            if (run() != 0) return -1;
+        HIP_RC(hipEventRecord(E.a, E.s));
+        for (int i = 0; i < iters; ++i)
+            if (run() != 0) return -1;
+        HIP_RC(hipEventRecord(E.b, E.s));
+        HIP_RC(hipEventSynchronize(E.b));
+        float ms = 0.f;
+        HIP_RC(hipEventElapsedTime(&ms, E.a, E.b));
+        *avg_us = ms * 1000.f / (float)iters;
+        return 0;
+    } catch (const std::exception &ex) {
+        emb::errorf("bertx_bench_project: %s\n", ex.what());
+        return -1;
+    }
+}

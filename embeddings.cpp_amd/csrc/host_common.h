@@ -30,6 +30,10 @@ inline size_t fmt_block_bytes(int f)
 }
 
 constexpr int kMaxLabels = 16;  // classifier rows a model file may carry
+// the ColBERT projection a model file may carry: dim % 32 == 0 in kProjMinDim .. kProjMaxDim;
+// its rows leave the library padded with +0 to proj_width = 64 ceil(dim / 64) columns
+constexpr int kProjMinDim = 32, kProjMaxDim = 256;
+inline int proj_width_of(int dim) { return dim > 0 ? (dim + 63) / 64 * 64 : 0; }
 
 // (f32 / f16 rows of any length: the classifier's bias has n_labels elements)
 inline size_t fmt_row_bytes(int f, int64_t k)
@@ -72,6 +76,9 @@ struct HostModel {
     // [d][d] in the header ftype + bias, classifier [n_labels][d] f32 + bias
     HostTensor pool_w, pool_b, cls_w, cls_b;
     int32_t n_labels = 0;           // 0: the file has no head
+    // the optional ColBERT projection linear.weight [dim][d] in the header ftype, no bias
+    HostTensor proj_w;
+    int32_t proj_dim = 0;           // 0: the file has no projection
     size_t total_bytes = 0;
     int n_tensors = 0;
 };
@@ -99,6 +106,10 @@ int quantize_file(const char *in, const char *out, int itype, bool verbose);
 // HF directory (config.json, vocab.txt, model.safetensors) -> model file (converter.cpp);
 // head: followed by the four head records (pooler.dense.*, classifier.*), refused
 // when the checkpoint lacks either
-int convert_hf_dir(const std::string &dir, const std::string &fname_out, int ftype, bool head = false);
+// colbert: followed by the projection record linear.weight (HF_ColBERT checkpoints:
+// encoder tensors bert.*, the projection un-prefixed), refused without it, with a
+// linear.bias or with a shape the loader would refuse
+int convert_hf_dir(const std::string &dir, const std::string &fname_out, int ftype, bool head = false,
+                   bool colbert = false);
 
 }  // namespace emb

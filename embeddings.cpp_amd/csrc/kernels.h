@@ -279,6 +279,20 @@ void launch_head_gather_f32(const float *x32, const int32_t *cu, int32_t n_seqs,
 int launch_head(const float *x, int32_t n_seqs, int32_t d, const float *wp, const float *bp, const float *wc,
                 const float *bc, int32_t n_labels, float *p, float *logits, hipStream_t s);
 
+// ---- the ColBERT projector (project.hip; the arithmetic: bert_hip.h "Projection") ----
+// out f32 [n_out][width], width = 64 ceil(dim / 64): output row i = the unit-length
+// projection of source row d_rows[i] (d_rows int32 [n_out] on the device; null: row i),
+// columns dim .. width - 1 exactly +0.  The source is the final-LayerNorm row, rounded
+// to f16 in registers: either z f16 [>= rows][d] with stats / ln_w / ln_b (the f16
+// chain's stream, the expression of launch_tokens_f32) or x32 f32 [rows][d] (the f32 /
+// q8 chains' final buffer); exactly one of z, x32 is non-null.  wimg: the weight as
+// build_proj_image (engine.h) lays it out.  Only mapped rows are read, only n_out rows
+// are stored.  d % 64 == 0, 64 <= d <= 1024, dim % 32 == 0, 32 <= dim <= 256, n_out >= 1;
+// returns -1 otherwise (nothing launched), -3 when the launch was refused.
+int launch_project(const uint16_t *z, const float2 *stats, const float *ln_w, const float *ln_b, const float *x32,
+                   int32_t d, const void *wimg, int32_t dim, const int32_t *d_rows, int32_t n_out, float *out,
+                   hipStream_t s);
+
 // Diagnostics: *cnt += number of non-finite values in p[0..n) (f32, or f16 if f16).
 void launch_count_nonfinite(const void *p, size_t n, int f16, unsigned *cnt, hipStream_t s);
 

@@ -142,6 +142,8 @@ HostTensor *slot(HostModel &m, const std::string &name, int32_t &e0, int32_t &e1
     if (name == "classifier.bias") { e0 = -1; return &m.cls_b; }
     if (name == "pooler.dense.weight") { vec = false; e0 = d; e1 = d; return &m.pool_w; }
     if (name == "classifier.weight") { vec = false; e0 = d; e1 = -1; return &m.cls_w; }
+    // the optional ColBERT projection; e1 = -1: the row count is the file's (dim)
+    if (name == "linear.weight") { vec = false; e0 = d; e1 = -1; return &m.proj_w; }
     static const std::string pre = "encoder.layer.";
     if (name.compare(0, pre.size(), pre) != 0) return nullptr;
     size_t pos = pre.size(), end = name.find('.', pos);
@@ -228,6 +230,15 @@ bool load_model_file(const char *path, HostModel &m, std::string &err, bool verb
         const bool cls_w = t == &m.cls_w, cls_b = t == &m.cls_b;
         if (cls_w && n_dims == 2 && ne[1] >= 1 && ne[1] <= kMaxLabels) e1 = ne[1];
         if (cls_b && ne[0] >= 1 && ne[0] <= kMaxLabels) e0 = ne[0];
+        if (t == &m.proj_w) {
+            if (n_dims != 2 || ne[0] != e0) { err = "tensor '" + name + "' has wrong shape in model file"; return false; }
+            if (ne[1] % 32 != 0 || ne[1] < kProjMinDim || ne[1] > kProjMaxDim) {
+                err = "tensor '" + name + "' has " + std::to_string(ne[1]) + " rows: the projection's dim must be a "
+                      "multiple of 32 in " + std::to_string(kProjMinDim) + " .. " + std::to_string(kProjMaxDim);
+                return false;
+            }
+            e1 = ne[1];
+        }
         if (ne[0] != e0 || ne[1] != e1) { err = "tensor '" + name + "' has wrong shape in model file"; return false; }
         if (!fmt_valid(fmt)) { err = "unknown ftype " + std::to_string(fmt) + " in model file"; return false; }
         if ((vec || cls_w) && fmt != FMT_F32) { err = "tensor '" + name + "' must be f32"; return false; }
@@ -266,6 +277,10 @@ bool load_model_file(const char *path, HostModel &m, std::string &err, bool verb
         if (m.cls_b.ne0 != m.cls_w.ne1) { err = "classifier.bias does not match classifier.weight"; return false; }
         m.n_labels = m.cls_w.ne1;
         if (verbose) std::printf("bert_load_from_file: n_labels = %d\n", m.n_labels);
+    }
+    if (m.proj_w.present()) {
+        m.proj_dim = m.proj_w.ne1;
+        if (verbose) std::printf("bert_load_from_file: proj_dim = %d\n", m.proj_dim);
     }
     if (verbose)
         std::printf("bert_load_from_file: model size = %8.2f MB / num tensors = %d\n",

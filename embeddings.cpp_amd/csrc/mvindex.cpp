@@ -8,6 +8,7 @@
 
 #include "engine.h"
 #include "hip_check.h"
+#include "task_pool.h"
 
 #include <algorithm>
 #include <cstring>
@@ -220,6 +221,28 @@ struct DevBuf {
     void *p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
+
+// The refusals of the ColBERT text forms: -6 a file without the projection record, -1 a
+// store of another width than the projected rows', then as text_ctx_ok.
+int32_t colbert_ctx_ok(bertx_mvindex *mv, struct bert_ctx *ctx, const char *who, int32_t *slot)
+{
+    if (!mv || !ctx) return -1;
+    if (bertx_proj_dim(ctx) <= 0) {
+        errorf("%s: this model file has no projection (linear.weight)\n", who);
+        return -6;
+    }
+    if (bertx_num_devices(ctx) == 0 || bertx_proj_width(ctx) != mv->w) {
+        errorf("%s: the context projects to rows of width %d, the store holds width %d\n", who, bertx_proj_width(ctx),
+               mv->w);
+        return -1;
+    }
+    *slot = slot_on(ctx, mv->ordinal);
+    if (*slot < 0) {
+        errorf("%s: the context has no replica on the store's device %d\n", who, mv->ordinal);
+        return -1;
+    }
+    return 0;
+}
 
 }  // namespace
 
@@ -549,6 +572,134 @@ int32_t bertx_mvindex_score_text(struct bertx_mvindex *mv, struct bert_ctx *ctx,
         return emb::score_host_ids(*mv, mv->st_q, L, ids, n, out);
     } catch (const std::exception &ex) {
         emb::errorf("bertx_mvindex_score_text: %s\n", ex.what());
+        return -1;
+    }
+}
+
+int32_t bertx_mvindex_add_texts_colbert(struct bertx_mvindex *mv, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                        const char **texts, int32_t doc_maxlen)
+{
+    int32_t slot = -1;
+    if (!texts || n < 1) return -1;
+    if (const int32_t rc = emb::colbert_ctx_ok(mv, ctx, "bertx_mvindex_add_texts_colbert", &slot)) return rc;
+    if (doc_maxlen < 4 || doc_maxlen > bert_n_max_tokens(ctx)) return -1;
+    for (int32_t i = 0; i < n; ++i)
+        if (!texts[i]) return -1;
+    try {
+        const size_t N = (size_t)doc_maxlen;
+        std::vector<int32_t> ids((size_t)n * N), keep((size_t)n * N), lens((size_t)n), kept((size_t)n), rcs((size_t)n, 0);
+        emb::TaskPool::instance().run(((int64_t)n + 7) / 8, n_threads > 0 ? n_threads : 1, [&](int64_t blk) {
+            const int e = (int)std::min<int64_t>(n, 8 * blk + 8);
+            for (int i = (int)(8 * blk); i < e; ++i) {
+                rcs[(size_t)i] = bertx_tokenize_colbert(ctx, texts[i], 1, doc_maxlen, ids.data() + i * N,
+                                                        keep.data() + i * N, &lens[(size_t)i]);
+                int32_t c = 0;
+                for (int32_t t = 0; rcs[(size_t)i] == 0 && t < lens[(size_t)i]; ++t) c += keep[i * N + t];
+                kept[(size_t)i] = c;
+            }
+        });
+        for (int32_t i = 0; i < n; ++i)
+            if (rcs[(size_t)i] != 0) return -1;
+        std::lock_guard<std::mutex> lk(mv->mu);
+        int64_t T = 0, slots = 0;
+        int32_t rc = emb::plan_add(*mv, kept.data(), n, &T, &slots);   // (a document keeps [CLS], [D] and [SEP]: >= 3)
+        if (rc != 0) return rc;
+        DeviceGuard g(mv->ordinal);
+        HIP_RC(g.status());
+        // the chunks of _add_texts; per chunk the kept tokens' packed rows are the row map,
+        // and the projector's device output goes straight into the pack kernel
+        std::vector<int32_t> flat, cu, map;
+        emb::DevBuf d_ids, d_cu, d_map, d_rows;
+        int64_t cap_tok = 0, cap_seq = 0;
+        {
+            emb::Ordered o(*mv, mv->stream);
+            rc = emb::upload_entries(*mv, n, mv->stream);
+            int32_t i = 0;
+            int64_t t0 = 0;
+            while (i < n && rc == 0) {
+                flat.clear();
+                map.clear();
+                cu.assign(1, 0);
+                int max_len = 0;
+                while (i < n && (cu.size() == 1 || ((int64_t)flat.size() + lens[(size_t)i] <= emb::kChunkTokens &&
+                                                    (int)cu.size() - 1 < emb::kChunkSeqs))) {
+                    const int32_t *p = ids.data() + i * N, *kp = keep.data() + i * N;
+                    for (int32_t t = 0; t < lens[(size_t)i]; ++t)
+                        if (kp[t]) map.push_back((int32_t)flat.size() + t);
+                    flat.insert(flat.end(), p, p + lens[(size_t)i]);
+                    cu.push_back((int32_t)flat.size());
+                    max_len = std::max(max_len, (int)lens[(size_t)i]);
+                    ++i;
+                }
+                const int64_t tok = (int64_t)flat.size(), seqs = (int64_t)cu.size() - 1, rows = (int64_t)map.size();
+                if (tok > cap_tok || seqs > cap_seq) {
+                    HIP_RC(hipStreamSynchronize(mv->stream));
+                    for (emb::DevBuf *b : {&d_ids, &d_cu, &d_map, &d_rows})
+                        if (b->p) { (void)hipFree(b->p); b->p = nullptr; }
+                    cap_tok = std::max(tok, cap_tok);
+                    cap_seq = std::max(seqs, cap_seq);
+                    HIP_RC(hipMalloc(&d_ids.p, (size_t)cap_tok * 4));
+                    HIP_RC(hipMalloc(&d_cu.p, (size_t)(cap_seq + 1) * 4));
+                    HIP_RC(hipMalloc(&d_map.p, (size_t)cap_tok * 4));
+                    HIP_RC(hipMalloc(&d_rows.p, (size_t)cap_tok * mv->w * 4));
+                }
+                if (bertx_reserve(ctx, slot, (int32_t)tok, (int32_t)seqs) != 0) { rc = -1; break; }
+                HIP_RC(hipMemcpyAsync(d_ids.p, flat.data(), (size_t)tok * 4, hipMemcpyHostToDevice, mv->stream));
+                HIP_RC(hipMemcpyAsync(d_cu.p, cu.data(), (size_t)(seqs + 1) * 4, hipMemcpyHostToDevice, mv->stream));
+                HIP_RC(hipMemcpyAsync(d_map.p, map.data(), (size_t)rows * 4, hipMemcpyHostToDevice, mv->stream));
+                rc = bertx_forward_project_device(ctx, slot, (const int32_t *)d_ids.p, nullptr, (const int32_t *)d_cu.p,
+                                                  (int32_t)seqs, max_len, (int32_t)tok, (const int32_t *)d_map.p,
+                                                  (int32_t)rows, (float *)d_rows.p, mv->stream);
+                if (rc == 0) rc = emb::pack(*mv, (const float *)d_rows.p, t0, rows, n, mv->stream);
+                // the chunk's host and device buffers are reused by the next one
+                if (rc == 0 && hipStreamSynchronize(mv->stream) != hipSuccess) rc = -1;
+                t0 += rows;
+            }
+        }
+        if (rc != 0) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(mv->stream);
+            emb::errorf("bertx_mvindex_add_texts_colbert: device %d failed while adding (%d)\n", mv->ordinal, rc);
+            return rc < 0 ? rc : -1;
+        }
+        return emb::commit(*mv, n, slots);
+    } catch (const std::exception &ex) {
+        emb::errorf("bertx_mvindex_add_texts_colbert: %s\n", ex.what());
+        return -1;
+    }
+}
+
+int32_t bertx_mvindex_score_text_colbert(struct bertx_mvindex *mv, struct bert_ctx *ctx, const char *query,
+                                         int32_t query_maxlen, const int32_t *ids, int32_t n, float *out)
+{
+    int32_t slot = -1;
+    if (!query || !out || n < 1) return -1;
+    if (const int32_t rc = emb::colbert_ctx_ok(mv, ctx, "bertx_mvindex_score_text_colbert", &slot)) return rc;
+    if (query_maxlen < 4 || query_maxlen > emb::kMaxLq || query_maxlen > bert_n_max_tokens(ctx)) return -1;
+    try {
+        // ids [L] and cu {0, L} in one staging buffer, as _score_text; L = query_maxlen
+        std::vector<int32_t> h((size_t)emb::kMaxLq + 2, 0), keep((size_t)emb::kMaxLq);
+        int32_t L = 0;
+        if (bertx_tokenize_colbert(ctx, query, 0, query_maxlen, h.data(), keep.data(), &L) != 0 || L != query_maxlen)
+            return -1;
+        h[(size_t)emb::kMaxLq] = 0;
+        h[(size_t)emb::kMaxLq + 1] = L;
+        std::lock_guard<std::mutex> lk(mv->mu);
+        DeviceGuard g(mv->ordinal);
+        HIP_RC(g.status());
+        if (bertx_reserve(ctx, slot, L, 1) != 0) return -1;
+        int32_t rc = 0;
+        {
+            emb::Ordered o(*mv, mv->stream);
+            HIP_RC(hipMemcpyAsync(mv->st_tok, h.data(), h.size() * 4, hipMemcpyHostToDevice, mv->stream));
+            HIP_RC(hipStreamSynchronize(mv->stream));   // h is pageable and leaves scope
+            rc = bertx_forward_project_device(ctx, slot, mv->st_tok, nullptr, mv->st_tok + emb::kMaxLq, 1, L, L, nullptr,
+                                              0, mv->st_q, mv->stream);
+        }
+        if (rc != 0) return rc < 0 ? rc : -1;
+        return emb::score_host_ids(*mv, mv->st_q, L, ids, n, out);
+    } catch (const std::exception &ex) {
+        emb::errorf("bertx_mvindex_score_text_colbert: %s\n", ex.what());
         return -1;
     }
 }

@@ -371,4 +371,28 @@ int32_t Vocab::pair_layout(const int32_t *pa, int32_t la, const int32_t *pb, int
     return 0;
 }
 
+bool Vocab::skiplisted(int32_t id) const
+{
+    if (id < 0 || (size_t)id >= tokens_.size() || tokens_[(size_t)id].size() != 1) return false;
+    const char c = tokens_[(size_t)id][0];
+    // Python's string.punctuation: the 32 printable ASCII characters that are neither
+    // alphanumeric nor the space
+    return (c >= '!' && c <= '/') || (c >= ':' && c <= '@') || (c >= '[' && c <= '`') || (c >= '{' && c <= '~');
+}
+
+int32_t Vocab::colbert_layout(const int32_t *p, int32_t lp, int32_t kind, int32_t maxlen, int32_t *ids, int32_t *keep) const
+{
+    if ((kind != 0 && kind != 1) || maxlen < 4) return -1;
+    const int32_t k = std::min(lp, maxlen - 3);
+    int32_t t = 0;
+    ids[t++] = 101;
+    ids[t++] = kind == 0 ? 1 : 2;   // [unused0] = [Q], [unused1] = [D]
+    for (int32_t i = 0; i < k; ++i) ids[t++] = p[i];
+    ids[t++] = 102;
+    if (kind == 0)
+        while (t < maxlen) ids[t++] = 103;   // [MASK] augmentation
+    for (int32_t i = 0; i < t; ++i) keep[i] = kind == 1 && skiplisted(ids[i]) ? 0 : 1;
+    return t;
+}
+
 }  // namespace emb

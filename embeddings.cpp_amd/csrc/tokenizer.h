@@ -35,6 +35,17 @@ public:
     static int32_t pair_layout(const int32_t *pa, int32_t la, const int32_t *pb, int32_t lb, bool truncate,
                                int32_t n_max, int32_t *ids, int32_t *types, int32_t *n_tokens);
 
+    // One text as ColBERT reads it (bert_hip.h bertx_tokenize_colbert), p its pieces:
+    // kind 0, a query: [CLS] [unused0] p[: maxlen - 3] [SEP], then [MASK] up to maxlen,
+    // every keep 1; kind 1, a document: [CLS] [unused1] p[: maxlen - 3] [SEP], keep 0
+    // exactly where skiplisted(id).  The ids 1, 2 and 103 are hard-coded as tokenize
+    // hard-codes 100 / 101 / 102.  Returns the count (at most maxlen; ids and keep hold
+    // maxlen), or -1 for another kind or maxlen < 4.
+    int32_t colbert_layout(const int32_t *p, int32_t lp, int32_t kind, int32_t maxlen, int32_t *ids, int32_t *keep) const;
+    // Whether the vocab string of id is one ASCII punctuation character (one of the 32
+    // of Python's string.punctuation): ColBERT's skiplist.
+    bool skiplisted(int32_t id) const;
+
     // bert_vocab_id_to_token semantics (bert.cpp:121-134).
     const char *id_to_token(int32_t id) const;
 

@@ -5,6 +5,8 @@
 // Reads only a local directory: there is no hub download.
 //   convert dir-model ftype --head   a BertForSequenceClassification checkpoint (a
 // cross-encoder reranker): the same file followed by the pooler and classifier records.
+//   convert dir-model ftype --colbert   an HF_ColBERT checkpoint (encoder tensors bert.*,
+// the un-prefixed linear.weight): the same file followed by the projection record.
 #include "bert_hip.h"
 
 #include <cstdio>
@@ -30,8 +32,11 @@ int main(int argc, char **argv)
         out = dir + (ftype == 0 ? "/ggml-model-f32.bin" : "/ggml-model-f16.bin");
     }
     const bool head = argc > 3 && std::string(argv[3]) == "--head";
-    if ((head ? bertx_convert_hf_head(dir.c_str(), out.c_str(), ftype) : bertx_convert_hf(dir.c_str(), out.c_str(), ftype)) != 0)
-        return 1;
+    const bool colbert = argc > 3 && std::string(argv[3]) == "--colbert";
+    const int rc = head      ? bertx_convert_hf_head(dir.c_str(), out.c_str(), ftype)
+                   : colbert ? bertx_convert_hf_colbert(dir.c_str(), out.c_str(), ftype)
+                             : bertx_convert_hf(dir.c_str(), out.c_str(), ftype);
+    if (rc != 0) return 1;
     std::printf("Done. Output file: %s\n\n", out.c_str());
     return 0;
 }

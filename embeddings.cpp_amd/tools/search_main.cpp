@@ -2,7 +2,8 @@
 // corpus, then print the k closest texts of every query) with the corpus resident on
 // the GPU and the search fused there (bertx_index_*).
 //
-// usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8] [-r RERANK_MODEL [-c N] | -l [-c N]]
+// usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8]
+//               [-r RERANK_MODEL [-c N] | -l [-c N] | -L COLBERT_MODEL [-c N]]
 // One text per line of CORPUS.txt; queries from stdin, one per line, `q` or EOF ends.
 // Per hit one line: rank<TAB>id<TAB>score<TAB>text.
 // -s: how the index stores its rows (bertx_index_create_ex): f16, the default, or int8
@@ -15,6 +16,12 @@
 // per-token vectors go into a token store beside the index (bertx_mvindex_*); per query
 // the N best of the index are re-scored by MaxSim and the k best of those are printed,
 // ordered by that score (equal scores by ascending id), which is the printed score.
+// -L: late interaction from a second model file, as -r takes a second model: a ColBERT
+// file (a model file with a linear.weight record).  The store is created at that model's
+// bertx_proj_width and filled with bertx_mvindex_add_texts_colbert ([D] marker,
+// punctuation rows dropped, doc_maxlen 180 capped at the model's n_max_tokens); the
+// candidates are re-scored with bertx_mvindex_score_text_colbert ([Q] marker, [MASK]
+// augmentation to query_maxlen 32).
 #include "bert.h"
 #include "bert_hip.h"
 
@@ -29,7 +36,7 @@
 
 int main(int argc, char **argv)
 {
-    const char *model = nullptr, *corpus = nullptr, *rerank = nullptr;
+    const char *model = nullptr, *corpus = nullptr, *rerank = nullptr, *colbert = nullptr;
     int k = 3, threads = 4, cand = 0, storage = BERTX_INDEX_F16;
     bool late = false;
     for (int i = 1; i < argc; ++i) {
@@ -43,14 +50,16 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "-r") && has) rerank = argv[++i];
         else if (!std::strcmp(argv[i], "-c") && has) cand = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "-l")) late = true;
+        else if (!std::strcmp(argv[i], "-L") && has) colbert = argv[++i];
         else { model = nullptr; break; }
     }
-    const bool second = rerank || late;
+    const bool second = rerank || late || colbert;
     if (second && cand == 0) cand = std::min(128, 4 * k);
-    if (!model || !corpus || k < 1 || k > 128 || threads < 1 || (rerank && late) ||
+    if (!model || !corpus || k < 1 || k > 128 || threads < 1 || (int)(rerank != nullptr) + late + (colbert != nullptr) > 1 ||
         (second ? cand < k || cand > 128 : cand != 0)) {
         std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads] [-s f16|int8] "
-                             "[-r RERANK_MODEL [-c N (k..128, default 4 k)] | -l [-c N]]\n", argv[0]);
+                             "[-r RERANK_MODEL [-c N (k..128, default 4 k)] | -l [-c N] | -L COLBERT_MODEL [-c N]]\n",
+                     argv[0]);
         return 2;
     }
     std::vector<std::string> texts;
@@ -84,6 +93,19 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    // -L: the ColBERT model (in rctx, the second model's place)
+    int32_t doc_maxlen = 0, query_maxlen = 0;
+    if (colbert) {
+        rctx = bert_load_from_file(colbert);
+        if (!rctx || bertx_proj_dim(rctx) < 1) {
+            std::fprintf(stderr, "search: '%s' %s\n", colbert, rctx ? "has no projection record" : "cannot be loaded");
+            if (rctx) bert_free(rctx);
+            bert_free(ctx);
+            return 1;
+        }
+        doc_maxlen = std::min<int32_t>(180, bert_n_max_tokens(rctx));
+        query_maxlen = std::min<int32_t>(32, bert_n_max_tokens(rctx));
+    }
     bertx_index *idx = bertx_index_create_ex(ctx, 0, (int32_t)texts.size(), storage);
     if (!idx) {
         if (rctx) bert_free(rctx);
@@ -108,6 +130,17 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    if (colbert) {
+        // the store's size: doc_maxlen slots bound every document (its kept rows are fewer)
+        const int64_t slots = (int64_t)texts.size() * ((doc_maxlen + 15) / 16 * 16);
+        mv = bertx_mvindex_create(rctx, 0, bertx_proj_width(rctx), (int32_t)texts.size(), slots);
+        if (!mv) {
+            bertx_index_free(idx);
+            bert_free(rctx);
+            bert_free(ctx);
+            return 1;
+        }
+    }
     int rc = 0;
     // the corpus in batches (one encoder call each)
     for (size_t i = 0; i < texts.size() && rc == 0; i += 256) {
@@ -116,7 +149,8 @@ int main(int argc, char **argv)
         if (bertx_index_add_texts(idx, ctx, threads, (int32_t)p.size(), p.data()) < 0) {
             std::fprintf(stderr, "search: indexing failed at text %zu\n", i);
             rc = 1;
-        } else if (mv && bertx_mvindex_add_texts(mv, ctx, threads, (int32_t)p.size(), p.data()) < 0) {
+        } else if (mv && (colbert ? bertx_mvindex_add_texts_colbert(mv, rctx, threads, (int32_t)p.size(), p.data(), doc_maxlen)
+                                  : bertx_mvindex_add_texts(mv, ctx, threads, (int32_t)p.size(), p.data())) < 0) {
             std::fprintf(stderr, "search: token indexing failed at text %zu\n", i);
             rc = 1;
         }
@@ -137,7 +171,8 @@ int main(int argc, char **argv)
         if (mv) {
             // the candidates re-scored by MaxSim (a -1 fill slot scores -inf and sorts last)
             std::vector<float> ms((size_t)kq);
-            if (bertx_mvindex_score_text(mv, ctx, qp, ids.data(), kq, ms.data()) != 0) {
+            if ((colbert ? bertx_mvindex_score_text_colbert(mv, rctx, qp, query_maxlen, ids.data(), kq, ms.data())
+                         : bertx_mvindex_score_text(mv, ctx, qp, ids.data(), kq, ms.data())) != 0) {
                 std::fprintf(stderr, "search: late-interaction scoring failed\n");
                 rc = 1;
                 break;

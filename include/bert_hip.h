@@ -535,10 +535,9 @@ BERT_API int32_t bertx_index_search_texts(struct bertx_index *idx, struct bert_c
  * hash; average device time of `iters` calls of bertx_mvindex_score_device after 3
  * warm-up calls.
  *
- * Not provided: a ColBERT `linear` projection record with its [Q] / [D] markers, [MASK]
- * query augmentation and punctuation skiplist (the free width lets a caller add vectors
- * it projected itself through _add / _add_device); int8 token storage; a full-scan fused
- * top-k; several queries per call; sharding over GPUs; deleting, saving and loading.
+ * Not provided: int8 token storage; a full-scan fused top-k; several queries per call;
+ * sharding over GPUs; deleting, saving and loading.  (ColBERT checkpoints: "Projection"
+ * below.)
  */
 struct bertx_mvindex;
 BERT_API struct bertx_mvindex *bertx_mvindex_create(struct bert_ctx *ctx, int32_t slot, int32_t width,
@@ -658,6 +657,106 @@ BERT_API int32_t bertx_bench_search_add_rate(int32_t d, int32_t N, double *add_r
 BERT_API int32_t bertx_bench_search_ex(int32_t d, int32_t N, int32_t B, int32_t k, int32_t storage, int32_t iters,
                                        float *avg_us);
 BERT_API int32_t bertx_bench_search_add_rate_ex(int32_t d, int32_t N, int32_t storage, double *add_rows_per_s);
+
+/*
+ * Projection: ColBERT checkpoints (the `linear` record, the [Q] / [D] markers, [MASK]
+ * query augmentation, the punctuation skiplist, a fused projector).
+ *
+ * Model file.  One optional record linear.weight, ne = {n_embd, dim}, in the header
+ * ftype like any 2-D weight (bertx_quantize_file quantizes it by its general rule);
+ * ColBERT's projection has no bias.  dim % 32 == 0 and 32 <= dim <= 256, else a load
+ * error.  A file without the record loads and runs exactly as before; a file may carry
+ * the record and the classification head.  bertx_convert_hf_colbert is bertx_convert_hf
+ * followed by the record, from an HF_ColBERT directory (encoder tensors bert.*, the
+ * projection the un-prefixed linear.weight [dim][hidden]); it refuses (message,
+ * non-zero) a checkpoint without linear.weight, with a linear.bias, or with a shape the
+ * loader would refuse, and prints one line when the directory's artifact.metadata says
+ * attend_to_mask_tokens is false (see "Not provided").  bertx_proj_dim: the record's
+ * dim, 0 for a file without one; bertx_proj_width = 64 ceil(dim / 64): the width of
+ * every projected row and a legal bertx_mvindex_create width (a 96-dim checkpoint gives
+ * 128-wide rows whose last 32 columns are +0, which changes no dot product).  Both work
+ * on tokenizer-only contexts.
+ *
+ * Arithmetic of a projected row, every named operation rounded once to f32, nearest even:
+ *   x     = the row's final-LayerNorm values, the bits BERTX_OUT_TOKENS gives for that row
+ *   a_k   = f16(x_k), nearest even
+ *   w_jk  = f16(W_jk), at load, from the library's own dequantized f32 values
+ *   p_j   = sum_k a_k w_jk, f32 from 0 in ascending blocks of 32 k
+ *           (v_mfma_f32_16x16x32_f16; the order inside a block is the instruction's)
+ *   ss    = sum_{j < dim} p_j p_j, f32, in an order that depends on dim only
+ *   ss == 0: the row is +0; else rinv = 1 / sqrt(ss) (sqrt, then the division),
+ *   out_j = p_j * rinv;  out_j = +0 for dim <= j < width.
+ * The same arithmetic runs under all three chains (the LayerNorm row is rounded to f16
+ * in registers; no fold constants are involved).  A row's output depends on that row's
+ * x and on W only, bit for bit: not on the batch, the row's position or the other rows.
+ *
+ * BERTX_OUT_PROJ (bertx_forward_device_ex): d_out is float[total_tokens][proj_width],
+ * unit rows, what bertx_mvindex_add_device takes.  It follows no pooling mode and is
+ * never pruned.  On a file without the record bertx_forward_device_ex knows no such kind
+ * and returns -1, as it did before the record existed; the entries below, which exist
+ * only for the projection, return -6 on such a file.
+ * bertx_forward_project_device: the same with a row map d_rows int32[n_rows] on that
+ * GPU (every value in [0, total_tokens), trusted): d_out is float[n_rows][proj_width],
+ * row i the projection of token d_rows[i]; only mapped rows are computed.  d_rows NULL:
+ * BERTX_OUT_PROJ (n_rows is ignored).  -6 on a file without the record.
+ * bertx_forward_project: the host form, with the routing and refusals of
+ * bertx_forward_tokens; out[i] receives float[n_tokens[i]][proj_width].
+ *
+ * bertx_tokenize_colbert (works on tokenizer-only contexts): the pieces are
+ * bert_tokenize's for the text alone; ids 1 ([unused0], the [Q] marker), 2 ([unused1],
+ * the [D] marker) and 103 ([MASK]) are hard-coded as the tokenizer hard-codes 100 / 101
+ * / 102.  kind 0, a query: [CLS] [unused0] pieces[: maxlen - 3] [SEP], then [MASK] up
+ * to maxlen; *n_tokens = maxlen; every keep 1.  kind 1, a document: [CLS] [unused1]
+ * pieces[: maxlen - 3] [SEP]; keep[i] is 0 exactly where the token's vocab string is
+ * one ASCII punctuation character (the 32 of Python's string.punctuation).  ids and
+ * keep hold maxlen entries.  maxlen < 4 or > n_max_tokens, or another kind: -1.
+ *
+ * Store, text forms (both need bertx_mvindex_dim == bertx_proj_width, -1 otherwise, and
+ * the record, -6 otherwise; a replica on the store's GPU as the plain text forms).
+ * bertx_mvindex_add_texts_colbert: tokenises as documents at doc_maxlen, runs the
+ * forward on the store's GPU in the chunks of _add_texts and projects only the kept
+ * rows through the row map, so punctuation tokens attend and are attended to but are
+ * not stored; a document's len is its kept count (at least 3); returns as _add (-2
+ * with nothing added when the kept rows do not fit).
+ * bertx_mvindex_score_text_colbert: the augmented query of query_maxlen tokens, all of
+ * whose rows score; query_maxlen > 64 (or < 4, or > n_max_tokens): -1.
+ *
+ * bertx_test_project (parity hook; host buffers, device 0, the rules of the row-kernel
+ * hooks): mode 0: src = z f16 [T][d] with stats float [T][2] (mean, 1/sigma), g, b f32
+ * [d]; mode 1: src = x f32 [T][d] (stats, g, b ignored).  W f32 [dim][d]; rows int32
+ * [n_out] (values in [0, T), checked) or NULL for the identity with n_out = T.  out
+ * f32 [out_rows][proj_width]: the device output starts as the caller's bytes and is
+ * copied back whole, with guard rows of NaN bits behind it; -5: a guard row was
+ * written; -1: a shape the kernel refuses or out_rows < n_out.
+ * bertx_bench_project (device 0, no context): mode 0 on T random rows; average device
+ * time of `iters` launches after 3 warm-up launches.
+ *
+ * Not provided: [MASK] rows excluded as attention keys (ColBERT's attend_to_mask_tokens
+ * = false, the setting colbertv2.0 was trained with): here the augmentation rows are
+ * ordinary tokens of the sentence; excluding them needs a key length separate from the
+ * row count in the attention kernels.  int8 token storage, a full-scan top-k, several
+ * queries per call.
+ */
+enum { BERTX_OUT_PROJ = 3 };
+BERT_API int32_t bertx_convert_hf_colbert(const char *dir_model, const char *fname_out, int32_t ftype);
+BERT_API int32_t bertx_proj_dim(struct bert_ctx *ctx);
+BERT_API int32_t bertx_proj_width(struct bert_ctx *ctx);
+BERT_API int32_t bertx_tokenize_colbert(struct bert_ctx *ctx, const char *text, int32_t kind, int32_t maxlen,
+                                        bert_vocab_id *ids, int32_t *keep, int32_t *n_tokens);
+BERT_API int32_t bertx_forward_project_device(struct bert_ctx *ctx, int32_t slot, const int32_t *d_ids,
+                                              const int32_t *d_types, const int32_t *d_cu, int32_t n_seqs,
+                                              int32_t max_len, int32_t total_tokens, const int32_t *d_rows,
+                                              int32_t n_rows, float *d_out, void *stream);
+BERT_API int32_t bertx_forward_project(struct bert_ctx *ctx, int32_t n, bert_vocab_id **batch_tokens, int32_t *n_tokens,
+                                       float **out);
+BERT_API int32_t bertx_mvindex_add_texts_colbert(struct bertx_mvindex *mv, struct bert_ctx *ctx, int32_t n_threads,
+                                                 int32_t n, const char **texts, int32_t doc_maxlen);
+BERT_API int32_t bertx_mvindex_score_text_colbert(struct bertx_mvindex *mv, struct bert_ctx *ctx, const char *query,
+                                                  int32_t query_maxlen, const int32_t *ids, int32_t n, float *out);
+BERT_API int32_t bertx_test_project(int32_t mode, const void *src, const float *stats, const float *g, const float *b,
+                                    int32_t T, int32_t d, const float *W, int32_t dim, const int32_t *rows,
+                                    int32_t n_out, float *out, int32_t out_rows);
+BERT_API int32_t bertx_bench_project(int32_t d, int32_t dim, int32_t T, int32_t iters, float *avg_us);
 
 BERT_API const char *bertx_version(void);
 
