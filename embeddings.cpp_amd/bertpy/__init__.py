@@ -214,6 +214,14 @@ def load_lib(path=None):
         c_i64 = ctypes.c_int64
         L.bertx_mvindex_create.restype = vp
         L.bertx_mvindex_create.argtypes = [vp, c_i32, c_i32, c_i32, c_i64]
+        L.bertx_mvindex_create_ex.restype = vp
+        L.bertx_mvindex_create_ex.argtypes = [vp, c_i32, c_i32, c_i32, c_i64, c_i32]
+        L.bertx_mvindex_storage.restype = c_i32
+        L.bertx_mvindex_storage.argtypes = [vp]
+        L.bertx_mvindex_doc_i8.restype = c_i32
+        L.bertx_mvindex_doc_i8.argtypes = [vp, c_i32, vp, vp]
+        L.bertx_bench_maxsim_ex.restype = c_i32
+        L.bertx_bench_maxsim_ex.argtypes = [c_i32] * 7 + [c_f32p]
         L.bertx_mvindex_free.restype = None
         L.bertx_mvindex_free.argtypes = [vp]
         for fn in (L.bertx_mvindex_clear, L.bertx_mvindex_docs, L.bertx_mvindex_capacity_docs, L.bertx_mvindex_dim):
@@ -645,20 +653,26 @@ class BertIndex:
 
 class BertTokenIndex:
     """A device-resident token store with a fused MaxSim scorer (bertx_mvindex_*): late
-    interaction.  Documents are [len][width] token vectors, stored as unit-length f16
-    rows on GPU `slot` of the model's context; ids are the insertion order.  A query of
-    up to 64 token vectors scores a document as sum_i max_j <q_i, c_j>; bert_hip.h gives
-    the arithmetic.  width None: the model's n_embd (what the text forms need)."""
+    interaction.  Documents are [len][width] token vectors, stored as unit-length rows,
+    f16 (storage="f16") or int8 with one f32 per token (storage="int8", half the bytes,
+    a less precise similarity), on GPU `slot` of the model's context; ids are the
+    insertion order.  A query of up to 64 token vectors scores a document as
+    sum_i max_j <q_i, c_j>; bert_hip.h gives the arithmetic of both kinds.  width None:
+    the model's n_embd (what the text forms need)."""
 
     MAX_QUERY_TOKENS = 64
+    STORAGE = BertIndex.STORAGE
 
-    def __init__(self, model, capacity_docs, capacity_token_slots, slot=0, width=None):
+    def __init__(self, model, capacity_docs, capacity_token_slots, slot=0, width=None, storage="f16"):
+        if storage not in self.STORAGE:
+            raise ValueError("storage must be 'f16' or 'int8', got %r" % (storage,))
         self.model = model
         self.lib = model.lib
-        self.mv = self.lib.bertx_mvindex_create(model.ctx, slot, model.n_embd if width is None else width,
-                                                capacity_docs, capacity_token_slots)
+        self.storage = storage
+        self.mv = self.lib.bertx_mvindex_create_ex(model.ctx, slot, model.n_embd if width is None else width,
+                                                   capacity_docs, capacity_token_slots, self.STORAGE[storage])
         if not self.mv:
-            raise RuntimeError("bertx_mvindex_create failed")
+            raise RuntimeError("bertx_mvindex_create_ex failed")
         self.dim = int(self.lib.bertx_mvindex_dim(self.mv))
         self.capacity_docs = int(self.lib.bertx_mvindex_capacity_docs(self.mv))
         self.capacity_token_slots = int(self.lib.bertx_mvindex_capacity_token_slots(self.mv))
@@ -719,7 +733,8 @@ class BertTokenIndex:
         return int(self.lib.bertx_mvindex_doc_len(self.mv, i))
 
     def doc(self, i):
-        """The stored rows of document i as f32 [len][width]: the exact f16 values."""
+        """The stored rows of document i as f32 [len][width]: the exact f16 values, or the
+        dequantized q * u of an int8 store."""
         n = self.doc_len(i)
         if n < 1:
             raise IndexError("no document %d" % i)
@@ -727,6 +742,18 @@ class BertTokenIndex:
         if self.lib.bertx_mvindex_doc(self.mv, i, out.ctypes.data) != 0:
             raise RuntimeError("bertx_mvindex_doc failed")
         return out
+
+    def doc_i8(self, i):
+        """(q int8 [len][width], u f32 [len]): the stored bytes and scales of document i of
+        an int8 store."""
+        n = self.doc_len(i)
+        if n < 1:
+            raise IndexError("no document %d" % i)
+        q = np.zeros((n, self.dim), np.int8)
+        u = np.zeros(n, np.float32)
+        if self.lib.bertx_mvindex_doc_i8(self.mv, i, q.ctypes.data, u.ctypes.data) != 0:
+            raise RuntimeError("bertx_mvindex_doc_i8 failed")
+        return q, u
 
     def _out(self, ids):
         n = len(self) if ids is None else len(ids)

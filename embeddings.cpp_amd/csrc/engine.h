@@ -358,7 +358,8 @@ int hip_device_count();
 
 // A token store (mvindex.cpp, bert_hip.h bertx_mvindex_*) of width w for cap_docs
 // documents in cap_slots token slots on device `ordinal`, without a context
-// (bertx_mvindex_create, the MaxSim bench).  NULL after a message.
-::bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t cap_slots);
+// (bertx_mvindex_create_ex, the MaxSim bench); storage BERTX_INDEX_F16 or _I8.  NULL
+// after a message.
+::bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t cap_slots, int storage);
 
 }  // namespace emb

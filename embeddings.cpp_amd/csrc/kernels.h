@@ -258,6 +258,15 @@ int launch_mv_pack(const float *d_rows, int64_t t0, int64_t count, int w, const 
 // is normalised as the rows are.  1 <= Lq <= 64, n >= 1; -1 otherwise, -3: launch refused.
 int launch_maxsim(const void *store, const void *d_table, int n_docs, int w, const float *d_q, int Lq,
                   const int32_t *d_ids, int n, float *d_out, hipStream_t s);
+// The same two over an int8 store (maxsim_i8.hip): rows in the SEARCH_I8 fragment order,
+// each the embedding index's int8 quantization q of the raw row, and scales f32 [token
+// slots], u = 1 / sqrt(sum q_i^2) per slot (0 for a zero row), so that q u has unit
+// length; sim = score_i8(isum, u_query, u_row).  maxsim_prepare_device covers both kinds.
+int maxsim_i8_prepare_device();
+int launch_mv_pack_i8(const float *d_rows, int64_t t0, int64_t count, int w, const int32_t *d_src_off,
+                      const void *d_table, int n_new, void *store, float *scales, hipStream_t s);
+int launch_maxsim_i8(const void *store, const float *scales, const void *d_table, int n_docs, int w, const float *d_q,
+                     int Lq, const int32_t *d_ids, int n, float *d_out, hipStream_t s);
 
 // ---- the classification head (head.hip): pooler dense + tanh + classifier on the
 // sentences' [CLS] rows, all f32, one form for the three chains ----

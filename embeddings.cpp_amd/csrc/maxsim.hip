@@ -232,7 +232,7 @@ int maxsim_prepare_device()
     if (e == hipSuccess) e = allow_lds<2>();
     if (e == hipSuccess) e = allow_lds<3>();
     if (e == hipSuccess) e = allow_lds<4>();
-    return e == hipSuccess ? 0 : -1;
+    return e == hipSuccess ? maxsim_i8_prepare_device() : -1;
 }
 
 int launch_mv_pack(const float *d_rows, int64_t t0, int64_t count, int w, const int32_t *d_src_off,

@@ -1,8 +1,9 @@
 // The token store of late interaction (bert_hip.h bertx_mvindex_*): an append-only set
-// of documents, each a run of unit-length f16 token rows in the search kernel's fragment
-// order (kernels.h, maxsim.hip), the fused MaxSim scorer over it, and the text forms on
-// top of the per-token forward.  After creation a store knows only its device ordinal
-// and its width.  The ordering rules are the embedding index's (index.cpp).
+// of documents, each a run of unit-length token rows in the search kernel's fragment
+// order, f16 (kernels.h, maxsim.hip) or int8 with one f32 per token slot (maxsim_i8.hip),
+// the fused MaxSim scorer over it, and the text forms on top of the per-token forward.
+// After creation a store knows only its device ordinal, its width and its storage kind.
+// The ordering rules are the embedding index's (index.cpp).
 #include "bert.h"
 #include "bert_hip.h"
 
@@ -20,9 +21,11 @@
 struct bertx_mvindex {
     int ordinal = 0;
     int w = 0;
+    int storage = BERTX_INDEX_F16;
     int64_t cap_docs = 0, cap_slots = 0;   // as given at creation
     int64_t n_docs = 0, used_slots = 0;    // used_slots: whole groups, 16 per group
-    void *store = nullptr;                 // f16, ceil(cap_slots / 16) groups in fragment order
+    void *store = nullptr;                 // f16 or int8, ceil(cap_slots / 16) groups in fragment order
+    float *scales = nullptr;               // int8: one f32 per token slot
     int32_t *table = nullptr;              // device: (first group, len) per document
     int32_t *src_off = nullptr;            // device: per document, its first source row in the add call that brought it
     // page-locked host images of both, written per add at the new documents' own entries
@@ -41,7 +44,7 @@ struct bertx_mvindex {
         emb::DeviceGuard g(ordinal);
         if (stream) (void)hipStreamSynchronize(stream);
         if (any && done) (void)hipEventSynchronize(done);
-        for (void *p : {store, (void *)table, (void *)src_off, (void *)st_rows, (void *)st_q, (void *)st_out,
+        for (void *p : {store, (void *)scales, (void *)table, (void *)src_off, (void *)st_rows, (void *)st_q, (void *)st_out,
                         (void *)st_ids, (void *)st_tok})
             if (p) (void)hipFree(p);
         if (h_table) (void)hipHostFree(h_table);
@@ -133,6 +136,9 @@ int32_t upload_entries(bertx_mvindex &mv, int32_t n, hipStream_t s)
 
 int32_t pack(bertx_mvindex &mv, const float *d_rows, int64_t t0, int64_t count, int32_t n, hipStream_t s)
 {
+    if (mv.storage == BERTX_INDEX_I8)
+        return launch_mv_pack_i8(d_rows, t0, count, mv.w, mv.src_off + mv.n_docs, mv.table + 2 * mv.n_docs, n, mv.store,
+                                 mv.scales, s);
     return launch_mv_pack(d_rows, t0, count, mv.w, mv.src_off + mv.n_docs, mv.table + 2 * mv.n_docs, n, mv.store, s);
 }
 
@@ -167,6 +173,8 @@ int32_t score_device_locked(bertx_mvindex &mv, const float *d_q, int32_t Lq, con
 {
     if (!d_q || !d_out || Lq < 1 || Lq > kMaxLq || n < 1) return -1;
     Ordered o(mv, s);
+    if (mv.storage == BERTX_INDEX_I8)
+        return launch_maxsim_i8(mv.store, mv.scales, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s);
     return launch_maxsim(mv.store, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s);
 }
 
@@ -191,6 +199,29 @@ int32_t score_host_ids(bertx_mvindex &mv, const float *d_q, int32_t Lq, const in
         HIP_RC(hipStreamSynchronize(mv.stream));
     }
     std::memcpy(out, hs.data(), hs.size() * 4);
+    return 0;
+}
+
+// The stored bytes q [len][w] and scales u [len] of document id of an int8 store (the
+// caller holds the lock, has checked the id and has selected the device).
+int32_t read_doc_i8(bertx_mvindex &mv, int32_t id, int8_t *q, float *u)
+{
+    const int w = mv.w, KB = w / 64;
+    const int64_t first = mv.h_table[2 * (size_t)id], len = mv.h_table[2 * (size_t)id + 1];
+    const size_t group_bytes = (size_t)16 * w, groups = (size_t)((len + 15) / 16);
+    std::vector<int8_t> raw(groups * group_bytes);
+    std::vector<float> us(groups * 16);
+    if (mv.any) HIP_RC(hipEventSynchronize(mv.done));
+    HIP_RC(hipMemcpy(raw.data(), (const int8_t *)mv.store + (size_t)first * group_bytes, raw.size(),
+                     hipMemcpyDeviceToHost));
+    HIP_RC(hipMemcpy(us.data(), mv.scales + (size_t)first * 16, us.size() * 4, hipMemcpyDeviceToHost));
+    for (int64_t r = 0; r < len; ++r) {
+        const int8_t *grp = raw.data() + (size_t)(r / 16) * group_bytes;
+        for (int kb = 0; kb < KB; ++kb)
+            for (int g = 0; g < 4; ++g)
+                std::memcpy(q + (size_t)r * w + 64 * kb + 16 * g, grp + ((size_t)kb * 64 + 16 * g + (r & 15)) * 16, 16);
+        u[r] = us[(size_t)r];
+    }
     return 0;
 }
 
@@ -246,8 +277,12 @@ int32_t colbert_ctx_ok(bertx_mvindex *mv, struct bert_ctx *ctx, const char *who,
 
 }  // namespace
 
-bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t cap_slots)
+bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t cap_slots, int storage)
 {
+    if (storage != BERTX_INDEX_F16 && storage != BERTX_INDEX_I8) {
+        errorf("bertx_mvindex_create: storage %d is neither BERTX_INDEX_F16 nor BERTX_INDEX_I8\n", storage);
+        return nullptr;
+    }
     if (w % 64 || w < 64 || w > 1024) {
         errorf("bertx_mvindex_create: width %d is not a multiple of 64 in 64 .. 1024\n", w);
         return nullptr;
@@ -266,13 +301,17 @@ bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t c
     if (!mv) return nullptr;
     mv->ordinal = ordinal;
     mv->w = w;
+    mv->storage = storage;
     mv->cap_docs = cap_docs;
     mv->cap_slots = cap_slots;
-    const size_t store_bytes = (size_t)((cap_slots + 15) / 16) * 16 * (size_t)w * 2;
+    const size_t slots16 = (size_t)((cap_slots + 15) / 16) * 16;
+    const bool i8 = storage == BERTX_INDEX_I8;
+    const size_t store_bytes = slots16 * (size_t)w * (i8 ? 1 : 2);
     const bool ok = maxsim_prepare_device() == 0 &&
                     hipStreamCreateWithFlags(&mv->stream, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&mv->done, hipEventDisableTiming) == hipSuccess &&
                     hipMalloc(&mv->store, store_bytes) == hipSuccess &&
+                    (!i8 || hipMalloc((void **)&mv->scales, slots16 * 4) == hipSuccess) &&
                     hipMalloc((void **)&mv->table, (size_t)cap_docs * 8) == hipSuccess &&
                     hipMalloc((void **)&mv->src_off, (size_t)cap_docs * 4) == hipSuccess &&
                     hipHostMalloc((void **)&mv->h_table, (size_t)cap_docs * 8, hipHostMallocDefault) == hipSuccess &&
@@ -285,7 +324,7 @@ bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t c
     if (!ok) {
         (void)hipGetLastError();
         errorf("bertx_mvindex_create: device %d could not allocate %zu bytes of token rows (+ %lld table entries)\n",
-               ordinal, store_bytes, (long long)cap_docs);
+               ordinal, store_bytes + (i8 ? slots16 * 4 : 0), (long long)cap_docs);
         delete mv;
         return nullptr;
     }
@@ -298,8 +337,8 @@ using emb::DeviceGuard;
 
 extern "C" {
 
-struct bertx_mvindex *bertx_mvindex_create(struct bert_ctx *ctx, int32_t slot, int32_t width, int32_t capacity_docs,
-                                           int64_t capacity_token_slots)
+struct bertx_mvindex *bertx_mvindex_create_ex(struct bert_ctx *ctx, int32_t slot, int32_t width, int32_t capacity_docs,
+                                              int64_t capacity_token_slots, int32_t storage)
 {
     if (!ctx) {
         emb::errorf("bertx_mvindex_create: no context\n");
@@ -315,8 +354,16 @@ struct bertx_mvindex *bertx_mvindex_create(struct bert_ctx *ctx, int32_t slot, i
                     bertx_num_devices(ctx));
         return nullptr;
     }
-    return emb::mvindex_create_on(ordinal, width, capacity_docs, capacity_token_slots);
+    return emb::mvindex_create_on(ordinal, width, capacity_docs, capacity_token_slots, storage);
 }
+
+struct bertx_mvindex *bertx_mvindex_create(struct bert_ctx *ctx, int32_t slot, int32_t width, int32_t capacity_docs,
+                                           int64_t capacity_token_slots)
+{
+    return bertx_mvindex_create_ex(ctx, slot, width, capacity_docs, capacity_token_slots, BERTX_INDEX_F16);
+}
+
+int32_t bertx_mvindex_storage(struct bertx_mvindex *mv) { return mv ? mv->storage : -1; }
 
 void bertx_mvindex_free(struct bertx_mvindex *mv) { delete mv; }
 
@@ -406,6 +453,22 @@ int32_t bertx_mvindex_doc(struct bertx_mvindex *mv, int32_t id, float *out)
     if (id < 0 || id >= mv->n_docs) return -1;
     DeviceGuard g(mv->ordinal);
     HIP_RC(g.status());
+    if (mv->storage == BERTX_INDEX_I8) {
+        try {
+            const int w = mv->w;
+            const int64_t len = mv->h_table[2 * (size_t)id + 1];
+            std::vector<int8_t> q((size_t)len * w);
+            std::vector<float> u((size_t)len);
+            const int32_t rc = emb::read_doc_i8(*mv, id, q.data(), u.data());
+            if (rc != 0) return rc;
+            for (int64_t r = 0; r < len; ++r)
+                for (int i = 0; i < w; ++i) out[(size_t)r * w + i] = (float)q[(size_t)r * w + i] * u[(size_t)r];
+        } catch (const std::bad_alloc &) {
+            emb::errorf("bertx_mvindex_doc: out of host memory\n");
+            return -1;
+        }
+        return 0;
+    }
     try {
         const int w = mv->w, KB = w / 32;
         const int64_t first = mv->h_table[2 * (size_t)id], len = mv->h_table[2 * (size_t)id + 1];
@@ -424,6 +487,29 @@ int32_t bertx_mvindex_doc(struct bertx_mvindex *mv, int32_t id, float *out)
         }
     } catch (const std::bad_alloc &) {
         emb::errorf("bertx_mvindex_doc: out of host memory\n");
+        return -1;
+    }
+    return 0;
+}
+
+int32_t bertx_mvindex_doc_i8(struct bertx_mvindex *mv, int32_t id, int8_t *q, float *u)
+{
+    if (!mv || !q || !u) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    if (mv->storage != BERTX_INDEX_I8 || id < 0 || id >= mv->n_docs) return -1;
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    try {
+        // through buffers of its own: a failed copy leaves the outputs untouched
+        const int64_t len = mv->h_table[2 * (size_t)id + 1];
+        std::vector<int8_t> hq((size_t)len * mv->w);
+        std::vector<float> hu((size_t)len);
+        const int32_t rc = emb::read_doc_i8(*mv, id, hq.data(), hu.data());
+        if (rc != 0) return rc;
+        std::memcpy(q, hq.data(), hq.size());
+        std::memcpy(u, hu.data(), hu.size() * 4);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_mvindex_doc_i8: out of host memory\n");
         return -1;
     }
     return 0;
@@ -705,8 +791,8 @@ int32_t bertx_mvindex_score_text_colbert(struct bertx_mvindex *mv, struct bert_c
 }
 
 // MaxSim micro-benchmark (bert_hip.h): device 0, no context.
-int32_t bertx_bench_maxsim(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t iters,
-                           float *avg_us)
+int32_t bertx_bench_maxsim_ex(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t storage,
+                              int32_t iters, float *avg_us)
 {
     using namespace emb;
     if (n_docs < 1 || doc_len < 0 || doc_len > 4096 || n_cand < 1 || iters < 1 || !avg_us || hip_device_count() == 0)
@@ -738,7 +824,7 @@ int32_t bertx_bench_maxsim(int32_t w, int32_t n_docs, int32_t doc_len, int32_t L
                 bertx_mvindex_free(mv);
             }
         } H;
-        H.mv = mvindex_create_on(0, w, n_docs, slots);
+        H.mv = mvindex_create_on(0, w, n_docs, slots, storage);
         if (!H.mv) return -1;
         HIP_RC(hipStreamCreateWithFlags(&H.s, hipStreamNonBlocking));
         HIP_RC(hipEventCreate(&H.a));
@@ -779,6 +865,12 @@ int32_t bertx_bench_maxsim(int32_t w, int32_t n_docs, int32_t doc_len, int32_t L
         emb::errorf("bertx_bench_maxsim: %s\n", ex.what());
         return -1;
     }
+}
+
+int32_t bertx_bench_maxsim(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t iters,
+                           float *avg_us)
+{
+    return bertx_bench_maxsim_ex(w, n_docs, doc_len, Lq, n_cand, BERTX_INDEX_F16, iters, avg_us);
 }
 
 }  // extern "C"

@@ -24,13 +24,12 @@
 // products times the two scales (score_i8), so it is order-free as well.
 #include "device_common.h"
 #include "kernels.h"
+#include "quant_i8.h"
 
 #include <algorithm>
 
 namespace emb {
 namespace {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;          // 4 waves: each streams its own contiguous run of 16-row groups
 constexpr int kUnitsAhead = 8;         // prefetch ring: 8 units of 2 blocks = 16 KiB in flight per wave
@@ -62,47 +61,6 @@ __device__ __forceinline__ f32x4 mma(h16x8 a, h16x8 b, f32x4 c)
 __device__ __forceinline__ i32x4 mma(i32x4 a, i32x4 b, i32x4 c)
 {
     return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
-}
-
-// The int8 quantizer of stored rows and of queries, one wave per row x f32 [d]: lane
-// c < d / 16 takes elements 16c .. 16c + 15 and returns their 16 bytes (element 16c + j
-// in byte j), the other lanes return zeros; every lane gets the row's scale.
-//   amax = max |x_i|;  amax == 0: scale 0, every q 0;  else inv = 127 / amax,
-//   q_i = clamp(rint(x_i * inv), -127, 127) (nearest even), scale = amax / 127,
-// each operation rounded once to f32.  Non-finite input: the clamp still holds (a NaN
-// product becomes -127), the values are unspecified.
-__device__ __forceinline__ i32x4 quantize_row_i8(const float *__restrict__ x, int d, int lane, float &scale)
-{
-    float v[16];
-    const bool on = lane < (d >> 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float4 a = {0.f, 0.f, 0.f, 0.f};
-        if (on) a = *(const float4 *)(x + 16 * lane + 4 * j);
-        v[4 * j] = a.x; v[4 * j + 1] = a.y; v[4 * j + 2] = a.z; v[4 * j + 3] = a.w;
-    }
-    float amax = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(v[i]));
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-    i32x4 out = {0, 0, 0, 0};
-    scale = 0.f;
-    if (!(amax > 0.f)) return out;
-    const float inv = __fdiv_rn(127.0f, amax);
-    scale = __fdiv_rn(amax, 127.0f);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const float r = fminf(fmaxf(rintf(__fmul_rn(v[i], inv)), -127.0f), 127.0f);
-        out[i >> 2] |= ((int)r & 0xff) << (8 * (i & 3));
-    }
-    return out;
-}
-
-// The int8 score: the i32 sum is exact in f32 (|isum| <= 127 * 127 * 1024 < 2^24).
-__device__ __forceinline__ float score_i8(int isum, float scale_q, float scale_row)
-{
-    return __fmul_rn((float)isum, __fmul_rn(scale_q, scale_row));
 }
 
 // (score, id) order of the results: higher score first, equal scores by ascending

@@ -3,7 +3,7 @@
 // the GPU and the search fused there (bertx_index_*).
 //
 // usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8]
-//               [-r RERANK_MODEL [-c N] | -l [-c N] | -L COLBERT_MODEL [-c N]]
+//               [-r RERANK_MODEL [-c N] | -l [-c N] | -L COLBERT_MODEL [-c N]] [-S f16|int8]
 // One text per line of CORPUS.txt; queries from stdin, one per line, `q` or EOF ends.
 // Per hit one line: rank<TAB>id<TAB>score<TAB>text.
 // -s: how the index stores its rows (bertx_index_create_ex): f16, the default, or int8
@@ -22,6 +22,9 @@
 // punctuation rows dropped, doc_maxlen 180 capped at the model's n_max_tokens); the
 // candidates are re-scored with bertx_mvindex_score_text_colbert ([Q] marker, [MASK]
 // augmentation to query_maxlen 32).
+// -S: with -l or -L, how the token store keeps its rows (bertx_mvindex_create_ex): f16,
+// the default, or int8 with one f32 per token, half the bytes and a less precise
+// similarity.  -s still speaks of the index alone.
 #include "bert.h"
 #include "bert_hip.h"
 
@@ -37,7 +40,7 @@
 int main(int argc, char **argv)
 {
     const char *model = nullptr, *corpus = nullptr, *rerank = nullptr, *colbert = nullptr;
-    int k = 3, threads = 4, cand = 0, storage = BERTX_INDEX_F16;
+    int k = 3, threads = 4, cand = 0, storage = BERTX_INDEX_F16, mv_storage = -1;
     bool late = false;
     for (int i = 1; i < argc; ++i) {
         const bool has = i + 1 < argc;
@@ -47,6 +50,8 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "-t") && has) threads = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "-s") && has && !std::strcmp(argv[i + 1], "f16")) { storage = BERTX_INDEX_F16; ++i; }
         else if (!std::strcmp(argv[i], "-s") && has && !std::strcmp(argv[i + 1], "int8")) { storage = BERTX_INDEX_I8; ++i; }
+        else if (!std::strcmp(argv[i], "-S") && has && !std::strcmp(argv[i + 1], "f16")) { mv_storage = BERTX_INDEX_F16; ++i; }
+        else if (!std::strcmp(argv[i], "-S") && has && !std::strcmp(argv[i + 1], "int8")) { mv_storage = BERTX_INDEX_I8; ++i; }
         else if (!std::strcmp(argv[i], "-r") && has) rerank = argv[++i];
         else if (!std::strcmp(argv[i], "-c") && has) cand = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "-l")) late = true;
@@ -56,9 +61,10 @@ int main(int argc, char **argv)
     const bool second = rerank || late || colbert;
     if (second && cand == 0) cand = std::min(128, 4 * k);
     if (!model || !corpus || k < 1 || k > 128 || threads < 1 || (int)(rerank != nullptr) + late + (colbert != nullptr) > 1 ||
-        (second ? cand < k || cand > 128 : cand != 0)) {
+        (second ? cand < k || cand > 128 : cand != 0) || (mv_storage >= 0 && !late && !colbert)) {
         std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads] [-s f16|int8] "
-                             "[-r RERANK_MODEL [-c N (k..128, default 4 k)] | -l [-c N] | -L COLBERT_MODEL [-c N]]\n",
+                             "[-r RERANK_MODEL [-c N (k..128, default 4 k)] | -l [-c N] | -L COLBERT_MODEL [-c N]] "
+                             "[-S f16|int8 (the token store of -l / -L)]\n",
                      argv[0]);
         return 2;
     }
@@ -106,6 +112,7 @@ int main(int argc, char **argv)
         doc_maxlen = std::min<int32_t>(180, bert_n_max_tokens(rctx));
         query_maxlen = std::min<int32_t>(32, bert_n_max_tokens(rctx));
     }
+    if (mv_storage < 0) mv_storage = BERTX_INDEX_F16;
     bertx_index *idx = bertx_index_create_ex(ctx, 0, (int32_t)texts.size(), storage);
     if (!idx) {
         if (rctx) bert_free(rctx);
@@ -123,7 +130,7 @@ int main(int argc, char **argv)
             bert_tokenize(ctx, t.c_str(), tok.data(), &n, n_max);
             slots += (std::max(n, 1) + 15) / 16 * 16;
         }
-        mv = bertx_mvindex_create(ctx, 0, bert_n_embd(ctx), (int32_t)texts.size(), slots);
+        mv = bertx_mvindex_create_ex(ctx, 0, bert_n_embd(ctx), (int32_t)texts.size(), slots, mv_storage);
         if (!mv) {
             bertx_index_free(idx);
             bert_free(ctx);
@@ -133,7 +140,7 @@ int main(int argc, char **argv)
     if (colbert) {
         // the store's size: doc_maxlen slots bound every document (its kept rows are fewer)
         const int64_t slots = (int64_t)texts.size() * ((doc_maxlen + 15) / 16 * 16);
-        mv = bertx_mvindex_create(rctx, 0, bertx_proj_width(rctx), (int32_t)texts.size(), slots);
+        mv = bertx_mvindex_create_ex(rctx, 0, bertx_proj_width(rctx), (int32_t)texts.size(), slots, mv_storage);
         if (!mv) {
             bertx_index_free(idx);
             bert_free(rctx);

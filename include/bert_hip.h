@@ -535,13 +535,63 @@ BERT_API int32_t bertx_index_search_texts(struct bertx_index *idx, struct bert_c
  * hash; average device time of `iters` calls of bertx_mvindex_score_device after 3
  * warm-up calls.
  *
- * Not provided: int8 token storage; a full-scan fused top-k; several queries per call;
- * sharding over GPUs; deleting, saving and loading.  (ColBERT checkpoints: "Projection"
- * below.)
+ * Storage kinds.  bertx_mvindex_create_ex takes the kind: BERTX_INDEX_F16 (0) is exactly
+ * bertx_mvindex_create, everything above; BERTX_INDEX_I8 (1) stores a token row as `width`
+ * int8 values and one f32, width + 4 bytes instead of 2 width (the store allocates
+ * slots * width bytes and slots * 4 bytes of scales); any other value returns NULL after
+ * a message.  bertx_mvindex_storage returns the kind, -1 for NULL.  Every other entry
+ * (_add, _add_device, _score, _score_device, _clear, _add_texts, _score_text and the two
+ * _colbert text forms) follows the store's kind with the same signature, refusals,
+ * stream ordering and capturability.  The int8 arithmetic, one quantizer for stored rows
+ * and for query rows, every named operation rounded once to f32 (IEEE, nearest even):
+ *   (q, _) = the embedding index's quantizer on the raw row x ("Storage kinds" above:
+ *            amax = max_i |x_i|; amax == 0: all q_i = 0; else inv = 127 / amax,
+ *            q_i = clamp(rint(x_i * inv), -127, 127)); its scale output is not kept;
+ *   n2     = sum_i q_i * q_i in int32: exact, n2 <= 127 * 127 * 1024 < 2^24, so (float)n2
+ *            is exact;
+ *   n2 == 0: u = 0;  otherwise u = 1 / sqrt((float)n2) (sqrt, then the division);
+ *   stored: the `width` bytes q and the one f32 u; the dequantized row q_i * u has unit
+ *            length to f32 rounding;
+ *   sim(a, c)  = (float)isum * (u_a * u_c), isum = sum_i qa_i * qc_i in int32 (exact);
+ *   score(doc) = sum_{i < Lq} max_{j < len} sim(q_i, c_j): the max is exact; the sum over
+ *            i is the f16 scorer's order, spelled out: lane c (0 .. 15) adds m[c],
+ *            m[16 + c], ... in ascending order from +0 (a query index >= Lq adds +0),
+ *            then s += shfl_xor(s, o) for o = 8, 4, 2, 1 (lane l adds lane l ^ o's value
+ *            of the step before); lane 0 is the score.
+ * Nothing in this depends on a summation order the caller cannot reproduce (normalising
+ * after quantizing makes the norm an exact integer), so a restatement in float32 gives
+ * the bytes, the scales and the scores bit for bit.  The invariances of the f16 store
+ * hold word for word: a score depends on the query and on that document's rows only, not
+ * on its id, the other documents, the candidate list or its order.  Slots of a
+ * document's last group past len, and their scale slots, are never counted whatever they
+ * hold: they become -inf through a select.  Non-finite input, or an amax so small that
+ * 127 / amax overflows, gives unspecified values inside the clamp.
+ * Accuracy against the exact cosine: with x' = 127 x / amax in real arithmetic and
+ * e_x = |q - x'|_2 / |x'|_2 the relative quantization error of a row, the unit vectors
+ * differ by at most 2 e_x, so
+ *   |sim - cos(x, y)| <= 2 (e_x + e_y) + 2^-21,
+ * the 2^-21 covering the sqrt, the division, the two multiplies and the f32 rounding of
+ * (float)isum * (u_a * u_c).  int8 is the less precise kind: about 1e-2 per similarity
+ * on rows with a few channels 20 times larger than the rest.
+ * bertx_mvindex_doc on an int8 store returns (float)q * u (one f32 multiply);
+ * bertx_mvindex_doc_i8 returns the stored bytes q int8[len][width] and scales
+ * u float[len], or -1 on an f16 store or a bad id with the outputs untouched.
+ * bertx_bench_maxsim_ex is bertx_bench_maxsim over a store of the given kind.
+ *
+ * Not provided: int8 queries against f16 rows; 4-bit or residual codes; a full-scan fused
+ * top-k; several queries per call; sharding over GPUs; deleting, saving and loading.
+ * (ColBERT checkpoints: "Projection" below.)
  */
 struct bertx_mvindex;
 BERT_API struct bertx_mvindex *bertx_mvindex_create(struct bert_ctx *ctx, int32_t slot, int32_t width,
                                                     int32_t capacity_docs, int64_t capacity_token_slots);
+BERT_API struct bertx_mvindex *bertx_mvindex_create_ex(struct bert_ctx *ctx, int32_t slot, int32_t width,
+                                                       int32_t capacity_docs, int64_t capacity_token_slots,
+                                                       int32_t storage);
+BERT_API int32_t bertx_mvindex_storage(struct bertx_mvindex *mv);
+BERT_API int32_t bertx_mvindex_doc_i8(struct bertx_mvindex *mv, int32_t id, int8_t *q, float *u);
+BERT_API int32_t bertx_bench_maxsim_ex(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand,
+                                       int32_t storage, int32_t iters, float *avg_us);
 BERT_API void bertx_mvindex_free(struct bertx_mvindex *mv);
 BERT_API int32_t bertx_mvindex_clear(struct bertx_mvindex *mv);
 BERT_API int32_t bertx_mvindex_docs(struct bertx_mvindex *mv);
@@ -734,8 +784,8 @@ BERT_API int32_t bertx_bench_search_add_rate_ex(int32_t d, int32_t N, int32_t st
  * Not provided: [MASK] rows excluded as attention keys (ColBERT's attend_to_mask_tokens
  * = false, the setting colbertv2.0 was trained with): here the augmentation rows are
  * ordinary tokens of the sentence; excluding them needs a key length separate from the
- * row count in the attention kernels.  int8 token storage, a full-scan top-k, several
- * queries per call.
+ * row count in the attention kernels.  A full-scan top-k, several queries per call.
+ * (The ColBERT text forms follow the store's kind: an int8 store takes them unchanged.)
  */
 enum { BERTX_OUT_PROJ = 3 };
 BERT_API int32_t bertx_convert_hf_colbert(const char *dir_model, const char *fname_out, int32_t ftype);
