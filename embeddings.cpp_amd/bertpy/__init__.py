@@ -248,6 +248,17 @@ def load_lib(path=None):
         L.bertx_mvindex_score_text.argtypes = [vp, vp, ctypes.c_char_p, vp, c_i32, vp]
         L.bertx_bench_maxsim.restype = c_i32
         L.bertx_bench_maxsim.argtypes = [c_i32] * 6 + [c_f32p]
+        L.bertx_mvindex_search.restype = c_i32
+        L.bertx_mvindex_search.argtypes = [vp, vp, c_i32, c_i32, c_i32, vp, vp]
+        L.bertx_mvindex_search_device.restype = c_i32
+        L.bertx_mvindex_search_device.argtypes = [vp, vp, c_i32, c_i32, c_i32, vp, vp, vp]
+        L.bertx_mvindex_search_texts.restype = c_i32
+        L.bertx_mvindex_search_texts.argtypes = [vp, vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p), c_i32, vp, vp]
+        L.bertx_mvindex_search_texts_colbert.restype = c_i32
+        L.bertx_mvindex_search_texts_colbert.argtypes = [vp, vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p), c_i32,
+                                                         c_i32, vp, vp]
+        L.bertx_bench_maxsim_search.restype = c_i32
+        L.bertx_bench_maxsim_search.argtypes = [c_i32] * 8 + [c_f32p]
     except AttributeError:
         pass
     try:   # (ColBERT checkpoints: the projection record and its entries; absent from older BERT_LIB builds)
@@ -787,6 +798,45 @@ class BertTokenIndex:
         if rc != 0:
             raise RuntimeError("bertx_mvindex_score_text%s failed (%d)" % ("_colbert" if colbert is not None else "", rc))
         return out
+
+    def search(self, queries, k):
+        """(scores f32 [B][k], ids i32 [B][k]): per query the k best documents of the whole
+        store by MaxSim score, best first, equal scores by ascending id, (-inf, -1) where the
+        store has fewer than k documents; the scores are the bits of score().  queries: one
+        [Lq][width] array or a list of them; a ragged list is padded with zero rows to the
+        longest (a zero row adds +0).  At most 64 rows per query."""
+        if isinstance(queries, np.ndarray) and queries.ndim <= 2:
+            queries = [queries]
+        qs = [self._tokens(q) for q in queries]
+        if not qs:
+            raise ValueError("no queries")
+        Lq = max(len(q) for q in qs)
+        if Lq < 1 or Lq > self.MAX_QUERY_TOKENS:
+            raise ValueError("a query has %d rows, the limits are 1 .. %d" % (Lq, self.MAX_QUERY_TOKENS))
+        q = np.zeros((len(qs), Lq, self.dim), np.float32)
+        for i, a in enumerate(qs):
+            q[i, :len(a)] = a
+        scores = np.zeros((len(qs), k), np.float32)
+        ids = np.zeros((len(qs), k), np.int32)
+        rc = self.lib.bertx_mvindex_search(self.mv, q.ctypes.data, len(qs), Lq, k, scores.ctypes.data, ids.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_mvindex_search failed (%d)" % rc)
+        return scores, ids
+
+    def search_texts(self, texts, k, colbert=None):
+        """search() of the texts as queries; colbert=query_maxlen as in score_text."""
+        scores = np.zeros((len(texts), k), np.float32)
+        ids = np.zeros((len(texts), k), np.int32)
+        if colbert is not None:
+            rc = self.lib.bertx_mvindex_search_texts_colbert(self.mv, self.model.ctx, self.model.N_THREADS, len(texts),
+                                                             BertIndex._texts(texts), colbert, k, scores.ctypes.data,
+                                                             ids.ctypes.data)
+        else:
+            rc = self.lib.bertx_mvindex_search_texts(self.mv, self.model.ctx, self.model.N_THREADS, len(texts),
+                                                     BertIndex._texts(texts), k, scores.ctypes.data, ids.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_mvindex_search_texts%s failed (%d)" % ("_colbert" if colbert is not None else "", rc))
+        return scores, ids
 
     def rerank(self, query, ids, top_k=None):
         """(ids, scores) of the candidates by descending MaxSim score, equal scores by

@@ -267,6 +267,20 @@ int launch_mv_pack_i8(const float *d_rows, int64_t t0, int64_t count, int w, con
                       const void *d_table, int n_new, void *store, float *scales, hipStream_t s);
 int launch_maxsim_i8(const void *store, const float *scales, const void *d_table, int n_docs, int w, const float *d_q,
                      int Lq, const int32_t *d_ids, int n, float *d_out, hipStream_t s);
+// The full scan (maxsim_search.hip): d_scores f32 [B][k], d_ids i32 [B][k] = per query the
+// k best documents of all n_docs by the scorers' score, bit for bit, best first, equal
+// scores by ascending id, (-inf, -1) where the store has fewer than k documents.  d_q f32
+// [B][Lq][w]: B queries of exactly Lq rows (an all-zero row adds +0, as a query index
+// >= Lq does).  used_groups: the store's used token slots / 16; the documents lie
+// contiguous from group 0 in id order.  floor(4 / ceil(Lq / 16)) queries share one pass
+// over the store; per pass one streaming kernel and one or two selection kernels.  scratch:
+// maxsim_search_scratch_bytes() (sized by the current device's CU count and k = 128).
+// 1 <= Lq <= 64, 1 <= k <= 128, B >= 1; -1 otherwise (nothing launched), -3: launch refused.
+int maxsim_search_prepare_device();
+size_t maxsim_search_scratch_bytes();
+int launch_maxsim_search(const void *store, const float *scales, int storage, const void *d_table, int n_docs,
+                         int64_t used_groups, int w, const float *d_q, int B, int Lq, int k, void *scratch,
+                         float *d_scores, int32_t *d_ids, hipStream_t s);
 
 // ---- the classification head (head.hip): pooler dense + tanh + classifier on the
 // sentences' [CLS] rows, all f32, one form for the three chains ----

@@ -19,6 +19,7 @@
 // query and the document's own rows only, bit for bit.
 #include "device_common.h"
 #include "kernels.h"
+#include "maxsim_pack.h"
 
 #include <algorithm>
 
@@ -28,46 +29,6 @@ namespace {
 constexpr int kThreads = 256;      // 4 waves, each scores whole documents on its own
 constexpr int kRingUnits = 4;      // prefetch ring per wave: 4 units of 2 blocks = 8 KiB in flight
 constexpr int kLdsBudget = 160 * 1024;
-
-// One wave normalises row x f32 [w]: lane l takes the 8-element chunks l and l + 64
-// (w / 8 <= 128 chunks).  Sum of squares: each lane adds its chunks' squares in element
-// order into one f32 (lanes without a chunk hold 0), then the xor butterfly of
-// wave_sum; the order depends on w only.  out[j] = chunk l + 64 j as f16, zeros for a
-// chunk the row does not have and for a row whose sum of squares is 0.
-__device__ __forceinline__ void pack_row_f16(const float *__restrict__ x, int w, int lane, h16x8 (&out)[2])
-{
-    const int chunks = w >> 3;
-    float v[2][8];
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int c = lane + 64 * j;
-        float4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
-        if (c < chunks) {
-            a = *(const float4 *)(x + 8 * c);
-            b = *(const float4 *)(x + 8 * c + 4);
-        }
-        v[j][0] = a.x; v[j][1] = a.y; v[j][2] = a.z; v[j][3] = a.w;
-        v[j][4] = b.x; v[j][5] = b.y; v[j][6] = b.z; v[j][7] = b.w;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ss = __fadd_rn(ss, __fmul_rn(v[j][i], v[j][i]));
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) ss = __fadd_rn(ss, __shfl_xor(ss, o, 64));
-    const float rinv = ss > 0.f ? __fdiv_rn(1.0f, __fsqrt_rn(ss)) : 0.f;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) out[j][i] = ss > 0.f ? (h16)__fmul_rn(v[j][i], rinv) : (h16)0.0f;
-}
-
-// Where chunk c (elements 8c .. 8c + 7) of row `row` sits in an image of KB = w / 32
-// blocks per group, in h16x8 units: the A fragment of a stored row and the B fragment
-// of a query alike.
-__device__ __forceinline__ size_t frag_index(int64_t row, int c, int KB)
-{
-    return (size_t)((row >> 4) * KB + (c >> 2)) * 64 + 16 * (c & 3) + (int)(row & 15);
-}
 
 // Source rows t0 .. t0 + count - 1 of one add call (rows = row t0) into their slots; one
 // wave per row.  src_off[i] (i < n_new, ascending, src_off[0] = 0) is the first source

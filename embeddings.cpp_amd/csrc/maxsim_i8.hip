@@ -17,6 +17,7 @@
 // order of maxsim_kernel.  No step depends on an order the caller cannot reproduce.
 #include "device_common.h"
 #include "kernels.h"
+#include "maxsim_pack.h"
 #include "quant_i8.h"
 
 #include <algorithm>
@@ -27,37 +28,6 @@ namespace {
 constexpr int kThreads = 256;      // 4 waves, each scores whole documents on its own
 constexpr int kRingUnits = 8;      // prefetch ring per wave: 8 units of 1 block = 8 KiB in flight
 constexpr int kLdsBudget = 160 * 1024;
-
-// u of a quantized row, the lanes' bytes in v.  n2: each lane adds the squares of its 16
-// bytes (v_dot4_i32_i8), wave_sum_i32 adds the lanes; integer sums, so the order is
-// immaterial.
-__device__ __forceinline__ float unit_scale_i8(i32x4 v)
-{
-    int n2 = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) n2 = __builtin_amdgcn_sdot4(v[i], v[i], n2, false);   // four signed bytes each
-    n2 = wave_sum_i32(n2);
-    // sqrtf, not __fsqrt_rn: the intrinsic is the hardware's approximate root in this toolchain
-    return n2 > 0 ? __fdiv_rn(1.0f, sqrtf((float)n2)) : 0.f;
-}
-
-// One wave packs row x f32 [w]: lane c < w / 16 gets bytes 16c .. 16c + 15 (the other
-// lanes zeros), every lane gets u.
-__device__ __forceinline__ i32x4 pack_row_i8(const float *__restrict__ x, int w, int lane, float &u)
-{
-    float scale;
-    const i32x4 v = quantize_row_i8(x, w, lane, scale);
-    u = unit_scale_i8(v);
-    return v;
-}
-
-// Where chunk c (bytes 16c .. 16c + 15) of row `row` sits in an image of KB = w / 64
-// blocks per group, in i32x4 units: the A fragment of a stored row and the B fragment of
-// a query alike.
-__device__ __forceinline__ size_t frag_index(int64_t row, int c, int KB)
-{
-    return (size_t)((row >> 4) * KB + (c >> 2)) * 64 + 16 * (c & 3) + (int)(row & 15);
-}
 
 // mv_pack_kernel over an int8 store: the same (src_off, table) lookup, one wave per row.
 __global__ __launch_bounds__(kThreads) void mv_pack_i8_kernel(const float *__restrict__ rows, int64_t t0, int64_t count,

@@ -34,6 +34,7 @@ struct bertx_mvindex {
     // staging of the host forms
     float *st_rows = nullptr, *st_q = nullptr, *st_out = nullptr;
     int32_t *st_ids = nullptr, *st_tok = nullptr;
+    void *search_scratch = nullptr;        // the partial lists of the full-scan search (maxsim_search_scratch_bytes)
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;             // completion of the last device operation on the store
     hipStream_t last_stream = nullptr;
@@ -45,7 +46,7 @@ struct bertx_mvindex {
         if (stream) (void)hipStreamSynchronize(stream);
         if (any && done) (void)hipEventSynchronize(done);
         for (void *p : {store, (void *)scales, (void *)table, (void *)src_off, (void *)st_rows, (void *)st_q, (void *)st_out,
-                        (void *)st_ids, (void *)st_tok})
+                        (void *)st_ids, (void *)st_tok, search_scratch})
             if (p) (void)hipFree(p);
         if (h_table) (void)hipHostFree(h_table);
         if (h_src) (void)hipHostFree(h_src);
@@ -60,6 +61,8 @@ namespace {
 constexpr int kStageRows = 2048;    // token rows per staged chunk of the host add
 constexpr int kStageIds = 65536;    // candidates per staged chunk of the host score
 constexpr int kMaxLq = 64;
+constexpr int kMaxK = 128;
+constexpr int kSearchTexts = 1024;  // queries per forward of the search text forms (at most 2^16 tokens)
 constexpr int64_t kChunkTokens = 1 << 17;   // per device forward of add_texts, as run_forward chunks
 constexpr int kChunkSeqs = 4096;
 
@@ -178,6 +181,22 @@ int32_t score_device_locked(bertx_mvindex &mv, const float *d_q, int32_t Lq, con
     return launch_maxsim(mv.store, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s);
 }
 
+bool search_args_ok(const char *who, int32_t B, int32_t Lq, int32_t k)
+{
+    if (B >= 1 && Lq >= 1 && Lq <= kMaxLq && k >= 1 && k <= kMaxK) return true;
+    errorf("%s: B = %d, Lq = %d, k = %d are not in B >= 1, 1 <= Lq <= %d, 1 <= k <= %d\n", who, B, Lq, k, kMaxLq, kMaxK);
+    return false;
+}
+
+int32_t search_device_locked(bertx_mvindex &mv, const float *d_q, int32_t B, int32_t Lq, int32_t k, float *d_scores,
+                             int32_t *d_ids, hipStream_t s)
+{
+    if (!d_q || !d_scores || !d_ids || !search_args_ok("bertx_mvindex_search", B, Lq, k)) return -1;
+    Ordered o(mv, s);
+    return launch_maxsim_search(mv.store, mv.scales, mv.storage, mv.table, (int)mv.n_docs, mv.used_slots / 16, mv.w, d_q, B,
+                                Lq, k, mv.search_scratch, d_scores, d_ids, s);
+}
+
 // The query already on the device (mv.st_q or a caller's buffer on the store's stream):
 // scores of the host ids (or of all documents) into the host out, which is written
 // only when every chunk succeeded.
@@ -253,6 +272,24 @@ struct DevBuf {
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
+// B queries f32 [B][Lq][w] already on the device, on the store's stream: their results
+// into host vectors (the caller copies them out when the whole call succeeded).
+int32_t search_to_host(bertx_mvindex &mv, const float *d_q, int32_t B, int32_t Lq, int32_t k, float *scores, int32_t *ids)
+{
+    DevBuf d_s, d_i;
+    HIP_RC(hipMalloc(&d_s.p, (size_t)B * k * 4));
+    HIP_RC(hipMalloc(&d_i.p, (size_t)B * k * 4));
+    const int32_t rc = search_device_locked(mv, d_q, B, Lq, k, (float *)d_s.p, (int32_t *)d_i.p, mv.stream);
+    if (rc != 0) {
+        (void)hipStreamSynchronize(mv.stream);
+        return rc;
+    }
+    HIP_RC(hipMemcpyAsync(scores, d_s.p, (size_t)B * k * 4, hipMemcpyDeviceToHost, mv.stream));
+    HIP_RC(hipMemcpyAsync(ids, d_i.p, (size_t)B * k * 4, hipMemcpyDeviceToHost, mv.stream));
+    HIP_RC(hipStreamSynchronize(mv.stream));
+    return 0;
+}
+
 // The refusals of the ColBERT text forms: -6 a file without the projection record, -1 a
 // store of another width than the projected rows', then as text_ctx_ok.
 int32_t colbert_ctx_ok(bertx_mvindex *mv, struct bert_ctx *ctx, const char *who, int32_t *slot)
@@ -307,7 +344,8 @@ bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t c
     const size_t slots16 = (size_t)((cap_slots + 15) / 16) * 16;
     const bool i8 = storage == BERTX_INDEX_I8;
     const size_t store_bytes = slots16 * (size_t)w * (i8 ? 1 : 2);
-    const bool ok = maxsim_prepare_device() == 0 &&
+    const bool ok = maxsim_prepare_device() == 0 && maxsim_search_prepare_device() == 0 &&
+                    hipMalloc(&mv->search_scratch, maxsim_search_scratch_bytes()) == hipSuccess &&
                     hipStreamCreateWithFlags(&mv->stream, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&mv->done, hipEventDisableTiming) == hipSuccess &&
                     hipMalloc(&mv->store, store_bytes) == hipSuccess &&
@@ -790,13 +828,197 @@ int32_t bertx_mvindex_score_text_colbert(struct bertx_mvindex *mv, struct bert_c
     }
 }
 
-// MaxSim micro-benchmark (bert_hip.h): device 0, no context.
-int32_t bertx_bench_maxsim_ex(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t storage,
-                              int32_t iters, float *avg_us)
+int32_t bertx_mvindex_search_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq, int32_t k,
+                                    float *d_scores, int32_t *d_ids, void *stream)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    return emb::search_device_locked(*mv, d_q, B, Lq, k, d_scores, d_ids, stream ? (hipStream_t)stream : mv->stream);
+}
+
+int32_t bertx_mvindex_search(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t k, float *scores,
+                             int32_t *ids)
+{
+    if (!mv || !q || !scores || !ids || !emb::search_args_ok("bertx_mvindex_search", B, Lq, k)) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    try {
+        const size_t nq = (size_t)B * Lq * mv->w, nr = (size_t)B * k;
+        std::vector<float> hs(nr);
+        std::vector<int32_t> hi(nr);
+        emb::DevBuf d_q;
+        HIP_RC(hipMalloc(&d_q.p, nq * 4));
+        HIP_RC(hipMemcpyAsync(d_q.p, q, nq * 4, hipMemcpyHostToDevice, mv->stream));
+        const int32_t rc = emb::search_to_host(*mv, (const float *)d_q.p, B, Lq, k, hs.data(), hi.data());
+        if (rc != 0) return rc;
+        std::memcpy(scores, hs.data(), nr * 4);
+        std::memcpy(ids, hi.data(), nr * 4);
+        return 0;
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_mvindex_search: out of host memory\n");
+        return -1;
+    }
+}
+
+int32_t bertx_mvindex_search_texts(struct bertx_mvindex *mv, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                   const char **texts, int32_t k, float *scores, int32_t *ids)
+{
+    int32_t slot = -1;
+    if (!texts || !scores || !ids || n < 1) return -1;
+    if (emb::text_ctx_ok(mv, ctx, "bertx_mvindex_search_texts", &slot) != 0) return -1;
+    if (!emb::search_args_ok("bertx_mvindex_search_texts", n, 1, k)) return -1;
+    try {
+        const int32_t n_max = bert_n_max_tokens(ctx), lim = std::min<int32_t>(n_max, emb::kMaxLq);
+        const int w = mv->w;
+        std::vector<int32_t> tok((size_t)n * n_max), lens((size_t)n);
+        if (bertx_tokenize_batch(ctx, n_threads, n, texts, n_max, tok.data(), lens.data()) != 0) return -1;
+        for (int32_t i = 0; i < n; ++i) {
+            if (lens[(size_t)i] > lim) {
+                emb::errorf("bertx_mvindex_search_texts: query %d has %d tokens, maximum is %d\n", i, lens[(size_t)i], lim);
+                return -4;
+            }
+            if (lens[(size_t)i] < 1) return -1;
+        }
+        std::vector<float> hs((size_t)n * k);
+        std::vector<int32_t> hi((size_t)n * k), flat, cu;
+        std::lock_guard<std::mutex> lk(mv->mu);
+        DeviceGuard g(mv->ordinal);
+        HIP_RC(g.status());
+        const int32_t cap = std::min<int32_t>(n, emb::kSearchTexts);
+        emb::DevBuf d_tok, d_cu, d_rows, d_q;
+        HIP_RC(hipMalloc(&d_tok.p, (size_t)cap * emb::kMaxLq * 4));
+        HIP_RC(hipMalloc(&d_cu.p, (size_t)(cap + 1) * 4));
+        HIP_RC(hipMalloc(&d_rows.p, (size_t)cap * emb::kMaxLq * w * 4));
+        HIP_RC(hipMalloc(&d_q.p, (size_t)cap * emb::kMaxLq * w * 4));
+        // chunks of whole queries: one per-token forward, the rows laid out [m][Lmax][w] with
+        // zero rows behind the shorter queries (device-to-device), then the search
+        for (int32_t i0 = 0; i0 < n; i0 += cap) {
+            const int32_t m = std::min(cap, n - i0);
+            flat.clear();
+            cu.assign(1, 0);
+            int32_t Lmax = 0;
+            for (int32_t i = i0; i < i0 + m; ++i) {
+                const int32_t *p = tok.data() + (size_t)i * n_max;
+                flat.insert(flat.end(), p, p + lens[(size_t)i]);
+                cu.push_back((int32_t)flat.size());
+                Lmax = std::max(Lmax, lens[(size_t)i]);
+            }
+            const int32_t T = (int32_t)flat.size();
+            if (bertx_reserve(ctx, slot, T, m) != 0) return -1;
+            int32_t rc = 0;
+            {
+                emb::Ordered o(*mv, mv->stream);
+                HIP_RC(hipMemcpyAsync(d_tok.p, flat.data(), (size_t)T * 4, hipMemcpyHostToDevice, mv->stream));
+                HIP_RC(hipMemcpyAsync(d_cu.p, cu.data(), (size_t)(m + 1) * 4, hipMemcpyHostToDevice, mv->stream));
+                rc = bertx_forward_tokens_device(ctx, slot, (const int32_t *)d_tok.p, (const int32_t *)d_cu.p, m, Lmax, T,
+                                                 (float *)d_rows.p, mv->stream);
+                if (rc == 0) {
+                    HIP_RC(hipMemsetAsync(d_q.p, 0, (size_t)m * Lmax * w * 4, mv->stream));
+                    for (int32_t j = 0; j < m; ++j)
+                        HIP_RC(hipMemcpyAsync((float *)d_q.p + (size_t)j * Lmax * w, (const float *)d_rows.p + (size_t)cu[(size_t)j] * w,
+                                              (size_t)lens[(size_t)(i0 + j)] * w * 4, hipMemcpyDeviceToDevice, mv->stream));
+                }
+            }
+            if (rc == 0)
+                rc = emb::search_to_host(*mv, (const float *)d_q.p, m, Lmax, k, hs.data() + (size_t)i0 * k,
+                                         hi.data() + (size_t)i0 * k);
+            if (rc != 0) {
+                (void)hipGetLastError();
+                (void)hipStreamSynchronize(mv->stream);
+                return rc < 0 ? rc : -1;
+            }
+        }
+        std::memcpy(scores, hs.data(), hs.size() * 4);
+        std::memcpy(ids, hi.data(), hi.size() * 4);
+        return 0;
+    } catch (const std::exception &ex) {
+        emb::errorf("bertx_mvindex_search_texts: %s\n", ex.what());
+        return -1;
+    }
+}
+
+int32_t bertx_mvindex_search_texts_colbert(struct bertx_mvindex *mv, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                           const char **texts, int32_t query_maxlen, int32_t k, float *scores,
+                                           int32_t *ids)
+{
+    int32_t slot = -1;
+    if (!texts || !scores || !ids || n < 1) return -1;
+    if (const int32_t rc = emb::colbert_ctx_ok(mv, ctx, "bertx_mvindex_search_texts_colbert", &slot)) return rc;
+    if (query_maxlen < 4 || query_maxlen > emb::kMaxLq || query_maxlen > bert_n_max_tokens(ctx)) return -1;
+    if (!emb::search_args_ok("bertx_mvindex_search_texts_colbert", n, query_maxlen, k)) return -1;
+    for (int32_t i = 0; i < n; ++i)
+        if (!texts[i]) return -1;
+    try {
+        // every augmented query has L = query_maxlen tokens, all kept: the projector's output
+        // is the [n][L][w] layout itself
+        const size_t L = (size_t)query_maxlen;
+        const int w = mv->w;
+        std::vector<int32_t> tok((size_t)n * L), lens((size_t)n), rcs((size_t)n, 0);
+        emb::TaskPool::instance().run(((int64_t)n + 7) / 8, n_threads > 0 ? n_threads : 1, [&](int64_t blk) {
+            const int e = (int)std::min<int64_t>(n, 8 * blk + 8);
+            std::vector<int32_t> keep(L);
+            for (int i = (int)(8 * blk); i < e; ++i)
+                rcs[(size_t)i] = bertx_tokenize_colbert(ctx, texts[i], 0, query_maxlen, tok.data() + i * L, keep.data(),
+                                                        &lens[(size_t)i]);
+        });
+        for (int32_t i = 0; i < n; ++i)
+            if (rcs[(size_t)i] != 0 || lens[(size_t)i] != query_maxlen) return -1;
+        std::vector<float> hs((size_t)n * k);
+        std::vector<int32_t> hi((size_t)n * k), cu;
+        std::lock_guard<std::mutex> lk(mv->mu);
+        DeviceGuard g(mv->ordinal);
+        HIP_RC(g.status());
+        const int32_t cap = std::min<int32_t>(n, emb::kSearchTexts);
+        emb::DevBuf d_tok, d_cu, d_q;
+        HIP_RC(hipMalloc(&d_tok.p, (size_t)cap * L * 4));
+        HIP_RC(hipMalloc(&d_cu.p, (size_t)(cap + 1) * 4));
+        HIP_RC(hipMalloc(&d_q.p, (size_t)cap * L * w * 4));
+        cu.resize((size_t)cap + 1);
+        for (int32_t j = 0; j <= cap; ++j) cu[(size_t)j] = j * query_maxlen;
+        for (int32_t i0 = 0; i0 < n; i0 += cap) {
+            const int32_t m = std::min(cap, n - i0), T = m * query_maxlen;
+            if (bertx_reserve(ctx, slot, T, m) != 0) return -1;
+            int32_t rc = 0;
+            {
+                emb::Ordered o(*mv, mv->stream);
+                HIP_RC(hipMemcpyAsync(d_tok.p, tok.data() + (size_t)i0 * L, (size_t)T * 4, hipMemcpyHostToDevice, mv->stream));
+                HIP_RC(hipMemcpyAsync(d_cu.p, cu.data(), (size_t)(m + 1) * 4, hipMemcpyHostToDevice, mv->stream));
+                rc = bertx_forward_project_device(ctx, slot, (const int32_t *)d_tok.p, nullptr, (const int32_t *)d_cu.p, m,
+                                                  query_maxlen, T, nullptr, 0, (float *)d_q.p, mv->stream);
+            }
+            if (rc == 0)
+                rc = emb::search_to_host(*mv, (const float *)d_q.p, m, query_maxlen, k, hs.data() + (size_t)i0 * k,
+                                         hi.data() + (size_t)i0 * k);
+            if (rc != 0) {
+                (void)hipGetLastError();
+                (void)hipStreamSynchronize(mv->stream);
+                return rc < 0 ? rc : -1;
+            }
+        }
+        std::memcpy(scores, hs.data(), hs.size() * 4);
+        std::memcpy(ids, hi.data(), hi.size() * 4);
+        return 0;
+    } catch (const std::exception &ex) {
+        emb::errorf("bertx_mvindex_search_texts_colbert: %s\n", ex.what());
+        return -1;
+    }
+}
+
+}  // extern "C"
+
+// The MaxSim micro-benchmarks (bert_hip.h): device 0, no context.  B == 0: the scorer over
+// n_cand candidates; B >= 1: the full-scan search of B queries for the k best.
+static int32_t bench_store(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t B, int32_t k,
+                           int32_t storage, int32_t iters, float *avg_us)
 {
     using namespace emb;
     if (n_docs < 1 || doc_len < 0 || doc_len > 4096 || n_cand < 1 || iters < 1 || !avg_us || hip_device_count() == 0)
         return -1;
+    if (B > 0 && !search_args_ok("bertx_bench_maxsim_search", B, Lq, k)) return -1;
+    const int32_t nq = std::max(B, 1);
     try {
         // ragged (doc_len 0): 16 .. 512 tokens by a hash of the id
         std::vector<int32_t> lens((size_t)n_docs), ids((size_t)n_cand);
@@ -814,7 +1036,7 @@ int32_t bertx_bench_maxsim_ex(int32_t w, int32_t n_docs, int32_t doc_len, int32_
             bertx_mvindex *mv = nullptr;
             hipStream_t s = nullptr;
             hipEvent_t a = nullptr, b = nullptr;
-            DevBuf rows, q, id, out;
+            DevBuf rows, q, id, out, oid;
             ~Holder()
             {
                 if (s) (void)hipStreamSynchronize(s);
@@ -831,9 +1053,10 @@ int32_t bertx_bench_maxsim_ex(int32_t w, int32_t n_docs, int32_t doc_len, int32_
         HIP_RC(hipEventCreate(&H.b));
         constexpr int64_t kFillRows = 1 << 18;
         HIP_RC(hipMalloc(&H.rows.p, (size_t)(kFillRows + 4096) * w * 4));
-        HIP_RC(hipMalloc(&H.q.p, (size_t)kMaxLq * w * 4));
+        HIP_RC(hipMalloc(&H.q.p, (size_t)nq * kMaxLq * w * 4));
         HIP_RC(hipMalloc(&H.id.p, (size_t)n_cand * 4));
-        HIP_RC(hipMalloc(&H.out.p, (size_t)n_cand * 4));
+        HIP_RC(hipMalloc(&H.out.p, (size_t)std::max(n_cand, nq * kMaxK) * 4));
+        HIP_RC(hipMalloc(&H.oid.p, (size_t)nq * kMaxK * 4));
         for (int32_t i = 0; i < n_docs;) {
             int32_t j = i;
             int64_t rows = 0;
@@ -843,10 +1066,13 @@ int32_t bertx_bench_maxsim_ex(int32_t w, int32_t n_docs, int32_t doc_len, int32_
             HIP_RC(hipStreamSynchronize(H.s));   // the fill buffer is reused
             i = j;
         }
-        if (Lq < 1 || Lq > kMaxLq || launch_unit_rows((float *)H.q.p, Lq, w, 777u, H.s) != 0) return -1;
+        if (Lq < 1 || Lq > kMaxLq || launch_unit_rows((float *)H.q.p, (int64_t)nq * Lq, w, 777u, H.s) != 0) return -1;
         HIP_RC(hipMemcpyAsync(H.id.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, H.s));
         HIP_RC(hipStreamSynchronize(H.s));
         auto run = [&] {
+            if (B > 0)
+                return bertx_mvindex_search_device(H.mv, (const float *)H.q.p, B, Lq, k, (float *)H.out.p,
+                                                   (int32_t *)H.oid.p, H.s);
             return bertx_mvindex_score_device(H.mv, (const float *)H.q.p, Lq, (const int32_t *)H.id.p, n_cand,
                                               (float *)H.out.p, H.s);
         };
@@ -865,6 +1091,21 @@ int32_t bertx_bench_maxsim_ex(int32_t w, int32_t n_docs, int32_t doc_len, int32_
         emb::errorf("bertx_bench_maxsim: %s\n", ex.what());
         return -1;
     }
+}
+
+extern "C" {
+
+int32_t bertx_bench_maxsim_ex(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t storage,
+                              int32_t iters, float *avg_us)
+{
+    return bench_store(w, n_docs, doc_len, Lq, n_cand, 0, 0, storage, iters, avg_us);
+}
+
+int32_t bertx_bench_maxsim_search(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t B, int32_t k,
+                                  int32_t storage, int32_t iters, float *avg_us)
+{
+    if (B < 1) return -1;
+    return bench_store(w, n_docs, doc_len, Lq, 1, B, k, storage, iters, avg_us);
 }
 
 int32_t bertx_bench_maxsim(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t iters,

@@ -3,7 +3,7 @@
 // the GPU and the search fused there (bertx_index_*).
 //
 // usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8]
-//               [-r RERANK_MODEL [-c N] | -l [-c N] | -L COLBERT_MODEL [-c N]] [-S f16|int8]
+//               [-r RERANK_MODEL [-c N] | -l [-c N | -a] | -L COLBERT_MODEL [-c N | -a]] [-S f16|int8]
 // One text per line of CORPUS.txt; queries from stdin, one per line, `q` or EOF ends.
 // Per hit one line: rank<TAB>id<TAB>score<TAB>text.
 // -s: how the index stores its rows (bertx_index_create_ex): f16, the default, or int8
@@ -22,6 +22,11 @@
 // punctuation rows dropped, doc_maxlen 180 capped at the model's n_max_tokens); the
 // candidates are re-scored with bertx_mvindex_score_text_colbert ([Q] marker, [MASK]
 // augmentation to query_maxlen 32).
+// -a: with -l or -L, full-scan late interaction: no embedding index is created or
+// consulted; every query goes through bertx_mvindex_search_texts (-l) or
+// bertx_mvindex_search_texts_colbert (-L), which score every stored document by MaxSim
+// on the GPU and keep the k best there.  The printed score is the MaxSim score.  -a
+// without -l or -L, or together with -c or -r, is a usage error.
 // -S: with -l or -L, how the token store keeps its rows (bertx_mvindex_create_ex): f16,
 // the default, or int8 with one f32 per token, half the bytes and a less precise
 // similarity.  -s still speaks of the index alone.
@@ -41,7 +46,7 @@ int main(int argc, char **argv)
 {
     const char *model = nullptr, *corpus = nullptr, *rerank = nullptr, *colbert = nullptr;
     int k = 3, threads = 4, cand = 0, storage = BERTX_INDEX_F16, mv_storage = -1;
-    bool late = false;
+    bool late = false, all = false;
     for (int i = 1; i < argc; ++i) {
         const bool has = i + 1 < argc;
         if (!std::strcmp(argv[i], "-m") && has) model = argv[++i];
@@ -55,15 +60,17 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "-r") && has) rerank = argv[++i];
         else if (!std::strcmp(argv[i], "-c") && has) cand = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "-l")) late = true;
+        else if (!std::strcmp(argv[i], "-a")) all = true;
         else if (!std::strcmp(argv[i], "-L") && has) colbert = argv[++i];
         else { model = nullptr; break; }
     }
     const bool second = rerank || late || colbert;
-    if (second && cand == 0) cand = std::min(128, 4 * k);
-    if (!model || !corpus || k < 1 || k > 128 || threads < 1 || (int)(rerank != nullptr) + late + (colbert != nullptr) > 1 ||
-        (second ? cand < k || cand > 128 : cand != 0) || (mv_storage >= 0 && !late && !colbert)) {
+    const bool bad_all = all && ((!late && !colbert) || cand != 0);
+    if (second && !all && cand == 0) cand = std::min(128, 4 * k);
+    if (bad_all || !model || !corpus || k < 1 || k > 128 || threads < 1 || (int)(rerank != nullptr) + late + (colbert != nullptr) > 1 ||
+        (second && !all ? cand < k || cand > 128 : cand != 0) || (mv_storage >= 0 && !late && !colbert)) {
         std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads] [-s f16|int8] "
-                             "[-r RERANK_MODEL [-c N (k..128, default 4 k)] | -l [-c N] | -L COLBERT_MODEL [-c N]] "
+                             "[-r RERANK_MODEL [-c N (k..128, default 4 k)] | -l [-c N | -a] | -L COLBERT_MODEL [-c N | -a]] "
                              "[-S f16|int8 (the token store of -l / -L)]\n",
                      argv[0]);
         return 2;
@@ -113,8 +120,8 @@ int main(int argc, char **argv)
         query_maxlen = std::min<int32_t>(32, bert_n_max_tokens(rctx));
     }
     if (mv_storage < 0) mv_storage = BERTX_INDEX_F16;
-    bertx_index *idx = bertx_index_create_ex(ctx, 0, (int32_t)texts.size(), storage);
-    if (!idx) {
+    bertx_index *idx = all ? nullptr : bertx_index_create_ex(ctx, 0, (int32_t)texts.size(), storage);
+    if (!idx && !all) {
         if (rctx) bert_free(rctx);
         bert_free(ctx);
         return 1;
@@ -153,7 +160,7 @@ int main(int argc, char **argv)
     for (size_t i = 0; i < texts.size() && rc == 0; i += 256) {
         std::vector<const char *> p;
         for (size_t j = i; j < texts.size() && j < i + 256; ++j) p.push_back(texts[j].c_str());
-        if (bertx_index_add_texts(idx, ctx, threads, (int32_t)p.size(), p.data()) < 0) {
+        if (idx && bertx_index_add_texts(idx, ctx, threads, (int32_t)p.size(), p.data()) < 0) {
             std::fprintf(stderr, "search: indexing failed at text %zu\n", i);
             rc = 1;
         } else if (mv && (colbert ? bertx_mvindex_add_texts_colbert(mv, rctx, threads, (int32_t)p.size(), p.data(), doc_maxlen)
@@ -162,7 +169,7 @@ int main(int argc, char **argv)
             rc = 1;
         }
     }
-    const int kq = second ? cand : k;   // what the index is asked for
+    const int kq = second && !all ? cand : k;   // what the index (-a: the token store) is asked for
     std::vector<float> scores((size_t)kq);
     std::vector<int32_t> ids((size_t)kq);
     for (std::string q; rc == 0 && std::getline(std::cin, q);) {
@@ -170,6 +177,20 @@ int main(int argc, char **argv)
         if (q == "q") break;
         if (q.empty()) continue;
         const char *qp = q.c_str();
+        if (all) {
+            // the full scan: the k best of every stored document by MaxSim, selected on the GPU
+            if ((colbert ? bertx_mvindex_search_texts_colbert(mv, rctx, threads, 1, &qp, query_maxlen, k, scores.data(),
+                                                              ids.data())
+                         : bertx_mvindex_search_texts(mv, ctx, threads, 1, &qp, k, scores.data(), ids.data())) != 0) {
+                std::fprintf(stderr, "search: late-interaction search failed\n");
+                rc = 1;
+                break;
+            }
+            for (int j = 0; j < k && ids[(size_t)j] >= 0; ++j)
+                std::printf("%d\t%d\t%.4f\t%s\n", j + 1, ids[(size_t)j], scores[(size_t)j], texts[(size_t)ids[(size_t)j]].c_str());
+            std::fflush(stdout);
+            continue;
+        }
         if (bertx_index_search_texts(idx, ctx, threads, 1, &qp, kq, scores.data(), ids.data()) != 0) {
             std::fprintf(stderr, "search: query failed\n");
             rc = 1;

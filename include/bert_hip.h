@@ -578,9 +578,42 @@ BERT_API int32_t bertx_index_search_texts(struct bertx_index *idx, struct bert_c
  * u float[len], or -1 on an f16 store or a bad id with the outputs untouched.
  * bertx_bench_maxsim_ex is bertx_bench_maxsim over a store of the given kind.
  *
- * Not provided: int8 queries against f16 rows; 4-bit or residual codes; a full-scan fused
- * top-k; several queries per call; sharding over GPUs; deleting, saving and loading.
- * (ColBERT checkpoints: "Projection" below.)
+ * Full-scan search: the k best documents of the whole store, several queries per call.
+ * bertx_mvindex_search / _search_device: q is float[B][Lq][width], B >= 1 queries of
+ * exactly Lq rows each, 1 <= Lq <= 64, 1 <= k <= 128; scores is float[B][k] and ids
+ * int32[B][k].  Per query the entries come best first, equal scores by ascending id; with
+ * fewer than k documents the remaining slots are (-inf, -1), so an empty store gives all
+ * fill.  score(query, doc) is, bit for bit, what bertx_mvindex_score returns for that
+ * query and document on the same store, f16 and int8 alike: it does not depend on the
+ * other queries of the call, B, k, the document count or where the document sits.
+ * A shorter query is padded by the caller with all-zero rows: a zero row normalises to
+ * zeros (u = 0 on an int8 store), its similarity to every stored row is +0, so it adds
+ * +0 to the sum exactly as a query index >= Lq does in the scorer, and the padded query's
+ * scores are the bits of the unpadded one's.  That is why one Lq per call suffices.
+ * Queries of ceil(Lq / 16) = 1, 2, 3, 4 tiles share one pass over the stored bytes 4, 2,
+ * 1, 1 at a time; a call runs ceil(B / that) passes.  A refusal (B, Lq or k out of range,
+ * a NULL pointer) returns -1 after a message with the outputs untouched.  The device form
+ * follows bertx_mvindex_score_device word for word: device pointers on the store's GPU
+ * and a hipStream_t (NULL: the store's own stream), asynchronous, ordered after the
+ * store's previous operation, allocating nothing (the partial lists, 128 pairs of 8 B
+ * for 4 queries and up to 1,024 + 32 lists = 4.1 MiB, belong to the store) and never synchronising,
+ * so it can be captured into a HIP graph; a captured search keeps the document count of
+ * its capture.  The host form stages through the store's stream.
+ * bertx_mvindex_search_texts: n queries tokenised as _score_text tokenises one, one
+ * batched per-token forward on the store's GPU per 1,024 queries, the rows laid out
+ * [n][Lmax][width] on the device with zero rows behind the shorter queries, then the
+ * search; needs what _score_text needs.  A query over 64 tokens (or over n_max_tokens)
+ * fails the whole call with -4 and the outputs untouched.
+ * bertx_mvindex_search_texts_colbert ("Projection" below): the same over the augmented
+ * queries of query_maxlen tokens each, through the projector; refusals as
+ * _score_text_colbert.
+ * bertx_bench_maxsim_search: the store of bertx_bench_maxsim_ex, B random queries of Lq
+ * rows; average device time of `iters` calls of bertx_mvindex_search_device after 3
+ * warm-up calls.
+ *
+ * Not provided: int8 queries against f16 rows; 4-bit or residual codes; candidate
+ * generation (centroids, pruning); per-query lengths on the device; sharding over GPUs;
+ * deleting, saving and loading.  (ColBERT checkpoints: "Projection" below.)
  */
 struct bertx_mvindex;
 BERT_API struct bertx_mvindex *bertx_mvindex_create(struct bert_ctx *ctx, int32_t slot, int32_t width,
@@ -614,6 +647,14 @@ BERT_API int32_t bertx_mvindex_score_text(struct bertx_mvindex *mv, struct bert_
                                           const int32_t *ids, int32_t n, float *out);
 BERT_API int32_t bertx_bench_maxsim(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand,
                                     int32_t iters, float *avg_us);
+BERT_API int32_t bertx_mvindex_search(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t k,
+                                      float *scores, int32_t *ids);
+BERT_API int32_t bertx_mvindex_search_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq, int32_t k,
+                                             float *d_scores, int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_mvindex_search_texts(struct bertx_mvindex *mv, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                            const char **texts, int32_t k, float *scores, int32_t *ids);
+BERT_API int32_t bertx_bench_maxsim_search(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t B, int32_t k,
+                                           int32_t storage, int32_t iters, float *avg_us);
 
 /*
  * Cross-encoder reranking: token types and a classification head.
@@ -784,7 +825,7 @@ BERT_API int32_t bertx_bench_search_add_rate_ex(int32_t d, int32_t N, int32_t st
  * Not provided: [MASK] rows excluded as attention keys (ColBERT's attend_to_mask_tokens
  * = false, the setting colbertv2.0 was trained with): here the augmentation rows are
  * ordinary tokens of the sentence; excluding them needs a key length separate from the
- * row count in the attention kernels.  A full-scan top-k, several queries per call.
+ * row count in the attention kernels.
  * (The ColBERT text forms follow the store's kind: an int8 store takes them unchanged.)
  */
 enum { BERTX_OUT_PROJ = 3 };
@@ -803,6 +844,9 @@ BERT_API int32_t bertx_mvindex_add_texts_colbert(struct bertx_mvindex *mv, struc
                                                  int32_t n, const char **texts, int32_t doc_maxlen);
 BERT_API int32_t bertx_mvindex_score_text_colbert(struct bertx_mvindex *mv, struct bert_ctx *ctx, const char *query,
                                                   int32_t query_maxlen, const int32_t *ids, int32_t n, float *out);
+BERT_API int32_t bertx_mvindex_search_texts_colbert(struct bertx_mvindex *mv, struct bert_ctx *ctx, int32_t n_threads,
+                                                    int32_t n, const char **texts, int32_t query_maxlen, int32_t k,
+                                                    float *scores, int32_t *ids);
 BERT_API int32_t bertx_test_project(int32_t mode, const void *src, const float *stats, const float *g, const float *b,
                                     int32_t T, int32_t d, const float *W, int32_t dim, const int32_t *rows,
                                     int32_t n_out, float *out, int32_t out_rows);
