@@ -283,6 +283,26 @@ def load_lib(path=None):
         L.bertx_bench_project.argtypes = [c_i32] * 4 + [c_f32p]
     except AttributeError:
         pass
+    try:   # (key counts: [MASK] rows that are not attention keys; absent from older BERT_LIB builds)
+        L.bertx_forward_device_kv.restype = c_i32
+        L.bertx_forward_device_kv.argtypes = [vp, c_i32, vp, vp, vp, vp, c_i32, c_i32, c_i32, c_i32, vp, c_i32, vp, vp]
+        for fn in (L.bertx_forward_tokens_kv, L.bertx_forward_project_kv):
+            fn.restype = c_i32
+            fn.argtypes = [vp, c_i32, ctypes.POINTER(c_i32p), c_i32p, c_i32p, ctypes.POINTER(c_f32p)]
+        L.bertx_tokenize_colbert_ex.restype = c_i32
+        L.bertx_tokenize_colbert_ex.argtypes = [vp, ctypes.c_char_p, c_i32, c_i32, vp, vp, c_i32p, c_i32p]
+        L.bertx_set_mask_keys.restype = c_i32
+        L.bertx_set_mask_keys.argtypes = [vp, c_i32]
+        L.bertx_mask_keys.restype = c_i32
+        L.bertx_mask_keys.argtypes = [vp]
+        L.bertx_test_attention_kv.restype = c_i32
+        L.bertx_test_attention_kv.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, c_i32, vp]
+        L.bertx_test_attention_f32_kv.restype = c_i32
+        L.bertx_test_attention_f32_kv.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, c_i32, c_i32, vp, c_i32]
+        L.bertx_bench_attention_kv.restype = c_i32
+        L.bertx_bench_attention_kv.argtypes = [c_i32] * 7 + [c_f32p]
+    except AttributeError:
+        pass
     L.bertx_bench_gemm.restype = c_i32
     L.bertx_bench_gemm.argtypes = [c_i32] * 7 + [c_f32p]
     L.bertx_bench_attention.restype = c_i32
@@ -356,7 +376,18 @@ class BertModel:
         """Whether CLS pooling runs the last layer on the sentences' first rows only (default on)."""
         self.lib.bertx_set_cls_pruning(self.ctx, 1 if on else 0)
 
-    def _forward_rows(self, fn, name, ids_list, width):
+    @property
+    def mask_keys(self):
+        """Whether the store's ColBERT query forms keep the [MASK] rows as attention keys (default True)."""
+        return bool(self.lib.bertx_mask_keys(self.ctx))
+
+    def set_mask_keys(self, on):
+        """False: score_text / search_texts with colbert= let no row attend to a query's [MASK] rows
+        (ColBERT's attend_to_mask_tokens = false); True: the [MASK] rows are ordinary keys."""
+        if self.lib.bertx_set_mask_keys(self.ctx, 1 if on else 0) != 0:
+            raise RuntimeError("bertx_set_mask_keys failed")
+
+    def _forward_rows(self, fn, name, ids_list, width, n_keys=None):
         n = len(ids_list)
         lens = np.fromiter((len(x) for x in ids_list), np.int32, n)
         flat = (np.concatenate(ids_list) if n else np.zeros(0)).astype(np.int32, copy=False)
@@ -367,14 +398,26 @@ class BertModel:
             np.cumsum(lens[:-1], out=offs[1:])
         tp = (flat.ctypes.data + 4 * offs).astype(np.uintp)
         op = (out.ctypes.data + out.strides[0] * offs).astype(np.uintp)
-        rc = fn(self.ctx, n, tp.ctypes.data_as(ctypes.POINTER(c_i32p)), _as_i32p(lens),
-                op.ctypes.data_as(ctypes.POINTER(c_f32p)))
+        if n_keys is None:
+            rc = fn(self.ctx, n, tp.ctypes.data_as(ctypes.POINTER(c_i32p)), _as_i32p(lens),
+                    op.ctypes.data_as(ctypes.POINTER(c_f32p)))
+        else:
+            keys = np.ascontiguousarray(n_keys, np.int32)
+            if keys.shape != (n,):
+                raise ValueError("n_keys must hold one count per sentence")
+            rc = fn(self.ctx, n, tp.ctypes.data_as(ctypes.POINTER(c_i32p)), _as_i32p(lens), _as_i32p(keys),
+                    op.ctypes.data_as(ctypes.POINTER(c_f32p)))
         if rc != 0:
             raise RuntimeError("%s failed (%d)" % (name, rc))
         return [out[int(o):int(o) + int(l)] for o, l in zip(offs, lens)]
 
-    def forward_tokens(self, ids_list):
-        """Per-token final hidden states (un-normalised): a list of [len][n_embd] f32 arrays."""
+    def forward_tokens(self, ids_list, n_keys=None):
+        """Per-token final hidden states (un-normalised): a list of [len][n_embd] f32 arrays.
+        n_keys: one count per sentence, 1 .. its length: only its first n_keys[i] rows are
+        attention keys (every row is still a query and an output row)."""
+        if n_keys is not None:
+            return self._forward_rows(self.lib.bertx_forward_tokens_kv, "bertx_forward_tokens_kv", ids_list, self.n_embd,
+                                      n_keys)
         return self._forward_rows(self.lib.bertx_forward_tokens, "bertx_forward_tokens", ids_list, self.n_embd)
 
     # -- ColBERT checkpoints: files with a linear.weight record --
@@ -388,19 +431,30 @@ class BertModel:
         """Width of every projected row, 64 ceil(proj_dim / 64): a legal BertTokenIndex width."""
         return int(self.lib.bertx_proj_width(self.ctx))
 
-    def tokenize_colbert(self, text, kind, maxlen):
+    def tokenize_colbert(self, text, kind, maxlen, with_keys=False):
         """(ids, keep) of a query ("query" / 0: [CLS] [Q] pieces [SEP] and [MASK] up to maxlen) or a
-        document ("doc" / 1: [CLS] [D] pieces [SEP], keep 0 on punctuation tokens)."""
+        document ("doc" / 1: [CLS] [D] pieces [SEP], keep 0 on punctuation tokens).  with_keys:
+        (ids, keep, n_keys), the count of rows up to and including [SEP] for a query, all for a document."""
         kind = {"query": 0, "doc": 1}.get(kind, kind)
         ids, keep, n = np.zeros(max(maxlen, 1), np.int32), np.zeros(max(maxlen, 1), np.int32), c_i32(0)
+        if with_keys:
+            nk = c_i32(0)
+            rc = self.lib.bertx_tokenize_colbert_ex(self.ctx, self._bytes(text), kind, maxlen, ids.ctypes.data,
+                                                    keep.ctypes.data, ctypes.byref(n), ctypes.byref(nk))
+            if rc != 0:
+                raise ValueError("bertx_tokenize_colbert_ex failed (%d)" % rc)
+            return ids[:n.value].copy(), keep[:n.value].copy(), int(nk.value)
         rc = self.lib.bertx_tokenize_colbert(self.ctx, self._bytes(text), kind, maxlen, ids.ctypes.data, keep.ctypes.data,
                                              ctypes.byref(n))
         if rc != 0:
             raise ValueError("bertx_tokenize_colbert failed (%d)" % rc)
         return ids[:n.value].copy(), keep[:n.value].copy()
 
-    def forward_project(self, ids_list):
-        """Per-token unit-length projected rows: a list of [len][proj_width] f32 arrays."""
+    def forward_project(self, ids_list, n_keys=None):
+        """Per-token unit-length projected rows: a list of [len][proj_width] f32 arrays; n_keys as forward_tokens."""
+        if n_keys is not None:
+            return self._forward_rows(self.lib.bertx_forward_project_kv, "bertx_forward_project_kv", ids_list,
+                                      self.proj_width, n_keys)
         return self._forward_rows(self.lib.bertx_forward_project, "bertx_forward_project", ids_list, self.proj_width)
 
     def encode(self, sentences, batch_size=16):
@@ -784,7 +838,8 @@ class BertTokenIndex:
         return out
 
     def score_text(self, query, ids=None, colbert=None):
-        """colbert=query_maxlen (at most 64): the query as a ColBERT query, [MASK]-augmented."""
+        """colbert=query_maxlen (at most 64): the query as a ColBERT query, [MASK]-augmented; whether its
+        [MASK] rows are attention keys follows the model's mask_keys setting (BertModel.set_mask_keys)."""
         ids = self._ids(ids)
         n, out = self._out(ids)
         if n == 0:

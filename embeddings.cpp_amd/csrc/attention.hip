@@ -17,6 +17,27 @@ namespace emb {
 // bits stays at their call sites: exp2f against the hardware exp2 (FAST), S
 // scaled in f32 against Q pre-scaled in f16, and which blocks are masked.
 // ---------------------------------------------------------------------------
+// ---------------------------------------------------------------------------
+// Key counts.  Every kernel here exists twice: KV = false is the plain form, all
+// of a sentence's rows its keys; KV = true reads keys[b], 1 <= keys[b] <= len,
+// the rows of sentence b that are keys and values (a ColBERT query's rows up to
+// [SEP]; the [MASK] rows behind them are queries only).  The count bounds the
+// mask, the K / V loads and the block loops; the sentence's length bounds the
+// query rows, the Q loads and the stores.  A compile-time variant, so the plain
+// form's code is what it was before there were counts (key_count:
+// device_common.h, shared with f32.hip).
+// ---------------------------------------------------------------------------
+// an item (sentence, head) of the persistent kernel; the plain form carries no count
+template <bool KV> struct AttItem;
+template <> struct AttItem<false> {
+    int start, len, h;
+    __device__ __forceinline__ int keys() const { return len; }
+};
+template <> struct AttItem<true> {
+    int start, len, h, nk;
+    __device__ __forceinline__ int keys() const { return nk; }
+};
+
 struct RowMaxSum { float m, l; };   // a query's running max and its row sum under that max
 template <bool FAST>
 __device__ __forceinline__ float ex2(float x)
@@ -77,9 +98,10 @@ __device__ __forceinline__ void store_row_h16x4(const f32x16 (&o)[NT], float l_i
 // -1e5 mask does after its fp16 exp (bert.cpp:957-961, 1024-1025).
 // ---------------------------------------------------------------------------
 
-template <int DH>
+template <int DH, bool KV>
 __global__ __launch_bounds__(256) void attention_kernel(const h16 *__restrict__ qkv, const int32_t *__restrict__ cu,
-                                                        int d, int nqt, int nh, float sl2, h16 *__restrict__ out)
+                                                        int d, int nqt, int nh, float sl2, h16 *__restrict__ out,
+                                                        const int32_t *__restrict__ keys)
 {
     constexpr int KT = 64, KSTR = DH + 8, VSTR = KT + 8;
     __shared__ __attribute__((aligned(16))) h16 Ks[KT * KSTR];
@@ -92,6 +114,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const h16 *__restrict__ 
     const int start = cu[b], len = cu[b + 1] - start;
     const int q0 = qt * ATT_QT;
     if (q0 >= len) return;
+    const int nk = key_count<KV>(keys, b, len);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int hi = lane >> 5, lq = lane & 31;
     const int ld = 3 * d;
@@ -109,7 +132,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const h16 *__restrict__ 
         for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
     RowMaxSum ms = {-INFINITY, 0.f};
 
-    const int nkt = (len + KT - 1) / KT;
+    const int nkt = (nk + KT - 1) / KT;
     for (int kt = 0; kt < nkt; ++kt) {
         const int k0 = kt * KT;
         __syncthreads();
@@ -117,15 +140,15 @@ __global__ __launch_bounds__(256) void attention_kernel(const h16 *__restrict__ 
         for (int c = tid; c < KT * DH / 8; c += 256) {
             const int r = c / (DH / 8), ch = c % (DH / 8);
             uint4 kv = {0u, 0u, 0u, 0u};
-            if (k0 + r < len) kv = *(const uint4 *)(qkv + (size_t)(start + k0 + r) * ld + d + h * DH + ch * 8);
+            if (k0 + r < nk) kv = *(const uint4 *)(qkv + (size_t)(start + k0 + r) * ld + d + h * DH + ch * 8);
             *(uint4 *)(Ks + r * KSTR + ch * 8) = kv;
         }
         // V tile transposed into Vt[d][key] (key fastest across lanes: conflict-free 2-byte writes)
         for (int c = tid; c < KT * DH / 8; c += 256) {
             const int r = c % KT, ch = c / KT;
-            // keys past the sentence: zeros (their P is exactly 0; 0 * garbage could be NaN)
+            // keys past the counted ones: zeros (their P is exactly 0; 0 * garbage could be NaN)
             h16x8 vv = {};
-            if (k0 + r < len) vv = *(const h16x8 *)(qkv + (size_t)(start + k0 + r) * ld + 2 * d + h * DH + ch * 8);
+            if (k0 + r < nk) vv = *(const h16x8 *)(qkv + (size_t)(start + k0 + r) * ld + 2 * d + h * DH + ch * 8);
 #pragma unroll
             for (int e = 0; e < 8; ++e) Vt[(ch * 8 + e) * VSTR + r] = vv[e];
         }
@@ -148,7 +171,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const h16 *__restrict__ 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int key = k0 + kh * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                const float v = key < len ? s[kh][r] * sl2 : -INFINITY;
+                const float v = key < nk ? s[kh][r] * sl2 : -INFINITY;
                 s[kh][r] = v;
                 mx = fmaxf(mx, v);
             }
@@ -189,10 +212,11 @@ __global__ __launch_bounds__(256) void attention_kernel(const h16 *__restrict__ 
 // Q is pre-scaled by log2(e)/sqrt(dh) (f16), so S comes out in the exp2 domain;
 // keys past the sentence end are masked (only in the last 64-key block).
 // ---------------------------------------------------------------------------
-template <int DH>
+template <int DH, bool KV>
 __global__ __launch_bounds__(1024) void attention_lds_kernel(const h16 *__restrict__ qkv,
                                                              const int32_t *__restrict__ cu, int d, int nh,
-                                                             float sl2, h16 *__restrict__ out)
+                                                             float sl2, h16 *__restrict__ out,
+                                                             const int32_t *__restrict__ keys)
 {
     constexpr int RB = DH * 2, CH = RB / 16, LMAX = ATT_LDS_MAX;
     __shared__ __attribute__((aligned(16))) char smem[2 * LMAX * RB];
@@ -200,10 +224,11 @@ __global__ __launch_bounds__(1024) void attention_lds_kernel(const h16 *__restri
     const int h = blockIdx.x % nh, b = blockIdx.x / nh;
     const int start = cu[b], len = cu[b + 1] - start;
     if (len <= 0) return;
+    const int nk = key_count<KV>(keys, b, len);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int hi = lane >> 5, lq = lane & 31;
     const int ld = 3 * d;
-    const int nrows = (len + 63) & ~63;
+    const int nrows = (nk + 63) & ~63;                    // the counted keys' 64-row blocks
 
     // ---- K and V of the sentence -> LDS (64 chunks of 16 B per wave-instruction) ----
     {
@@ -212,7 +237,7 @@ __global__ __launch_bounds__(1024) void attention_lds_kernel(const h16 *__restri
         const h16 *vbase = kbase + d;
         for (int i = w; i < ninstr; i += 16) {
             const int g = i * 64 + lane, row = g / CH, pc = g % CH;
-            const int srow = min(row, len - 1);          // rows past the end: finite copies, masked / P = 0
+            const int srow = min(row, nk - 1);           // rows past the end: finite copies, masked / P = 0
             const RowSwz sw = row_swz<CH>(row);
             glds<16>(kbase + (size_t)srow * ld + (pc ^ sw.k) * 8, Kl + i * 1024);
             glds<16>(vbase + (size_t)srow * ld + (pc ^ sw.v) * 8, Vl + i * 1024);
@@ -256,13 +281,13 @@ __global__ __launch_bounds__(1024) void attention_lds_kernel(const h16 *__restri
                 s[kh] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, qf[st], s[kh], 0, 0, 0);
             }
         }
-        if (kb + 64 > len) {
+        if (kb + 64 > nk) {
 #pragma unroll
             for (int kh = 0; kh < 2; ++kh)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = kb + 32 * kh + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    if (key >= len) s[kh][r] = -INFINITY;
+                    if (key >= nk) s[kh][r] = -INFINITY;
                 }
         }
         float mx = s[0][0];
@@ -353,9 +378,11 @@ __device__ __forceinline__ void wait_all_vm()
 // a workgroup's first item waits for its loads in the open.  Per-phase cycles:
 // ATT_STAMPS build, scripts/att_stamps.py.
 // ---------------------------------------------------------------------------
+template <bool KV>
 __global__ __launch_bounds__(1024) void attention_lds3_kernel(const h16 *__restrict__ qkv,
                                                               const int32_t *__restrict__ cu, int d, int nh,
-                                                              int n_items, float sl2, h16 *__restrict__ out)
+                                                              int n_items, float sl2, h16 *__restrict__ out,
+                                                              const int32_t *__restrict__ keys)
 {
     constexpr int DH = AttWave64::DH, RB = AttWave64::RB, CH = AttWave64::CH, LMAX = ATT_LDS_MAX, RH = LMAX / 2;
     constexpr int VB = LMAX * RB;                         // the V image behind the K image
@@ -364,28 +391,29 @@ __global__ __launch_bounds__(1024) void attention_lds3_kernel(const h16 *__restr
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ld = 3 * d;
 
-    struct Item { int start, len, h; };
+    using Item = AttItem<KV>;
     auto item = [&](int i) {
         const int b = i / nh;
         Item r;
         r.h = i - b * nh;
         r.start = cu[b];
         r.len = cu[b + 1] - r.start;
+        if constexpr (KV) r.nk = keys[b];
         return r;
     };
     // region r (rows 256 r .. 256 r + 255) of `it`: piece i = rows 8i .. 8i + 7;
     // wave w issues pieces 32 r + w and 32 r + w + 16 when they hold rows of the
-    // sentence's 64-row blocks; rows past the end are finite copies (masked / P = 0).
+    // counted keys' 64-row blocks; rows past the end are finite copies (masked / P = 0).
     auto issue = [&](const Item &it, int r) {
         const int lane = lane_id_opaque();                // recomputed here: hoisted, its
-        const int nrows = (it.len + 63) & ~63;            // derivatives spill around the block loop
+        const int nrows = (it.keys() + 63) & ~63;         // derivatives spill around the block loop
         const h16 *kbase = qkv + (size_t)it.start * ld + d + it.h * DH;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int i = 32 * r + w + 16 * j;
             if (8 * i < nrows) {
                 const int row = 8 * i + (lane >> 3), pc = lane & 7;
-                const size_t so = (size_t)min(row, it.len - 1) * ld;
+                const size_t so = (size_t)min(row, it.keys() - 1) * ld;
                 const RowSwz sw = row_swz<CH>(row);
                 glds16_hidden(kbase + so + (pc ^ sw.k) * 8, smem + i * 1024);
                 glds16_hidden(kbase + d + so + (pc ^ sw.v) * 8, smem + VB + i * 1024);
@@ -416,11 +444,12 @@ __global__ __launch_bounds__(1024) void attention_lds3_kernel(const h16 *__restr
         ASTAMP(0, __builtin_amdgcn_s_memtime());
         const int nx_i = cur_i + (int)gridDim.x;
         const bool more = nx_i < n_items;                 // workgroup-uniform
-        Item nx = {0, 0, 0};
+        Item nx = {};
         if (more) nx = item(nx_i);
-        a.len = cur.len;
-        const int nrows = (a.len + 63) & ~63;
-        const bool active = 32 * w < a.len;               // wave-uniform
+        a.nk = cur.keys();
+        a.rows = cur.len;
+        const int nrows = (a.nk + 63) & ~63;
+        const bool active = 32 * w < a.rows;              // wave-uniform
         a.scale_q(sl2);
         // the item's region B, issued after the first use of Q (the compiler's
         // wait for the Q loads retires every older piece); the empty asm keeps
@@ -489,9 +518,11 @@ __global__ __launch_bounds__(1024) void attention_lds3_kernel(const h16 *__restr
 // kernel (batch-composition invariance: a short sentence alone takes this
 // kernel, inside a longer batch attention_pp).
 // ---------------------------------------------------------------------------
+template <bool KV>
 __global__ __launch_bounds__(128) void attention_short_kernel(const h16 *__restrict__ qkv,
                                                               const int32_t *__restrict__ cu, int d, int nh,
-                                                              float sl2, h16 *__restrict__ out)
+                                                              float sl2, h16 *__restrict__ out,
+                                                              const int32_t *__restrict__ keys)
 {
     constexpr int DH = AttWave64::DH, RB = AttWave64::RB, CH = AttWave64::CH, NK = 64, VB = NK * RB;
     __shared__ __attribute__((aligned(16))) char smem[2 * NK * RB];
@@ -501,9 +532,11 @@ __global__ __launch_bounds__(128) void attention_short_kernel(const h16 *__restr
     const int hi = lane >> 5, lq = lane & 31;
     const int ld = 3 * d;
     if (len <= 0) return;                                 // workgroup-uniform
+    const int nk = key_count<KV>(keys, b, len);
     AttWave64 a;
     a.init(lane, smem, 0);
-    a.len = len;
+    a.nk = nk;
+    a.rows = len;
     // the wave's Q rows first: their loads fly with the K / V loads below
     {
         const h16 *qrow = qkv + (size_t)(start + min(32 * w + lq, len - 1)) * ld + h * DH;
@@ -515,7 +548,7 @@ __global__ __launch_bounds__(128) void attention_short_kernel(const h16 *__restr
 #pragma unroll
     for (int k = 0; k < NK * 8 / 128; ++k) {
         const int c = tid + 128 * k, r = c >> 3, j = c & 7;
-        const size_t so = (size_t)min(r, len - 1) * ld + 8 * j;
+        const size_t so = (size_t)min(r, nk - 1) * ld + 8 * j;
         const uint4 kv = *(const uint4 *)(kbase + so);
         const uint4 vv = *(const uint4 *)(kbase + d + so);
         const RowSwz sw = row_swz<CH>(r);
@@ -547,9 +580,11 @@ __global__ __launch_bounds__(128) void attention_short_kernel(const h16 *__restr
 // per CU with a 2-stage ring, a barrier per block pair, and a persistent form
 // whose ring runs on across units; profiles/r06_attention_pp_ab.log.  A priority
 // split between the co-resident workgroups: no effect, r06_attention_pp_prio_ab.log.)
+template <bool KV>
 __global__ __launch_bounds__(512, 4) void attention_pp_kernel(const h16 *__restrict__ qkv,
                                                               const int32_t *__restrict__ cu, int d, int nh,
-                                                              float sl2, h16 *__restrict__ out)
+                                                              float sl2, h16 *__restrict__ out,
+                                                              const int32_t *__restrict__ keys)
 {
     constexpr int NW = 8, NS = 4, DH = AttWave64::DH, RB = AttWave64::RB, CH = AttWave64::CH;
     constexpr int SB = 2 * 64 * RB, VO = 64 * RB;         // a stage: 64 K rows, then 64 V rows
@@ -565,7 +600,8 @@ __global__ __launch_bounds__(512, 4) void attention_pp_kernel(const h16 *__restr
     const int b = it / nh, h = it - b * nh;
     const int start = cu[b], len = cu[b + 1] - start;
     if (q0 >= len) return;                                // workgroup-uniform: no queries
-    const int nblk = (len + 63) >> 6;
+    const int nk = key_count<KV>(keys, b, len);
+    const int nblk = (nk + 63) >> 6;                      // the ring runs over the counted keys' blocks
     const bool active = q0 + 32 * w < len;                // wave-uniform
     const h16 *kbase = qkv + (size_t)start * ld + d + h * DH;
     PST_DECL;   // (stamps builds only, diag_att_stamps.h)
@@ -581,7 +617,7 @@ __global__ __launch_bounds__(512, 4) void attention_pp_kernel(const h16 *__restr
         for (int k = 0; k < PW; ++k) {
             const int i = w + NW * k, r8 = i & 7;
             const int row = 64 * j + 8 * r8 + (ln >> 3), pc = ln & 7;
-            const size_t so = (size_t)min(row, len - 1) * ld;
+            const size_t so = (size_t)min(row, nk - 1) * ld;
             char *dst = smem + (j % NS) * SB + i * 1024;
             const RowSwz sw = row_swz<CH>(row);
             if (i < 8) glds16_hidden(kbase + so + (pc ^ sw.k) * 8, dst);
@@ -605,7 +641,8 @@ __global__ __launch_bounds__(512, 4) void attention_pp_kernel(const h16 *__restr
     for (int j = 0; j < NS - 1; ++j) issue(j);
 
     a.init(lane, smem, VO);                               // k_base = v_base = the block's stage
-    a.len = len;
+    a.nk = nk;
+    a.rows = len;
     a.clear();
     // block j: this wave's pieces of it retired (blocks j + 1 .. j + NS - 2 may
     // fly), then the barrier publishes every wave's and frees block j - 1's stage,
@@ -687,38 +724,48 @@ static AttKernel choose_attention(int dh, int max_len, int variant)
     return pp_env ? AttKernel::PP : AttKernel::LDS3;
 }
 
+// One launch, plain (KV = false, keys unused) or with key counts
+template <bool KV>
+static void launch_attention_as(AttKernel kernel, const h16 *qkv, const int32_t *cu, const int32_t *keys, int n_items,
+                                int max_len, int n_head, int d, int dh, float sl2, h16 *out, hipStream_t s)
+{
+    switch (kernel) {
+    case AttKernel::Short:
+        if (n_items > 0) attention_short_kernel<KV><<<n_items, 128, 0, s>>>(qkv, cu, d, n_head, sl2, out, keys);
+        break;
+    case AttKernel::PP:
+        if (n_items > 0) attention_pp_kernel<KV><<<2 * n_items, 512, 0, s>>>(qkv, cu, d, n_head, sl2, out, keys);
+        break;
+    case AttKernel::LDS3: {   // persistent: one workgroup per CU
+        const int grid = std::min(n_items, g_att_variant == 7 ? 7 : device_cu_count());
+        if (grid > 0) attention_lds3_kernel<KV><<<grid, 1024, 0, s>>>(qkv, cu, d, n_head, n_items, sl2, out, keys);
+        break;
+    }
+    case AttKernel::LDS_DH32:
+        attention_lds_kernel<32, KV><<<n_items, 1024, 0, s>>>(qkv, cu, d, n_head, sl2, out, keys);
+        break;
+    case AttKernel::Streaming: {
+        const int nqt = (max_len + ATT_QT - 1) / ATT_QT;
+        const int grid = nqt * n_items;
+        if (dh == 64) attention_kernel<64, KV><<<grid, 256, 0, s>>>(qkv, cu, d, nqt, n_head, sl2, out, keys);
+        else attention_kernel<32, KV><<<grid, 256, 0, s>>>(qkv, cu, d, nqt, n_head, sl2, out, keys);
+        break;
+    }
+    }
+}
+
 void launch_attention(const uint16_t *qkv_, const int32_t *cu, int32_t n_seqs, int32_t max_len, int32_t n_head,
-                      int32_t d, uint16_t *out_, hipStream_t s)
+                      int32_t d, uint16_t *out_, hipStream_t s, const int32_t *keys)
 {
     const int dh = d / n_head, n_items = n_seqs * n_head;
     const float sl2 = (1.0f / sqrtf((float)dh)) * 1.4426950408889634f;
     const h16 *qkv = (const h16 *)qkv_;
     h16 *out = (h16 *)out_;
+    // (the kernel is chosen by the sentences' lengths, with or without counts)
     const AttKernel kernel = choose_attention(dh, max_len, g_att_variant);
     g_att_ran = (int)kernel;
-    switch (kernel) {
-    case AttKernel::Short:
-        if (n_items > 0) attention_short_kernel<<<n_items, 128, 0, s>>>(qkv, cu, d, n_head, sl2, out);
-        break;
-    case AttKernel::PP:
-        if (n_items > 0) attention_pp_kernel<<<2 * n_items, 512, 0, s>>>(qkv, cu, d, n_head, sl2, out);
-        break;
-    case AttKernel::LDS3: {   // persistent: one workgroup per CU
-        const int grid = std::min(n_items, g_att_variant == 7 ? 7 : device_cu_count());
-        if (grid > 0) attention_lds3_kernel<<<grid, 1024, 0, s>>>(qkv, cu, d, n_head, n_items, sl2, out);
-        break;
-    }
-    case AttKernel::LDS_DH32:
-        attention_lds_kernel<32><<<n_items, 1024, 0, s>>>(qkv, cu, d, n_head, sl2, out);
-        break;
-    case AttKernel::Streaming: {
-        const int nqt = (max_len + ATT_QT - 1) / ATT_QT;
-        const int grid = nqt * n_items;
-        if (dh == 64) attention_kernel<64><<<grid, 256, 0, s>>>(qkv, cu, d, nqt, n_head, sl2, out);
-        else attention_kernel<32><<<grid, 256, 0, s>>>(qkv, cu, d, nqt, n_head, sl2, out);
-        break;
-    }
-    }
+    if (keys) launch_attention_as<true>(kernel, qkv, cu, keys, n_items, max_len, n_head, d, dh, sl2, out, s);
+    else launch_attention_as<false>(kernel, qkv, cu, nullptr, n_items, max_len, n_head, d, dh, sl2, out, s);
 }
 
 }  // namespace emb

@@ -64,7 +64,7 @@ struct AttWave64 {
     h16x8 abias, bbias;       // the bias MFMA's operands: ones-column of K, (-c)-row of Q
     int koff[DH / 16], voff[DH / 32];   // lane-constant offsets into a block's K / V rows
     const char *lds;
-    int len, hi;
+    int nk, rows, hi;         // counted keys (the mask), the sentence's rows (the store's bound)
 
     // lane roles and bias operands; `vo` is added to every V offset
     __device__ __forceinline__ void init(int lane, const char *lds_, int vo)
@@ -87,7 +87,8 @@ struct AttWave64 {
         bbias = h16x8{zero, zero, zero, zero, zero, zero, zero, zero};
         c = 0.f;
         l = 0.f;
-        len = 0;
+        nk = 0;
+        rows = 0;
     }
     // a new query: nothing of the block state stays live
     __device__ __forceinline__ void clear()
@@ -114,7 +115,7 @@ struct AttWave64 {
         bbias[0] = hi ? (h16)0.0f : (h16)(-c);
     }
 
-    // S^T = K Q^T (- c with bias) of keys kb .. kb + 63; keys past the sentence -inf
+    // S^T = K Q^T (- c with bias) of keys kb .. kb + 63; keys past the counted ones -inf
     __device__ __forceinline__ void qk(int kb, int k_base, bool bias)
     {
         int kbo[DH / 16];
@@ -137,13 +138,13 @@ struct AttWave64 {
                 s[kh] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, qf[st], s[kh], 0, 0, 0);
             }
         }
-        if (kb + 64 > len) {
+        if (kb + 64 > nk) {
 #pragma unroll
             for (int kh = 0; kh < 2; ++kh)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = kb + 32 * kh + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    if (key >= len) s[kh][r] = -INFINITY;
+                    if (key >= nk) s[kh][r] = -INFINITY;
                 }
         }
     }
@@ -245,8 +246,9 @@ struct AttWave64 {
     // 16-B stores per lane instead of eight 8-B ones (the store tail is
     // issue-bound).  Both lanes of a pair hold the same query, so the swaps
     // run on every lane.  The stores are bounds-checked buffer stores with the
-    // sentence's rows [start, start + len) of `out` as the resource: a row
-    // q >= len lies past num_records and its store is dropped.
+    // sentence's rows [start, start + rows) of `out` as the resource: a row
+    // q >= rows lies past num_records and its store is dropped.  (rows is the
+    // sentence's length whatever its key count: every row is a query.)
     __device__ __forceinline__ void store(h16 *out, int start, int d, int h, int q) const
     {
         static_assert(DH / 16 == 4, "four stores per lane");
@@ -269,7 +271,7 @@ struct AttWave64 {
                 pk[2 * p + 1][k] = r[1];
             }
         const __amdgpu_buffer_rsrc_t ors =
-            __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)start * d), (short)0, len * d * 2, 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)start * d), (short)0, rows * d * 2, 0x00020000);
         const int ob = (q * d + h * DH + 8 * hi) * 2;
 #pragma unroll
         for (int p = 0; p < DH / 16; ++p) {

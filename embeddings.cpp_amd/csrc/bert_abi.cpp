@@ -11,6 +11,7 @@
 #include "tokenizer.h"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -88,6 +89,9 @@ struct bert_ctx {
     int pool = 0;       // BERTX_POOL_MEAN / BERTX_POOL_CLS (bertx_set_pooling), mirrored on every replica
     int n_labels = 0;   // logits per sentence of the file's classification head; 0: none (bertx_n_labels)
     int proj_dim = 0;   // rows of the file's ColBERT projection; 0: none (bertx_proj_dim)
+    // whether a ColBERT query's [MASK] rows are attention keys (bertx_set_mask_keys).  One value
+    // for the context: the replicas hold no copy, the counts travel with each forward.
+    std::atomic<int> mask_keys{1};
     // routing state of run_forward: the cost of the work routed to each replica and
     // not yet finished, and the rotation that breaks ties between equal loads
     std::mutex route_mu;
@@ -469,9 +473,20 @@ static bert_ctx *load_guarded(const char *fname, int act_mode)
         }
         pool = BERTX_POOL_CLS;
     }
+    // whether ColBERT queries keep their [MASK] rows as keys, BERT_MASK_KEYS=0|1 (unset: 1)
+    const char *em = std::getenv("BERT_MASK_KEYS");
+    int mask_keys = 1;
+    if (em && *em) {
+        if (std::strcmp(em, "0") != 0 && std::strcmp(em, "1") != 0) {
+            emb::errorf("bert_load_from_file: BERT_MASK_KEYS='%s' is not 0 or 1\n", em);
+            return nullptr;
+        }
+        mask_keys = em[0] - '0';
+    }
     try {
         bert_ctx *ctx = load_context(fname, act_mode);
         if (ctx && pool != BERTX_POOL_MEAN) bertx_set_pooling(ctx, pool);
+        if (ctx) bertx_set_mask_keys(ctx, mask_keys);
         return ctx;
     } catch (const std::bad_alloc &) {
         emb::errorf("bert_load_from_file: out of host memory\n");
@@ -643,6 +658,15 @@ int32_t bertx_set_pooling(struct bert_ctx *ctx, int32_t pool)
 
 int32_t bertx_pooling(struct bert_ctx *ctx) { return ctx ? ctx->pool : -1; }
 
+int32_t bertx_set_mask_keys(struct bert_ctx *ctx, int32_t on)
+{
+    if (!ctx || (on != 0 && on != 1)) return -1;
+    ctx->mask_keys.store(on);
+    return 0;
+}
+
+int32_t bertx_mask_keys(struct bert_ctx *ctx) { return ctx ? ctx->mask_keys.load() : -1; }
+
 int32_t bertx_set_cls_pruning(struct bert_ctx *ctx, int32_t on)
 {
     if (!ctx) return -1;
@@ -666,8 +690,9 @@ int32_t bertx_forward_tokens_device(struct bert_ctx *ctx, int32_t slot, const in
 }
 
 // The per-token host forms: every token's final-LayerNorm row, or (proj) its projection.
+// n_keys (or null): sentence i's key count, which travels with it into its chunk.
 static int32_t forward_rows(struct bert_ctx *ctx, int32_t n, bert_vocab_id **batch_tokens, int32_t *n_tokens,
-                            float **out, bool proj)
+                            float **out, bool proj, const int32_t *n_keys = nullptr)
 {
     if (!ctx || n < 0 || (n > 0 && (!batch_tokens || !n_tokens || !out))) return -1;
     if (proj && ctx->proj_dim <= 0) {
@@ -684,6 +709,7 @@ static int32_t forward_rows(struct bert_ctx *ctx, int32_t n, bert_vocab_id **bat
             return -4;
         }
         if (n_tokens[i] <= 0) return -1;
+        if (n_keys && (n_keys[i] < 1 || n_keys[i] > n_tokens[i])) return -1;   // before any output is written
     }
     if (n == 0) return 0;
     // the whole call on the least-loaded replica, in chunks the workspace holds
@@ -701,17 +727,19 @@ static int32_t forward_rows(struct bert_ctx *ctx, int32_t n, bert_vocab_id **bat
         Device &D = *ctx->devices[(size_t)dv];
         std::lock_guard<std::mutex> lk(D.mutex());
         std::vector<const int32_t *> tp;
-        std::vector<int32_t> lp;
+        std::vector<int32_t> lp, kp;
         std::vector<float *> op;
         int i = 0;
         while (i < n && rc == 0) {
-            tp.clear(); lp.clear(); op.clear();
+            tp.clear(); lp.clear(); op.clear(); kp.clear();
             int64_t tok = 0;
             while (i < n && (tp.empty() || (tok + n_tokens[i] <= kChunkTokens && (int)tp.size() < kChunkSeqs))) {
                 tp.push_back(batch_tokens[i]); lp.push_back(n_tokens[i]); op.push_back(out[i]);
+                if (n_keys) kp.push_back(n_keys[i]);
                 tok += n_tokens[i++];
             }
-            rc = D.forward_host(tp.data(), lp.data(), (int)tp.size(), op.data(), true, nullptr, false, proj);
+            rc = D.forward_host(tp.data(), lp.data(), (int)tp.size(), op.data(), true, nullptr, false, proj,
+                                n_keys ? kp.data() : nullptr);
         }
     } catch (...) {
         rc = -1;
@@ -737,6 +765,18 @@ int32_t bertx_forward_project(struct bert_ctx *ctx, int32_t n, bert_vocab_id **b
     return forward_rows(ctx, n, batch_tokens, n_tokens, out, true);
 }
 
+int32_t bertx_forward_tokens_kv(struct bert_ctx *ctx, int32_t n, bert_vocab_id **batch_tokens, int32_t *n_tokens,
+                                const int32_t *n_keys, float **out)
+{
+    return forward_rows(ctx, n, batch_tokens, n_tokens, out, false, n_keys);
+}
+
+int32_t bertx_forward_project_kv(struct bert_ctx *ctx, int32_t n, bert_vocab_id **batch_tokens, int32_t *n_tokens,
+                                 const int32_t *n_keys, float **out)
+{
+    return forward_rows(ctx, n, batch_tokens, n_tokens, out, true, n_keys);
+}
+
 int32_t bertx_proj_dim(struct bert_ctx *ctx) { return ctx ? ctx->proj_dim : 0; }
 int32_t bertx_proj_width(struct bert_ctx *ctx) { return ctx ? emb::proj_width_of(ctx->proj_dim) : 0; }
 
@@ -757,7 +797,14 @@ int32_t bertx_forward_project_device(struct bert_ctx *ctx, int32_t slot, const i
 int32_t bertx_tokenize_colbert(struct bert_ctx *ctx, const char *text, int32_t kind, int32_t maxlen, bert_vocab_id *ids,
                                int32_t *keep, int32_t *n_tokens)
 {
-    if (!ctx || !text || !ids || !keep || !n_tokens || (kind != 0 && kind != 1)) return -1;
+    int32_t n_keys = 0;
+    return bertx_tokenize_colbert_ex(ctx, text, kind, maxlen, ids, keep, n_tokens, &n_keys);
+}
+
+int32_t bertx_tokenize_colbert_ex(struct bert_ctx *ctx, const char *text, int32_t kind, int32_t maxlen,
+                                  bert_vocab_id *ids, int32_t *keep, int32_t *n_tokens, int32_t *n_keys)
+{
+    if (!ctx || !text || !ids || !keep || !n_tokens || !n_keys || (kind != 0 && kind != 1)) return -1;
     if (maxlen < 4 || maxlen > ctx->hp.n_max_tokens) return -1;
     try {
         thread_local std::vector<int32_t> p;
@@ -765,6 +812,8 @@ int32_t bertx_tokenize_colbert(struct bert_ctx *ctx, const char *text, int32_t k
         const int32_t t = ctx->vocab.colbert_layout(p.data(), (int32_t)p.size(), kind, maxlen, ids, keep);
         if (t < 0) return -1;
         *n_tokens = t;
+        // a query's rows up to and including [SEP]; the [MASK] rows behind it are not counted
+        *n_keys = kind == 0 ? 3 + std::min<int32_t>((int32_t)p.size(), maxlen - 3) : t;
         return 0;
     } catch (...) {
         emb::errorf("libbert: tokenization failed\n");
@@ -863,6 +912,25 @@ int32_t bertx_forward_device_ex(struct bert_ctx *ctx, int32_t slot, const int32_
     emb::DeviceGuard g(D.ordinal());
     return D.forward_ex(d_ids, d_types, d_cu, n_seqs, max_len, total_tokens, out_kind, d_out,
                         stream ? (hipStream_t)stream : D.stream());
+}
+
+int32_t bertx_forward_device_kv(struct bert_ctx *ctx, int32_t slot, const int32_t *d_ids, const int32_t *d_types,
+                                const int32_t *d_cu, const int32_t *d_keys, int32_t n_seqs, int32_t max_len,
+                                int32_t total_tokens, int32_t out_kind, const int32_t *d_rows, int32_t n_rows,
+                                float *d_out, void *stream)
+{
+    if (!ctx || slot < 0 || slot >= (int32_t)ctx->devices.size()) return -1;
+    if (out_kind != BERTX_OUT_TOKENS && out_kind != BERTX_OUT_PROJ) return -1;
+    const bool mapped = out_kind == BERTX_OUT_PROJ && d_rows != nullptr;
+    if (mapped && n_rows < 0) return -1;
+    if (out_kind == BERTX_OUT_PROJ && ctx->proj_dim <= 0) return -6;
+    if (max_len > ctx->hp.n_max_tokens || max_len <= 0) return -4;
+    Device &D = *ctx->devices[(size_t)slot];
+    std::lock_guard<std::mutex> lk(D.mutex());
+    emb::DeviceGuard g(D.ordinal());
+    return D.forward_ex(d_ids, d_types, d_cu, n_seqs, max_len, total_tokens, out_kind, d_out,
+                        stream ? (hipStream_t)stream : D.stream(), -1.0, mapped ? d_rows : nullptr, mapped ? n_rows : 0,
+                        d_keys);
 }
 
 int32_t bertx_tokenize_pair(struct bert_ctx *ctx, const char *text_a, const char *text_b, int32_t truncate,

@@ -465,8 +465,8 @@ int convert_hf_dir(const std::string &dir, const std::string &fname_out, int fty
         if (read_file(dir + "/artifact.metadata", s) && parse_json(s, meta)) {
             const JVal *a = meta.get("attend_to_mask_tokens");
             if (a && a->kind == JVal::BOOL && !a->b)
-                infof("convert: --colbert: this checkpoint was trained with attend_to_mask_tokens = false; this "
-                      "library's query [MASK] rows are ordinary attention keys\n");
+                infof("convert: --colbert: this checkpoint was trained with attend_to_mask_tokens = false; encode its "
+                      "queries with BERT_MASK_KEYS=0 (bertx_set_mask_keys(ctx, 0), search -M), else [MASK] rows are keys\n");
         }
     }
     FILE *f = std::fopen(fname_out.c_str(), "wb");

@@ -216,6 +216,15 @@ __device__ __forceinline__ int xcd_block(int b, int nb)
     return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (b >> 3);
 }
 
+// The rows of sentence b that are attention keys and values (attention.hip, f32.hip):
+// with counts (KV) keys[b], 1 <= keys[b] <= len; the plain form reads nothing.
+template <bool KV>
+__device__ __forceinline__ int key_count(const int32_t *keys, int b, int len)
+{
+    if constexpr (KV) return keys[b];
+    else return len;
+}
+
 __device__ __forceinline__ void lds_barrier()
 {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -278,6 +278,7 @@ Device::~Device()
     if (h_ids_) (void)hipHostFree(h_ids_);
     if (h_cu_) (void)hipHostFree(h_cu_);
     if (h_types_) (void)hipHostFree(h_types_);
+    if (h_keys_) (void)hipHostFree(h_keys_);
     if (h_out_) (void)hipHostFree(h_out_);
     if (done_ev_) (void)hipEventDestroy(done_ev_);
     if (stream_) (void)hipStreamDestroy(stream_);
@@ -385,12 +386,14 @@ bool Device::reserve(int64_t tokens, int64_t seqs, int max_len)
     const int64_t rows_c = ns + GEMM_BM + 256, rc16 = c32 ? 0 : rows_c;
     const size_t o_stc = take(rc16 * 8), o_zc = take(rc16 * d * 2), o_partc = take(rc16 * (d / 32) * 8);
     const size_t o_attc = take(rc16 * d * 2), o_ffnc = take(rc16 * f * 2);
+    const size_t o_keys = take(ns * 4);   // the sentences' key counts (forward_host with counts)
     drop_graphs();   // captured graphs hold the old workspace pointers
     if (ws_) { (void)hipFree(ws_); ws_ = nullptr; }
     if (h_ids_) { (void)hipHostFree(h_ids_); h_ids_ = nullptr; }
     if (h_cu_) { (void)hipHostFree(h_cu_); h_cu_ = nullptr; }
     if (h_out_) { (void)hipHostFree(h_out_); h_out_ = nullptr; }
     if (h_types_) { (void)hipHostFree(h_types_); h_types_ = nullptr; }
+    if (h_keys_) { (void)hipHostFree(h_keys_); h_keys_ = nullptr; }
     cap_tokens_ = cap_seqs_ = cap_pool_ = 0;
     HIP_OK(hipMalloc((void **)&ws_, off));
     // on the replica's own (non-blocking) stream: a null-stream memset would not
@@ -403,6 +406,7 @@ bool Device::reserve(int64_t tokens, int64_t seqs, int max_len)
     d_ids_ = (int32_t *)(ws_ + o_ids); d_cu_ = (int32_t *)(ws_ + o_cu); d_out_ = (float *)(ws_ + o_out);
     pool_part_ = (float *)(ws_ + o_pool);
     d_types_ = (int32_t *)(ws_ + o_types);
+    d_keys_ = (int32_t *)(ws_ + o_keys);
     head_x_ = (float *)(ws_ + o_hx); head_p_ = (float *)(ws_ + o_hp);
     stc_ = (float2 *)(ws_ + o_stc); zc_ = (uint16_t *)(ws_ + o_zc); partc_ = (float2 *)(ws_ + o_partc);
     attc_ = (uint16_t *)(ws_ + o_attc); ffnc_ = (uint16_t *)(ws_ + o_ffnc);
@@ -413,6 +417,7 @@ bool Device::reserve(int64_t tokens, int64_t seqs, int max_len)
     HIP_OK(hipHostMalloc((void **)&h_ids_, nt * 4, hipHostMallocDefault));
     HIP_OK(hipHostMalloc((void **)&h_cu_, (ns + 1) * 4, hipHostMallocDefault));
     HIP_OK(hipHostMalloc((void **)&h_types_, nt * 4, hipHostMallocDefault));
+    HIP_OK(hipHostMalloc((void **)&h_keys_, ns * 4, hipHostMallocDefault));
     HIP_OK(hipHostMalloc((void **)&h_out_, ns * d * 4, hipHostMallocDefault));
     cap_tokens_ = nt;
     cap_seqs_ = ns;

@@ -176,10 +176,14 @@ public:
     // projection of token d_rows[i] (d_rows int32 [n_rows] on this GPU, every value in
     // [0, total_tokens), trusted), or with d_rows null float[total_tokens][proj_width],
     // every token in order; -6 on a file without the record.  Never pruned.
+    // d_keys (KIND_TOKENS and KIND_PROJ only, -1 with another kind; null: none): int32
+    // [n_seqs] on this GPU, sentence b's first d_keys[b] rows are the keys and values of
+    // its attention, 1 <= d_keys[b] <= its length (trusted); every row stays a query and
+    // an output row.  Those kinds never run the pruned last layer.
     enum OutKind : int { KIND_POOLED = 0, KIND_TOKENS = 1, KIND_LOGITS = 2, KIND_PROJ = 3 };
     int forward_ex(const int32_t *d_ids, const int32_t *d_types, const int32_t *d_cu, int n_seqs, int max_len,
                    int total_tokens, int out_kind, float *d_out, hipStream_t s, double len2_sum = -1.0,
-                   const int32_t *d_rows = nullptr, int n_rows = 0);
+                   const int32_t *d_rows = nullptr, int n_rows = 0, const int32_t *d_keys = nullptr);
     int n_labels() const { return n_labels_; }
     int proj_dim() const { return proj_dim_; }
     int proj_width() const { return proj_width_of(proj_dim_); }
@@ -189,9 +193,11 @@ public:
     // lens[i] x n_embd floats (the per-token output).  types (or null: all 0): the
     // token type ids, types[i] beside tokens[i].  logits: out[i] receives the
     // n_labels logits of sentence i instead.  proj (with tok_out): out[i] receives
-    // lens[i] x proj_width floats, the projected rows (KIND_PROJ).
+    // lens[i] x proj_width floats, the projected rows (KIND_PROJ).  keys (with tok_out;
+    // null: none): keys[i] is sentence i's key count, 1 .. lens[i] (checked by the caller).
     int forward_host(const int32_t *const *tokens, const int32_t *lens, int n, float *const *out, bool tok_out = false,
-                     const int32_t *const *types = nullptr, bool logits = false, bool proj = false);
+                     const int32_t *const *types = nullptr, bool logits = false, bool proj = false,
+                     const int32_t *keys = nullptr);
 
     // Pooling of the sentence embeddings (bert_hip.h): BERTX_POOL_MEAN / BERTX_POOL_CLS,
     // and whether CLS pooling runs the last layer on the sentences' first rows only
@@ -229,11 +235,12 @@ private:
         const void *types;   // the token types pointer (null: all 0) is baked into the embedding launch
         const void *rows;    // OUT_PROJ: the row map (null: every token) and its length
         int n_rows;
+        const void *keys;    // the key counts pointer (null: none) is baked into the attention launches
         bool operator==(const GraphKey &o) const
         {
             return ids == o.ids && cu == o.cu && out == o.out && s == o.s && n_seqs == o.n_seqs &&
                    max_len == o.max_len && T == o.T && mode == o.mode && types == o.types && rows == o.rows &&
-                   n_rows == o.n_rows;
+                   n_rows == o.n_rows && keys == o.keys;
         }
     };
     // what the launch sequence ends in (and, for CLS and the logits, how its last layer runs)
@@ -327,7 +334,9 @@ private:
     const int32_t *types_ = nullptr;   // ... and its token types (null: all 0)
     const int32_t *map_ = nullptr;     // ... and, OUT_PROJ, its row map (null: every token) of n_map_ rows
     int n_map_ = 0;
-    int32_t *h_ids_ = nullptr, *h_cu_ = nullptr, *h_types_ = nullptr;   // pinned staging
+    const int32_t *keys_ = nullptr;    // ... and its key counts (null: every row of a sentence is a key)
+    int32_t *d_keys_ = nullptr;        // forward_host's counts on the device [cap_seqs_]
+    int32_t *h_ids_ = nullptr, *h_cu_ = nullptr, *h_types_ = nullptr, *h_keys_ = nullptr;   // pinned staging
     float *h_out_ = nullptr;
 
     // HIP graphs of the launch sequence (cleared when the workspace moves)

@@ -223,10 +223,13 @@ __device__ __forceinline__ float era_lanes_sum(const float (&a)[8])
                      add_rn(add_rn(a[4], a[5]), add_rn(a[6], a[7])));
 }
 
-template <int DH, bool ERA>
+// KV: the sentence's first keys[b] rows are its keys and values (1 <= keys[b] <= len),
+// every row a query; the plain form reads no count and is the code it was.
+template <int DH, bool ERA, bool KV>
 __global__ __launch_bounds__(256) void f32_attention_kernel(const float *__restrict__ qkv, const int32_t *__restrict__ cu,
                                                             int d, int s_stride, float scale, float *__restrict__ out,
-                                                            const uint16_t *__restrict__ exp_tab)
+                                                            const uint16_t *__restrict__ exp_tab,
+                                                            const int32_t *__restrict__ keys)
 {
     extern __shared__ float smem[];
     float(*qs)[DH] = (float(*)[DH])smem;                      // [16][DH]
@@ -235,17 +238,18 @@ __global__ __launch_bounds__(256) void f32_attention_kernel(const float *__restr
     const int q0 = blockIdx.x * 16, h = blockIdx.y, b = blockIdx.z;
     const int start = cu[b], len = cu[b + 1] - start;
     if (q0 >= len) return;   // whole workgroup
+    const int nk = key_count<KV>(keys, b, len);
     const int tid = threadIdx.x, qi = tid >> 4, l16 = tid & 15;
     const size_t ld = 3 * (size_t)d;
     for (int i = tid; i < 16 * DH; i += 256) {
         const int r = i / DH, e = i % DH;
         qs[r][e] = q0 + r < len ? qkv[(size_t)(start + q0 + r) * ld + h * DH + e] : 0.f;
     }
-    for (int k0 = 0; k0 < len; k0 += 64) {
+    for (int k0 = 0; k0 < nk; k0 += 64) {
         __syncthreads();
         for (int i = tid; i < 64 * DH; i += 256) {
             const int r = i / DH, e = i % DH;
-            kv[r][e] = k0 + r < len ? qkv[(size_t)(start + k0 + r) * ld + d + h * DH + e] : 0.f;
+            kv[r][e] = k0 + r < nk ? qkv[(size_t)(start + k0 + r) * ld + d + h * DH + e] : 0.f;
         }
         __syncthreads();
 #pragma unroll
@@ -262,17 +266,17 @@ __global__ __launch_bounds__(256) void f32_attention_kernel(const float *__restr
 #pragma unroll 8
                 for (int e = 0; e < DH; ++e) a = fmaf(kv[kk][e], qs[qi][e], a);
             }
-            if (k0 + kk < len) S[qi * s_stride + k0 + kk] = a * scale;
+            if (k0 + kk < nk) S[qi * s_stride + k0 + kk] = a * scale;
         }
     }
     __syncthreads();
     float *row = S + qi * s_stride;
     float mx = -INFINITY;
-    for (int k = l16; k < len; k += 16) mx = fmaxf(mx, row[k]);
+    for (int k = l16; k < nk; k += 16) mx = fmaxf(mx, row[k]);
 #pragma unroll
     for (int o = 8; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
     double sum = 0.0;
-    for (int k = l16; k < len; k += 16) {
+    for (int k = l16; k < nk; k += 16) {
         const float e = era_table(exp_tab, row[k] - mx);
         row[k] = e;
         sum += (double)e;
@@ -280,7 +284,7 @@ __global__ __launch_bounds__(256) void f32_attention_kernel(const float *__restr
 #pragma unroll
     for (int o = 8; o >= 1; o >>= 1) sum += __shfl_xor(sum, o, 64);
     const float inv = (float)(1.0 / sum);
-    for (int k = l16; k < len; k += 16) row[k] *= inv;
+    for (int k = l16; k < nk; k += 16) row[k] *= inv;
     constexpr int NE = DH / 16;
     float o_acc[NE];
     float o_la[ERA ? NE : 1][8];   // ERA: lane (key & 7) sums of each output
@@ -290,14 +294,14 @@ __global__ __launch_bounds__(256) void f32_attention_kernel(const float *__restr
     for (int j = 0; j < (ERA ? NE : 1); ++j)
 #pragma unroll
         for (int u = 0; u < 8; ++u) o_la[j][u] = 0.f;
-    for (int k0 = 0; k0 < len; k0 += 64) {
+    for (int k0 = 0; k0 < nk; k0 += 64) {
         __syncthreads();   // row updates visible; previous V tile consumed
         for (int i = tid; i < 64 * DH; i += 256) {
             const int r = i / DH, e = i % DH;
-            kv[r][e] = k0 + r < len ? qkv[(size_t)(start + k0 + r) * ld + 2 * d + h * DH + e] : 0.f;
+            kv[r][e] = k0 + r < nk ? qkv[(size_t)(start + k0 + r) * ld + 2 * d + h * DH + e] : 0.f;
         }
         __syncthreads();
-        const int kn = min(64, len - k0);
+        const int kn = min(64, nk - k0);
         if (ERA) {
             // (rows past kn of the tile are zero-filled and their p is not read)
             for (int kk = 0; kk < kn; kk += 8)
@@ -459,8 +463,23 @@ static size_t device_lds_limit()
     return (size_t)n;
 }
 
+template <bool KV>
+static void launch_f32_attention_as(int dh, bool era_order, dim3 g, size_t lds, hipStream_t s, const float *qkv,
+                                    const int32_t *cu, int d, int s_stride, float scale, float *out,
+                                    const uint16_t *exp_tab, const int32_t *keys)
+{
+    if (era_order) {
+        if (dh == 64) f32_attention_kernel<64, true, KV><<<g, 256, lds, s>>>(qkv, cu, d, s_stride, scale, out, exp_tab, keys);
+        else f32_attention_kernel<32, true, KV><<<g, 256, lds, s>>>(qkv, cu, d, s_stride, scale, out, exp_tab, keys);
+        return;
+    }
+    if (dh == 64) f32_attention_kernel<64, false, KV><<<g, 256, lds, s>>>(qkv, cu, d, s_stride, scale, out, exp_tab, keys);
+    else f32_attention_kernel<32, false, KV><<<g, 256, lds, s>>>(qkv, cu, d, s_stride, scale, out, exp_tab, keys);
+}
+
 int launch_f32_attention(const float *qkv, const int32_t *cu, int32_t n_seqs, int32_t max_len, int32_t n_head,
-                         int32_t d, float *out, hipStream_t s, const uint16_t *exp_tab, bool era_order)
+                         int32_t d, float *out, hipStream_t s, const uint16_t *exp_tab, bool era_order,
+                         const int32_t *keys)
 {
     const int dh = d / n_head;
     if (d % n_head || (dh != 32 && dh != 64) || max_len <= 0 || !exp_tab) return -1;
@@ -471,13 +490,8 @@ int launch_f32_attention(const float *qkv, const int32_t *cu, int32_t n_seqs, in
     if (lds > device_lds_limit()) return -1;
     const dim3 g((max_len + 15) / 16, n_head, n_seqs);
     const float scale = 1.0f / sqrtf((float)dh);
-    if (era_order) {
-        if (dh == 64) f32_attention_kernel<64, true><<<g, 256, lds, s>>>(qkv, cu, d, s_stride, scale, out, exp_tab);
-        else f32_attention_kernel<32, true><<<g, 256, lds, s>>>(qkv, cu, d, s_stride, scale, out, exp_tab);
-        return 0;
-    }
-    if (dh == 64) f32_attention_kernel<64, false><<<g, 256, lds, s>>>(qkv, cu, d, s_stride, scale, out, exp_tab);
-    else f32_attention_kernel<32, false><<<g, 256, lds, s>>>(qkv, cu, d, s_stride, scale, out, exp_tab);
+    if (keys) launch_f32_attention_as<true>(dh, era_order, g, lds, s, qkv, cu, d, s_stride, scale, out, exp_tab, keys);
+    else launch_f32_attention_as<false>(dh, era_order, g, lds, s, qkv, cu, d, s_stride, scale, out, exp_tab, nullptr);
     return 0;
 }
 

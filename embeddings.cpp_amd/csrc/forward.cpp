@@ -77,9 +77,12 @@ struct Device::Launcher {
 };
 
 int Device::forward_ex(const int32_t *d_ids, const int32_t *d_types, const int32_t *d_cu, int n_seqs, int max_len, int T,
-                       int out_kind, float *d_out, hipStream_t s, double len2_sum, const int32_t *d_rows, int n_rows)
+                       int out_kind, float *d_out, hipStream_t s, double len2_sum, const int32_t *d_rows, int n_rows,
+                       const int32_t *d_keys)
 {
     if (out_kind != KIND_POOLED && out_kind != KIND_TOKENS && out_kind != KIND_LOGITS && out_kind != KIND_PROJ) return -1;
+    // key counts come with the per-token outputs only (which never take the pruned last layer)
+    if (d_keys && out_kind != KIND_TOKENS && out_kind != KIND_PROJ) return -1;
     if (out_kind == KIND_LOGITS && n_labels_ <= 0) return -6;
     if (out_kind == KIND_PROJ && proj_dim_ <= 0) return -6;
     const bool mapped = out_kind == KIND_PROJ && d_rows != nullptr;
@@ -93,6 +96,7 @@ int Device::forward_ex(const int32_t *d_ids, const int32_t *d_types, const int32
                 : pool_ != 1              ? OUT_MEAN
                                           : can_prune ? OUT_CLS_PRUNED : OUT_CLS;
     types_ = d_types;
+    keys_ = d_keys;
     // attention work for the per-kernel stats: exact from the host's lengths when
     // known, else T max_len (exact for equal lengths, an upper bound otherwise)
     att_flop_ = 4.0 * hp_.n_embd * (len2_sum >= 0 ? len2_sum : (double)T * max_len);
@@ -113,7 +117,7 @@ int Device::forward_ordered(const int32_t *d_ids, const int32_t *d_cu, int n_seq
     static const bool graphs_env = [] { const char *e = std::getenv("BERT_GRAPHS"); return !(e && *e == '0'); }();
     if (profiling_ || check || !use_graphs_ || !graphs_env || s == nullptr)
         return launch_all(d_ids, d_cu, n_seqs, max_len, T, d_out, s, check);
-    const GraphKey key{d_ids, d_cu, d_out, s, n_seqs, max_len, T, out_mode_, types_, map_, n_map_};
+    const GraphKey key{d_ids, d_cu, d_out, s, n_seqs, max_len, T, out_mode_, types_, map_, n_map_, keys_};
     for (auto &g : graphs_)
         if (g.key == key) return hipGraphLaunch(g.exec, s) == hipSuccess ? 0 : -1;
     // a shape seen for the first time runs eagerly (one-off batches never pay
@@ -212,7 +216,7 @@ int Device::chain_f16(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, 
                 return -1;
             run.finite(Out{"gather", "_cls", l, zc_, (size_t)Mc * d});
         } else {
-            run.run(K_ATTENTION, att_flop, [&] { launch_attention(qkv_, d_cu, n_seqs, max_len, hp_.n_head, d, att_, s); },
+            run.run(K_ATTENTION, att_flop, [&] { launch_attention(qkv_, d_cu, n_seqs, max_len, hp_.n_head, d, att_, s, keys_); },
                     Out{"attention", "", l, att_, Td});
         }
         if (layer_tail(run, L, l, r, gz, bz) != 0) return -1;
@@ -358,7 +362,7 @@ int Device::chain_32(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, i
         const DevLayer &L = layers_[(size_t)l];
         if (!proj(K_GEMM_QKV, "gemm_qkv", l, L.qkv, L.w32_qkv, 3 * d, d, x32_, L.b_qkv, 0, nullptr, qkv32_)) return -1;
         if (!run.run(K_ATTENTION, att_flop_, [&] {
-                return launch_f32_attention(qkv32_, d_cu, n_seqs, max_len, hp_.n_head, d, att32_, s, exp_tab_, exact);
+                return launch_f32_attention(qkv32_, d_cu, n_seqs, max_len, hp_.n_head, d, att32_, s, exp_tab_, exact, keys_);
             }, Out{"attention", "", l, att32_, Td, 0}))
             return -1;
         if (!proj(K_GEMM_O, "gemm_o", l, L.o, L.w32_o, d, d, att32_, L.b_o, 2, x32_, z32_)) return -1;
@@ -396,9 +400,10 @@ int Device::chain_32(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, i
 }
 
 int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int n, float *const *out, bool tok_out,
-                         const int32_t *const *types, bool logits, bool proj)
+                         const int32_t *const *types, bool logits, bool proj, const int32_t *keys)
 {
     if (!ok_) return -3;
+    if (keys && !tok_out) return -1;
     if (logits && n_labels_ <= 0) return -6;
     if (proj && proj_dim_ <= 0) return -6;
     if (n <= 0) return 0;
@@ -426,6 +431,10 @@ int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int 
         HIP_RC(hipMemcpyAsync(d_types_, h_types_, sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, stream_));
     }
     const int32_t *dty = types ? d_types_ : nullptr;
+    if (keys) {
+        std::memcpy(h_keys_, keys, sizeof(int32_t) * (size_t)n);
+        HIP_RC(hipMemcpyAsync(d_keys_, h_keys_, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, stream_));
+    }
     const size_t d = (size_t)hp_.n_embd;
     if (tok_out) {
         // per-token output: a device buffer of its own, grown on demand, and plain
@@ -441,7 +450,7 @@ int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int 
         }
         const size_t tw = proj ? (size_t)proj_width() : d;   // floats per row of this output
         const int rc = forward_ex(d_ids_, dty, d_cu_, n, max_len, (int)T, proj ? KIND_PROJ : KIND_TOKENS, tok_out_, stream_,
-                                  len2);
+                                  len2, nullptr, 0, keys ? d_keys_ : nullptr);
         if (rc != 0) return rc;
         HIP_RC(hipStreamSynchronize(stream_));
         for (int i = 0; i < n; ++i)

@@ -521,8 +521,9 @@ extern "C" int32_t bertx_bench_gemm(int32_t fmt, int32_t N, int32_t K, int32_t M
 // attention micro-benchmark (bert_hip.h): n_seqs sentences of `len` tokens,
 // random Q/K/V, device-timed launches of variant `variant`
 // ---------------------------------------------------------------------------
-extern "C" int32_t bertx_bench_attention(int32_t n_seqs, int32_t len, int32_t n_head, int32_t dh, int32_t variant,
-                                         int32_t iters, float *avg_us)
+// n_keys: one key count for every sentence, or 0 for the plain launch
+static int32_t bench_attention(int32_t n_seqs, int32_t len, int32_t n_keys, int32_t n_head, int32_t dh,
+                               int32_t variant, int32_t iters, float *avg_us)
 {
     using namespace emb;
     if (n_seqs <= 0 || len <= 0 || iters <= 0 || hip_device_count() == 0) return -1;
@@ -539,19 +540,34 @@ extern "C" int32_t bertx_bench_attention(int32_t n_seqs, int32_t len, int32_t n_
     const uint16_t *dq = (const uint16_t *)B.up(hq.data(), hq.size() * 2, 0);
     const int32_t *dcu = (const int32_t *)B.up(hcu.data(), hcu.size() * 4, 0);
     uint16_t *dout = (uint16_t *)B.up(nullptr, 0, rows * d * 2);
+    const std::vector<int32_t> hk((size_t)n_seqs, n_keys);
+    const int32_t *dk = n_keys ? (const int32_t *)B.up(hk.data(), hk.size() * 4, 0) : nullptr;
     if (B.bad) return -1;
     ScopedSet var(g_att_variant, variant);
-    for (int i = 0; i < 3; ++i) launch_attention(dq, dcu, n_seqs, len, n_head, d, dout, nullptr);
+    for (int i = 0; i < 3; ++i) launch_attention(dq, dcu, n_seqs, len, n_head, d, dout, nullptr, dk);
     EventPair ev;
     HIP_RC(ev.create());
     HIP_RC(hipEventRecord(ev.a, nullptr));
-    for (int i = 0; i < iters; ++i) launch_attention(dq, dcu, n_seqs, len, n_head, d, dout, nullptr);
+    for (int i = 0; i < iters; ++i) launch_attention(dq, dcu, n_seqs, len, n_head, d, dout, nullptr, dk);
     HIP_RC(hipEventRecord(ev.b, nullptr));
     HIP_RC(hipEventSynchronize(ev.b));
     float ms = 0.f;
     HIP_RC(hipEventElapsedTime(&ms, ev.a, ev.b));
     *avg_us = ms * 1000.f / (float)iters;
     return 0;
+}
+
+extern "C" int32_t bertx_bench_attention(int32_t n_seqs, int32_t len, int32_t n_head, int32_t dh, int32_t variant,
+                                         int32_t iters, float *avg_us)
+{
+    return bench_attention(n_seqs, len, 0, n_head, dh, variant, iters, avg_us);
+}
+
+extern "C" int32_t bertx_bench_attention_kv(int32_t n_seqs, int32_t len, int32_t n_keys, int32_t n_head, int32_t dh,
+                                            int32_t variant, int32_t iters, float *avg_us)
+{
+    if (n_keys < 1 || n_keys > len) return -1;
+    return bench_attention(n_seqs, len, n_keys, n_head, dh, variant, iters, avg_us);
 }
 
 namespace emb {
@@ -881,13 +897,23 @@ extern "C" int32_t bertx_test_f32_rows(int32_t kind, const float *x, const int32
     return 0;
 }
 
-extern "C" int32_t bertx_test_attention_f32(const float *qkv, const int32_t *cu, int32_t n_seqs, int32_t max_len,
-                                            int32_t n_head, int32_t d, int32_t era, float *out, int32_t out_rows)
+// host key counts of a hook: each within 1 .. the sentence's length (cu already checked)
+static bool hook_keys_ok(const int32_t *keys, const int32_t *cu, int32_t n_seqs)
+{
+    for (int i = 0; i < n_seqs; ++i)
+        if (keys[i] < 1 || keys[i] > cu[i + 1] - cu[i]) return false;
+    return true;
+}
+
+extern "C" int32_t bertx_test_attention_f32_kv(const float *qkv, const int32_t *cu, const int32_t *keys,
+                                               int32_t n_seqs, int32_t max_len, int32_t n_head, int32_t d,
+                                               int32_t era, float *out, int32_t out_rows)
 {
     using namespace emb;
     if (!qkv || !out || n_head <= 0 || d <= 0 || d % n_head || !hook_cu_ok(cu, n_seqs, max_len) ||
         out_rows < cu[n_seqs] || hip_device_count() == 0)
         return -1;
+    if (keys && !hook_keys_ok(keys, cu, n_seqs)) return -1;
     const size_t T = (size_t)cu[n_seqs];
     DeviceGuard guard(0);
     HIP_RC(guard.status());
@@ -898,11 +924,18 @@ extern "C" int32_t bertx_test_attention_f32(const float *qkv, const int32_t *cu,
     std::vector<uint16_t> tg, te;
     era_tables(tg, te);
     const uint16_t *de = (const uint16_t *)B.up(te.data(), te.size() * 2, 0);
+    const int32_t *dk = keys ? (const int32_t *)B.up(keys, (size_t)n_seqs * 4, 0) : nullptr;
     if (B.bad) return -1;
-    const int lrc = launch_f32_attention(dq, dcu, n_seqs, max_len, n_head, d, dout, nullptr, de, era != 0);
+    const int lrc = launch_f32_attention(dq, dcu, n_seqs, max_len, n_head, d, dout, nullptr, de, era != 0, dk);
     if (const int rc = hook_finish()) return rc;
     HIP_RC(hipMemcpy(out, dout, (size_t)out_rows * d * 4, hipMemcpyDeviceToHost));
     return lrc;
+}
+
+extern "C" int32_t bertx_test_attention_f32(const float *qkv, const int32_t *cu, int32_t n_seqs, int32_t max_len,
+                                            int32_t n_head, int32_t d, int32_t era, float *out, int32_t out_rows)
+{
+    return bertx_test_attention_f32_kv(qkv, cu, nullptr, n_seqs, max_len, n_head, d, era, out, out_rows);
 }
 
 // ---------------------------------------------------------------------------
@@ -910,8 +943,8 @@ extern "C" int32_t bertx_test_attention_f32(const float *qkv, const int32_t *cu,
 // buffer starts as NaN bits (0xffff), so a row the kernel did not write, and a
 // write past the rows it owns, both show.
 // ---------------------------------------------------------------------------
-extern "C" int32_t bertx_test_attention(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head,
-                                        int32_t d, int32_t variant, uint16_t *out)
+extern "C" int32_t bertx_test_attention_kv(const uint16_t *qkv, const int32_t *cu, const int32_t *keys,
+                                           int32_t n_seqs, int32_t n_head, int32_t d, int32_t variant, uint16_t *out)
 {
     using namespace emb;
     if (!qkv || !cu || !out || n_seqs <= 0 || n_head <= 0 || d % n_head || hip_device_count() == 0) return -1;
@@ -922,6 +955,7 @@ extern "C" int32_t bertx_test_attention(const uint16_t *qkv, const int32_t *cu, 
         if (cu[i + 1] < cu[i]) return -1;
         max_len = std::max(max_len, cu[i + 1] - cu[i]);
     }
+    if (keys && !hook_keys_ok(keys, cu, n_seqs)) return -1;
     const size_t T = (size_t)cu[n_seqs];
     // Rows behind the T packed ones.  qkv: the widest over-read of any kernel
     // launched here is the streaming kernel's, which loads the Q rows of all ATT_QT
@@ -936,12 +970,13 @@ extern "C" int32_t bertx_test_attention(const uint16_t *qkv, const int32_t *cu, 
     const uint16_t *dq = (const uint16_t *)B.up(qkv, T * 3 * d * 2, (T + PAD) * 3 * d * 2);
     const int32_t *dcu = (const int32_t *)B.up(cu, ((size_t)n_seqs + 1) * 4, 0);
     uint16_t *dout = (uint16_t *)B.up(nullptr, 0, (T + PAD) * d * 2);
+    const int32_t *dk = keys ? (const int32_t *)B.up(keys, (size_t)n_seqs * 4, 0) : nullptr;
     if (B.bad) return -1;
     HIP_RC(hipMemset(dout, 0xff, (T + PAD) * d * 2));
     ScopedSet var(g_att_variant, variant);
     // variant -1: the streaming kernel, reached by claiming a length past the LDS form
     launch_attention(dq, dcu, n_seqs, variant == -1 ? std::max(max_len, ATT_LDS_MAX + 1) : max_len, n_head, d, dout,
-                     nullptr);
+                     nullptr, dk);
     if (const int rc = hook_finish()) return rc;
     HIP_RC(hipMemcpy(out, dout, T * d * 2, hipMemcpyDeviceToHost));
     std::vector<uint16_t> pad(PAD * d);
@@ -949,6 +984,12 @@ extern "C" int32_t bertx_test_attention(const uint16_t *qkv, const int32_t *cu, 
     for (const uint16_t v : pad)
         if (v != 0xffff) return -5;   // a store past the last sentence
     return 0;
+}
+
+extern "C" int32_t bertx_test_attention(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t n_head,
+                                        int32_t d, int32_t variant, uint16_t *out)
+{
+    return bertx_test_attention_kv(qkv, cu, nullptr, n_seqs, n_head, d, variant, out);
 }
 
 extern "C" int32_t bertx_test_attention_ran(void) { return emb::g_att_ran; }

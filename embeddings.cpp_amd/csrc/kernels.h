@@ -133,8 +133,12 @@ extern thread_local int g_att_variant;
 extern thread_local int g_att_ran;
 
 // Per (sentence, head) softmax(Q K^T / sqrt(dh)) V over the sentence's own keys.
+// keys (device int32 [n_seqs], or null): sentence b's first keys[b] rows are its
+// keys and values, 1 <= keys[b] <= len, every row stays a query (both attention
+// launchers).  Null is the plain launch: the same kernels, none reads a count.
+// (No default: every caller says whether it has counts.)
 void launch_attention(const uint16_t *qkv, const int32_t *cu, int32_t n_seqs, int32_t max_len, int32_t n_head,
-                      int32_t d, uint16_t *out, hipStream_t s);
+                      int32_t d, uint16_t *out, hipStream_t s, const int32_t *keys);
 
 // out[b] = mean_{i<len} LN(y[start+i]) / ||.||  (bert.cpp:1087-1095), from z and
 // the row statistics (LN fold).  Two stages: per-64-token-chunk partial sums into
@@ -182,7 +186,8 @@ int launch_f32_gemm(const float *X, int32_t M, const float *W, int32_t N, int32_
 // era_order (the q8-activation chain): Q K^T and P V summed in ggml_vec_dot_f32's own
 // order (eight lanes, rounded multiply and add, pairwise horizontal sum).
 int launch_f32_attention(const float *qkv, const int32_t *cu, int32_t n_seqs, int32_t max_len, int32_t n_head,
-                         int32_t d, float *out, hipStream_t s, const uint16_t *exp_tab, bool era_order = false);
+                         int32_t d, float *out, hipStream_t s, const uint16_t *exp_tab, bool era_order,
+                         const int32_t *keys);
 // out[b] = mean_{i<len} x[start + i] / ||.|| (bert.cpp:1087-1095); era_order: the token
 // sum in ggml_vec_dot_f32's order.
 void launch_f32_pool(const float *x, const int32_t *cu, int32_t n_seqs, int32_t d, float *out, hipStream_t s,

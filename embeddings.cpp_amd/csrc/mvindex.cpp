@@ -358,7 +358,7 @@ bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t c
                     hipMalloc((void **)&mv->st_q, (size_t)kMaxLq * w * 4) == hipSuccess &&
                     hipMalloc((void **)&mv->st_out, (size_t)kStageIds * 4) == hipSuccess &&
                     hipMalloc((void **)&mv->st_ids, (size_t)kStageIds * 4) == hipSuccess &&
-                    hipMalloc((void **)&mv->st_tok, (size_t)(kMaxLq + 2) * 4) == hipSuccess;
+                    hipMalloc((void **)&mv->st_tok, (size_t)(kMaxLq + 3) * 4) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         errorf("bertx_mvindex_create: device %d could not allocate %zu bytes of token rows (+ %lld table entries)\n",
@@ -801,13 +801,17 @@ int32_t bertx_mvindex_score_text_colbert(struct bertx_mvindex *mv, struct bert_c
     if (const int32_t rc = emb::colbert_ctx_ok(mv, ctx, "bertx_mvindex_score_text_colbert", &slot)) return rc;
     if (query_maxlen < 4 || query_maxlen > emb::kMaxLq || query_maxlen > bert_n_max_tokens(ctx)) return -1;
     try {
-        // ids [L] and cu {0, L} in one staging buffer, as _score_text; L = query_maxlen
-        std::vector<int32_t> h((size_t)emb::kMaxLq + 2, 0), keep((size_t)emb::kMaxLq);
-        int32_t L = 0;
-        if (bertx_tokenize_colbert(ctx, query, 0, query_maxlen, h.data(), keep.data(), &L) != 0 || L != query_maxlen)
+        // ids [L], cu {0, L} and the key count in one staging buffer, as _score_text; L = query_maxlen
+        std::vector<int32_t> h((size_t)emb::kMaxLq + 3, 0), keep((size_t)emb::kMaxLq);
+        int32_t L = 0, nk = 0;
+        if (bertx_tokenize_colbert_ex(ctx, query, 0, query_maxlen, h.data(), keep.data(), &L, &nk) != 0 ||
+            L != query_maxlen)
             return -1;
         h[(size_t)emb::kMaxLq] = 0;
         h[(size_t)emb::kMaxLq + 1] = L;
+        h[(size_t)emb::kMaxLq + 2] = nk;
+        // the context's setting: [MASK] rows as keys (no counts), or the rows up to [SEP] only
+        const bool counted = bertx_mask_keys(ctx) == 0;
         std::lock_guard<std::mutex> lk(mv->mu);
         DeviceGuard g(mv->ordinal);
         HIP_RC(g.status());
@@ -817,8 +821,9 @@ int32_t bertx_mvindex_score_text_colbert(struct bertx_mvindex *mv, struct bert_c
             emb::Ordered o(*mv, mv->stream);
             HIP_RC(hipMemcpyAsync(mv->st_tok, h.data(), h.size() * 4, hipMemcpyHostToDevice, mv->stream));
             HIP_RC(hipStreamSynchronize(mv->stream));   // h is pageable and leaves scope
-            rc = bertx_forward_project_device(ctx, slot, mv->st_tok, nullptr, mv->st_tok + emb::kMaxLq, 1, L, L, nullptr,
-                                              0, mv->st_q, mv->stream);
+            rc = bertx_forward_device_kv(ctx, slot, mv->st_tok, nullptr, mv->st_tok + emb::kMaxLq,
+                                         counted ? mv->st_tok + emb::kMaxLq + 2 : nullptr, 1, L, L, BERTX_OUT_PROJ,
+                                         nullptr, 0, mv->st_q, mv->stream);
         }
         if (rc != 0) return rc < 0 ? rc : -1;
         return emb::score_host_ids(*mv, mv->st_q, L, ids, n, out);
@@ -956,14 +961,16 @@ int32_t bertx_mvindex_search_texts_colbert(struct bertx_mvindex *mv, struct bert
         // is the [n][L][w] layout itself
         const size_t L = (size_t)query_maxlen;
         const int w = mv->w;
-        std::vector<int32_t> tok((size_t)n * L), lens((size_t)n), rcs((size_t)n, 0);
+        std::vector<int32_t> tok((size_t)n * L), lens((size_t)n), nks((size_t)n), rcs((size_t)n, 0);
         emb::TaskPool::instance().run(((int64_t)n + 7) / 8, n_threads > 0 ? n_threads : 1, [&](int64_t blk) {
             const int e = (int)std::min<int64_t>(n, 8 * blk + 8);
             std::vector<int32_t> keep(L);
             for (int i = (int)(8 * blk); i < e; ++i)
-                rcs[(size_t)i] = bertx_tokenize_colbert(ctx, texts[i], 0, query_maxlen, tok.data() + i * L, keep.data(),
-                                                        &lens[(size_t)i]);
+                rcs[(size_t)i] = bertx_tokenize_colbert_ex(ctx, texts[i], 0, query_maxlen, tok.data() + i * L, keep.data(),
+                                                           &lens[(size_t)i], &nks[(size_t)i]);
         });
+        // the context's setting: [MASK] rows as keys (no counts), or each query's rows up to [SEP] only
+        const bool counted = bertx_mask_keys(ctx) == 0;
         for (int32_t i = 0; i < n; ++i)
             if (rcs[(size_t)i] != 0 || lens[(size_t)i] != query_maxlen) return -1;
         std::vector<float> hs((size_t)n * k);
@@ -972,10 +979,11 @@ int32_t bertx_mvindex_search_texts_colbert(struct bertx_mvindex *mv, struct bert
         DeviceGuard g(mv->ordinal);
         HIP_RC(g.status());
         const int32_t cap = std::min<int32_t>(n, emb::kSearchTexts);
-        emb::DevBuf d_tok, d_cu, d_q;
+        emb::DevBuf d_tok, d_cu, d_q, d_nk;
         HIP_RC(hipMalloc(&d_tok.p, (size_t)cap * L * 4));
         HIP_RC(hipMalloc(&d_cu.p, (size_t)(cap + 1) * 4));
         HIP_RC(hipMalloc(&d_q.p, (size_t)cap * L * w * 4));
+        if (counted) HIP_RC(hipMalloc(&d_nk.p, (size_t)cap * 4));
         cu.resize((size_t)cap + 1);
         for (int32_t j = 0; j <= cap; ++j) cu[(size_t)j] = j * query_maxlen;
         for (int32_t i0 = 0; i0 < n; i0 += cap) {
@@ -986,8 +994,11 @@ int32_t bertx_mvindex_search_texts_colbert(struct bertx_mvindex *mv, struct bert
                 emb::Ordered o(*mv, mv->stream);
                 HIP_RC(hipMemcpyAsync(d_tok.p, tok.data() + (size_t)i0 * L, (size_t)T * 4, hipMemcpyHostToDevice, mv->stream));
                 HIP_RC(hipMemcpyAsync(d_cu.p, cu.data(), (size_t)(m + 1) * 4, hipMemcpyHostToDevice, mv->stream));
-                rc = bertx_forward_project_device(ctx, slot, (const int32_t *)d_tok.p, nullptr, (const int32_t *)d_cu.p, m,
-                                                  query_maxlen, T, nullptr, 0, (float *)d_q.p, mv->stream);
+                if (counted)
+                    HIP_RC(hipMemcpyAsync(d_nk.p, nks.data() + i0, (size_t)m * 4, hipMemcpyHostToDevice, mv->stream));
+                rc = bertx_forward_device_kv(ctx, slot, (const int32_t *)d_tok.p, nullptr, (const int32_t *)d_cu.p,
+                                             (const int32_t *)d_nk.p, m, query_maxlen, T, BERTX_OUT_PROJ, nullptr, 0,
+                                             (float *)d_q.p, mv->stream);
             }
             if (rc == 0)
                 rc = emb::search_to_host(*mv, (const float *)d_q.p, m, query_maxlen, k, hs.data() + (size_t)i0 * k,

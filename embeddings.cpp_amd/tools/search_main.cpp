@@ -3,7 +3,7 @@
 // the GPU and the search fused there (bertx_index_*).
 //
 // usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8]
-//               [-r RERANK_MODEL [-c N] | -l [-c N | -a] | -L COLBERT_MODEL [-c N | -a]] [-S f16|int8]
+//               [-r RERANK_MODEL [-c N] | -l [-c N | -a] | -L COLBERT_MODEL [-M] [-c N | -a]] [-S f16|int8]
 // One text per line of CORPUS.txt; queries from stdin, one per line, `q` or EOF ends.
 // Per hit one line: rank<TAB>id<TAB>score<TAB>text.
 // -s: how the index stores its rows (bertx_index_create_ex): f16, the default, or int8
@@ -22,6 +22,9 @@
 // punctuation rows dropped, doc_maxlen 180 capped at the model's n_max_tokens); the
 // candidates are re-scored with bertx_mvindex_score_text_colbert ([Q] marker, [MASK]
 // augmentation to query_maxlen 32).
+// -M: with -L, no row of a query attends to its [MASK] rows (bertx_set_mask_keys(ctx, 0):
+// ColBERT's attend_to_mask_tokens = false, as colbertv2.0 was trained).  -M without -L
+// is a usage error.
 // -a: with -l or -L, full-scan late interaction: no embedding index is created or
 // consulted; every query goes through bertx_mvindex_search_texts (-l) or
 // bertx_mvindex_search_texts_colbert (-L), which score every stored document by MaxSim
@@ -46,7 +49,7 @@ int main(int argc, char **argv)
 {
     const char *model = nullptr, *corpus = nullptr, *rerank = nullptr, *colbert = nullptr;
     int k = 3, threads = 4, cand = 0, storage = BERTX_INDEX_F16, mv_storage = -1;
-    bool late = false, all = false;
+    bool late = false, all = false, no_mask_keys = false;
     for (int i = 1; i < argc; ++i) {
         const bool has = i + 1 < argc;
         if (!std::strcmp(argv[i], "-m") && has) model = argv[++i];
@@ -61,6 +64,7 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "-c") && has) cand = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "-l")) late = true;
         else if (!std::strcmp(argv[i], "-a")) all = true;
+        else if (!std::strcmp(argv[i], "-M")) no_mask_keys = true;
         else if (!std::strcmp(argv[i], "-L") && has) colbert = argv[++i];
         else { model = nullptr; break; }
     }
@@ -68,9 +72,10 @@ int main(int argc, char **argv)
     const bool bad_all = all && ((!late && !colbert) || cand != 0);
     if (second && !all && cand == 0) cand = std::min(128, 4 * k);
     if (bad_all || !model || !corpus || k < 1 || k > 128 || threads < 1 || (int)(rerank != nullptr) + late + (colbert != nullptr) > 1 ||
-        (second && !all ? cand < k || cand > 128 : cand != 0) || (mv_storage >= 0 && !late && !colbert)) {
+        (second && !all ? cand < k || cand > 128 : cand != 0) || (mv_storage >= 0 && !late && !colbert) ||
+        (no_mask_keys && !colbert)) {
         std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads] [-s f16|int8] "
-                             "[-r RERANK_MODEL [-c N (k..128, default 4 k)] | -l [-c N | -a] | -L COLBERT_MODEL [-c N | -a]] "
+                             "[-r RERANK_MODEL [-c N (k..128, default 4 k)] | -l [-c N | -a] | -L COLBERT_MODEL [-M] [-c N | -a]] "
                              "[-S f16|int8 (the token store of -l / -L)]\n",
                      argv[0]);
         return 2;
@@ -118,6 +123,7 @@ int main(int argc, char **argv)
         }
         doc_maxlen = std::min<int32_t>(180, bert_n_max_tokens(rctx));
         query_maxlen = std::min<int32_t>(32, bert_n_max_tokens(rctx));
+        if (no_mask_keys) bertx_set_mask_keys(rctx, 0);
     }
     if (mv_storage < 0) mv_storage = BERTX_INDEX_F16;
     bertx_index *idx = all ? nullptr : bertx_index_create_ex(ctx, 0, (int32_t)texts.size(), storage);

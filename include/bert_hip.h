@@ -762,7 +762,7 @@ BERT_API int32_t bertx_bench_search_add_rate_ex(int32_t d, int32_t N, int32_t st
  * projection the un-prefixed linear.weight [dim][hidden]); it refuses (message,
  * non-zero) a checkpoint without linear.weight, with a linear.bias, or with a shape the
  * loader would refuse, and prints one line when the directory's artifact.metadata says
- * attend_to_mask_tokens is false (see "Not provided").  bertx_proj_dim: the record's
+ * attend_to_mask_tokens is false (see "Key counts").  bertx_proj_dim: the record's
  * dim, 0 for a file without one; bertx_proj_width = 64 ceil(dim / 64): the width of
  * every projected row and a legal bertx_mvindex_create width (a 96-dim checkpoint gives
  * 128-wide rows whose last 32 columns are +0, which changes no dot product).  Both work
@@ -822,10 +822,44 @@ BERT_API int32_t bertx_bench_search_add_rate_ex(int32_t d, int32_t N, int32_t st
  * bertx_bench_project (device 0, no context): mode 0 on T random rows; average device
  * time of `iters` launches after 3 warm-up launches.
  *
- * Not provided: [MASK] rows excluded as attention keys (ColBERT's attend_to_mask_tokens
- * = false, the setting colbertv2.0 was trained with): here the augmentation rows are
- * ordinary tokens of the sentence; excluding them needs a key length separate from the
- * row count in the attention kernels.
+ * Key counts: [MASK] rows that are not attention keys (ColBERT's attend_to_mask_tokens =
+ * false, the setting colbertv2.0 was trained with).  A sentence of len rows may carry one
+ * number keys, 1 <= keys <= len: all len rows are queries and produce output rows, only
+ * the first keys rows are keys and values of every layer's attention -- HF's
+ * attention_mask of a right-padded row, on the packed layout.  In every attention
+ * kernel of the three chains a key j >= keys scores -inf through the mask that handles
+ * j >= len (its P is exactly 0); K / V loads and the 64-key block loops run over
+ * ceil(keys / 64) blocks, an excluded block is neither loaded nor multiplied; the query
+ * rows, the Q loads and the stores stay bounded by len.  Nothing else of the forward
+ * changes.  A sentence's rows depend on its ids, its types and its key count only, bit
+ * for bit: not on the batch, the order, or the kernel the batch selects.  With
+ * keys == len the rows are those of the same call without counts.
+ * bertx_forward_device_kv: bertx_forward_device_ex / bertx_forward_project_device with
+ * d_keys int32[n_seqs] on that GPU (trusted: 1 <= d_keys[b] <= the sentence's length).
+ * out_kind BERTX_OUT_TOKENS or BERTX_OUT_PROJ, any other -1 (the pooled and logits
+ * outputs take no counts, so a forward with counts never runs the pruned last layer);
+ * d_rows / n_rows: the row map of bertx_forward_project_device, used with PROJ only
+ * (NULL: every row).  d_keys NULL: exactly the launches and bits of those two entries.
+ * Asynchronous and capturable as they are; the pointer is part of a captured forward's
+ * key.  -6: PROJ on a file without the record.
+ * bertx_forward_tokens_kv / bertx_forward_project_kv: the host forms with n_keys int32[n],
+ * one count per sentence, which travels with its sentence through the routing and the
+ * chunks; a count outside 1 .. n_tokens[i] returns -1 with every output untouched;
+ * n_keys NULL is bertx_forward_tokens / bertx_forward_project.
+ * bertx_tokenize_colbert_ex: bertx_tokenize_colbert plus *n_keys: for a query the rows up
+ * to and including [SEP], 3 + min(pieces, maxlen - 3); for a document *n_tokens.
+ * bertx_set_mask_keys(ctx, on) / bertx_mask_keys: whether the ColBERT query forms of the
+ * store keep the [MASK] rows as keys.  1 (the default): they do, no counts are passed;
+ * 0: bertx_mvindex_score_text_colbert and bertx_mvindex_search_texts_colbert pass each
+ * query's count to the forward.  One value per context, for all its replicas;
+ * BERT_MASK_KEYS=0|1 is read at every load as BERT_POOL is (another value: a load
+ * error); a value other than 0 / 1: -1.  The document forms and every other entry
+ * ignore it.
+ * bertx_test_attention_kv / bertx_test_attention_f32_kv (parity hooks): the hooks
+ * without _kv plus keys, host int32[n_seqs] (NULL: the plain hook), with their
+ * NaN-filled output, guard rows and return codes; a count outside 1 .. len: -1.
+ * bertx_bench_attention_kv: bertx_bench_attention with the one count n_keys for every
+ * sentence (1 .. len, else -1).
  * (The ColBERT text forms follow the store's kind: an int8 store takes them unchanged.)
  */
 enum { BERTX_OUT_PROJ = 3 };
@@ -851,6 +885,25 @@ BERT_API int32_t bertx_test_project(int32_t mode, const void *src, const float *
                                     int32_t T, int32_t d, const float *W, int32_t dim, const int32_t *rows,
                                     int32_t n_out, float *out, int32_t out_rows);
 BERT_API int32_t bertx_bench_project(int32_t d, int32_t dim, int32_t T, int32_t iters, float *avg_us);
+BERT_API int32_t bertx_forward_device_kv(struct bert_ctx *ctx, int32_t slot, const int32_t *d_ids, const int32_t *d_types,
+                                         const int32_t *d_cu, const int32_t *d_keys, int32_t n_seqs, int32_t max_len,
+                                         int32_t total_tokens, int32_t out_kind, const int32_t *d_rows, int32_t n_rows,
+                                         float *d_out, void *stream);
+BERT_API int32_t bertx_forward_tokens_kv(struct bert_ctx *ctx, int32_t n, bert_vocab_id **batch_tokens,
+                                         int32_t *n_tokens, const int32_t *n_keys, float **out);
+BERT_API int32_t bertx_forward_project_kv(struct bert_ctx *ctx, int32_t n, bert_vocab_id **batch_tokens,
+                                          int32_t *n_tokens, const int32_t *n_keys, float **out);
+BERT_API int32_t bertx_tokenize_colbert_ex(struct bert_ctx *ctx, const char *text, int32_t kind, int32_t maxlen,
+                                           bert_vocab_id *ids, int32_t *keep, int32_t *n_tokens, int32_t *n_keys);
+BERT_API int32_t bertx_set_mask_keys(struct bert_ctx *ctx, int32_t on);
+BERT_API int32_t bertx_mask_keys(struct bert_ctx *ctx);
+BERT_API int32_t bertx_test_attention_kv(const uint16_t *qkv, const int32_t *cu, const int32_t *keys, int32_t n_seqs,
+                                         int32_t n_head, int32_t d, int32_t variant, uint16_t *out);
+BERT_API int32_t bertx_test_attention_f32_kv(const float *qkv, const int32_t *cu, const int32_t *keys, int32_t n_seqs,
+                                             int32_t max_len, int32_t n_head, int32_t d, int32_t era, float *out,
+                                             int32_t out_rows);
+BERT_API int32_t bertx_bench_attention_kv(int32_t n_seqs, int32_t len, int32_t n_keys, int32_t n_head, int32_t dh,
+                                          int32_t variant, int32_t iters, float *avg_us);
 
 BERT_API const char *bertx_version(void);
 
