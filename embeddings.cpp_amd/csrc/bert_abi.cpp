@@ -6,6 +6,7 @@
 #include "bert_hip.h"
 #include "ggml.h"
 
+#include "chunk_rule.h"
 #include "engine.h"
 #include "task_pool.h"
 #include "tokenizer.h"
@@ -103,8 +104,6 @@ struct bert_ctx {
 
 namespace {
 
-constexpr int64_t kChunkTokens = 1 << 17;   // tokens per device forward (workspace bound)
-constexpr int kChunkSeqs = 4096;            // sentences per device forward (pool / output staging bound)
 // A call is split only over replicas that are idle (no routed work in flight), and
 // only while each share keeps at least kMinShareTokens.  The choice, from the
 // measured per-share latency on one replica (scripts/share_curve.py,
@@ -156,7 +155,7 @@ double sentence_cost(const emb::HParams &hp, int L)
 // replicas, the k least-loaded by the cost still in flight on them (ties rotate,
 // so consecutive small calls spread over the replicas too); its sentences are split over those k
 // by cost, longest first to the least-loaded share (LPT).  Each replica walks its
-// sentences in chunks of <= kChunkTokens on its persistent worker thread (the
+// sentences in chunks (chunk_rule.h) on its persistent worker thread (the
 // caller runs one share itself).  Results are independent of the routing and the
 // split: every kernel computes a sentence from its own tokens only.
 // types (or null) ride along with the ids; logits: outs[i] receives the n_labels raw
@@ -221,8 +220,7 @@ int run_forward(bert_ctx *ctx, const int32_t *const *toks, const int32_t *lens, 
         while (i < mine.size()) {
             tp.clear(); lp.clear(); op.clear(); yp.clear();
             int64_t tok = 0;
-            while (i < mine.size() && (tp.empty() || (tok + lens[mine[i]] <= kChunkTokens &&
-                                                       (int)tp.size() < kChunkSeqs))) {
+            for (const size_t e = emb::chunk_end([&](size_t j) { return lens[mine[j]]; }, i, mine.size()); i < e;) {
                 const int idx = mine[i++];
                 tp.push_back(toks[idx]); lp.push_back(lens[idx]); op.push_back(outs[idx]);
                 if (types) yp.push_back(types[idx]);
@@ -732,11 +730,9 @@ static int32_t forward_rows(struct bert_ctx *ctx, int32_t n, bert_vocab_id **bat
         int i = 0;
         while (i < n && rc == 0) {
             tp.clear(); lp.clear(); op.clear(); kp.clear();
-            int64_t tok = 0;
-            while (i < n && (tp.empty() || (tok + n_tokens[i] <= kChunkTokens && (int)tp.size() < kChunkSeqs))) {
+            for (const int e = (int)emb::chunk_end([&](size_t j) { return n_tokens[j]; }, (size_t)i, (size_t)n); i < e; ++i) {
                 tp.push_back(batch_tokens[i]); lp.push_back(n_tokens[i]); op.push_back(out[i]);
                 if (n_keys) kp.push_back(n_keys[i]);
-                tok += n_tokens[i++];
             }
             rc = D.forward_host(tp.data(), lp.data(), (int)tp.size(), op.data(), true, nullptr, false, proj,
                                 n_keys ? kp.data() : nullptr);

@@ -2,11 +2,14 @@
 // matrix of f16 or int8 rows in HBM in the search kernel's fragment order (kernels.h),
 // the fused top-k search over it, and the text forms on top of bert_encode_batch.
 // After creation an index knows only its device ordinal, its width and its storage.
+// The ordering of its device operations and the unpackers of the read-back forms are
+// shared with the token store (store_common.h).
 #include "bert.h"
 #include "bert_hip.h"
 
 #include "engine.h"
 #include "hip_check.h"
+#include "store_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -28,15 +31,13 @@ struct bertx_index {
     float *st_rows = nullptr, *st_scores = nullptr;
     int32_t *st_ids = nullptr;
     hipStream_t stream = nullptr;
-    // every device operation on the index is ordered after the previous one: an
-    // operation on another stream first waits (on the device) for this event
-    hipEvent_t done = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool any = false;
+    emb::StoreOrder ord;
     std::mutex mu;
     ~bertx_index()
     {
         emb::DeviceGuard g(ordinal);
+        // (no wait for ord.done, unlike the token store: an operation in flight on a caller's
+        // stream reads device memory only, and hipFree waits for the device itself)
         if (stream) (void)hipStreamSynchronize(stream);
         if (rows) (void)hipFree(rows);
         if (scales) (void)hipFree(scales);
@@ -44,7 +45,7 @@ struct bertx_index {
         if (st_rows) (void)hipFree(st_rows);
         if (st_scores) (void)hipFree(st_scores);
         if (st_ids) (void)hipFree(st_ids);
-        if (done) (void)hipEventDestroy(done);
+        if (ord.done) (void)hipEventDestroy(ord.done);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -55,33 +56,6 @@ namespace {
 constexpr int kStage = 256;   // rows / queries per staged chunk of the host forms
 constexpr int kMaxK = 128;
 
-bool capturing(hipStream_t s)
-{
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return st != hipStreamCaptureStatusNone;
-}
-
-// Orders an operation on `s` after the index's previous one and, on destruction,
-// records it as the new previous one.  A capturing stream records and waits for
-// nothing outside its graph: the captured operation is ordered by its stream alone.
-struct Ordered {
-    bertx_index &ix;
-    hipStream_t s;
-    const bool cap;
-    Ordered(bertx_index &i, hipStream_t st) : ix(i), s(st), cap(capturing(st))
-    {
-        if (!cap && ix.any && ix.last_stream != s) (void)hipStreamWaitEvent(s, ix.done, 0);
-    }
-    ~Ordered()
-    {
-        if (cap) return;
-        (void)hipEventRecord(ix.done, s);
-        ix.last_stream = s;
-        ix.any = true;
-    }
-};
-
 int32_t add_device_locked(bertx_index &ix, const float *d_rows, int32_t n, hipStream_t s)
 {
     if (!d_rows || n < 1) return -1;
@@ -90,7 +64,7 @@ int32_t add_device_locked(bertx_index &ix, const float *d_rows, int32_t n, hipSt
         return -2;
     }
     {
-        Ordered o(ix, s);
+        Ordered o(ix.ord, s);
         const int rc = launch_index_add(d_rows, n, ix.d, ix.n, ix.storage, ix.rows, ix.scales, s);
         if (rc != 0) return rc;
     }
@@ -103,7 +77,7 @@ int32_t search_device_locked(bertx_index &ix, const float *d_q, int32_t B, int32
                              hipStream_t s)
 {
     if (!d_q || !d_scores || !d_ids || B < 1 || k < 1 || k > kMaxK) return -1;
-    Ordered o(ix, s);
+    Ordered o(ix.ord, s);
     return launch_search(ix.rows, ix.scales, ix.storage, ix.n, ix.d, d_q, B, k, ix.scratch, d_scores, d_ids, s);
 }
 
@@ -138,7 +112,7 @@ bertx_index *index_create_on(int ordinal, int d, int64_t capacity, int storage)
     const size_t row_bytes = padded * (size_t)d * (storage == BERTX_INDEX_I8 ? 1 : 2);
     const size_t scratch_bytes = (size_t)64 * (size_t)search_max_workgroups(capacity) * kMaxK * 8;
     const bool ok = search_prepare_device() == 0 && hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking) == hipSuccess &&
-                    hipEventCreateWithFlags(&ix->done, hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(&ix->ord.done, hipEventDisableTiming) == hipSuccess &&
                     hipMalloc(&ix->rows, row_bytes) == hipSuccess && hipMalloc(&ix->scratch, scratch_bytes) == hipSuccess &&
                     (storage != BERTX_INDEX_I8 || hipMalloc((void **)&ix->scales, padded * 4) == hipSuccess) &&
                     hipMalloc((void **)&ix->st_rows, (size_t)kStage * d * 4) == hipSuccess &&
@@ -193,6 +167,8 @@ int32_t bertx_index_clear(struct bertx_index *idx)
 {
     if (!idx) return -1;
     std::lock_guard<std::mutex> lk(idx->mu);
+    // (no wait for the device, unlike the token store's clear: the index keeps no host image
+    // that a copy in flight could still read, and the next add is ordered behind every search)
     idx->n = 0;
     return 0;
 }
@@ -249,22 +225,16 @@ int32_t bertx_index_add(struct bertx_index *idx, const float *rows, int32_t n)
 static int32_t read_rows_i8(struct bertx_index *idx, int32_t first, int32_t n, std::vector<int8_t> &q,
                             std::vector<float> &scale)
 {
-    const int d = idx->d, KB = d / 64;
+    const int d = idx->d;
     const int64_t g0 = first / 16, g1 = ((int64_t)first + n + 15) / 16;
     const size_t group_bytes = (size_t)16 * d;
     std::vector<int8_t> raw((size_t)(g1 - g0) * group_bytes);
     q.resize((size_t)n * d);
     scale.resize((size_t)n);
-    if (idx->any) HIP_RC(hipEventSynchronize(idx->done));
+    HIP_RC(idx->ord.wait());
     HIP_RC(hipMemcpy(raw.data(), (const int8_t *)idx->rows + (size_t)g0 * group_bytes, raw.size(), hipMemcpyDeviceToHost));
     HIP_RC(hipMemcpy(scale.data(), idx->scales + first, (size_t)n * 4, hipMemcpyDeviceToHost));
-    for (int64_t r = first; r < (int64_t)first + n; ++r) {
-        const int8_t *grp = raw.data() + (size_t)(r / 16 - g0) * group_bytes;
-        int8_t *o = q.data() + (size_t)(r - first) * d;
-        for (int kb = 0; kb < KB; ++kb)
-            for (int g = 0; g < 4; ++g)
-                std::memcpy(o + 64 * kb + 16 * g, grp + ((size_t)kb * 64 + 16 * g + (r & 15)) * 16, 16);
-    }
+    emb::unpack_i8_rows(raw.data(), 16 * g0, first, n, d, q.data());
     return 0;
 }
 
@@ -285,21 +255,14 @@ int32_t bertx_index_rows(struct bertx_index *idx, int32_t first, int32_t n, floa
                 for (int i = 0; i < idx->d; ++i) out[r * idx->d + i] = (float)q[r * idx->d + i] * scale[r];
             return 0;
         }
-        const int d = idx->d, KB = d / 32;
+        const int d = idx->d;
         const int64_t g0 = first / 16, g1 = ((int64_t)first + n + 15) / 16;
         const size_t group_halfs = (size_t)16 * d;
         std::vector<uint16_t> raw((size_t)(g1 - g0) * group_halfs);
-        if (idx->any) HIP_RC(hipEventSynchronize(idx->done));
+        HIP_RC(idx->ord.wait());
         HIP_RC(hipMemcpy(raw.data(), (const uint16_t *)idx->rows + (size_t)g0 * group_halfs, raw.size() * 2,
                          hipMemcpyDeviceToHost));
-        for (int64_t r = first; r < (int64_t)first + n; ++r) {
-            const uint16_t *grp = raw.data() + (size_t)(r / 16 - g0) * group_halfs;
-            float *o = out + (size_t)(r - first) * d;
-            for (int kb = 0; kb < KB; ++kb)
-                for (int q = 0; q < 4; ++q)
-                    for (int j = 0; j < 8; ++j)
-                        o[32 * kb + 8 * q + j] = emb::f16_to_f32(grp[((size_t)kb * 64 + 16 * q + (r & 15)) * 8 + j]);
-        }
+        emb::unpack_f16_rows(raw.data(), 16 * g0, first, n, d, out);
     } catch (const std::bad_alloc &) {
         emb::errorf("bertx_index_rows: out of host memory\n");
         return -1;

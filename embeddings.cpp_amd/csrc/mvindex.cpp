@@ -3,12 +3,17 @@
 // order, f16 (kernels.h, maxsim.hip) or int8 with one f32 per token slot (maxsim_i8.hip),
 // the fused MaxSim scorer over it, and the text forms on top of the per-token forward.
 // After creation a store knows only its device ordinal, its width and its storage kind.
-// The ordering rules are the embedding index's (index.cpp).
+// The ordering rules and the unpackers are shared with the embedding index
+// (store_common.h).  A text form is an entry point's argument checks, one of two
+// tokenizers that describe the call's texts as a TextRows, and one body per verb (add,
+// score, search); the bodies do not know which tokenizer ran.
 #include "bert.h"
 #include "bert_hip.h"
 
+#include "chunk_rule.h"
 #include "engine.h"
 #include "hip_check.h"
+#include "store_common.h"
 #include "task_pool.h"
 
 #include <algorithm>
@@ -36,21 +41,21 @@ struct bertx_mvindex {
     int32_t *st_ids = nullptr, *st_tok = nullptr;
     void *search_scratch = nullptr;        // the partial lists of the full-scan search (maxsim_search_scratch_bytes)
     hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;             // completion of the last device operation on the store
-    hipStream_t last_stream = nullptr;
-    bool any = false;
+    emb::StoreOrder ord;
     std::mutex mu;
     ~bertx_mvindex()
     {
         emb::DeviceGuard g(ordinal);
         if (stream) (void)hipStreamSynchronize(stream);
-        if (any && done) (void)hipEventSynchronize(done);
+        // (unlike the embedding index: an add on a caller's stream copies from the page-locked
+        // images freed below)
+        if (ord.done) (void)ord.wait();
         for (void *p : {store, (void *)scales, (void *)table, (void *)src_off, (void *)st_rows, (void *)st_q, (void *)st_out,
                         (void *)st_ids, (void *)st_tok, search_scratch})
             if (p) (void)hipFree(p);
         if (h_table) (void)hipHostFree(h_table);
         if (h_src) (void)hipHostFree(h_src);
-        if (done) (void)hipEventDestroy(done);
+        if (ord.done) (void)hipEventDestroy(ord.done);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -63,34 +68,6 @@ constexpr int kStageIds = 65536;    // candidates per staged chunk of the host s
 constexpr int kMaxLq = 64;
 constexpr int kMaxK = 128;
 constexpr int kSearchTexts = 1024;  // queries per forward of the search text forms (at most 2^16 tokens)
-constexpr int64_t kChunkTokens = 1 << 17;   // per device forward of add_texts, as run_forward chunks
-constexpr int kChunkSeqs = 4096;
-
-bool capturing(hipStream_t s)
-{
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return st != hipStreamCaptureStatusNone;
-}
-
-// Orders an operation on `s` after the store's previous one and records it as the new
-// previous one (index.cpp Ordered; a capturing stream waits for and records nothing).
-struct Ordered {
-    bertx_mvindex &mv;
-    hipStream_t s;
-    const bool cap;
-    Ordered(bertx_mvindex &m, hipStream_t st) : mv(m), s(st), cap(capturing(st))
-    {
-        if (!cap && mv.any && mv.last_stream != s) (void)hipStreamWaitEvent(s, mv.done, 0);
-    }
-    ~Ordered()
-    {
-        if (cap) return;
-        (void)hipEventRecord(mv.done, s);
-        mv.last_stream = s;
-        mv.any = true;
-    }
-};
 
 // The first half of an add: checks the lens and both capacities and writes the new
 // documents' entries into the host images.  Returns 0 with *T the source rows and
@@ -160,7 +137,7 @@ int32_t add_device_locked(bertx_mvindex &mv, const float *d_rows, const int32_t 
     int32_t rc = plan_add(mv, lens, n, &T, &slots);
     if (rc != 0) return rc;
     {
-        Ordered o(mv, s);
+        Ordered o(mv.ord, s);
         rc = upload_entries(mv, n, s);
         if (rc == 0) rc = pack(mv, d_rows, 0, T, n, s);
     }
@@ -175,7 +152,7 @@ int32_t score_device_locked(bertx_mvindex &mv, const float *d_q, int32_t Lq, con
                             float *d_out, hipStream_t s)
 {
     if (!d_q || !d_out || Lq < 1 || Lq > kMaxLq || n < 1) return -1;
-    Ordered o(mv, s);
+    Ordered o(mv.ord, s);
     if (mv.storage == BERTX_INDEX_I8)
         return launch_maxsim_i8(mv.store, mv.scales, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s);
     return launch_maxsim(mv.store, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s);
@@ -192,7 +169,7 @@ int32_t search_device_locked(bertx_mvindex &mv, const float *d_q, int32_t B, int
                              int32_t *d_ids, hipStream_t s)
 {
     if (!d_q || !d_scores || !d_ids || !search_args_ok("bertx_mvindex_search", B, Lq, k)) return -1;
-    Ordered o(mv, s);
+    Ordered o(mv.ord, s);
     return launch_maxsim_search(mv.store, mv.scales, mv.storage, mv.table, (int)mv.n_docs, mv.used_slots / 16, mv.w, d_q, B,
                                 Lq, k, mv.search_scratch, d_scores, d_ids, s);
 }
@@ -225,30 +202,25 @@ int32_t score_host_ids(bertx_mvindex &mv, const float *d_q, int32_t Lq, const in
 // caller holds the lock, has checked the id and has selected the device).
 int32_t read_doc_i8(bertx_mvindex &mv, int32_t id, int8_t *q, float *u)
 {
-    const int w = mv.w, KB = w / 64;
     const int64_t first = mv.h_table[2 * (size_t)id], len = mv.h_table[2 * (size_t)id + 1];
-    const size_t group_bytes = (size_t)16 * w, groups = (size_t)((len + 15) / 16);
+    const size_t group_bytes = (size_t)16 * mv.w, groups = (size_t)((len + 15) / 16);
     std::vector<int8_t> raw(groups * group_bytes);
     std::vector<float> us(groups * 16);
-    if (mv.any) HIP_RC(hipEventSynchronize(mv.done));
+    HIP_RC(mv.ord.wait());
     HIP_RC(hipMemcpy(raw.data(), (const int8_t *)mv.store + (size_t)first * group_bytes, raw.size(),
                      hipMemcpyDeviceToHost));
     HIP_RC(hipMemcpy(us.data(), mv.scales + (size_t)first * 16, us.size() * 4, hipMemcpyDeviceToHost));
-    for (int64_t r = 0; r < len; ++r) {
-        const int8_t *grp = raw.data() + (size_t)(r / 16) * group_bytes;
-        for (int kb = 0; kb < KB; ++kb)
-            for (int g = 0; g < 4; ++g)
-                std::memcpy(q + (size_t)r * w + 64 * kb + 16 * g, grp + ((size_t)kb * 64 + 16 * g + (r & 15)) * 16, 16);
-        u[r] = us[(size_t)r];
-    }
+    unpack_i8_rows(raw.data(), 0, 0, len, mv.w, q);
+    std::memcpy(u, us.data(), (size_t)len * 4);
     return 0;
 }
 
-// The context's replica on the store's GPU, or -1.
-int32_t slot_on(struct bert_ctx *ctx, int ordinal)
+// The context's replica on the store's GPU, or -1 with a message.
+int32_t slot_on(struct bert_ctx *ctx, int ordinal, const char *who)
 {
     for (int32_t s = 0; s < bertx_num_devices(ctx); ++s)
         if (bertx_device_ordinal(ctx, s) == ordinal) return s;
+    errorf("%s: the context has no replica on the store's device %d\n", who, ordinal);
     return -1;
 }
 
@@ -259,18 +231,8 @@ int32_t text_ctx_ok(bertx_mvindex *mv, struct bert_ctx *ctx, const char *who, in
         errorf("%s: the context cannot produce token rows of width %d\n", who, mv->w);
         return -1;
     }
-    *slot = slot_on(ctx, mv->ordinal);
-    if (*slot < 0) {
-        errorf("%s: the context has no replica on the store's device %d\n", who, mv->ordinal);
-        return -1;
-    }
-    return 0;
+    return (*slot = slot_on(ctx, mv->ordinal, who)) < 0 ? -1 : 0;
 }
-
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
 
 // B queries f32 [B][Lq][w] already on the device, on the store's stream: their results
 // into host vectors (the caller copies them out when the whole call succeeded).
@@ -304,11 +266,241 @@ int32_t colbert_ctx_ok(bertx_mvindex *mv, struct bert_ctx *ctx, const char *who,
                mv->w);
         return -1;
     }
-    *slot = slot_on(ctx, mv->ordinal);
-    if (*slot < 0) {
-        errorf("%s: the context has no replica on the store's device %d\n", who, mv->ordinal);
-        return -1;
+    return (*slot = slot_on(ctx, mv->ordinal, who)) < 0 ? -1 : 0;
+}
+
+// How a call's texts became rows: filled by one of the two tokenizers before the store's
+// lock is taken, read by the bodies below.
+struct TextRows {
+    std::vector<int32_t> ids;    // text i's ids at ids[i * stride]
+    size_t stride = 0;
+    std::vector<int32_t> lens;   // tokens per text
+    std::vector<int32_t> keep;   // empty: every token's row is kept; else beside ids, 1: the token's row is kept
+    std::vector<int32_t> kept;   // rows per text
+    std::vector<int32_t> keys;   // empty: every token is an attention key; else the key count per text
+    int32_t out_kind = BERTX_OUT_TOKENS;
+    int32_t slot = -1;           // the context's replica on the store's GPU
+};
+
+// The plain form: every token's final hidden state (the callers check the lens against
+// their own limits).
+int32_t tokenize_plain(struct bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts, int32_t slot, TextRows &t)
+{
+    const int32_t n_max = bert_n_max_tokens(ctx);
+    t.slot = slot;
+    t.stride = (size_t)n_max;
+    t.ids.resize((size_t)n * t.stride);
+    t.lens.resize((size_t)n);
+    if (bertx_tokenize_batch(ctx, n_threads, n, texts, n_max, t.ids.data(), t.lens.data()) != 0) return -1;
+    t.kept = t.lens;
+    return 0;
+}
+
+// The ColBERT form, kind 1 documents (punctuation rows dropped), kind 0 queries ([MASK]-
+// augmented to maxlen, every row kept): the projected rows.  The context's mask_keys
+// setting is read here, once per call: a query's [MASK] rows are keys (no counts), or its
+// rows up to [SEP] only.
+int32_t tokenize_colbert(struct bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts, int32_t kind,
+                         int32_t maxlen, int32_t slot, TextRows &t)
+{
+    const size_t N = (size_t)maxlen;
+    const bool doc = kind == 1;
+    t.slot = slot;
+    t.out_kind = BERTX_OUT_PROJ;
+    t.stride = N;
+    t.ids.resize((size_t)n * N);
+    t.lens.resize((size_t)n);
+    t.kept.resize((size_t)n);
+    t.keys.resize((size_t)n);
+    if (doc) t.keep.resize((size_t)n * N);
+    std::vector<int32_t> rcs((size_t)n, 0);
+    TaskPool::instance().run(((int64_t)n + 7) / 8, n_threads > 0 ? n_threads : 1, [&](int64_t blk) {
+        const int e = (int)std::min<int64_t>(n, 8 * blk + 8);
+        std::vector<int32_t> all(doc ? 0 : N);   // a query's mask: all ones
+        for (int i = (int)(8 * blk); i < e; ++i) {
+            int32_t *kp = doc ? t.keep.data() + i * N : all.data();
+            rcs[(size_t)i] = bertx_tokenize_colbert_ex(ctx, texts[i], kind, maxlen, t.ids.data() + i * N, kp,
+                                                       &t.lens[(size_t)i], &t.keys[(size_t)i]);
+            int32_t c = 0;
+            for (int32_t j = 0; rcs[(size_t)i] == 0 && j < t.lens[(size_t)i]; ++j) c += kp[j];
+            t.kept[(size_t)i] = doc ? c : t.lens[(size_t)i];
+        }
+    });
+    if (doc || bertx_mask_keys(ctx) != 0) t.keys.clear();
+    for (int32_t i = 0; i < n; ++i)
+        if (rcs[(size_t)i] != 0 || (!doc && t.lens[(size_t)i] != maxlen)) return -1;
+    return 0;
+}
+
+// The host and device buffers of a call's forwards, reused from chunk to chunk.
+struct ChunkBufs {
+    std::vector<int32_t> flat, cu, map;
+    DevBuf d_ids, d_cu, d_map, d_keys, d_rows;
+    int64_t cap_tok = 0, cap_seq = 0;
+};
+
+// Grow-only: room for a chunk of tok tokens in seqs texts.
+int32_t grow(bertx_mvindex &mv, const TextRows &t, ChunkBufs &b, int64_t tok, int64_t seqs)
+{
+    if (tok <= b.cap_tok && seqs <= b.cap_seq) return 0;
+    if (b.d_rows.p) HIP_RC(hipStreamSynchronize(mv.stream));   // the previous chunk may still read them
+    for (DevBuf *d : {&b.d_ids, &b.d_cu, &b.d_map, &b.d_keys, &b.d_rows})
+        if (d->p) { (void)hipFree(d->p); d->p = nullptr; }
+    b.cap_tok = std::max(tok, b.cap_tok);
+    b.cap_seq = std::max(seqs, b.cap_seq);
+    HIP_RC(hipMalloc(&b.d_ids.p, (size_t)b.cap_tok * 4));
+    HIP_RC(hipMalloc(&b.d_cu.p, (size_t)(b.cap_seq + 1) * 4));
+    if (!t.keep.empty()) HIP_RC(hipMalloc(&b.d_map.p, (size_t)b.cap_tok * 4));
+    if (!t.keys.empty()) HIP_RC(hipMalloc(&b.d_keys.p, (size_t)b.cap_seq * 4));
+    HIP_RC(hipMalloc(&b.d_rows.p, (size_t)b.cap_tok * mv.w * 4));
+    return 0;
+}
+
+// Texts i0 .. i1 - 1 through one forward on the store's stream: their kept rows, in
+// order, f32 [*n_rows][w] at *d_rows (a buffer of b: the next chunk reuses it).  With a
+// keep mask the kept tokens' packed positions are the forward's row map.
+int32_t forward_chunk(bertx_mvindex &mv, struct bert_ctx *ctx, const TextRows &t, size_t i0, size_t i1, ChunkBufs &b,
+                      const float **d_rows, int64_t *n_rows)
+{
+    const bool mapped = !t.keep.empty(), counted = !t.keys.empty();
+    b.flat.clear();
+    b.map.clear();
+    b.cu.assign(1, 0);
+    int32_t max_len = 0;
+    for (size_t i = i0; i < i1; ++i) {
+        const int32_t *p = t.ids.data() + i * t.stride, len = t.lens[i];
+        for (int32_t j = 0; mapped && j < len; ++j)
+            if (t.keep[i * t.stride + (size_t)j]) b.map.push_back((int32_t)b.flat.size() + j);
+        b.flat.insert(b.flat.end(), p, p + len);
+        b.cu.push_back((int32_t)b.flat.size());
+        max_len = std::max(max_len, len);
     }
+    const int64_t tok = (int64_t)b.flat.size(), seqs = (int64_t)(i1 - i0), rows = mapped ? (int64_t)b.map.size() : tok;
+    if (const int32_t rc = grow(mv, t, b, tok, seqs)) return rc;
+    if (bertx_reserve(ctx, t.slot, (int32_t)tok, (int32_t)seqs) != 0) return -1;
+    HIP_RC(hipMemcpyAsync(b.d_ids.p, b.flat.data(), (size_t)tok * 4, hipMemcpyHostToDevice, mv.stream));
+    HIP_RC(hipMemcpyAsync(b.d_cu.p, b.cu.data(), (size_t)(seqs + 1) * 4, hipMemcpyHostToDevice, mv.stream));
+    if (mapped) HIP_RC(hipMemcpyAsync(b.d_map.p, b.map.data(), (size_t)rows * 4, hipMemcpyHostToDevice, mv.stream));
+    if (counted) HIP_RC(hipMemcpyAsync(b.d_keys.p, t.keys.data() + i0, (size_t)seqs * 4, hipMemcpyHostToDevice, mv.stream));
+    *d_rows = (const float *)b.d_rows.p;
+    *n_rows = rows;
+    return bertx_forward_device_kv(ctx, t.slot, (const int32_t *)b.d_ids.p, nullptr, (const int32_t *)b.d_cu.p,
+                                   (const int32_t *)b.d_keys.p, (int32_t)seqs, max_len, (int32_t)tok, t.out_kind,
+                                   (const int32_t *)b.d_map.p, (int32_t)rows, (float *)b.d_rows.p, mv.stream);
+}
+
+// One document per text.  Chunks of whole texts as run_forward cuts them; each chunk's
+// rows go from the forward's device output straight into the pack kernel on the store's
+// stream.  who: the entry point, for the messages.
+int32_t add_texts(bertx_mvindex &mv, struct bert_ctx *ctx, const TextRows &t, int32_t n, const char *who)
+{
+    std::lock_guard<std::mutex> lk(mv.mu);
+    int64_t T = 0, slots = 0;
+    int32_t rc = plan_add(mv, t.kept.data(), n, &T, &slots);   // (a ColBERT document keeps [CLS], [D] and [SEP]: >= 3)
+    if (rc != 0) return rc;
+    DeviceGuard g(mv.ordinal);
+    HIP_RC(g.status());
+    ChunkBufs b;
+    {
+        Ordered o(mv.ord, mv.stream);
+        rc = upload_entries(mv, n, mv.stream);
+        int64_t t0 = 0;
+        for (size_t i = 0; i < (size_t)n && rc == 0;) {
+            const size_t e = chunk_end([&](size_t j) { return t.lens[j]; }, i, (size_t)n);
+            const float *d_rows = nullptr;
+            int64_t rows = 0;
+            rc = forward_chunk(mv, ctx, t, i, e, b, &d_rows, &rows);
+            if (rc == 0) rc = pack(mv, d_rows, t0, rows, n, mv.stream);
+            // the chunk's host and device buffers are reused by the next one
+            if (rc == 0 && hipStreamSynchronize(mv.stream) != hipSuccess) rc = -1;
+            t0 += rows;
+            i = e;
+        }
+    }
+    if (rc != 0) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(mv.stream);   // the entries may be rewritten by the next add
+        errorf("%s: device %d failed while adding (%d)\n", who, mv.ordinal, rc);
+        return rc < 0 ? rc : -1;
+    }
+    return commit(mv, n, slots);
+}
+
+// The one query of t against the host ids.  Ids [L], cu {0, L} and the key count travel
+// in the store's token staging and the rows land in its query staging: no device memory
+// is allocated per call.
+int32_t score_text(bertx_mvindex &mv, struct bert_ctx *ctx, const TextRows &t, const int32_t *ids, int32_t n, float *out)
+{
+    const int32_t L = t.lens[0];
+    std::vector<int32_t> h((size_t)kMaxLq + 3, 0);
+    std::memcpy(h.data(), t.ids.data(), (size_t)L * 4);
+    h[(size_t)kMaxLq + 1] = L;
+    if (!t.keys.empty()) h[(size_t)kMaxLq + 2] = t.keys[0];
+    std::lock_guard<std::mutex> lk(mv.mu);
+    DeviceGuard g(mv.ordinal);
+    HIP_RC(g.status());
+    if (bertx_reserve(ctx, t.slot, L, 1) != 0) return -1;
+    int32_t rc = 0;
+    {
+        Ordered o(mv.ord, mv.stream);
+        HIP_RC(hipMemcpyAsync(mv.st_tok, h.data(), h.size() * 4, hipMemcpyHostToDevice, mv.stream));
+        HIP_RC(hipStreamSynchronize(mv.stream));   // h is pageable and leaves scope
+        rc = bertx_forward_device_kv(ctx, t.slot, mv.st_tok, nullptr, mv.st_tok + kMaxLq,
+                                     t.keys.empty() ? nullptr : mv.st_tok + kMaxLq + 2, 1, L, L, t.out_kind, nullptr, 0,
+                                     mv.st_q, mv.stream);
+    }
+    if (rc != 0) return rc < 0 ? rc : -1;
+    return score_host_ids(mv, mv.st_q, L, ids, n, out);
+}
+
+// The n queries of t, kSearchTexts per forward.  The search reads [m][Lmax][w]: a
+// forward whose queries all have Lmax rows (the ColBERT form) hands its output over as
+// it is; otherwise the rows are laid out with zero rows behind the shorter queries
+// (device-to-device) first.  The outputs are written when every chunk succeeded.
+int32_t search_texts(bertx_mvindex &mv, struct bert_ctx *ctx, const TextRows &t, int32_t n, int32_t k, float *scores,
+                     int32_t *ids)
+{
+    const size_t w = (size_t)mv.w;
+    std::vector<float> hs((size_t)n * k);
+    std::vector<int32_t> hi((size_t)n * k);
+    std::lock_guard<std::mutex> lk(mv.mu);
+    DeviceGuard g(mv.ordinal);
+    HIP_RC(g.status());
+    const int32_t cap = std::min<int32_t>(n, kSearchTexts);
+    const int64_t cap_tok = (int64_t)cap * std::min<int64_t>((int64_t)t.stride, kMaxLq);
+    ChunkBufs b;
+    DevBuf d_pad;
+    if (const int32_t rc = grow(mv, t, b, cap_tok, cap)) return rc;   // once: no chunk is larger
+    for (int32_t i0 = 0; i0 < n; i0 += cap) {
+        const int32_t m = std::min(cap, n - i0);
+        const int32_t Lmax = *std::max_element(t.kept.begin() + i0, t.kept.begin() + i0 + m);
+        const float *d_q = nullptr;
+        int64_t rows = 0;
+        int32_t rc = 0;
+        {
+            Ordered o(mv.ord, mv.stream);
+            rc = forward_chunk(mv, ctx, t, (size_t)i0, (size_t)(i0 + m), b, &d_q, &rows);
+            if (rc == 0 && rows != (int64_t)m * Lmax) {
+                if (!d_pad.p) HIP_RC(hipMalloc(&d_pad.p, (size_t)cap_tok * w * 4));
+                HIP_RC(hipMemsetAsync(d_pad.p, 0, (size_t)m * Lmax * w * 4, mv.stream));
+                for (int32_t j = 0; j < m; ++j) {
+                    const size_t len = (size_t)t.kept[(size_t)(i0 + j)];
+                    HIP_RC(hipMemcpyAsync((float *)d_pad.p + (size_t)j * Lmax * w, d_q, len * w * 4, hipMemcpyDeviceToDevice,
+                                          mv.stream));
+                    d_q += len * w;
+                }
+                d_q = (const float *)d_pad.p;
+            }
+        }
+        if (rc == 0) rc = search_to_host(mv, d_q, m, Lmax, k, hs.data() + (size_t)i0 * k, hi.data() + (size_t)i0 * k);
+        if (rc != 0) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(mv.stream);
+            return rc < 0 ? rc : -1;
+        }
+    }
+    std::memcpy(scores, hs.data(), hs.size() * 4);
+    std::memcpy(ids, hi.data(), hi.size() * 4);
     return 0;
 }
 
@@ -347,7 +539,7 @@ bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t c
     const bool ok = maxsim_prepare_device() == 0 && maxsim_search_prepare_device() == 0 &&
                     hipMalloc(&mv->search_scratch, maxsim_search_scratch_bytes()) == hipSuccess &&
                     hipStreamCreateWithFlags(&mv->stream, hipStreamNonBlocking) == hipSuccess &&
-                    hipEventCreateWithFlags(&mv->done, hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(&mv->ord.done, hipEventDisableTiming) == hipSuccess &&
                     hipMalloc(&mv->store, store_bytes) == hipSuccess &&
                     (!i8 || hipMalloc((void **)&mv->scales, slots16 * 4) == hipSuccess) &&
                     hipMalloc((void **)&mv->table, (size_t)cap_docs * 8) == hipSuccess &&
@@ -412,7 +604,8 @@ int32_t bertx_mvindex_clear(struct bertx_mvindex *mv)
     DeviceGuard g(mv->ordinal);
     HIP_RC(g.status());
     // the host images' entries are about to be reused: no copy of them may be in flight
-    if (mv->any) HIP_RC(hipEventSynchronize(mv->done));
+    // (the embedding index keeps no such images and does not wait)
+    HIP_RC(mv->ord.wait());
     mv->n_docs = 0;
     mv->used_slots = 0;
     return 0;
@@ -456,7 +649,7 @@ int32_t bertx_mvindex_add(struct bertx_mvindex *mv, const float *rows, const int
     DeviceGuard g(mv->ordinal);
     HIP_RC(g.status());
     {
-        emb::Ordered o(*mv, mv->stream);
+        emb::Ordered o(mv->ord, mv->stream);
         rc = emb::upload_entries(*mv, n, mv->stream);
         for (int64_t t = 0; t < T && rc == 0; t += emb::kStageRows) {
             const int64_t m = std::min<int64_t>(emb::kStageRows, T - t);
@@ -508,21 +701,13 @@ int32_t bertx_mvindex_doc(struct bertx_mvindex *mv, int32_t id, float *out)
         return 0;
     }
     try {
-        const int w = mv->w, KB = w / 32;
         const int64_t first = mv->h_table[2 * (size_t)id], len = mv->h_table[2 * (size_t)id + 1];
-        const size_t group_halfs = (size_t)16 * w;
+        const size_t group_halfs = (size_t)16 * mv->w;
         std::vector<uint16_t> raw((size_t)((len + 15) / 16) * group_halfs);
-        if (mv->any) HIP_RC(hipEventSynchronize(mv->done));
+        HIP_RC(mv->ord.wait());
         HIP_RC(hipMemcpy(raw.data(), (const uint16_t *)mv->store + (size_t)first * group_halfs, raw.size() * 2,
                          hipMemcpyDeviceToHost));
-        for (int64_t r = 0; r < len; ++r) {
-            const uint16_t *grp = raw.data() + (size_t)(r / 16) * group_halfs;
-            float *o = out + (size_t)r * w;
-            for (int kb = 0; kb < KB; ++kb)
-                for (int q = 0; q < 4; ++q)
-                    for (int j = 0; j < 8; ++j)
-                        o[32 * kb + 8 * q + j] = emb::f16_to_f32(grp[((size_t)kb * 64 + 16 * q + (r & 15)) * 8 + j]);
-        }
+        emb::unpack_f16_rows(raw.data(), 0, 0, len, mv->w, out);
     } catch (const std::bad_alloc &) {
         emb::errorf("bertx_mvindex_doc: out of host memory\n");
         return -1;
@@ -586,72 +771,16 @@ int32_t bertx_mvindex_add_texts(struct bertx_mvindex *mv, struct bert_ctx *ctx, 
     if (!texts || n < 1) return -1;
     if (emb::text_ctx_ok(mv, ctx, "bertx_mvindex_add_texts", &slot) != 0) return -1;
     try {
+        emb::TextRows t;
+        if (emb::tokenize_plain(ctx, n_threads, n, texts, slot, t) != 0) return -1;
         const int32_t n_max = bert_n_max_tokens(ctx);
-        std::vector<int32_t> ids((size_t)n * n_max), lens((size_t)n);
-        if (bertx_tokenize_batch(ctx, n_threads, n, texts, n_max, ids.data(), lens.data()) != 0) return -1;
         for (int32_t i = 0; i < n; ++i)
-            if (lens[(size_t)i] > n_max) {
+            if (t.lens[(size_t)i] > n_max) {
                 emb::errorf("Too many tokens, maximum is %d\n", n_max);
-                emb::errorf("bertx_mvindex_add_texts: text %d has %d tokens; nothing was added\n", i, lens[(size_t)i]);
+                emb::errorf("bertx_mvindex_add_texts: text %d has %d tokens; nothing was added\n", i, t.lens[(size_t)i]);
                 return -4;
             }
-        std::lock_guard<std::mutex> lk(mv->mu);
-        int64_t T = 0, slots = 0;
-        int32_t rc = emb::plan_add(*mv, lens.data(), n, &T, &slots);
-        if (rc != 0) return rc;
-        DeviceGuard g(mv->ordinal);
-        HIP_RC(g.status());
-        // chunks of whole texts as run_forward cuts them; each chunk's token rows go from
-        // the forward's device output straight into the pack kernel on the store's stream
-        std::vector<int32_t> flat, cu;
-        emb::DevBuf d_ids, d_cu, d_rows;
-        int64_t cap_tok = 0, cap_seq = 0;
-        {
-            emb::Ordered o(*mv, mv->stream);
-            rc = emb::upload_entries(*mv, n, mv->stream);
-            int32_t i = 0;
-            int64_t t0 = 0;
-            while (i < n && rc == 0) {
-                flat.clear();
-                cu.assign(1, 0);
-                int max_len = 0;
-                while (i < n && (cu.size() == 1 || ((int64_t)flat.size() + lens[(size_t)i] <= emb::kChunkTokens &&
-                                                    (int)cu.size() - 1 < emb::kChunkSeqs))) {
-                    const int32_t *p = ids.data() + (size_t)i * n_max;
-                    flat.insert(flat.end(), p, p + lens[(size_t)i]);
-                    cu.push_back((int32_t)flat.size());
-                    max_len = std::max(max_len, (int)lens[(size_t)i]);
-                    ++i;
-                }
-                const int64_t tok = (int64_t)flat.size(), seqs = (int64_t)cu.size() - 1;
-                if (tok > cap_tok || seqs > cap_seq) {
-                    HIP_RC(hipStreamSynchronize(mv->stream));
-                    for (emb::DevBuf *b : {&d_ids, &d_cu, &d_rows})
-                        if (b->p) { (void)hipFree(b->p); b->p = nullptr; }
-                    cap_tok = std::max(tok, cap_tok);
-                    cap_seq = std::max(seqs, cap_seq);
-                    HIP_RC(hipMalloc(&d_ids.p, (size_t)cap_tok * 4));
-                    HIP_RC(hipMalloc(&d_cu.p, (size_t)(cap_seq + 1) * 4));
-                    HIP_RC(hipMalloc(&d_rows.p, (size_t)cap_tok * mv->w * 4));
-                }
-                if (bertx_reserve(ctx, slot, (int32_t)tok, (int32_t)seqs) != 0) { rc = -1; break; }
-                HIP_RC(hipMemcpyAsync(d_ids.p, flat.data(), (size_t)tok * 4, hipMemcpyHostToDevice, mv->stream));
-                HIP_RC(hipMemcpyAsync(d_cu.p, cu.data(), (size_t)(seqs + 1) * 4, hipMemcpyHostToDevice, mv->stream));
-                rc = bertx_forward_tokens_device(ctx, slot, (const int32_t *)d_ids.p, (const int32_t *)d_cu.p,
-                                                 (int32_t)seqs, max_len, (int32_t)tok, (float *)d_rows.p, mv->stream);
-                if (rc == 0) rc = emb::pack(*mv, (const float *)d_rows.p, t0, tok, n, mv->stream);
-                // the chunk's host and device buffers are reused by the next one
-                if (rc == 0 && hipStreamSynchronize(mv->stream) != hipSuccess) rc = -1;
-                t0 += tok;
-            }
-        }
-        if (rc != 0) {
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(mv->stream);
-            emb::errorf("bertx_mvindex_add_texts: device %d failed while adding (%d)\n", mv->ordinal, rc);
-            return rc < 0 ? rc : -1;
-        }
-        return emb::commit(*mv, n, slots);
+        return emb::add_texts(*mv, ctx, t, n, "bertx_mvindex_add_texts");
     } catch (const std::exception &ex) {
         emb::errorf("bertx_mvindex_add_texts: %s\n", ex.what());
         return -1;
@@ -665,35 +794,16 @@ int32_t bertx_mvindex_score_text(struct bertx_mvindex *mv, struct bert_ctx *ctx,
     if (!query || !out || n < 1) return -1;
     if (emb::text_ctx_ok(mv, ctx, "bertx_mvindex_score_text", &slot) != 0) return -1;
     try {
-        const int32_t n_max = bert_n_max_tokens(ctx);
-        std::vector<int32_t> tok((size_t)n_max + 2);
-        int32_t L = 0;
-        bert_tokenize(ctx, query, tok.data(), &L, n_max);
+        emb::TextRows t;
+        if (emb::tokenize_plain(ctx, 1, 1, &query, slot, t) != 0) return -1;
+        const int32_t n_max = bert_n_max_tokens(ctx), L = t.lens[0];
         if (L > n_max || L > emb::kMaxLq) {
             emb::errorf("bertx_mvindex_score_text: the query has %d tokens, maximum is %d\n", L,
                         std::min<int32_t>(n_max, emb::kMaxLq));
             return -4;
         }
         if (L < 1) return -1;
-        std::lock_guard<std::mutex> lk(mv->mu);
-        DeviceGuard g(mv->ordinal);
-        HIP_RC(g.status());
-        // ids [L] and cu {0, L} in one staging buffer, the token rows into the query staging
-        std::vector<int32_t> h((size_t)emb::kMaxLq + 2, 0);
-        std::memcpy(h.data(), tok.data(), (size_t)L * 4);
-        h[(size_t)emb::kMaxLq] = 0;
-        h[(size_t)emb::kMaxLq + 1] = L;
-        if (bertx_reserve(ctx, slot, L, 1) != 0) return -1;
-        int32_t rc = 0;
-        {
-            emb::Ordered o(*mv, mv->stream);
-            HIP_RC(hipMemcpyAsync(mv->st_tok, h.data(), h.size() * 4, hipMemcpyHostToDevice, mv->stream));
-            HIP_RC(hipStreamSynchronize(mv->stream));   // h is pageable and leaves scope
-            rc = bertx_forward_tokens_device(ctx, slot, mv->st_tok, mv->st_tok + emb::kMaxLq, 1, L, L, mv->st_q,
-                                             mv->stream);
-        }
-        if (rc != 0) return rc < 0 ? rc : -1;
-        return emb::score_host_ids(*mv, mv->st_q, L, ids, n, out);
+        return emb::score_text(*mv, ctx, t, ids, n, out);
     } catch (const std::exception &ex) {
         emb::errorf("bertx_mvindex_score_text: %s\n", ex.what());
         return -1;
@@ -710,83 +820,9 @@ int32_t bertx_mvindex_add_texts_colbert(struct bertx_mvindex *mv, struct bert_ct
     for (int32_t i = 0; i < n; ++i)
         if (!texts[i]) return -1;
     try {
-        const size_t N = (size_t)doc_maxlen;
-        std::vector<int32_t> ids((size_t)n * N), keep((size_t)n * N), lens((size_t)n), kept((size_t)n), rcs((size_t)n, 0);
-        emb::TaskPool::instance().run(((int64_t)n + 7) / 8, n_threads > 0 ? n_threads : 1, [&](int64_t blk) {
-            const int e = (int)std::min<int64_t>(n, 8 * blk + 8);
-            for (int i = (int)(8 * blk); i < e; ++i) {
-                rcs[(size_t)i] = bertx_tokenize_colbert(ctx, texts[i], 1, doc_maxlen, ids.data() + i * N,
-                                                        keep.data() + i * N, &lens[(size_t)i]);
-                int32_t c = 0;
-                for (int32_t t = 0; rcs[(size_t)i] == 0 && t < lens[(size_t)i]; ++t) c += keep[i * N + t];
-                kept[(size_t)i] = c;
-            }
-        });
-        for (int32_t i = 0; i < n; ++i)
-            if (rcs[(size_t)i] != 0) return -1;
-        std::lock_guard<std::mutex> lk(mv->mu);
-        int64_t T = 0, slots = 0;
-        int32_t rc = emb::plan_add(*mv, kept.data(), n, &T, &slots);   // (a document keeps [CLS], [D] and [SEP]: >= 3)
-        if (rc != 0) return rc;
-        DeviceGuard g(mv->ordinal);
-        HIP_RC(g.status());
-        // the chunks of _add_texts; per chunk the kept tokens' packed rows are the row map,
-        // and the projector's device output goes straight into the pack kernel
-        std::vector<int32_t> flat, cu, map;
-        emb::DevBuf d_ids, d_cu, d_map, d_rows;
-        int64_t cap_tok = 0, cap_seq = 0;
-        {
-            emb::Ordered o(*mv, mv->stream);
-            rc = emb::upload_entries(*mv, n, mv->stream);
-            int32_t i = 0;
-            int64_t t0 = 0;
-            while (i < n && rc == 0) {
-                flat.clear();
-                map.clear();
-                cu.assign(1, 0);
-                int max_len = 0;
-                while (i < n && (cu.size() == 1 || ((int64_t)flat.size() + lens[(size_t)i] <= emb::kChunkTokens &&
-                                                    (int)cu.size() - 1 < emb::kChunkSeqs))) {
-                    const int32_t *p = ids.data() + i * N, *kp = keep.data() + i * N;
-                    for (int32_t t = 0; t < lens[(size_t)i]; ++t)
-                        if (kp[t]) map.push_back((int32_t)flat.size() + t);
-                    flat.insert(flat.end(), p, p + lens[(size_t)i]);
-                    cu.push_back((int32_t)flat.size());
-                    max_len = std::max(max_len, (int)lens[(size_t)i]);
-                    ++i;
-                }
-                const int64_t tok = (int64_t)flat.size(), seqs = (int64_t)cu.size() - 1, rows = (int64_t)map.size();
-                if (tok > cap_tok || seqs > cap_seq) {
-                    HIP_RC(hipStreamSynchronize(mv->stream));
-                    for (emb::DevBuf *b : {&d_ids, &d_cu, &d_map, &d_rows})
-                        if (b->p) { (void)hipFree(b->p); b->p = nullptr; }
-                    cap_tok = std::max(tok, cap_tok);
-                    cap_seq = std::max(seqs, cap_seq);
-                    HIP_RC(hipMalloc(&d_ids.p, (size_t)cap_tok * 4));
-                    HIP_RC(hipMalloc(&d_cu.p, (size_t)(cap_seq + 1) * 4));
-                    HIP_RC(hipMalloc(&d_map.p, (size_t)cap_tok * 4));
-                    HIP_RC(hipMalloc(&d_rows.p, (size_t)cap_tok * mv->w * 4));
-                }
-                if (bertx_reserve(ctx, slot, (int32_t)tok, (int32_t)seqs) != 0) { rc = -1; break; }
-                HIP_RC(hipMemcpyAsync(d_ids.p, flat.data(), (size_t)tok * 4, hipMemcpyHostToDevice, mv->stream));
-                HIP_RC(hipMemcpyAsync(d_cu.p, cu.data(), (size_t)(seqs + 1) * 4, hipMemcpyHostToDevice, mv->stream));
-                HIP_RC(hipMemcpyAsync(d_map.p, map.data(), (size_t)rows * 4, hipMemcpyHostToDevice, mv->stream));
-                rc = bertx_forward_project_device(ctx, slot, (const int32_t *)d_ids.p, nullptr, (const int32_t *)d_cu.p,
-                                                  (int32_t)seqs, max_len, (int32_t)tok, (const int32_t *)d_map.p,
-                                                  (int32_t)rows, (float *)d_rows.p, mv->stream);
-                if (rc == 0) rc = emb::pack(*mv, (const float *)d_rows.p, t0, rows, n, mv->stream);
-                // the chunk's host and device buffers are reused by the next one
-                if (rc == 0 && hipStreamSynchronize(mv->stream) != hipSuccess) rc = -1;
-                t0 += rows;
-            }
-        }
-        if (rc != 0) {
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(mv->stream);
-            emb::errorf("bertx_mvindex_add_texts_colbert: device %d failed while adding (%d)\n", mv->ordinal, rc);
-            return rc < 0 ? rc : -1;
-        }
-        return emb::commit(*mv, n, slots);
+        emb::TextRows t;
+        if (emb::tokenize_colbert(ctx, n_threads, n, texts, 1, doc_maxlen, slot, t) != 0) return -1;
+        return emb::add_texts(*mv, ctx, t, n, "bertx_mvindex_add_texts_colbert");
     } catch (const std::exception &ex) {
         emb::errorf("bertx_mvindex_add_texts_colbert: %s\n", ex.what());
         return -1;
@@ -801,32 +837,9 @@ int32_t bertx_mvindex_score_text_colbert(struct bertx_mvindex *mv, struct bert_c
     if (const int32_t rc = emb::colbert_ctx_ok(mv, ctx, "bertx_mvindex_score_text_colbert", &slot)) return rc;
     if (query_maxlen < 4 || query_maxlen > emb::kMaxLq || query_maxlen > bert_n_max_tokens(ctx)) return -1;
     try {
-        // ids [L], cu {0, L} and the key count in one staging buffer, as _score_text; L = query_maxlen
-        std::vector<int32_t> h((size_t)emb::kMaxLq + 3, 0), keep((size_t)emb::kMaxLq);
-        int32_t L = 0, nk = 0;
-        if (bertx_tokenize_colbert_ex(ctx, query, 0, query_maxlen, h.data(), keep.data(), &L, &nk) != 0 ||
-            L != query_maxlen)
-            return -1;
-        h[(size_t)emb::kMaxLq] = 0;
-        h[(size_t)emb::kMaxLq + 1] = L;
-        h[(size_t)emb::kMaxLq + 2] = nk;
-        // the context's setting: [MASK] rows as keys (no counts), or the rows up to [SEP] only
-        const bool counted = bertx_mask_keys(ctx) == 0;
-        std::lock_guard<std::mutex> lk(mv->mu);
-        DeviceGuard g(mv->ordinal);
-        HIP_RC(g.status());
-        if (bertx_reserve(ctx, slot, L, 1) != 0) return -1;
-        int32_t rc = 0;
-        {
-            emb::Ordered o(*mv, mv->stream);
-            HIP_RC(hipMemcpyAsync(mv->st_tok, h.data(), h.size() * 4, hipMemcpyHostToDevice, mv->stream));
-            HIP_RC(hipStreamSynchronize(mv->stream));   // h is pageable and leaves scope
-            rc = bertx_forward_device_kv(ctx, slot, mv->st_tok, nullptr, mv->st_tok + emb::kMaxLq,
-                                         counted ? mv->st_tok + emb::kMaxLq + 2 : nullptr, 1, L, L, BERTX_OUT_PROJ,
-                                         nullptr, 0, mv->st_q, mv->stream);
-        }
-        if (rc != 0) return rc < 0 ? rc : -1;
-        return emb::score_host_ids(*mv, mv->st_q, L, ids, n, out);
+        emb::TextRows t;
+        if (emb::tokenize_colbert(ctx, 1, 1, &query, 0, query_maxlen, slot, t) != 0) return -1;
+        return emb::score_text(*mv, ctx, t, ids, n, out);
     } catch (const std::exception &ex) {
         emb::errorf("bertx_mvindex_score_text_colbert: %s\n", ex.what());
         return -1;
@@ -876,69 +889,17 @@ int32_t bertx_mvindex_search_texts(struct bertx_mvindex *mv, struct bert_ctx *ct
     if (emb::text_ctx_ok(mv, ctx, "bertx_mvindex_search_texts", &slot) != 0) return -1;
     if (!emb::search_args_ok("bertx_mvindex_search_texts", n, 1, k)) return -1;
     try {
-        const int32_t n_max = bert_n_max_tokens(ctx), lim = std::min<int32_t>(n_max, emb::kMaxLq);
-        const int w = mv->w;
-        std::vector<int32_t> tok((size_t)n * n_max), lens((size_t)n);
-        if (bertx_tokenize_batch(ctx, n_threads, n, texts, n_max, tok.data(), lens.data()) != 0) return -1;
+        emb::TextRows t;
+        if (emb::tokenize_plain(ctx, n_threads, n, texts, slot, t) != 0) return -1;
+        const int32_t lim = std::min<int32_t>(bert_n_max_tokens(ctx), emb::kMaxLq);
         for (int32_t i = 0; i < n; ++i) {
-            if (lens[(size_t)i] > lim) {
-                emb::errorf("bertx_mvindex_search_texts: query %d has %d tokens, maximum is %d\n", i, lens[(size_t)i], lim);
+            if (t.lens[(size_t)i] > lim) {
+                emb::errorf("bertx_mvindex_search_texts: query %d has %d tokens, maximum is %d\n", i, t.lens[(size_t)i], lim);
                 return -4;
             }
-            if (lens[(size_t)i] < 1) return -1;
+            if (t.lens[(size_t)i] < 1) return -1;
         }
-        std::vector<float> hs((size_t)n * k);
-        std::vector<int32_t> hi((size_t)n * k), flat, cu;
-        std::lock_guard<std::mutex> lk(mv->mu);
-        DeviceGuard g(mv->ordinal);
-        HIP_RC(g.status());
-        const int32_t cap = std::min<int32_t>(n, emb::kSearchTexts);
-        emb::DevBuf d_tok, d_cu, d_rows, d_q;
-        HIP_RC(hipMalloc(&d_tok.p, (size_t)cap * emb::kMaxLq * 4));
-        HIP_RC(hipMalloc(&d_cu.p, (size_t)(cap + 1) * 4));
-        HIP_RC(hipMalloc(&d_rows.p, (size_t)cap * emb::kMaxLq * w * 4));
-        HIP_RC(hipMalloc(&d_q.p, (size_t)cap * emb::kMaxLq * w * 4));
-        // chunks of whole queries: one per-token forward, the rows laid out [m][Lmax][w] with
-        // zero rows behind the shorter queries (device-to-device), then the search
-        for (int32_t i0 = 0; i0 < n; i0 += cap) {
-            const int32_t m = std::min(cap, n - i0);
-            flat.clear();
-            cu.assign(1, 0);
-            int32_t Lmax = 0;
-            for (int32_t i = i0; i < i0 + m; ++i) {
-                const int32_t *p = tok.data() + (size_t)i * n_max;
-                flat.insert(flat.end(), p, p + lens[(size_t)i]);
-                cu.push_back((int32_t)flat.size());
-                Lmax = std::max(Lmax, lens[(size_t)i]);
-            }
-            const int32_t T = (int32_t)flat.size();
-            if (bertx_reserve(ctx, slot, T, m) != 0) return -1;
-            int32_t rc = 0;
-            {
-                emb::Ordered o(*mv, mv->stream);
-                HIP_RC(hipMemcpyAsync(d_tok.p, flat.data(), (size_t)T * 4, hipMemcpyHostToDevice, mv->stream));
-                HIP_RC(hipMemcpyAsync(d_cu.p, cu.data(), (size_t)(m + 1) * 4, hipMemcpyHostToDevice, mv->stream));
-                rc = bertx_forward_tokens_device(ctx, slot, (const int32_t *)d_tok.p, (const int32_t *)d_cu.p, m, Lmax, T,
-                                                 (float *)d_rows.p, mv->stream);
-                if (rc == 0) {
-                    HIP_RC(hipMemsetAsync(d_q.p, 0, (size_t)m * Lmax * w * 4, mv->stream));
-                    for (int32_t j = 0; j < m; ++j)
-                        HIP_RC(hipMemcpyAsync((float *)d_q.p + (size_t)j * Lmax * w, (const float *)d_rows.p + (size_t)cu[(size_t)j] * w,
-                                              (size_t)lens[(size_t)(i0 + j)] * w * 4, hipMemcpyDeviceToDevice, mv->stream));
-                }
-            }
-            if (rc == 0)
-                rc = emb::search_to_host(*mv, (const float *)d_q.p, m, Lmax, k, hs.data() + (size_t)i0 * k,
-                                         hi.data() + (size_t)i0 * k);
-            if (rc != 0) {
-                (void)hipGetLastError();
-                (void)hipStreamSynchronize(mv->stream);
-                return rc < 0 ? rc : -1;
-            }
-        }
-        std::memcpy(scores, hs.data(), hs.size() * 4);
-        std::memcpy(ids, hi.data(), hi.size() * 4);
-        return 0;
+        return emb::search_texts(*mv, ctx, t, n, k, scores, ids);
     } catch (const std::exception &ex) {
         emb::errorf("bertx_mvindex_search_texts: %s\n", ex.what());
         return -1;
@@ -957,61 +918,9 @@ int32_t bertx_mvindex_search_texts_colbert(struct bertx_mvindex *mv, struct bert
     for (int32_t i = 0; i < n; ++i)
         if (!texts[i]) return -1;
     try {
-        // every augmented query has L = query_maxlen tokens, all kept: the projector's output
-        // is the [n][L][w] layout itself
-        const size_t L = (size_t)query_maxlen;
-        const int w = mv->w;
-        std::vector<int32_t> tok((size_t)n * L), lens((size_t)n), nks((size_t)n), rcs((size_t)n, 0);
-        emb::TaskPool::instance().run(((int64_t)n + 7) / 8, n_threads > 0 ? n_threads : 1, [&](int64_t blk) {
-            const int e = (int)std::min<int64_t>(n, 8 * blk + 8);
-            std::vector<int32_t> keep(L);
-            for (int i = (int)(8 * blk); i < e; ++i)
-                rcs[(size_t)i] = bertx_tokenize_colbert_ex(ctx, texts[i], 0, query_maxlen, tok.data() + i * L, keep.data(),
-                                                           &lens[(size_t)i], &nks[(size_t)i]);
-        });
-        // the context's setting: [MASK] rows as keys (no counts), or each query's rows up to [SEP] only
-        const bool counted = bertx_mask_keys(ctx) == 0;
-        for (int32_t i = 0; i < n; ++i)
-            if (rcs[(size_t)i] != 0 || lens[(size_t)i] != query_maxlen) return -1;
-        std::vector<float> hs((size_t)n * k);
-        std::vector<int32_t> hi((size_t)n * k), cu;
-        std::lock_guard<std::mutex> lk(mv->mu);
-        DeviceGuard g(mv->ordinal);
-        HIP_RC(g.status());
-        const int32_t cap = std::min<int32_t>(n, emb::kSearchTexts);
-        emb::DevBuf d_tok, d_cu, d_q, d_nk;
-        HIP_RC(hipMalloc(&d_tok.p, (size_t)cap * L * 4));
-        HIP_RC(hipMalloc(&d_cu.p, (size_t)(cap + 1) * 4));
-        HIP_RC(hipMalloc(&d_q.p, (size_t)cap * L * w * 4));
-        if (counted) HIP_RC(hipMalloc(&d_nk.p, (size_t)cap * 4));
-        cu.resize((size_t)cap + 1);
-        for (int32_t j = 0; j <= cap; ++j) cu[(size_t)j] = j * query_maxlen;
-        for (int32_t i0 = 0; i0 < n; i0 += cap) {
-            const int32_t m = std::min(cap, n - i0), T = m * query_maxlen;
-            if (bertx_reserve(ctx, slot, T, m) != 0) return -1;
-            int32_t rc = 0;
-            {
-                emb::Ordered o(*mv, mv->stream);
-                HIP_RC(hipMemcpyAsync(d_tok.p, tok.data() + (size_t)i0 * L, (size_t)T * 4, hipMemcpyHostToDevice, mv->stream));
-                HIP_RC(hipMemcpyAsync(d_cu.p, cu.data(), (size_t)(m + 1) * 4, hipMemcpyHostToDevice, mv->stream));
-                if (counted)
-                    HIP_RC(hipMemcpyAsync(d_nk.p, nks.data() + i0, (size_t)m * 4, hipMemcpyHostToDevice, mv->stream));
-                rc = bertx_forward_device_kv(ctx, slot, (const int32_t *)d_tok.p, nullptr, (const int32_t *)d_cu.p,
-                                             (const int32_t *)d_nk.p, m, query_maxlen, T, BERTX_OUT_PROJ, nullptr, 0,
-                                             (float *)d_q.p, mv->stream);
-            }
-            if (rc == 0)
-                rc = emb::search_to_host(*mv, (const float *)d_q.p, m, query_maxlen, k, hs.data() + (size_t)i0 * k,
-                                         hi.data() + (size_t)i0 * k);
-            if (rc != 0) {
-                (void)hipGetLastError();
-                (void)hipStreamSynchronize(mv->stream);
-                return rc < 0 ? rc : -1;
-            }
-        }
-        std::memcpy(scores, hs.data(), hs.size() * 4);
-        std::memcpy(ids, hi.data(), hi.size() * 4);
-        return 0;
+        emb::TextRows t;
+        if (emb::tokenize_colbert(ctx, n_threads, n, texts, 0, query_maxlen, slot, t) != 0) return -1;
+        return emb::search_texts(*mv, ctx, t, n, k, scores, ids);
     } catch (const std::exception &ex) {
         emb::errorf("bertx_mvindex_search_texts_colbert: %s\n", ex.what());
         return -1;

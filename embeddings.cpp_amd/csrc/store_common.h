@@ -1,0 +1,84 @@
+// What the two device-resident stores share (index.cpp, mvindex.cpp): the ordering of a
+// store's device operations, an owned device buffer, and the host loops that unpack the
+// search kernels' fragment order (kernels.h) into rows.  Host code only.
+#pragma once
+
+#include "host_common.h"
+
+#include <hip/hip_runtime.h>
+
+namespace emb {
+
+inline bool capturing(hipStream_t s)
+{
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return st != hipStreamCaptureStatusNone;
+}
+
+// Every device operation on a store is ordered after the previous one: an operation on
+// another stream first waits (on the device) for `done`.  The store creates and destroys
+// the event; the fields are read and written under the store's mutex.
+struct StoreOrder {
+    hipEvent_t done = nullptr;          // completion of the last device operation on the store
+    hipStream_t last_stream = nullptr;  // ... and the stream it ran on
+    bool any = false;
+    // the host waits for the last operation (before it reads the store with a blocking copy)
+    hipError_t wait() const { return any ? hipEventSynchronize(done) : hipSuccess; }
+};
+
+// Orders an operation on `s` after the store's previous one and, on destruction, records
+// it as the new previous one.  A capturing stream records and waits for nothing outside
+// its graph: the captured operation is ordered by its stream alone.
+struct Ordered {
+    StoreOrder &o;
+    hipStream_t s;
+    const bool cap;
+    Ordered(StoreOrder &ord, hipStream_t st) : o(ord), s(st), cap(capturing(st))
+    {
+        if (!cap && o.any && o.last_stream != s) (void)hipStreamWaitEvent(s, o.done, 0);
+    }
+    ~Ordered()
+    {
+        if (cap) return;
+        (void)hipEventRecord(o.done, s);
+        o.last_stream = s;
+        o.any = true;
+    }
+};
+
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+// The unpackers.  image: a host copy of whole 16-row groups of width w, of which the
+// first holds row image_first (a multiple of 16); rows first .. first + n - 1 of it go to
+// out [n][w].  An int8 store's scales stay with the caller (the two stores index them
+// differently).
+inline void unpack_f16_rows(const uint16_t *image, int64_t image_first, int64_t first, int64_t n, int w, float *out)
+{
+    const int KB = w / 32;
+    const size_t group_halfs = (size_t)16 * w;
+    for (int64_t r = first; r < first + n; ++r) {
+        const uint16_t *grp = image + (size_t)((r - image_first) / 16) * group_halfs;
+        float *o = out + (size_t)(r - first) * w;
+        for (int kb = 0; kb < KB; ++kb)
+            for (int q = 0; q < 4; ++q)
+                for (int j = 0; j < 8; ++j) o[32 * kb + 8 * q + j] = f16_to_f32(grp[((size_t)kb * 64 + 16 * q + (r & 15)) * 8 + j]);
+    }
+}
+
+inline void unpack_i8_rows(const int8_t *image, int64_t image_first, int64_t first, int64_t n, int w, int8_t *out)
+{
+    const int KB = w / 64;
+    const size_t group_bytes = (size_t)16 * w;
+    for (int64_t r = first; r < first + n; ++r) {
+        const int8_t *grp = image + (size_t)((r - image_first) / 16) * group_bytes;
+        int8_t *o = out + (size_t)(r - first) * w;
+        for (int kb = 0; kb < KB; ++kb)
+            for (int g = 0; g < 4; ++g) std::memcpy(o + 64 * kb + 16 * g, grp + ((size_t)kb * 64 + 16 * g + (r & 15)) * 16, 16);
+    }
+}
+
+}  // namespace emb

@@ -316,6 +316,39 @@ def test_add_texts_colbert_equals_the_manual_route(proj_models, fmt, act):
         assert np.isneginf(a.score_text(q, ids, colbert=QUERY_MAXLEN)[[1, 4]]).all()
 
 
+def test_add_texts_colbert_across_the_sentence_limit(proj_models):
+    """4,097 texts in one call: the last one is a forward of its own.  Two texts of three drop
+    punctuation rows, among them the last of the first forward and the only one of the second,
+    so neither forward's row map is the identity."""
+    m = bertpy.BertModel(proj_models[("tiny32", "f16")])
+    vocab = ["stone", "river", "bridge", "water", "plain", "words", "marks", "one", "two", "three"]
+    n = 4097
+
+    def text(i):
+        a, b, c = vocab[i % 10], vocab[i // 10 % 10], vocab[i // 100 % 10]
+        return "%s, %s. %s!" % (a, b, c) if i % 3 != 2 else "%s %s %s %s" % (a, b, c, vocab[i // 1000])
+
+    texts = [text(i) for i in range(n)]
+    kept = []
+    for t in texts:
+        ids, keep = m.tokenize_colbert(t, "doc", DOC_MAXLEN)
+        kept.append(int(keep.sum()))
+        assert (keep == 0).any() == ("," in t)
+    assert "," in texts[4095] and "," in texts[4096] and "," not in texts[4094]
+    slots = sum((k + 15) // 16 * 16 for k in kept)
+    a = bertpy.BertTokenIndex(m, n, slots, width=m.proj_width)
+    assert a.add_texts(texts, colbert=DOC_MAXLEN) == 0
+    assert len(a) == n and a.token_slots == slots
+    assert [a.doc_len(i) for i in range(n)] == kept
+    picks = [0, 1, 2, 4094, 4095, 4096]
+    docs, _ = manual_docs(m, [texts[i] for i in picks], DOC_MAXLEN)
+    b = bertpy.BertTokenIndex(m, len(picks), sum((len(d) + 15) // 16 * 16 for d in docs), width=m.proj_width)
+    assert b.add(docs) == 0
+    for j, i in enumerate(picks):
+        assert a.doc_len(i) == b.doc_len(j) == len(docs[j]) >= 3
+        assert np.array_equal(bits(a.doc(i)), bits(b.doc(j))), i
+
+
 def test_store_colbert_refusals(lib, proj_models):
     m = bertpy.BertModel(proj_models[("tiny32", "f16")])
     plain = bertpy.BertModel(os.path.join(GOLDEN, "tiny64", "ggml-model-f16.bin"))

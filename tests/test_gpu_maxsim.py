@@ -432,6 +432,86 @@ def test_text_path_equals_the_manual_path(tok_golden):
     assert len(a) == 40
 
 
+# ---- 9b. the chunk boundaries of the text and host forms, bit for bit ----
+def check_docs_against_the_manual_path(m, a, ids, picks):
+    """Documents `picks` of store a (filled by add_texts) against a store filled by
+    add(forward_tokens(.)) of those documents' ids."""
+    b = bertpy.BertTokenIndex(m, len(picks), sum((len(ids[i]) + 15) // 16 * 16 for i in picks))
+    assert b.add(m.forward_tokens([ids[i] for i in picks])) == 0
+    for j, i in enumerate(picks):
+        assert a.doc_len(i) == b.doc_len(j) == len(ids[i]), i
+        assert same(a.doc(i), b.doc(j)), i
+
+
+def test_add_texts_across_the_sentence_limit(tok_golden):
+    """4,097 texts in one call: a device forward takes at most 4,096 sentences, so the last
+    text is a chunk of its own."""
+    m = bertpy.BertModel(TINY64)
+    _, words = corpus_texts(tok_golden)
+    W, n = len(words), 4097
+    texts = [" ".join(words[(i + 97 * j) % W] for j in range(2 + i % 2)) for i in range(n)]
+    ids = [np.array(m.tokenize(t)[0], np.int32) for t in texts]
+    lens = [len(t) for t in ids]
+    assert set(lens) == {4, 5} and sum(lens) < 2 ** 17              # the sentence limit alone cuts
+    a = bertpy.BertTokenIndex(m, n, 16 * n)
+    assert a.add_texts(texts) == 0
+    assert len(a) == n and a.token_slots == 16 * n
+    assert [a.doc_len(i) for i in range(n)] == lens
+    check_docs_against_the_manual_path(m, a, ids, [0, 1, 4094, 4095, 4096])
+
+
+def test_add_texts_across_the_token_limit(tok_golden):
+    """Texts of 512 tokens each: 256 of them are 2^17 tokens, one device forward; the 257th
+    opens the second chunk."""
+    m = bertpy.BertModel(TINY64)
+    _, words = corpus_texts(tok_golden)
+    W, L = len(words), m.n_max_tokens
+    assert L == 512
+    texts = [" ".join(words[(i + 31 * j + j * j) % W] for j in range(L - 2)) for i in range(257)]
+    ids = [np.array(m.tokenize(t)[0], np.int32) for t in texts]
+    lens = [len(t) for t in ids]
+    assert lens == [L] * 257
+    assert sum(lens[:256]) <= 131072 < sum(lens[:257]) and len(lens) <= 4096   # the token limit alone cuts
+    a = bertpy.BertTokenIndex(m, 257, 257 * L)
+    assert a.add_texts(texts) == 0
+    assert len(a) == 257 and a.token_slots == 257 * L
+    assert [a.doc_len(i) for i in range(257)] == lens
+    check_docs_against_the_manual_path(m, a, ids, [0, 255, 256])
+
+
+def test_host_score_across_the_staging_chunk(model_of_width):
+    """65,537 candidates: the host form stages 65,536 ids at a time."""
+    w = 64
+    ix, q = store_of(model_of_width(w), M.pack_case(w)), M.token_rows(np.random.default_rng(82), 17, w)
+    n, N = len(ix), 65537
+    want = ix.score(q)
+    ids = (np.arange(N) % n).astype(np.int32)
+    ids[65535] = ids[65536] = -1
+    assert ids[65534] >= 0 and N - 65536 == 1
+    got = ix.score(q, ids)
+    exp = np.where(ids >= 0, want[np.maximum(ids, 0)], np.float32(-np.inf)).astype(np.float32)
+    assert got.shape == (N,) and same(got, exp)
+
+
+@pytest.mark.parametrize("storage", ("f16", "int8"))
+def test_host_add_across_the_staging_chunk(model_of_width, storage):
+    """One host add of 4,200 rows is staged 2,048 source rows at a time: documents 1 and 4
+    straddle source rows 2,048 and 4,096, document 2 begins at row 2,057 of the call."""
+    w = 64
+    m = model_of_width(w)
+    rng = np.random.default_rng(83)
+    lens = [2040, 17, 2030, 1, 33, 79]
+    starts = np.concatenate([[0], np.cumsum(lens)])
+    assert starts[1] < 2048 < starts[2] and starts[4] < 4096 < starts[5] and starts[-1] == 4200
+    docs = [M.token_rows(rng, n, w) for n in lens]
+    ix = bertpy.BertTokenIndex(m, len(docs), slots_of(docs), storage=storage)
+    assert ix.add(docs) == 0 and len(ix) == len(docs) and ix.token_slots == slots_of(docs)
+    for i, d in enumerate(docs):                                      # alone, every document starts at source row 0
+        one = bertpy.BertTokenIndex(m, 1, slots_of([d]), storage=storage)
+        assert one.add([d]) == 0
+        assert ix.doc_len(i) == len(d) and same(ix.doc(i), one.doc(0)), i
+
+
 # ---- 10. rerank ----
 @pytest.mark.parametrize("w,Lq,N,seed", M.RANKING_CASES)
 def test_rerank_order_is_the_reference_order(model_of_width, w, Lq, N, seed):

@@ -296,6 +296,44 @@ def test_search_texts_colbert_equals_score_text_colbert(colbert_model, storage):
     assert L.bertx_mvindex_search_texts_colbert(ix.mv, plain.ctx, 2, 3, texts, 32, 1, out.ctypes.data, out.ctypes.data) == -6
 
 
+def check_rows_alone(ix, queries, k, colbert=None):
+    """1,025 queries in one call are two forwards (1,024 per forward): the rows on both sides
+    of the cut, and the first, are the bits of the same query searched alone."""
+    assert len(queries) == 1025
+    s, i = ix.search_texts(queries, k, colbert=colbert)
+    assert s.shape == i.shape == (1025, k)
+    for r in (0, 1023, 1024):
+        s1, i1 = ix.search_texts([queries[r]], k, colbert=colbert)
+        assert same(s[r], s1[0]) and np.array_equal(i[r], i1[0]), r
+    return s, i
+
+
+@pytest.mark.parametrize("storage", STORAGES)
+def test_search_texts_across_the_query_chunk(model, tok_golden, storage):
+    words = corpus_words(tok_golden)
+    W = len(words)
+    ix = bertpy.BertTokenIndex(model, 20, 20 * 48, storage=storage)
+    assert ix.add_texts(corpus_texts(words, 20)) == 0
+    # 1 .. 30 words: the first forward pads to 32 rows per query, the second, query 1024 alone, to 7
+    queries = [" ".join(words[(3 * i + 11 * j) % W] for j in range(1 + i % 30)) for i in range(1025)]
+    lens = [len(model.tokenize(q)[0]) for q in queries]
+    assert max(lens[:1024]) == 32 and lens[1024] == 7 and lens[1023] == 6 and lens[0] == 3
+    s, i = check_rows_alone(ix, queries, 3)
+    assert np.all(i >= 0) and np.all(i < 20)
+
+
+@pytest.mark.parametrize("storage", STORAGES)
+def test_search_texts_colbert_across_the_query_chunk(colbert_model, storage):
+    c = bertpy.BertModel(colbert_model)
+    ix = bertpy.BertTokenIndex(c, 20, 20 * 32, width=c.proj_width, storage=storage)
+    assert ix.add_texts(COLBERT_TEXTS + [t + " " + u for t, u in zip(COLBERT_TEXTS, COLBERT_TEXTS[1:] + COLBERT_TEXTS[:1])],
+                        colbert=32) == 0 and len(ix) == 20
+    vocab = ["stone", "river", "bridge", "water", "plain", "words", "marks", "one", "two", "three", "a,", "b."]
+    queries = [" ".join(vocab[(i + 5 * j + i // 12) % 12] for j in range(1 + i % 7)) for i in range(1025)]
+    s, i = check_rows_alone(ix, queries, 3, colbert=32)
+    assert np.all(i >= 0) and np.all(i < 20)
+
+
 def tool_lines(args, queries):
     r = subprocess.run([os.path.join(ROOT, "build", "bin", "search")] + args, input="\n".join(queries) + "\nq\n",
                        capture_output=True, text=True, timeout=120)
