@@ -261,6 +261,40 @@ def load_lib(path=None):
         L.bertx_bench_maxsim_search.argtypes = [c_i32] * 8 + [c_f32p]
     except AttributeError:
         pass
+    try:   # (centroid codes and the pruned search of the token store: absent from older BERT_LIB builds)
+        c_i64 = ctypes.c_int64
+        c_u32 = ctypes.c_uint32
+        L.bertx_mvindex_set_centroids.restype = c_i32
+        L.bertx_mvindex_set_centroids.argtypes = [vp, vp, c_i32]
+        L.bertx_mvindex_train_centroids.restype = c_i32
+        L.bertx_mvindex_train_centroids.argtypes = [vp, c_i32, c_i32, c_u32]
+        L.bertx_mvindex_centroids.restype = c_i32
+        L.bertx_mvindex_centroids.argtypes = [vp]
+        L.bertx_mvindex_centroid.restype = c_i32
+        L.bertx_mvindex_centroid.argtypes = [vp, c_i32, vp]
+        L.bertx_mvindex_doc_codes.restype = c_i32
+        L.bertx_mvindex_doc_codes.argtypes = [vp, c_i32, vp]
+        L.bertx_mvindex_candidates.restype = c_i32
+        L.bertx_mvindex_candidates.argtypes = [vp, vp, c_i32, c_i32, c_i32, vp, vp]
+        L.bertx_mvindex_candidates_device.restype = c_i32
+        L.bertx_mvindex_candidates_device.argtypes = [vp, vp, c_i32, c_i32, c_i32, vp, vp, vp]
+        L.bertx_mvindex_search_pruned.restype = c_i32
+        L.bertx_mvindex_search_pruned.argtypes = [vp, vp, c_i32, c_i32, c_i32, c_i32, vp, vp]
+        L.bertx_mvindex_search_pruned_device.restype = c_i32
+        L.bertx_mvindex_search_pruned_device.argtypes = [vp, vp, c_i32, c_i32, c_i32, c_i32, vp, vp, vp]
+        L.bertx_mvindex_search_pruned_texts.restype = c_i32
+        L.bertx_mvindex_search_pruned_texts.argtypes = [vp, vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p), c_i32, c_i32,
+                                                        c_i32, vp, vp]
+        L.bertx_bench_maxsim_pruned.restype = c_i32
+        L.bertx_bench_maxsim_pruned.argtypes = [c_i32] * 10 + [c_f32p]
+        L.bertx_test_approx_ran.restype = c_i32
+        L.bertx_test_approx_ran.argtypes = [c_i32]
+        L.bertx_test_kmeans_update.restype = c_i32
+        L.bertx_test_kmeans_update.argtypes = [vp, vp, c_i32, c_i32, c_i32, vp]
+        L.bertx_test_kmeans_sample.restype = c_i32
+        L.bertx_test_kmeans_sample.argtypes = [c_i64, c_u32, vp]
+    except AttributeError:
+        pass
     try:   # (ColBERT checkpoints: the projection record and its entries; absent from older BERT_LIB builds)
         L.bertx_convert_hf_colbert.restype = c_i32
         L.bertx_convert_hf_colbert.argtypes = [ctypes.c_char_p, ctypes.c_char_p, c_i32]
@@ -878,10 +912,93 @@ class BertTokenIndex:
             raise RuntimeError("bertx_mvindex_search failed (%d)" % rc)
         return scores, ids
 
-    def search_texts(self, texts, k, colbert=None):
-        """search() of the texts as queries; colbert=query_maxlen as in score_text."""
+    def _queries(self, queries):
+        """One [Lq][width] array or a list of them as f32 [B][Lq][width], zero rows behind the shorter."""
+        if isinstance(queries, np.ndarray) and queries.ndim <= 2:
+            queries = [queries]
+        qs = [self._tokens(q) for q in queries]
+        if not qs:
+            raise ValueError("no queries")
+        Lq = max(len(q) for q in qs)
+        q = np.zeros((len(qs), Lq, self.dim), np.float32)
+        for i, a in enumerate(qs):
+            q[i, :len(a)] = a
+        return q
+
+    def set_centroids(self, cent):
+        """Centroids f32 [C][width], C a multiple of 16 in 16 .. 65,536: packed as stored rows
+        are; every stored token, and every token added later, gets the code of its nearest one
+        (bert_hip.h "Centroid codes").  A second call replaces them; clear() keeps them."""
+        cent = self._tokens(cent)
+        rc = self.lib.bertx_mvindex_set_centroids(self.mv, cent.ctypes.data, len(cent))
+        if rc != 0:
+            raise RuntimeError("bertx_mvindex_set_centroids failed (%d)" % rc)
+
+    def train_centroids(self, C, iters=8, seed=0):
+        """Deterministic spherical k-means over a sample of the stored rows; leaves the store coded."""
+        rc = self.lib.bertx_mvindex_train_centroids(self.mv, C, iters, seed)
+        if rc != 0:
+            raise RuntimeError("bertx_mvindex_train_centroids failed (%d)" % rc)
+
+    @property
+    def n_centroids(self):
+        return int(self.lib.bertx_mvindex_centroids(self.mv))
+
+    def centroid(self, c):
+        """The stored values of centroid c as f32 [width] (as doc())."""
+        out = np.zeros(self.dim, np.float32)
+        if self.lib.bertx_mvindex_centroid(self.mv, c, out.ctypes.data) != 0:
+            raise IndexError("no centroid %d" % c)
+        return out
+
+    def doc_codes(self, i):
+        """uint16 [len]: per token of document i the index of its nearest centroid."""
+        n = self.doc_len(i)
+        if n < 1:
+            raise IndexError("no document %d" % i)
+        out = np.zeros(n, np.uint16)
+        if self.lib.bertx_mvindex_doc_codes(self.mv, i, out.ctypes.data) != 0:
+            raise RuntimeError("bertx_mvindex_doc_codes failed (no centroids?)")
+        return out
+
+    def candidates(self, queries, n_cand):
+        """(approx f32 [B][n_cand], ids i32 [B][n_cand]): per query the n_cand best documents by
+        centroid interaction, MaxSim with every stored row replaced by its centroid; best
+        first, equal scores by ascending id, (-inf, -1) fill.  n_cand at most 128."""
+        q = self._queries(queries)
+        approx = np.zeros((len(q), n_cand), np.float32)
+        ids = np.zeros((len(q), n_cand), np.int32)
+        rc = self.lib.bertx_mvindex_candidates(self.mv, q.ctypes.data, q.shape[0], q.shape[1], n_cand, approx.ctypes.data,
+                                               ids.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_mvindex_candidates failed (%d)" % rc)
+        return approx, ids
+
+    def search_pruned(self, queries, k, n_cand):
+        """search() over the n_cand candidates of candidates() only: their exact scores (the
+        bits of score()), the k best.  k <= n_cand <= 128; with n_cand >= len(self) the result
+        is search()'s."""
+        q = self._queries(queries)
+        scores = np.zeros((len(q), k), np.float32)
+        ids = np.zeros((len(q), k), np.int32)
+        rc = self.lib.bertx_mvindex_search_pruned(self.mv, q.ctypes.data, q.shape[0], q.shape[1], k, n_cand,
+                                                  scores.ctypes.data, ids.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_mvindex_search_pruned failed (%d)" % rc)
+        return scores, ids
+
+    def search_texts(self, texts, k, colbert=None, n_cand=None):
+        """search() of the texts as queries; colbert=query_maxlen as in score_text.  n_cand: the
+        pruned search (search_pruned) over that many candidates per query; None: the full scan."""
         scores = np.zeros((len(texts), k), np.float32)
         ids = np.zeros((len(texts), k), np.int32)
+        if n_cand is not None:
+            rc = self.lib.bertx_mvindex_search_pruned_texts(self.mv, self.model.ctx, self.model.N_THREADS, len(texts),
+                                                            BertIndex._texts(texts), k, n_cand, colbert or 0,
+                                                            scores.ctypes.data, ids.ctypes.data)
+            if rc != 0:
+                raise RuntimeError("bertx_mvindex_search_pruned_texts failed (%d)" % rc)
+            return scores, ids
         if colbert is not None:
             rc = self.lib.bertx_mvindex_search_texts_colbert(self.mv, self.model.ctx, self.model.N_THREADS, len(texts),
                                                              BertIndex._texts(texts), colbert, k, scores.ctypes.data,

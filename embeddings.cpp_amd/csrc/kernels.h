@@ -287,6 +287,35 @@ int launch_maxsim_search(const void *store, const float *scales, int storage, co
                          int64_t used_groups, int w, const float *d_q, int B, int Lq, int k, void *scratch,
                          float *d_scores, int32_t *d_ids, hipStream_t s);
 
+// ---- centroid codes of the token store (maxsim_codes.hip; bert_hip.h "Centroid codes") ----
+// The centroids are C rows (a multiple of 16) packed as one document of C tokens from group
+// 0 of their own buffer (launch_mv_pack / launch_mv_pack_i8), cent_u their f32 (int8).
+// codes uint16 [token slots]: for every slot of groups g0 .. g1 - 1 of the store the index of
+// the centroid of highest sim to the slot's row, the row re-packed from its stored values in
+// the query role, equal sims to the lower index.  Then the slots of documents d0 .. d1 - 1
+// past their len are set to 0.  Once per device: maxsim_codes_prepare_device.
+int maxsim_codes_prepare_device();
+int launch_mv_assign(const void *store, const float *scales, int storage, const void *d_table, int64_t g0, int64_t g1,
+                     int d0, int d1, int w, const void *cent, const float *cent_u, int C, uint16_t *codes,
+                     hipStream_t s);
+
+// ---- centroid interaction (maxsim_approx.hip; bert_hip.h "Pruned search") ----
+// One pass of nq queries of ceil(Lq / 16) tiles each (at most four tiles), d_q f32
+// [nq][Lq][w]: the table T f32 [C][16 tiles] = sim(query row, centroid) into tscratch
+// (256 C bytes), the scan of every document's codes and the selection: d_approx / d_ids
+// [nq][n_cand] by `better` with (-inf, -1) fill.  scratch: the search's.  *form: 1 the
+// table went to LDS, 2 it stayed in global memory.  stages: 1 the table kernel, 2 the scan and
+// the selection, 3 both (the benches time them apart).  -1: bad arguments, -3: launch refused.
+int maxsim_approx_prepare_device();
+int launch_maxsim_candidates(const uint16_t *codes, const void *d_table, int n_docs, int64_t used_groups, int storage,
+                             int w, const void *cent, const float *cent_u, int C, const float *d_q, int nq, int Lq,
+                             int n_cand, float *tscratch, void *scratch, float *d_approx, int32_t *d_ids, int stages,
+                             int *form, hipStream_t s);
+// out_s / out_i [nq][k] = the k best by `better` of each query's n_cand (exact[j], ids[j])
+// pairs; a pair whose id is -1 counts as the fill.
+int launch_maxsim_rerank_select(const float *exact, const int32_t *ids, int nq, int n_cand, int k, float *out_s,
+                                int32_t *out_i, hipStream_t s);
+
 // ---- the classification head (head.hip): pooler dense + tanh + classifier on the
 // sentences' [CLS] rows, all f32, one form for the three chains ----
 constexpr int HEAD_MAX_LABELS = 16;

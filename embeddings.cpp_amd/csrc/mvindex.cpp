@@ -13,10 +13,13 @@
 #include "chunk_rule.h"
 #include "engine.h"
 #include "hip_check.h"
+#include "kmeans_update.h"
 #include "store_common.h"
 #include "task_pool.h"
 
 #include <algorithm>
+#include <atomic>
+#include <cmath>
 #include <cstring>
 #include <limits>
 #include <mutex>
@@ -40,6 +43,17 @@ struct bertx_mvindex {
     float *st_rows = nullptr, *st_q = nullptr, *st_out = nullptr;
     int32_t *st_ids = nullptr, *st_tok = nullptr;
     void *search_scratch = nullptr;        // the partial lists of the full-scan search (maxsim_search_scratch_bytes)
+    // centroid codes (set_centroids; all null / 0 before): the C centroids packed as one
+    // document of their own buffer, their f32 (int8), one code per token slot, the table of
+    // a candidates pass (256 C bytes), and the candidate lists of kCandQueries queries
+    int32_t C = 0, cap_C = 0;
+    void *cent = nullptr;
+    float *cent_u = nullptr;
+    uint16_t *codes = nullptr;
+    float *tscratch = nullptr;
+    float *cand_approx = nullptr, *cand_exact = nullptr;
+    int32_t *cand_ids = nullptr;
+    int32_t *cent_entry = nullptr;         // device: (0, C) the centroids' table entry, then their source offset 0
     hipStream_t stream = nullptr;
     emb::StoreOrder ord;
     std::mutex mu;
@@ -51,7 +65,8 @@ struct bertx_mvindex {
         // images freed below)
         if (ord.done) (void)ord.wait();
         for (void *p : {store, (void *)scales, (void *)table, (void *)src_off, (void *)st_rows, (void *)st_q, (void *)st_out,
-                        (void *)st_ids, (void *)st_tok, search_scratch})
+                        (void *)st_ids, (void *)st_tok, search_scratch, cent, (void *)cent_u, (void *)codes,
+                        (void *)tscratch, (void *)cand_approx, (void *)cand_exact, (void *)cand_ids, (void *)cent_entry})
             if (p) (void)hipFree(p);
         if (h_table) (void)hipHostFree(h_table);
         if (h_src) (void)hipHostFree(h_src);
@@ -68,6 +83,24 @@ constexpr int kStageIds = 65536;    // candidates per staged chunk of the host s
 constexpr int kMaxLq = 64;
 constexpr int kMaxK = 128;
 constexpr int kSearchTexts = 1024;  // queries per forward of the search text forms (at most 2^16 tokens)
+constexpr int kCandQueries = 64;    // queries whose candidate lists the store's scratch holds at a time
+
+std::atomic<int> g_approx_forms{0};   // bertx_test_approx_ran: 1 the table went to LDS, 2 global memory
+
+// The codes of the documents first_doc .. first_doc + n - 1, which take the groups from g0 on
+// (a store without centroids keeps none).
+int32_t assign_codes(bertx_mvindex &mv, int64_t g0, int64_t g1, int32_t d0, int32_t d1, hipStream_t s)
+{
+    if (mv.C == 0 || g1 <= g0) return 0;
+    return launch_mv_assign(mv.store, mv.scales, mv.storage, mv.table, g0, g1, d0, d1, mv.w, mv.cent, mv.cent_u, mv.C,
+                            mv.codes, s);
+}
+
+// After the rows of an add are packed, on the same stream: the new documents' codes.
+int32_t assign_new(bertx_mvindex &mv, int32_t n, int64_t slots, hipStream_t s)
+{
+    return assign_codes(mv, mv.used_slots / 16, (mv.used_slots + slots) / 16, (int32_t)mv.n_docs, (int32_t)mv.n_docs + n, s);
+}
 
 // The first half of an add: checks the lens and both capacities and writes the new
 // documents' entries into the host images.  Returns 0 with *T the source rows and
@@ -140,6 +173,7 @@ int32_t add_device_locked(bertx_mvindex &mv, const float *d_rows, const int32_t 
         Ordered o(mv.ord, s);
         rc = upload_entries(mv, n, s);
         if (rc == 0) rc = pack(mv, d_rows, 0, T, n, s);
+        if (rc == 0) rc = assign_new(mv, n, slots, s);
     }
     if (rc != 0) {
         (void)hipStreamSynchronize(s);   // the entries may be rewritten by the next add
@@ -215,6 +249,40 @@ int32_t read_doc_i8(bertx_mvindex &mv, int32_t id, int8_t *q, float *u)
     return 0;
 }
 
+// bertx_mvindex_doc under the caller's lock, the id checked and the device selected.
+int32_t doc_locked(bertx_mvindex *mv, int32_t id, float *out)
+{
+    if (mv->storage == BERTX_INDEX_I8) {
+        try {
+            const int w = mv->w;
+            const int64_t len = mv->h_table[2 * (size_t)id + 1];
+            std::vector<int8_t> q((size_t)len * w);
+            std::vector<float> u((size_t)len);
+            const int32_t rc = emb::read_doc_i8(*mv, id, q.data(), u.data());
+            if (rc != 0) return rc;
+            for (int64_t r = 0; r < len; ++r)
+                for (int i = 0; i < w; ++i) out[(size_t)r * w + i] = (float)q[(size_t)r * w + i] * u[(size_t)r];
+        } catch (const std::bad_alloc &) {
+            emb::errorf("bertx_mvindex_doc: out of host memory\n");
+            return -1;
+        }
+        return 0;
+    }
+    try {
+        const int64_t first = mv->h_table[2 * (size_t)id], len = mv->h_table[2 * (size_t)id + 1];
+        const size_t group_halfs = (size_t)16 * mv->w;
+        std::vector<uint16_t> raw((size_t)((len + 15) / 16) * group_halfs);
+        HIP_RC(mv->ord.wait());
+        HIP_RC(hipMemcpy(raw.data(), (const uint16_t *)mv->store + (size_t)first * group_halfs, raw.size() * 2,
+                         hipMemcpyDeviceToHost));
+        emb::unpack_f16_rows(raw.data(), 0, 0, len, mv->w, out);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_mvindex_doc: out of host memory\n");
+        return -1;
+    }
+    return 0;
+}
+
 // The context's replica on the store's GPU, or -1 with a message.
 int32_t slot_on(struct bert_ctx *ctx, int ordinal, const char *who)
 {
@@ -234,14 +302,85 @@ int32_t text_ctx_ok(bertx_mvindex *mv, struct bert_ctx *ctx, const char *who, in
     return (*slot = slot_on(ctx, mv->ordinal, who)) < 0 ? -1 : 0;
 }
 
+bool pruned_args_ok(const bertx_mvindex &mv, const char *who, int32_t B, int32_t Lq, int32_t k, int32_t n_cand)
+{
+    if (B < 1 || Lq < 1 || Lq > kMaxLq || k < 1 || k > n_cand || n_cand > kMaxK) {
+        errorf("%s: B = %d, Lq = %d, k = %d, n_cand = %d are not in B >= 1, 1 <= Lq <= %d, 1 <= k <= n_cand <= %d\n", who, B,
+               Lq, k, n_cand, kMaxLq, kMaxK);
+        return false;
+    }
+    if (mv.C == 0) {
+        errorf("%s: no centroids set (bertx_mvindex_set_centroids / _train_centroids)\n", who);
+        return false;
+    }
+    return true;
+}
+
+// The candidate lists of B queries, floor(4 / ceil(Lq / 16)) per pass; the caller orders the
+// stream.
+int32_t candidates_launch(bertx_mvindex &mv, const float *d_q, int32_t B, int32_t Lq, int32_t n_cand, float *d_approx,
+                          int32_t *d_ids, hipStream_t s)
+{
+    const int32_t per_pass = 4 / ((Lq + 15) / 16);
+    for (int32_t b0 = 0; b0 < B; b0 += per_pass) {
+        int form = 0;
+        const int32_t rc = launch_maxsim_candidates(mv.codes, mv.table, (int)mv.n_docs, mv.used_slots / 16, mv.storage, mv.w,
+                                                    mv.cent, mv.cent_u, mv.C, d_q + (size_t)b0 * Lq * mv.w,
+                                                    std::min(per_pass, B - b0), Lq, n_cand, mv.tscratch, mv.search_scratch,
+                                                    d_approx + (size_t)b0 * n_cand, d_ids + (size_t)b0 * n_cand, 3, &form, s);
+        if (rc != 0) return rc;
+        g_approx_forms.fetch_or(form);
+    }
+    return 0;
+}
+
+int32_t candidates_device_locked(bertx_mvindex &mv, const float *d_q, int32_t B, int32_t Lq, int32_t n_cand,
+                                 float *d_approx, int32_t *d_ids, hipStream_t s)
+{
+    if (!d_q || !d_approx || !d_ids || !pruned_args_ok(mv, "bertx_mvindex_candidates", B, Lq, 1, n_cand)) return -1;
+    Ordered o(mv.ord, s);
+    return candidates_launch(mv, d_q, B, Lq, n_cand, d_approx, d_ids, s);
+}
+
+// kCandQueries queries at a time through the store's candidate scratch: their candidates,
+// the scorer over each query's candidate ids (a fill id -1 scores -inf), the k best.
+int32_t search_pruned_device_locked(bertx_mvindex &mv, const float *d_q, int32_t B, int32_t Lq, int32_t k, int32_t n_cand,
+                                    float *d_scores, int32_t *d_ids, hipStream_t s)
+{
+    if (!d_q || !d_scores || !d_ids || !pruned_args_ok(mv, "bertx_mvindex_search_pruned", B, Lq, k, n_cand)) return -1;
+    Ordered o(mv.ord, s);
+    for (int32_t c0 = 0; c0 < B; c0 += kCandQueries) {
+        const int32_t m = std::min(kCandQueries, B - c0);
+        const float *Q = d_q + (size_t)c0 * Lq * mv.w;
+        int32_t rc = candidates_launch(mv, Q, m, Lq, n_cand, mv.cand_approx, mv.cand_ids, s);
+        for (int32_t b = 0; b < m && rc == 0; ++b) {
+            const float *qb = Q + (size_t)b * Lq * mv.w;
+            const int32_t *ib = mv.cand_ids + (size_t)b * n_cand;
+            float *ob = mv.cand_exact + (size_t)b * n_cand;
+            rc = mv.storage == BERTX_INDEX_I8
+                     ? launch_maxsim_i8(mv.store, mv.scales, mv.table, (int)mv.n_docs, mv.w, qb, Lq, ib, n_cand, ob, s)
+                     : launch_maxsim(mv.store, mv.table, (int)mv.n_docs, mv.w, qb, Lq, ib, n_cand, ob, s);
+        }
+        if (rc == 0)
+            rc = launch_maxsim_rerank_select(mv.cand_exact, mv.cand_ids, m, n_cand, k, d_scores + (size_t)c0 * k,
+                                             d_ids + (size_t)c0 * k, s);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
 // B queries f32 [B][Lq][w] already on the device, on the store's stream: their results
-// into host vectors (the caller copies them out when the whole call succeeded).
-int32_t search_to_host(bertx_mvindex &mv, const float *d_q, int32_t B, int32_t Lq, int32_t k, float *scores, int32_t *ids)
+// into host vectors (the caller copies them out when the whole call succeeded).  n_cand > 0:
+// by the pruned search.
+int32_t search_to_host(bertx_mvindex &mv, const float *d_q, int32_t B, int32_t Lq, int32_t k, float *scores, int32_t *ids,
+                       int32_t n_cand = 0)
 {
     DevBuf d_s, d_i;
     HIP_RC(hipMalloc(&d_s.p, (size_t)B * k * 4));
     HIP_RC(hipMalloc(&d_i.p, (size_t)B * k * 4));
-    const int32_t rc = search_device_locked(mv, d_q, B, Lq, k, (float *)d_s.p, (int32_t *)d_i.p, mv.stream);
+    const int32_t rc = n_cand > 0 ? search_pruned_device_locked(mv, d_q, B, Lq, k, n_cand, (float *)d_s.p, (int32_t *)d_i.p,
+                                                                mv.stream)
+                                  : search_device_locked(mv, d_q, B, Lq, k, (float *)d_s.p, (int32_t *)d_i.p, mv.stream);
     if (rc != 0) {
         (void)hipStreamSynchronize(mv.stream);
         return rc;
@@ -416,6 +555,7 @@ int32_t add_texts(bertx_mvindex &mv, struct bert_ctx *ctx, const TextRows &t, in
             t0 += rows;
             i = e;
         }
+        if (rc == 0) rc = assign_new(mv, n, slots, mv.stream);
     }
     if (rc != 0) {
         (void)hipGetLastError();
@@ -458,7 +598,7 @@ int32_t score_text(bertx_mvindex &mv, struct bert_ctx *ctx, const TextRows &t, c
 // it is; otherwise the rows are laid out with zero rows behind the shorter queries
 // (device-to-device) first.  The outputs are written when every chunk succeeded.
 int32_t search_texts(bertx_mvindex &mv, struct bert_ctx *ctx, const TextRows &t, int32_t n, int32_t k, float *scores,
-                     int32_t *ids)
+                     int32_t *ids, int32_t n_cand = 0)
 {
     const size_t w = (size_t)mv.w;
     std::vector<float> hs((size_t)n * k);
@@ -492,7 +632,8 @@ int32_t search_texts(bertx_mvindex &mv, struct bert_ctx *ctx, const TextRows &t,
                 d_q = (const float *)d_pad.p;
             }
         }
-        if (rc == 0) rc = search_to_host(mv, d_q, m, Lmax, k, hs.data() + (size_t)i0 * k, hi.data() + (size_t)i0 * k);
+        if (rc == 0)
+            rc = search_to_host(mv, d_q, m, Lmax, k, hs.data() + (size_t)i0 * k, hi.data() + (size_t)i0 * k, n_cand);
         if (rc != 0) {
             (void)hipGetLastError();
             (void)hipStreamSynchronize(mv.stream);
@@ -537,6 +678,7 @@ bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t c
     const bool i8 = storage == BERTX_INDEX_I8;
     const size_t store_bytes = slots16 * (size_t)w * (i8 ? 1 : 2);
     const bool ok = maxsim_prepare_device() == 0 && maxsim_search_prepare_device() == 0 &&
+                    maxsim_codes_prepare_device() == 0 && maxsim_approx_prepare_device() == 0 &&
                     hipMalloc(&mv->search_scratch, maxsim_search_scratch_bytes()) == hipSuccess &&
                     hipStreamCreateWithFlags(&mv->stream, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&mv->ord.done, hipEventDisableTiming) == hipSuccess &&
@@ -561,6 +703,117 @@ bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t c
     return mv;
 }
 
+}  // namespace emb
+
+namespace emb {
+namespace {
+
+bool centroid_count_ok(const char *who, int32_t C)
+{
+    if (C >= 16 && C <= 65536 && C % 16 == 0) return true;
+    errorf("%s: C = %d is not a multiple of 16 in 16 .. 65536\n", who, C);
+    return false;
+}
+
+// bertx_mvindex_set_centroids under the caller's lock with the device selected.  The
+// buffers grow first, all or none; then the rows are packed through the add's staging by
+// the store's own pack kernel, as one document of C tokens, and every stored token is coded.
+int32_t set_centroids_locked(bertx_mvindex &mv, const float *cent, int32_t C)
+{
+    if (!cent || !centroid_count_ok("bertx_mvindex_set_centroids", C)) return -1;
+    const bool i8 = mv.storage == BERTX_INDEX_I8;
+    if (C > mv.cap_C) {
+        const size_t slots16 = (size_t)((mv.cap_slots + 15) / 16) * 16;
+        DevBuf n_cent, n_u, n_t, n_codes, n_a, n_x, n_i, n_e;
+        const bool ok = hipMalloc(&n_cent.p, (size_t)C * mv.w * (i8 ? 1 : 2)) == hipSuccess &&
+                        (!i8 || hipMalloc(&n_u.p, (size_t)C * 4) == hipSuccess) &&
+                        hipMalloc(&n_t.p, (size_t)256 * C) == hipSuccess &&
+                        (mv.codes || (hipMalloc(&n_codes.p, slots16 * 2) == hipSuccess &&
+                                      hipMalloc(&n_a.p, (size_t)kCandQueries * kMaxK * 4) == hipSuccess &&
+                                      hipMalloc(&n_x.p, (size_t)kCandQueries * kMaxK * 4) == hipSuccess &&
+                                      hipMalloc(&n_i.p, (size_t)kCandQueries * kMaxK * 4) == hipSuccess &&
+                                      hipMalloc(&n_e.p, 16) == hipSuccess));
+        if (!ok) {
+            (void)hipGetLastError();
+            errorf("bertx_mvindex_set_centroids: device %d could not allocate the buffers of %d centroids\n", mv.ordinal, C);
+            return -3;
+        }
+        HIP_RC(mv.ord.wait());   // the old buffers may still be read
+        std::swap(mv.cent, n_cent.p);
+        void *u = mv.cent_u, *t = mv.tscratch;
+        mv.cent_u = (float *)n_u.p;
+        mv.tscratch = (float *)n_t.p;
+        n_u.p = u;
+        n_t.p = t;
+        if (!mv.codes) {
+            mv.codes = (uint16_t *)n_codes.p;
+            mv.cand_approx = (float *)n_a.p;
+            mv.cand_exact = (float *)n_x.p;
+            mv.cand_ids = (int32_t *)n_i.p;
+            mv.cent_entry = (int32_t *)n_e.p;
+            n_codes.p = n_a.p = n_x.p = n_i.p = n_e.p = nullptr;
+        }
+        mv.cap_C = C;
+    }
+    mv.C = 0;   // until every step below has been queued
+    const int32_t entry[4] = {0, C, 0, 0};
+    int32_t rc = 0;
+    {
+        Ordered o(mv.ord, mv.stream);
+        if (hipMemcpyAsync(mv.cent_entry, entry, sizeof entry, hipMemcpyHostToDevice, mv.stream) != hipSuccess) rc = -1;
+        for (int64_t t = 0; t < C && rc == 0; t += kStageRows) {
+            const int64_t m = std::min<int64_t>(kStageRows, C - t);
+            if (hipMemcpyAsync(mv.st_rows, cent + (size_t)t * mv.w, (size_t)m * mv.w * 4, hipMemcpyHostToDevice, mv.stream) !=
+                hipSuccess)
+                rc = -1;
+            if (rc == 0)
+                rc = i8 ? launch_mv_pack_i8(mv.st_rows, t, m, mv.w, mv.cent_entry + 2, mv.cent_entry, 1, mv.cent, mv.cent_u,
+                                            mv.stream)
+                        : launch_mv_pack(mv.st_rows, t, m, mv.w, mv.cent_entry + 2, mv.cent_entry, 1, mv.cent, mv.stream);
+            if (rc == 0 && hipStreamSynchronize(mv.stream) != hipSuccess) rc = -1;   // the staging buffer is reused
+        }
+        if (rc == 0) {
+            mv.C = C;
+            rc = assign_codes(mv, 0, mv.used_slots / 16, 0, (int32_t)mv.n_docs, mv.stream);
+        }
+    }
+    if (rc != 0) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(mv.stream);
+        mv.C = 0;
+        errorf("bertx_mvindex_set_centroids: device %d failed (%d); the store has no centroids now\n", mv.ordinal, rc);
+    }
+    return rc;
+}
+
+// B queries on the host through the device form `run`, per results of each: staged through
+// buffers of the call, the outputs written when everything succeeded.
+template <class Run>
+int32_t queries_to_host(bertx_mvindex &mv, const float *q, int32_t B, int32_t Lq, int32_t per, Run run, float *scores,
+                        int32_t *ids)
+{
+    const size_t nq = (size_t)B * Lq * mv.w, nr = (size_t)B * per;
+    std::vector<float> hs(nr);
+    std::vector<int32_t> hi(nr);
+    DevBuf d_q, d_s, d_i;
+    HIP_RC(hipMalloc(&d_q.p, nq * 4));
+    HIP_RC(hipMalloc(&d_s.p, nr * 4));
+    HIP_RC(hipMalloc(&d_i.p, nr * 4));
+    HIP_RC(hipMemcpyAsync(d_q.p, q, nq * 4, hipMemcpyHostToDevice, mv.stream));
+    const int32_t rc = run((const float *)d_q.p, (float *)d_s.p, (int32_t *)d_i.p);
+    if (rc != 0) {
+        (void)hipStreamSynchronize(mv.stream);
+        return rc;
+    }
+    HIP_RC(hipMemcpyAsync(hs.data(), d_s.p, nr * 4, hipMemcpyDeviceToHost, mv.stream));
+    HIP_RC(hipMemcpyAsync(hi.data(), d_i.p, nr * 4, hipMemcpyDeviceToHost, mv.stream));
+    HIP_RC(hipStreamSynchronize(mv.stream));
+    std::memcpy(scores, hs.data(), nr * 4);
+    std::memcpy(ids, hi.data(), nr * 4);
+    return 0;
+}
+
+}  // namespace
 }  // namespace emb
 
 using emb::DeviceGuard;
@@ -659,6 +912,7 @@ int32_t bertx_mvindex_add(struct bertx_mvindex *mv, const float *rows, const int
             if (rc == 0) rc = emb::pack(*mv, mv->st_rows, t, m, n, mv->stream);
             if (rc == 0 && hipStreamSynchronize(mv->stream) != hipSuccess) rc = -1;   // the staging buffer is reused
         }
+        if (rc == 0) rc = emb::assign_new(*mv, n, slots, mv->stream);
     }
     if (rc != 0) {
         (void)hipGetLastError();
@@ -684,35 +938,7 @@ int32_t bertx_mvindex_doc(struct bertx_mvindex *mv, int32_t id, float *out)
     if (id < 0 || id >= mv->n_docs) return -1;
     DeviceGuard g(mv->ordinal);
     HIP_RC(g.status());
-    if (mv->storage == BERTX_INDEX_I8) {
-        try {
-            const int w = mv->w;
-            const int64_t len = mv->h_table[2 * (size_t)id + 1];
-            std::vector<int8_t> q((size_t)len * w);
-            std::vector<float> u((size_t)len);
-            const int32_t rc = emb::read_doc_i8(*mv, id, q.data(), u.data());
-            if (rc != 0) return rc;
-            for (int64_t r = 0; r < len; ++r)
-                for (int i = 0; i < w; ++i) out[(size_t)r * w + i] = (float)q[(size_t)r * w + i] * u[(size_t)r];
-        } catch (const std::bad_alloc &) {
-            emb::errorf("bertx_mvindex_doc: out of host memory\n");
-            return -1;
-        }
-        return 0;
-    }
-    try {
-        const int64_t first = mv->h_table[2 * (size_t)id], len = mv->h_table[2 * (size_t)id + 1];
-        const size_t group_halfs = (size_t)16 * mv->w;
-        std::vector<uint16_t> raw((size_t)((len + 15) / 16) * group_halfs);
-        HIP_RC(mv->ord.wait());
-        HIP_RC(hipMemcpy(raw.data(), (const uint16_t *)mv->store + (size_t)first * group_halfs, raw.size() * 2,
-                         hipMemcpyDeviceToHost));
-        emb::unpack_f16_rows(raw.data(), 0, 0, len, mv->w, out);
-    } catch (const std::bad_alloc &) {
-        emb::errorf("bertx_mvindex_doc: out of host memory\n");
-        return -1;
-    }
-    return 0;
+    return emb::doc_locked(mv, id, out);
 }
 
 int32_t bertx_mvindex_doc_i8(struct bertx_mvindex *mv, int32_t id, int8_t *q, float *u)
@@ -927,17 +1153,268 @@ int32_t bertx_mvindex_search_texts_colbert(struct bertx_mvindex *mv, struct bert
     }
 }
 
+int32_t bertx_mvindex_set_centroids(struct bertx_mvindex *mv, const float *cent, int32_t C)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    if (!cent || !emb::centroid_count_ok("bertx_mvindex_set_centroids", C)) return -1;
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    return emb::set_centroids_locked(*mv, cent, C);
+}
+
+int32_t bertx_mvindex_centroids(struct bertx_mvindex *mv)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    return mv->C;
+}
+
+int32_t bertx_mvindex_centroid(struct bertx_mvindex *mv, int32_t c, float *out)
+{
+    if (!mv || !out) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    if (c < 0 || c >= mv->C) return -1;
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    try {
+        const int w = mv->w;
+        const size_t grp = (size_t)(c / 16);
+        HIP_RC(mv->ord.wait());
+        if (mv->storage == BERTX_INDEX_I8) {
+            std::vector<int8_t> raw((size_t)16 * w), q((size_t)w);
+            float u = 0.f;
+            HIP_RC(hipMemcpy(raw.data(), (const int8_t *)mv->cent + grp * raw.size(), raw.size(), hipMemcpyDeviceToHost));
+            HIP_RC(hipMemcpy(&u, mv->cent_u + c, 4, hipMemcpyDeviceToHost));
+            emb::unpack_i8_rows(raw.data(), (int64_t)grp * 16, c, 1, w, q.data());
+            for (int i = 0; i < w; ++i) out[i] = (float)q[(size_t)i] * u;
+        } else {
+            std::vector<uint16_t> raw((size_t)16 * w);
+            std::vector<float> row((size_t)w);
+            HIP_RC(hipMemcpy(raw.data(), (const uint16_t *)mv->cent + grp * raw.size(), raw.size() * 2, hipMemcpyDeviceToHost));
+            emb::unpack_f16_rows(raw.data(), (int64_t)grp * 16, c, 1, w, row.data());
+            std::memcpy(out, row.data(), row.size() * 4);
+        }
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_mvindex_centroid: out of host memory\n");
+        return -1;
+    }
+    return 0;
+}
+
+int32_t bertx_mvindex_doc_codes(struct bertx_mvindex *mv, int32_t id, uint16_t *codes)
+{
+    if (!mv || !codes) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    if (mv->C == 0 || id < 0 || id >= mv->n_docs) return -1;
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    try {
+        const int64_t first = mv->h_table[2 * (size_t)id], len = mv->h_table[2 * (size_t)id + 1];
+        std::vector<uint16_t> h((size_t)len);
+        HIP_RC(mv->ord.wait());
+        HIP_RC(hipMemcpy(h.data(), mv->codes + (size_t)first * 16, h.size() * 2, hipMemcpyDeviceToHost));
+        std::memcpy(codes, h.data(), h.size() * 2);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_mvindex_doc_codes: out of host memory\n");
+        return -1;
+    }
+    return 0;
+}
+
+int32_t bertx_mvindex_train_centroids(struct bertx_mvindex *mv, int32_t C, int32_t iters, uint32_t seed)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    if (!emb::centroid_count_ok("bertx_mvindex_train_centroids", C)) return -1;
+    if (iters < 0 || mv->n_docs < 1) {
+        emb::errorf("bertx_mvindex_train_centroids: iters = %d, %lld documents: nothing to train on\n", iters,
+                    (long long)mv->n_docs);
+        return -1;
+    }
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    try {
+        const int w = mv->w;
+        int64_t T = 0;
+        for (int64_t d = 0; d < mv->n_docs; ++d) T += mv->h_table[2 * (size_t)d + 1];
+        const emb::KmeansSample sm = emb::kmeans_sample(T, seed);
+        if (C > sm.n) {
+            emb::errorf("bertx_mvindex_train_centroids: C = %d exceeds the sample of %lld token rows\n", C, (long long)sm.n);
+            return -1;
+        }
+        // the sample's rows (bertx_mvindex_doc's values) and the slots their codes sit in
+        std::vector<float> sample((size_t)sm.n * w), rows;
+        std::vector<int64_t> slot((size_t)sm.n);
+        int64_t t0 = 0, next = sm.start, i = 0;
+        for (int32_t d = 0; d < mv->n_docs; ++d) {
+            const int64_t first = mv->h_table[2 * (size_t)d], len = mv->h_table[2 * (size_t)d + 1];
+            if (next < t0 + len) {
+                rows.resize((size_t)len * w);
+                const int32_t rc = emb::doc_locked(mv, d, rows.data());
+                if (rc != 0) return rc;
+                for (; next < t0 + len; next += sm.stride, ++i) {
+                    std::memcpy(sample.data() + (size_t)i * w, rows.data() + (size_t)(next - t0) * w, (size_t)w * 4);
+                    slot[(size_t)i] = first * 16 + (next - t0);
+                }
+            }
+            t0 += len;
+        }
+        std::vector<float> cent((size_t)C * w);
+        for (int64_t c = 0; c < C; ++c)
+            std::memcpy(cent.data() + (size_t)c * w, sample.data() + (size_t)emb::kmeans_initial_row(c, sm.n, C) * w,
+                        (size_t)w * 4);
+        std::vector<uint16_t> all((size_t)mv->used_slots), codes((size_t)sm.n);
+        for (int32_t it = 0; it < iters; ++it) {
+            const int32_t rc = emb::set_centroids_locked(*mv, cent.data(), C);
+            if (rc != 0) return rc;
+            HIP_RC(mv->ord.wait());
+            HIP_RC(hipMemcpy(all.data(), mv->codes, all.size() * 2, hipMemcpyDeviceToHost));
+            for (int64_t j = 0; j < sm.n; ++j) codes[(size_t)j] = all[(size_t)slot[(size_t)j]];
+            (void)emb::kmeans_update(sample.data(), codes.data(), sm.n, w, C, cent.data());
+        }
+        return emb::set_centroids_locked(*mv, cent.data(), C);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_mvindex_train_centroids: out of host memory\n");
+        return -1;
+    }
+}
+
+int32_t bertx_test_kmeans_update(const float *sample, const uint16_t *codes, int32_t n, int32_t w, int32_t C, float *cent)
+{
+    if (!sample || !codes || !cent || n < 0 || w < 1 || C < 1) return -1;
+    return (int32_t)emb::kmeans_update(sample, codes, n, w, C, cent);
+}
+
+int32_t bertx_test_kmeans_sample(int64_t T, uint32_t seed, int64_t *out3)
+{
+    if (!out3 || T < 0) return -1;
+    const emb::KmeansSample s = emb::kmeans_sample(T, seed);
+    out3[0] = s.stride;
+    out3[1] = s.start;
+    out3[2] = s.n;
+    return 0;
+}
+
+int32_t bertx_test_approx_ran(int32_t reset)
+{
+    return reset ? emb::g_approx_forms.exchange(0) : emb::g_approx_forms.load();
+}
+
+int32_t bertx_mvindex_candidates_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq, int32_t n_cand,
+                                        float *d_approx, int32_t *d_ids, void *stream)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    return emb::candidates_device_locked(*mv, d_q, B, Lq, n_cand, d_approx, d_ids, stream ? (hipStream_t)stream : mv->stream);
+}
+
+int32_t bertx_mvindex_candidates(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t n_cand,
+                                 float *approx, int32_t *ids)
+{
+    if (!mv || !q || !approx || !ids) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    if (!emb::pruned_args_ok(*mv, "bertx_mvindex_candidates", B, Lq, 1, n_cand)) return -1;
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    try {
+        return emb::queries_to_host(*mv, q, B, Lq, n_cand, [&](const float *dq, float *ds, int32_t *di) {
+            return emb::candidates_device_locked(*mv, dq, B, Lq, n_cand, ds, di, mv->stream);
+        }, approx, ids);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_mvindex_candidates: out of host memory\n");
+        return -1;
+    }
+}
+
+int32_t bertx_mvindex_search_pruned_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq, int32_t k,
+                                           int32_t n_cand, float *d_scores, int32_t *d_ids, void *stream)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    return emb::search_pruned_device_locked(*mv, d_q, B, Lq, k, n_cand, d_scores, d_ids,
+                                            stream ? (hipStream_t)stream : mv->stream);
+}
+
+int32_t bertx_mvindex_search_pruned(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t k,
+                                    int32_t n_cand, float *scores, int32_t *ids)
+{
+    if (!mv || !q || !scores || !ids) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    if (!emb::pruned_args_ok(*mv, "bertx_mvindex_search_pruned", B, Lq, k, n_cand)) return -1;
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    try {
+        return emb::queries_to_host(*mv, q, B, Lq, k, [&](const float *dq, float *ds, int32_t *di) {
+            return emb::search_pruned_device_locked(*mv, dq, B, Lq, k, n_cand, ds, di, mv->stream);
+        }, scores, ids);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_mvindex_search_pruned: out of host memory\n");
+        return -1;
+    }
+}
+
+int32_t bertx_mvindex_search_pruned_texts(struct bertx_mvindex *mv, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                          const char **texts, int32_t k, int32_t n_cand, int32_t colbert_query_maxlen,
+                                          float *scores, int32_t *ids)
+{
+    int32_t slot = -1;
+    const char *who = "bertx_mvindex_search_pruned_texts";
+    if (!texts || !scores || !ids || n < 1) return -1;
+    const bool colbert = colbert_query_maxlen != 0;
+    if (colbert) {
+        if (const int32_t rc = emb::colbert_ctx_ok(mv, ctx, who, &slot)) return rc;
+        if (colbert_query_maxlen < 4 || colbert_query_maxlen > emb::kMaxLq || colbert_query_maxlen > bert_n_max_tokens(ctx))
+            return -1;
+    } else if (emb::text_ctx_ok(mv, ctx, who, &slot) != 0) {
+        return -1;
+    }
+    {
+        std::lock_guard<std::mutex> lk(mv->mu);
+        if (!emb::pruned_args_ok(*mv, who, n, colbert ? colbert_query_maxlen : 1, k, n_cand)) return -1;
+    }
+    for (int32_t i = 0; i < n; ++i)
+        if (!texts[i]) return -1;
+    try {
+        emb::TextRows t;
+        if (colbert) {
+            if (emb::tokenize_colbert(ctx, n_threads, n, texts, 0, colbert_query_maxlen, slot, t) != 0) return -1;
+        } else {
+            if (emb::tokenize_plain(ctx, n_threads, n, texts, slot, t) != 0) return -1;
+            const int32_t lim = std::min<int32_t>(bert_n_max_tokens(ctx), emb::kMaxLq);
+            for (int32_t i = 0; i < n; ++i) {
+                if (t.lens[(size_t)i] > lim) {
+                    emb::errorf("%s: query %d has %d tokens, maximum is %d\n", who, i, t.lens[(size_t)i], lim);
+                    return -4;
+                }
+                if (t.lens[(size_t)i] < 1) return -1;
+            }
+        }
+        return emb::search_texts(*mv, ctx, t, n, k, scores, ids, n_cand);
+    } catch (const std::exception &ex) {
+        emb::errorf("%s: %s\n", who, ex.what());
+        return -1;
+    }
+}
+
 }  // extern "C"
 
 // The MaxSim micro-benchmarks (bert_hip.h): device 0, no context.  B == 0: the scorer over
-// n_cand candidates; B >= 1: the full-scan search of B queries for the k best.
+// n_cand candidates; B >= 1: the full-scan search of B queries for the k best.  C > 0 (with
+// B >= 1): C hash-chosen stored rows become the centroids and avg_us[3] gets the table
+// kernels, the scans with their selections, and the whole pruned search of n_cand candidates.
 static int32_t bench_store(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t B, int32_t k,
-                           int32_t storage, int32_t iters, float *avg_us)
+                           int32_t storage, int32_t iters, float *avg_us, int32_t C = 0)
 {
     using namespace emb;
     if (n_docs < 1 || doc_len < 0 || doc_len > 4096 || n_cand < 1 || iters < 1 || !avg_us || hip_device_count() == 0)
         return -1;
     if (B > 0 && !search_args_ok("bertx_bench_maxsim_search", B, Lq, k)) return -1;
+    if (C > 0 && (B < 1 || k > n_cand || n_cand > kMaxK || !centroid_count_ok("bertx_bench_maxsim_pruned", C))) return -1;
     const int32_t nq = std::max(B, 1);
     try {
         // ragged (doc_len 0): 16 .. 512 tokens by a hash of the id
@@ -989,6 +1466,49 @@ static int32_t bench_store(int32_t w, int32_t n_docs, int32_t doc_len, int32_t L
         if (Lq < 1 || Lq > kMaxLq || launch_unit_rows((float *)H.q.p, (int64_t)nq * Lq, w, 777u, H.s) != 0) return -1;
         HIP_RC(hipMemcpyAsync(H.id.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, H.s));
         HIP_RC(hipStreamSynchronize(H.s));
+        auto timed = [&](auto &&fn, float *us) -> int32_t {
+            for (int i = 0; i < 3; ++i)
+                if (fn() != 0) return -1;
+            HIP_RC(hipEventRecord(H.a, H.s));
+            for (int i = 0; i < iters; ++i)
+                if (fn() != 0) return -1;
+            HIP_RC(hipEventRecord(H.b, H.s));
+            HIP_RC(hipEventSynchronize(H.b));
+            float ms = 0.f;
+            HIP_RC(hipEventElapsedTime(&ms, H.a, H.b));
+            *us = ms * 1000.f / (float)iters;
+            return 0;
+        };
+        if (C > 0) {
+            std::vector<float> cent((size_t)C * w), rows;
+            for (int32_t c = 0; c < C; ++c) {
+                const int32_t id = (int32_t)(((uint64_t)c * 2654435761ull + 777ull) % (uint64_t)n_docs);
+                rows.resize((size_t)lens[(size_t)id] * w);
+                if (bertx_mvindex_doc(H.mv, id, rows.data()) != 0) return -1;
+                std::memcpy(cent.data() + (size_t)c * w, rows.data() + (size_t)(c % lens[(size_t)id]) * w, (size_t)w * 4);
+            }
+            if (bertx_mvindex_set_centroids(H.mv, cent.data(), C) != 0) return -1;
+            HIP_RC(H.mv->ord.wait());
+            bertx_mvindex &mv = *H.mv;
+            const int32_t per_pass = 4 / ((Lq + 15) / 16);
+            auto stage = [&](int st) -> int32_t {
+                for (int32_t b0 = 0; b0 < B; b0 += per_pass) {
+                    const int32_t rc = launch_maxsim_candidates(
+                        mv.codes, mv.table, (int)mv.n_docs, mv.used_slots / 16, mv.storage, mv.w, mv.cent, mv.cent_u, mv.C,
+                        (const float *)H.q.p + (size_t)b0 * Lq * w, std::min(per_pass, B - b0), Lq, n_cand, mv.tscratch,
+                        mv.search_scratch, (float *)H.out.p + (size_t)b0 * n_cand, (int32_t *)H.oid.p + (size_t)b0 * n_cand,
+                        st, nullptr, H.s);
+                    if (rc != 0) return rc;
+                }
+                return 0;
+            };
+            if (timed([&] { return stage(1); }, avg_us) != 0) return -1;
+            if (timed([&] { return stage(2); }, avg_us + 1) != 0) return -1;
+            return timed([&] {
+                return bertx_mvindex_search_pruned_device(H.mv, (const float *)H.q.p, B, Lq, k, n_cand, (float *)H.out.p,
+                                                          (int32_t *)H.oid.p, H.s);
+            }, avg_us + 2);
+        }
         auto run = [&] {
             if (B > 0)
                 return bertx_mvindex_search_device(H.mv, (const float *)H.q.p, B, Lq, k, (float *)H.out.p,
@@ -996,17 +1516,7 @@ static int32_t bench_store(int32_t w, int32_t n_docs, int32_t doc_len, int32_t L
             return bertx_mvindex_score_device(H.mv, (const float *)H.q.p, Lq, (const int32_t *)H.id.p, n_cand,
                                               (float *)H.out.p, H.s);
         };
-        for (int i = 0; i < 3; ++i)
-            if (run() != 0) return -1;
-        HIP_RC(hipEventRecord(H.a, H.s));
-        for (int i = 0; i < iters; ++i)
-            if (run() != 0) return -1;
-        HIP_RC(hipEventRecord(H.b, H.s));
-        HIP_RC(hipEventSynchronize(H.b));
-        float ms = 0.f;
-        HIP_RC(hipEventElapsedTime(&ms, H.a, H.b));
-        *avg_us = ms * 1000.f / (float)iters;
-        return 0;
+        return timed(run, avg_us);
     } catch (const std::exception &ex) {
         emb::errorf("bertx_bench_maxsim: %s\n", ex.what());
         return -1;
@@ -1026,6 +1536,13 @@ int32_t bertx_bench_maxsim_search(int32_t w, int32_t n_docs, int32_t doc_len, in
 {
     if (B < 1) return -1;
     return bench_store(w, n_docs, doc_len, Lq, 1, B, k, storage, iters, avg_us);
+}
+
+int32_t bertx_bench_maxsim_pruned(int32_t w, int32_t n_docs, int32_t doc_len, int32_t C, int32_t Lq, int32_t B, int32_t k,
+                                  int32_t n_cand, int32_t storage, int32_t iters, float *avg_us)
+{
+    if (B < 1 || C < 1) return -1;
+    return bench_store(w, n_docs, doc_len, Lq, n_cand, B, k, storage, iters, avg_us, C);
 }
 
 int32_t bertx_bench_maxsim(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t iters,

@@ -3,7 +3,8 @@
 // the GPU and the search fused there (bertx_index_*).
 //
 // usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8]
-//               [-r RERANK_MODEL [-c N] | -l [-c N | -a] | -L COLBERT_MODEL [-M] [-c N | -a]] [-S f16|int8]
+//               [-r RERANK_MODEL [-c N] | -l [-c N | -a [-C N [-c N]]] | -L COLBERT_MODEL [-M] [-c N | -a [-C N [-c N]]]]
+//               [-S f16|int8]
 // One text per line of CORPUS.txt; queries from stdin, one per line, `q` or EOF ends.
 // Per hit one line: rank<TAB>id<TAB>score<TAB>text.
 // -s: how the index stores its rows (bertx_index_create_ex): f16, the default, or int8
@@ -29,7 +30,11 @@
 // consulted; every query goes through bertx_mvindex_search_texts (-l) or
 // bertx_mvindex_search_texts_colbert (-L), which score every stored document by MaxSim
 // on the GPU and keep the k best there.  The printed score is the MaxSim score.  -a
-// without -l or -L, or together with -c or -r, is a usage error.
+// without -l or -L, or together with -r, or with -c but without -C, is a usage error.
+// -C N: with -a, the pruned search: after indexing, N centroids (a multiple of 16) are trained
+// on the stored token rows (bertx_mvindex_train_centroids, 8 iterations) and every query goes
+// through bertx_mvindex_search_pruned_texts: centroid interaction picks -c candidates (default
+// min(128, 4 k), k .. 128), the MaxSim scorer ranks those.  -C without -a is a usage error.
 // -S: with -l or -L, how the token store keeps its rows (bertx_mvindex_create_ex): f16,
 // the default, or int8 with one f32 per token, half the bytes and a less precise
 // similarity.  -s still speaks of the index alone.
@@ -48,7 +53,7 @@
 int main(int argc, char **argv)
 {
     const char *model = nullptr, *corpus = nullptr, *rerank = nullptr, *colbert = nullptr;
-    int k = 3, threads = 4, cand = 0, storage = BERTX_INDEX_F16, mv_storage = -1;
+    int k = 3, threads = 4, cand = 0, cents = 0, storage = BERTX_INDEX_F16, mv_storage = -1;
     bool late = false, all = false, no_mask_keys = false;
     for (int i = 1; i < argc; ++i) {
         const bool has = i + 1 < argc;
@@ -62,6 +67,7 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "-S") && has && !std::strcmp(argv[i + 1], "int8")) { mv_storage = BERTX_INDEX_I8; ++i; }
         else if (!std::strcmp(argv[i], "-r") && has) rerank = argv[++i];
         else if (!std::strcmp(argv[i], "-c") && has) cand = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "-C") && has) { cents = std::atoi(argv[++i]); if (cents < 1) cents = -1; }
         else if (!std::strcmp(argv[i], "-l")) late = true;
         else if (!std::strcmp(argv[i], "-a")) all = true;
         else if (!std::strcmp(argv[i], "-M")) no_mask_keys = true;
@@ -69,13 +75,15 @@ int main(int argc, char **argv)
         else { model = nullptr; break; }
     }
     const bool second = rerank || late || colbert;
-    const bool bad_all = all && ((!late && !colbert) || cand != 0);
-    if (second && !all && cand == 0) cand = std::min(128, 4 * k);
+    const bool bad_all = (all && ((!late && !colbert) || (cand != 0 && cents == 0))) || (cents != 0 && !all) || cents < 0 ||
+                         cents % 16 || cents > 65536;
+    if (second && (!all || cents) && cand == 0) cand = std::min(128, 4 * k);
     if (bad_all || !model || !corpus || k < 1 || k > 128 || threads < 1 || (int)(rerank != nullptr) + late + (colbert != nullptr) > 1 ||
-        (second && !all ? cand < k || cand > 128 : cand != 0) || (mv_storage >= 0 && !late && !colbert) ||
+        (second && (!all || cents) ? cand < k || cand > 128 : cand != 0) || (mv_storage >= 0 && !late && !colbert) ||
         (no_mask_keys && !colbert)) {
         std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads] [-s f16|int8] "
-                             "[-r RERANK_MODEL [-c N (k..128, default 4 k)] | -l [-c N | -a] | -L COLBERT_MODEL [-M] [-c N | -a]] "
+                             "[-r RERANK_MODEL [-c N (k..128, default 4 k)] | -l [-c N | -a [-C CENTROIDS [-c N]]] | "
+                             "-L COLBERT_MODEL [-M] [-c N | -a [-C CENTROIDS [-c N]]]] "
                              "[-S f16|int8 (the token store of -l / -L)]\n",
                      argv[0]);
         return 2;
@@ -175,6 +183,10 @@ int main(int argc, char **argv)
             rc = 1;
         }
     }
+    if (rc == 0 && cents && bertx_mvindex_train_centroids(mv, cents, 8, 0) != 0) {
+        std::fprintf(stderr, "search: training %d centroids failed\n", cents);
+        rc = 1;
+    }
     const int kq = second && !all ? cand : k;   // what the index (-a: the token store) is asked for
     std::vector<float> scores((size_t)kq);
     std::vector<int32_t> ids((size_t)kq);
@@ -185,9 +197,14 @@ int main(int argc, char **argv)
         const char *qp = q.c_str();
         if (all) {
             // the full scan: the k best of every stored document by MaxSim, selected on the GPU
-            if ((colbert ? bertx_mvindex_search_texts_colbert(mv, rctx, threads, 1, &qp, query_maxlen, k, scores.data(),
-                                                              ids.data())
-                         : bertx_mvindex_search_texts(mv, ctx, threads, 1, &qp, k, scores.data(), ids.data())) != 0) {
+            // (-C: the same over the candidates of the centroid interaction only)
+            const int32_t qrc =
+                cents ? bertx_mvindex_search_pruned_texts(mv, colbert ? rctx : ctx, threads, 1, &qp, k, cand,
+                                                          colbert ? query_maxlen : 0, scores.data(), ids.data())
+                : colbert ? bertx_mvindex_search_texts_colbert(mv, rctx, threads, 1, &qp, query_maxlen, k, scores.data(),
+                                                               ids.data())
+                          : bertx_mvindex_search_texts(mv, ctx, threads, 1, &qp, k, scores.data(), ids.data());
+            if (qrc != 0) {
                 std::fprintf(stderr, "search: late-interaction search failed\n");
                 rc = 1;
                 break;

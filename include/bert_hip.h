@@ -611,9 +611,85 @@ BERT_API int32_t bertx_index_search_texts(struct bertx_index *idx, struct bert_c
  * rows; average device time of `iters` calls of bertx_mvindex_search_device after 3
  * warm-up calls.
  *
- * Not provided: int8 queries against f16 rows; 4-bit or residual codes; candidate
- * generation (centroids, pruning); per-query lengths on the device; sharding over GPUs;
- * deleting, saving and loading.  (ColBERT checkpoints: "Projection" below.)
+ * Centroid codes.  A store can keep C centroids and one uint16 code per token slot: the
+ * index of the centroid nearest to the slot's stored row.  Without centroids every entry
+ * above does what it did; with them the add forms also code the rows they store, in the
+ * same stream order.
+ * bertx_mvindex_set_centroids(mv, cent float[C][width] on the host, C): C a multiple of 16
+ * in 16 .. 65,536 (-1 otherwise).  The rows are packed by the store's own row packer (the
+ * arithmetic above, f16 or int8), so a centroid holds exactly the bits that a one-token
+ * document added from the same f32 row would hold.  The call (re)assigns the code of every
+ * stored token; a second call replaces the centroids and assigns every code again; _clear
+ * keeps the centroids.  The buffers (the centroids, codes for capacity_token_slots, the
+ * table scratch of 256 C bytes, the candidate lists of 64 queries) are allocated by the
+ * first call and reallocated only when C grows; an allocation failure returns -3 with
+ * nothing changed.  The call synchronises with the store's stream.  A HIP graph captured
+ * before a set_centroids call must not be replayed after it: it holds the old buffers'
+ * addresses and the old C.
+ * The code of a stored row is a contract in terms of the entries above.  Let S_c be a
+ * store of the same kind and width whose documents are the centroids, one row each, added
+ * from the same f32 rows, and x what bertx_mvindex_doc returns for the row (the stored
+ * values widened; q * u on int8).  Then
+ *   code = the id that bertx_mvindex_search(S_c, x, B = 1, Lq = 1, k = 1) returns:
+ * the centroid of highest sim in the scorer's arithmetic, x going through the query packer
+ * (the normaliser runs again; on f16 it is not idempotent), equal similarities to the
+ * lower index.  A row stored as zeros gets code 0.  The slots of a document's last group
+ * past len hold code 0, so that a lookup is always in range; they never count towards a
+ * score.
+ * _centroids: the count, 0 if none.  _centroid(mv, c, out float[width]): the stored values
+ * of centroid c widened, as _doc.  _doc_codes(mv, id, codes uint16[len]): a document's codes
+ * (-1 without centroids or for a bad id, outputs untouched).
+ * bertx_mvindex_train_centroids(mv, C, iters, seed): spherical k-means, reproducible from
+ * the entries above.  Number the valid token rows 0 .. T - 1 in (document, token) order;
+ * the sample is every stride-th of them from row seed % stride on, stride =
+ * max(1, ceil(T / 2^18)), n_sample rows, their values _doc's.  The initial centroid c is
+ * sample row floor(c n_sample / C).  Each of the `iters` iterations calls _set_centroids
+ * (which codes the whole store on the GPU), reads the sample's codes, and replaces centroid
+ * c by the sum of its members, in f64, added one after the other in ascending sample order,
+ * divided by the count (f64) and rounded to f32; a centroid without a member keeps its f32
+ * row.  A final _set_centroids leaves the store coded.  The update runs on the host without
+ * atomics, so two runs give the same bits.  -1: C out of range or above n_sample, an empty
+ * store, iters < 0.
+ *
+ * Pruned search: centroid interaction first, the exact scorer on the survivors.
+ * bertx_mvindex_candidates / _candidates_device(mv, q float[B][Lq][width], B, Lq, n_cand,
+ * approx float[B][n_cand], ids int32[B][n_cand]), 1 <= Lq <= 64, 1 <= n_cand <= 128:
+ *   T[i][c]        = sim(q_i, centroid c) in the store's sim, the query packed as the
+ *                    scorers pack it;
+ *   approx(q, doc) = sum_{i < Lq} max_{j < len} T[i][code_j]: the max is exact, the sum in
+ *                    the scorer's order (lane c adds m[c], m[16 + c], ... from +0, then the
+ *                    four-step butterfly).
+ * So approx(q, doc) is, bit for bit, what bertx_mvindex_score returns for q on a store in
+ * which that document's rows were added from the caller's f32 centroid rows cent[code_j].
+ * Per query the n_cand best documents by (approx, then ascending id) come first to last,
+ * (-inf, -1) where the store has fewer.  A result does not depend on B, the other queries,
+ * n_cand, the document count or where the document sits.  A pass of 4, 2, 1 or 1 queries (1,
+ * 2, 3 or 4 tiles of 16 rows) runs a table kernel on the matrix cores, a scan that reads
+ * only the 2-byte codes, and a selection that merges the workgroups' sorted lists.  The
+ * scan copies the table into LDS when its 64 * tiles * C bytes (three tiles take the line of
+ * four) fit beside the lists in 160 KiB (C up to about 512 at four tiles, 2,048 at one) and
+ * reads it from global memory otherwise; both give the same bits;
+ * bertx_test_approx_ran reports which ran (bit 0: LDS, bit 1: global; a non-zero argument
+ * also resets it).
+ * bertx_mvindex_search_pruned / _search_pruned_device(mv, q, B, Lq, k, n_cand, scores
+ * float[B][k], ids int32[B][k]), 1 <= k <= n_cand <= 128: per query the n_cand candidates,
+ * their exact scores by the scorer kernel, then the k best by (score, ascending id), (-inf,
+ * -1) fill.  The scores are the scorer's bits; with n_cand >= docs the result is
+ * bertx_mvindex_search's, bit for bit.  The candidate scratch belongs to the store.  The
+ * device forms follow _search_device word for word (asynchronous, ordered after the store's
+ * previous operation, allocating nothing, never synchronising, capturable).
+ * bertx_mvindex_search_pruned_texts: _search_texts (colbert_query_maxlen 0) or
+ * _search_texts_colbert (the augmented queries of that many tokens) with the pruned search
+ * in place of the full scan; their refusals.
+ * Refusals, a message and the outputs untouched: -1 for arguments out of range, for a store
+ * without centroids and for a C that is not a multiple of 16; -4 for over-long texts.
+ * bertx_bench_maxsim_pruned: the store of bertx_bench_maxsim_ex with C hash-chosen stored
+ * rows as centroids; avg_us[0 .. 2] = the table kernels, the scans with their selections,
+ * and the whole pruned search of B queries, each the average of `iters` calls after 3.
+ *
+ * Not provided: int8 queries against f16 rows; 4-bit or residual codes; candidate lists
+ * longer than 128; per-query lengths on the device; sharding over GPUs; deleting, saving
+ * and loading.  (ColBERT checkpoints: "Projection" below.)
  */
 struct bertx_mvindex;
 BERT_API struct bertx_mvindex *bertx_mvindex_create(struct bert_ctx *ctx, int32_t slot, int32_t width,
@@ -655,6 +731,32 @@ BERT_API int32_t bertx_mvindex_search_texts(struct bertx_mvindex *mv, struct ber
                                             const char **texts, int32_t k, float *scores, int32_t *ids);
 BERT_API int32_t bertx_bench_maxsim_search(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t B, int32_t k,
                                            int32_t storage, int32_t iters, float *avg_us);
+BERT_API int32_t bertx_mvindex_set_centroids(struct bertx_mvindex *mv, const float *cent, int32_t C);
+BERT_API int32_t bertx_mvindex_train_centroids(struct bertx_mvindex *mv, int32_t C, int32_t iters, uint32_t seed);
+BERT_API int32_t bertx_mvindex_centroids(struct bertx_mvindex *mv);
+BERT_API int32_t bertx_mvindex_centroid(struct bertx_mvindex *mv, int32_t c, float *out);
+BERT_API int32_t bertx_mvindex_doc_codes(struct bertx_mvindex *mv, int32_t id, uint16_t *codes);
+BERT_API int32_t bertx_mvindex_candidates(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t n_cand,
+                                          float *approx, int32_t *ids);
+BERT_API int32_t bertx_mvindex_candidates_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq,
+                                                 int32_t n_cand, float *d_approx, int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_mvindex_search_pruned(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t k,
+                                             int32_t n_cand, float *scores, int32_t *ids);
+BERT_API int32_t bertx_mvindex_search_pruned_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq,
+                                                    int32_t k, int32_t n_cand, float *d_scores, int32_t *d_ids,
+                                                    void *stream);
+BERT_API int32_t bertx_mvindex_search_pruned_texts(struct bertx_mvindex *mv, struct bert_ctx *ctx, int32_t n_threads,
+                                                   int32_t n, const char **texts, int32_t k, int32_t n_cand,
+                                                   int32_t colbert_query_maxlen, float *scores, int32_t *ids);
+BERT_API int32_t bertx_bench_maxsim_pruned(int32_t w, int32_t n_docs, int32_t doc_len, int32_t C, int32_t Lq, int32_t B,
+                                           int32_t k, int32_t n_cand, int32_t storage, int32_t iters, float *avg_us);
+/* Test hooks: which table placement the candidate scans took; the host half of training
+ * (kmeans_update.h): one update in place, returning the centroids without a member; the
+ * sample rule, out3 = {stride, start, n_sample}. */
+BERT_API int32_t bertx_test_approx_ran(int32_t reset);
+BERT_API int32_t bertx_test_kmeans_update(const float *sample, const uint16_t *codes, int32_t n, int32_t w, int32_t C,
+                                          float *cent);
+BERT_API int32_t bertx_test_kmeans_sample(int64_t T, uint32_t seed, int64_t *out3);
 
 /*
  * Cross-encoder reranking: token types and a classification head.
