@@ -295,6 +295,17 @@ def load_lib(path=None):
         L.bertx_test_kmeans_sample.argtypes = [c_i64, c_u32, vp]
     except AttributeError:
         pass
+    try:   # (residual-coded token stores; absent from older BERT_LIB builds)
+        L.bertx_mvindex_set_residual_buckets.restype = c_i32
+        L.bertx_mvindex_set_residual_buckets.argtypes = [vp, vp, vp]
+        L.bertx_mvindex_train_residual_buckets.restype = c_i32
+        L.bertx_mvindex_train_residual_buckets.argtypes = [vp, c_i32, vp, vp]
+        L.bertx_mvindex_doc_residual.restype = c_i32
+        L.bertx_mvindex_doc_residual.argtypes = [vp, c_i32, vp, vp, vp]
+        L.bertx_bench_maxsim_res.restype = c_i32
+        L.bertx_bench_maxsim_res.argtypes = [c_i32] * 8 + [c_f32p]
+    except AttributeError:
+        pass
     try:   # (ColBERT checkpoints: the projection record and its entries; absent from older BERT_LIB builds)
         L.bertx_convert_hf_colbert.restype = c_i32
         L.bertx_convert_hf_colbert.argtypes = [ctypes.c_char_p, ctypes.c_char_p, c_i32]
@@ -757,14 +768,20 @@ class BertTokenIndex:
     a less precise similarity), on GPU `slot` of the model's context; ids are the
     insertion order.  A query of up to 64 token vectors scores a document as
     sum_i max_j <q_i, c_j>; bert_hip.h gives the arithmetic of both kinds.  width None:
-    the model's n_embd (what the text forms need)."""
+    the model's n_embd (what the text forms need).
+    storage="res2" / "res4" (bert_hip.h "Residual codes"): no rows, per token the code of
+    its nearest centroid, 2 or 4 bits per element for the residual and one f32; such a store
+    needs set_centroids and set_residual_buckets before its first document, has no full scan
+    (search_pruned only) and cannot train centroids: train those, and the buckets
+    (train_residual_buckets), on an f16 store of a sample."""
 
     MAX_QUERY_TOKENS = 64
-    STORAGE = BertIndex.STORAGE
+    STORAGE = dict(BertIndex.STORAGE, res2=4, res4=5)
+    RESIDUAL_BITS = {"res2": 2, "res4": 4}
 
     def __init__(self, model, capacity_docs, capacity_token_slots, slot=0, width=None, storage="f16"):
         if storage not in self.STORAGE:
-            raise ValueError("storage must be 'f16' or 'int8', got %r" % (storage,))
+            raise ValueError("storage must be 'f16', 'int8', 'res2' or 'res4', got %r" % (storage,))
         self.model = model
         self.lib = model.lib
         self.storage = storage
@@ -939,6 +956,43 @@ class BertTokenIndex:
         rc = self.lib.bertx_mvindex_train_centroids(self.mv, C, iters, seed)
         if rc != 0:
             raise RuntimeError("bertx_mvindex_train_centroids failed (%d)" % rc)
+
+    def set_residual_buckets(self, cutoffs, weights):
+        """The codec of a residual store: cutoffs f32 [2^NB - 1] (finite, non-decreasing) and
+        weights f32 [2^NB] (kept as f16).  Before the first document only."""
+        nb = self.RESIDUAL_BITS.get(self.storage, 0)
+        cutoffs = np.ascontiguousarray(np.asarray(cutoffs, np.float32).reshape(-1))
+        weights = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+        if nb and (len(cutoffs) != (1 << nb) - 1 or len(weights) != 1 << nb):
+            raise ValueError("expected %d cutoffs and %d weights" % ((1 << nb) - 1, 1 << nb))
+        rc = self.lib.bertx_mvindex_set_residual_buckets(self.mv, cutoffs.ctypes.data, weights.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_mvindex_set_residual_buckets failed (%d)" % rc)
+
+    def train_residual_buckets(self, nbits):
+        """(cutoffs f32 [2^nbits - 1], weights f32 [2^nbits]) by ColBERTv2's quantile rule over
+        the residuals of this f16 store's rows against its centroids (bert_hip.h)."""
+        cutoffs = np.zeros(max((1 << nbits) - 1, 1), np.float32)
+        weights = np.zeros(max(1 << nbits, 1), np.float32)
+        rc = self.lib.bertx_mvindex_train_residual_buckets(self.mv, nbits, cutoffs.ctypes.data, weights.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_mvindex_train_residual_buckets failed (%d)" % rc)
+        return cutoffs, weights
+
+    def doc_residual(self, i):
+        """(codes uint16 [len], bits uint8 [len][width NB / 8], u f32 [len]): the stored state
+        of document i of a residual store; element j of a row sits in byte j NB / 8 at bit
+        NB (j mod 8 / NB)."""
+        n = self.doc_len(i)
+        if n < 1:
+            raise IndexError("no document %d" % i)
+        nb = self.RESIDUAL_BITS.get(self.storage, 2)
+        codes = np.zeros(n, np.uint16)
+        bits = np.zeros((n, self.dim * nb // 8), np.uint8)
+        u = np.zeros(n, np.float32)
+        if self.lib.bertx_mvindex_doc_residual(self.mv, i, codes.ctypes.data, bits.ctypes.data, u.ctypes.data) != 0:
+            raise RuntimeError("bertx_mvindex_doc_residual failed")
+        return codes, bits, u
 
     @property
     def n_centroids(self):

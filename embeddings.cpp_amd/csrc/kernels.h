@@ -316,6 +316,23 @@ int launch_maxsim_candidates(const uint16_t *codes, const void *d_table, int n_d
 int launch_maxsim_rerank_select(const float *exact, const int32_t *ids, int nq, int n_cand, int k, float *out_s,
                                 int32_t *out_i, hipStream_t s);
 
+// ---- residual-coded token storage (maxsim_res.hip; bert_hip.h "Residual codes") ----
+// A slot keeps its code, nbits = 2 or 4 bits per element (the layout: maxsim_res.hip) and
+// one f32 u.  An add packs its rows into a staging image in the f16 store layout whose
+// table is the call's entries counted from the call's first group (launch_res_rel_table:
+// d_rel[i] = (d_table_new[i].first - g0, len)), codes it with launch_mv_assign, and encodes:
+// bits and u of `groups` groups from the staging image, their codes, the f16 centroid image,
+// cuts f32 [2^nbits - 1] and wts f16 [2^nbits] on the device.  bits, u and codes point at the
+// call's first group.  launch_maxsim_res is launch_maxsim over such a store: pair uint32
+// [2^(2 nbits)] on the device, pair[b0 | b1 << nbits] = wts[b0] | wts[b1] << 16.
+int maxsim_res_prepare_device();
+int launch_res_rel_table(const void *d_table_new, int n_new, int64_t g0, void *d_rel, hipStream_t s);
+int launch_res_encode(const void *staging, int64_t groups, int w, int nbits, const uint16_t *codes, const void *cent,
+                      const float *cuts, const uint16_t *wts, uint32_t *bits, float *u, hipStream_t s);
+int launch_maxsim_res(const uint32_t *bits, const float *u, const uint16_t *codes, const void *cent, const uint32_t *pair,
+                      int nbits, const void *d_table, int n_docs, int w, const float *d_q, int Lq, const int32_t *d_ids, int n,
+                      float *d_out, hipStream_t s);
+
 // ---- the classification head (head.hip): pooler dense + tanh + classifier on the
 // sentences' [CLS] rows, all f32, one form for the three chains ----
 constexpr int HEAD_MAX_LABELS = 16;

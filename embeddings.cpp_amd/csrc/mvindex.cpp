@@ -2,6 +2,8 @@
 // of documents, each a run of unit-length token rows in the search kernel's fragment
 // order, f16 (kernels.h, maxsim.hip) or int8 with one f32 per token slot (maxsim_i8.hip),
 // the fused MaxSim scorer over it, and the text forms on top of the per-token forward.
+// A residual store (maxsim_res.hip) keeps no rows: per slot the centroid code, 2 or 4 bits
+// per element and one f32; its adds go through a staging image in the f16 store layout.
 // After creation a store knows only its device ordinal, its width and its storage kind.
 // The ordering rules and the unpackers are shared with the embedding index
 // (store_common.h).  A text form is an entry point's argument checks, one of two
@@ -54,6 +56,18 @@ struct bertx_mvindex {
     float *cand_approx = nullptr, *cand_exact = nullptr;
     int32_t *cand_ids = nullptr;
     int32_t *cent_entry = nullptr;         // device: (0, C) the centroids' table entry, then their source offset 0
+    // residual kinds (store stays null): the slots' bits and u; the codec on the device (cutoffs
+    // f32, weights f16, the scorer's pair table), the weights on the host; the staging image of an add
+    // (f16 store layout) with its table, both grown by the add that needs more
+    uint32_t *res_bits = nullptr;
+    float *res_u = nullptr, *res_cuts = nullptr;
+    uint16_t *res_wts = nullptr;
+    uint32_t *res_pair = nullptr;
+    bool has_buckets = false;
+    uint16_t h_wts[16] = {};
+    void *stage_img = nullptr;
+    int32_t *stage_tab = nullptr;
+    int64_t stage_slots = 0, stage_docs = 0;
     hipStream_t stream = nullptr;
     emb::StoreOrder ord;
     std::mutex mu;
@@ -66,7 +80,9 @@ struct bertx_mvindex {
         if (ord.done) (void)ord.wait();
         for (void *p : {store, (void *)scales, (void *)table, (void *)src_off, (void *)st_rows, (void *)st_q, (void *)st_out,
                         (void *)st_ids, (void *)st_tok, search_scratch, cent, (void *)cent_u, (void *)codes,
-                        (void *)tscratch, (void *)cand_approx, (void *)cand_exact, (void *)cand_ids, (void *)cent_entry})
+                        (void *)tscratch, (void *)cand_approx, (void *)cand_exact, (void *)cand_ids, (void *)cent_entry,
+                        (void *)res_bits, (void *)res_u, (void *)res_cuts, (void *)res_wts, (void *)res_pair, stage_img,
+                        (void *)stage_tab})
             if (p) (void)hipFree(p);
         if (h_table) (void)hipHostFree(h_table);
         if (h_src) (void)hipHostFree(h_src);
@@ -87,6 +103,32 @@ constexpr int kCandQueries = 64;    // queries whose candidate lists the store's
 
 std::atomic<int> g_approx_forms{0};   // bertx_test_approx_ran: 1 the table went to LDS, 2 global memory
 
+// Bits per element of a residual store, 0 for the kinds that keep rows.
+int res_nbits(const bertx_mvindex &mv)
+{
+    return mv.storage == BERTX_INDEX_RES2 ? 2 : mv.storage == BERTX_INDEX_RES4 ? 4 : 0;
+}
+
+// The kind whose table and assign kernels serve the store's centroids: a residual store's
+// centroids are an f16 store's.
+int cent_kind(const bertx_mvindex &mv) { return res_nbits(mv) ? (int)BERTX_INDEX_F16 : mv.storage; }
+
+// A residual store encodes against its centroids and buckets: an add without either is refused.
+bool add_refused(const bertx_mvindex &mv, const char *who)
+{
+    if (!res_nbits(mv) || (mv.C > 0 && mv.has_buckets)) return false;
+    errorf("%s: a residual store needs centroids (bertx_mvindex_set_centroids) and buckets "
+           "(bertx_mvindex_set_residual_buckets) before documents\n", who);
+    return true;
+}
+
+bool full_scan_refused(const bertx_mvindex &mv, const char *who)
+{
+    if (!res_nbits(mv)) return false;
+    errorf("%s: the full scan of a residual store is not provided (bertx_mvindex_search_pruned)\n", who);
+    return true;
+}
+
 // The codes of the documents first_doc .. first_doc + n - 1, which take the groups from g0 on
 // (a store without centroids keeps none).
 int32_t assign_codes(bertx_mvindex &mv, int64_t g0, int64_t g1, int32_t d0, int32_t d1, hipStream_t s)
@@ -99,6 +141,17 @@ int32_t assign_codes(bertx_mvindex &mv, int64_t g0, int64_t g1, int32_t d0, int3
 // After the rows of an add are packed, on the same stream: the new documents' codes.
 int32_t assign_new(bertx_mvindex &mv, int32_t n, int64_t slots, hipStream_t s)
 {
+    if (const int nb = res_nbits(mv)) {
+        // the staging image is an f16 store of the call's documents alone, whose codes, bits and
+        // u are the real arrays from the call's first group on
+        const size_t g0 = (size_t)(mv.used_slots / 16), per_group = (size_t)mv.w * nb / 2;   // dwords of bits per group
+        uint16_t *codes = mv.codes + g0 * 16;
+        const int32_t rc = launch_mv_assign(mv.stage_img, nullptr, BERTX_INDEX_F16, mv.stage_tab, 0, slots / 16, 0, n, mv.w,
+                                            mv.cent, nullptr, mv.C, codes, s);
+        if (rc != 0) return rc;
+        return launch_res_encode(mv.stage_img, slots / 16, mv.w, nb, codes, mv.cent, mv.res_cuts, mv.res_wts,
+                                 mv.res_bits + g0 * per_group, mv.res_u + g0 * 16, s);
+    }
     return assign_codes(mv, mv.used_slots / 16, (mv.used_slots + slots) / 16, (int32_t)mv.n_docs, (int32_t)mv.n_docs + n, s);
 }
 
@@ -147,8 +200,38 @@ int32_t upload_entries(bertx_mvindex &mv, int32_t n, hipStream_t s)
     return 0;
 }
 
+// Before the first pack of an add, inside its stream order: the new documents' entries go to
+// the device; a residual store also grows its staging image to the call's size (waiting for
+// whatever still reads the old one) and writes the staging table.
+int32_t begin_add(bertx_mvindex &mv, int32_t n, int64_t slots, hipStream_t s)
+{
+    if (const int32_t rc = upload_entries(mv, n, s)) return rc;
+    if (!res_nbits(mv)) return 0;
+    if (slots > mv.stage_slots || n > mv.stage_docs) {
+        const int64_t ns = std::max(slots, mv.stage_slots), nd = std::max<int64_t>(n, mv.stage_docs);
+        HIP_RC(mv.ord.wait());
+        if (mv.stage_img) (void)hipFree(mv.stage_img);
+        if (mv.stage_tab) (void)hipFree(mv.stage_tab);
+        mv.stage_img = nullptr;
+        mv.stage_tab = nullptr;
+        mv.stage_slots = mv.stage_docs = 0;
+        if (hipMalloc(&mv.stage_img, (size_t)ns * mv.w * 2) != hipSuccess ||
+            hipMalloc((void **)&mv.stage_tab, (size_t)nd * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            errorf("bertx_mvindex_add: device %d could not allocate the staging image of %lld token slots\n", mv.ordinal,
+                   (long long)ns);
+            return -3;
+        }
+        mv.stage_slots = ns;
+        mv.stage_docs = nd;
+    }
+    return launch_res_rel_table(mv.table + 2 * mv.n_docs, n, mv.used_slots / 16, mv.stage_tab, s);
+}
+
 int32_t pack(bertx_mvindex &mv, const float *d_rows, int64_t t0, int64_t count, int32_t n, hipStream_t s)
 {
+    if (res_nbits(mv))
+        return launch_mv_pack(d_rows, t0, count, mv.w, mv.src_off + mv.n_docs, mv.stage_tab, n, mv.stage_img, s);
     if (mv.storage == BERTX_INDEX_I8)
         return launch_mv_pack_i8(d_rows, t0, count, mv.w, mv.src_off + mv.n_docs, mv.table + 2 * mv.n_docs, n, mv.store,
                                  mv.scales, s);
@@ -165,13 +248,13 @@ int32_t commit(bertx_mvindex &mv, int32_t n, int64_t slots)
 
 int32_t add_device_locked(bertx_mvindex &mv, const float *d_rows, const int32_t *lens, int32_t n, hipStream_t s)
 {
-    if (!d_rows) return -1;
+    if (!d_rows || add_refused(mv, "bertx_mvindex_add_device")) return -1;
     int64_t T = 0, slots = 0;
     int32_t rc = plan_add(mv, lens, n, &T, &slots);
     if (rc != 0) return rc;
     {
         Ordered o(mv.ord, s);
-        rc = upload_entries(mv, n, s);
+        rc = begin_add(mv, n, slots, s);
         if (rc == 0) rc = pack(mv, d_rows, 0, T, n, s);
         if (rc == 0) rc = assign_new(mv, n, slots, s);
     }
@@ -182,14 +265,25 @@ int32_t add_device_locked(bertx_mvindex &mv, const float *d_rows, const int32_t 
     return commit(mv, n, slots);
 }
 
+// The scorer of the store's kind; the caller orders the stream.  (On a residual store without
+// documents every id is out of range, and neither codes nor centroids are read.)
+int32_t score_launch(bertx_mvindex &mv, const float *d_q, int32_t Lq, const int32_t *d_ids, int32_t n, float *d_out,
+                     hipStream_t s)
+{
+    if (mv.storage == BERTX_INDEX_I8)
+        return launch_maxsim_i8(mv.store, mv.scales, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s);
+    if (const int nb = res_nbits(mv))
+        return launch_maxsim_res(mv.res_bits, mv.res_u, mv.codes, mv.cent, mv.res_pair, nb, mv.table, (int)mv.n_docs, mv.w,
+                                 d_q, Lq, d_ids, n, d_out, s);
+    return launch_maxsim(mv.store, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s);
+}
+
 int32_t score_device_locked(bertx_mvindex &mv, const float *d_q, int32_t Lq, const int32_t *d_ids, int32_t n,
                             float *d_out, hipStream_t s)
 {
     if (!d_q || !d_out || Lq < 1 || Lq > kMaxLq || n < 1) return -1;
     Ordered o(mv.ord, s);
-    if (mv.storage == BERTX_INDEX_I8)
-        return launch_maxsim_i8(mv.store, mv.scales, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s);
-    return launch_maxsim(mv.store, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s);
+    return score_launch(mv, d_q, Lq, d_ids, n, d_out, s);
 }
 
 bool search_args_ok(const char *who, int32_t B, int32_t Lq, int32_t k)
@@ -203,6 +297,7 @@ int32_t search_device_locked(bertx_mvindex &mv, const float *d_q, int32_t B, int
                              int32_t *d_ids, hipStream_t s)
 {
     if (!d_q || !d_scores || !d_ids || !search_args_ok("bertx_mvindex_search", B, Lq, k)) return -1;
+    if (full_scan_refused(mv, "bertx_mvindex_search")) return -1;
     Ordered o(mv.ord, s);
     return launch_maxsim_search(mv.store, mv.scales, mv.storage, mv.table, (int)mv.n_docs, mv.used_slots / 16, mv.w, d_q, B,
                                 Lq, k, mv.search_scratch, d_scores, d_ids, s);
@@ -249,9 +344,74 @@ int32_t read_doc_i8(bertx_mvindex &mv, int32_t id, int8_t *q, float *u)
     return 0;
 }
 
+// The stored state of document id of a residual store in the canonical order of
+// bertx_mvindex_doc_residual: codes [len], bits [len][w NB / 8], u [len] (the caller holds
+// the lock, has checked the id and has selected the device).
+int32_t read_doc_res(bertx_mvindex &mv, int32_t id, uint16_t *codes, uint8_t *bits, float *u)
+{
+    const int nb = res_nbits(mv), w = mv.w, UG = w / 64, DW = nb / 2;
+    const int64_t first = mv.h_table[2 * (size_t)id], len = mv.h_table[2 * (size_t)id + 1];
+    const size_t groups = (size_t)((len + 15) / 16), group_dw = (size_t)UG * 64 * DW, row_bytes = (size_t)w * nb / 8;
+    std::vector<uint32_t> raw(groups * group_dw);
+    HIP_RC(mv.ord.wait());
+    HIP_RC(hipMemcpy(raw.data(), mv.res_bits + (size_t)first * group_dw, raw.size() * 4, hipMemcpyDeviceToHost));
+    HIP_RC(hipMemcpy(codes, mv.codes + (size_t)first * 16, (size_t)len * 2, hipMemcpyDeviceToHost));
+    HIP_RC(hipMemcpy(u, mv.res_u + (size_t)first * 16, (size_t)len * 4, hipMemcpyDeviceToHost));
+    // lane 16g + f of unit un holds row f's elements 8g .. 8g + 7 of blocks 2 un, 2 un + 1:
+    // 2 (NB 2) or 4 (NB 4) canonical bytes per block, little-endian
+    for (int64_t r = 0; r < len; ++r) {
+        uint8_t *o = bits + (size_t)r * row_bytes;
+        for (int kb = 0; kb < w / 32; ++kb)
+            for (int g = 0; g < 4; ++g) {
+                const uint32_t *at = raw.data() + (size_t)(r / 16) * group_dw + ((size_t)(kb / 2) * 64 + 16 * g + (r & 15)) * DW;
+                const uint32_t v = nb == 2 ? (at[0] >> (16 * (kb & 1))) & 0xffffu : at[kb & 1];
+                for (int b = 0; b < nb; ++b) o[((size_t)4 * kb + g) * nb + b] = (uint8_t)(v >> (8 * b));
+            }
+    }
+    return 0;
+}
+
+// The f32 values of every centroid of a store whose centroids are f16 rows.
+int32_t read_centroids_f16(bertx_mvindex &mv, std::vector<float> &out)
+{
+    std::vector<uint16_t> raw((size_t)mv.C * mv.w);
+    out.resize(raw.size());
+    HIP_RC(mv.ord.wait());
+    HIP_RC(hipMemcpy(raw.data(), mv.cent, raw.size() * 2, hipMemcpyDeviceToHost));
+    unpack_f16_rows(raw.data(), 0, 0, mv.C, mv.w, out.data());
+    return 0;
+}
+
 // bertx_mvindex_doc under the caller's lock, the id checked and the device selected.
 int32_t doc_locked(bertx_mvindex *mv, int32_t id, float *out)
 {
+    if (const int nb = emb::res_nbits(*mv)) {
+        try {
+            const int w = mv->w;
+            const int64_t len = mv->h_table[2 * (size_t)id + 1];
+            std::vector<uint16_t> codes((size_t)len);
+            std::vector<uint8_t> bits((size_t)len * w * nb / 8);
+            std::vector<float> u((size_t)len), c((size_t)w);
+            if (const int32_t rc = read_doc_res(*mv, id, codes.data(), bits.data(), u.data())) return rc;
+            std::vector<uint16_t> raw((size_t)16 * w);
+            for (int64_t r = 0; r < len; ++r) {
+                const size_t cg = codes[(size_t)r] / 16;
+                HIP_RC(hipMemcpy(raw.data(), (const uint16_t *)mv->cent + cg * raw.size(), raw.size() * 2, hipMemcpyDeviceToHost));
+                unpack_f16_rows(raw.data(), (int64_t)cg * 16, codes[(size_t)r], 1, w, c.data());
+                const uint8_t *b = bits.data() + (size_t)r * w * nb / 8;
+                for (int i = 0; i < w; ++i) {
+                    const int k = (b[(size_t)i * nb / 8] >> (nb * (i % (8 / nb)))) & ((1 << nb) - 1);
+                    // e = c + wt in f16: the f32 sum of two f16 values rounded once more gives the same bits
+                    const float e = f16_to_f32(f32_to_f16(c[(size_t)i] + f16_to_f32(mv->h_wts[k])));
+                    out[(size_t)r * w + i] = e * u[(size_t)r];
+                }
+            }
+        } catch (const std::bad_alloc &) {
+            emb::errorf("bertx_mvindex_doc: out of host memory\n");
+            return -1;
+        }
+        return 0;
+    }
     if (mv->storage == BERTX_INDEX_I8) {
         try {
             const int w = mv->w;
@@ -324,7 +484,7 @@ int32_t candidates_launch(bertx_mvindex &mv, const float *d_q, int32_t B, int32_
     const int32_t per_pass = 4 / ((Lq + 15) / 16);
     for (int32_t b0 = 0; b0 < B; b0 += per_pass) {
         int form = 0;
-        const int32_t rc = launch_maxsim_candidates(mv.codes, mv.table, (int)mv.n_docs, mv.used_slots / 16, mv.storage, mv.w,
+        const int32_t rc = launch_maxsim_candidates(mv.codes, mv.table, (int)mv.n_docs, mv.used_slots / 16, cent_kind(mv), mv.w,
                                                     mv.cent, mv.cent_u, mv.C, d_q + (size_t)b0 * Lq * mv.w,
                                                     std::min(per_pass, B - b0), Lq, n_cand, mv.tscratch, mv.search_scratch,
                                                     d_approx + (size_t)b0 * n_cand, d_ids + (size_t)b0 * n_cand, 3, &form, s);
@@ -357,9 +517,7 @@ int32_t search_pruned_device_locked(bertx_mvindex &mv, const float *d_q, int32_t
             const float *qb = Q + (size_t)b * Lq * mv.w;
             const int32_t *ib = mv.cand_ids + (size_t)b * n_cand;
             float *ob = mv.cand_exact + (size_t)b * n_cand;
-            rc = mv.storage == BERTX_INDEX_I8
-                     ? launch_maxsim_i8(mv.store, mv.scales, mv.table, (int)mv.n_docs, mv.w, qb, Lq, ib, n_cand, ob, s)
-                     : launch_maxsim(mv.store, mv.table, (int)mv.n_docs, mv.w, qb, Lq, ib, n_cand, ob, s);
+            rc = score_launch(mv, qb, Lq, ib, n_cand, ob, s);
         }
         if (rc == 0)
             rc = launch_maxsim_rerank_select(mv.cand_exact, mv.cand_ids, m, n_cand, k, d_scores + (size_t)c0 * k,
@@ -534,6 +692,7 @@ int32_t forward_chunk(bertx_mvindex &mv, struct bert_ctx *ctx, const TextRows &t
 int32_t add_texts(bertx_mvindex &mv, struct bert_ctx *ctx, const TextRows &t, int32_t n, const char *who)
 {
     std::lock_guard<std::mutex> lk(mv.mu);
+    if (add_refused(mv, who)) return -1;
     int64_t T = 0, slots = 0;
     int32_t rc = plan_add(mv, t.kept.data(), n, &T, &slots);   // (a ColBERT document keeps [CLS], [D] and [SEP]: >= 3)
     if (rc != 0) return rc;
@@ -542,7 +701,7 @@ int32_t add_texts(bertx_mvindex &mv, struct bert_ctx *ctx, const TextRows &t, in
     ChunkBufs b;
     {
         Ordered o(mv.ord, mv.stream);
-        rc = upload_entries(mv, n, mv.stream);
+        rc = begin_add(mv, n, slots, mv.stream);
         int64_t t0 = 0;
         for (size_t i = 0; i < (size_t)n && rc == 0;) {
             const size_t e = chunk_end([&](size_t j) { return t.lens[j]; }, i, (size_t)n);
@@ -649,8 +808,9 @@ int32_t search_texts(bertx_mvindex &mv, struct bert_ctx *ctx, const TextRows &t,
 
 bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t cap_slots, int storage)
 {
-    if (storage != BERTX_INDEX_F16 && storage != BERTX_INDEX_I8) {
-        errorf("bertx_mvindex_create: storage %d is neither BERTX_INDEX_F16 nor BERTX_INDEX_I8\n", storage);
+    if (storage != BERTX_INDEX_F16 && storage != BERTX_INDEX_I8 && storage != BERTX_INDEX_RES2 &&
+        storage != BERTX_INDEX_RES4) {
+        errorf("bertx_mvindex_create: storage %d is none of BERTX_INDEX_F16, _I8, _RES2, _RES4\n", storage);
         return nullptr;
     }
     if (w % 64 || w < 64 || w > 1024) {
@@ -676,13 +836,21 @@ bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t c
     mv->cap_slots = cap_slots;
     const size_t slots16 = (size_t)((cap_slots + 15) / 16) * 16;
     const bool i8 = storage == BERTX_INDEX_I8;
-    const size_t store_bytes = slots16 * (size_t)w * (i8 ? 1 : 2);
+    const int nb = res_nbits(*mv);
+    // a residual store keeps no rows: w nb / 8 bytes of bits and one f32 per slot, and the codec
+    const size_t store_bytes = nb ? slots16 * (size_t)w * nb / 8 + slots16 * 4 : slots16 * (size_t)w * (i8 ? 1 : 2);
     const bool ok = maxsim_prepare_device() == 0 && maxsim_search_prepare_device() == 0 &&
                     maxsim_codes_prepare_device() == 0 && maxsim_approx_prepare_device() == 0 &&
                     hipMalloc(&mv->search_scratch, maxsim_search_scratch_bytes()) == hipSuccess &&
                     hipStreamCreateWithFlags(&mv->stream, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&mv->ord.done, hipEventDisableTiming) == hipSuccess &&
-                    hipMalloc(&mv->store, store_bytes) == hipSuccess &&
+                    (nb ? maxsim_res_prepare_device() == 0 &&
+                              hipMalloc((void **)&mv->res_bits, slots16 * (size_t)w * nb / 8) == hipSuccess &&
+                              hipMalloc((void **)&mv->res_u, slots16 * 4) == hipSuccess &&
+                              hipMalloc((void **)&mv->res_cuts, 64) == hipSuccess &&
+                              hipMalloc((void **)&mv->res_wts, 32) == hipSuccess &&
+                              hipMalloc((void **)&mv->res_pair, 1024) == hipSuccess
+                        : hipMalloc(&mv->store, store_bytes) == hipSuccess) &&
                     (!i8 || hipMalloc((void **)&mv->scales, slots16 * 4) == hipSuccess) &&
                     hipMalloc((void **)&mv->table, (size_t)cap_docs * 8) == hipSuccess &&
                     hipMalloc((void **)&mv->src_off, (size_t)cap_docs * 4) == hipSuccess &&
@@ -896,6 +1064,7 @@ int32_t bertx_mvindex_add(struct bertx_mvindex *mv, const float *rows, const int
 {
     if (!mv || !rows) return -1;
     std::lock_guard<std::mutex> lk(mv->mu);
+    if (emb::add_refused(*mv, "bertx_mvindex_add")) return -1;
     int64_t T = 0, slots = 0;
     int32_t rc = emb::plan_add(*mv, lens, n, &T, &slots);
     if (rc != 0) return rc;
@@ -903,7 +1072,7 @@ int32_t bertx_mvindex_add(struct bertx_mvindex *mv, const float *rows, const int
     HIP_RC(g.status());
     {
         emb::Ordered o(mv->ord, mv->stream);
-        rc = emb::upload_entries(*mv, n, mv->stream);
+        rc = emb::begin_add(*mv, n, slots, mv->stream);
         for (int64_t t = 0; t < T && rc == 0; t += emb::kStageRows) {
             const int64_t m = std::min<int64_t>(emb::kStageRows, T - t);
             if (hipMemcpyAsync(mv->st_rows, rows + (size_t)t * mv->w, (size_t)m * mv->w * 4, hipMemcpyHostToDevice,
@@ -1086,6 +1255,7 @@ int32_t bertx_mvindex_search(struct bertx_mvindex *mv, const float *q, int32_t B
                              int32_t *ids)
 {
     if (!mv || !q || !scores || !ids || !emb::search_args_ok("bertx_mvindex_search", B, Lq, k)) return -1;
+    if (emb::full_scan_refused(*mv, "bertx_mvindex_search")) return -1;
     std::lock_guard<std::mutex> lk(mv->mu);
     DeviceGuard g(mv->ordinal);
     HIP_RC(g.status());
@@ -1113,6 +1283,7 @@ int32_t bertx_mvindex_search_texts(struct bertx_mvindex *mv, struct bert_ctx *ct
     int32_t slot = -1;
     if (!texts || !scores || !ids || n < 1) return -1;
     if (emb::text_ctx_ok(mv, ctx, "bertx_mvindex_search_texts", &slot) != 0) return -1;
+    if (emb::full_scan_refused(*mv, "bertx_mvindex_search_texts")) return -1;
     if (!emb::search_args_ok("bertx_mvindex_search_texts", n, 1, k)) return -1;
     try {
         emb::TextRows t;
@@ -1139,6 +1310,7 @@ int32_t bertx_mvindex_search_texts_colbert(struct bertx_mvindex *mv, struct bert
     int32_t slot = -1;
     if (!texts || !scores || !ids || n < 1) return -1;
     if (const int32_t rc = emb::colbert_ctx_ok(mv, ctx, "bertx_mvindex_search_texts_colbert", &slot)) return rc;
+    if (emb::full_scan_refused(*mv, "bertx_mvindex_search_texts_colbert")) return -1;
     if (query_maxlen < 4 || query_maxlen > emb::kMaxLq || query_maxlen > bert_n_max_tokens(ctx)) return -1;
     if (!emb::search_args_ok("bertx_mvindex_search_texts_colbert", n, query_maxlen, k)) return -1;
     for (int32_t i = 0; i < n; ++i)
@@ -1158,9 +1330,123 @@ int32_t bertx_mvindex_set_centroids(struct bertx_mvindex *mv, const float *cent,
     if (!mv) return -1;
     std::lock_guard<std::mutex> lk(mv->mu);
     if (!cent || !emb::centroid_count_ok("bertx_mvindex_set_centroids", C)) return -1;
+    if (emb::res_nbits(*mv) && mv->n_docs > 0) {
+        emb::errorf("bertx_mvindex_set_centroids: a residual store with documents keeps no rows to code again\n");
+        return -1;
+    }
     DeviceGuard g(mv->ordinal);
     HIP_RC(g.status());
     return emb::set_centroids_locked(*mv, cent, C);
+}
+
+int32_t bertx_mvindex_set_residual_buckets(struct bertx_mvindex *mv, const float *cutoffs, const float *weights)
+{
+    if (!mv || !cutoffs || !weights) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    const int nb = emb::res_nbits(*mv);
+    if (!nb || mv->n_docs > 0) {
+        emb::errorf("bertx_mvindex_set_residual_buckets: %s\n",
+                    nb ? "the store holds documents encoded with its buckets" : "not a residual store");
+        return -1;
+    }
+    const int nw = 1 << nb;
+    for (int k = 0; k < nw; ++k)
+        if (!std::isfinite(weights[k]) || (k < nw - 1 && !std::isfinite(cutoffs[k])) ||
+            (k > 0 && k < nw - 1 && cutoffs[k] < cutoffs[k - 1])) {
+            emb::errorf("bertx_mvindex_set_residual_buckets: cutoffs must be finite and non-decreasing, weights finite\n");
+            return -1;
+        }
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    float cuts[15] = {};
+    uint16_t wts[16] = {};
+    uint32_t pair[256] = {};
+    for (int k = 0; k < nw - 1; ++k) cuts[k] = cutoffs[k];
+    for (int k = 0; k < nw; ++k) wts[k] = emb::f32_to_f16(weights[k]);
+    for (int b1 = 0; b1 < nw; ++b1)
+        for (int b0 = 0; b0 < nw; ++b0) pair[b0 | (b1 << nb)] = (uint32_t)wts[b0] | ((uint32_t)wts[b1] << 16);
+    HIP_RC(mv->ord.wait());   // an empty store's scorer still copies the pair table
+    HIP_RC(hipMemcpy(mv->res_cuts, cuts, sizeof cuts, hipMemcpyHostToDevice));
+    HIP_RC(hipMemcpy(mv->res_wts, wts, sizeof wts, hipMemcpyHostToDevice));
+    HIP_RC(hipMemcpy(mv->res_pair, pair, sizeof pair, hipMemcpyHostToDevice));
+    std::memcpy(mv->h_wts, wts, sizeof wts);
+    mv->has_buckets = true;
+    return 0;
+}
+
+int32_t bertx_mvindex_doc_residual(struct bertx_mvindex *mv, int32_t id, uint16_t *codes, uint8_t *bits, float *u)
+{
+    if (!mv || !codes || !bits || !u) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    const int nb = emb::res_nbits(*mv);
+    if (!nb || id < 0 || id >= mv->n_docs) return -1;
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    try {
+        // through buffers of its own: a failed copy leaves the outputs untouched
+        const int64_t len = mv->h_table[2 * (size_t)id + 1];
+        std::vector<uint16_t> hc((size_t)len);
+        std::vector<uint8_t> hb((size_t)len * mv->w * nb / 8);
+        std::vector<float> hu((size_t)len);
+        const int32_t rc = emb::read_doc_res(*mv, id, hc.data(), hb.data(), hu.data());
+        if (rc != 0) return rc;
+        std::memcpy(codes, hc.data(), hc.size() * 2);
+        std::memcpy(bits, hb.data(), hb.size());
+        std::memcpy(u, hu.data(), hu.size() * 4);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_mvindex_doc_residual: out of host memory\n");
+        return -1;
+    }
+    return 0;
+}
+
+int32_t bertx_mvindex_train_residual_buckets(struct bertx_mvindex *src, int32_t nbits, float *cutoffs, float *weights)
+{
+    if (!src || !cutoffs || !weights) return -1;
+    std::lock_guard<std::mutex> lk(src->mu);
+    if (src->storage != BERTX_INDEX_F16 || src->C == 0 || src->n_docs < 1 || (nbits != 2 && nbits != 4)) {
+        emb::errorf("bertx_mvindex_train_residual_buckets: needs an f16 store with centroids and documents, and 2 or 4 "
+                    "bits\n");
+        return -1;
+    }
+    DeviceGuard g(src->ordinal);
+    HIP_RC(g.status());
+    try {
+        const int w = src->w;
+        int64_t T = 0;
+        for (int64_t d = 0; d < src->n_docs; ++d) T += src->h_table[2 * (size_t)d + 1];
+        const int64_t stride = std::max<int64_t>(1, (T + 65535) / 65536);
+        std::vector<float> cent, rows, res;
+        if (const int32_t rc = emb::read_centroids_f16(*src, cent)) return rc;
+        std::vector<uint16_t> codes((size_t)src->used_slots);
+        HIP_RC(hipMemcpy(codes.data(), src->codes, codes.size() * 2, hipMemcpyDeviceToHost));
+        res.reserve((size_t)((T + stride - 1) / stride) * w);
+        int64_t t0 = 0, next = 0;
+        for (int32_t d = 0; d < src->n_docs; ++d) {
+            const int64_t first = src->h_table[2 * (size_t)d], len = src->h_table[2 * (size_t)d + 1];
+            if (next < t0 + len) {
+                rows.resize((size_t)len * w);
+                if (const int32_t rc = emb::doc_locked(src, d, rows.data())) return rc;
+                for (; next < t0 + len; next += stride) {
+                    const float *v = rows.data() + (size_t)(next - t0) * w;
+                    const float *c = cent.data() + (size_t)codes[(size_t)(first * 16 + (next - t0))] * w;
+                    for (int i = 0; i < w; ++i) res.push_back(v[i] - c[i]);
+                }
+            }
+            t0 += len;
+        }
+        std::sort(res.begin(), res.end());
+        const int64_t n = (int64_t)res.size(), nw = (int64_t)1 << nbits;
+        std::vector<float> hc((size_t)nw - 1), hw((size_t)nw);
+        for (int64_t k = 1; k < nw; ++k) hc[(size_t)k - 1] = res[(size_t)std::min(n - 1, k * n / nw)];
+        for (int64_t k = 0; k < nw; ++k) hw[(size_t)k] = res[(size_t)std::min(n - 1, (2 * k + 1) * n / (2 * nw))];
+        std::memcpy(cutoffs, hc.data(), hc.size() * 4);
+        std::memcpy(weights, hw.data(), hw.size() * 4);
+        return 0;
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_mvindex_train_residual_buckets: out of host memory\n");
+        return -1;
+    }
 }
 
 int32_t bertx_mvindex_centroids(struct bertx_mvindex *mv)
@@ -1227,6 +1513,10 @@ int32_t bertx_mvindex_train_centroids(struct bertx_mvindex *mv, int32_t C, int32
     if (!mv) return -1;
     std::lock_guard<std::mutex> lk(mv->mu);
     if (!emb::centroid_count_ok("bertx_mvindex_train_centroids", C)) return -1;
+    if (emb::res_nbits(*mv)) {
+        emb::errorf("bertx_mvindex_train_centroids: a residual store keeps no rows to train from (train on an f16 store)\n");
+        return -1;
+    }
     if (iters < 0 || mv->n_docs < 1) {
         emb::errorf("bertx_mvindex_train_centroids: iters = %d, %lld documents: nothing to train on\n", iters,
                     (long long)mv->n_docs);
@@ -1523,7 +1813,122 @@ static int32_t bench_store(int32_t w, int32_t n_docs, int32_t doc_len, int32_t L
     }
 }
 
+// bertx_bench_maxsim_res: bench_store's documents (the same lens and fill seeds) twice: in an
+// f16 store, whose C hash-chosen rows become the centroids and which trains the buckets, then
+// in the residual store.
+static int32_t bench_res(int32_t w, int32_t n_docs, int32_t doc_len, int32_t C, int32_t Lq, int32_t n_cand, int32_t storage,
+                         int32_t iters, float *avg_us)
+{
+    using namespace emb;
+    if (n_docs < 1 || doc_len < 0 || doc_len > 4096 || n_cand < 1 || iters < 1 || !avg_us || Lq < 1 || Lq > kMaxLq ||
+        (storage != BERTX_INDEX_RES2 && storage != BERTX_INDEX_RES4) || hip_device_count() == 0 ||
+        !centroid_count_ok("bertx_bench_maxsim_res", C))
+        return -1;
+    try {
+        std::vector<int32_t> lens((size_t)n_docs), ids((size_t)n_cand);
+        int64_t slots = 0;
+        for (int32_t i = 0; i < n_docs; ++i) {
+            uint32_t h = (uint32_t)i * 2654435761u + 99u;
+            h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
+            lens[(size_t)i] = doc_len ? doc_len : 16 + (int32_t)(h % 497u);
+            slots += (lens[(size_t)i] + 15) / 16 * 16;
+        }
+        for (int32_t c = 0; c < n_cand; ++c) ids[(size_t)c] = (int32_t)(((uint64_t)c * 2654435761ull + 12345ull) % (uint64_t)n_docs);
+        DeviceGuard guard(0);
+        HIP_RC(guard.status());
+        struct Holder {
+            bertx_mvindex *f16 = nullptr, *res = nullptr;
+            hipStream_t s = nullptr;
+            hipEvent_t a = nullptr, b = nullptr;
+            DevBuf rows, q, id, out, oid;
+            ~Holder()
+            {
+                if (s) (void)hipStreamSynchronize(s);
+                if (a) (void)hipEventDestroy(a);
+                if (b) (void)hipEventDestroy(b);
+                if (s) (void)hipStreamDestroy(s);
+                bertx_mvindex_free(f16);
+                bertx_mvindex_free(res);
+            }
+        } H;
+        HIP_RC(hipStreamCreateWithFlags(&H.s, hipStreamNonBlocking));
+        HIP_RC(hipEventCreate(&H.a));
+        HIP_RC(hipEventCreate(&H.b));
+        constexpr int64_t kFillRows = 1 << 18;
+        HIP_RC(hipMalloc(&H.rows.p, (size_t)(kFillRows + 4096) * w * 4));
+        HIP_RC(hipMalloc(&H.q.p, (size_t)kMaxLq * w * 4));
+        HIP_RC(hipMalloc(&H.id.p, (size_t)n_cand * 4));
+        HIP_RC(hipMalloc(&H.out.p, (size_t)std::max(n_cand, kMaxK) * 4));
+        HIP_RC(hipMalloc(&H.oid.p, (size_t)kMaxK * 4));
+        auto fill = [&](bertx_mvindex *mv) -> int32_t {
+            for (int32_t i = 0; i < n_docs;) {
+                int32_t j = i;
+                int64_t rows = 0;
+                while (j < n_docs && (j == i || rows + lens[(size_t)j] <= kFillRows)) rows += lens[(size_t)j++];
+                if (launch_unit_rows((float *)H.rows.p, rows, w, 12345u + (uint32_t)i, H.s) != 0) return -1;
+                if (bertx_mvindex_add_device(mv, (const float *)H.rows.p, lens.data() + i, j - i, H.s) < 0) return -1;
+                HIP_RC(hipStreamSynchronize(H.s));   // the fill buffer is reused
+                i = j;
+            }
+            return 0;
+        };
+        H.f16 = mvindex_create_on(0, w, n_docs, slots, BERTX_INDEX_F16);
+        if (!H.f16 || fill(H.f16) != 0) return -1;
+        std::vector<float> cent((size_t)C * w), rows;
+        for (int32_t c = 0; c < C; ++c) {
+            const int32_t id = (int32_t)(((uint64_t)c * 2654435761ull + 777ull) % (uint64_t)n_docs);
+            rows.resize((size_t)lens[(size_t)id] * w);
+            if (bertx_mvindex_doc(H.f16, id, rows.data()) != 0) return -1;
+            std::memcpy(cent.data() + (size_t)c * w, rows.data() + (size_t)(c % lens[(size_t)id]) * w, (size_t)w * 4);
+        }
+        float cuts[15], wts[16];
+        if (bertx_mvindex_set_centroids(H.f16, cent.data(), C) != 0) return -1;
+        if (bertx_mvindex_train_residual_buckets(H.f16, storage == BERTX_INDEX_RES2 ? 2 : 4, cuts, wts) != 0) return -1;
+        bertx_mvindex_free(H.f16);
+        H.f16 = nullptr;
+        H.res = mvindex_create_on(0, w, n_docs, slots, storage);
+        if (!H.res || bertx_mvindex_set_centroids(H.res, cent.data(), C) != 0 ||
+            bertx_mvindex_set_residual_buckets(H.res, cuts, wts) != 0 || fill(H.res) != 0)
+            return -1;
+        if (launch_unit_rows((float *)H.q.p, Lq, w, 777u, H.s) != 0) return -1;
+        HIP_RC(hipMemcpyAsync(H.id.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, H.s));
+        HIP_RC(hipStreamSynchronize(H.s));
+        auto timed = [&](auto &&fn, float *us) -> int32_t {
+            for (int i = 0; i < 3; ++i)
+                if (fn() != 0) return -1;
+            HIP_RC(hipEventRecord(H.a, H.s));
+            for (int i = 0; i < iters; ++i)
+                if (fn() != 0) return -1;
+            HIP_RC(hipEventRecord(H.b, H.s));
+            HIP_RC(hipEventSynchronize(H.b));
+            float ms = 0.f;
+            HIP_RC(hipEventElapsedTime(&ms, H.a, H.b));
+            *us = ms * 1000.f / (float)iters;
+            return 0;
+        };
+        if (timed([&] {
+                return bertx_mvindex_score_device(H.res, (const float *)H.q.p, Lq, (const int32_t *)H.id.p, n_cand,
+                                                  (float *)H.out.p, H.s);
+            }, avg_us) != 0)
+            return -1;
+        const int32_t nc = std::min(n_cand, kMaxK), k = std::min(nc, 10);
+        return timed([&] {
+            return bertx_mvindex_search_pruned_device(H.res, (const float *)H.q.p, 1, Lq, k, nc, (float *)H.out.p,
+                                                      (int32_t *)H.oid.p, H.s);
+        }, avg_us + 1);
+    } catch (const std::exception &ex) {
+        emb::errorf("bertx_bench_maxsim_res: %s\n", ex.what());
+        return -1;
+    }
+}
+
 extern "C" {
+
+int32_t bertx_bench_maxsim_res(int32_t w, int32_t n_docs, int32_t doc_len, int32_t C, int32_t Lq, int32_t n_cand,
+                               int32_t storage, int32_t iters, float *avg_us)
+{
+    return bench_res(w, n_docs, doc_len, C, Lq, n_cand, storage, iters, avg_us);
+}
 
 int32_t bertx_bench_maxsim_ex(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t storage,
                               int32_t iters, float *avg_us)

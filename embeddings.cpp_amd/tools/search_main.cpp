@@ -4,7 +4,7 @@
 //
 // usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8]
 //               [-r RERANK_MODEL [-c N] | -l [-c N | -a [-C N [-c N]]] | -L COLBERT_MODEL [-M] [-c N | -a [-C N [-c N]]]]
-//               [-S f16|int8]
+//               [-S f16|int8|res2|res4]
 // One text per line of CORPUS.txt; queries from stdin, one per line, `q` or EOF ends.
 // Per hit one line: rank<TAB>id<TAB>score<TAB>text.
 // -s: how the index stores its rows (bertx_index_create_ex): f16, the default, or int8
@@ -38,6 +38,12 @@
 // -S: with -l or -L, how the token store keeps its rows (bertx_mvindex_create_ex): f16,
 // the default, or int8 with one f32 per token, half the bytes and a less precise
 // similarity.  -s still speaks of the index alone.
+// -S res2 | res4: with -a -C N, a residual-coded token store (bert_hip.h "Residual codes"):
+// the corpus first fills a temporary f16 store, on which the N centroids and then the
+// residual buckets are trained (bertx_mvindex_train_residual_buckets); the residual store
+// gets those centroids (read back with bertx_mvindex_centroid) and buckets, the corpus is
+// added to it, the f16 store is freed, and the queries go through the pruned search.
+// -S res* without -C is a usage error.
 #include "bert.h"
 #include "bert_hip.h"
 
@@ -53,7 +59,7 @@
 int main(int argc, char **argv)
 {
     const char *model = nullptr, *corpus = nullptr, *rerank = nullptr, *colbert = nullptr;
-    int k = 3, threads = 4, cand = 0, cents = 0, storage = BERTX_INDEX_F16, mv_storage = -1;
+    int k = 3, threads = 4, cand = 0, cents = 0, storage = BERTX_INDEX_F16, mv_storage = -1, res_storage = -1;
     bool late = false, all = false, no_mask_keys = false;
     for (int i = 1; i < argc; ++i) {
         const bool has = i + 1 < argc;
@@ -65,6 +71,11 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "-s") && has && !std::strcmp(argv[i + 1], "int8")) { storage = BERTX_INDEX_I8; ++i; }
         else if (!std::strcmp(argv[i], "-S") && has && !std::strcmp(argv[i + 1], "f16")) { mv_storage = BERTX_INDEX_F16; ++i; }
         else if (!std::strcmp(argv[i], "-S") && has && !std::strcmp(argv[i + 1], "int8")) { mv_storage = BERTX_INDEX_I8; ++i; }
+        else if (!std::strcmp(argv[i], "-S") && has && (!std::strcmp(argv[i + 1], "res2") || !std::strcmp(argv[i + 1], "res4"))) {
+            // (the store that is filled first is the f16 one the centroids and buckets are trained on)
+            mv_storage = BERTX_INDEX_F16;
+            res_storage = argv[++i][3] == '2' ? BERTX_INDEX_RES2 : BERTX_INDEX_RES4;
+        }
         else if (!std::strcmp(argv[i], "-r") && has) rerank = argv[++i];
         else if (!std::strcmp(argv[i], "-c") && has) cand = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "-C") && has) { cents = std::atoi(argv[++i]); if (cents < 1) cents = -1; }
@@ -80,11 +91,11 @@ int main(int argc, char **argv)
     if (second && (!all || cents) && cand == 0) cand = std::min(128, 4 * k);
     if (bad_all || !model || !corpus || k < 1 || k > 128 || threads < 1 || (int)(rerank != nullptr) + late + (colbert != nullptr) > 1 ||
         (second && (!all || cents) ? cand < k || cand > 128 : cand != 0) || (mv_storage >= 0 && !late && !colbert) ||
-        (no_mask_keys && !colbert)) {
+        (no_mask_keys && !colbert) || (res_storage >= 0 && cents == 0)) {
         std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads] [-s f16|int8] "
                              "[-r RERANK_MODEL [-c N (k..128, default 4 k)] | -l [-c N | -a [-C CENTROIDS [-c N]]] | "
                              "-L COLBERT_MODEL [-M] [-c N | -a [-C CENTROIDS [-c N]]]] "
-                             "[-S f16|int8 (the token store of -l / -L)]\n",
+                             "[-S f16|int8 (the token store of -l / -L) | res2|res4 (with -a -C)]\n",
                      argv[0]);
         return 2;
     }
@@ -170,22 +181,46 @@ int main(int argc, char **argv)
         }
     }
     int rc = 0;
-    // the corpus in batches (one encoder call each)
-    for (size_t i = 0; i < texts.size() && rc == 0; i += 256) {
-        std::vector<const char *> p;
-        for (size_t j = i; j < texts.size() && j < i + 256; ++j) p.push_back(texts[j].c_str());
-        if (idx && bertx_index_add_texts(idx, ctx, threads, (int32_t)p.size(), p.data()) < 0) {
-            std::fprintf(stderr, "search: indexing failed at text %zu\n", i);
-            rc = 1;
-        } else if (mv && (colbert ? bertx_mvindex_add_texts_colbert(mv, rctx, threads, (int32_t)p.size(), p.data(), doc_maxlen)
-                                  : bertx_mvindex_add_texts(mv, ctx, threads, (int32_t)p.size(), p.data())) < 0) {
-            std::fprintf(stderr, "search: token indexing failed at text %zu\n", i);
-            rc = 1;
+    // the corpus in batches (one encoder call each); `to`: the token store that takes them
+    auto add_corpus = [&](bertx_index *ix, bertx_mvindex *to) {
+        for (size_t i = 0; i < texts.size() && rc == 0; i += 256) {
+            std::vector<const char *> p;
+            for (size_t j = i; j < texts.size() && j < i + 256; ++j) p.push_back(texts[j].c_str());
+            if (ix && bertx_index_add_texts(ix, ctx, threads, (int32_t)p.size(), p.data()) < 0) {
+                std::fprintf(stderr, "search: indexing failed at text %zu\n", i);
+                rc = 1;
+            } else if (to && (colbert ? bertx_mvindex_add_texts_colbert(to, rctx, threads, (int32_t)p.size(), p.data(), doc_maxlen)
+                                      : bertx_mvindex_add_texts(to, ctx, threads, (int32_t)p.size(), p.data())) < 0) {
+                std::fprintf(stderr, "search: token indexing failed at text %zu\n", i);
+                rc = 1;
+            }
         }
-    }
+    };
+    add_corpus(idx, mv);
     if (rc == 0 && cents && bertx_mvindex_train_centroids(mv, cents, 8, 0) != 0) {
         std::fprintf(stderr, "search: training %d centroids failed\n", cents);
         rc = 1;
+    }
+    if (rc == 0 && res_storage >= 0) {
+        // mv is the temporary f16 store: its centroids and the buckets trained on it go to the
+        // residual store, which takes the corpus and mv's place
+        const int32_t w = bertx_mvindex_dim(mv);
+        std::vector<float> cent((size_t)cents * w), cuts(15), wts(16);
+        for (int c = 0; c < cents && rc == 0; ++c)
+            if (bertx_mvindex_centroid(mv, c, cent.data() + (size_t)c * w) != 0) rc = 1;
+        if (rc == 0 && bertx_mvindex_train_residual_buckets(mv, res_storage == BERTX_INDEX_RES2 ? 2 : 4, cuts.data(),
+                                                            wts.data()) != 0)
+            rc = 1;
+        bertx_mvindex *rs = rc ? nullptr
+                               : bertx_mvindex_create_ex(colbert ? rctx : ctx, 0, w, bertx_mvindex_capacity_docs(mv),
+                                                         bertx_mvindex_capacity_token_slots(mv), res_storage);
+        bertx_mvindex_free(mv);
+        mv = rs;
+        if (!mv || bertx_mvindex_set_centroids(mv, cent.data(), cents) != 0 ||
+            bertx_mvindex_set_residual_buckets(mv, cuts.data(), wts.data()) != 0)
+            rc = 1;
+        if (rc == 0) add_corpus(nullptr, mv);
+        if (rc != 0) std::fprintf(stderr, "search: building the residual store failed\n");
     }
     const int kq = second && !all ? cand : k;   // what the index (-a: the token store) is asked for
     std::vector<float> scores((size_t)kq);

@@ -538,7 +538,8 @@ BERT_API int32_t bertx_index_search_texts(struct bertx_index *idx, struct bert_c
  * Storage kinds.  bertx_mvindex_create_ex takes the kind: BERTX_INDEX_F16 (0) is exactly
  * bertx_mvindex_create, everything above; BERTX_INDEX_I8 (1) stores a token row as `width`
  * int8 values and one f32, width + 4 bytes instead of 2 width (the store allocates
- * slots * width bytes and slots * 4 bytes of scales); any other value returns NULL after
+ * slots * width bytes and slots * 4 bytes of scales); BERTX_INDEX_RES2 (4) and _RES4 (5)
+ * are the kinds of "Residual codes" below (2 and 3 are no kinds); any other value returns NULL after
  * a message.  bertx_mvindex_storage returns the kind, -1 for NULL.  Every other entry
  * (_add, _add_device, _score, _score_device, _clear, _add_texts, _score_text and the two
  * _colbert text forms) follows the store's kind with the same signature, refusals,
@@ -687,10 +688,90 @@ BERT_API int32_t bertx_index_search_texts(struct bertx_index *idx, struct bert_c
  * rows as centroids; avg_us[0 .. 2] = the table kernels, the scans with their selections,
  * and the whole pruned search of B queries, each the average of `iters` calls after 3.
  *
- * Not provided: int8 queries against f16 rows; 4-bit or residual codes; candidate lists
- * longer than 128; per-query lengths on the device; sharding over GPUs; deleting, saving
- * and loading.  (ColBERT checkpoints: "Projection" below.)
+ * Residual codes (ColBERTv2's compression).  BERTX_INDEX_RES2 (4) and BERTX_INDEX_RES4 (5)
+ * for bertx_mvindex_create_ex keep no token row: per token slot the uint16 centroid code
+ * (the `codes` of "Centroid codes"), NB = 2 or 4 bits per element (width * NB / 8 bytes of
+ * bucket indices) and one f32 u, width * NB / 8 + 6 bytes in all (38 at width 128, NB 2,
+ * against 256 + 2 in f16 and 132 + 2 in int8).  Widths as above.  bertx_index_create_ex, the
+ * embedding index, refuses both kinds.  The centroids of a residual store are packed by the
+ * f16 row packer: they hold exactly the bits that an f16 store given the same `cent` rows
+ * holds.
+ * bertx_mvindex_set_residual_buckets(mv, cutoffs float[2^NB - 1], weights float[2^NB]): the
+ * codec.  Cutoffs finite and non-decreasing, weights finite (-1 otherwise).  The store keeps
+ * cut_k as f32 and wt_k = f16(weights[k]), nearest even.  Refused (-1, a message, nothing
+ * changed) on an f16 or int8 store and on a residual store that holds documents; _clear
+ * keeps centroids and buckets.
+ * The arithmetic, every named operation rounded once.  For a source row x let F be an f16
+ * store of the same width with the same centroids (the "twin"):
+ *   v    = the unit f16 row of pack_row_f16, the bits F stores and bertx_mvindex_doc(F)
+ *          returns;
+ *   code = the code F assigns ("Centroid codes" above); c = that centroid's stored f16 values;
+ *   r_i  = f32(v_i) - f32(c_i), one f32 subtraction;
+ *   b_i  = #{k : cut_k < r_i}, in 0 .. 2^NB - 1;
+ *   e_i  = c_i + wt[b_i], ONE IEEE f16 addition, nearest even, f16 subnormals kept (what
+ *          v_pk_add_f16 computes, and what np.float16 + np.float16 computes: numpy adds in
+ *          f32 and rounds again, which is innocuous because 24 >= 2 * 11 + 2);
+ *   ss   = sum_i e_i^2 taken exactly: every finite f16 is a multiple of 2^-24, every square
+ *          a multiple of 2^-48, so an f64 accumulation in any order is exact while ss < 32
+ *          (a unit centroid plus a small residual keeps ss near 1); ss >= 32 or a non-finite
+ *          e gives unspecified values;
+ *   s    = (float)ss;  u = 1 / sqrtf(s) (sqrt, then the division) if ss > 0, else 0;
+ *   stored: code, the b_i and u;
+ *   sim(q, tok) = acc * u, one f32 multiply; acc is the f16 scorer's accumulation of q16 . e:
+ *          the query through pack_row_f16, the width / 32 v_mfma_f32_16x16x32_f16 in
+ *          ascending k from a zero accumulator;
+ *   score(doc)  = sum_i max_j sim(q_i, tok_j): the max exact, slots past len -inf through a
+ *          select whatever bits, code and u they hold, the sum in the scorer's order (lane c
+ *          adds m[c], m[16 + c], ... from +0, then the butterfly 8, 4, 2, 1).
+ * Nothing stored depends on an order the caller cannot reproduce, so a restatement in numpy
+ * gives code, bits and u bit for bit; acc is an MFMA sum, so scores are checked as the f16
+ * store's are, against the float64 MaxSim of (q16, e, u).  The bound: |q16| and |e u| are
+ * at most 1 + 2^-10 each, the accumulation of `width` products adds at most width * 2^-24
+ * per similarity as in the f16 store (an |e| of 1 / u scales acc and its error alike, and u
+ * scales both back), |acc * u| < 2 so its one extra rounding adds at most 2^-24 per
+ * similarity, once per query row after the exact max, and the f32 sum of the Lq maxima is
+ * the f16 store's (u itself is the same f32 on both sides of the comparison):
+ *   |score - exact| <= Lq (2 width + Lq) 2^-24 + Lq 2^-24.
+ * The invariances of the f16 store hold word for word (id, the other documents, the
+ * candidate list and its order).  One add call of n documents stores the bits that n calls
+ * of one document store.
+ * An add (_add, _add_device and the text forms) is refused (-1) without centroids or without
+ * buckets.  It packs the call's rows into a staging image of the store's own (2 * width
+ * bytes per token slot of the largest call so far), codes them with the f16 assign kernel
+ * and encodes; slots past len get code 0.
+ * Readback: bertx_mvindex_doc returns (float)e_i * u.  bertx_mvindex_doc_residual(mv, id,
+ * codes uint16[len], bits uint8[len][width * NB / 8], u float[len]): element i sits in byte
+ * i * NB / 8 at bit offset NB * (i mod (8 / NB)), low bits first; -1 on another kind or a bad
+ * id, outputs untouched.  _doc_i8 stays -1.
+ * _score / _score_device, _candidates* and _search_pruned* (and _search_pruned_texts) work
+ * as on the other kinds, with the same signatures, stream ordering and capturability: the
+ * candidates from the f16 table kernel and the code scan, the exact stage by a scorer that
+ * gathers each candidate row's centroid chunks by its code and decodes them straight into
+ * the MFMA fragments.  Refused on a residual store (-1, a message, outputs untouched):
+ * _search, _search_device, _search_texts and _search_texts_colbert (the full scan of a
+ * residual store is not provided); _train_centroids (no rows to train from); _set_centroids
+ * once documents are stored (no rows to code again).
+ * bertx_mvindex_train_residual_buckets(src, nbits, cutoffs, weights): ColBERTv2's quantile
+ * rule on the host, deterministic.  src is an f16 store with centroids and documents (-1
+ * otherwise; nbits 2 or 4).  The valid token rows in (document, token) order, every
+ * stride-th from row 0, stride = max(1, ceil(T / 2^16)); all n = rows * width residuals r as
+ * above (v, code and c from _doc, _doc_codes and _centroid), sorted ascending;
+ *   cutoffs[k - 1] = sorted[min(n - 1, floor(k n / 2^NB))],  k = 1 .. 2^NB - 1;
+ *   weights[k]     = sorted[min(n - 1, floor((2k + 1) n / 2^(NB + 1)))];  no interpolation.
+ * The workflow: fill an f16 store with a sample; _train_centroids on it; read the centroids
+ * back with _centroid; train the buckets; create the residual store; _set_centroids and
+ * _set_residual_buckets; add the corpus.
+ * bertx_bench_maxsim_res: the documents of bertx_bench_maxsim_ex in a residual store, C
+ * hash-chosen rows of the f16 twin as centroids and buckets trained from it; avg_us[0] =
+ * bertx_mvindex_score_device over n_cand candidates, avg_us[1] = the pruned search of one
+ * query for the 10 best of min(n_cand, 128) candidates; each the average of `iters` calls
+ * after 3.
+ *
+ * Not provided: int8 queries against f16 rows; the full scan of a residual store, 1-bit
+ * codes; candidate lists longer than 128; per-query lengths on the device; sharding over
+ * GPUs; deleting, saving and loading.  (ColBERT checkpoints: "Projection" below.)
  */
+enum { BERTX_INDEX_RES2 = 4, BERTX_INDEX_RES4 = 5 };   /* token stores only: "Residual codes" above */
 struct bertx_mvindex;
 BERT_API struct bertx_mvindex *bertx_mvindex_create(struct bert_ctx *ctx, int32_t slot, int32_t width,
                                                     int32_t capacity_docs, int64_t capacity_token_slots);
@@ -750,6 +831,12 @@ BERT_API int32_t bertx_mvindex_search_pruned_texts(struct bertx_mvindex *mv, str
                                                    int32_t colbert_query_maxlen, float *scores, int32_t *ids);
 BERT_API int32_t bertx_bench_maxsim_pruned(int32_t w, int32_t n_docs, int32_t doc_len, int32_t C, int32_t Lq, int32_t B,
                                            int32_t k, int32_t n_cand, int32_t storage, int32_t iters, float *avg_us);
+BERT_API int32_t bertx_mvindex_set_residual_buckets(struct bertx_mvindex *mv, const float *cutoffs, const float *weights);
+BERT_API int32_t bertx_mvindex_train_residual_buckets(struct bertx_mvindex *src, int32_t nbits, float *cutoffs,
+                                                      float *weights);
+BERT_API int32_t bertx_mvindex_doc_residual(struct bertx_mvindex *mv, int32_t id, uint16_t *codes, uint8_t *bits, float *u);
+BERT_API int32_t bertx_bench_maxsim_res(int32_t w, int32_t n_docs, int32_t doc_len, int32_t C, int32_t Lq, int32_t n_cand,
+                                        int32_t storage, int32_t iters, float *avg_us);
 /* Test hooks: which table placement the candidate scans took; the host half of training
  * (kmeans_update.h): one update in place, returning the centroids without a member; the
  * sample rule, out3 = {stride, start, n_sample}. */
