@@ -188,6 +188,24 @@ def load_lib(path=None):
         L.bertx_bench_search_add_rate_ex.argtypes = [c_i32, c_i32, c_i32, ctypes.POINTER(ctypes.c_double)]
     except AttributeError:
         pass
+    try:   # (binary storage, listed rows, the rescored search: absent from older BERT_LIB builds)
+        L.bertx_index_rows_bits.restype = c_i32
+        L.bertx_index_rows_bits.argtypes = [vp, c_i32, c_i32, vp]
+        L.bertx_index_score_ids.restype = c_i32
+        L.bertx_index_score_ids.argtypes = [vp, vp, c_i32, vp, c_i32, vp]
+        L.bertx_index_score_ids_device.restype = c_i32
+        L.bertx_index_score_ids_device.argtypes = [vp, vp, c_i32, vp, c_i32, vp, vp]
+        L.bertx_index_search_rescored.restype = c_i32
+        L.bertx_index_search_rescored.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, vp, vp]
+        L.bertx_index_search_rescored_device.restype = c_i32
+        L.bertx_index_search_rescored_device.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, vp, vp, vp]
+        L.bertx_index_search_rescored_texts.restype = c_i32
+        L.bertx_index_search_rescored_texts.argtypes = [vp, vp, vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p), c_i32,
+                                                        c_i32, vp, vp]
+        L.bertx_bench_search_rescored.restype = c_i32
+        L.bertx_bench_search_rescored.argtypes = [c_i32] * 7 + [c_f32p]
+    except AttributeError:
+        pass
     try:   # (cross-encoder reranking: absent from older BERT_LIB builds)
         L.bertx_convert_hf_head.restype = c_i32
         L.bertx_convert_hf_head.argtypes = [ctypes.c_char_p, ctypes.c_char_p, c_i32]
@@ -673,7 +691,7 @@ class BertIndex:
 
     def __init__(self, model, capacity, slot=0, storage="f16"):
         if storage not in self.STORAGE:
-            raise ValueError("storage must be 'f16' or 'int8', got %r" % (storage,))
+            raise ValueError("storage must be %s, got %r" % (" or ".join(repr(s) for s in self.STORAGE), storage))
         self.model = model
         self.lib = model.lib
         self.storage = storage
@@ -759,6 +777,69 @@ class BertIndex:
         if n and self.lib.bertx_index_rows_i8(self.idx, first, n, q.ctypes.data, scale.ctypes.data) != 0:
             raise RuntimeError("bertx_index_rows_i8 failed")
         return q, scale
+
+    def score_ids(self, queries, ids):
+        """scores f32 [B][n]: the score of (query b, row ids[b][j]) with the bits search() gives
+        that pair, -inf for an id outside the index (a search's -1 fill included); n <= 128."""
+        q = self._rows(queries)
+        ids = np.ascontiguousarray(np.asarray(ids, np.int32))
+        if ids.ndim == 1:
+            ids = ids[None, :]
+        if ids.ndim != 2 or ids.shape[0] != q.shape[0]:
+            raise ValueError("expected ids of shape (%d, n), got %r" % (q.shape[0], ids.shape))
+        scores = np.zeros(ids.shape, np.float32)
+        rc = self.lib.bertx_index_score_ids(self.idx, q.ctypes.data, q.shape[0], ids.ctypes.data, ids.shape[1],
+                                            scores.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_index_score_ids failed (%d)" % rc)
+        return scores
+
+    @staticmethod
+    def _n_cand(k, n_cand):
+        return min(128, 4 * k) if n_cand is None else n_cand
+
+    def search_rescored(self, queries, k, fine, n_cand=None):
+        """The two-stage search: this index finds n_cand candidates per query (default
+        min(128, 4 k)), `fine` (another BertIndex of the same width whose rows were added in
+        the same order) scores them, the k best by fine's scores come back.  Bit for bit
+        search(n_cand) -> fine.score_ids -> the order of the results."""
+        q = self._rows(queries)
+        scores = np.zeros((q.shape[0], k), np.float32)
+        ids = np.zeros((q.shape[0], k), np.int32)
+        rc = self.lib.bertx_index_search_rescored(self.idx, fine.idx, q.ctypes.data, q.shape[0], k, self._n_cand(k, n_cand),
+                                                  scores.ctypes.data, ids.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_index_search_rescored failed (%d)" % rc)
+        return scores, ids
+
+    def search_rescored_texts(self, texts, k, fine, n_cand=None):
+        scores = np.zeros((len(texts), k), np.float32)
+        ids = np.zeros((len(texts), k), np.int32)
+        rc = self.lib.bertx_index_search_rescored_texts(self.idx, fine.idx, self.model.ctx, self.model.N_THREADS, len(texts),
+                                                        self._texts(texts), k, self._n_cand(k, n_cand), scores.ctypes.data,
+                                                        ids.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_index_search_rescored_texts failed (%d)" % rc)
+        return scores, ids
+
+
+class BertBinaryIndex(BertIndex):
+    """A BertIndex that keeps a row as its d sign bits (bit = x > 0), one sixteenth of f16.
+    A score is d - 2 hamming(bits_query, bits_row), an exact integer: the dot product of the
+    two +-1 vectors, no cosine.  Its use is as the first stage of search_rescored() in front
+    of an f16 or int8 BertIndex of the same rows; bert_hip.h "Binary storage"."""
+
+    STORAGE = {"binary": 8}
+
+    def __init__(self, model, capacity, slot=0, storage="binary"):
+        super().__init__(model, capacity, slot, storage)
+
+    def rows_bits(self, first, n):
+        """The stored bits uint8 [n][dim / 8] in np.packbits order."""
+        out = np.zeros((n, self.dim // 8), np.uint8)
+        if n and self.lib.bertx_index_rows_bits(self.idx, first, n, out.ctypes.data) != 0:
+            raise RuntimeError("bertx_index_rows_bits failed")
+        return out
 
 
 class BertTokenIndex:

@@ -678,6 +678,52 @@ extern "C" int32_t bertx_bench_search_add_rate_ex(int32_t d, int32_t N, int32_t 
     return 0;
 }
 
+extern "C" int32_t bertx_bench_search_rescored(int32_t d, int32_t N, int32_t B, int32_t k, int32_t n_cand, int32_t fine,
+                                               int32_t iters, float *avg_us)
+{
+    using namespace emb;
+    if (N <= 0 || B <= 0 || iters <= 0 || !avg_us || k < 1 || k > n_cand || n_cand > 128 || hip_device_count() == 0 ||
+        (fine != BERTX_INDEX_F16 && fine != BERTX_INDEX_I8))
+        return -1;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs bufs;
+    IndexHolder H, F;
+    StreamHolder S;   // destroyed (after a synchronise) before the indexes and the buffers
+    HIP_RC(hipStreamCreateWithFlags(&S.s, hipStreamNonBlocking));
+    // the same rows in both: bench_index's rows depend on the position alone
+    if (bench_index(d, N, BERTX_INDEX_BIN, bufs, H, S.s, nullptr) != 0 || bench_index(d, N, fine, bufs, F, S.s, nullptr) != 0)
+        return -1;
+    float *q = (float *)bufs.up(nullptr, 0, (size_t)B * d * 4);
+    float *sc = (float *)bufs.up(nullptr, 0, (size_t)B * 128 * 4);
+    int32_t *id = (int32_t *)bufs.up(nullptr, 0, (size_t)B * 128 * 4);
+    float *cs = (float *)bufs.up(nullptr, 0, (size_t)B * 128 * 4);
+    int32_t *ci = (int32_t *)bufs.up(nullptr, 0, (size_t)B * 128 * 4);
+    if (bufs.bad || launch_unit_rows(q, B, d, 777u, S.s) != 0) return -1;
+    EventPair ev;
+    HIP_RC(ev.create());
+    for (int what = 0; what < 3; ++what) {
+        auto call = [&]() -> int32_t {
+            if (what == 0) return bertx_index_search_rescored_device(H.ix, F.ix, q, B, k, n_cand, sc, id, S.s);
+            if (what == 1) return bertx_index_score_ids_device(F.ix, q, B, ci, n_cand, sc, S.s);
+            return bertx_index_search_device(H.ix, q, B, n_cand, cs, ci, S.s);
+        };
+        // (the ids the scorer is timed on are the binary search's: it runs once before any timing)
+        if (what == 0 && bertx_index_search_device(H.ix, q, B, n_cand, cs, ci, S.s) != 0) return -1;
+        for (int i = 0; i < 3; ++i)
+            if (call() != 0) return -1;
+        HIP_RC(hipEventRecord(ev.a, S.s));
+        for (int i = 0; i < iters; ++i)
+            if (call() != 0) return -1;
+        HIP_RC(hipEventRecord(ev.b, S.s));
+        HIP_RC(hipEventSynchronize(ev.b));
+        float ms = 0.f;
+        HIP_RC(hipEventElapsedTime(&ms, ev.a, ev.b));
+        avg_us[what] = ms * 1000.f / (float)iters;
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------
 // Row-kernel parity hooks (norm.hip, f32.hip, table_read.h): one launch over host
 // buffers.  The caller's output buffers (out_rows rows, at least the rows the

@@ -1,6 +1,7 @@
 // The device-resident embedding index (bert_hip.h bertx_index_*): an append-only
-// matrix of f16 or int8 rows in HBM in the search kernel's fragment order (kernels.h),
-// the fused top-k search over it, and the text forms on top of bert_encode_batch.
+// matrix of f16, int8 or binary rows in HBM in the search kernels' order (kernels.h),
+// the fused top-k search over it, the scorer of listed rows, the two-stage search over
+// two indexes, and the text forms on top of bert_encode_batch.
 // After creation an index knows only its device ordinal, its width and its storage.
 // The ordering of its device operations and the unpackers of the read-back forms are
 // shared with the token store (store_common.h).
@@ -24,9 +25,13 @@ struct bertx_index {
     int d = 0;
     int storage = BERTX_INDEX_F16;
     int64_t cap = 0, n = 0;
-    void *rows = nullptr;        // f16 or int8, ceil(cap / 16) groups in fragment order
+    void *rows = nullptr;        // f16 or int8: ceil(cap / 16) groups in fragment order; binary: ceil(cap / 64) in bit order
     float *scales = nullptr;     // int8: one per row of the padded capacity
     void *scratch = nullptr;     // partial lists of one search launch
+    // the rescored search's candidates, kStage queries at a time, [kStage][128] each: what this
+    // index (as the coarse one) found, and what the fine index made of it
+    float *cand_s = nullptr, *cand_exact = nullptr;
+    int32_t *cand_i = nullptr, *cand_kept = nullptr;
     // staging of the host forms, kStage rows or queries at a time
     float *st_rows = nullptr, *st_scores = nullptr;
     int32_t *st_ids = nullptr;
@@ -45,6 +50,10 @@ struct bertx_index {
         if (st_rows) (void)hipFree(st_rows);
         if (st_scores) (void)hipFree(st_scores);
         if (st_ids) (void)hipFree(st_ids);
+        if (cand_s) (void)hipFree(cand_s);
+        if (cand_exact) (void)hipFree(cand_exact);
+        if (cand_i) (void)hipFree(cand_i);
+        if (cand_kept) (void)hipFree(cand_kept);
         if (ord.done) (void)hipEventDestroy(ord.done);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -56,6 +65,17 @@ namespace {
 constexpr int kStage = 256;   // rows / queries per staged chunk of the host forms
 constexpr int kMaxK = 128;
 
+bool kind_known(int storage)
+{
+    return storage == BERTX_INDEX_F16 || storage == BERTX_INDEX_I8 || storage == BERTX_INDEX_BIN;
+}
+
+void refuse_kind(int storage)
+{
+    errorf("bertx_index_create: storage %d is none of BERTX_INDEX_F16 (0), BERTX_INDEX_I8 (1), BERTX_INDEX_BIN (8)\n",
+           storage);
+}
+
 int32_t add_device_locked(bertx_index &ix, const float *d_rows, int32_t n, hipStream_t s)
 {
     if (!d_rows || n < 1) return -1;
@@ -65,7 +85,9 @@ int32_t add_device_locked(bertx_index &ix, const float *d_rows, int32_t n, hipSt
     }
     {
         Ordered o(ix.ord, s);
-        const int rc = launch_index_add(d_rows, n, ix.d, ix.n, ix.storage, ix.rows, ix.scales, s);
+        const int rc = ix.storage == BERTX_INDEX_BIN
+                           ? launch_index_add_bin(d_rows, n, ix.d, ix.n, ix.rows, s)
+                           : launch_index_add(d_rows, n, ix.d, ix.n, ix.storage, ix.rows, ix.scales, s);
         if (rc != 0) return rc;
     }
     const int32_t first = (int32_t)ix.n;
@@ -73,20 +95,74 @@ int32_t add_device_locked(bertx_index &ix, const float *d_rows, int32_t n, hipSt
     return first;
 }
 
+// the search of the index's kind on s (idx locked; the caller orders it)
+int search_launch(bertx_index &ix, const float *d_q, int32_t B, int32_t k, float *d_scores, int32_t *d_ids, hipStream_t s)
+{
+    if (ix.storage == BERTX_INDEX_BIN) return launch_search_bin(ix.rows, ix.n, ix.d, d_q, B, k, ix.scratch, d_scores, d_ids, s);
+    return launch_search(ix.rows, ix.scales, ix.storage, ix.n, ix.d, d_q, B, k, ix.scratch, d_scores, d_ids, s);
+}
+
 int32_t search_device_locked(bertx_index &ix, const float *d_q, int32_t B, int32_t k, float *d_scores, int32_t *d_ids,
                              hipStream_t s)
 {
     if (!d_q || !d_scores || !d_ids || B < 1 || k < 1 || k > kMaxK) return -1;
     Ordered o(ix.ord, s);
-    return launch_search(ix.rows, ix.scales, ix.storage, ix.n, ix.d, d_q, B, k, ix.scratch, d_scores, d_ids, s);
+    return search_launch(ix, d_q, B, k, d_scores, d_ids, s);
+}
+
+int32_t score_ids_device_locked(bertx_index &ix, const float *d_q, int32_t B, const int32_t *d_ids, int32_t n,
+                                float *d_scores, hipStream_t s)
+{
+    if (!d_q || !d_ids || !d_scores || B < 1 || n < 1 || n > kMaxK) return -1;
+    Ordered o(ix.ord, s);
+    return launch_index_score_ids(ix.rows, ix.scales, ix.storage, ix.n, ix.d, d_q, B, d_ids, n, d_scores, nullptr, s);
+}
+
+// What the two indexes of a rescored search must be to each other; a message otherwise.
+bool rescored_pair_ok(const bertx_index *coarse, const bertx_index *fine, const char *who)
+{
+    if (!coarse || !fine) return false;
+    if (coarse == fine) {
+        errorf("%s: coarse and fine are the same index\n", who);
+        return false;
+    }
+    if (coarse->d != fine->d || coarse->ordinal != fine->ordinal) {
+        errorf("%s: coarse (width %d, device %d) and fine (width %d, device %d) do not match\n", who, coarse->d,
+               coarse->ordinal, fine->d, fine->ordinal);
+        return false;
+    }
+    return true;
+}
+
+// Both indexes locked.  B walks in chunks of kStage: the coarse search for n_cand, the fine
+// index's scores of those ids (an id the fine index does not hold becomes the fill), the k
+// best of them.  The candidates lie in the coarse index's buffers.
+int32_t search_rescored_device_locked(bertx_index &coarse, bertx_index &fine, const float *d_q, int32_t B, int32_t k,
+                                      int32_t n_cand, float *d_scores, int32_t *d_ids, hipStream_t s)
+{
+    if (!d_q || !d_scores || !d_ids || B < 1 || k < 1 || k > n_cand || n_cand > kMaxK) return -1;
+    Ordered oc(coarse.ord, s), of(fine.ord, s);
+    for (int32_t b0 = 0; b0 < B; b0 += kStage) {
+        const int32_t m = std::min(kStage, B - b0);
+        const float *q = d_q + (size_t)b0 * coarse.d;
+        int rc = search_launch(coarse, q, m, n_cand, coarse.cand_s, coarse.cand_i, s);
+        if (rc == 0)
+            rc = launch_index_score_ids(fine.rows, fine.scales, fine.storage, fine.n, fine.d, q, m, coarse.cand_i, n_cand,
+                                        coarse.cand_exact, coarse.cand_kept, s);
+        if (rc == 0)
+            rc = launch_maxsim_rerank_select(coarse.cand_exact, coarse.cand_kept, m, n_cand, k, d_scores + (size_t)b0 * k,
+                                             d_ids + (size_t)b0 * k, s);
+        if (rc != 0) return rc;
+    }
+    return 0;
 }
 
 }  // namespace
 
 bertx_index *index_create_on(int ordinal, int d, int64_t capacity, int storage)
 {
-    if (storage != BERTX_INDEX_F16 && storage != BERTX_INDEX_I8) {
-        errorf("bertx_index_create: storage %d is neither BERTX_INDEX_F16 (0) nor BERTX_INDEX_I8 (1)\n", storage);
+    if (!kind_known(storage)) {
+        refuse_kind(storage);
         return nullptr;
     }
     if (capacity < 1 || capacity > 0x7ffffff0ll) {
@@ -109,15 +185,22 @@ bertx_index *index_create_on(int ordinal, int d, int64_t capacity, int storage)
     ix->cap = capacity;
     ix->storage = storage;
     const size_t padded = (size_t)((capacity + 15) / 16) * 16;
-    const size_t row_bytes = padded * (size_t)d * (storage == BERTX_INDEX_I8 ? 1 : 2);
-    const size_t scratch_bytes = (size_t)64 * (size_t)search_max_workgroups(capacity) * kMaxK * 8;
-    const bool ok = search_prepare_device() == 0 && hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking) == hipSuccess &&
+    const bool bin = storage == BERTX_INDEX_BIN;
+    const size_t row_bytes = bin ? search_bin_image_bytes(capacity, d) : padded * (size_t)d * (storage == BERTX_INDEX_I8 ? 1 : 2);
+    const size_t scratch_bytes =
+        (size_t)64 * (size_t)(bin ? search_bin_max_workgroups(capacity) : search_max_workgroups(capacity)) * kMaxK * 8;
+    const size_t cand_bytes = (size_t)kStage * kMaxK * 4;
+    const bool ok = (bin ? search_bin_prepare_device() : search_prepare_device()) == 0 && hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&ix->ord.done, hipEventDisableTiming) == hipSuccess &&
                     hipMalloc(&ix->rows, row_bytes) == hipSuccess && hipMalloc(&ix->scratch, scratch_bytes) == hipSuccess &&
                     (storage != BERTX_INDEX_I8 || hipMalloc((void **)&ix->scales, padded * 4) == hipSuccess) &&
                     hipMalloc((void **)&ix->st_rows, (size_t)kStage * d * 4) == hipSuccess &&
                     hipMalloc((void **)&ix->st_scores, (size_t)kStage * kMaxK * 4) == hipSuccess &&
-                    hipMalloc((void **)&ix->st_ids, (size_t)kStage * kMaxK * 4) == hipSuccess;
+                    hipMalloc((void **)&ix->st_ids, (size_t)kStage * kMaxK * 4) == hipSuccess &&
+                    hipMalloc((void **)&ix->cand_s, cand_bytes) == hipSuccess &&
+                    hipMalloc((void **)&ix->cand_exact, cand_bytes) == hipSuccess &&
+                    hipMalloc((void **)&ix->cand_i, cand_bytes) == hipSuccess &&
+                    hipMalloc((void **)&ix->cand_kept, cand_bytes) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         errorf("bertx_index_create: device %d could not allocate %zu bytes of rows (+ %zu of scratch)\n", ordinal,
@@ -145,8 +228,8 @@ struct bertx_index *bertx_index_create_ex(struct bert_ctx *ctx, int32_t slot, in
         emb::errorf("bertx_index_create: no context\n");
         return nullptr;
     }
-    if (storage != BERTX_INDEX_F16 && storage != BERTX_INDEX_I8) {
-        emb::errorf("bertx_index_create: storage %d is neither BERTX_INDEX_F16 (0) nor BERTX_INDEX_I8 (1)\n", storage);
+    if (!emb::kind_known(storage)) {
+        emb::refuse_kind(storage);
         return nullptr;
     }
     if (bertx_num_devices(ctx) == 0) {
@@ -238,6 +321,22 @@ static int32_t read_rows_i8(struct bertx_index *idx, int32_t first, int32_t n, s
     return 0;
 }
 
+// The bits of rows first .. first + n - 1 of a binary index (idx locked, the range checked)
+// out of bit order: bits uint8 [n][d / 8] in np.packbits order.
+static int32_t read_rows_bits(struct bertx_index *idx, int32_t first, int32_t n, std::vector<uint8_t> &bits)
+{
+    const int d = idx->d;
+    const int64_t g0 = first / 64, g1 = ((int64_t)first + n + 63) / 64;
+    const size_t group_words = (size_t)((d + 127) / 128) * 256;
+    std::vector<uint32_t> raw((size_t)(g1 - g0) * group_words);
+    bits.resize((size_t)n * (d / 8));
+    HIP_RC(idx->ord.wait());
+    HIP_RC(hipMemcpy(raw.data(), (const uint32_t *)idx->rows + (size_t)g0 * group_words, raw.size() * 4,
+                     hipMemcpyDeviceToHost));
+    emb::unpack_bin_rows(raw.data(), 64 * g0, first, n, d, bits.data());
+    return 0;
+}
+
 int32_t bertx_index_rows(struct bertx_index *idx, int32_t first, int32_t n, float *out)
 {
     if (!idx || !out || first < 0 || n < 1) return -1;
@@ -246,6 +345,14 @@ int32_t bertx_index_rows(struct bertx_index *idx, int32_t first, int32_t n, floa
     DeviceGuard g(idx->ordinal);
     HIP_RC(g.status());
     try {
+        if (idx->storage == BERTX_INDEX_BIN) {
+            std::vector<uint8_t> bits;
+            const int32_t rc = read_rows_bits(idx, first, n, bits);
+            if (rc != 0) return rc;
+            const size_t total = (size_t)n * idx->d;
+            for (size_t i = 0; i < total; ++i) out[i] = (bits[i >> 3] >> (7 - (i & 7))) & 1 ? 1.0f : -1.0f;
+            return 0;
+        }
         if (idx->storage == BERTX_INDEX_I8) {
             std::vector<int8_t> q;
             std::vector<float> scale;
@@ -287,6 +394,110 @@ int32_t bertx_index_rows_i8(struct bertx_index *idx, int32_t first, int32_t n, i
         std::memcpy(scale, hs.data(), hs.size() * 4);
     } catch (const std::bad_alloc &) {
         emb::errorf("bertx_index_rows_i8: out of host memory\n");
+        return -1;
+    }
+    return 0;
+}
+
+int32_t bertx_index_rows_bits(struct bertx_index *idx, int32_t first, int32_t n, uint8_t *out)
+{
+    if (!idx || !out || first < 0 || n < 1) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (idx->storage != BERTX_INDEX_BIN || (int64_t)first + n > idx->n) return -1;
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    try {
+        // the caller's output is written only once the copy has succeeded
+        std::vector<uint8_t> bits;
+        const int32_t rc = read_rows_bits(idx, first, n, bits);
+        if (rc != 0) return rc;
+        std::memcpy(out, bits.data(), bits.size());
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_index_rows_bits: out of host memory\n");
+        return -1;
+    }
+    return 0;
+}
+
+int32_t bertx_index_score_ids_device(struct bertx_index *idx, const float *d_queries, int32_t B, const int32_t *d_ids,
+                                     int32_t n, float *d_scores, void *stream)
+{
+    if (!idx) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    return emb::score_ids_device_locked(*idx, d_queries, B, d_ids, n, d_scores, stream ? (hipStream_t)stream : idx->stream);
+}
+
+int32_t bertx_index_score_ids(struct bertx_index *idx, const float *queries, int32_t B, const int32_t *ids, int32_t n,
+                              float *scores)
+{
+    if (!idx || !queries || !ids || !scores || B < 1 || n < 1 || n > emb::kMaxK) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    try {
+        // the caller's output is written only once every chunk has succeeded
+        std::vector<float> hs((size_t)B * n);
+        for (int32_t i = 0; i < B; i += emb::kStage) {
+            const int32_t m = std::min(emb::kStage, B - i);
+            HIP_RC(hipMemcpyAsync(idx->st_rows, queries + (size_t)i * idx->d, (size_t)m * idx->d * 4, hipMemcpyHostToDevice,
+                                  idx->stream));
+            HIP_RC(hipMemcpyAsync(idx->st_ids, ids + (size_t)i * n, (size_t)m * n * 4, hipMemcpyHostToDevice, idx->stream));
+            const int32_t rc = emb::score_ids_device_locked(*idx, idx->st_rows, m, idx->st_ids, n, idx->st_scores, idx->stream);
+            if (rc != 0) return rc;
+            HIP_RC(hipMemcpyAsync(hs.data() + (size_t)i * n, idx->st_scores, (size_t)m * n * 4, hipMemcpyDeviceToHost,
+                                  idx->stream));
+            HIP_RC(hipStreamSynchronize(idx->stream));
+        }
+        std::memcpy(scores, hs.data(), hs.size() * 4);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_index_score_ids: out of host memory\n");
+        return -1;
+    }
+    return 0;
+}
+
+int32_t bertx_index_search_rescored_device(struct bertx_index *coarse, struct bertx_index *fine, const float *d_queries,
+                                           int32_t B, int32_t k, int32_t n_cand, float *d_scores, int32_t *d_ids,
+                                           void *stream)
+{
+    if (!emb::rescored_pair_ok(coarse, fine, "bertx_index_search_rescored")) return -1;
+    std::scoped_lock lk(coarse->mu, fine->mu);   // both, in an order that cannot deadlock against the reverse pair
+    DeviceGuard g(coarse->ordinal);
+    HIP_RC(g.status());
+    return emb::search_rescored_device_locked(*coarse, *fine, d_queries, B, k, n_cand, d_scores, d_ids,
+                                              stream ? (hipStream_t)stream : coarse->stream);
+}
+
+int32_t bertx_index_search_rescored(struct bertx_index *coarse, struct bertx_index *fine, const float *queries, int32_t B,
+                                    int32_t k, int32_t n_cand, float *scores, int32_t *ids)
+{
+    if (!queries || !scores || !ids || B < 1 || k < 1 || k > n_cand || n_cand > emb::kMaxK) return -1;
+    if (!emb::rescored_pair_ok(coarse, fine, "bertx_index_search_rescored")) return -1;
+    std::scoped_lock lk(coarse->mu, fine->mu);
+    DeviceGuard g(coarse->ordinal);
+    HIP_RC(g.status());
+    try {
+        // the caller's outputs are written only once every chunk has succeeded
+        std::vector<float> hs((size_t)B * k);
+        std::vector<int32_t> hi((size_t)B * k);
+        hipStream_t s = coarse->stream;
+        for (int32_t i = 0; i < B; i += emb::kStage) {
+            const int32_t m = std::min(emb::kStage, B - i);
+            HIP_RC(hipMemcpyAsync(coarse->st_rows, queries + (size_t)i * coarse->d, (size_t)m * coarse->d * 4,
+                                  hipMemcpyHostToDevice, s));
+            const int32_t rc = emb::search_rescored_device_locked(*coarse, *fine, coarse->st_rows, m, k, n_cand,
+                                                                  coarse->st_scores, coarse->st_ids, s);
+            if (rc != 0) return rc;
+            HIP_RC(hipMemcpyAsync(hs.data() + (size_t)i * k, coarse->st_scores, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
+            HIP_RC(hipMemcpyAsync(hi.data() + (size_t)i * k, coarse->st_ids, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
+            HIP_RC(hipStreamSynchronize(s));
+        }
+        std::memcpy(scores, hs.data(), hs.size() * 4);
+        std::memcpy(ids, hi.data(), hi.size() * 4);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_index_search_rescored: out of host memory\n");
         return -1;
     }
     return 0;
@@ -387,6 +598,22 @@ int32_t bertx_index_search_texts(struct bertx_index *idx, struct bert_ctx *ctx, 
         return rc != 0 ? rc : bertx_index_search(idx, rows.data(), n, k, scores, ids);
     } catch (const std::exception &ex) {
         emb::errorf("bertx_index_search_texts: %s\n", ex.what());
+        return -1;
+    }
+}
+
+int32_t bertx_index_search_rescored_texts(struct bertx_index *coarse, struct bertx_index *fine, struct bert_ctx *ctx,
+                                          int32_t n_threads, int32_t n, const char **texts, int32_t k, int32_t n_cand,
+                                          float *scores, int32_t *ids)
+{
+    try {
+        if (!scores || !ids || k < 1 || k > n_cand || n_cand > emb::kMaxK) return -1;
+        if (!emb::rescored_pair_ok(coarse, fine, "bertx_index_search_rescored_texts")) return -1;
+        std::vector<float> rows;
+        const int32_t rc = encode_texts(coarse, ctx, n_threads, n, texts, rows, "bertx_index_search_rescored_texts");
+        return rc != 0 ? rc : bertx_index_search_rescored(coarse, fine, rows.data(), n, k, n_cand, scores, ids);
+    } catch (const std::exception &ex) {
+        emb::errorf("bertx_index_search_rescored_texts: %s\n", ex.what());
         return -1;
     }
 }

@@ -243,8 +243,39 @@ int launch_index_add(const float *d_rows, int64_t n, int d, int64_t first, int s
 // launch was refused.
 int launch_search(const void *corpus, const float *scales, int storage, int64_t n_rows, int d, const float *d_queries,
                   int B, int k, void *scratch, float *d_scores, int32_t *d_ids, hipStream_t s);
+// The second half of launch_search on its own, for the other scans that keep lists in its
+// layout: partial (score, id) pairs of 8 B, [nq][P][k], every list in the order of the
+// results with (-inf, -1) fill -> d_scores / d_ids [nq][k].  One workgroup per query.
+int launch_search_merge(const void *partial, int nq, int P, int k, float *d_scores, int32_t *d_ids, hipStream_t s);
 // Benches: out f32 [n][d] (device) = unit rows of hashed values.
 int launch_unit_rows(float *d_out, int64_t n, int d, uint32_t seed, hipStream_t s);
+
+// ---- binary storage of the embedding index (search_bin.hip; the layout, the binarizer
+// and the score: bin_bits.h; the contract: bert_hip.h "Binary storage") ----
+enum { SEARCH_BIN = 8 };   // = BERTX_INDEX_BIN
+// Once per process and device before the first launch_search_bin (the LDS attribute).
+int search_bin_prepare_device();
+// Bytes of the image of an index of this capacity: ceil(capacity / 64) groups of
+// ceil(d / 128) KiB.
+size_t search_bin_image_bytes(int64_t capacity_rows, int d);
+// The most workgroups a scan over an index of this capacity uses (current device); the
+// scratch of launch_search_bin holds 64 * that * 128 (score, id) pairs of 8 B.
+int64_t search_bin_max_workgroups(int64_t capacity_rows);
+// rows f32 [n][d] (device) -> the sign bits of rows first .. first + n - 1 of the image.
+int launch_index_add_bin(const float *d_rows, int64_t n, int d, int64_t first, void *corpus, hipStream_t s);
+// launch_search over a binary image: the score is d - 2 popcount(bits_q xor bits_row).
+// One scan kernel and the merge (launch_search_merge) per 64 queries.
+int launch_search_bin(const void *corpus, int64_t n_rows, int d, const float *d_queries, int B, int k, void *scratch,
+                      float *d_scores, int32_t *d_ids, hipStream_t s);
+
+// ---- scores of listed rows of the embedding index (search_rescore.hip), all three kinds ----
+// d_scores [B][n] = the score of (query b, row d_ids[b][n]) with the bits launch_search /
+// launch_search_bin give that pair, -inf for an id outside [0, n_rows).  d_ids_out (may be
+// null) [B][n]: the id, or -1 where the score is -inf for that reason.  1 <= n <= 128,
+// B >= 1; -1 otherwise (nothing launched), -3: launch refused.
+int launch_index_score_ids(const void *corpus, const float *scales, int storage, int64_t n_rows, int d,
+                           const float *d_queries, int B, const int32_t *d_ids, int n, float *d_scores,
+                           int32_t *d_ids_out, hipStream_t s);
 
 // ---- the token store of late interaction (maxsim.hip, mvindex.cpp): documents of len
 // token rows in the SEARCH_F16 fragment order, every document on a group boundary, and

@@ -461,6 +461,13 @@ int launch_search(const void *corpus, const float *scales, int storage, int64_t 
     return 0;
 }
 
+int launch_search_merge(const void *partial, int nq, int P, int k, float *d_scores, int32_t *d_ids, hipStream_t s)
+{
+    if (!partial || nq < 1 || P < 1 || k < 1 || k > 128) return -1;
+    search_merge_kernel<<<(unsigned)nq, kThreads, 0, s>>>((const Hit *)partial, P, k, d_scores, d_ids);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
 int launch_unit_rows(float *d_out, int64_t n, int d, uint32_t seed, hipStream_t s)
 {
     if (n <= 0 || d <= 0) return -1;

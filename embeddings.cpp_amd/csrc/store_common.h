@@ -81,4 +81,22 @@ inline void unpack_i8_rows(const int8_t *image, int64_t image_first, int64_t fir
     }
 }
 
+// The binary index's bit order (bin_bits.h): image holds whole 64-row groups of
+// ceil(w / 128) blocks, image_first a multiple of 64; element i of a row is bit i % 32 of
+// dword (i % 128) / 32 of the row's 16-B chunk i / 128.  out uint8 [n][w / 8] in np.packbits
+// order: element i is bit 7 - i % 8 of byte i / 8.
+inline void unpack_bin_rows(const uint32_t *image, int64_t image_first, int64_t first, int64_t n, int w, uint8_t *out)
+{
+    const size_t group_words = (size_t)((w + 127) / 128) * 256;
+    for (int64_t r = first; r < first + n; ++r) {
+        const uint32_t *grp = image + (size_t)((r - image_first) / 64) * group_words;
+        uint8_t *o = out + (size_t)(r - first) * (w / 8);
+        std::memset(o, 0, (size_t)(w / 8));
+        for (int i = 0; i < w; ++i) {
+            const uint32_t word = grp[((size_t)(i / 128) * 64 + (size_t)(r & 63)) * 4 + (i % 128) / 32];
+            if ((word >> (i % 32)) & 1) o[i / 8] |= (uint8_t)(0x80 >> (i % 8));
+        }
+    }
+}
+
 }  // namespace emb

@@ -2,13 +2,20 @@
 // corpus, then print the k closest texts of every query) with the corpus resident on
 // the GPU and the search fused there (bertx_index_*).
 //
-// usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8]
+// usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8|binary [-R f16|int8 [-B N]]]
 //               [-r RERANK_MODEL [-c N] | -l [-c N | -a [-C N [-c N]]] | -L COLBERT_MODEL [-M] [-c N | -a [-C N [-c N]]]]
 //               [-S f16|int8|res2|res4]
 // One text per line of CORPUS.txt; queries from stdin, one per line, `q` or EOF ends.
 // Per hit one line: rank<TAB>id<TAB>score<TAB>text.
 // -s: how the index stores its rows (bertx_index_create_ex): f16, the default, or int8
-// with one scale per row, half the bytes and a less precise first stage.
+// with one scale per row, half the bytes and a less precise first stage, or binary: a row
+// as its sign bits, one sixteenth of the bytes, searched by Hamming distance; the printed
+// score is then d - 2 hamming, an integer (bert_hip.h "Binary storage").
+// -R f16|int8: with -s binary, a second index of that kind is kept beside the binary one
+// and every query goes through bertx_index_search_rescored_texts: the binary index picks
+// -B candidates (default min(128, 4 K), K .. 128, K being k, or the -c value when a second
+// stage follows), the second index scores them and the K best by its scores go on.  -R or
+// -B without -s binary, and -B without -R, are usage errors.
 // -r: a second stage.  Per query the N best of the index (default 4 k, at most the
 // index's 128) are re-scored as (query, text) pairs by the cross-encoder RERANK_MODEL
 // (a model file with a classification head, bertx_rerank) and the k best of those are
@@ -60,6 +67,7 @@ int main(int argc, char **argv)
 {
     const char *model = nullptr, *corpus = nullptr, *rerank = nullptr, *colbert = nullptr;
     int k = 3, threads = 4, cand = 0, cents = 0, storage = BERTX_INDEX_F16, mv_storage = -1, res_storage = -1;
+    int fine_storage = -1, bin_cand = 0;
     bool late = false, all = false, no_mask_keys = false;
     for (int i = 1; i < argc; ++i) {
         const bool has = i + 1 < argc;
@@ -69,6 +77,10 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "-t") && has) threads = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "-s") && has && !std::strcmp(argv[i + 1], "f16")) { storage = BERTX_INDEX_F16; ++i; }
         else if (!std::strcmp(argv[i], "-s") && has && !std::strcmp(argv[i + 1], "int8")) { storage = BERTX_INDEX_I8; ++i; }
+        else if (!std::strcmp(argv[i], "-s") && has && !std::strcmp(argv[i + 1], "binary")) { storage = BERTX_INDEX_BIN; ++i; }
+        else if (!std::strcmp(argv[i], "-R") && has && !std::strcmp(argv[i + 1], "f16")) { fine_storage = BERTX_INDEX_F16; ++i; }
+        else if (!std::strcmp(argv[i], "-R") && has && !std::strcmp(argv[i + 1], "int8")) { fine_storage = BERTX_INDEX_I8; ++i; }
+        else if (!std::strcmp(argv[i], "-B") && has) { bin_cand = std::atoi(argv[++i]); if (bin_cand < 1) bin_cand = -1; }
         else if (!std::strcmp(argv[i], "-S") && has && !std::strcmp(argv[i + 1], "f16")) { mv_storage = BERTX_INDEX_F16; ++i; }
         else if (!std::strcmp(argv[i], "-S") && has && !std::strcmp(argv[i + 1], "int8")) { mv_storage = BERTX_INDEX_I8; ++i; }
         else if (!std::strcmp(argv[i], "-S") && has && (!std::strcmp(argv[i + 1], "res2") || !std::strcmp(argv[i + 1], "res4"))) {
@@ -89,10 +101,16 @@ int main(int argc, char **argv)
     const bool bad_all = (all && ((!late && !colbert) || (cand != 0 && cents == 0))) || (cents != 0 && !all) || cents < 0 ||
                          cents % 16 || cents > 65536;
     if (second && (!all || cents) && cand == 0) cand = std::min(128, 4 * k);
-    if (bad_all || !model || !corpus || k < 1 || k > 128 || threads < 1 || (int)(rerank != nullptr) + late + (colbert != nullptr) > 1 ||
+    // the rescored first stage: what it is asked for (K) and how many binary candidates it takes
+    const int first_k = second && !all ? cand : k;
+    const bool bad_bin = ((fine_storage >= 0 || bin_cand != 0) && (storage != BERTX_INDEX_BIN || all)) ||
+                         (bin_cand != 0 && fine_storage < 0);
+    if (fine_storage >= 0 && bin_cand == 0) bin_cand = std::min(128, 4 * first_k);
+    if (bad_bin || (fine_storage >= 0 && (bin_cand < first_k || bin_cand > 128)) || bad_all || !model || !corpus || k < 1 || k > 128 || threads < 1 || (int)(rerank != nullptr) + late + (colbert != nullptr) > 1 ||
         (second && (!all || cents) ? cand < k || cand > 128 : cand != 0) || (mv_storage >= 0 && !late && !colbert) ||
         (no_mask_keys && !colbert) || (res_storage >= 0 && cents == 0)) {
-        std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads] [-s f16|int8] "
+        std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads] "
+                             "[-s f16|int8|binary [-R f16|int8 (rescore the binary candidates) [-B N (K..128, default 4 K)]]] "
                              "[-r RERANK_MODEL [-c N (k..128, default 4 k)] | -l [-c N | -a [-C CENTROIDS [-c N]]] | "
                              "-L COLBERT_MODEL [-M] [-c N | -a [-C CENTROIDS [-c N]]]] "
                              "[-S f16|int8 (the token store of -l / -L) | res2|res4 (with -a -C)]\n",
@@ -146,7 +164,9 @@ int main(int argc, char **argv)
     }
     if (mv_storage < 0) mv_storage = BERTX_INDEX_F16;
     bertx_index *idx = all ? nullptr : bertx_index_create_ex(ctx, 0, (int32_t)texts.size(), storage);
-    if (!idx && !all) {
+    bertx_index *fine = idx && fine_storage >= 0 ? bertx_index_create_ex(ctx, 0, (int32_t)texts.size(), fine_storage) : nullptr;
+    if ((!idx && !all) || (fine_storage >= 0 && !fine)) {
+        bertx_index_free(idx);
         if (rctx) bert_free(rctx);
         bert_free(ctx);
         return 1;
@@ -164,6 +184,7 @@ int main(int argc, char **argv)
         }
         mv = bertx_mvindex_create_ex(ctx, 0, bert_n_embd(ctx), (int32_t)texts.size(), slots, mv_storage);
         if (!mv) {
+            bertx_index_free(fine);
             bertx_index_free(idx);
             bert_free(ctx);
             return 1;
@@ -174,6 +195,7 @@ int main(int argc, char **argv)
         const int64_t slots = (int64_t)texts.size() * ((doc_maxlen + 15) / 16 * 16);
         mv = bertx_mvindex_create_ex(rctx, 0, bertx_proj_width(rctx), (int32_t)texts.size(), slots, mv_storage);
         if (!mv) {
+            bertx_index_free(fine);
             bertx_index_free(idx);
             bert_free(rctx);
             bert_free(ctx);
@@ -186,7 +208,8 @@ int main(int argc, char **argv)
         for (size_t i = 0; i < texts.size() && rc == 0; i += 256) {
             std::vector<const char *> p;
             for (size_t j = i; j < texts.size() && j < i + 256; ++j) p.push_back(texts[j].c_str());
-            if (ix && bertx_index_add_texts(ix, ctx, threads, (int32_t)p.size(), p.data()) < 0) {
+            if (ix && (bertx_index_add_texts(ix, ctx, threads, (int32_t)p.size(), p.data()) < 0 ||
+                       (fine && bertx_index_add_texts(fine, ctx, threads, (int32_t)p.size(), p.data()) < 0))) {
                 std::fprintf(stderr, "search: indexing failed at text %zu\n", i);
                 rc = 1;
             } else if (to && (colbert ? bertx_mvindex_add_texts_colbert(to, rctx, threads, (int32_t)p.size(), p.data(), doc_maxlen)
@@ -249,7 +272,8 @@ int main(int argc, char **argv)
             std::fflush(stdout);
             continue;
         }
-        if (bertx_index_search_texts(idx, ctx, threads, 1, &qp, kq, scores.data(), ids.data()) != 0) {
+        if ((fine ? bertx_index_search_rescored_texts(idx, fine, ctx, threads, 1, &qp, kq, bin_cand, scores.data(), ids.data())
+                  : bertx_index_search_texts(idx, ctx, threads, 1, &qp, kq, scores.data(), ids.data())) != 0) {
             std::fprintf(stderr, "search: query failed\n");
             rc = 1;
             break;
@@ -306,6 +330,7 @@ int main(int argc, char **argv)
         std::fflush(stdout);
     }
     bertx_mvindex_free(mv);
+    bertx_index_free(fine);
     bertx_index_free(idx);
     if (rctx) bert_free(rctx);
     bert_free(ctx);

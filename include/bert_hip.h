@@ -439,11 +439,56 @@ BERT_API int32_t bertx_tokenize_batch(struct bert_ctx *ctx, int32_t n_threads, i
  * first .. first + n - 1, or -1 on an f16 index or a bad range with the outputs
  * untouched.
  *
+ * Binary storage.  BERTX_INDEX_BIN (8; the embedding index only, bertx_mvindex_create_ex
+ * refuses it) stores a row as its d sign bits, d / 8 bytes: one sixteenth of f16.  One
+ * rule for stored rows and for queries:
+ *   bit_i = 1 iff x_i > 0: +0, -0, negative values and NaN give 0; a positive subnormal
+ *   and +inf give 1 (sentence-transformers' `embeddings > 0`);
+ *   score(query, row) = d - 2 * popcount(bits_query xor bits_row), returned as f32.
+ * The score is an exact integer with |score| <= 1024, the dot product of the two +-1
+ * vectors, and depends on that query's and that row's bits only: not on the row's id, the
+ * row count or the other queries.  Ordering, fill and limits are those of the other kinds:
+ * scores descend, equal scores (the normal case here: at most d + 1 distinct values) come
+ * by ascending id, (-inf, -1) fill, 1 <= k <= 128, B >= 1, widths as above.  What the
+ * score is not: it is no cosine and carries no error bound against one.  For random sign
+ * patterns E[score / d] = 1 - 2 theta / pi, theta the angle of the two vectors; how well it
+ * ranks a model's embeddings is a property of the model.  Every bertx_index_* entry
+ * follows the kind with the same signature, refusals, ordering rules and capturability.
+ * bertx_index_rows returns +1.0 / -1.0, bertx_index_rows_i8 returns -1 as on f16, and
+ * bertx_index_rows_bits returns the stored bits uint8[n][d / 8] of rows first ..
+ * first + n - 1 in np.packbits order (element i is bit 7 - i % 8 of byte i / 8), or -1 on
+ * another kind or a bad range with the output untouched.
+ *
+ * Listed rows.  bertx_index_score_ids / _score_ids_device (every kind): queries
+ * float[B][d], ids int32[B][n], 1 <= n <= 128 -> scores float[B][n], scores[b][j] = the
+ * score of (query b, row ids[b][j]) with exactly the bits bertx_index_search gives that
+ * pair, -inf for an id outside [0, size); so the id output of a search, -1 fill included,
+ * can be passed as it is.  Refusals return a negative error with the output untouched.
+ * The device form follows bertx_index_search_device word for word.
+ *
+ * Two-stage search.  bertx_index_search_rescored / _device (coarse, fine, queries, B, k,
+ * n_cand, scores, ids), k <= n_cand <= 128, stated through the entries above:
+ *   cand = the ids of bertx_index_search(coarse, queries, n_cand);
+ *   s    = bertx_index_score_ids(fine, queries, cand);
+ *   a pair whose id is -1 or one fine does not hold (s = -inf for that reason) is the fill
+ *   (-inf, -1); the result is the k best (s, id) pairs in the order of the results, the
+ *   fill last.
+ * The result is that composition bit for bit; with n_cand >= size(coarse) it is
+ * bertx_index_search(fine, k) restricted to the rows coarse holds.  coarse and fine are
+ * different indexes of one width on one GPU, else -1 after a message; coarse may be of
+ * any kind (binary is the point), and so may fine.  Row ids correspond by insertion
+ * order: keeping the two in step is the caller's job.  The call is ordered behind the
+ * earlier operations on both indexes; the candidates lie in a buffer coarse got when it
+ * was created, so the device form allocates nothing, never synchronises and can be
+ * captured; two concurrent calls on the same coarse index are serialised.
+ * bertx_index_search_rescored_texts encodes as bertx_index_search_texts does.
+ *
  * Not provided: an index sharded over several GPUs, deleting rows, saving and
- * loading, f32 storage, f16 queries against int8 rows, 4-bit or binary storage,
- * rescoring against f16 copies.
+ * loading, f32 storage, f16 queries against int8 rows, 4-bit storage, binary rows
+ * against unbinarized queries (asymmetric scores), a fine copy kept in host memory.
  */
 enum { BERTX_INDEX_F16 = 0, BERTX_INDEX_I8 = 1 };
+enum { BERTX_INDEX_BIN = 8 };   /* the embedding index only: "Binary storage" above */
 struct bertx_index;
 BERT_API struct bertx_index *bertx_index_create(struct bert_ctx *ctx, int32_t slot, int32_t capacity_rows);
 BERT_API struct bertx_index *bertx_index_create_ex(struct bert_ctx *ctx, int32_t slot, int32_t capacity_rows,
@@ -466,6 +511,19 @@ BERT_API int32_t bertx_index_add_texts(struct bertx_index *idx, struct bert_ctx 
                                        const char **texts);
 BERT_API int32_t bertx_index_search_texts(struct bertx_index *idx, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
                                           const char **texts, int32_t k, float *scores, int32_t *ids);
+BERT_API int32_t bertx_index_rows_bits(struct bertx_index *idx, int32_t first, int32_t n, uint8_t *out);
+BERT_API int32_t bertx_index_score_ids(struct bertx_index *idx, const float *queries, int32_t B, const int32_t *ids,
+                                       int32_t n, float *scores);
+BERT_API int32_t bertx_index_score_ids_device(struct bertx_index *idx, const float *d_queries, int32_t B,
+                                              const int32_t *d_ids, int32_t n, float *d_scores, void *stream);
+BERT_API int32_t bertx_index_search_rescored(struct bertx_index *coarse, struct bertx_index *fine, const float *queries,
+                                             int32_t B, int32_t k, int32_t n_cand, float *scores, int32_t *ids);
+BERT_API int32_t bertx_index_search_rescored_device(struct bertx_index *coarse, struct bertx_index *fine,
+                                                    const float *d_queries, int32_t B, int32_t k, int32_t n_cand,
+                                                    float *d_scores, int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_index_search_rescored_texts(struct bertx_index *coarse, struct bertx_index *fine,
+                                                   struct bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts,
+                                                   int32_t k, int32_t n_cand, float *scores, int32_t *ids);
 
 /*
  * Token store: late interaction (ColBERT's MaxSim) over per-token vectors.  An
@@ -937,6 +995,15 @@ BERT_API int32_t bertx_bench_search_add_rate(int32_t d, int32_t N, double *add_r
 BERT_API int32_t bertx_bench_search_ex(int32_t d, int32_t N, int32_t B, int32_t k, int32_t storage, int32_t iters,
                                        float *avg_us);
 BERT_API int32_t bertx_bench_search_add_rate_ex(int32_t d, int32_t N, int32_t storage, double *add_rows_per_s);
+/*
+ * The two-stage search on the same data: a binary index and an index of kind `fine`
+ * (BERTX_INDEX_F16 or _I8) of the same N rows.  avg_us[0]: bertx_index_search_rescored_device
+ * (binary, fine, B, k, n_cand); avg_us[1]: bertx_index_score_ids_device on the fine index
+ * over the binary search's n_cand ids alone; avg_us[2]: the binary search for n_cand alone.
+ * Each the average device time of `iters` calls after 3 warm-up calls.
+ */
+BERT_API int32_t bertx_bench_search_rescored(int32_t d, int32_t N, int32_t B, int32_t k, int32_t n_cand, int32_t fine,
+                                             int32_t iters, float *avg_us);
 
 /*
  * Projection: ColBERT checkpoints (the `linear` record, the [Q] / [D] markers, [MASK]
