@@ -199,6 +199,23 @@ def load_lib(path=None):
         L.bertx_index_search_rescored.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, vp, vp]
         L.bertx_index_search_rescored_device.restype = c_i32
         L.bertx_index_search_rescored_device.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, vp, vp, vp]
+        L.bertx_index_remove.restype = c_i32
+        L.bertx_index_remove.argtypes = [vp, vp, c_i32]
+        L.bertx_index_remove_device.restype = c_i32
+        L.bertx_index_remove_device.argtypes = [vp, vp, c_i32, vp]
+        L.bertx_index_live.restype = c_i32
+        L.bertx_index_live.argtypes = [vp]
+        L.bertx_index_deleted.restype = c_i32
+        L.bertx_index_deleted.argtypes = [vp, c_i32, c_i32, vp]
+        L.bertx_index_search_filtered.restype = c_i32
+        L.bertx_index_search_filtered.argtypes = [vp, vp, c_i32, c_i32, vp, c_i32, c_i32, vp, vp]
+        L.bertx_index_search_filtered_device.restype = c_i32
+        L.bertx_index_search_filtered_device.argtypes = [vp, vp, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp]
+        L.bertx_index_search_rescored_filtered.restype = c_i32
+        L.bertx_index_search_rescored_filtered.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, vp]
+        L.bertx_index_search_rescored_filtered_device.restype = c_i32
+        L.bertx_index_search_rescored_filtered_device.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, vp,
+                                                                  vp]
         L.bertx_index_search_rescored_texts.restype = c_i32
         L.bertx_index_search_rescored_texts.argtypes = [vp, vp, vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p), c_i32,
                                                         c_i32, vp, vp]
@@ -743,12 +760,51 @@ class BertIndex:
             raise RuntimeError("bertx_index_add_texts failed (%d)" % rc)
         return rc
 
-    def search(self, queries, k):
-        """(scores f32 [B][k], ids i32 [B][k]) of the k best rows per query, best first."""
+    def remove(self, ids):
+        """Delete the listed rows: they are never returned again, their ids are not reused and
+        len() does not change.  Ids outside the index are ignored, repeats are harmless."""
+        a = np.ascontiguousarray(np.asarray(ids, np.int32).ravel())
+        rc = self.lib.bertx_index_remove(self.idx, a.ctypes.data, a.size)
+        if rc != 0:
+            raise RuntimeError("bertx_index_remove failed (%d)" % rc)
+
+    def live(self):
+        """len() minus the deleted rows."""
+        return int(self.lib.bertx_index_live(self.idx))
+
+    def deleted(self, first, n):
+        """bool [n]: whether rows first .. first + n - 1 are deleted."""
+        out = np.zeros(n, np.uint8)
+        if n and self.lib.bertx_index_deleted(self.idx, first, n, out.ctypes.data) != 0:
+            raise RuntimeError("bertx_index_deleted failed")
+        return out.astype(bool)
+
+    def _allow(self, allow, B):
+        """(words uint32 [n_filters][words] or None, n_filters, words) of allow= bool [size] or
+        [B][size]: 32 rows to a word, row r = bit r % 32 of word r / 32, padded to whole words."""
+        if allow is None:
+            return None, 0, 0
+        a = np.asarray(allow, bool)
+        size = len(self)
+        if a.shape not in ((size,), (B, size)):
+            raise ValueError("expected allow of shape (%d,) or (%d, %d), got %r" % (size, B, size, a.shape))
+        a = np.atleast_2d(a)
+        words = (size + 31) // 32
+        padded = np.zeros((a.shape[0], 32 * words), bool)
+        padded[:, :size] = a
+        packed = np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view(np.uint32)
+        return packed.reshape(a.shape[0], words), a.shape[0], words
+
+    def search(self, queries, k, allow=None):
+        """(scores f32 [B][k], ids i32 [B][k]) of the k best rows per query, best first.  Deleted
+        rows are never returned; allow (bool [size], or [B][size] for one filter per query)
+        limits the search to the rows it marks."""
         q = self._rows(queries)
         scores = np.zeros((q.shape[0], k), np.float32)
         ids = np.zeros((q.shape[0], k), np.int32)
-        rc = self.lib.bertx_index_search(self.idx, q.ctypes.data, q.shape[0], k, scores.ctypes.data, ids.ctypes.data)
+        f, nf, words = self._allow(allow, q.shape[0])
+        rc = self.lib.bertx_index_search_filtered(self.idx, q.ctypes.data, q.shape[0], k, None if f is None else f.ctypes.data,
+                                                  nf, words, scores.ctypes.data, ids.ctypes.data)
         if rc != 0:
             raise RuntimeError("bertx_index_search failed (%d)" % rc)
         return scores, ids
@@ -798,16 +854,18 @@ class BertIndex:
     def _n_cand(k, n_cand):
         return min(128, 4 * k) if n_cand is None else n_cand
 
-    def search_rescored(self, queries, k, fine, n_cand=None):
+    def search_rescored(self, queries, k, fine, n_cand=None, allow=None):
         """The two-stage search: this index finds n_cand candidates per query (default
         min(128, 4 k)), `fine` (another BertIndex of the same width whose rows were added in
         the same order) scores them, the k best by fine's scores come back.  Bit for bit
-        search(n_cand) -> fine.score_ids -> the order of the results."""
+        search(n_cand, allow) -> fine.score_ids -> the order of the results."""
         q = self._rows(queries)
         scores = np.zeros((q.shape[0], k), np.float32)
         ids = np.zeros((q.shape[0], k), np.int32)
-        rc = self.lib.bertx_index_search_rescored(self.idx, fine.idx, q.ctypes.data, q.shape[0], k, self._n_cand(k, n_cand),
-                                                  scores.ctypes.data, ids.ctypes.data)
+        f, nf, words = self._allow(allow, q.shape[0])
+        rc = self.lib.bertx_index_search_rescored_filtered(self.idx, fine.idx, q.ctypes.data, q.shape[0], k,
+                                                           self._n_cand(k, n_cand), None if f is None else f.ctypes.data, nf,
+                                                           words, scores.ctypes.data, ids.ctypes.data)
         if rc != 0:
             raise RuntimeError("bertx_index_search_rescored failed (%d)" % rc)
         return scores, ids

@@ -27,6 +27,12 @@ struct bertx_index {
     int64_t cap = 0, n = 0;
     void *rows = nullptr;        // f16 or int8: ceil(cap / 16) groups in fragment order; binary: ceil(cap / 64) in bit order
     float *scales = nullptr;     // int8: one per row of the padded capacity
+    // the tombstones (index_mask.hip): bit r % 32 of word r / 32 is 1 once row r was removed;
+    // `removed`: some remove was accepted since creation or the last clear, so searches take
+    // the masked kernels (read at launch time, as n is)
+    uint32_t *tomb = nullptr;
+    int64_t tomb_words = 0;
+    bool removed = false;
     void *scratch = nullptr;     // partial lists of one search launch
     // the rescored search's candidates, kStage queries at a time, [kStage][128] each: what this
     // index (as the coarse one) found, and what the fine index made of it
@@ -46,6 +52,7 @@ struct bertx_index {
         if (stream) (void)hipStreamSynchronize(stream);
         if (rows) (void)hipFree(rows);
         if (scales) (void)hipFree(scales);
+        if (tomb) (void)hipFree(tomb);
         if (scratch) (void)hipFree(scratch);
         if (st_rows) (void)hipFree(st_rows);
         if (st_scores) (void)hipFree(st_scores);
@@ -64,6 +71,36 @@ namespace {
 
 constexpr int kStage = 256;   // rows / queries per staged chunk of the host forms
 constexpr int kMaxK = 128;
+constexpr int kStageIds = kStage * kMaxK;   // int32 values the id staging buffer holds
+
+// The filters of one search (device memory): none (d null, n 0), one for every query
+// (stride 0) or one per query, `stride` words apart.
+struct Filters {
+    const uint32_t *d = nullptr;
+    int64_t stride = 0;
+    Filters from(int64_t query) const
+    {
+        Filters f = *this;
+        if (f.d) f.d += (size_t)query * (size_t)stride;
+        return f;
+    }
+};
+
+// What bertx_index_search_filtered accepts (idx locked): no filter as (NULL, 0), else 1 or B
+// filters of at least ceil(size / 32) words.
+bool filters_ok(const bertx_index &ix, const void *filters, int32_t n_filters, int32_t words, int32_t B)
+{
+    if (!filters || n_filters == 0) return !filters && n_filters == 0;
+    return (n_filters == 1 || n_filters == B) && (int64_t)words >= (ix.n + 31) / 32;
+}
+
+Filters filters_of(const uint32_t *d_filters, int32_t n_filters, int32_t words)
+{
+    Filters f;
+    f.d = d_filters;
+    f.stride = n_filters > 1 ? words : 0;
+    return f;
+}
 
 bool kind_known(int storage)
 {
@@ -95,19 +132,41 @@ int32_t add_device_locked(bertx_index &ix, const float *d_rows, int32_t n, hipSt
     return first;
 }
 
-// the search of the index's kind on s (idx locked; the caller orders it)
-int search_launch(bertx_index &ix, const float *d_q, int32_t B, int32_t k, float *d_scores, int32_t *d_ids, hipStream_t s)
+// the search of the index's kind on s (idx locked; the caller orders it): the unmasked
+// kernels while nothing was removed and no filter is given, else the masked ones
+int search_launch(bertx_index &ix, const float *d_q, int32_t B, int32_t k, float *d_scores, int32_t *d_ids, hipStream_t s,
+                  const Filters &f)
 {
-    if (ix.storage == BERTX_INDEX_BIN) return launch_search_bin(ix.rows, ix.n, ix.d, d_q, B, k, ix.scratch, d_scores, d_ids, s);
-    return launch_search(ix.rows, ix.scales, ix.storage, ix.n, ix.d, d_q, B, k, ix.scratch, d_scores, d_ids, s);
+    const SearchMask mask{ix.tomb, f.d, f.stride};
+    const SearchMask *m = ix.removed || f.d ? &mask : nullptr;
+    if (ix.storage == BERTX_INDEX_BIN)
+        return launch_search_bin(ix.rows, ix.n, ix.d, d_q, B, k, ix.scratch, d_scores, d_ids, s, m);
+    return launch_search(ix.rows, ix.scales, ix.storage, ix.n, ix.d, d_q, B, k, ix.scratch, d_scores, d_ids, s, m);
+}
+
+// the scorer of listed rows on s (idx locked; the caller orders it): a deleted row as an id the index does not hold
+int score_ids_launch(bertx_index &ix, const float *d_q, int32_t B, const int32_t *d_ids, int32_t n, float *d_scores,
+                     int32_t *d_kept, hipStream_t s)
+{
+    return launch_index_score_ids(ix.rows, ix.scales, ix.storage, ix.n, ix.d, d_q, B, d_ids, n, d_scores, d_kept, s,
+                                  ix.removed ? ix.tomb : nullptr);
 }
 
 int32_t search_device_locked(bertx_index &ix, const float *d_q, int32_t B, int32_t k, float *d_scores, int32_t *d_ids,
-                             hipStream_t s)
+                             hipStream_t s, const Filters &f = Filters())
 {
     if (!d_q || !d_scores || !d_ids || B < 1 || k < 1 || k > kMaxK) return -1;
     Ordered o(ix.ord, s);
-    return search_launch(ix, d_q, B, k, d_scores, d_ids, s);
+    return search_launch(ix, d_q, B, k, d_scores, d_ids, s, f);
+}
+
+int32_t remove_device_locked(bertx_index &ix, const int32_t *d_ids, int32_t n, hipStream_t s)
+{
+    if (!d_ids || n < 1) return -1;
+    Ordered o(ix.ord, s);
+    const int rc = launch_index_remove(d_ids, n, ix.n, ix.tomb, s);
+    if (rc == 0) ix.removed = true;
+    return rc;
 }
 
 int32_t score_ids_device_locked(bertx_index &ix, const float *d_q, int32_t B, const int32_t *d_ids, int32_t n,
@@ -115,7 +174,7 @@ int32_t score_ids_device_locked(bertx_index &ix, const float *d_q, int32_t B, co
 {
     if (!d_q || !d_ids || !d_scores || B < 1 || n < 1 || n > kMaxK) return -1;
     Ordered o(ix.ord, s);
-    return launch_index_score_ids(ix.rows, ix.scales, ix.storage, ix.n, ix.d, d_q, B, d_ids, n, d_scores, nullptr, s);
+    return score_ids_launch(ix, d_q, B, d_ids, n, d_scores, nullptr, s);
 }
 
 // What the two indexes of a rescored search must be to each other; a message otherwise.
@@ -134,21 +193,21 @@ bool rescored_pair_ok(const bertx_index *coarse, const bertx_index *fine, const 
     return true;
 }
 
-// Both indexes locked.  B walks in chunks of kStage: the coarse search for n_cand, the fine
-// index's scores of those ids (an id the fine index does not hold becomes the fill), the k
-// best of them.  The candidates lie in the coarse index's buffers.
+// Both indexes locked.  B walks in chunks of kStage: the coarse search for n_cand (its
+// tombstones and the filters limit the candidates), the fine index's scores of those ids (an
+// id the fine index does not hold, or has deleted, becomes the fill), the k best of them.
+// The candidates lie in the coarse index's buffers.
 int32_t search_rescored_device_locked(bertx_index &coarse, bertx_index &fine, const float *d_q, int32_t B, int32_t k,
-                                      int32_t n_cand, float *d_scores, int32_t *d_ids, hipStream_t s)
+                                      int32_t n_cand, float *d_scores, int32_t *d_ids, hipStream_t s,
+                                      const Filters &f = Filters())
 {
     if (!d_q || !d_scores || !d_ids || B < 1 || k < 1 || k > n_cand || n_cand > kMaxK) return -1;
     Ordered oc(coarse.ord, s), of(fine.ord, s);
     for (int32_t b0 = 0; b0 < B; b0 += kStage) {
         const int32_t m = std::min(kStage, B - b0);
         const float *q = d_q + (size_t)b0 * coarse.d;
-        int rc = search_launch(coarse, q, m, n_cand, coarse.cand_s, coarse.cand_i, s);
-        if (rc == 0)
-            rc = launch_index_score_ids(fine.rows, fine.scales, fine.storage, fine.n, fine.d, q, m, coarse.cand_i, n_cand,
-                                        coarse.cand_exact, coarse.cand_kept, s);
+        int rc = search_launch(coarse, q, m, n_cand, coarse.cand_s, coarse.cand_i, s, f.from(b0));
+        if (rc == 0) rc = score_ids_launch(fine, q, m, coarse.cand_i, n_cand, coarse.cand_exact, coarse.cand_kept, s);
         if (rc == 0)
             rc = launch_maxsim_rerank_select(coarse.cand_exact, coarse.cand_kept, m, n_cand, k, d_scores + (size_t)b0 * k,
                                              d_ids + (size_t)b0 * k, s);
@@ -190,6 +249,7 @@ bertx_index *index_create_on(int ordinal, int d, int64_t capacity, int storage)
     const size_t scratch_bytes =
         (size_t)64 * (size_t)(bin ? search_bin_max_workgroups(capacity) : search_max_workgroups(capacity)) * kMaxK * 8;
     const size_t cand_bytes = (size_t)kStage * kMaxK * 4;
+    ix->tomb_words = index_mask_words(capacity);
     const bool ok = (bin ? search_bin_prepare_device() : search_prepare_device()) == 0 && hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&ix->ord.done, hipEventDisableTiming) == hipSuccess &&
                     hipMalloc(&ix->rows, row_bytes) == hipSuccess && hipMalloc(&ix->scratch, scratch_bytes) == hipSuccess &&
@@ -200,7 +260,10 @@ bertx_index *index_create_on(int ordinal, int d, int64_t capacity, int storage)
                     hipMalloc((void **)&ix->cand_s, cand_bytes) == hipSuccess &&
                     hipMalloc((void **)&ix->cand_exact, cand_bytes) == hipSuccess &&
                     hipMalloc((void **)&ix->cand_i, cand_bytes) == hipSuccess &&
-                    hipMalloc((void **)&ix->cand_kept, cand_bytes) == hipSuccess;
+                    hipMalloc((void **)&ix->cand_kept, cand_bytes) == hipSuccess &&
+                    hipMalloc((void **)&ix->tomb, (size_t)ix->tomb_words * 4) == hipSuccess &&
+                    hipMemsetAsync(ix->tomb, 0, (size_t)ix->tomb_words * 4, ix->stream) == hipSuccess &&
+                    hipStreamSynchronize(ix->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         errorf("bertx_index_create: device %d could not allocate %zu bytes of rows (+ %zu of scratch)\n", ordinal,
@@ -252,6 +315,14 @@ int32_t bertx_index_clear(struct bertx_index *idx)
     std::lock_guard<std::mutex> lk(idx->mu);
     // (no wait for the device, unlike the token store's clear: the index keeps no host image
     // that a copy in flight could still read, and the next add is ordered behind every search)
+    if (idx->removed) {
+        // the tombstones back to zero, ordered behind every operation so far
+        DeviceGuard g(idx->ordinal);
+        HIP_RC(g.status());
+        emb::Ordered o(idx->ord, idx->stream);
+        HIP_RC(hipMemsetAsync(idx->tomb, 0, (size_t)idx->tomb_words * 4, idx->stream));
+        idx->removed = false;
+    }
     idx->n = 0;
     return 0;
 }
@@ -458,27 +529,56 @@ int32_t bertx_index_score_ids(struct bertx_index *idx, const float *queries, int
     return 0;
 }
 
+// The filters of a host call, uint32 [n_filters][words], staged in a device buffer of the
+// call's own (idx locked, its device current); the copy is ordered on the index's stream.
+static int32_t stage_filters(struct bertx_index *idx, const uint32_t *filters, int32_t n_filters, int32_t words,
+                             emb::DevBuf &buf)
+{
+    if (!filters) return 0;
+    const size_t bytes = (size_t)n_filters * (size_t)words * 4;
+    HIP_RC(hipMalloc(&buf.p, std::max<size_t>(bytes, 4)));
+    if (bytes) HIP_RC(hipMemcpyAsync(buf.p, filters, bytes, hipMemcpyHostToDevice, idx->stream));
+    return 0;
+}
+
+int32_t bertx_index_search_rescored_filtered_device(struct bertx_index *coarse, struct bertx_index *fine,
+                                                    const float *d_queries, int32_t B, int32_t k, int32_t n_cand,
+                                                    const uint32_t *d_filters, int32_t n_filters, int32_t words,
+                                                    float *d_scores, int32_t *d_ids, void *stream)
+{
+    if (!emb::rescored_pair_ok(coarse, fine, "bertx_index_search_rescored")) return -1;
+    std::scoped_lock lk(coarse->mu, fine->mu);   // both, in an order that cannot deadlock against the reverse pair
+    if (!emb::filters_ok(*coarse, d_filters, n_filters, words, B)) return -1;
+    DeviceGuard g(coarse->ordinal);
+    HIP_RC(g.status());
+    return emb::search_rescored_device_locked(*coarse, *fine, d_queries, B, k, n_cand, d_scores, d_ids,
+                                              stream ? (hipStream_t)stream : coarse->stream,
+                                              emb::filters_of(d_filters, n_filters, words));
+}
+
 int32_t bertx_index_search_rescored_device(struct bertx_index *coarse, struct bertx_index *fine, const float *d_queries,
                                            int32_t B, int32_t k, int32_t n_cand, float *d_scores, int32_t *d_ids,
                                            void *stream)
 {
-    if (!emb::rescored_pair_ok(coarse, fine, "bertx_index_search_rescored")) return -1;
-    std::scoped_lock lk(coarse->mu, fine->mu);   // both, in an order that cannot deadlock against the reverse pair
-    DeviceGuard g(coarse->ordinal);
-    HIP_RC(g.status());
-    return emb::search_rescored_device_locked(*coarse, *fine, d_queries, B, k, n_cand, d_scores, d_ids,
-                                              stream ? (hipStream_t)stream : coarse->stream);
+    return bertx_index_search_rescored_filtered_device(coarse, fine, d_queries, B, k, n_cand, nullptr, 0, 0, d_scores, d_ids,
+                                                       stream);
 }
 
-int32_t bertx_index_search_rescored(struct bertx_index *coarse, struct bertx_index *fine, const float *queries, int32_t B,
-                                    int32_t k, int32_t n_cand, float *scores, int32_t *ids)
+int32_t bertx_index_search_rescored_filtered(struct bertx_index *coarse, struct bertx_index *fine, const float *queries,
+                                             int32_t B, int32_t k, int32_t n_cand, const uint32_t *filters,
+                                             int32_t n_filters, int32_t words, float *scores, int32_t *ids)
 {
     if (!queries || !scores || !ids || B < 1 || k < 1 || k > n_cand || n_cand > emb::kMaxK) return -1;
     if (!emb::rescored_pair_ok(coarse, fine, "bertx_index_search_rescored")) return -1;
     std::scoped_lock lk(coarse->mu, fine->mu);
+    if (!emb::filters_ok(*coarse, filters, n_filters, words, B)) return -1;
     DeviceGuard g(coarse->ordinal);
     HIP_RC(g.status());
+    emb::DevBuf fbuf;   // (freed after the last chunk's synchronise)
     try {
+        const int32_t frc = stage_filters(coarse, filters, n_filters, words, fbuf);
+        if (frc != 0) return frc;
+        const emb::Filters f = emb::filters_of((const uint32_t *)fbuf.p, n_filters, words);
         // the caller's outputs are written only once every chunk has succeeded
         std::vector<float> hs((size_t)B * k);
         std::vector<int32_t> hi((size_t)B * k);
@@ -488,7 +588,7 @@ int32_t bertx_index_search_rescored(struct bertx_index *coarse, struct bertx_ind
             HIP_RC(hipMemcpyAsync(coarse->st_rows, queries + (size_t)i * coarse->d, (size_t)m * coarse->d * 4,
                                   hipMemcpyHostToDevice, s));
             const int32_t rc = emb::search_rescored_device_locked(*coarse, *fine, coarse->st_rows, m, k, n_cand,
-                                                                  coarse->st_scores, coarse->st_ids, s);
+                                                                  coarse->st_scores, coarse->st_ids, s, f.from(i));
             if (rc != 0) return rc;
             HIP_RC(hipMemcpyAsync(hs.data() + (size_t)i * k, coarse->st_scores, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
             HIP_RC(hipMemcpyAsync(hi.data() + (size_t)i * k, coarse->st_ids, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
@@ -503,24 +603,44 @@ int32_t bertx_index_search_rescored(struct bertx_index *coarse, struct bertx_ind
     return 0;
 }
 
-int32_t bertx_index_search_device(struct bertx_index *idx, const float *d_queries, int32_t B, int32_t k,
-                                  float *d_scores, int32_t *d_ids, void *stream)
+int32_t bertx_index_search_rescored(struct bertx_index *coarse, struct bertx_index *fine, const float *queries, int32_t B,
+                                    int32_t k, int32_t n_cand, float *scores, int32_t *ids)
+{
+    return bertx_index_search_rescored_filtered(coarse, fine, queries, B, k, n_cand, nullptr, 0, 0, scores, ids);
+}
+
+int32_t bertx_index_search_filtered_device(struct bertx_index *idx, const float *d_queries, int32_t B, int32_t k,
+                                           const uint32_t *d_filters, int32_t n_filters, int32_t words, float *d_scores,
+                                           int32_t *d_ids, void *stream)
 {
     if (!idx) return -1;
     std::lock_guard<std::mutex> lk(idx->mu);
+    if (!emb::filters_ok(*idx, d_filters, n_filters, words, B)) return -1;
     DeviceGuard g(idx->ordinal);
     HIP_RC(g.status());
-    return emb::search_device_locked(*idx, d_queries, B, k, d_scores, d_ids, stream ? (hipStream_t)stream : idx->stream);
+    return emb::search_device_locked(*idx, d_queries, B, k, d_scores, d_ids, stream ? (hipStream_t)stream : idx->stream,
+                                     emb::filters_of(d_filters, n_filters, words));
 }
 
-int32_t bertx_index_search(struct bertx_index *idx, const float *queries, int32_t B, int32_t k, float *scores,
-                           int32_t *ids)
+int32_t bertx_index_search_device(struct bertx_index *idx, const float *d_queries, int32_t B, int32_t k,
+                                  float *d_scores, int32_t *d_ids, void *stream)
+{
+    return bertx_index_search_filtered_device(idx, d_queries, B, k, nullptr, 0, 0, d_scores, d_ids, stream);
+}
+
+int32_t bertx_index_search_filtered(struct bertx_index *idx, const float *queries, int32_t B, int32_t k,
+                                    const uint32_t *filters, int32_t n_filters, int32_t words, float *scores, int32_t *ids)
 {
     if (!idx || !queries || !scores || !ids || B < 1 || k < 1 || k > emb::kMaxK) return -1;
     std::lock_guard<std::mutex> lk(idx->mu);
+    if (!emb::filters_ok(*idx, filters, n_filters, words, B)) return -1;
     DeviceGuard g(idx->ordinal);
     HIP_RC(g.status());
+    emb::DevBuf fbuf;   // (freed after the last chunk's synchronise)
     try {
+        const int32_t frc = stage_filters(idx, filters, n_filters, words, fbuf);
+        if (frc != 0) return frc;
+        const emb::Filters f = emb::filters_of((const uint32_t *)fbuf.p, n_filters, words);
         // the caller's outputs are written only once every chunk has succeeded
         std::vector<float> hs((size_t)B * k);
         std::vector<int32_t> hi((size_t)B * k);
@@ -528,7 +648,8 @@ int32_t bertx_index_search(struct bertx_index *idx, const float *queries, int32_
             const int32_t m = std::min(emb::kStage, B - i);
             HIP_RC(hipMemcpyAsync(idx->st_rows, queries + (size_t)i * idx->d, (size_t)m * idx->d * 4, hipMemcpyHostToDevice,
                                   idx->stream));
-            const int32_t rc = emb::search_device_locked(*idx, idx->st_rows, m, k, idx->st_scores, idx->st_ids, idx->stream);
+            const int32_t rc = emb::search_device_locked(*idx, idx->st_rows, m, k, idx->st_scores, idx->st_ids, idx->stream,
+                                                         f.from(i));
             if (rc != 0) return rc;
             HIP_RC(hipMemcpyAsync(hs.data() + (size_t)i * k, idx->st_scores, (size_t)m * k * 4, hipMemcpyDeviceToHost,
                                   idx->stream));
@@ -540,6 +661,84 @@ int32_t bertx_index_search(struct bertx_index *idx, const float *queries, int32_
         std::memcpy(ids, hi.data(), hi.size() * 4);
     } catch (const std::bad_alloc &) {
         emb::errorf("bertx_index_search: out of host memory\n");
+        return -1;
+    }
+    return 0;
+}
+
+int32_t bertx_index_search(struct bertx_index *idx, const float *queries, int32_t B, int32_t k, float *scores,
+                           int32_t *ids)
+{
+    return bertx_index_search_filtered(idx, queries, B, k, nullptr, 0, 0, scores, ids);
+}
+
+int32_t bertx_index_remove_device(struct bertx_index *idx, const int32_t *d_ids, int32_t n, void *stream)
+{
+    if (!idx) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    return emb::remove_device_locked(*idx, d_ids, n, stream ? (hipStream_t)stream : idx->stream);
+}
+
+int32_t bertx_index_remove(struct bertx_index *idx, const int32_t *ids, int32_t n)
+{
+    if (!idx || !ids || n < 1) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    for (int32_t i = 0; i < n; i += emb::kStageIds) {
+        const int32_t m = std::min(emb::kStageIds, n - i);
+        HIP_RC(hipMemcpyAsync(idx->st_ids, ids + i, (size_t)m * 4, hipMemcpyHostToDevice, idx->stream));
+        const int32_t rc = emb::remove_device_locked(*idx, idx->st_ids, m, idx->stream);
+        if (rc != 0) return rc;
+        HIP_RC(hipStreamSynchronize(idx->stream));   // the staging buffer is reused
+    }
+    return 0;
+}
+
+int32_t bertx_index_live(struct bertx_index *idx)
+{
+    if (!idx) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    int32_t dead = 0;
+    {
+        emb::Ordered o(idx->ord, idx->stream);
+        const int rc = emb::launch_index_count_deleted(idx->tomb, idx->n, idx->st_ids, idx->stream);
+        if (rc != 0) return rc;
+        HIP_RC(hipMemcpyAsync(&dead, idx->st_ids, 4, hipMemcpyDeviceToHost, idx->stream));
+    }
+    HIP_RC(hipStreamSynchronize(idx->stream));
+    return (int32_t)idx->n - dead;
+}
+
+int32_t bertx_index_deleted(struct bertx_index *idx, int32_t first, int32_t n, uint8_t *out)
+{
+    if (!idx || !out || first < 0 || n < 1) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if ((int64_t)first + n > idx->n) return -1;
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    try {
+        // the caller's output is written only once every chunk has succeeded
+        std::vector<uint8_t> flags((size_t)n);
+        constexpr int32_t kChunk = emb::kStageIds * 4;   // bytes of the id staging buffer, one flag each
+        for (int32_t i = 0; i < n; i += kChunk) {
+            const int32_t m = std::min(kChunk, n - i);
+            {
+                emb::Ordered o(idx->ord, idx->stream);
+                const int rc = emb::launch_index_deleted_flags(idx->tomb, (int64_t)first + i, m, (uint8_t *)idx->st_ids,
+                                                               idx->stream);
+                if (rc != 0) return rc;
+                HIP_RC(hipMemcpyAsync(flags.data() + i, idx->st_ids, (size_t)m, hipMemcpyDeviceToHost, idx->stream));
+            }
+            HIP_RC(hipStreamSynchronize(idx->stream));
+        }
+        std::memcpy(out, flags.data(), flags.size());
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_index_deleted: out of host memory\n");
         return -1;
     }
     return 0;

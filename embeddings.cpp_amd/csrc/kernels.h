@@ -219,6 +219,17 @@ int launch_q8_gemm(const DevWeight &W, const int8_t *xq, const float *xd, const 
 // lane 16g + f = row f, bytes 16g .. 16g + 15, and a second buffer of one f32 scale per
 // row (the arithmetic: bert_hip.h, search.hip quantize_row_i8 / score_i8) ----
 enum { SEARCH_F16 = 0, SEARCH_I8 = 1 };   // = BERTX_INDEX_F16 / _I8
+// The row masks of a masked search (index_mask.hip; bert_hip.h "Deleting rows and filtered
+// search"): 32 rows to a uint32_t word, row r = bit r % 32 of word r / 32.  A row is offered
+// iff it is < n_rows, its bit in tomb is 0 and its bit in the query's filter is 1.
+struct SearchMask {
+    const uint32_t *tomb;    // the index's tombstones, index_mask_words(capacity) words
+    const uint32_t *filt;    // null: no filter; else at least ceil(n_rows / 32) words per filter
+    int64_t stride;          // words from one query's filter to the next; 0: one filter for all
+};
+// (the masked kernels take the mask as a template parameter pack of none or one)
+constexpr const SearchMask &first_mask(const SearchMask &m) { return m; }
+constexpr const uint32_t *first_tomb(const uint32_t *t) { return t; }
 // Once per process and device (the calling thread's current one) before the first
 // launch_search: lets the search kernels use the CU's whole LDS.  Returns 0 or -1.
 int search_prepare_device();
@@ -241,8 +252,11 @@ int launch_index_add(const float *d_rows, int64_t n, int d, int64_t first, int s
 // of search_group_queries queries.  scales: the int8 rows' scales (not read for f16).
 // 1 <= k <= 128, B >= 1; returns -1 for bad arguments (nothing launched), -3 when a
 // launch was refused.
+// mask (may be null): the masked kernels, which offer a row only when it is admissible as
+// well; null launches the unmasked instantiations with the arguments above and nothing else.
 int launch_search(const void *corpus, const float *scales, int storage, int64_t n_rows, int d, const float *d_queries,
-                  int B, int k, void *scratch, float *d_scores, int32_t *d_ids, hipStream_t s);
+                  int B, int k, void *scratch, float *d_scores, int32_t *d_ids, hipStream_t s,
+                  const SearchMask *mask = nullptr);
 // The second half of launch_search on its own, for the other scans that keep lists in its
 // layout: partial (score, id) pairs of 8 B, [nq][P][k], every list in the order of the
 // results with (-inf, -1) fill -> d_scores / d_ids [nq][k].  One workgroup per query.
@@ -266,16 +280,29 @@ int launch_index_add_bin(const float *d_rows, int64_t n, int d, int64_t first, v
 // launch_search over a binary image: the score is d - 2 popcount(bits_q xor bits_row).
 // One scan kernel and the merge (launch_search_merge) per 64 queries.
 int launch_search_bin(const void *corpus, int64_t n_rows, int d, const float *d_queries, int B, int k, void *scratch,
-                      float *d_scores, int32_t *d_ids, hipStream_t s);
+                      float *d_scores, int32_t *d_ids, hipStream_t s, const SearchMask *mask = nullptr);
 
 // ---- scores of listed rows of the embedding index (search_rescore.hip), all three kinds ----
 // d_scores [B][n] = the score of (query b, row d_ids[b][n]) with the bits launch_search /
 // launch_search_bin give that pair, -inf for an id outside [0, n_rows).  d_ids_out (may be
 // null) [B][n]: the id, or -1 where the score is -inf for that reason.  1 <= n <= 128,
 // B >= 1; -1 otherwise (nothing launched), -3: launch refused.
+// tomb (may be null): the index's tombstones; a row whose bit is 1 scores as an id outside
+// [0, n_rows) does.  null launches the unmasked instantiation.
 int launch_index_score_ids(const void *corpus, const float *scales, int storage, int64_t n_rows, int d,
                            const float *d_queries, int B, const int32_t *d_ids, int n, float *d_scores,
-                           int32_t *d_ids_out, hipStream_t s);
+                           int32_t *d_ids_out, hipStream_t s, const uint32_t *tomb = nullptr);
+
+// ---- the tombstones of the embedding index (index_mask.hip) ----
+// Words of an index's tombstones: whole 64-row pairs over the capacity (the binary scan reads
+// a pair per group).
+int64_t index_mask_words(int64_t capacity_rows);
+// Sets the tombstones of d_ids int32 [n] (device); ids outside [0, n_rows) are ignored.
+int launch_index_remove(const int32_t *d_ids, int n, int64_t n_rows, uint32_t *tomb, hipStream_t s);
+// *d_count = the tombstones set among rows [0, n_rows) (a memset and one kernel).
+int launch_index_count_deleted(const uint32_t *tomb, int64_t n_rows, int32_t *d_count, hipStream_t s);
+// d_out uint8 [n] = the tombstones of rows first .. first + n - 1, 0 or 1.
+int launch_index_deleted_flags(const uint32_t *tomb, int64_t first, int n, uint8_t *d_out, hipStream_t s);
 
 // ---- the token store of late interaction (maxsim.hip, mvindex.cpp): documents of len
 // token rows in the SEARCH_F16 fragment order, every document on a group boundary, and

@@ -85,12 +85,22 @@ inline size_t search_lds_bytes(int storage, int QT, int d, int k)
 // int8: row_scale f32 [rows]; a row's scale is read only for rows < n_rows, one group
 // ahead of its use, and the group's i32 sums become scores (score_i8) on their way to
 // the score tile.  f16: row_scale is not used.
-template <int QT, int ST>
+// Mask: nothing, the unmasked kernel, whose arguments end at row_scale; or one SearchMask,
+// the masked kernel, which offers a row only when its tombstone is 0 and its
+// bit in the query's filter is 1.  The tombstones and a shared filter are wave-uniform words:
+// like the int8 scales they come through the scalar cache a group ahead of their use and
+// stay out of the counter that paces the ring.  Per-query filters are one vector load per
+// lane and step: lane 16h + i holds the word of query w + 4i for the rows of quarter h.
+// Every word index is clamped to the words that cover rows < n_rows.
+template <int QT, int ST, class... Mask>
 __global__ __launch_bounds__(kThreads) void search_kernel(const typename Store<ST>::Block *__restrict__ corpus,
                                                           const float *__restrict__ queries, int nq, int d,
                                                           int n_rows, int k, int per, Hit *__restrict__ partial,
-                                                          const float *__restrict__ row_scale)
+                                                          const float *__restrict__ row_scale, Mask... mask)
 {
+    constexpr bool MK = sizeof...(Mask) != 0;
+    SearchMask m{nullptr, nullptr, 0};
+    if constexpr (MK) m = first_mask(mask...);
     typedef Store<ST> S;
     typedef typename S::Block Block;
     typedef typename S::Acc Acc;
@@ -162,6 +172,21 @@ __global__ __launch_bounds__(kThreads) void search_kernel(const typename Store<S
             for (int i = 0; i < 16; ++i) o[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), i));
         }
     };
+    // masked: the admissible words (tombstone 0 and shared filter 1) of the 32 rows around the
+    // four groups of the step in which this wave streams group grp: wave h is (h - w) * steps
+    // groups away, the waves walk in step.  Wave-uniform addresses, as the scales.
+    typedef const __attribute__((address_space(4))) uint32_t *WordPtr;
+    const int last_word = max((n_rows + 31) >> 5, 1) - 1;
+    const bool per_query = MK && m.filt && m.stride != 0;
+    auto load_admissible = [&](int grp, uint32_t (&o)[4]) {
+        const WordPtr tomb_c = (WordPtr)(uintptr_t)m.tomb, filt_c = (WordPtr)(uintptr_t)m.filt;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int word = min((grp + (h - ws) * steps) >> 1, last_word);
+            o[h] = ~tomb_c[word];
+            if (m.filt && !per_query) o[h] &= filt_c[word];
+        }
+    };
 
     // the ring is filled and refilled in the order it is consumed (the scheduling
     // barriers keep the compiler from reordering the loads), so a unit's loads
@@ -179,6 +204,10 @@ __global__ __launch_bounds__(kThreads) void search_kernel(const typename Store<S
     float rs[16] = {};                                            // int8: the scales of group g, loaded a group ahead
     if constexpr (ST == SEARCH_I8) {
         if (U > 0) load_scales(g0, rs);
+    }
+    uint32_t adm[4] = {};                                         // masked: the admissible words of this step's groups
+    if constexpr (MK) {
+        if (U > 0) load_admissible(g0, adm);
     }
     Acc acc[QT];
 #pragma unroll
@@ -239,9 +268,32 @@ __global__ __launch_bounds__(kThreads) void search_kernel(const typename Store<S
                     if (lane == 0) gb[w] = g;
                     lds_barrier();
                     const int64_t row = (int64_t)gb[lane >> 4] * 16 + (lane & 15);
-                    const bool valid = row < n_rows;
-                    for (int q = w; q < nqv; q += 4)
-                        list_offer(lists + (size_t)q * k, k, tile[q * 64 + lane], (int32_t)row, valid, lane);
+                    bool valid = row < n_rows;
+                    if constexpr (!MK) {
+                        for (int q = w; q < nqv; q += 4)
+                            list_offer(lists + (size_t)q * k, k, tile[q * 64 + lane], (int32_t)row, valid, lane);
+                    } else {
+                        // this lane's quarter's word, by bit masks as the scales above
+                        uint32_t word = 0;
+#pragma unroll
+                        for (int h = 0; h < 4; ++h) word |= adm[h] & (uint32_t)hmask[h];
+                        valid = valid && ((word >> (row & 31)) & 1u);
+                        load_admissible(g + 1, adm);
+                        uint32_t fq = 0;                          // per-query filters: query w + 4 (lane & 15)'s word of this lane's quarter
+                        if (per_query && w + 4 * (lane & 15) < nqv)
+                            fq = m.filt[(size_t)(w + 4 * (lane & 15)) * m.stride + min((int)(row >> 5), last_word)];
+                        if (!per_query) {   // uniform: the loop without the shuffle is the unmasked kernel's
+                            for (int q = w; q < nqv; q += 4)
+                                list_offer(lists + (size_t)q * k, k, tile[q * 64 + lane], (int32_t)row, valid, lane);
+                        } else {
+                            for (int q = w, i = 0; q < nqv; q += 4, ++i) {
+                                // (the shuffle by every lane, before any lane-dependent condition)
+                                const uint32_t fw = (uint32_t)__shfl((int)fq, (lane & 48) | i, 64);
+                                const bool ok = valid & (bool)((fw >> (row & 31)) & 1u);
+                                list_offer(lists + (size_t)q * k, k, tile[q * 64 + lane], (int32_t)row, ok, lane);
+                            }
+                        }
+                    }
                     lds_barrier();
                     kb = 0;
                     ++g;
@@ -353,37 +405,38 @@ __global__ __launch_bounds__(kThreads) void unit_rows_kernel(float *__restrict__
     for (int c = lane; c < d; c += 64) out[r * d + c] *= inv;
 }
 
-template <int QT, int ST>
+template <int QT, int ST, class... Mask>
 hipError_t allow_lds()
 {
-    return hipFuncSetAttribute((const void *)search_kernel<QT, ST>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    return hipFuncSetAttribute((const void *)search_kernel<QT, ST, Mask...>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                kLdsBudget);
 }
 
-template <int ST>
+template <int ST, class... Mask>
 hipError_t allow_lds_all()
 {
-    hipError_t e = allow_lds<1, ST>();
-    if (e == hipSuccess) e = allow_lds<2, ST>();
-    if (e == hipSuccess) e = allow_lds<3, ST>();
-    if (e == hipSuccess) e = allow_lds<4, ST>();
+    hipError_t e = allow_lds<1, ST, Mask...>();
+    if (e == hipSuccess) e = allow_lds<2, ST, Mask...>();
+    if (e == hipSuccess) e = allow_lds<3, ST, Mask...>();
+    if (e == hipSuccess) e = allow_lds<4, ST, Mask...>();
     return e;
 }
 
 // One group of nq <= 64 queries: the streaming kernel over P row ranges, then the merge.
-template <int ST>
+// mask: none (the unmasked kernel) or the group's SearchMask.
+template <int ST, class... Mask>
 int launch_group(const void *corpus, const float *row_scale, const float *Q, int nq, int d, int n_rows, int k,
-                 int per, int P, Hit *part, float *d_scores, int32_t *d_ids, hipStream_t s)
+                 int per, int P, Hit *part, float *d_scores, int32_t *d_ids, hipStream_t s, Mask... mask)
 {
     typedef typename Store<ST>::Block Block;
     const int QT = (nq + 15) / 16;
     const size_t lds = search_lds_bytes<ST>(QT, d, k);
     const Block *C = (const Block *)corpus;
     switch (QT) {
-    case 1: search_kernel<1, ST><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, n_rows, k, per, part, row_scale); break;
-    case 2: search_kernel<2, ST><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, n_rows, k, per, part, row_scale); break;
-    case 3: search_kernel<3, ST><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, n_rows, k, per, part, row_scale); break;
-    default: search_kernel<4, ST><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, n_rows, k, per, part, row_scale); break;
+    case 1: search_kernel<1, ST, Mask...><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, n_rows, k, per, part, row_scale, mask...); break;
+    case 2: search_kernel<2, ST, Mask...><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, n_rows, k, per, part, row_scale, mask...); break;
+    case 3: search_kernel<3, ST, Mask...><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, n_rows, k, per, part, row_scale, mask...); break;
+    default: search_kernel<4, ST, Mask...><<<(unsigned)P, kThreads, lds, s>>>(C, Q, nq, d, n_rows, k, per, part, row_scale, mask...); break;
     }
     if (hipGetLastError() != hipSuccess) return -3;
     search_merge_kernel<<<nq, kThreads, 0, s>>>(part, P, k, d_scores, d_ids);
@@ -396,6 +449,8 @@ int search_prepare_device()
 {
     hipError_t e = allow_lds_all<SEARCH_F16>();
     if (e == hipSuccess) e = allow_lds_all<SEARCH_I8>();
+    if (e == hipSuccess) e = allow_lds_all<SEARCH_F16, SearchMask>();
+    if (e == hipSuccess) e = allow_lds_all<SEARCH_I8, SearchMask>();
     return e == hipSuccess ? 0 : -1;
 }
 
@@ -429,10 +484,11 @@ int launch_index_add(const float *d_rows, int64_t n, int d, int64_t first, int s
 }
 
 int launch_search(const void *corpus, const float *scales, int storage, int64_t n_rows, int d, const float *d_queries,
-                  int B, int k, void *scratch, float *d_scores, int32_t *d_ids, hipStream_t s)
+                  int B, int k, void *scratch, float *d_scores, int32_t *d_ids, hipStream_t s, const SearchMask *mask)
 {
     if (B < 1 || k < 1 || k > 128 || d % 64 || d < 64 || d > 1024 || n_rows < 0 || n_rows > 0x7ffffff0) return -1;
     if ((storage != SEARCH_F16 && storage != SEARCH_I8) || (storage == SEARCH_I8 && !scales)) return -1;
+    if (mask && !mask->tomb) return -1;
     const int QG = search_group_queries(d, k, storage);
     if (search_lds_bytes(storage, 1, d, k) > (size_t)kLdsBudget) return -1;
     // the row ranges: P workgroups of `per` groups each, per % 4 == 0 (one group per wave and step)
@@ -451,11 +507,22 @@ int launch_search(const void *corpus, const float *scales, int storage, int64_t 
         const float *Q = d_queries + (size_t)b0 * d;
         float *S = d_scores + (size_t)b0 * k;
         int32_t *I = d_ids + (size_t)b0 * k;
-        const int rc = storage == SEARCH_I8
-                           ? launch_group<SEARCH_I8>(corpus, scales, Q, nq, d, (int)n_rows, k, (int)per, (int)P,
-                                                     (Hit *)scratch, S, I, s)
-                           : launch_group<SEARCH_F16>(corpus, nullptr, Q, nq, d, (int)n_rows, k, (int)per, (int)P,
-                                                      (Hit *)scratch, S, I, s);
+        int rc;
+        if (mask) {
+            // this group's filters; an empty index has no row to admit and its filters may have no word
+            SearchMask gm = *mask;
+            if (n_rows == 0) gm.filt = nullptr;
+            if (gm.filt) gm.filt += (size_t)b0 * (size_t)gm.stride;
+            rc = storage == SEARCH_I8 ? launch_group<SEARCH_I8>(corpus, scales, Q, nq, d, (int)n_rows, k, (int)per, (int)P,
+                                                                (Hit *)scratch, S, I, s, gm)
+                                      : launch_group<SEARCH_F16>(corpus, nullptr, Q, nq, d, (int)n_rows, k, (int)per, (int)P,
+                                                                 (Hit *)scratch, S, I, s, gm);
+        } else {
+            rc = storage == SEARCH_I8 ? launch_group<SEARCH_I8>(corpus, scales, Q, nq, d, (int)n_rows, k, (int)per, (int)P,
+                                                                (Hit *)scratch, S, I, s)
+                                      : launch_group<SEARCH_F16>(corpus, nullptr, Q, nq, d, (int)n_rows, k, (int)per, (int)P,
+                                                                 (Hit *)scratch, S, I, s);
+        }
         if (rc != 0) return rc;
     }
     return 0;

@@ -43,11 +43,21 @@ constexpr int ring_groups(int NB) { return 16 / NB > 8 ? 8 : 16 / NB > 2 ? 16 / 
 // partial: [query][P][k].  Rows >= n_rows (the rest of the last group, stale rows after a
 // clear, the groups a range has past the end) are never offered; loads past the last
 // filled group are redirected to it, so they stay inside the allocation.
-template <int NB>
+// Mask: nothing, the unmasked kernel; or one SearchMask, the masked kernel.
+// A group's 64 tombstones and its 64 bits of a shared filter are one word pair each, wave-
+// uniform, read through the scalar cache a group ahead; a group none of whose rows is
+// admissible is left at once, before any Hamming distance.  Per-query filters are one
+// vector load per group: lane 16h + i < 32 holds half h of query w + 4i's pair.  Word
+// indices are clamped to the words that cover rows < n_rows (tombstones: to the last group).
+template <int NB, class... Mask>
 __global__ __launch_bounds__(kThreads) void search_bin_kernel(const uint4 *__restrict__ corpus,
                                                               const float *__restrict__ queries, int nq, int d,
-                                                              int n_rows, int k, int per, Hit *__restrict__ partial)
+                                                              int n_rows, int k, int per, Hit *__restrict__ partial,
+                                                              Mask... mask)
 {
+    constexpr bool MK = sizeof...(Mask) != 0;
+    SearchMask m{nullptr, nullptr, 0};
+    if constexpr (MK) m = first_mask(mask...);
     extern __shared__ uint4 smem[];
     constexpr int R = ring_groups(NB);
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -87,6 +97,19 @@ __global__ __launch_bounds__(kThreads) void search_bin_kernel(const uint4 *__res
 #pragma unroll
         for (int c = 0; c < NB; ++c) o[c] = p[c * 64];
     };
+    // masked: bit l = row 64 g + l is admissible as far as the tombstones and a shared filter say
+    typedef const __attribute__((address_space(4))) uint32_t *WordPtr;
+    const int last_word = max((n_rows + 31) >> 5, 1) - 1;
+    const bool per_query = MK && m.filt && m.stride != 0;
+    auto load_admissible = [&](int g) {
+        const WordPtr tomb_c = (WordPtr)(uintptr_t)m.tomb, filt_c = (WordPtr)(uintptr_t)m.filt;
+        const int w0 = 2 * min(g, last);
+        uint64_t a = ~((uint64_t)tomb_c[w0] | (uint64_t)tomb_c[w0 + 1] << 32);
+        if (m.filt && !per_query) a &= (uint64_t)filt_c[min(w0, last_word)] | (uint64_t)filt_c[min(w0 + 1, last_word)] << 32;
+        return a;
+    };
+    uint64_t adm = 0;
+    if constexpr (MK) adm = load_admissible(g0);
     // the ring is filled and refilled in the order it is consumed, so a group's loads are
     // always the oldest ones outstanding
     uint4 ring[R][NB];
@@ -107,12 +130,31 @@ __global__ __launch_bounds__(kThreads) void search_bin_kernel(const uint4 *__res
             load(g + R, ring[j]);
             __builtin_amdgcn_sched_barrier(0);
             const int64_t row = (int64_t)g * 64 + lane;
-            const bool valid = row < n_rows;
-            for (int q = w; q < nq; q += 4) {
-                int ham = 0;
+            bool valid = row < n_rows;
+            if constexpr (!MK) {
+                for (int q = w; q < nq; q += 4) {
+                    int ham = 0;
 #pragma unroll
-                for (int c = 0; c < NB; ++c) ham = bin_distance(r[c], qb[(size_t)q * NB + c], ham);
-                list_offer(lists + (size_t)q * k, k, bin_score(d, ham), (int32_t)row, valid, lane);
+                    for (int c = 0; c < NB; ++c) ham = bin_distance(r[c], qb[(size_t)q * NB + c], ham);
+                    list_offer(lists + (size_t)q * k, k, bin_score(d, ham), (int32_t)row, valid, lane);
+                }
+            } else {
+                valid = valid && ((adm >> lane) & 1);
+                adm = load_admissible(g + 1);
+                if (__ballot(valid) == 0) continue;   // uniform: no row of the group for any of this wave's queries
+                uint32_t fq = 0;                      // per-query filters: half lane >> 4 of query w + 4 (lane & 15)'s pair
+                if (per_query && lane < 32 && w + 4 * (lane & 15) < nq)
+                    fq = m.filt[(size_t)(w + 4 * (lane & 15)) * m.stride + min(2 * g + (lane >> 4), last_word)];
+                for (int q = w, i = 0; q < nq; q += 4, ++i) {
+                    int ham = 0;
+#pragma unroll
+                    for (int c = 0; c < NB; ++c) ham = bin_distance(r[c], qb[(size_t)q * NB + c], ham);
+                    // (the shuffle by every lane, before any lane-dependent condition)
+                    uint32_t fw = ~0u;
+                    if (per_query) fw = (uint32_t)__shfl((int)fq, ((lane >> 5) << 4) | i, 64);   // (a uniform branch)
+                    const bool ok = valid & (bool)((fw >> (lane & 31)) & 1u);
+                    list_offer(lists + (size_t)q * k, k, bin_score(d, ham), (int32_t)row, ok, lane);
+                }
             }
         }
     }
@@ -139,20 +181,41 @@ __global__ __launch_bounds__(256) void index_add_bin_kernel(const float *__restr
     }
 }
 
-template <int NB>
+// mask: none (the unmasked kernel) or the launch's SearchMask
+template <int NB, class... Mask>
 int launch_scan(const void *corpus, const float *Q, int nq, int d, int n_rows, int k, int per, int P, Hit *part,
-                hipStream_t s)
+                hipStream_t s, Mask... mask)
 {
-    search_bin_kernel<NB><<<(unsigned)P, kThreads, search_bin_lds_bytes(nq, NB, k), s>>>((const uint4 *)corpus, Q, nq, d,
-                                                                                        n_rows, k, per, part);
+    search_bin_kernel<NB, Mask...><<<(unsigned)P, kThreads, search_bin_lds_bytes(nq, NB, k), s>>>(
+        (const uint4 *)corpus, Q, nq, d, n_rows, k, per, part, mask...);
     return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+template <class... Mask>
+int launch_scan_of(int NB, const void *corpus, const float *Q, int nq, int d, int n_rows, int k, int per, int P, Hit *part,
+                   hipStream_t s, Mask... mask)
+{
+    switch (NB) {
+    case 1: return launch_scan<1>(corpus, Q, nq, d, n_rows, k, per, P, part, s, mask...);
+    case 2: return launch_scan<2>(corpus, Q, nq, d, n_rows, k, per, P, part, s, mask...);
+    case 3: return launch_scan<3>(corpus, Q, nq, d, n_rows, k, per, P, part, s, mask...);
+    case 4: return launch_scan<4>(corpus, Q, nq, d, n_rows, k, per, P, part, s, mask...);
+    case 5: return launch_scan<5>(corpus, Q, nq, d, n_rows, k, per, P, part, s, mask...);
+    case 6: return launch_scan<6>(corpus, Q, nq, d, n_rows, k, per, P, part, s, mask...);
+    case 7: return launch_scan<7>(corpus, Q, nq, d, n_rows, k, per, P, part, s, mask...);
+    default: return launch_scan<8>(corpus, Q, nq, d, n_rows, k, per, P, part, s, mask...);
+    }
 }
 
 template <int NB>
 hipError_t allow_lds()
 {
-    return hipFuncSetAttribute((const void *)search_bin_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               kLdsBudget);
+    hipError_t e = hipFuncSetAttribute((const void *)search_bin_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       kLdsBudget);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)search_bin_kernel<NB, SearchMask>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                kLdsBudget);
+    return e;
 }
 
 }  // namespace
@@ -189,9 +252,10 @@ int launch_index_add_bin(const float *d_rows, int64_t n, int d, int64_t first, v
 }
 
 int launch_search_bin(const void *corpus, int64_t n_rows, int d, const float *d_queries, int B, int k, void *scratch,
-                      float *d_scores, int32_t *d_ids, hipStream_t s)
+                      float *d_scores, int32_t *d_ids, hipStream_t s, const SearchMask *mask)
 {
     if (B < 1 || k < 1 || k > 128 || d % 64 || d < 64 || d > 1024 || n_rows < 0 || n_rows > 0x7ffffff0) return -1;
+    if (mask && !mask->tomb) return -1;
     const int NB = (d + 127) / 128;
     const int64_t groups = std::max<int64_t>(1, (n_rows + 63) / 64);
     const int cus = device_cu_count();
@@ -204,15 +268,14 @@ int launch_search_bin(const void *corpus, int64_t n_rows, int d, const float *d_
         P = (groups + per - 1) / per;
         const float *Q = d_queries + (size_t)b0 * d;
         int rc;
-        switch (NB) {
-        case 1: rc = launch_scan<1>(corpus, Q, nq, d, (int)n_rows, k, (int)per, (int)P, (Hit *)scratch, s); break;
-        case 2: rc = launch_scan<2>(corpus, Q, nq, d, (int)n_rows, k, (int)per, (int)P, (Hit *)scratch, s); break;
-        case 3: rc = launch_scan<3>(corpus, Q, nq, d, (int)n_rows, k, (int)per, (int)P, (Hit *)scratch, s); break;
-        case 4: rc = launch_scan<4>(corpus, Q, nq, d, (int)n_rows, k, (int)per, (int)P, (Hit *)scratch, s); break;
-        case 5: rc = launch_scan<5>(corpus, Q, nq, d, (int)n_rows, k, (int)per, (int)P, (Hit *)scratch, s); break;
-        case 6: rc = launch_scan<6>(corpus, Q, nq, d, (int)n_rows, k, (int)per, (int)P, (Hit *)scratch, s); break;
-        case 7: rc = launch_scan<7>(corpus, Q, nq, d, (int)n_rows, k, (int)per, (int)P, (Hit *)scratch, s); break;
-        default: rc = launch_scan<8>(corpus, Q, nq, d, (int)n_rows, k, (int)per, (int)P, (Hit *)scratch, s); break;
+        if (mask) {
+            // this launch's filters; an empty index has no row to admit and its filters may have no word
+            SearchMask gm = *mask;
+            if (n_rows == 0) gm.filt = nullptr;
+            if (gm.filt) gm.filt += (size_t)b0 * (size_t)gm.stride;
+            rc = launch_scan_of(NB, corpus, Q, nq, d, (int)n_rows, k, (int)per, (int)P, (Hit *)scratch, s, gm);
+        } else {
+            rc = launch_scan_of(NB, corpus, Q, nq, d, (int)n_rows, k, (int)per, (int)P, (Hit *)scratch, s);
         }
         if (rc != 0) return rc;
         rc = launch_search_merge(scratch, nq, (int)P, k, d_scores + (size_t)b0 * k, d_ids + (size_t)b0 * k, s);

@@ -25,19 +25,25 @@ namespace {
 // scores [B][n]: -inf for an id outside [0, n_rows).  ids_out (may be null) [B][n]: the id,
 // or -1 where the score is -inf.  The rows of such ids are not read (row 0's slot of the
 // allocation is, and its result dropped).
-template <int ST>
+// Tomb: nothing, the unmasked kernel; or the index's tombstones (const uint32_t *, index_mask.hip),
+// the masked kernel: a deleted row is treated exactly as an id outside [0, n_rows).
+template <int ST, class... Tomb>
 __global__ __launch_bounds__(64) void score_ids_kernel(const void *__restrict__ corpus,
                                                        const float *__restrict__ row_scale,
                                                        const float *__restrict__ queries, int d, int n_rows,
                                                        const int32_t *__restrict__ ids, int n,
-                                                       float *__restrict__ scores, int32_t *__restrict__ ids_out)
+                                                       float *__restrict__ scores, int32_t *__restrict__ ids_out,
+                                                       Tomb... tomb)
 {
     const int lane = threadIdx.x, f = lane & 15, g = lane >> 4;
     const size_t b = blockIdx.y;
     const int j = blockIdx.x * 16 + f;
     const float *x = queries + b * d;
     const int32_t id = j < n ? ids[b * n + j] : -1;
-    const bool ok = (uint32_t)id < (uint32_t)n_rows;
+    bool ok = (uint32_t)id < (uint32_t)n_rows;
+    if constexpr (sizeof...(Tomb) != 0) {
+        if (ok) ok = !((first_tomb(tomb...)[id >> 5] >> (id & 31)) & 1u);
+    }
     const int64_t row = ok ? id : 0;
     float v;
     bool writer;
@@ -82,11 +88,30 @@ __global__ __launch_bounds__(64) void score_ids_kernel(const void *__restrict__ 
     }
 }
 
+template <int ST, class... Tomb>
+void launch_score_ids(dim3 grid, const void *corpus, const float *scales, const float *Q, int d, int n_rows,
+                      const int32_t *I, int n, float *S, int32_t *O, hipStream_t s, Tomb... tomb)
+{
+    score_ids_kernel<ST, Tomb...><<<grid, 64, 0, s>>>(corpus, scales, Q, d, n_rows, I, n, S, O, tomb...);
+}
+
+template <class... Tomb>
+void launch_score_ids_of(int storage, dim3 grid, const void *corpus, const float *scales, const float *Q, int d, int n_rows,
+                         const int32_t *I, int n, float *S, int32_t *O, hipStream_t s, Tomb... tomb)
+{
+    if (storage == SEARCH_F16)
+        launch_score_ids<SEARCH_F16>(grid, corpus, nullptr, Q, d, n_rows, I, n, S, O, s, tomb...);
+    else if (storage == SEARCH_I8)
+        launch_score_ids<SEARCH_I8>(grid, corpus, scales, Q, d, n_rows, I, n, S, O, s, tomb...);
+    else
+        launch_score_ids<SEARCH_BIN>(grid, corpus, nullptr, Q, d, n_rows, I, n, S, O, s, tomb...);
+}
+
 }  // namespace
 
 int launch_index_score_ids(const void *corpus, const float *scales, int storage, int64_t n_rows, int d,
                            const float *d_queries, int B, const int32_t *d_ids, int n, float *d_scores,
-                           int32_t *d_ids_out, hipStream_t s)
+                           int32_t *d_ids_out, hipStream_t s, const uint32_t *tomb)
 {
     if (B < 1 || n < 1 || n > 128 || d % 64 || d < 64 || d > 1024 || n_rows < 0 || n_rows > 0x7ffffff0 || !corpus) return -1;
     if ((storage != SEARCH_F16 && storage != SEARCH_I8 && storage != SEARCH_BIN) || (storage == SEARCH_I8 && !scales))
@@ -98,12 +123,10 @@ int launch_index_score_ids(const void *corpus, const float *scales, int storage,
         const int32_t *I = d_ids + (size_t)b0 * n;
         float *S = d_scores + (size_t)b0 * n;
         int32_t *O = d_ids_out ? d_ids_out + (size_t)b0 * n : nullptr;
-        if (storage == SEARCH_F16)
-            score_ids_kernel<SEARCH_F16><<<grid, 64, 0, s>>>(corpus, nullptr, Q, d, (int)n_rows, I, n, S, O);
-        else if (storage == SEARCH_I8)
-            score_ids_kernel<SEARCH_I8><<<grid, 64, 0, s>>>(corpus, scales, Q, d, (int)n_rows, I, n, S, O);
+        if (tomb)
+            launch_score_ids_of(storage, grid, corpus, scales, Q, d, (int)n_rows, I, n, S, O, s, tomb);
         else
-            score_ids_kernel<SEARCH_BIN><<<grid, 64, 0, s>>>(corpus, nullptr, Q, d, (int)n_rows, I, n, S, O);
+            launch_score_ids_of(storage, grid, corpus, scales, Q, d, (int)n_rows, I, n, S, O, s);
         if (hipGetLastError() != hipSuccess) return -3;
     }
     return 0;

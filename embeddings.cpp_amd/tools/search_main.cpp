@@ -7,6 +7,10 @@
 //               [-S f16|int8|res2|res4]
 // One text per line of CORPUS.txt; queries from stdin, one per line, `q` or EOF ends.
 // Per hit one line: rank<TAB>id<TAB>score<TAB>text.
+// A stdin line `:del ID [ID ...]` removes those rows from the embedding index
+// (bertx_index_remove; with -R from both indexes) and prints `deleted N`, N being the change
+// of bertx_index_live; later queries no longer return them.  With -a there is no embedding
+// index: the line is answered with a message and ignored.
 // -s: how the index stores its rows (bertx_index_create_ex): f16, the default, or int8
 // with one scale per row, half the bytes and a less precise first stage, or binary: a row
 // as its sign bits, one sixteenth of the bytes, searched by Hamming distance; the printed
@@ -252,6 +256,30 @@ int main(int argc, char **argv)
         if (!q.empty() && q.back() == '\r') q.pop_back();
         if (q == "q") break;
         if (q.empty()) continue;
+        if (q.compare(0, 4, ":del") == 0 && (q.size() == 4 || q[4] == ' ' || q[4] == '\t')) {
+            if (!idx) {
+                std::printf("no embedding index (-a): nothing deleted\n");
+                std::fflush(stdout);
+                continue;
+            }
+            std::vector<int32_t> del;
+            const char *p = q.c_str() + 4;
+            for (char *end = nullptr;; p = end) {
+                const long v = std::strtol(p, &end, 10);
+                if (end == p) break;
+                del.push_back(v < 0 || v > 0x7fffffffl ? -1 : (int32_t)v);
+            }
+            const int32_t before = bertx_index_live(idx);
+            if (!del.empty() && (bertx_index_remove(idx, del.data(), (int32_t)del.size()) != 0 ||
+                                 (fine && bertx_index_remove(fine, del.data(), (int32_t)del.size()) != 0))) {
+                std::fprintf(stderr, "search: deleting failed\n");
+                rc = 1;
+                break;
+            }
+            std::printf("deleted %d\n", before - bertx_index_live(idx));
+            std::fflush(stdout);
+            continue;
+        }
         const char *qp = q.c_str();
         if (all) {
             // the full scan: the k best of every stored document by MaxSim, selected on the GPU

@@ -483,9 +483,55 @@ BERT_API int32_t bertx_tokenize_batch(struct bert_ctx *ctx, int32_t n_threads, i
  * captured; two concurrent calls on the same coarse index are serialised.
  * bertx_index_search_rescored_texts encodes as bertx_index_search_texts does.
  *
- * Not provided: an index sharded over several GPUs, deleting rows, saving and
- * loading, f32 storage, f16 queries against int8 rows, 4-bit storage, binary rows
- * against unbinarized queries (asymmetric scores), a fine copy kept in host memory.
+ * Deleting rows and filtered search.  Two masks over row ids, both packed 32 rows to a
+ * uint32_t word: row r is bit r % 32 of word r / 32 (np.packbits(x, bitorder="little") viewed
+ * as uint32).  Tombstones belong to the index, lie on its device, cover the capacity and start
+ * as zeros; bit 1 = deleted.  Filters are the caller's, per call; bit 1 = the row may be
+ * returned.  A row is admissible for query b iff id < size, its tombstone is 0 and, when a
+ * filter is given, its bit in query b's filter is 1.
+ * bertx_index_remove / _remove_device (ids int32[n], host / device; n >= 1, anything else a
+ * negative error with nothing changed): sets the tombstones of the listed ids and returns 0.
+ * Ids outside [0, size), size being the row count when the call is made, are ignored;
+ * repeated ids are harmless; the bits are set by atomic OR, so no order matters.  The device
+ * form is asynchronous, allocates nothing, never synchronises, can be captured, and is
+ * ordered as bertx_index_add_device is.  Ids are never reused: bertx_index_size does not
+ * change, and bertx_index_rows / _rows_i8 / _rows_bits still return a deleted row's stored
+ * values.  bertx_index_clear also zeroes the tombstones (ordered on the index's stream), so a
+ * clear followed by adds starts clean.
+ * bertx_index_live: size minus the deleted rows in [0, size); a host call that synchronises.
+ * bertx_index_deleted: out uint8[n] = 0 or 1 for rows first .. first + n - 1; -1 on a bad
+ * range with the output untouched.
+ * bertx_index_search_filtered / _device: bertx_index_search over the admissible rows.
+ * filters uint32[n_filters][words] (host / device); n_filters is 1 (one filter for every
+ * query) or B (query b uses filter b); words >= ceil(size / 32) is also the stride between
+ * filters; bits of rows >= size are ignored, whatever they hold.  filters == NULL with
+ * n_filters == 0 is exactly bertx_index_search.  The result is the k best admissible rows
+ * with the scorer's bits, the same order (score descending, id ascending) and the same
+ * (-inf, -1) fill when fewer than k rows are admissible.  1 <= k <= 128, B >= 1; every
+ * refusal (a null pointer, n_filters not 0, 1 or B, too few words, a filter pointer without
+ * a count or the reverse) returns a negative error with the outputs untouched.  The device
+ * form allocates nothing; the host form allocates and frees a staging buffer for the filters
+ * per call.  The filter is read when the kernel runs: a captured search sees the bits the
+ * buffer holds at replay.
+ * On an index with deletions the entries above follow: bertx_index_search / _search_device
+ * return admissible rows only; bertx_index_score_ids gives -inf for a deleted id (and the
+ * rescored search's kept-id -1), exactly as for an id outside [0, size); the text forms call
+ * these.  The composition that defines the two-stage search stays literally true: coarse's
+ * tombstones (and the filter) limit the candidates, a candidate fine has deleted becomes the
+ * fill.  bertx_index_search_rescored_filtered / _device is that composition with
+ * bertx_index_search_filtered(coarse, queries, n_cand, filters) as its first line.
+ * An index from which nothing was removed since creation or the last clear, searched without
+ * a filter, launches the kernels it launched before masks existed, with the same arguments:
+ * the masked kernels are other instantiations, chosen at launch time by a host flag that any
+ * accepted remove sets and clear resets (the rule the row count follows in captured graphs:
+ * a graph captured before the first removal keeps launching the unmasked kernels).
+ *
+ * Not provided: an index sharded over several GPUs, compaction (reclaiming deleted rows'
+ * bytes or renumbering), skipping the loads of fully masked groups, a gather path for very
+ * selective filters, masks on the token store, saving and loading (the mask layout above is
+ * what a file would carry), f32 storage, f16 queries against int8 rows, 4-bit storage,
+ * binary rows against unbinarized queries (asymmetric scores), a fine copy kept in host
+ * memory.
  */
 enum { BERTX_INDEX_F16 = 0, BERTX_INDEX_I8 = 1 };
 enum { BERTX_INDEX_BIN = 8 };   /* the embedding index only: "Binary storage" above */
@@ -524,6 +570,24 @@ BERT_API int32_t bertx_index_search_rescored_device(struct bertx_index *coarse, 
 BERT_API int32_t bertx_index_search_rescored_texts(struct bertx_index *coarse, struct bertx_index *fine,
                                                    struct bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts,
                                                    int32_t k, int32_t n_cand, float *scores, int32_t *ids);
+BERT_API int32_t bertx_index_remove(struct bertx_index *idx, const int32_t *ids, int32_t n);
+BERT_API int32_t bertx_index_remove_device(struct bertx_index *idx, const int32_t *d_ids, int32_t n, void *stream);
+BERT_API int32_t bertx_index_live(struct bertx_index *idx);
+BERT_API int32_t bertx_index_deleted(struct bertx_index *idx, int32_t first, int32_t n, uint8_t *out);
+BERT_API int32_t bertx_index_search_filtered(struct bertx_index *idx, const float *queries, int32_t B, int32_t k,
+                                             const uint32_t *filters, int32_t n_filters, int32_t words, float *scores,
+                                             int32_t *ids);
+BERT_API int32_t bertx_index_search_filtered_device(struct bertx_index *idx, const float *d_queries, int32_t B, int32_t k,
+                                                    const uint32_t *d_filters, int32_t n_filters, int32_t words,
+                                                    float *d_scores, int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_index_search_rescored_filtered(struct bertx_index *coarse, struct bertx_index *fine,
+                                                      const float *queries, int32_t B, int32_t k, int32_t n_cand,
+                                                      const uint32_t *filters, int32_t n_filters, int32_t words,
+                                                      float *scores, int32_t *ids);
+BERT_API int32_t bertx_index_search_rescored_filtered_device(struct bertx_index *coarse, struct bertx_index *fine,
+                                                             const float *d_queries, int32_t B, int32_t k, int32_t n_cand,
+                                                             const uint32_t *d_filters, int32_t n_filters, int32_t words,
+                                                             float *d_scores, int32_t *d_ids, void *stream);
 
 /*
  * Token store: late interaction (ColBERT's MaxSim) over per-token vectors.  An
