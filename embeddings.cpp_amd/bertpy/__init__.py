@@ -330,6 +330,13 @@ def load_lib(path=None):
         L.bertx_test_kmeans_sample.argtypes = [c_i64, c_u32, vp]
     except AttributeError:
         pass
+    try:   # (the cap on a token store's scan grids, a test hook; absent from older BERT_LIB builds)
+        L.bertx_test_mvindex_grid.restype = c_i32
+        L.bertx_test_mvindex_grid.argtypes = [vp, c_i32]
+        L.bertx_test_mvindex_last_grid.restype = c_i32
+        L.bertx_test_mvindex_last_grid.argtypes = [vp]
+    except AttributeError:
+        pass
     try:   # (residual-coded token stores; absent from older BERT_LIB builds)
         L.bertx_mvindex_set_residual_buckets.restype = c_i32
         L.bertx_mvindex_set_residual_buckets.argtypes = [vp, vp, vp]

@@ -319,8 +319,11 @@ int launch_mv_pack(const float *d_rows, int64_t t0, int64_t count, int w, const 
 // d_out[c] = sum_{i < Lq} max_{j < len} sim(q_i, row j of document id), id = d_ids[c] (or c
 // when d_ids is null), for c < n; -inf for an id outside [0, n_docs).  d_q f32 [Lq][w]
 // is normalised as the rows are.  1 <= Lq <= 64, n >= 1; -1 otherwise, -3: launch refused.
+// max_wg, ran_wg (here and on every scan of the store below; bert_hip.h bertx_test_mvindex_grid):
+// max_wg > 0 bounds the scan kernel's workgroups after the launcher's own rule and before
+// anything derived from them; *ran_wg, when given, receives the workgroups it launched.
 int launch_maxsim(const void *store, const void *d_table, int n_docs, int w, const float *d_q, int Lq,
-                  const int32_t *d_ids, int n, float *d_out, hipStream_t s);
+                  const int32_t *d_ids, int n, float *d_out, hipStream_t s, int max_wg = 0, int *ran_wg = nullptr);
 // The same two over an int8 store (maxsim_i8.hip): rows in the SEARCH_I8 fragment order,
 // each the embedding index's int8 quantization q of the raw row, and scales f32 [token
 // slots], u = 1 / sqrt(sum q_i^2) per slot (0 for a zero row), so that q u has unit
@@ -329,7 +332,8 @@ int maxsim_i8_prepare_device();
 int launch_mv_pack_i8(const float *d_rows, int64_t t0, int64_t count, int w, const int32_t *d_src_off,
                       const void *d_table, int n_new, void *store, float *scales, hipStream_t s);
 int launch_maxsim_i8(const void *store, const float *scales, const void *d_table, int n_docs, int w, const float *d_q,
-                     int Lq, const int32_t *d_ids, int n, float *d_out, hipStream_t s);
+                     int Lq, const int32_t *d_ids, int n, float *d_out, hipStream_t s, int max_wg = 0,
+                     int *ran_wg = nullptr);
 // The full scan (maxsim_search.hip): d_scores f32 [B][k], d_ids i32 [B][k] = per query the
 // k best documents of all n_docs by the scorers' score, bit for bit, best first, equal
 // scores by ascending id, (-inf, -1) where the store has fewer than k documents.  d_q f32
@@ -343,7 +347,7 @@ int maxsim_search_prepare_device();
 size_t maxsim_search_scratch_bytes();
 int launch_maxsim_search(const void *store, const float *scales, int storage, const void *d_table, int n_docs,
                          int64_t used_groups, int w, const float *d_q, int B, int Lq, int k, void *scratch,
-                         float *d_scores, int32_t *d_ids, hipStream_t s);
+                         float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg = 0, int *ran_wg = nullptr);
 
 // ---- centroid codes of the token store (maxsim_codes.hip; bert_hip.h "Centroid codes") ----
 // The centroids are C rows (a multiple of 16) packed as one document of C tokens from group
@@ -368,7 +372,7 @@ int maxsim_approx_prepare_device();
 int launch_maxsim_candidates(const uint16_t *codes, const void *d_table, int n_docs, int64_t used_groups, int storage,
                              int w, const void *cent, const float *cent_u, int C, const float *d_q, int nq, int Lq,
                              int n_cand, float *tscratch, void *scratch, float *d_approx, int32_t *d_ids, int stages,
-                             int *form, hipStream_t s);
+                             int *form, hipStream_t s, int max_wg = 0, int *ran_wg = nullptr);
 // out_s / out_i [nq][k] = the k best by `better` of each query's n_cand (exact[j], ids[j])
 // pairs; a pair whose id is -1 counts as the fill.
 int launch_maxsim_rerank_select(const float *exact, const int32_t *ids, int nq, int n_cand, int k, float *out_s,
@@ -389,7 +393,7 @@ int launch_res_encode(const void *staging, int64_t groups, int w, int nbits, con
                       const float *cuts, const uint16_t *wts, uint32_t *bits, float *u, hipStream_t s);
 int launch_maxsim_res(const uint32_t *bits, const float *u, const uint16_t *codes, const void *cent, const uint32_t *pair,
                       int nbits, const void *d_table, int n_docs, int w, const float *d_q, int Lq, const int32_t *d_ids, int n,
-                      float *d_out, hipStream_t s);
+                      float *d_out, hipStream_t s, int max_wg = 0, int *ran_wg = nullptr);
 
 // ---- the classification head (head.hip): pooler dense + tanh + classifier on the
 // sentences' [CLS] rows, all f32, one form for the three chains ----

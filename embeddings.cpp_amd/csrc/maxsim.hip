@@ -208,7 +208,7 @@ int launch_mv_pack(const float *d_rows, int64_t t0, int64_t count, int w, const 
 }
 
 int launch_maxsim(const void *store, const void *d_table, int n_docs, int w, const float *d_q, int Lq,
-                  const int32_t *d_ids, int n, float *d_out, hipStream_t s)
+                  const int32_t *d_ids, int n, float *d_out, hipStream_t s, int max_wg, int *ran_wg)
 {
     // (the candidate index advances by at most 4 * 4 * CUs per step, in int32)
     if (Lq < 1 || Lq > 64 || n < 1 || n > 0x7fff0000 || n_docs < 0 || w % 64 || w < 64 || w > 1024) return -1;
@@ -217,7 +217,9 @@ int launch_maxsim(const void *store, const void *d_table, int n_docs, int w, con
     if (lds > (size_t)kLdsBudget) return -1;
     // as many workgroups per CU as the LDS holds, at most 4 (16 waves of 8 KiB in flight)
     const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (int64_t)kLdsBudget / (int64_t)lds));
-    const int64_t P = std::max<int64_t>(1, std::min<int64_t>(per_cu * device_cu_count(), ((int64_t)n + 3) / 4));
+    int64_t P = std::max<int64_t>(1, std::min<int64_t>(per_cu * device_cu_count(), ((int64_t)n + 3) / 4));
+    if (max_wg > 0) P = std::min<int64_t>(P, max_wg);
+    if (ran_wg) *ran_wg = (int)P;
     const h16x8 *S = (const h16x8 *)store;
     const int2 *T = (const int2 *)d_table;
     switch (QT) {

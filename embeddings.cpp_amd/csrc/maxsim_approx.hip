@@ -426,7 +426,7 @@ int maxsim_approx_prepare_device()
 int launch_maxsim_candidates(const uint16_t *codes, const void *d_table, int n_docs, int64_t used_groups, int storage,
                              int w, const void *cent, const float *cent_u, int C, const float *d_q, int nq, int Lq,
                              int n_cand, float *tscratch, void *scratch, float *d_approx, int32_t *d_ids, int stages,
-                             int *form, hipStream_t s)
+                             int *form, hipStream_t s, int max_wg, int *ran_wg)
 {
     if (Lq < 1 || Lq > 64 || n_cand < 1 || n_cand > 128 || n_docs < 0 || used_groups < 0 || used_groups > 0x7ffffff0ll ||
         w % 64 || w < 64 || w > 1024 || C < 16 || C > 65536 || C % 16 || !codes || !cent || !tscratch || !scratch)
@@ -447,9 +447,11 @@ int launch_maxsim_candidates(const uint16_t *codes, const void *d_table, int n_d
     const size_t lds = in_lds ? lists + tbytes : lists;
     const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(kMaxWgPerCu, (int64_t)kLdsBudget / (int64_t)lds));
     const int max_lists = std::min(4 * device_cu_count(), 1024);   // the full scan's grid cap, which sized the scratch
-    const int P = (int)std::max<int64_t>(
+    int P = (int)std::max<int64_t>(
         1, std::min<int64_t>(std::min<int64_t>(per_cu * device_cu_count(), max_lists),
                              ((int64_t)G + kScanWaves - 1) / kScanWaves));
+    if (max_wg > 0) P = std::min(P, max_wg);
+    if (ran_wg) *ran_wg = P;
     if (in_lds)
         approx_scan_kernel<true><<<(unsigned)P, kScanThreads, lds, s>>>((const uint32_t *)codes, (const int2 *)d_table, n_docs,
                                                                         G, tscratch, C, QTq, nq, Lq, n_cand, (Hit *)scratch);

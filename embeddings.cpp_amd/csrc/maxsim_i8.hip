@@ -266,7 +266,7 @@ int launch_mv_pack_i8(const float *d_rows, int64_t t0, int64_t count, int w, con
 }
 
 int launch_maxsim_i8(const void *store, const float *scales, const void *d_table, int n_docs, int w, const float *d_q,
-                     int Lq, const int32_t *d_ids, int n, float *d_out, hipStream_t s)
+                     int Lq, const int32_t *d_ids, int n, float *d_out, hipStream_t s, int max_wg, int *ran_wg)
 {
     // (the candidate index advances by at most 4 * 4 * CUs per step, in int32)
     if (Lq < 1 || Lq > 64 || n < 1 || n > 0x7fff0000 || n_docs < 0 || w % 64 || w < 64 || w > 1024 || !scales) return -1;
@@ -275,7 +275,9 @@ int launch_maxsim_i8(const void *store, const float *scales, const void *d_table
     if (lds > (size_t)kLdsBudget) return -1;
     // as many workgroups per CU as the LDS holds, at most 4 (16 waves of 8 KiB in flight)
     const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (int64_t)kLdsBudget / (int64_t)lds));
-    const int64_t P = std::max<int64_t>(1, std::min<int64_t>(per_cu * device_cu_count(), ((int64_t)n + 3) / 4));
+    int64_t P = std::max<int64_t>(1, std::min<int64_t>(per_cu * device_cu_count(), ((int64_t)n + 3) / 4));
+    if (max_wg > 0) P = std::min<int64_t>(P, max_wg);
+    if (ran_wg) *ran_wg = (int)P;
     const i32x4 *S = (const i32x4 *)store;
     const int2 *T = (const int2 *)d_table;
     switch (QT) {

@@ -299,15 +299,16 @@ void launch_maxsim_res(unsigned P, size_t lds, hipStream_t s, const uint32_t *bi
 template <int NB>
 int launch_maxsim_res_nb(const uint32_t *bits, const float *u, const uint16_t *codes, const void *cent, const uint32_t *pair,
                          const void *d_table, int n_docs, int w, const float *d_q, int Lq, const int32_t *d_ids, int n,
-                         float *d_out, hipStream_t s)
+                         float *d_out, hipStream_t s, int max_wg, int *ran_wg)
 {
     const int QT = (Lq + 15) / 16;
     const size_t lds = res_lds_bytes(QT, w, NB);
     if (lds > (size_t)kLdsBudget) return -1;
     // as many workgroups per CU as the LDS holds, at most 4 (launch_maxsim's rule)
     const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (int64_t)kLdsBudget / (int64_t)lds));
-    const unsigned P =
-        (unsigned)std::max<int64_t>(1, std::min<int64_t>(per_cu * device_cu_count(), ((int64_t)n + 3) / 4));
+    unsigned P = (unsigned)std::max<int64_t>(1, std::min<int64_t>(per_cu * device_cu_count(), ((int64_t)n + 3) / 4));
+    if (max_wg > 0) P = std::min(P, (unsigned)max_wg);
+    if (ran_wg) *ran_wg = (int)P;
     switch (QT) {
     case 1: launch_maxsim_res<1, NB>(P, lds, s, bits, u, codes, cent, pair, d_table, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
     case 2: launch_maxsim_res<2, NB>(P, lds, s, bits, u, codes, cent, pair, d_table, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
@@ -359,13 +360,15 @@ int launch_res_encode(const void *staging, int64_t groups, int w, int nbits, con
 
 int launch_maxsim_res(const uint32_t *bits, const float *u, const uint16_t *codes, const void *cent, const uint32_t *pair,
                       int nbits, const void *d_table, int n_docs, int w, const float *d_q, int Lq, const int32_t *d_ids, int n,
-                      float *d_out, hipStream_t s)
+                      float *d_out, hipStream_t s, int max_wg, int *ran_wg)
 {
     if (Lq < 1 || Lq > 64 || n < 1 || n > 0x7fff0000 || n_docs < 0 || w % 64 || w < 64 || w > 1024 ||
         (nbits != 2 && nbits != 4) || !bits || !u || !pair)
         return -1;   // (codes and cent are read for stored documents only, which need them to exist)
-    return nbits == 2 ? launch_maxsim_res_nb<2>(bits, u, codes, cent, pair, d_table, n_docs, w, d_q, Lq, d_ids, n, d_out, s)
-                      : launch_maxsim_res_nb<4>(bits, u, codes, cent, pair, d_table, n_docs, w, d_q, Lq, d_ids, n, d_out, s);
+    return nbits == 2 ? launch_maxsim_res_nb<2>(bits, u, codes, cent, pair, d_table, n_docs, w, d_q, Lq, d_ids, n, d_out, s,
+                                                max_wg, ran_wg)
+                      : launch_maxsim_res_nb<4>(bits, u, codes, cent, pair, d_table, n_docs, w, d_q, Lq, d_ids, n, d_out, s,
+                                                max_wg, ran_wg);
 }
 
 }  // namespace emb

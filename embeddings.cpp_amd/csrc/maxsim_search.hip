@@ -387,7 +387,7 @@ void launch_pass(const void *store, const float *scales, const void *table, int 
 
 template <int ST>
 int launch_all(const void *store, const float *scales, const void *table, int n_docs, int G, int w, const float *d_q,
-               int B, int Lq, int k, void *scratch, float *d_scores, int32_t *d_ids, hipStream_t s)
+               int B, int Lq, int k, void *scratch, float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg, int *ran_wg)
 {
     const int QTq = (Lq + 15) / 16, per_pass = 4 / QTq;
     const int cus = device_cu_count();
@@ -397,7 +397,9 @@ int launch_all(const void *store, const float *scales, const void *table, int n_
         if (lds > (size_t)kLdsBudget) return -1;
         // as many workgroups per CU as the LDS holds, at most 4; never more waves than groups
         const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(kMaxWgPerCu, (int64_t)kLdsBudget / (int64_t)lds));
-        const int P = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(per_cu * cus, kMaxWg), ((int64_t)G + 3) / 4));
+        int P = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(per_cu * cus, kMaxWg), ((int64_t)G + 3) / 4));
+        if (max_wg > 0) P = std::min(P, max_wg);
+        if (ran_wg) *ran_wg = P;
         const float *Q = d_q + (size_t)b0 * Lq * w;
         Hit *part = (Hit *)scratch;
         switch (QTq * 8 + nq) {
@@ -450,7 +452,7 @@ size_t maxsim_search_scratch_bytes()
 
 int launch_maxsim_search(const void *store, const float *scales, int storage, const void *d_table, int n_docs,
                          int64_t used_groups, int w, const float *d_q, int B, int Lq, int k, void *scratch,
-                         float *d_scores, int32_t *d_ids, hipStream_t s)
+                         float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg, int *ran_wg)
 {
     if (B < 1 || Lq < 1 || Lq > 64 || k < 1 || k > 128 || n_docs < 0 || used_groups < 0 || used_groups > 0x7ffffff0ll ||
         w % 64 || w < 64 || w > 1024 || !scratch)
@@ -458,9 +460,9 @@ int launch_maxsim_search(const void *store, const float *scales, int storage, co
     if ((storage != SEARCH_F16 && storage != SEARCH_I8) || (storage == SEARCH_I8 && !scales)) return -1;
     if (storage == SEARCH_I8)
         return launch_all<SEARCH_I8>(store, scales, d_table, n_docs, (int)used_groups, w, d_q, B, Lq, k, scratch, d_scores,
-                                     d_ids, s);
+                                     d_ids, s, max_wg, ran_wg);
     return launch_all<SEARCH_F16>(store, nullptr, d_table, n_docs, (int)used_groups, w, d_q, B, Lq, k, scratch, d_scores,
-                                  d_ids, s);
+                                  d_ids, s, max_wg, ran_wg);
 }
 
 }  // namespace emb

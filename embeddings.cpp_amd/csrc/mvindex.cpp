@@ -44,6 +44,9 @@ struct bertx_mvindex {
     // staging of the host forms
     float *st_rows = nullptr, *st_q = nullptr, *st_out = nullptr;
     int32_t *st_ids = nullptr, *st_tok = nullptr;
+    // test hook (bertx_test_mvindex_grid): a positive grid_cap bounds the workgroups of every scan
+    // launched for this store; last_grid: the scan kernel's workgroups at the latest such launch
+    int grid_cap = 0, last_grid = 0;
     void *search_scratch = nullptr;        // the partial lists of the full-scan search (maxsim_search_scratch_bytes)
     // centroid codes (set_centroids; all null / 0 before): the C centroids packed as one
     // document of their own buffer, their f32 (int8), one code per token slot, the table of
@@ -271,11 +274,13 @@ int32_t score_launch(bertx_mvindex &mv, const float *d_q, int32_t Lq, const int3
                      hipStream_t s)
 {
     if (mv.storage == BERTX_INDEX_I8)
-        return launch_maxsim_i8(mv.store, mv.scales, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s);
+        return launch_maxsim_i8(mv.store, mv.scales, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s,
+                                mv.grid_cap, &mv.last_grid);
     if (const int nb = res_nbits(mv))
         return launch_maxsim_res(mv.res_bits, mv.res_u, mv.codes, mv.cent, mv.res_pair, nb, mv.table, (int)mv.n_docs, mv.w,
-                                 d_q, Lq, d_ids, n, d_out, s);
-    return launch_maxsim(mv.store, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s);
+                                 d_q, Lq, d_ids, n, d_out, s, mv.grid_cap, &mv.last_grid);
+    return launch_maxsim(mv.store, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s, mv.grid_cap,
+                         &mv.last_grid);
 }
 
 int32_t score_device_locked(bertx_mvindex &mv, const float *d_q, int32_t Lq, const int32_t *d_ids, int32_t n,
@@ -300,7 +305,7 @@ int32_t search_device_locked(bertx_mvindex &mv, const float *d_q, int32_t B, int
     if (full_scan_refused(mv, "bertx_mvindex_search")) return -1;
     Ordered o(mv.ord, s);
     return launch_maxsim_search(mv.store, mv.scales, mv.storage, mv.table, (int)mv.n_docs, mv.used_slots / 16, mv.w, d_q, B,
-                                Lq, k, mv.search_scratch, d_scores, d_ids, s);
+                                Lq, k, mv.search_scratch, d_scores, d_ids, s, mv.grid_cap, &mv.last_grid);
 }
 
 // The query already on the device (mv.st_q or a caller's buffer on the store's stream):
@@ -487,7 +492,8 @@ int32_t candidates_launch(bertx_mvindex &mv, const float *d_q, int32_t B, int32_
         const int32_t rc = launch_maxsim_candidates(mv.codes, mv.table, (int)mv.n_docs, mv.used_slots / 16, cent_kind(mv), mv.w,
                                                     mv.cent, mv.cent_u, mv.C, d_q + (size_t)b0 * Lq * mv.w,
                                                     std::min(per_pass, B - b0), Lq, n_cand, mv.tscratch, mv.search_scratch,
-                                                    d_approx + (size_t)b0 * n_cand, d_ids + (size_t)b0 * n_cand, 3, &form, s);
+                                                    d_approx + (size_t)b0 * n_cand, d_ids + (size_t)b0 * n_cand, 3, &form, s,
+                                                    mv.grid_cap, &mv.last_grid);
         if (rc != 0) return rc;
         g_approx_forms.fetch_or(form);
     }
@@ -1589,6 +1595,22 @@ int32_t bertx_test_kmeans_sample(int64_t T, uint32_t seed, int64_t *out3)
 int32_t bertx_test_approx_ran(int32_t reset)
 {
     return reset ? emb::g_approx_forms.exchange(0) : emb::g_approx_forms.load();
+}
+
+int32_t bertx_test_mvindex_grid(struct bertx_mvindex *mv, int32_t max_wg)
+{
+    if (!mv || max_wg < 0) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    const int32_t before = mv->grid_cap;
+    mv->grid_cap = max_wg;
+    return before;
+}
+
+int32_t bertx_test_mvindex_last_grid(struct bertx_mvindex *mv)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    return mv->last_grid;
 }
 
 int32_t bertx_mvindex_candidates_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq, int32_t n_cand,

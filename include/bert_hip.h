@@ -963,6 +963,19 @@ BERT_API int32_t bertx_bench_maxsim_res(int32_t w, int32_t n_docs, int32_t doc_l
  * (kmeans_update.h): one update in place, returning the centroids without a member; the
  * sample rule, out3 = {stride, start, n_sample}. */
 BERT_API int32_t bertx_test_approx_ran(int32_t reset);
+/* Test hooks: a cap on the grids of one store's scans.  The scorers, the full scan and the
+ * centroid scan size their grids by the device's CU count, so at a test's store a wave sees
+ * a handful of documents where production gives it hundreds.  max_wg > 0 bounds the
+ * workgroups of every scan kernel launched for this store from then on (score, search,
+ * candidates, search_pruned, their _device and text forms), applied after the launcher's
+ * own rule and before the selection levels that follow from it; 0 removes the cap.  Returns
+ * the previous value, or -1 for a negative max_wg (or a null store) with nothing changed.
+ * A capped scan returns what the uncapped one returns, bit for bit: a score depends on the
+ * query and the document alone.
+ * bertx_test_mvindex_last_grid: the workgroups of the scan kernel (not of the selection
+ * behind it) at the store's most recent scan launch, 0 before the first. */
+BERT_API int32_t bertx_test_mvindex_grid(struct bertx_mvindex *mv, int32_t max_wg);
+BERT_API int32_t bertx_test_mvindex_last_grid(struct bertx_mvindex *mv);
 BERT_API int32_t bertx_test_kmeans_update(const float *sample, const uint16_t *codes, int32_t n, int32_t w, int32_t C,
                                           float *cent);
 BERT_API int32_t bertx_test_kmeans_sample(int64_t T, uint32_t seed, int64_t *out3);
