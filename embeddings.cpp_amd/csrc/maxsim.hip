@@ -17,23 +17,18 @@
 // an f32 accumulator from 0), the max is exact, the sum over i is f32 in an order
 // fixed by Lq alone.  One wave scores one whole document, so a score depends on the
 // query and the document's own rows only, bit for bit.
-#include "device_common.h"
-#include "kernels.h"
-#include "maxsim_pack.h"
-
-#include <algorithm>
+#include "maxsim_common.h"
 
 namespace emb {
 namespace {
 
 constexpr int kThreads = 256;      // 4 waves, each scores whole documents on its own
 constexpr int kRingUnits = 4;      // prefetch ring per wave: 4 units of 2 blocks = 8 KiB in flight
-constexpr int kLdsBudget = 160 * 1024;
 
 // Source rows t0 .. t0 + count - 1 of one add call (rows = row t0) into their slots; one
-// wave per row.  src_off[i] (i < n_new, ascending, src_off[0] = 0) is the first source
-// row of the call's i-th document, table[i] = (first group, len) of it: row t belongs
-// to the last document whose src_off is <= t and goes to slot 16 first + (t - src_off).
+// wave per row.  src_off says which of the call's n_new documents a row belongs to
+// (maxsim_common.h source_doc), table[that document] = (first group, len) where it goes:
+// slot 16 first + (t - src_off).
 __global__ __launch_bounds__(kThreads) void mv_pack_kernel(const float *__restrict__ rows, int64_t t0, int64_t count,
                                                            int w, const int32_t *__restrict__ src_off,
                                                            const int2 *__restrict__ table, int n_new,
@@ -43,13 +38,9 @@ __global__ __launch_bounds__(kThreads) void mv_pack_kernel(const float *__restri
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= count) return;
     const int64_t t = t0 + r;
-    int lo = 0, hi = n_new - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((int64_t)src_off[mid] <= t) lo = mid; else hi = mid - 1;
-    }
-    const int2 e = table[lo];
-    const int64_t j = t - src_off[lo];
+    const int d = source_doc(src_off, n_new, t);
+    const int2 e = table[d];
+    const int64_t j = t - src_off[d];
     if (j >= e.y) return;   // (never: the host sizes count by the lens)
     h16x8 v[2];
     pack_row_f16(rows + (size_t)r * w, w, lane, v);
@@ -64,17 +55,15 @@ __global__ __launch_bounds__(kThreads) void mv_pack_kernel(const float *__restri
 
 __host__ __device__ inline size_t maxsim_lds_bytes(int QT, int w) { return (size_t)QT * 16 * w * 2; }
 
-// Persistent workgroups.  Prologue: the Lq query rows normalised (pack_row_f16, one wave
-// per row) into B fragments in LDS, lane 16g + c of block (t, kb) = query 16t + c,
-// elements 32kb + 8g .. + 7; queries Lq .. 16 QT - 1 are zeros.  Then wave v of the
+// Persistent workgroups.  Prologue: the Lq query rows normalised into B fragments in LDS
+// (maxsim_common.h pack_queries, one query of QT tiles).  Then wave v of the
 // grid takes candidates v, v + waves, ...: no barrier and no cross-wave step follows
 // the prologue.  Per candidate: the document's ceil(len / 16) w / 32 blocks stream
 // through a register ring of kRingUnits units of 2 blocks (loads past the document's
 // last block re-read that block); after a group's last block accumulator register r
 // of lane 16g + c is (row 4g + r of the group, query c): rows >= len become -inf and
 // the four fold into the lane's running maxima, which start at -inf.  After the
-// document two shuffles per tile fold the four g, lane c adds its columns c, 16 + c,
-// ... (a padded column adds +0), a 16-lane butterfly adds the lanes, lane 0 stores.
+// document the epilogue (maxsim_common.h doc_score) sums the maxima; lane 0 stores.
 // An id outside [0, n_docs) gets -inf and touches nothing else.
 template <int QT>
 __global__ __launch_bounds__(kThreads) void maxsim_kernel(const h16x8 *__restrict__ store,
@@ -88,6 +77,8 @@ __global__ __launch_bounds__(kThreads) void maxsim_kernel(const h16x8 *__restric
     const int KB = w >> 5, chunks = w >> 3;
     h16x8 *qf = (h16x8 *)smem;                                    // [QT][KB][64]
 
+    // pack_queries<SEARCH_F16>(q, Tiles<1>, Tiles<QT>, ...) written out: called as a function
+    // it costs maxsim_kernel<1> two registers in the ring loop
     for (int i = wv; i < QT * 16; i += 4) {
         h16x8 v[2] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
         if (i < Lq) pack_row_f16(q + (size_t)i * w, w, lane, v);
@@ -165,34 +156,18 @@ __global__ __launch_bounds__(kThreads) void maxsim_kernel(const h16x8 *__restric
             }
         }
     done:
-        float s = 0.f;
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            float m = mx[t];
-            m = fmaxf(m, __shfl_xor(m, 16, 64));
-            m = fmaxf(m, __shfl_xor(m, 32, 64));
-            s = __fadd_rn(s, 16 * t + (lane & 15) < Lq ? m : 0.f);
-        }
-#pragma unroll
-        for (int o = 8; o >= 1; o >>= 1) s = __fadd_rn(s, __shfl_xor(s, o, 64));
+        const float s = doc_score<QT>(mx, Lq, lane);
         if (lane == 0) out[c] = s;
     }
-}
-
-template <int QT>
-hipError_t allow_lds()
-{
-    return hipFuncSetAttribute((const void *)maxsim_kernel<QT>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
 }
 
 }  // namespace
 
 int maxsim_prepare_device()
 {
-    hipError_t e = allow_lds<1>();
-    if (e == hipSuccess) e = allow_lds<2>();
-    if (e == hipSuccess) e = allow_lds<3>();
-    if (e == hipSuccess) e = allow_lds<4>();
+    hipError_t e = hipSuccess;
+    for (int qt = 1; qt <= 4 && e == hipSuccess; ++qt)
+        with_tiles(qt, [&](auto QT) { e = allow_lds((const void *)maxsim_kernel<decltype(QT)::value>); });
     return e == hipSuccess ? maxsim_i8_prepare_device() : -1;
 }
 
@@ -215,19 +190,11 @@ int launch_maxsim(const void *store, const void *d_table, int n_docs, int w, con
     const int QT = (Lq + 15) / 16;
     const size_t lds = maxsim_lds_bytes(QT, w);
     if (lds > (size_t)kLdsBudget) return -1;
-    // as many workgroups per CU as the LDS holds, at most 4 (16 waves of 8 KiB in flight)
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (int64_t)kLdsBudget / (int64_t)lds));
-    int64_t P = std::max<int64_t>(1, std::min<int64_t>(per_cu * device_cu_count(), ((int64_t)n + 3) / 4));
-    if (max_wg > 0) P = std::min<int64_t>(P, max_wg);
-    if (ran_wg) *ran_wg = (int)P;
-    const h16x8 *S = (const h16x8 *)store;
-    const int2 *T = (const int2 *)d_table;
-    switch (QT) {
-    case 1: maxsim_kernel<1><<<(unsigned)P, kThreads, lds, s>>>(S, T, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
-    case 2: maxsim_kernel<2><<<(unsigned)P, kThreads, lds, s>>>(S, T, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
-    case 3: maxsim_kernel<3><<<(unsigned)P, kThreads, lds, s>>>(S, T, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
-    default: maxsim_kernel<4><<<(unsigned)P, kThreads, lds, s>>>(S, T, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
-    }
+    const unsigned P = (unsigned)scorer_grid(lds, n, max_wg, ran_wg);
+    with_tiles(QT, [&](auto qt) {
+        maxsim_kernel<decltype(qt)::value><<<P, kThreads, lds, s>>>((const h16x8 *)store, (const int2 *)d_table, n_docs, d_q,
+                                                                    Lq, w, d_ids, n, d_out);
+    });
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -12,13 +12,8 @@
 // centroids cent[code_j]: the same sims, the exact max, lane c's sum of its query's
 // columns c, 16 + c, ... in ascending order from +0 (a row >= Lq adds +0) and the
 // four-step butterfly.  One wave scores one whole document.
-#include "device_common.h"
-#include "kernels.h"
-#include "maxsim_pack.h"
-#include "quant_i8.h"
+#include "maxsim_common.h"
 #include "topk_list.h"
-
-#include <algorithm>
 
 namespace emb {
 namespace {
@@ -26,35 +21,11 @@ namespace {
 constexpr int kTableThreads = 256;  // 4 waves, each takes one centroid group
 constexpr int kScanThreads = 512;   // 8 waves share one copy of the table in LDS
 constexpr int kScanWaves = kScanThreads / 64;
-constexpr int kLdsBudget = 160 * 1024;
-constexpr int kMaxWgPerCu = 4;      // up to 32 waves per CU where the table leaves the LDS for it
+// (kMaxWgPerCu workgroups of it: up to 32 waves per CU where the table leaves the LDS for it)
 
 // The floats of one line of the table: 16 per tile, three tiles padded to four, so that a
 // code becomes an address by a shift.
 __host__ __device__ inline int line_floats(int TT) { return TT == 3 ? 64 : 16 * TT; }
-
-template <int ST> struct Kind;
-template <> struct Kind<SEARCH_F16> {
-    typedef h16x8 Block;
-    typedef f32x4 Acc;
-    static constexpr int kShift = 5;
-    __host__ __device__ static constexpr size_t row_bytes(int w) { return (size_t)w * 2; }
-};
-template <> struct Kind<SEARCH_I8> {
-    typedef i32x4 Block;
-    typedef i32x4 Acc;
-    static constexpr int kShift = 6;
-    __host__ __device__ static constexpr size_t row_bytes(int w) { return (size_t)w; }
-};
-
-__device__ __forceinline__ f32x4 mma(h16x8 a, h16x8 b, f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ i32x4 mma(i32x4 a, i32x4 b, i32x4 c)
-{
-    return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
-}
 
 template <int ST>
 __host__ __device__ inline size_t table_lds_bytes(int TT, int w)
@@ -63,8 +34,8 @@ __host__ __device__ inline size_t table_lds_bytes(int TT, int w)
 }
 
 // NQ queries of QTq tiles each, q f32 [NQ][Lq][w], TT = QTq NQ <= 4 tiles.  The prologue is
-// maxsim_search_kernel's: tile t = QTq * (query of the pass) + (tile of the query), its rows
-// packed as the scorers pack theirs, rows >= Lq of a query zeros (u = 0).  Wave v of the
+// the scorers' (maxsim_common.h pack_queries): tile t = QTq * (query of the pass) + (tile of
+// the query).  Wave v of the
 // grid takes centroid group v: its blocks in ascending k against every tile from zero
 // accumulators; accumulator register r of lane 16g + c is (centroid 16 cg + 4g + r, query
 // row c of tile t) and goes to T[centroid][16 t + c].
@@ -83,25 +54,7 @@ __global__ __launch_bounds__(kTableThreads) void approx_table_kernel(const typen
     Block *qf = (Block *)smem;                                    // [TT][KB][64]
     float *qu = (float *)(qf + (size_t)TT * KB * 64);             // [64]
 
-    for (int i = wv; i < TT * 16; i += 4) {
-        const int t = i >> 4, qi = t / QTq, rq = ((t - qi * QTq) << 4) + (i & 15);
-        const float *src = q + ((size_t)qi * Lq + min(rq, Lq - 1)) * w;
-        if constexpr (ST == SEARCH_F16) {
-            h16x8 v[2] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
-            if (rq < Lq) pack_row_f16(src, w, lane, v);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int c = lane + 64 * j;
-                if (c < (w >> 3)) qf[frag_index(i, c, KB)] = v[j];
-            }
-        } else {
-            i32x4 v = {0, 0, 0, 0};
-            float u = 0.f;
-            if (rq < Lq) v = pack_row_i8(src, w, lane, u);
-            if (lane < (w >> 4)) qf[frag_index(i, lane, KB)] = v;
-            if (lane == 0) qu[i] = u;
-        }
-    }
+    pack_queries<ST>(q, NQ, QTq, Lq, w, qf, qu, wv, lane);
     lds_barrier();
 
     const int cg = (int)blockIdx.x * 4 + wv;
@@ -126,32 +79,15 @@ __global__ __launch_bounds__(kTableThreads) void approx_table_kernel(const typen
         float uq = 0.f;
         if constexpr (ST == SEARCH_I8) uq = qu[16 * t + c];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float sim;
-            if constexpr (ST == SEARCH_I8) sim = score_i8(acc[t][r], uq, urow[r]);
-            else sim = acc[t][r];
-            T[(size_t)(16 * cg + 4 * g4 + r) * LINE + 16 * t + c] = sim;
-        }
+        for (int r = 0; r < 4; ++r) T[(size_t)(16 * cg + 4 * g4 + r) * LINE + 16 * t + c] = sim(acc[t][r], uq, urow[r]);
     }
-}
-
-typedef const __attribute__((address_space(4))) int2 *TablePtr;
-
-__device__ __forceinline__ int first_doc_at(TablePtr tab, int n_docs, int g)
-{
-    int lo = 0, hi = n_docs;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (tab[mid].x < g) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 __host__ __device__ inline size_t scan_list_bytes(int NQ, int n_cand) { return (size_t)kScanWaves * NQ * n_cand * sizeof(Hit); }
 
 // The documents are dealt to the grid's waves as maxsim_search_kernel deals them: wave v of
 // W takes those whose first group lies in [v G / W, (v + 1) G / W), one contiguous run of
-// groups.  Lane l stands for column min(l, 16 TT - 1) of the table's lines: query row l & 15
+// groups (maxsim_common.h first_doc_at).  Lane l stands for column min(l, 16 TT - 1) of the table's lines: query row l & 15
 // of tile l >> 4.  The run's codes come 128 at a time, one dword (two codes) per lane, the
 // load after next always in flight (loads past the run re-read its last dword); a group's
 // eight dwords are read out of the lanes into scalar registers, so a code is wave-uniform
@@ -409,17 +345,10 @@ int launch_table(const void *cent, const float *cent_u, int C, const float *Q, i
 
 int maxsim_approx_prepare_device()
 {
-    hipError_t e = hipFuncSetAttribute((const void *)approx_table_kernel<SEARCH_F16>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void *)approx_table_kernel<SEARCH_I8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kLdsBudget);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void *)approx_scan_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kLdsBudget);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void *)approx_scan_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kLdsBudget);
+    hipError_t e = allow_lds((const void *)approx_table_kernel<SEARCH_F16>);
+    if (e == hipSuccess) e = allow_lds((const void *)approx_table_kernel<SEARCH_I8>);
+    if (e == hipSuccess) e = allow_lds((const void *)approx_scan_kernel<true>);
+    if (e == hipSuccess) e = allow_lds((const void *)approx_scan_kernel<false>);
     return e == hipSuccess ? 0 : -1;
 }
 
@@ -445,13 +374,7 @@ int launch_maxsim_candidates(const uint16_t *codes, const void *d_table, int n_d
     const size_t tbytes = (size_t)4 * line_floats(QTq * nq) * C;
     const bool in_lds = lists + tbytes <= (size_t)kLdsBudget;
     const size_t lds = in_lds ? lists + tbytes : lists;
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(kMaxWgPerCu, (int64_t)kLdsBudget / (int64_t)lds));
-    const int max_lists = std::min(4 * device_cu_count(), 1024);   // the full scan's grid cap, which sized the scratch
-    int P = (int)std::max<int64_t>(
-        1, std::min<int64_t>(std::min<int64_t>(per_cu * device_cu_count(), max_lists),
-                             ((int64_t)G + kScanWaves - 1) / kScanWaves));
-    if (max_wg > 0) P = std::min(P, max_wg);
-    if (ran_wg) *ran_wg = P;
+    const int P = scan_grid(lds, G, kScanWaves, max_wg, ran_wg);   // the full scan's rule, which sized the scratch
     if (in_lds)
         approx_scan_kernel<true><<<(unsigned)P, kScanThreads, lds, s>>>((const uint32_t *)codes, (const int2 *)d_table, n_docs,
                                                                         G, tscratch, C, QTq, nq, Lq, n_cand, (Hit *)scratch);
@@ -463,7 +386,7 @@ int launch_maxsim_candidates(const uint16_t *codes, const void *d_table, int n_d
     if (form) *form = in_lds ? 1 : 2;
     // the n_cand best of the P lists per query: one level up to kMergeSeg lists, else two
     // (the first level's lists lie behind the grid's, the layout of maxsim_search_scratch_bytes)
-    Hit *part = (Hit *)scratch, *part2 = part + (size_t)4 * max_lists * 128;
+    Hit *part = (Hit *)scratch, *part2 = part + (size_t)4 * scan_max_lists() * 128;
     const int S = (P + kMergeSeg - 1) / kMergeSeg;
     if (S > 1) {
         merge_select_kernel<<<dim3((unsigned)nq, (unsigned)S), 64, 0, s>>>(part, P, n_cand, kMergeSeg, part2, nullptr, nullptr);

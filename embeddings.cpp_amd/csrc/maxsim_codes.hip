@@ -8,41 +8,12 @@
 // in the stored-row role of the scorers' MFMA sequence, ascending k from a zero
 // accumulator, and the centroid of highest sim wins, equal sims going to the lower index.
 // A row stored as zeros has sim 0 to every centroid and gets code 0.
-#include "device_common.h"
-#include "kernels.h"
-#include "maxsim_pack.h"
-#include "quant_i8.h"
-
-#include <algorithm>
+#include "maxsim_common.h"
 
 namespace emb {
 namespace {
 
 constexpr int kThreads = 256;      // 4 waves, each codes one 16-slot group of the store
-constexpr int kLdsBudget = 160 * 1024;
-
-template <int ST> struct Kind;
-template <> struct Kind<SEARCH_F16> {
-    typedef h16x8 Block;
-    typedef f32x4 Acc;
-    static constexpr int kShift = 5;
-    __host__ __device__ static constexpr size_t row_bytes(int w) { return (size_t)w * 2; }
-};
-template <> struct Kind<SEARCH_I8> {
-    typedef i32x4 Block;
-    typedef i32x4 Acc;
-    static constexpr int kShift = 6;
-    __host__ __device__ static constexpr size_t row_bytes(int w) { return (size_t)w; }
-};
-
-__device__ __forceinline__ f32x4 mma(h16x8 a, h16x8 b, f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ i32x4 mma(i32x4 a, i32x4 b, i32x4 c)
-{
-    return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
-}
 
 // LDS per wave: the 16 rows as query fragments, one widened row, the 16 query u.
 template <int ST>
@@ -134,11 +105,9 @@ __global__ __launch_bounds__(kThreads) void mv_assign_kernel(const typename Kind
         const float urow[4] = {ur.x, ur.y, ur.z, ur.w};
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            float sim;
-            if constexpr (ST == SEARCH_I8) sim = score_i8(acc[r], uq, urow[r]);
-            else sim = acc[r];
-            if (sim > best) {
-                best = sim;
+            const float s = sim(acc[r], uq, urow[r]);
+            if (s > best) {
+                best = s;
                 bi = 16 * cg + 4 * g4 + r;
             }
         }
@@ -185,11 +154,8 @@ int launch_assign(const void *store, const float *scales, int64_t g0, int64_t g1
 
 int maxsim_codes_prepare_device()
 {
-    hipError_t e = hipFuncSetAttribute((const void *)mv_assign_kernel<SEARCH_F16>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void *)mv_assign_kernel<SEARCH_I8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kLdsBudget);
+    hipError_t e = allow_lds((const void *)mv_assign_kernel<SEARCH_F16>);
+    if (e == hipSuccess) e = allow_lds((const void *)mv_assign_kernel<SEARCH_I8>);
     return e == hipSuccess ? 0 : -1;
 }
 

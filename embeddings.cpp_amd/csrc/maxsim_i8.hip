@@ -15,19 +15,13 @@
 // sim(a, c) = score_i8(isum, u_a, u_c) with the exact int32 isum of v_mfma_i32_16x16x64_i8;
 // score(doc) = sum_{i < Lq} max_{j < len} sim(q_i, c_j), the max exact and the sum in the
 // order of maxsim_kernel.  No step depends on an order the caller cannot reproduce.
-#include "device_common.h"
-#include "kernels.h"
-#include "maxsim_pack.h"
-#include "quant_i8.h"
-
-#include <algorithm>
+#include "maxsim_common.h"
 
 namespace emb {
 namespace {
 
 constexpr int kThreads = 256;      // 4 waves, each scores whole documents on its own
 constexpr int kRingUnits = 8;      // prefetch ring per wave: 8 units of 1 block = 8 KiB in flight
-constexpr int kLdsBudget = 160 * 1024;
 
 // mv_pack_kernel over an int8 store: the same (src_off, table) lookup, one wave per row.
 __global__ __launch_bounds__(kThreads) void mv_pack_i8_kernel(const float *__restrict__ rows, int64_t t0, int64_t count,
@@ -39,13 +33,9 @@ __global__ __launch_bounds__(kThreads) void mv_pack_i8_kernel(const float *__res
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= count) return;
     const int64_t t = t0 + r;
-    int lo = 0, hi = n_new - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((int64_t)src_off[mid] <= t) lo = mid; else hi = mid - 1;
-    }
-    const int2 e = table[lo];
-    const int64_t j = t - src_off[lo];
+    const int d = source_doc(src_off, n_new, t);
+    const int2 e = table[d];
+    const int64_t j = t - src_off[d];
     if (j >= e.y) return;   // (never: the host sizes count by the lens)
     float u;
     const i32x4 v = pack_row_i8(rows + (size_t)r * w, w, lane, u);
@@ -65,7 +55,7 @@ __host__ __device__ inline size_t maxsim_i8_lds_bytes(int QT, int w) { return (s
 // past the document's last block re-read that block), in whole passes over the ring and
 // a tail (below).  A unit is one block and one dword per lane of its group's u:
 // lane 16g + c asks for the u of row 4g + (c & 3), so the four u a lane needs sit in its
-// own quad and come out by four DPP moves.  The u ride in the ring, not a group ahead
+// own quad and come out by four DPP moves (maxsim_common.h quad_u).  The u ride in the ring, not a group ahead
 // through the scalar cache as search.hip's do: a wave that scores one document alone
 // (1,000 candidates) would wait out one scalar miss per group, and a vector load issued
 // out of ring order would drain the ring through the in-order vector-memory counter.
@@ -74,7 +64,7 @@ __host__ __device__ inline size_t maxsim_i8_lds_bytes(int QT, int w) { return (s
 // always inside the buffer.  After a group's last block accumulator register r of lane
 // 16g + c is (row 4g + r of the group, query c): sim = score_i8(acc, u_query, u_row),
 // rows >= len select -inf, and the four fold into the lane's running maxima.  The
-// epilogue is maxsim_kernel's.
+// epilogue is the scorers' one (maxsim_common.h doc_score).
 // An id outside [0, n_docs) gets -inf and touches nothing else.
 template <int QT>
 __global__ __launch_bounds__(kThreads) void maxsim_i8_kernel(const i32x4 *__restrict__ store,
@@ -181,11 +171,8 @@ __global__ __launch_bounds__(kThreads) void maxsim_i8_kernel(const i32x4 *__rest
             // unit and before the refill, so that the slot's old dword is dead when the
             // new one is asked for (else the compiler keeps both and waits for every load
             // in flight to copy one over the other)
-            const int ug = __float_as_int(ring_u[j]);
-            const float rrow[4] = {__int_as_float(__builtin_amdgcn_mov_dpp(ug, 0x00, 0xf, 0xf, false)),
-                                   __int_as_float(__builtin_amdgcn_mov_dpp(ug, 0x55, 0xf, 0xf, false)),
-                                   __int_as_float(__builtin_amdgcn_mov_dpp(ug, 0xaa, 0xf, 0xf, false)),
-                                   __int_as_float(__builtin_amdgcn_mov_dpp(ug, 0xff, 0xf, 0xf, false))};
+            float rrow[4];
+            quad_u(ring_u[j], rrow);
 #pragma unroll
             for (int t = 0; t < QT; ++t) {
                 const i32x4 b = qf[((size_t)t * KB + kb) * 64 + lane];
@@ -222,35 +209,18 @@ __global__ __launch_bounds__(kThreads) void maxsim_i8_kernel(const i32x4 *__rest
             if (u0 + j >= U) break;   // wave-uniform
             unit(j, false);
         }
-        float s = 0.f;
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            float m = mx[t];
-            m = fmaxf(m, __shfl_xor(m, 16, 64));
-            m = fmaxf(m, __shfl_xor(m, 32, 64));
-            s = __fadd_rn(s, 16 * t + (lane & 15) < Lq ? m : 0.f);
-        }
-#pragma unroll
-        for (int o = 8; o >= 1; o >>= 1) s = __fadd_rn(s, __shfl_xor(s, o, 64));
+        const float s = doc_score<QT>(mx, Lq, lane);
         if (lane == 0) out[c] = s;
     }
-}
-
-template <int QT>
-hipError_t allow_lds()
-{
-    return hipFuncSetAttribute((const void *)maxsim_i8_kernel<QT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               kLdsBudget);
 }
 
 }  // namespace
 
 int maxsim_i8_prepare_device()
 {
-    hipError_t e = allow_lds<1>();
-    if (e == hipSuccess) e = allow_lds<2>();
-    if (e == hipSuccess) e = allow_lds<3>();
-    if (e == hipSuccess) e = allow_lds<4>();
+    hipError_t e = hipSuccess;
+    for (int qt = 1; qt <= 4 && e == hipSuccess; ++qt)
+        with_tiles(qt, [&](auto QT) { e = allow_lds((const void *)maxsim_i8_kernel<decltype(QT)::value>); });
     return e == hipSuccess ? 0 : -1;
 }
 
@@ -273,19 +243,11 @@ int launch_maxsim_i8(const void *store, const float *scales, const void *d_table
     const int QT = (Lq + 15) / 16;
     const size_t lds = maxsim_i8_lds_bytes(QT, w);
     if (lds > (size_t)kLdsBudget) return -1;
-    // as many workgroups per CU as the LDS holds, at most 4 (16 waves of 8 KiB in flight)
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (int64_t)kLdsBudget / (int64_t)lds));
-    int64_t P = std::max<int64_t>(1, std::min<int64_t>(per_cu * device_cu_count(), ((int64_t)n + 3) / 4));
-    if (max_wg > 0) P = std::min<int64_t>(P, max_wg);
-    if (ran_wg) *ran_wg = (int)P;
-    const i32x4 *S = (const i32x4 *)store;
-    const int2 *T = (const int2 *)d_table;
-    switch (QT) {
-    case 1: maxsim_i8_kernel<1><<<(unsigned)P, kThreads, lds, s>>>(S, scales, T, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
-    case 2: maxsim_i8_kernel<2><<<(unsigned)P, kThreads, lds, s>>>(S, scales, T, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
-    case 3: maxsim_i8_kernel<3><<<(unsigned)P, kThreads, lds, s>>>(S, scales, T, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
-    default: maxsim_i8_kernel<4><<<(unsigned)P, kThreads, lds, s>>>(S, scales, T, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
-    }
+    const unsigned P = (unsigned)scorer_grid(lds, n, max_wg, ran_wg);
+    with_tiles(QT, [&](auto qt) {
+        maxsim_i8_kernel<decltype(qt)::value><<<P, kThreads, lds, s>>>((const i32x4 *)store, scales, (const int2 *)d_table,
+                                                                       n_docs, d_q, Lq, w, d_ids, n, d_out);
+    });
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -14,18 +14,13 @@
 // That is the canonical order of bertx_mvindex_doc_residual cut into 2- or 4-byte pieces
 // (element i in byte i NB / 8 at bit NB (i mod 8 / NB)); unpack_res_bits below and
 // mvindex.cpp's reader are its inverse.
-#include "device_common.h"
-#include "kernels.h"
-#include "maxsim_pack.h"
-
-#include <algorithm>
+#include "maxsim_common.h"
 
 namespace emb {
 namespace {
 
 constexpr int kThreads = 256;      // 4 waves: each scores whole documents / encodes one group on its own
 constexpr int kRingUnits = 4;      // prefetch ring per wave: 4 units of 2 gathered chunks and their bits
-constexpr int kLdsBudget = 160 * 1024;
 
 // The staging table of an add: the call's documents with their first groups counted from
 // the call's first group, so that the f16 pack and assign kernels see a store of their own.
@@ -113,8 +108,8 @@ __host__ __device__ inline size_t res_lds_bytes(int QT, int w, int NB)
 }
 
 // maxsim_kernel's skeleton (maxsim.hip): persistent workgroups, the query normalised into B
-// fragments in LDS in the prologue, beside them the pair table pt[b0 | b1 << NB] = the
-// packed f16 (wt[b0], wt[b1]); then wave v of the grid takes candidates v, v + waves, ...
+// fragments in LDS in the prologue (maxsim_common.h pack_queries), beside them the pair
+// table pt[b0 | b1 << NB] = the packed f16 (wt[b0], wt[b1]); then wave v of the grid takes candidates v, v + waves, ...
 // with no barrier and no cross-wave step.  Per candidate a load cursor runs kRingUnits
 // units ahead of the MFMAs: per unit (two blocks of a 16-slot group) lane 16g + f gathers
 // the two 16-byte chunks of row f's centroid from the centroid image and loads the unit's
@@ -124,7 +119,7 @@ __host__ __device__ inline size_t res_lds_bytes(int QT, int w, int NB)
 // (one ds_read_b32), one packed f16 add gives two elements of the A fragment.  After a
 // group's last block accumulator register r of lane 16g + c is (row 4g + r, query c): it is
 // multiplied by u[4g + r], rows >= len become -inf, and the four fold into the lane's
-// running maximum.  The epilogue is maxsim_kernel's.
+// running maximum.  The epilogue is the scorers' one (maxsim_common.h doc_score).
 template <int QT, int NB>
 __global__ __launch_bounds__(kThreads) void maxsim_res_kernel(const uint32_t *__restrict__ bits,
                                                               const float *__restrict__ us,
@@ -140,19 +135,11 @@ __global__ __launch_bounds__(kThreads) void maxsim_res_kernel(const uint32_t *__
     typedef uint32_t Bits __attribute__((ext_vector_type(DW)));
     extern __shared__ uint4 smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int KB = w >> 5, chunks = w >> 3, UG = KB >> 1;
+    const int KB = w >> 5, UG = KB >> 1;
     h16x8 *qf = (h16x8 *)smem;                                    // [QT][KB][64]
     const uint32_t *pt = (const uint32_t *)(qf + (size_t)QT * KB * 64);   // [NP]
 
-    for (int i = wv; i < QT * 16; i += 4) {
-        h16x8 v[2] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
-        if (i < Lq) pack_row_f16(q + (size_t)i * w, w, lane, v);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int c = lane + 64 * k;
-            if (c < chunks) qf[frag_index(i, c, KB)] = v[k];
-        }
-    }
+    pack_queries<SEARCH_F16>(q, Tiles<1>{}, Tiles<QT>{}, Lq, w, qf, nullptr, wv, lane);
     for (int i = tid; i < NP; i += kThreads) ((uint32_t *)pt)[i] = pair[i];
     lds_barrier();
 
@@ -266,34 +253,9 @@ __global__ __launch_bounds__(kThreads) void maxsim_res_kernel(const uint32_t *__
             }
         }
     done:
-        float s = 0.f;
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            float m = mx[t];
-            m = fmaxf(m, __shfl_xor(m, 16, 64));
-            m = fmaxf(m, __shfl_xor(m, 32, 64));
-            s = __fadd_rn(s, 16 * t + f < Lq ? m : 0.f);
-        }
-#pragma unroll
-        for (int o = 8; o >= 1; o >>= 1) s = __fadd_rn(s, __shfl_xor(s, o, 64));
+        const float s = doc_score<QT>(mx, Lq, lane);
         if (lane == 0) out[c] = s;
     }
-}
-
-template <int QT, int NB>
-hipError_t allow_lds()
-{
-    return hipFuncSetAttribute((const void *)maxsim_res_kernel<QT, NB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               kLdsBudget);
-}
-
-template <int QT, int NB>
-void launch_maxsim_res(unsigned P, size_t lds, hipStream_t s, const uint32_t *bits, const float *u, const uint16_t *codes,
-                       const void *cent, const uint32_t *pair, const void *d_table, int n_docs, const float *d_q, int Lq,
-                       int w, const int32_t *d_ids, int n, float *d_out)
-{
-    maxsim_res_kernel<QT, NB><<<P, kThreads, lds, s>>>(bits, u, codes, (const h16x8 *)cent, pair, (const int2 *)d_table,
-                                                       n_docs, d_q, Lq, w, d_ids, n, d_out);
 }
 
 template <int NB>
@@ -304,17 +266,11 @@ int launch_maxsim_res_nb(const uint32_t *bits, const float *u, const uint16_t *c
     const int QT = (Lq + 15) / 16;
     const size_t lds = res_lds_bytes(QT, w, NB);
     if (lds > (size_t)kLdsBudget) return -1;
-    // as many workgroups per CU as the LDS holds, at most 4 (launch_maxsim's rule)
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (int64_t)kLdsBudget / (int64_t)lds));
-    unsigned P = (unsigned)std::max<int64_t>(1, std::min<int64_t>(per_cu * device_cu_count(), ((int64_t)n + 3) / 4));
-    if (max_wg > 0) P = std::min(P, (unsigned)max_wg);
-    if (ran_wg) *ran_wg = (int)P;
-    switch (QT) {
-    case 1: launch_maxsim_res<1, NB>(P, lds, s, bits, u, codes, cent, pair, d_table, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
-    case 2: launch_maxsim_res<2, NB>(P, lds, s, bits, u, codes, cent, pair, d_table, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
-    case 3: launch_maxsim_res<3, NB>(P, lds, s, bits, u, codes, cent, pair, d_table, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
-    default: launch_maxsim_res<4, NB>(P, lds, s, bits, u, codes, cent, pair, d_table, n_docs, d_q, Lq, w, d_ids, n, d_out); break;
-    }
+    const unsigned P = (unsigned)scorer_grid(lds, n, max_wg, ran_wg);
+    with_tiles(QT, [&](auto qt) {
+        maxsim_res_kernel<decltype(qt)::value, NB><<<P, kThreads, lds, s>>>(
+            bits, u, codes, (const h16x8 *)cent, pair, (const int2 *)d_table, n_docs, d_q, Lq, w, d_ids, n, d_out);
+    });
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -322,14 +278,12 @@ int launch_maxsim_res_nb(const uint32_t *bits, const float *u, const uint16_t *c
 
 int maxsim_res_prepare_device()
 {
-    hipError_t e = allow_lds<1, 2>();
-    if (e == hipSuccess) e = allow_lds<2, 2>();
-    if (e == hipSuccess) e = allow_lds<3, 2>();
-    if (e == hipSuccess) e = allow_lds<4, 2>();
-    if (e == hipSuccess) e = allow_lds<1, 4>();
-    if (e == hipSuccess) e = allow_lds<2, 4>();
-    if (e == hipSuccess) e = allow_lds<3, 4>();
-    if (e == hipSuccess) e = allow_lds<4, 4>();
+    hipError_t e = hipSuccess;
+    for (int qt = 1; qt <= 4 && e == hipSuccess; ++qt)
+        with_tiles(qt, [&](auto QT) {
+            e = allow_lds((const void *)maxsim_res_kernel<decltype(QT)::value, 2>);
+            if (e == hipSuccess) e = allow_lds((const void *)maxsim_res_kernel<decltype(QT)::value, 4>);
+        });
     return e == hipSuccess ? 0 : -1;
 }
 

@@ -6,54 +6,31 @@
 // then takes the k best of the workgroups' lists by sorting them in LDS.
 //
 // score(query, doc) is, bit for bit, what the scorers return: the same pack_row_f16 /
-// pack_row_i8 of the query rows (maxsim_pack.h), per 16-row group the same MFMAs in
-// ascending k from a zero accumulator, rows >= len selected to -inf, the exact max, lane
-// c's sum of its query's columns c, 16 + c, ... in ascending order from +0 and the
-// four-step butterfly.  One wave scores one whole document, so a score depends on that
-// query and that document's rows only: not on the other queries of the call, B, k, the
+// pack_row_i8 of the query rows (maxsim_common.h pack_queries), per 16-row group the same
+// MFMAs in ascending k from a zero accumulator, rows >= len selected to -inf, the exact
+// max, and the scorers' own epilogue (maxsim_common.h doc_score).  One wave scores one
+// whole document, so a score depends on that query and that document's rows only: not on the other queries of the call, B, k, the
 // document count or where the document sits.
-#include "device_common.h"
-#include "kernels.h"
-#include "maxsim_pack.h"
+#include "maxsim_common.h"
 #include "topk_list.h"
-
-#include <algorithm>
 
 namespace emb {
 namespace {
 
 constexpr int kThreads = 256;      // 4 waves, each streams its own contiguous run of documents
-constexpr int kLdsBudget = 160 * 1024;
-constexpr int kMaxWgPerCu = 4;     // 16 waves of 8 KiB in flight per CU, as the scorers
 constexpr int kSelSeg = 32;        // lists one workgroup of the selection takes: 32 * 128 = 4,096 pairs in LDS
 constexpr int kSelMax = kSelSeg * 128;
-constexpr int kMaxWg = kSelSeg * kSelSeg;   // the grid's cap: two selection levels cover 1,024 lists
+static_assert(kScanMaxWg == kSelSeg * kSelSeg, "two selection levels cover the grid's lists");
 
-// What differs between the storage kinds (search.hip Store): the 16-B lane fragment of a
-// 1-KiB block, the k a block covers, the accumulator, the blocks of a ring unit and the
+// A storage kind (maxsim_common.h Kind) with its ring: the blocks of a ring unit and the
 // units of the ring (8 KiB in flight per wave either way, the scorers' depth).
 template <int ST> struct Store;
-template <> struct Store<SEARCH_F16> {
-    typedef h16x8 Block;
-    typedef f32x4 Acc;
-    static constexpr int kShift = 5, kUnit = 2, kRingUnits = 4;
-    __host__ __device__ static constexpr size_t row_bytes(int w) { return (size_t)w * 2; }
+template <> struct Store<SEARCH_F16> : Kind<SEARCH_F16> {
+    static constexpr int kUnit = 2, kRingUnits = 4;
 };
-template <> struct Store<SEARCH_I8> {
-    typedef i32x4 Block;
-    typedef i32x4 Acc;
-    static constexpr int kShift = 6, kUnit = 1, kRingUnits = 8;
-    __host__ __device__ static constexpr size_t row_bytes(int w) { return (size_t)w; }
+template <> struct Store<SEARCH_I8> : Kind<SEARCH_I8> {
+    static constexpr int kUnit = 1, kRingUnits = 8;
 };
-
-__device__ __forceinline__ f32x4 mma(h16x8 a, h16x8 b, f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ i32x4 mma(i32x4 a, i32x4 b, i32x4 c)
-{
-    return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
-}
 
 // LDS: the TT tiles of query fragments, the 64 query u (int8; kept for both kinds), one
 // list of k per wave and query.
@@ -63,28 +40,12 @@ __host__ __device__ inline size_t msearch_lds_bytes(int TT, int NQ, int w, int k
     return (size_t)TT * 16 * Store<ST>::row_bytes(w) + 64 * 4 + (size_t)4 * NQ * k * sizeof(Hit);
 }
 
-// The table lives in the constant address space for the stream: it does not change during
-// a search and every index into it is wave-uniform, so it comes through the scalar cache
-// and never enters the vector-memory counter that paces the ring (search.hip's row scales).
-typedef const __attribute__((address_space(4))) int2 *TablePtr;
-
-// The first document in [0, n_docs) whose first group is >= g, n_docs if none: the table's
-// first groups ascend with the id.
-__device__ __forceinline__ int first_doc_at(TablePtr tab, int n_docs, int g)
-{
-    int lo = 0, hi = n_docs;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (tab[mid].x < g) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // NQ queries of QTq tiles each, q f32 [NQ][Lq][w]; G = the store's used groups.
-// Prologue: tile t = QTq * (query of the pass) + (tile of the query); its rows packed as
-// the scorers pack theirs, rows >= Lq of a query zeros (u = 0).
+// Prologue: the scorers' (maxsim_common.h pack_queries), tile t = QTq * (query of the
+// pass) + (tile of the query).
 // Ranges: wave v of the grid's W takes the documents whose first group lies in
-// [v G / W, (v + 1) G / W): two binary searches, uniform over the wave.  Documents are
+// [v G / W, (v + 1) G / W): two binary searches (first_doc_at over the table in the
+// constant address space, TablePtr), uniform over the wave.  Documents are
 // contiguous in the store, so that is one contiguous run of groups, streamed through one
 // register ring that is refilled across document boundaries (loads past the run's last
 // block re-read that block).  int8: the rows' u ride in the ring as in maxsim_i8_kernel.
@@ -114,6 +75,8 @@ __global__ __launch_bounds__(kThreads) void maxsim_search_kernel(const typename 
     float *qu = (float *)(qf + (size_t)TT * KB * 64);             // [64]
     Hit *lists = (Hit *)(qu + 64);                                // [4][NQ][k]
 
+    // pack_queries<ST>(q, Tiles<NQ>, Tiles<QTq>, ...) written out: called as a function it
+    // changes the f16 kernels' registers and occupancy
     for (int i = wv; i < TT * 16; i += 4) {
         const int t = i >> 4, qi = t / QTq, rq = ((t - qi * QTq) << 4) + (i & 15);
         const float *src = q + ((size_t)qi * Lq + min(rq, Lq - 1)) * w;
@@ -206,13 +169,7 @@ __global__ __launch_bounds__(kThreads) void maxsim_search_kernel(const typename 
             // int8: the u of rows 4g .. 4g + 3, lanes 0 .. 3 of this lane's quad; taken in every
             // unit and before the refill (maxsim_i8_kernel)
             float rrow[4] = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (ST == SEARCH_I8) {
-                const int ug = __float_as_int(ring_u[j]);
-                rrow[0] = __int_as_float(__builtin_amdgcn_mov_dpp(ug, 0x00, 0xf, 0xf, false));
-                rrow[1] = __int_as_float(__builtin_amdgcn_mov_dpp(ug, 0x55, 0xf, 0xf, false));
-                rrow[2] = __int_as_float(__builtin_amdgcn_mov_dpp(ug, 0xaa, 0xf, 0xf, false));
-                rrow[3] = __int_as_float(__builtin_amdgcn_mov_dpp(ug, 0xff, 0xf, 0xf, false));
-            }
+            if constexpr (ST == SEARCH_I8) quad_u(ring_u[j], rrow);
 #pragma unroll
             for (int t = 0; t < TT; ++t) {
                 const Block b0 = qf[((size_t)t * KB + kb) * 64 + lane];
@@ -233,10 +190,8 @@ __global__ __launch_bounds__(kThreads) void maxsim_search_kernel(const typename 
                 for (int t = 0; t < TT; ++t) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        float sim;
-                        if constexpr (ST == SEARCH_I8) sim = score_i8(acc[t][r], uq[t], rrow[r]);
-                        else sim = acc[t][r];
-                        mx[t] = fmaxf(mx[t], row0 + r < len ? sim : -INFINITY);
+                        const float s = sim(acc[t][r], uq[t], rrow[r]);
+                        mx[t] = fmaxf(mx[t], row0 + r < len ? s : -INFINITY);
                     }
                     acc[t] = Acc{0, 0, 0, 0};
                 }
@@ -244,6 +199,9 @@ __global__ __launch_bounds__(kThreads) void maxsim_search_kernel(const typename 
                 if (rbase + 16 >= len) {   // wave-uniform: the document's last group
 #pragma unroll
                     for (int i = 0; i < NQ; ++i) {
+                        // doc_score<QTq> of the query's maxima (maxsim_common.h) written out, the
+                        // maxima reset on the way: called as a function it costs this kernel
+                        // its ring waits
                         float s = 0.f;
 #pragma unroll
                         for (int t = 0; t < QTq; ++t) {
@@ -356,33 +314,35 @@ int pow2_at_least(int n)
     return N;
 }
 
-template <int QTq, int NQ, int ST>
-hipError_t allow_lds()
+// f(QTq, NQ as integral constants) for the pass of nq queries of qtq tiles; false when the
+// pass does not fit four tiles (no kernel is instantiated for it).
+template <class F>
+bool with_pass(int qtq, int nq, F &&f)
 {
-    return hipFuncSetAttribute((const void *)maxsim_search_kernel<QTq, NQ, ST>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget);
+    bool fits = false;
+    with_tiles(qtq, [&](auto a) {
+        with_tiles(nq, [&](auto b) {
+            if constexpr (decltype(a)::value * decltype(b)::value <= 4) {
+                if (decltype(a)::value == qtq && decltype(b)::value == nq) {
+                    f(a, b);
+                    fits = true;
+                }
+            }
+        });
+    });
+    return fits;
 }
 
 template <int ST>
 hipError_t allow_lds_all()
 {
-    hipError_t e = allow_lds<1, 1, ST>();
-    if (e == hipSuccess) e = allow_lds<1, 2, ST>();
-    if (e == hipSuccess) e = allow_lds<1, 3, ST>();
-    if (e == hipSuccess) e = allow_lds<1, 4, ST>();
-    if (e == hipSuccess) e = allow_lds<2, 1, ST>();
-    if (e == hipSuccess) e = allow_lds<2, 2, ST>();
-    if (e == hipSuccess) e = allow_lds<3, 1, ST>();
-    if (e == hipSuccess) e = allow_lds<4, 1, ST>();
+    hipError_t e = hipSuccess;
+    for (int qtq = 1; qtq <= 4; ++qtq)
+        for (int nq = 1; nq <= 4 / qtq && e == hipSuccess; ++nq)
+            with_pass(qtq, nq, [&](auto a, auto b) {
+                e = allow_lds((const void *)maxsim_search_kernel<decltype(a)::value, decltype(b)::value, ST>);
+            });
     return e;
-}
-
-template <int QTq, int NQ, int ST>
-void launch_pass(const void *store, const float *scales, const void *table, int n_docs, int G, const float *Q, int Lq,
-                 int w, int k, int P, size_t lds, Hit *part, hipStream_t s)
-{
-    maxsim_search_kernel<QTq, NQ, ST><<<(unsigned)P, kThreads, lds, s>>>(
-        (const typename Store<ST>::Block *)store, scales, (const int2 *)table, n_docs, G, Q, Lq, w, k, part);
 }
 
 template <int ST>
@@ -390,33 +350,22 @@ int launch_all(const void *store, const float *scales, const void *table, int n_
                int B, int Lq, int k, void *scratch, float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg, int *ran_wg)
 {
     const int QTq = (Lq + 15) / 16, per_pass = 4 / QTq;
-    const int cus = device_cu_count();
     for (int b0 = 0; b0 < B; b0 += per_pass) {
         const int nq = std::min(per_pass, B - b0);
         const size_t lds = msearch_lds_bytes<ST>(QTq * nq, nq, w, k);
         if (lds > (size_t)kLdsBudget) return -1;
-        // as many workgroups per CU as the LDS holds, at most 4; never more waves than groups
-        const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(kMaxWgPerCu, (int64_t)kLdsBudget / (int64_t)lds));
-        int P = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(per_cu * cus, kMaxWg), ((int64_t)G + 3) / 4));
-        if (max_wg > 0) P = std::min(P, max_wg);
-        if (ran_wg) *ran_wg = P;
+        const int P = scan_grid(lds, G, 4, max_wg, ran_wg);
         const float *Q = d_q + (size_t)b0 * Lq * w;
         Hit *part = (Hit *)scratch;
-        switch (QTq * 8 + nq) {
-        case 8 + 1: launch_pass<1, 1, ST>(store, scales, table, n_docs, G, Q, Lq, w, k, P, lds, part, s); break;
-        case 8 + 2: launch_pass<1, 2, ST>(store, scales, table, n_docs, G, Q, Lq, w, k, P, lds, part, s); break;
-        case 8 + 3: launch_pass<1, 3, ST>(store, scales, table, n_docs, G, Q, Lq, w, k, P, lds, part, s); break;
-        case 8 + 4: launch_pass<1, 4, ST>(store, scales, table, n_docs, G, Q, Lq, w, k, P, lds, part, s); break;
-        case 16 + 1: launch_pass<2, 1, ST>(store, scales, table, n_docs, G, Q, Lq, w, k, P, lds, part, s); break;
-        case 16 + 2: launch_pass<2, 2, ST>(store, scales, table, n_docs, G, Q, Lq, w, k, P, lds, part, s); break;
-        case 24 + 1: launch_pass<3, 1, ST>(store, scales, table, n_docs, G, Q, Lq, w, k, P, lds, part, s); break;
-        case 32 + 1: launch_pass<4, 1, ST>(store, scales, table, n_docs, G, Q, Lq, w, k, P, lds, part, s); break;
-        default: return -1;
-        }
+        const bool fits = with_pass(QTq, nq, [&](auto a, auto b) {
+            maxsim_search_kernel<decltype(a)::value, decltype(b)::value, ST><<<(unsigned)P, kThreads, lds, s>>>(
+                (const typename Store<ST>::Block *)store, scales, (const int2 *)table, n_docs, G, Q, Lq, w, k, part);
+        });
+        if (!fits) return -1;
         if (hipGetLastError() != hipSuccess) return -3;
         // the k best of the P lists per query: one level up to kSelSeg lists, else two
         const int S = (P + kSelSeg - 1) / kSelSeg;
-        Hit *part2 = part + (size_t)4 * std::min(kMaxWgPerCu * cus, kMaxWg) * 128;
+        Hit *part2 = part + (size_t)4 * scan_max_lists() * 128;
         float *sc = d_scores + (size_t)b0 * k;
         int32_t *id = d_ids + (size_t)b0 * k;
         if (S > 1) {
@@ -446,7 +395,7 @@ int maxsim_search_prepare_device()
 size_t maxsim_search_scratch_bytes()
 {
     // the workgroups' lists, then the first selection level's: 4 queries, k = 128
-    const size_t P = (size_t)std::min(kMaxWgPerCu * device_cu_count(), kMaxWg);
+    const size_t P = (size_t)scan_max_lists();
     return 4 * (P + (P + kSelSeg - 1) / kSelSeg) * 128 * sizeof(Hit);
 }
 

@@ -810,78 +810,6 @@ int32_t search_texts(bertx_mvindex &mv, struct bert_ctx *ctx, const TextRows &t,
     return 0;
 }
 
-}  // namespace
-
-bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t cap_slots, int storage)
-{
-    if (storage != BERTX_INDEX_F16 && storage != BERTX_INDEX_I8 && storage != BERTX_INDEX_RES2 &&
-        storage != BERTX_INDEX_RES4) {
-        errorf("bertx_mvindex_create: storage %d is none of BERTX_INDEX_F16, _I8, _RES2, _RES4\n", storage);
-        return nullptr;
-    }
-    if (w % 64 || w < 64 || w > 1024) {
-        errorf("bertx_mvindex_create: width %d is not a multiple of 64 in 64 .. 1024\n", w);
-        return nullptr;
-    }
-    if (cap_docs < 1 || cap_docs > 0x7ffffff0ll || cap_slots < 16 || cap_slots > (0x7ffffff0ll << 4)) {
-        errorf("bertx_mvindex_create: capacity of %lld documents / %lld token slots is not in 1 .. 2^31 - 16 / "
-               "16 .. 2^35 - 256\n", (long long)cap_docs, (long long)cap_slots);
-        return nullptr;
-    }
-    DeviceGuard g(ordinal);
-    if (!g.ok()) {
-        errorf("bertx_mvindex_create: cannot select device %d\n", ordinal);
-        return nullptr;
-    }
-    bertx_mvindex *mv = new (std::nothrow) bertx_mvindex();
-    if (!mv) return nullptr;
-    mv->ordinal = ordinal;
-    mv->w = w;
-    mv->storage = storage;
-    mv->cap_docs = cap_docs;
-    mv->cap_slots = cap_slots;
-    const size_t slots16 = (size_t)((cap_slots + 15) / 16) * 16;
-    const bool i8 = storage == BERTX_INDEX_I8;
-    const int nb = res_nbits(*mv);
-    // a residual store keeps no rows: w nb / 8 bytes of bits and one f32 per slot, and the codec
-    const size_t store_bytes = nb ? slots16 * (size_t)w * nb / 8 + slots16 * 4 : slots16 * (size_t)w * (i8 ? 1 : 2);
-    const bool ok = maxsim_prepare_device() == 0 && maxsim_search_prepare_device() == 0 &&
-                    maxsim_codes_prepare_device() == 0 && maxsim_approx_prepare_device() == 0 &&
-                    hipMalloc(&mv->search_scratch, maxsim_search_scratch_bytes()) == hipSuccess &&
-                    hipStreamCreateWithFlags(&mv->stream, hipStreamNonBlocking) == hipSuccess &&
-                    hipEventCreateWithFlags(&mv->ord.done, hipEventDisableTiming) == hipSuccess &&
-                    (nb ? maxsim_res_prepare_device() == 0 &&
-                              hipMalloc((void **)&mv->res_bits, slots16 * (size_t)w * nb / 8) == hipSuccess &&
-                              hipMalloc((void **)&mv->res_u, slots16 * 4) == hipSuccess &&
-                              hipMalloc((void **)&mv->res_cuts, 64) == hipSuccess &&
-                              hipMalloc((void **)&mv->res_wts, 32) == hipSuccess &&
-                              hipMalloc((void **)&mv->res_pair, 1024) == hipSuccess
-                        : hipMalloc(&mv->store, store_bytes) == hipSuccess) &&
-                    (!i8 || hipMalloc((void **)&mv->scales, slots16 * 4) == hipSuccess) &&
-                    hipMalloc((void **)&mv->table, (size_t)cap_docs * 8) == hipSuccess &&
-                    hipMalloc((void **)&mv->src_off, (size_t)cap_docs * 4) == hipSuccess &&
-                    hipHostMalloc((void **)&mv->h_table, (size_t)cap_docs * 8, hipHostMallocDefault) == hipSuccess &&
-                    hipHostMalloc((void **)&mv->h_src, (size_t)cap_docs * 4, hipHostMallocDefault) == hipSuccess &&
-                    hipMalloc((void **)&mv->st_rows, (size_t)kStageRows * w * 4) == hipSuccess &&
-                    hipMalloc((void **)&mv->st_q, (size_t)kMaxLq * w * 4) == hipSuccess &&
-                    hipMalloc((void **)&mv->st_out, (size_t)kStageIds * 4) == hipSuccess &&
-                    hipMalloc((void **)&mv->st_ids, (size_t)kStageIds * 4) == hipSuccess &&
-                    hipMalloc((void **)&mv->st_tok, (size_t)(kMaxLq + 3) * 4) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        errorf("bertx_mvindex_create: device %d could not allocate %zu bytes of token rows (+ %lld table entries)\n",
-               ordinal, store_bytes + (i8 ? slots16 * 4 : 0), (long long)cap_docs);
-        delete mv;
-        return nullptr;
-    }
-    return mv;
-}
-
-}  // namespace emb
-
-namespace emb {
-namespace {
-
 bool centroid_count_ok(const char *who, int32_t C)
 {
     if (C >= 16 && C <= 65536 && C % 16 == 0) return true;
@@ -988,6 +916,72 @@ int32_t queries_to_host(bertx_mvindex &mv, const float *q, int32_t B, int32_t Lq
 }
 
 }  // namespace
+
+bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t cap_slots, int storage)
+{
+    if (storage != BERTX_INDEX_F16 && storage != BERTX_INDEX_I8 && storage != BERTX_INDEX_RES2 &&
+        storage != BERTX_INDEX_RES4) {
+        errorf("bertx_mvindex_create: storage %d is none of BERTX_INDEX_F16, _I8, _RES2, _RES4\n", storage);
+        return nullptr;
+    }
+    if (w % 64 || w < 64 || w > 1024) {
+        errorf("bertx_mvindex_create: width %d is not a multiple of 64 in 64 .. 1024\n", w);
+        return nullptr;
+    }
+    if (cap_docs < 1 || cap_docs > 0x7ffffff0ll || cap_slots < 16 || cap_slots > (0x7ffffff0ll << 4)) {
+        errorf("bertx_mvindex_create: capacity of %lld documents / %lld token slots is not in 1 .. 2^31 - 16 / "
+               "16 .. 2^35 - 256\n", (long long)cap_docs, (long long)cap_slots);
+        return nullptr;
+    }
+    DeviceGuard g(ordinal);
+    if (!g.ok()) {
+        errorf("bertx_mvindex_create: cannot select device %d\n", ordinal);
+        return nullptr;
+    }
+    bertx_mvindex *mv = new (std::nothrow) bertx_mvindex();
+    if (!mv) return nullptr;
+    mv->ordinal = ordinal;
+    mv->w = w;
+    mv->storage = storage;
+    mv->cap_docs = cap_docs;
+    mv->cap_slots = cap_slots;
+    const size_t slots16 = (size_t)((cap_slots + 15) / 16) * 16;
+    const bool i8 = storage == BERTX_INDEX_I8;
+    const int nb = res_nbits(*mv);
+    // a residual store keeps no rows: w nb / 8 bytes of bits and one f32 per slot, and the codec
+    const size_t store_bytes = nb ? slots16 * (size_t)w * nb / 8 + slots16 * 4 : slots16 * (size_t)w * (i8 ? 1 : 2);
+    const bool ok = maxsim_prepare_device() == 0 && maxsim_search_prepare_device() == 0 &&
+                    maxsim_codes_prepare_device() == 0 && maxsim_approx_prepare_device() == 0 &&
+                    hipMalloc(&mv->search_scratch, maxsim_search_scratch_bytes()) == hipSuccess &&
+                    hipStreamCreateWithFlags(&mv->stream, hipStreamNonBlocking) == hipSuccess &&
+                    hipEventCreateWithFlags(&mv->ord.done, hipEventDisableTiming) == hipSuccess &&
+                    (nb ? maxsim_res_prepare_device() == 0 &&
+                              hipMalloc((void **)&mv->res_bits, slots16 * (size_t)w * nb / 8) == hipSuccess &&
+                              hipMalloc((void **)&mv->res_u, slots16 * 4) == hipSuccess &&
+                              hipMalloc((void **)&mv->res_cuts, 64) == hipSuccess &&
+                              hipMalloc((void **)&mv->res_wts, 32) == hipSuccess &&
+                              hipMalloc((void **)&mv->res_pair, 1024) == hipSuccess
+                        : hipMalloc(&mv->store, store_bytes) == hipSuccess) &&
+                    (!i8 || hipMalloc((void **)&mv->scales, slots16 * 4) == hipSuccess) &&
+                    hipMalloc((void **)&mv->table, (size_t)cap_docs * 8) == hipSuccess &&
+                    hipMalloc((void **)&mv->src_off, (size_t)cap_docs * 4) == hipSuccess &&
+                    hipHostMalloc((void **)&mv->h_table, (size_t)cap_docs * 8, hipHostMallocDefault) == hipSuccess &&
+                    hipHostMalloc((void **)&mv->h_src, (size_t)cap_docs * 4, hipHostMallocDefault) == hipSuccess &&
+                    hipMalloc((void **)&mv->st_rows, (size_t)kStageRows * w * 4) == hipSuccess &&
+                    hipMalloc((void **)&mv->st_q, (size_t)kMaxLq * w * 4) == hipSuccess &&
+                    hipMalloc((void **)&mv->st_out, (size_t)kStageIds * 4) == hipSuccess &&
+                    hipMalloc((void **)&mv->st_ids, (size_t)kStageIds * 4) == hipSuccess &&
+                    hipMalloc((void **)&mv->st_tok, (size_t)(kMaxLq + 3) * 4) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        errorf("bertx_mvindex_create: device %d could not allocate %zu bytes of token rows (+ %lld table entries)\n",
+               ordinal, store_bytes + (i8 ? slots16 * 4 : 0), (long long)cap_docs);
+        delete mv;
+        return nullptr;
+    }
+    return mv;
+}
+
 }  // namespace emb
 
 using emb::DeviceGuard;
@@ -1715,12 +1709,121 @@ int32_t bertx_mvindex_search_pruned_texts(struct bertx_mvindex *mv, struct bert_
 
 }  // extern "C"
 
-// The MaxSim micro-benchmarks (bert_hip.h): device 0, no context.  B == 0: the scorer over
-// n_cand candidates; B >= 1: the full-scan search of B queries for the k best.  C > 0 (with
-// B >= 1): C hash-chosen stored rows become the centroids and avg_us[3] gets the table
-// kernels, the scans with their selections, and the whole pruned search of n_cand candidates.
-static int32_t bench_store(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t B, int32_t k,
-                           int32_t storage, int32_t iters, float *avg_us, int32_t C = 0)
+namespace {
+
+// What the MaxSim micro-benchmarks share (bench_store, bench_res; bert_hip.h): device 0
+// selected, no context; the documents' lens and the candidates' ids from hashes; a stream
+// with two events; the fill, query and result buffers; the stores, released with the rest.
+struct MaxsimBench {
+    static constexpr int64_t kFillRows = 1 << 18;
+    const int32_t w, n_docs, iters;
+    std::vector<int32_t> lens, ids;
+    int64_t slots = 0;
+    emb::DeviceGuard guard{0};
+    bertx_mvindex *mv = nullptr, *aux = nullptr;   // the store that is timed; bench_res: the f16 store that trains the codec
+    hipStream_t s = nullptr;
+    hipEvent_t a = nullptr, b = nullptr;
+    emb::DevBuf rows, q, id, out, oid;
+
+    // ragged (doc_len 0): 16 .. 512 tokens by a hash of the id
+    MaxsimBench(int32_t w_, int32_t n_docs_, int32_t doc_len, int32_t n_cand, int32_t iters_)
+        : w(w_), n_docs(n_docs_), iters(iters_), lens((size_t)n_docs_), ids((size_t)n_cand)
+    {
+        for (int32_t i = 0; i < n_docs; ++i) {
+            uint32_t h = (uint32_t)i * 2654435761u + 99u;
+            h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
+            lens[(size_t)i] = doc_len ? doc_len : 16 + (int32_t)(h % 497u);
+            slots += (lens[(size_t)i] + 15) / 16 * 16;
+        }
+        for (int32_t c = 0; c < n_cand; ++c) ids[(size_t)c] = (int32_t)(((uint64_t)c * 2654435761ull + 12345ull) % (uint64_t)n_docs);
+    }
+    ~MaxsimBench()
+    {
+        if (s) (void)hipStreamSynchronize(s);
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+        if (s) (void)hipStreamDestroy(s);
+        bertx_mvindex_free(aux);
+        bertx_mvindex_free(mv);
+    }
+
+    // the stream, the events and the buffers of nq queries
+    int32_t init(int32_t nq)
+    {
+        using namespace emb;
+        HIP_RC(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        HIP_RC(hipEventCreate(&a));
+        HIP_RC(hipEventCreate(&b));
+        HIP_RC(hipMalloc(&rows.p, (size_t)(kFillRows + 4096) * w * 4));
+        HIP_RC(hipMalloc(&q.p, (size_t)nq * kMaxLq * w * 4));
+        HIP_RC(hipMalloc(&id.p, ids.size() * 4));
+        HIP_RC(hipMalloc(&out.p, (size_t)std::max((int32_t)ids.size(), nq * kMaxK) * 4));
+        HIP_RC(hipMalloc(&oid.p, (size_t)nq * kMaxK * 4));
+        return 0;
+    }
+
+    // every document into `store`, up to kFillRows unit rows per add (seed 12345 + first id)
+    int32_t fill(bertx_mvindex *store)
+    {
+        for (int32_t i = 0; i < n_docs;) {
+            int32_t j = i;
+            int64_t n = 0;
+            while (j < n_docs && (j == i || n + lens[(size_t)j] <= kFillRows)) n += lens[(size_t)j++];
+            if (emb::launch_unit_rows((float *)rows.p, n, w, 12345u + (uint32_t)i, s) != 0) return -1;
+            if (bertx_mvindex_add_device(store, (const float *)rows.p, lens.data() + i, j - i, s) < 0) return -1;
+            HIP_RC(hipStreamSynchronize(s));   // the fill buffer is reused
+            i = j;
+        }
+        return 0;
+    }
+
+    // nq queries of Lq unit rows (seed 777) and the candidates' ids, on the device
+    int32_t queries(int32_t nq, int32_t Lq)
+    {
+        if (emb::launch_unit_rows((float *)q.p, (int64_t)nq * Lq, w, 777u, s) != 0) return -1;
+        HIP_RC(hipMemcpyAsync(id.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, s));
+        HIP_RC(hipStreamSynchronize(s));
+        return 0;
+    }
+
+    // the mean of `iters` calls of fn after three, by the events
+    template <class F>
+    int32_t timed(F &&fn, float *us)
+    {
+        for (int i = 0; i < 3; ++i)
+            if (fn() != 0) return -1;
+        HIP_RC(hipEventRecord(a, s));
+        for (int i = 0; i < iters; ++i)
+            if (fn() != 0) return -1;
+        HIP_RC(hipEventRecord(b, s));
+        HIP_RC(hipEventSynchronize(b));
+        float ms = 0.f;
+        HIP_RC(hipEventElapsedTime(&ms, a, b));
+        *us = ms * 1000.f / (float)iters;
+        return 0;
+    }
+
+    // C hash-chosen rows of `store` (row c mod len of a hashed document) as centroids
+    int32_t pick_centroids(bertx_mvindex *store, int32_t C, std::vector<float> &cent)
+    {
+        std::vector<float> doc;
+        cent.resize((size_t)C * w);
+        for (int32_t c = 0; c < C; ++c) {
+            const int32_t d = (int32_t)(((uint64_t)c * 2654435761ull + 777ull) % (uint64_t)n_docs);
+            doc.resize((size_t)lens[(size_t)d] * w);
+            if (bertx_mvindex_doc(store, d, doc.data()) != 0) return -1;
+            std::memcpy(cent.data() + (size_t)c * w, doc.data() + (size_t)(c % lens[(size_t)d]) * w, (size_t)w * 4);
+        }
+        return 0;
+    }
+};
+
+// B == 0: the scorer over n_cand candidates; B >= 1: the full-scan search of B queries for
+// the k best.  C > 0 (with B >= 1): C hash-chosen stored rows become the centroids and
+// avg_us[3] gets the table kernels, the scans with their selections, and the whole pruned
+// search of n_cand candidates.
+int32_t bench_store(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t B, int32_t k,
+                    int32_t storage, int32_t iters, float *avg_us, int32_t C = 0)
 {
     using namespace emb;
     if (n_docs < 1 || doc_len < 0 || doc_len > 4096 || n_cand < 1 || iters < 1 || !avg_us || hip_device_count() == 0)
@@ -1729,106 +1832,39 @@ static int32_t bench_store(int32_t w, int32_t n_docs, int32_t doc_len, int32_t L
     if (C > 0 && (B < 1 || k > n_cand || n_cand > kMaxK || !centroid_count_ok("bertx_bench_maxsim_pruned", C))) return -1;
     const int32_t nq = std::max(B, 1);
     try {
-        // ragged (doc_len 0): 16 .. 512 tokens by a hash of the id
-        std::vector<int32_t> lens((size_t)n_docs), ids((size_t)n_cand);
-        int64_t slots = 0;
-        for (int32_t i = 0; i < n_docs; ++i) {
-            uint32_t h = (uint32_t)i * 2654435761u + 99u;
-            h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
-            lens[(size_t)i] = doc_len ? doc_len : 16 + (int32_t)(h % 497u);
-            slots += (lens[(size_t)i] + 15) / 16 * 16;
-        }
-        for (int32_t c = 0; c < n_cand; ++c) ids[(size_t)c] = (int32_t)(((uint64_t)c * 2654435761ull + 12345ull) % (uint64_t)n_docs);
-        DeviceGuard guard(0);
-        HIP_RC(guard.status());
-        struct Holder {
-            bertx_mvindex *mv = nullptr;
-            hipStream_t s = nullptr;
-            hipEvent_t a = nullptr, b = nullptr;
-            DevBuf rows, q, id, out, oid;
-            ~Holder()
-            {
-                if (s) (void)hipStreamSynchronize(s);
-                if (a) (void)hipEventDestroy(a);
-                if (b) (void)hipEventDestroy(b);
-                if (s) (void)hipStreamDestroy(s);
-                bertx_mvindex_free(mv);
-            }
-        } H;
-        H.mv = mvindex_create_on(0, w, n_docs, slots, storage);
-        if (!H.mv) return -1;
-        HIP_RC(hipStreamCreateWithFlags(&H.s, hipStreamNonBlocking));
-        HIP_RC(hipEventCreate(&H.a));
-        HIP_RC(hipEventCreate(&H.b));
-        constexpr int64_t kFillRows = 1 << 18;
-        HIP_RC(hipMalloc(&H.rows.p, (size_t)(kFillRows + 4096) * w * 4));
-        HIP_RC(hipMalloc(&H.q.p, (size_t)nq * kMaxLq * w * 4));
-        HIP_RC(hipMalloc(&H.id.p, (size_t)n_cand * 4));
-        HIP_RC(hipMalloc(&H.out.p, (size_t)std::max(n_cand, nq * kMaxK) * 4));
-        HIP_RC(hipMalloc(&H.oid.p, (size_t)nq * kMaxK * 4));
-        for (int32_t i = 0; i < n_docs;) {
-            int32_t j = i;
-            int64_t rows = 0;
-            while (j < n_docs && (j == i || rows + lens[(size_t)j] <= kFillRows)) rows += lens[(size_t)j++];
-            if (launch_unit_rows((float *)H.rows.p, rows, w, 12345u + (uint32_t)i, H.s) != 0) return -1;
-            if (bertx_mvindex_add_device(H.mv, (const float *)H.rows.p, lens.data() + i, j - i, H.s) < 0) return -1;
-            HIP_RC(hipStreamSynchronize(H.s));   // the fill buffer is reused
-            i = j;
-        }
-        if (Lq < 1 || Lq > kMaxLq || launch_unit_rows((float *)H.q.p, (int64_t)nq * Lq, w, 777u, H.s) != 0) return -1;
-        HIP_RC(hipMemcpyAsync(H.id.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, H.s));
-        HIP_RC(hipStreamSynchronize(H.s));
-        auto timed = [&](auto &&fn, float *us) -> int32_t {
-            for (int i = 0; i < 3; ++i)
-                if (fn() != 0) return -1;
-            HIP_RC(hipEventRecord(H.a, H.s));
-            for (int i = 0; i < iters; ++i)
-                if (fn() != 0) return -1;
-            HIP_RC(hipEventRecord(H.b, H.s));
-            HIP_RC(hipEventSynchronize(H.b));
-            float ms = 0.f;
-            HIP_RC(hipEventElapsedTime(&ms, H.a, H.b));
-            *us = ms * 1000.f / (float)iters;
-            return 0;
-        };
+        MaxsimBench F(w, n_docs, doc_len, n_cand, iters);
+        HIP_RC(F.guard.status());
+        F.mv = mvindex_create_on(0, w, n_docs, F.slots, storage);
+        if (!F.mv || F.init(nq) != 0 || F.fill(F.mv) != 0) return -1;
+        if (Lq < 1 || Lq > kMaxLq || F.queries(nq, Lq) != 0) return -1;
+        const float *Q = (const float *)F.q.p;
+        float *out = (float *)F.out.p;
+        int32_t *oid = (int32_t *)F.oid.p;
         if (C > 0) {
-            std::vector<float> cent((size_t)C * w), rows;
-            for (int32_t c = 0; c < C; ++c) {
-                const int32_t id = (int32_t)(((uint64_t)c * 2654435761ull + 777ull) % (uint64_t)n_docs);
-                rows.resize((size_t)lens[(size_t)id] * w);
-                if (bertx_mvindex_doc(H.mv, id, rows.data()) != 0) return -1;
-                std::memcpy(cent.data() + (size_t)c * w, rows.data() + (size_t)(c % lens[(size_t)id]) * w, (size_t)w * 4);
-            }
-            if (bertx_mvindex_set_centroids(H.mv, cent.data(), C) != 0) return -1;
-            HIP_RC(H.mv->ord.wait());
-            bertx_mvindex &mv = *H.mv;
+            std::vector<float> cent;
+            if (F.pick_centroids(F.mv, C, cent) != 0 || bertx_mvindex_set_centroids(F.mv, cent.data(), C) != 0) return -1;
+            HIP_RC(F.mv->ord.wait());
+            bertx_mvindex &mv = *F.mv;
             const int32_t per_pass = 4 / ((Lq + 15) / 16);
             auto stage = [&](int st) -> int32_t {
                 for (int32_t b0 = 0; b0 < B; b0 += per_pass) {
                     const int32_t rc = launch_maxsim_candidates(
                         mv.codes, mv.table, (int)mv.n_docs, mv.used_slots / 16, mv.storage, mv.w, mv.cent, mv.cent_u, mv.C,
-                        (const float *)H.q.p + (size_t)b0 * Lq * w, std::min(per_pass, B - b0), Lq, n_cand, mv.tscratch,
-                        mv.search_scratch, (float *)H.out.p + (size_t)b0 * n_cand, (int32_t *)H.oid.p + (size_t)b0 * n_cand,
-                        st, nullptr, H.s);
+                        Q + (size_t)b0 * Lq * w, std::min(per_pass, B - b0), Lq, n_cand, mv.tscratch, mv.search_scratch,
+                        out + (size_t)b0 * n_cand, oid + (size_t)b0 * n_cand, st, nullptr, F.s);
                     if (rc != 0) return rc;
                 }
                 return 0;
             };
-            if (timed([&] { return stage(1); }, avg_us) != 0) return -1;
-            if (timed([&] { return stage(2); }, avg_us + 1) != 0) return -1;
-            return timed([&] {
-                return bertx_mvindex_search_pruned_device(H.mv, (const float *)H.q.p, B, Lq, k, n_cand, (float *)H.out.p,
-                                                          (int32_t *)H.oid.p, H.s);
-            }, avg_us + 2);
+            if (F.timed([&] { return stage(1); }, avg_us) != 0) return -1;
+            if (F.timed([&] { return stage(2); }, avg_us + 1) != 0) return -1;
+            return F.timed([&] { return bertx_mvindex_search_pruned_device(F.mv, Q, B, Lq, k, n_cand, out, oid, F.s); },
+                           avg_us + 2);
         }
-        auto run = [&] {
-            if (B > 0)
-                return bertx_mvindex_search_device(H.mv, (const float *)H.q.p, B, Lq, k, (float *)H.out.p,
-                                                   (int32_t *)H.oid.p, H.s);
-            return bertx_mvindex_score_device(H.mv, (const float *)H.q.p, Lq, (const int32_t *)H.id.p, n_cand,
-                                              (float *)H.out.p, H.s);
-        };
-        return timed(run, avg_us);
+        return F.timed([&] {
+            if (B > 0) return bertx_mvindex_search_device(F.mv, Q, B, Lq, k, out, oid, F.s);
+            return bertx_mvindex_score_device(F.mv, Q, Lq, (const int32_t *)F.id.p, n_cand, out, F.s);
+        }, avg_us);
     } catch (const std::exception &ex) {
         emb::errorf("bertx_bench_maxsim: %s\n", ex.what());
         return -1;
@@ -1838,8 +1874,8 @@ static int32_t bench_store(int32_t w, int32_t n_docs, int32_t doc_len, int32_t L
 // bertx_bench_maxsim_res: bench_store's documents (the same lens and fill seeds) twice: in an
 // f16 store, whose C hash-chosen rows become the centroids and which trains the buckets, then
 // in the residual store.
-static int32_t bench_res(int32_t w, int32_t n_docs, int32_t doc_len, int32_t C, int32_t Lq, int32_t n_cand, int32_t storage,
-                         int32_t iters, float *avg_us)
+int32_t bench_res(int32_t w, int32_t n_docs, int32_t doc_len, int32_t C, int32_t Lq, int32_t n_cand, int32_t storage,
+                  int32_t iters, float *avg_us)
 {
     using namespace emb;
     if (n_docs < 1 || doc_len < 0 || doc_len > 4096 || n_cand < 1 || iters < 1 || !avg_us || Lq < 1 || Lq > kMaxLq ||
@@ -1847,102 +1883,37 @@ static int32_t bench_res(int32_t w, int32_t n_docs, int32_t doc_len, int32_t C, 
         !centroid_count_ok("bertx_bench_maxsim_res", C))
         return -1;
     try {
-        std::vector<int32_t> lens((size_t)n_docs), ids((size_t)n_cand);
-        int64_t slots = 0;
-        for (int32_t i = 0; i < n_docs; ++i) {
-            uint32_t h = (uint32_t)i * 2654435761u + 99u;
-            h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
-            lens[(size_t)i] = doc_len ? doc_len : 16 + (int32_t)(h % 497u);
-            slots += (lens[(size_t)i] + 15) / 16 * 16;
-        }
-        for (int32_t c = 0; c < n_cand; ++c) ids[(size_t)c] = (int32_t)(((uint64_t)c * 2654435761ull + 12345ull) % (uint64_t)n_docs);
-        DeviceGuard guard(0);
-        HIP_RC(guard.status());
-        struct Holder {
-            bertx_mvindex *f16 = nullptr, *res = nullptr;
-            hipStream_t s = nullptr;
-            hipEvent_t a = nullptr, b = nullptr;
-            DevBuf rows, q, id, out, oid;
-            ~Holder()
-            {
-                if (s) (void)hipStreamSynchronize(s);
-                if (a) (void)hipEventDestroy(a);
-                if (b) (void)hipEventDestroy(b);
-                if (s) (void)hipStreamDestroy(s);
-                bertx_mvindex_free(f16);
-                bertx_mvindex_free(res);
-            }
-        } H;
-        HIP_RC(hipStreamCreateWithFlags(&H.s, hipStreamNonBlocking));
-        HIP_RC(hipEventCreate(&H.a));
-        HIP_RC(hipEventCreate(&H.b));
-        constexpr int64_t kFillRows = 1 << 18;
-        HIP_RC(hipMalloc(&H.rows.p, (size_t)(kFillRows + 4096) * w * 4));
-        HIP_RC(hipMalloc(&H.q.p, (size_t)kMaxLq * w * 4));
-        HIP_RC(hipMalloc(&H.id.p, (size_t)n_cand * 4));
-        HIP_RC(hipMalloc(&H.out.p, (size_t)std::max(n_cand, kMaxK) * 4));
-        HIP_RC(hipMalloc(&H.oid.p, (size_t)kMaxK * 4));
-        auto fill = [&](bertx_mvindex *mv) -> int32_t {
-            for (int32_t i = 0; i < n_docs;) {
-                int32_t j = i;
-                int64_t rows = 0;
-                while (j < n_docs && (j == i || rows + lens[(size_t)j] <= kFillRows)) rows += lens[(size_t)j++];
-                if (launch_unit_rows((float *)H.rows.p, rows, w, 12345u + (uint32_t)i, H.s) != 0) return -1;
-                if (bertx_mvindex_add_device(mv, (const float *)H.rows.p, lens.data() + i, j - i, H.s) < 0) return -1;
-                HIP_RC(hipStreamSynchronize(H.s));   // the fill buffer is reused
-                i = j;
-            }
-            return 0;
-        };
-        H.f16 = mvindex_create_on(0, w, n_docs, slots, BERTX_INDEX_F16);
-        if (!H.f16 || fill(H.f16) != 0) return -1;
-        std::vector<float> cent((size_t)C * w), rows;
-        for (int32_t c = 0; c < C; ++c) {
-            const int32_t id = (int32_t)(((uint64_t)c * 2654435761ull + 777ull) % (uint64_t)n_docs);
-            rows.resize((size_t)lens[(size_t)id] * w);
-            if (bertx_mvindex_doc(H.f16, id, rows.data()) != 0) return -1;
-            std::memcpy(cent.data() + (size_t)c * w, rows.data() + (size_t)(c % lens[(size_t)id]) * w, (size_t)w * 4);
-        }
+        MaxsimBench F(w, n_docs, doc_len, n_cand, iters);
+        HIP_RC(F.guard.status());
+        if (F.init(1) != 0) return -1;
+        F.aux = mvindex_create_on(0, w, n_docs, F.slots, BERTX_INDEX_F16);
+        if (!F.aux || F.fill(F.aux) != 0) return -1;
+        std::vector<float> cent;
         float cuts[15], wts[16];
-        if (bertx_mvindex_set_centroids(H.f16, cent.data(), C) != 0) return -1;
-        if (bertx_mvindex_train_residual_buckets(H.f16, storage == BERTX_INDEX_RES2 ? 2 : 4, cuts, wts) != 0) return -1;
-        bertx_mvindex_free(H.f16);
-        H.f16 = nullptr;
-        H.res = mvindex_create_on(0, w, n_docs, slots, storage);
-        if (!H.res || bertx_mvindex_set_centroids(H.res, cent.data(), C) != 0 ||
-            bertx_mvindex_set_residual_buckets(H.res, cuts, wts) != 0 || fill(H.res) != 0)
+        if (F.pick_centroids(F.aux, C, cent) != 0 || bertx_mvindex_set_centroids(F.aux, cent.data(), C) != 0) return -1;
+        if (bertx_mvindex_train_residual_buckets(F.aux, storage == BERTX_INDEX_RES2 ? 2 : 4, cuts, wts) != 0) return -1;
+        bertx_mvindex_free(F.aux);
+        F.aux = nullptr;
+        F.mv = mvindex_create_on(0, w, n_docs, F.slots, storage);
+        if (!F.mv || bertx_mvindex_set_centroids(F.mv, cent.data(), C) != 0 ||
+            bertx_mvindex_set_residual_buckets(F.mv, cuts, wts) != 0 || F.fill(F.mv) != 0)
             return -1;
-        if (launch_unit_rows((float *)H.q.p, Lq, w, 777u, H.s) != 0) return -1;
-        HIP_RC(hipMemcpyAsync(H.id.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, H.s));
-        HIP_RC(hipStreamSynchronize(H.s));
-        auto timed = [&](auto &&fn, float *us) -> int32_t {
-            for (int i = 0; i < 3; ++i)
-                if (fn() != 0) return -1;
-            HIP_RC(hipEventRecord(H.a, H.s));
-            for (int i = 0; i < iters; ++i)
-                if (fn() != 0) return -1;
-            HIP_RC(hipEventRecord(H.b, H.s));
-            HIP_RC(hipEventSynchronize(H.b));
-            float ms = 0.f;
-            HIP_RC(hipEventElapsedTime(&ms, H.a, H.b));
-            *us = ms * 1000.f / (float)iters;
-            return 0;
-        };
-        if (timed([&] {
-                return bertx_mvindex_score_device(H.res, (const float *)H.q.p, Lq, (const int32_t *)H.id.p, n_cand,
-                                                  (float *)H.out.p, H.s);
-            }, avg_us) != 0)
+        if (F.queries(1, Lq) != 0) return -1;
+        const float *Q = (const float *)F.q.p;
+        float *out = (float *)F.out.p;
+        if (F.timed([&] { return bertx_mvindex_score_device(F.mv, Q, Lq, (const int32_t *)F.id.p, n_cand, out, F.s); },
+                    avg_us) != 0)
             return -1;
         const int32_t nc = std::min(n_cand, kMaxK), k = std::min(nc, 10);
-        return timed([&] {
-            return bertx_mvindex_search_pruned_device(H.res, (const float *)H.q.p, 1, Lq, k, nc, (float *)H.out.p,
-                                                      (int32_t *)H.oid.p, H.s);
-        }, avg_us + 1);
+        return F.timed([&] { return bertx_mvindex_search_pruned_device(F.mv, Q, 1, Lq, k, nc, out, (int32_t *)F.oid.p, F.s); },
+                       avg_us + 1);
     } catch (const std::exception &ex) {
         emb::errorf("bertx_bench_maxsim_res: %s\n", ex.what());
         return -1;
     }
 }
+
+}  // namespace
 
 extern "C" {
 
