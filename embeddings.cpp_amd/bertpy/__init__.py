@@ -337,6 +337,34 @@ def load_lib(path=None):
         L.bertx_test_mvindex_last_grid.argtypes = [vp]
     except AttributeError:
         pass
+    try:   # (document deletion and filtered search of the token store; absent from older BERT_LIB builds)
+        L.bertx_mvindex_remove.restype = c_i32
+        L.bertx_mvindex_remove.argtypes = [vp, vp, c_i32]
+        L.bertx_mvindex_remove_device.restype = c_i32
+        L.bertx_mvindex_remove_device.argtypes = [vp, vp, c_i32, vp]
+        L.bertx_mvindex_live.restype = c_i32
+        L.bertx_mvindex_live.argtypes = [vp]
+        L.bertx_mvindex_deleted.restype = c_i32
+        L.bertx_mvindex_deleted.argtypes = [vp, c_i32, c_i32, vp]
+        L.bertx_mvindex_search_filtered.restype = c_i32
+        L.bertx_mvindex_search_filtered.argtypes = [vp, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, vp]
+        L.bertx_mvindex_search_filtered_device.restype = c_i32
+        L.bertx_mvindex_search_filtered_device.argtypes = [vp, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp]
+        L.bertx_mvindex_candidates_filtered.restype = c_i32
+        L.bertx_mvindex_candidates_filtered.argtypes = [vp, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, vp]
+        L.bertx_mvindex_candidates_filtered_device.restype = c_i32
+        L.bertx_mvindex_candidates_filtered_device.argtypes = [vp, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp]
+        L.bertx_mvindex_search_pruned_filtered.restype = c_i32
+        L.bertx_mvindex_search_pruned_filtered.argtypes = [vp, vp, c_i32, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, vp]
+        L.bertx_mvindex_search_pruned_filtered_device.restype = c_i32
+        L.bertx_mvindex_search_pruned_filtered_device.argtypes = [vp, vp, c_i32, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, vp,
+                                                                  vp]
+        L.bertx_test_mvindex_last_masked.restype = c_i32
+        L.bertx_test_mvindex_last_masked.argtypes = [vp]
+        L.bertx_bench_maxsim_masked.restype = c_i32
+        L.bertx_bench_maxsim_masked.argtypes = [c_i32] * 11 + [c_f32p]
+    except AttributeError:
+        pass
     try:   # (residual-coded token stores; absent from older BERT_LIB builds)
         L.bertx_mvindex_set_residual_buckets.restype = c_i32
         L.bertx_mvindex_set_residual_buckets.argtypes = [vp, vp, vp]
@@ -704,6 +732,30 @@ class BertModel:
         return out
 
 
+def pack_allow(allow, B, size):
+    """(words uint32 [n_filters][words] or None, n_filters, words) of an allow= filter over `size`
+    units (rows of a BertIndex, documents of a BertTokenIndex) for B queries: a bool / 0-1 array
+    [size] (one filter for every query) or [B][size] (one per query), packed 32 units to a word,
+    unit r = bit r % 32 of word r / 32, padded to whole words; or the packed words themselves, a
+    uint32 array [words] or [B][words] with words >= ceil(size / 32), passed on as they are."""
+    if allow is None:
+        return None, 0, 0
+    raw = np.asarray(allow)
+    need = (size + 31) // 32
+    if raw.dtype == np.uint32 and raw.shape not in ((size,), (B, size)) and raw.ndim in (1, 2) and raw.shape[-1] >= need \
+            and (raw.ndim == 1 or raw.shape[0] in (1, B)):
+        packed = np.ascontiguousarray(np.atleast_2d(raw))
+        return packed, packed.shape[0], packed.shape[1]
+    a = raw.astype(bool)
+    if a.shape not in ((size,), (B, size)):
+        raise ValueError("expected allow of shape (%d,) or (%d, %d), got %r" % (size, B, size, a.shape))
+    a = np.atleast_2d(a)
+    padded = np.zeros((a.shape[0], 32 * need), bool)
+    padded[:, :size] = a
+    packed = np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view(np.uint32)
+    return packed.reshape(a.shape[0], need), a.shape[0], need
+
+
 class BertIndex:
     """A device-resident embedding index with fused top-k search (bertx_index_*): rows of
     the model's n_embd, stored as f16 (storage="f16") or as int8 with one f32 scale per
@@ -787,20 +839,9 @@ class BertIndex:
         return out.astype(bool)
 
     def _allow(self, allow, B):
-        """(words uint32 [n_filters][words] or None, n_filters, words) of allow= bool [size] or
-        [B][size]: 32 rows to a word, row r = bit r % 32 of word r / 32, padded to whole words."""
-        if allow is None:
-            return None, 0, 0
-        a = np.asarray(allow, bool)
-        size = len(self)
-        if a.shape not in ((size,), (B, size)):
-            raise ValueError("expected allow of shape (%d,) or (%d, %d), got %r" % (size, B, size, a.shape))
-        a = np.atleast_2d(a)
-        words = (size + 31) // 32
-        padded = np.zeros((a.shape[0], 32 * words), bool)
-        padded[:, :size] = a
-        packed = np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view(np.uint32)
-        return packed.reshape(a.shape[0], words), a.shape[0], words
+        """pack_allow over this store's len(): shared by BertIndex (rows) and BertTokenIndex
+        (documents)."""
+        return pack_allow(allow, B, len(self))
 
     def search(self, queries, k, allow=None):
         """(scores f32 [B][k], ids i32 [B][k]) of the k best rows per query, best first.  Deleted
@@ -955,6 +996,28 @@ class BertTokenIndex:
     def clear(self):
         self.lib.bertx_mvindex_clear(self.mv)
 
+    _allow = BertIndex._allow
+
+    def remove(self, ids):
+        """Delete the listed documents: they are never returned again (score() gives them -inf),
+        their ids are not reused, len() and token_slots do not change and doc() still answers.
+        Ids outside the store are ignored, repeats are harmless."""
+        a = np.ascontiguousarray(np.asarray(ids, np.int32).ravel())
+        rc = self.lib.bertx_mvindex_remove(self.mv, a.ctypes.data, a.size)
+        if rc != 0:
+            raise RuntimeError("bertx_mvindex_remove failed (%d)" % rc)
+
+    def live(self):
+        """len() minus the deleted documents."""
+        return int(self.lib.bertx_mvindex_live(self.mv))
+
+    def deleted(self, first, n):
+        """bool [n]: whether documents first .. first + n - 1 are deleted."""
+        out = np.zeros(n, np.uint8)
+        if n and self.lib.bertx_mvindex_deleted(self.mv, first, n, out.ctypes.data) != 0:
+            raise RuntimeError("bertx_mvindex_deleted failed")
+        return out.astype(bool)
+
     def _tokens(self, a):
         a = np.ascontiguousarray(np.asarray(a, np.float32))
         if a.ndim == 1:
@@ -1051,12 +1114,15 @@ class BertTokenIndex:
             raise RuntimeError("bertx_mvindex_score_text%s failed (%d)" % ("_colbert" if colbert is not None else "", rc))
         return out
 
-    def search(self, queries, k):
+    def search(self, queries, k, allow=None):
         """(scores f32 [B][k], ids i32 [B][k]): per query the k best documents of the whole
         store by MaxSim score, best first, equal scores by ascending id, (-inf, -1) where the
         store has fewer than k documents; the scores are the bits of score().  queries: one
         [Lq][width] array or a list of them; a ragged list is padded with zero rows to the
-        longest (a zero row adds +0).  At most 64 rows per query."""
+        longest (a zero row adds +0).  At most 64 rows per query.  Deleted documents are never
+        returned; allow (pack_allow: bool [docs], [B][docs] for one filter per query, or packed
+        uint32 words) limits the search to the documents it marks, with (-inf, -1) where fewer
+        than k are admissible (bert_hip.h "Deleting documents and filtered search")."""
         if isinstance(queries, np.ndarray) and queries.ndim <= 2:
             queries = [queries]
         qs = [self._tokens(q) for q in queries]
@@ -1070,7 +1136,12 @@ class BertTokenIndex:
             q[i, :len(a)] = a
         scores = np.zeros((len(qs), k), np.float32)
         ids = np.zeros((len(qs), k), np.int32)
-        rc = self.lib.bertx_mvindex_search(self.mv, q.ctypes.data, len(qs), Lq, k, scores.ctypes.data, ids.ctypes.data)
+        if allow is None:
+            rc = self.lib.bertx_mvindex_search(self.mv, q.ctypes.data, len(qs), Lq, k, scores.ctypes.data, ids.ctypes.data)
+        else:
+            f, nf, words = self._allow(allow, len(qs))
+            rc = self.lib.bertx_mvindex_search_filtered(self.mv, q.ctypes.data, len(qs), Lq, k, f.ctypes.data, nf, words,
+                                                        scores.ctypes.data, ids.ctypes.data)
         if rc != 0:
             raise RuntimeError("bertx_mvindex_search failed (%d)" % rc)
         return scores, ids
@@ -1161,28 +1232,41 @@ class BertTokenIndex:
             raise RuntimeError("bertx_mvindex_doc_codes failed (no centroids?)")
         return out
 
-    def candidates(self, queries, n_cand):
+    def candidates(self, queries, n_cand, allow=None):
         """(approx f32 [B][n_cand], ids i32 [B][n_cand]): per query the n_cand best documents by
         centroid interaction, MaxSim with every stored row replaced by its centroid; best
-        first, equal scores by ascending id, (-inf, -1) fill.  n_cand at most 128."""
+        first, equal scores by ascending id, (-inf, -1) fill.  n_cand at most 128.  Only
+        admissible documents are candidates: never a deleted one, and with allow (as in
+        search()) only those it marks."""
         q = self._queries(queries)
         approx = np.zeros((len(q), n_cand), np.float32)
         ids = np.zeros((len(q), n_cand), np.int32)
-        rc = self.lib.bertx_mvindex_candidates(self.mv, q.ctypes.data, q.shape[0], q.shape[1], n_cand, approx.ctypes.data,
-                                               ids.ctypes.data)
+        if allow is None:
+            rc = self.lib.bertx_mvindex_candidates(self.mv, q.ctypes.data, q.shape[0], q.shape[1], n_cand,
+                                                   approx.ctypes.data, ids.ctypes.data)
+        else:
+            f, nf, words = self._allow(allow, q.shape[0])
+            rc = self.lib.bertx_mvindex_candidates_filtered(self.mv, q.ctypes.data, q.shape[0], q.shape[1], n_cand,
+                                                            f.ctypes.data, nf, words, approx.ctypes.data, ids.ctypes.data)
         if rc != 0:
             raise RuntimeError("bertx_mvindex_candidates failed (%d)" % rc)
         return approx, ids
 
-    def search_pruned(self, queries, k, n_cand):
+    def search_pruned(self, queries, k, n_cand, allow=None):
         """search() over the n_cand candidates of candidates() only: their exact scores (the
         bits of score()), the k best.  k <= n_cand <= 128; with n_cand >= len(self) the result
-        is search()'s."""
+        is search()'s.  allow as in candidates(): with n_cand at least the number of admissible
+        documents the result is search(queries, k, allow)'s."""
         q = self._queries(queries)
         scores = np.zeros((len(q), k), np.float32)
         ids = np.zeros((len(q), k), np.int32)
-        rc = self.lib.bertx_mvindex_search_pruned(self.mv, q.ctypes.data, q.shape[0], q.shape[1], k, n_cand,
-                                                  scores.ctypes.data, ids.ctypes.data)
+        if allow is None:
+            rc = self.lib.bertx_mvindex_search_pruned(self.mv, q.ctypes.data, q.shape[0], q.shape[1], k, n_cand,
+                                                      scores.ctypes.data, ids.ctypes.data)
+        else:
+            f, nf, words = self._allow(allow, q.shape[0])
+            rc = self.lib.bertx_mvindex_search_pruned_filtered(self.mv, q.ctypes.data, q.shape[0], q.shape[1], k, n_cand,
+                                                               f.ctypes.data, nf, words, scores.ctypes.data, ids.ctypes.data)
         if rc != 0:
             raise RuntimeError("bertx_mvindex_search_pruned failed (%d)" % rc)
         return scores, ids

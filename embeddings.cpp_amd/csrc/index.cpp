@@ -73,33 +73,11 @@ constexpr int kStage = 256;   // rows / queries per staged chunk of the host for
 constexpr int kMaxK = 128;
 constexpr int kStageIds = kStage * kMaxK;   // int32 values the id staging buffer holds
 
-// The filters of one search (device memory): none (d null, n 0), one for every query
-// (stride 0) or one per query, `stride` words apart.
-struct Filters {
-    const uint32_t *d = nullptr;
-    int64_t stride = 0;
-    Filters from(int64_t query) const
-    {
-        Filters f = *this;
-        if (f.d) f.d += (size_t)query * (size_t)stride;
-        return f;
-    }
-};
-
-// What bertx_index_search_filtered accepts (idx locked): no filter as (NULL, 0), else 1 or B
-// filters of at least ceil(size / 32) words.
+// What bertx_index_search_filtered accepts (idx locked; store_common.h filters_fit, which
+// the token store shares with the Filters themselves).
 bool filters_ok(const bertx_index &ix, const void *filters, int32_t n_filters, int32_t words, int32_t B)
 {
-    if (!filters || n_filters == 0) return !filters && n_filters == 0;
-    return (n_filters == 1 || n_filters == B) && (int64_t)words >= (ix.n + 31) / 32;
-}
-
-Filters filters_of(const uint32_t *d_filters, int32_t n_filters, int32_t words)
-{
-    Filters f;
-    f.d = d_filters;
-    f.stride = n_filters > 1 ? words : 0;
-    return f;
+    return filters_fit(ix.n, filters, n_filters, words, B);
 }
 
 bool kind_known(int storage)
@@ -529,15 +507,11 @@ int32_t bertx_index_score_ids(struct bertx_index *idx, const float *queries, int
     return 0;
 }
 
-// The filters of a host call, uint32 [n_filters][words], staged in a device buffer of the
-// call's own (idx locked, its device current); the copy is ordered on the index's stream.
+// store_common.h stage_filters on the index's stream (idx locked, its device current)
 static int32_t stage_filters(struct bertx_index *idx, const uint32_t *filters, int32_t n_filters, int32_t words,
                              emb::DevBuf &buf)
 {
-    if (!filters) return 0;
-    const size_t bytes = (size_t)n_filters * (size_t)words * 4;
-    HIP_RC(hipMalloc(&buf.p, std::max<size_t>(bytes, 4)));
-    if (bytes) HIP_RC(hipMemcpyAsync(buf.p, filters, bytes, hipMemcpyHostToDevice, idx->stream));
+    HIP_RC(emb::stage_filters(idx->stream, filters, n_filters, words, buf));
     return 0;
 }
 

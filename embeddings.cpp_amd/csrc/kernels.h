@@ -230,6 +230,13 @@ struct SearchMask {
 // (the masked kernels take the mask as a template parameter pack of none or one)
 constexpr const SearchMask &first_mask(const SearchMask &m) { return m; }
 constexpr const uint32_t *first_tomb(const uint32_t *t) { return t; }
+// The mask of the pass of a token-store scan that starts at query q0 of the call: its own
+// filters (a shared filter has stride 0).
+inline SearchMask pass_mask(SearchMask m, int64_t q0)
+{
+    if (m.filt) m.filt += q0 * m.stride;
+    return m;
+}
 // Once per process and device (the calling thread's current one) before the first
 // launch_search: lets the search kernels use the CU's whole LDS.  Returns 0 or -1.
 int search_prepare_device();
@@ -319,11 +326,15 @@ int launch_mv_pack(const float *d_rows, int64_t t0, int64_t count, int w, const 
 // d_out[c] = sum_{i < Lq} max_{j < len} sim(q_i, row j of document id), id = d_ids[c] (or c
 // when d_ids is null), for c < n; -inf for an id outside [0, n_docs).  d_q f32 [Lq][w]
 // is normalised as the rows are.  1 <= Lq <= 64, n >= 1; -1 otherwise, -3: launch refused.
+// tomb (here and on the other two scorers; may be null): the store's tombstones, one bit per
+// document as index_mask.hip packs them; a document whose bit is 1 scores -inf as an id outside
+// [0, n_docs) does.  null launches the unmasked instantiation with the arguments above.
 // max_wg, ran_wg (here and on every scan of the store below; bert_hip.h bertx_test_mvindex_grid):
 // max_wg > 0 bounds the scan kernel's workgroups after the launcher's own rule and before
 // anything derived from them; *ran_wg, when given, receives the workgroups it launched.
 int launch_maxsim(const void *store, const void *d_table, int n_docs, int w, const float *d_q, int Lq,
-                  const int32_t *d_ids, int n, float *d_out, hipStream_t s, int max_wg = 0, int *ran_wg = nullptr);
+                  const int32_t *d_ids, int n, float *d_out, hipStream_t s, int max_wg = 0, int *ran_wg = nullptr,
+                  const uint32_t *tomb = nullptr);
 // The same two over an int8 store (maxsim_i8.hip): rows in the SEARCH_I8 fragment order,
 // each the embedding index's int8 quantization q of the raw row, and scales f32 [token
 // slots], u = 1 / sqrt(sum q_i^2) per slot (0 for a zero row), so that q u has unit
@@ -333,7 +344,7 @@ int launch_mv_pack_i8(const float *d_rows, int64_t t0, int64_t count, int w, con
                       const void *d_table, int n_new, void *store, float *scales, hipStream_t s);
 int launch_maxsim_i8(const void *store, const float *scales, const void *d_table, int n_docs, int w, const float *d_q,
                      int Lq, const int32_t *d_ids, int n, float *d_out, hipStream_t s, int max_wg = 0,
-                     int *ran_wg = nullptr);
+                     int *ran_wg = nullptr, const uint32_t *tomb = nullptr);
 // The full scan (maxsim_search.hip): d_scores f32 [B][k], d_ids i32 [B][k] = per query the
 // k best documents of all n_docs by the scorers' score, bit for bit, best first, equal
 // scores by ascending id, (-inf, -1) where the store has fewer than k documents.  d_q f32
@@ -343,11 +354,17 @@ int launch_maxsim_i8(const void *store, const float *scales, const void *d_table
 // over the store; per pass one streaming kernel and one or two selection kernels.  scratch:
 // maxsim_search_scratch_bytes() (sized by the current device's CU count and k = 128).
 // 1 <= Lq <= 64, 1 <= k <= 128, B >= 1; -1 otherwise (nothing launched), -3: launch refused.
+// mask (here and on launch_maxsim_candidates; may be null): a SearchMask over documents, tomb
+// the store's tombstones and filt the call's filters, one for all (stride 0) or one per query
+// of d_q; the masked kernels list a document for a query only when it is admissible (bert_hip.h
+// "Deleting documents and filtered search").  null launches the unmasked instantiations with
+// the arguments above and nothing else.
 int maxsim_search_prepare_device();
 size_t maxsim_search_scratch_bytes();
 int launch_maxsim_search(const void *store, const float *scales, int storage, const void *d_table, int n_docs,
                          int64_t used_groups, int w, const float *d_q, int B, int Lq, int k, void *scratch,
-                         float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg = 0, int *ran_wg = nullptr);
+                         float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg = 0, int *ran_wg = nullptr,
+                         const SearchMask *mask = nullptr);
 
 // ---- centroid codes of the token store (maxsim_codes.hip; bert_hip.h "Centroid codes") ----
 // The centroids are C rows (a multiple of 16) packed as one document of C tokens from group
@@ -372,7 +389,8 @@ int maxsim_approx_prepare_device();
 int launch_maxsim_candidates(const uint16_t *codes, const void *d_table, int n_docs, int64_t used_groups, int storage,
                              int w, const void *cent, const float *cent_u, int C, const float *d_q, int nq, int Lq,
                              int n_cand, float *tscratch, void *scratch, float *d_approx, int32_t *d_ids, int stages,
-                             int *form, hipStream_t s, int max_wg = 0, int *ran_wg = nullptr);
+                             int *form, hipStream_t s, int max_wg = 0, int *ran_wg = nullptr,
+                             const SearchMask *mask = nullptr);
 // out_s / out_i [nq][k] = the k best by `better` of each query's n_cand (exact[j], ids[j])
 // pairs; a pair whose id is -1 counts as the fill.
 int launch_maxsim_rerank_select(const float *exact, const int32_t *ids, int nq, int n_cand, int k, float *out_s,
@@ -393,7 +411,7 @@ int launch_res_encode(const void *staging, int64_t groups, int w, int nbits, con
                       const float *cuts, const uint16_t *wts, uint32_t *bits, float *u, hipStream_t s);
 int launch_maxsim_res(const uint32_t *bits, const float *u, const uint16_t *codes, const void *cent, const uint32_t *pair,
                       int nbits, const void *d_table, int n_docs, int w, const float *d_q, int Lq, const int32_t *d_ids, int n,
-                      float *d_out, hipStream_t s, int max_wg = 0, int *ran_wg = nullptr);
+                      float *d_out, hipStream_t s, int max_wg = 0, int *ran_wg = nullptr, const uint32_t *tomb = nullptr);
 
 // ---- the classification head (head.hip): pooler dense + tanh + classifier on the
 // sentences' [CLS] rows, all f32, one form for the three chains ----

@@ -65,12 +65,15 @@ __host__ __device__ inline size_t maxsim_lds_bytes(int QT, int w) { return (size
 // the four fold into the lane's running maxima, which start at -inf.  After the
 // document the epilogue (maxsim_common.h doc_score) sums the maxima; lane 0 stores.
 // An id outside [0, n_docs) gets -inf and touches nothing else.
-template <int QT>
+// Tomb: nothing, the unmasked kernel; or the store's tombstones (const uint32_t *), the masked
+// kernel: a deleted document is treated exactly as an id outside [0, n_docs); its bit is read
+// for ids in range only.
+template <int QT, class... Tomb>
 __global__ __launch_bounds__(kThreads) void maxsim_kernel(const h16x8 *__restrict__ store,
                                                           const int2 *__restrict__ table, int n_docs,
                                                           const float *__restrict__ q, int Lq, int w,
                                                           const int32_t *__restrict__ ids, int n,
-                                                          float *__restrict__ out)
+                                                          float *__restrict__ out, Tomb... tomb)
 {
     extern __shared__ uint4 smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -96,7 +99,11 @@ __global__ __launch_bounds__(kThreads) void maxsim_kernel(const h16x8 *__restric
     const int g4 = lane >> 4;
     for (int c = (int)blockIdx.x * 4 + ws; c < n; c += stride) {
         const int id = __builtin_amdgcn_readfirstlane(ids ? ids[c] : c);
-        if ((unsigned)id >= (unsigned)n_docs) {
+        bool gone = (unsigned)id >= (unsigned)n_docs;
+        if constexpr (sizeof...(Tomb) != 0) {
+            if (!gone) gone = doc_deleted(first_tomb(tomb...), id);
+        }
+        if (gone) {
             if (lane == 0) out[c] = -INFINITY;
             continue;
         }
@@ -167,7 +174,10 @@ int maxsim_prepare_device()
 {
     hipError_t e = hipSuccess;
     for (int qt = 1; qt <= 4 && e == hipSuccess; ++qt)
-        with_tiles(qt, [&](auto QT) { e = allow_lds((const void *)maxsim_kernel<decltype(QT)::value>); });
+        with_tiles(qt, [&](auto QT) {
+            e = allow_lds((const void *)maxsim_kernel<decltype(QT)::value>);
+            if (e == hipSuccess) e = allow_lds((const void *)maxsim_kernel<decltype(QT)::value, const uint32_t *>);
+        });
     return e == hipSuccess ? maxsim_i8_prepare_device() : -1;
 }
 
@@ -183,7 +193,7 @@ int launch_mv_pack(const float *d_rows, int64_t t0, int64_t count, int w, const 
 }
 
 int launch_maxsim(const void *store, const void *d_table, int n_docs, int w, const float *d_q, int Lq,
-                  const int32_t *d_ids, int n, float *d_out, hipStream_t s, int max_wg, int *ran_wg)
+                  const int32_t *d_ids, int n, float *d_out, hipStream_t s, int max_wg, int *ran_wg, const uint32_t *tomb)
 {
     // (the candidate index advances by at most 4 * 4 * CUs per step, in int32)
     if (Lq < 1 || Lq > 64 || n < 1 || n > 0x7fff0000 || n_docs < 0 || w % 64 || w < 64 || w > 1024) return -1;
@@ -192,8 +202,12 @@ int launch_maxsim(const void *store, const void *d_table, int n_docs, int w, con
     if (lds > (size_t)kLdsBudget) return -1;
     const unsigned P = (unsigned)scorer_grid(lds, n, max_wg, ran_wg);
     with_tiles(QT, [&](auto qt) {
-        maxsim_kernel<decltype(qt)::value><<<P, kThreads, lds, s>>>((const h16x8 *)store, (const int2 *)d_table, n_docs, d_q,
-                                                                    Lq, w, d_ids, n, d_out);
+        if (tomb)
+            maxsim_kernel<decltype(qt)::value, const uint32_t *><<<P, kThreads, lds, s>>>(
+                (const h16x8 *)store, (const int2 *)d_table, n_docs, d_q, Lq, w, d_ids, n, d_out, tomb);
+        else
+            maxsim_kernel<decltype(qt)::value><<<P, kThreads, lds, s>>>((const h16x8 *)store, (const int2 *)d_table, n_docs, d_q,
+                                                                        Lq, w, d_ids, n, d_out);
     });
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

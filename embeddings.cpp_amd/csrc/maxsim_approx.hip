@@ -100,12 +100,19 @@ __host__ __device__ inline size_t scan_list_bytes(int NQ, int n_cand) { return (
 // lists of query i and writes partial [query][P][n_cand].
 // LDS_T: the table is first copied into LDS, [C][LINE] behind the lists; else the lookups
 // read it from global memory.  The values, and so the results, are the same.
-template <bool LDS_T>
+// Mask: nothing, the unmasked kernel, whose arguments end at partial; or one SearchMask over
+// documents (filt at the pass's first filter), the masked kernel: maxsim_search_kernel's
+// change at the document close, for either placement of the table.
+template <bool LDS_T, class... Mask>
 __global__ __launch_bounds__(kScanThreads) void approx_scan_kernel(const uint32_t *__restrict__ codes,
                                                                    const int2 *__restrict__ table, int n_docs, int G,
                                                                    const float *__restrict__ T, int C, int QTq, int NQ,
-                                                                   int Lq, int n_cand, Hit *__restrict__ partial)
+                                                                   int Lq, int n_cand, Hit *__restrict__ partial,
+                                                                   Mask... mask)
 {
+    constexpr bool MK = sizeof...(Mask) != 0;
+    SearchMask m{nullptr, nullptr, 0};
+    if constexpr (MK) m = first_mask(mask...);
     extern __shared__ uint4 smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int TT = QTq * NQ, LINE = line_floats(TT);
@@ -155,10 +162,23 @@ __global__ __launch_bounds__(kScanThreads) void approx_scan_kernel(const uint32_
         int id = dA, len = tab[dA].y, len_next = tab[min(dA + 1, n_docs - 1)].y, rbase = 0;
         float ps[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         int pid = -1, npend = 0;
+        // masked: the admissible words of the open document and of the one behind it; per lane
+        // the parked document's bit per query
+        uint32_t aw[4] = {}, an[4] = {};
+        int pok = 0;
+        if constexpr (MK) {
+            admit_words<4>(m, NQ, dA, aw);
+            admit_words<4>(m, NQ, min(dA + 1, n_docs - 1), an);
+        }
         auto flush = [&]() {
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (i < NQ) list_offer(mine + (size_t)i * n_cand, n_cand, ps[i], pid, lane < npend, lane);
+            for (int i = 0; i < 4; ++i) {
+                if constexpr (MK) {
+                    if (i < NQ) list_offer(mine + (size_t)i * n_cand, n_cand, ps[i], pid, lane < npend && ((pok >> i) & 1), lane);
+                } else {
+                    if (i < NQ) list_offer(mine + (size_t)i * n_cand, n_cand, ps[i], pid, lane < npend, lane);
+                }
+            }
             npend = 0;
         };
         // the group whose codes are dwords 8 gi .. 8 gi + 7 of `cur`
@@ -204,11 +224,23 @@ __global__ __launch_bounds__(kScanThreads) void approx_scan_kernel(const uint32_
                     ps[i] = lane == npend ? s0 : ps[i];
                 }
                 pid = lane == npend ? id : pid;
-                ++npend;
+                if constexpr (MK) {
+                    const int ok = admit_bits<4>(aw, NQ, id);   // bit i: query i of the pass admits the document
+                    pok = lane == npend ? ok : pok;
+                    npend += ok != 0;                           // no query admits it: the lane is taken again
+                } else {
+                    ++npend;
+                }
                 ++id;
                 mx = -INFINITY;
                 len = len_next;
                 len_next = tab[min(id + 1, n_docs - 1)].y;
+                if constexpr (MK) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) aw[i] = an[i];
+                    // wave-uniform: the document behind the one that opens starts a word
+                    if (((id + 1) & 31) == 0 && id + 1 < n_docs) admit_words<4>(m, NQ, id + 1, an);
+                }
                 rbase = 0;
                 if (npend == 64) flush();
             } else {
@@ -349,17 +381,20 @@ int maxsim_approx_prepare_device()
     if (e == hipSuccess) e = allow_lds((const void *)approx_table_kernel<SEARCH_I8>);
     if (e == hipSuccess) e = allow_lds((const void *)approx_scan_kernel<true>);
     if (e == hipSuccess) e = allow_lds((const void *)approx_scan_kernel<false>);
+    if (e == hipSuccess) e = allow_lds((const void *)approx_scan_kernel<true, SearchMask>);
+    if (e == hipSuccess) e = allow_lds((const void *)approx_scan_kernel<false, SearchMask>);
     return e == hipSuccess ? 0 : -1;
 }
 
 int launch_maxsim_candidates(const uint16_t *codes, const void *d_table, int n_docs, int64_t used_groups, int storage,
                              int w, const void *cent, const float *cent_u, int C, const float *d_q, int nq, int Lq,
                              int n_cand, float *tscratch, void *scratch, float *d_approx, int32_t *d_ids, int stages,
-                             int *form, hipStream_t s, int max_wg, int *ran_wg)
+                             int *form, hipStream_t s, int max_wg, int *ran_wg, const SearchMask *mask)
 {
     if (Lq < 1 || Lq > 64 || n_cand < 1 || n_cand > 128 || n_docs < 0 || used_groups < 0 || used_groups > 0x7ffffff0ll ||
         w % 64 || w < 64 || w > 1024 || C < 16 || C > 65536 || C % 16 || !codes || !cent || !tscratch || !scratch)
         return -1;
+    if (mask && !mask->tomb) return -1;
     if ((storage != SEARCH_F16 && storage != SEARCH_I8) || (storage == SEARCH_I8 && !cent_u)) return -1;
     const int QTq = (Lq + 15) / 16;
     if (nq < 1 || nq * QTq > 4) return -1;
@@ -375,7 +410,13 @@ int launch_maxsim_candidates(const uint16_t *codes, const void *d_table, int n_d
     const bool in_lds = lists + tbytes <= (size_t)kLdsBudget;
     const size_t lds = in_lds ? lists + tbytes : lists;
     const int P = scan_grid(lds, G, kScanWaves, max_wg, ran_wg);   // the full scan's rule, which sized the scratch
-    if (in_lds)
+    if (mask && in_lds)
+        approx_scan_kernel<true, SearchMask><<<(unsigned)P, kScanThreads, lds, s>>>(
+            (const uint32_t *)codes, (const int2 *)d_table, n_docs, G, tscratch, C, QTq, nq, Lq, n_cand, (Hit *)scratch, *mask);
+    else if (mask)
+        approx_scan_kernel<false, SearchMask><<<(unsigned)P, kScanThreads, lds, s>>>(
+            (const uint32_t *)codes, (const int2 *)d_table, n_docs, G, tscratch, C, QTq, nq, Lq, n_cand, (Hit *)scratch, *mask);
+    else if (in_lds)
         approx_scan_kernel<true><<<(unsigned)P, kScanThreads, lds, s>>>((const uint32_t *)codes, (const int2 *)d_table, n_docs,
                                                                         G, tscratch, C, QTq, nq, Lq, n_cand, (Hit *)scratch);
     else

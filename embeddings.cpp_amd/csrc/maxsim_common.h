@@ -142,6 +142,46 @@ __device__ __forceinline__ int first_doc_at(TablePtr tab, int n_docs, int g)
     return lo;
 }
 
+// The document masks of the masked scans (bert_hip.h "Deleting documents and filtered
+// search"): kernels.h SearchMask with a document in the place of a row.  A
+// document is wave-uniform in the scans, so its mask words are too, and come as the table
+// does: through the constant address space.
+typedef const __attribute__((address_space(4))) uint32_t *MaskPtr;
+
+// a[i], i < nq <= N: the admissible word of query i of the pass (m.filt points at the pass's
+// first filter) for the 32 documents around `doc`: ~tombstones & filter, the tombstones alone
+// without a filter.  doc < n_docs: the words past ceil(n_docs / 32) are never indexed.
+template <int N>
+__device__ __forceinline__ void admit_words(const SearchMask &m, int nq, int doc, uint32_t (&a)[N])
+{
+    const MaskPtr tomb = (MaskPtr)(uintptr_t)m.tomb, filt = (MaskPtr)(uintptr_t)m.filt;
+    const uint32_t live = ~tomb[doc >> 5];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        if (i >= nq) break;
+        a[i] = m.filt ? live & filt[(int64_t)i * m.stride + (doc >> 5)] : live;
+    }
+}
+
+// Bit i of the result: query i of the pass admits `doc`, by the words admit_words gave for it.
+template <int N>
+__device__ __forceinline__ int admit_bits(const uint32_t (&a)[N], int nq, int doc)
+{
+    int ok = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        if (i >= nq) break;
+        ok |= (int)((a[i] >> (doc & 31)) & 1u) << i;
+    }
+    return ok;
+}
+
+// The scorers' test of a candidate under tombstones: the bit of an id in [0, n_docs).
+__device__ __forceinline__ bool doc_deleted(const uint32_t *tomb, int id)
+{
+    return (((MaskPtr)(uintptr_t)tomb)[id >> 5] >> (id & 31)) & 1u;
+}
+
 // The document of source row t of an add call: src_off[i] (i < n_new, ascending,
 // src_off[0] = 0) is the first source row of the call's i-th document, and row t belongs to
 // the last document d whose src_off is <= t.  With table[d] = (first group, len) the row

@@ -66,13 +66,16 @@ __host__ __device__ inline size_t maxsim_i8_lds_bytes(int QT, int w) { return (s
 // rows >= len select -inf, and the four fold into the lane's running maxima.  The
 // epilogue is the scorers' one (maxsim_common.h doc_score).
 // An id outside [0, n_docs) gets -inf and touches nothing else.
-template <int QT>
+// Tomb: nothing, the unmasked kernel; or the store's tombstones (const uint32_t *), the masked
+// kernel: a deleted document is treated exactly as an id outside [0, n_docs); its bit is read
+// for ids in range only.
+template <int QT, class... Tomb>
 __global__ __launch_bounds__(kThreads) void maxsim_i8_kernel(const i32x4 *__restrict__ store,
                                                              const float *__restrict__ scales,
                                                              const int2 *__restrict__ table, int n_docs,
                                                              const float *__restrict__ q, int Lq, int w,
                                                              const int32_t *__restrict__ ids, int n,
-                                                             float *__restrict__ out)
+                                                             float *__restrict__ out, Tomb... tomb)
 {
     extern __shared__ uint4 smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -125,7 +128,11 @@ __global__ __launch_bounds__(kThreads) void maxsim_i8_kernel(const i32x4 *__rest
 
     for (int c = (int)blockIdx.x * 4 + ws; c < n; c += stride) {
         const int id = __builtin_amdgcn_readfirstlane(ids ? ids[c] : c);
-        if ((unsigned)id >= (unsigned)n_docs) {
+        bool gone = (unsigned)id >= (unsigned)n_docs;
+        if constexpr (sizeof...(Tomb) != 0) {
+            if (!gone) gone = doc_deleted(first_tomb(tomb...), id);
+        }
+        if (gone) {
             if (lane == 0) out[c] = -INFINITY;
             continue;
         }
@@ -220,7 +227,10 @@ int maxsim_i8_prepare_device()
 {
     hipError_t e = hipSuccess;
     for (int qt = 1; qt <= 4 && e == hipSuccess; ++qt)
-        with_tiles(qt, [&](auto QT) { e = allow_lds((const void *)maxsim_i8_kernel<decltype(QT)::value>); });
+        with_tiles(qt, [&](auto QT) {
+            e = allow_lds((const void *)maxsim_i8_kernel<decltype(QT)::value>);
+            if (e == hipSuccess) e = allow_lds((const void *)maxsim_i8_kernel<decltype(QT)::value, const uint32_t *>);
+        });
     return e == hipSuccess ? 0 : -1;
 }
 
@@ -236,7 +246,8 @@ int launch_mv_pack_i8(const float *d_rows, int64_t t0, int64_t count, int w, con
 }
 
 int launch_maxsim_i8(const void *store, const float *scales, const void *d_table, int n_docs, int w, const float *d_q,
-                     int Lq, const int32_t *d_ids, int n, float *d_out, hipStream_t s, int max_wg, int *ran_wg)
+                     int Lq, const int32_t *d_ids, int n, float *d_out, hipStream_t s, int max_wg, int *ran_wg,
+                     const uint32_t *tomb)
 {
     // (the candidate index advances by at most 4 * 4 * CUs per step, in int32)
     if (Lq < 1 || Lq > 64 || n < 1 || n > 0x7fff0000 || n_docs < 0 || w % 64 || w < 64 || w > 1024 || !scales) return -1;
@@ -245,8 +256,12 @@ int launch_maxsim_i8(const void *store, const float *scales, const void *d_table
     if (lds > (size_t)kLdsBudget) return -1;
     const unsigned P = (unsigned)scorer_grid(lds, n, max_wg, ran_wg);
     with_tiles(QT, [&](auto qt) {
-        maxsim_i8_kernel<decltype(qt)::value><<<P, kThreads, lds, s>>>((const i32x4 *)store, scales, (const int2 *)d_table,
-                                                                       n_docs, d_q, Lq, w, d_ids, n, d_out);
+        if (tomb)
+            maxsim_i8_kernel<decltype(qt)::value, const uint32_t *><<<P, kThreads, lds, s>>>(
+                (const i32x4 *)store, scales, (const int2 *)d_table, n_docs, d_q, Lq, w, d_ids, n, d_out, tomb);
+        else
+            maxsim_i8_kernel<decltype(qt)::value><<<P, kThreads, lds, s>>>((const i32x4 *)store, scales, (const int2 *)d_table,
+                                                                           n_docs, d_q, Lq, w, d_ids, n, d_out);
     });
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -120,7 +120,10 @@ __host__ __device__ inline size_t res_lds_bytes(int QT, int w, int NB)
 // group's last block accumulator register r of lane 16g + c is (row 4g + r, query c): it is
 // multiplied by u[4g + r], rows >= len become -inf, and the four fold into the lane's
 // running maximum.  The epilogue is the scorers' one (maxsim_common.h doc_score).
-template <int QT, int NB>
+// Tomb: nothing, the unmasked kernel; or the store's tombstones (const uint32_t *), the masked
+// kernel: a deleted document is treated exactly as an id outside [0, n_docs); its bit is read
+// for ids in range only.
+template <int QT, int NB, class... Tomb>
 __global__ __launch_bounds__(kThreads) void maxsim_res_kernel(const uint32_t *__restrict__ bits,
                                                               const float *__restrict__ us,
                                                               const uint16_t *__restrict__ codes,
@@ -129,7 +132,7 @@ __global__ __launch_bounds__(kThreads) void maxsim_res_kernel(const uint32_t *__
                                                               const int2 *__restrict__ table, int n_docs,
                                                               const float *__restrict__ q, int Lq, int w,
                                                               const int32_t *__restrict__ ids, int n,
-                                                              float *__restrict__ out)
+                                                              float *__restrict__ out, Tomb... tomb)
 {
     constexpr int DW = NB / 2, NP = 1 << (2 * NB);
     typedef uint32_t Bits __attribute__((ext_vector_type(DW)));
@@ -149,7 +152,11 @@ __global__ __launch_bounds__(kThreads) void maxsim_res_kernel(const uint32_t *__
     const int g4 = lane >> 4, f = lane & 15;
     for (int c = (int)blockIdx.x * 4 + ws; c < n; c += stride) {
         const int id = __builtin_amdgcn_readfirstlane(ids ? ids[c] : c);
-        if ((unsigned)id >= (unsigned)n_docs) {
+        bool gone = (unsigned)id >= (unsigned)n_docs;
+        if constexpr (sizeof...(Tomb) != 0) {
+            if (!gone) gone = doc_deleted(first_tomb(tomb...), id);
+        }
+        if (gone) {
             if (lane == 0) out[c] = -INFINITY;
             continue;
         }
@@ -261,15 +268,19 @@ __global__ __launch_bounds__(kThreads) void maxsim_res_kernel(const uint32_t *__
 template <int NB>
 int launch_maxsim_res_nb(const uint32_t *bits, const float *u, const uint16_t *codes, const void *cent, const uint32_t *pair,
                          const void *d_table, int n_docs, int w, const float *d_q, int Lq, const int32_t *d_ids, int n,
-                         float *d_out, hipStream_t s, int max_wg, int *ran_wg)
+                         float *d_out, hipStream_t s, int max_wg, int *ran_wg, const uint32_t *tomb)
 {
     const int QT = (Lq + 15) / 16;
     const size_t lds = res_lds_bytes(QT, w, NB);
     if (lds > (size_t)kLdsBudget) return -1;
     const unsigned P = (unsigned)scorer_grid(lds, n, max_wg, ran_wg);
     with_tiles(QT, [&](auto qt) {
-        maxsim_res_kernel<decltype(qt)::value, NB><<<P, kThreads, lds, s>>>(
-            bits, u, codes, (const h16x8 *)cent, pair, (const int2 *)d_table, n_docs, d_q, Lq, w, d_ids, n, d_out);
+        if (tomb)
+            maxsim_res_kernel<decltype(qt)::value, NB, const uint32_t *><<<P, kThreads, lds, s>>>(
+                bits, u, codes, (const h16x8 *)cent, pair, (const int2 *)d_table, n_docs, d_q, Lq, w, d_ids, n, d_out, tomb);
+        else
+            maxsim_res_kernel<decltype(qt)::value, NB><<<P, kThreads, lds, s>>>(
+                bits, u, codes, (const h16x8 *)cent, pair, (const int2 *)d_table, n_docs, d_q, Lq, w, d_ids, n, d_out);
     });
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -283,6 +294,8 @@ int maxsim_res_prepare_device()
         with_tiles(qt, [&](auto QT) {
             e = allow_lds((const void *)maxsim_res_kernel<decltype(QT)::value, 2>);
             if (e == hipSuccess) e = allow_lds((const void *)maxsim_res_kernel<decltype(QT)::value, 4>);
+            if (e == hipSuccess) e = allow_lds((const void *)maxsim_res_kernel<decltype(QT)::value, 2, const uint32_t *>);
+            if (e == hipSuccess) e = allow_lds((const void *)maxsim_res_kernel<decltype(QT)::value, 4, const uint32_t *>);
         });
     return e == hipSuccess ? 0 : -1;
 }
@@ -314,15 +327,15 @@ int launch_res_encode(const void *staging, int64_t groups, int w, int nbits, con
 
 int launch_maxsim_res(const uint32_t *bits, const float *u, const uint16_t *codes, const void *cent, const uint32_t *pair,
                       int nbits, const void *d_table, int n_docs, int w, const float *d_q, int Lq, const int32_t *d_ids, int n,
-                      float *d_out, hipStream_t s, int max_wg, int *ran_wg)
+                      float *d_out, hipStream_t s, int max_wg, int *ran_wg, const uint32_t *tomb)
 {
     if (Lq < 1 || Lq > 64 || n < 1 || n > 0x7fff0000 || n_docs < 0 || w % 64 || w < 64 || w > 1024 ||
         (nbits != 2 && nbits != 4) || !bits || !u || !pair)
         return -1;   // (codes and cent are read for stored documents only, which need them to exist)
     return nbits == 2 ? launch_maxsim_res_nb<2>(bits, u, codes, cent, pair, d_table, n_docs, w, d_q, Lq, d_ids, n, d_out, s,
-                                                max_wg, ran_wg)
+                                                max_wg, ran_wg, tomb)
                       : launch_maxsim_res_nb<4>(bits, u, codes, cent, pair, d_table, n_docs, w, d_q, Lq, d_ids, n, d_out, s,
-                                                max_wg, ran_wg);
+                                                max_wg, ran_wg, tomb);
 }
 
 }  // namespace emb

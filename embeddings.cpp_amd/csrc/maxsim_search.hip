@@ -56,13 +56,25 @@ __host__ __device__ inline size_t msearch_lds_bytes(int TT, int NQ, int w, int k
 // once per pass over the ring when the next pass could overflow the 64 lanes, and at the
 // end; nothing in the stream crosses waves.  Then one barrier, wave q folds the four
 // waves' lists of query q and writes partial [query][P][k].
-template <int QTq, int NQ, int ST>
+// Mask: nothing, the unmasked kernel, whose arguments end at partial; or one SearchMask over
+// documents (filt at the pass's first filter), the masked kernel.  The mask
+// acts where a document closes.  Its admissible words (maxsim_common.h admit_words, one per
+// query of the pass, wave-uniform, through the scalar cache) are held for the open document
+// and for the one behind it; the word of the next 32 documents is asked for when the document
+// before them opens, a whole document ahead of its first use, as len_next is.  A document that
+// no query of the pass admits takes no pending lane; one that some admit takes a lane, and the
+// queries' bits are parked beside its scores (`pok`) and become each query's offer predicate.
+// The scores themselves are computed as ever.
+template <int QTq, int NQ, int ST, class... Mask>
 __global__ __launch_bounds__(kThreads) void maxsim_search_kernel(const typename Store<ST>::Block *__restrict__ store,
                                                                  const float *__restrict__ scales,
                                                                  const int2 *__restrict__ table, int n_docs, int G,
                                                                  const float *__restrict__ q, int Lq, int w, int k,
-                                                                 Hit *__restrict__ partial)
+                                                                 Hit *__restrict__ partial, Mask... mask)
 {
+    constexpr bool MK = sizeof...(Mask) != 0;
+    SearchMask m{nullptr, nullptr, 0};
+    if constexpr (MK) m = first_mask(mask...);
     typedef Store<ST> S;
     typedef typename S::Block Block;
     typedef typename S::Acc Acc;
@@ -157,9 +169,21 @@ __global__ __launch_bounds__(kThreads) void maxsim_search_kernel(const typename 
 #pragma unroll
         for (int i = 0; i < NQ; ++i) ps[i] = -INFINITY;
         int pid = -1, npend = 0;
+        // masked: the admissible words of the open document and of the one behind it; per lane
+        // the parked document's bit per query
+        uint32_t aw[NQ] = {}, an[NQ] = {};
+        int pok = 0;
+        if constexpr (MK) {
+            admit_words<NQ>(m, NQ, dA, aw);
+            admit_words<NQ>(m, NQ, min(dA + 1, n_docs - 1), an);
+        }
         auto flush = [&]() {
 #pragma unroll
-            for (int i = 0; i < NQ; ++i) list_offer(mine + (size_t)i * k, k, ps[i], pid, lane < npend, lane);
+            for (int i = 0; i < NQ; ++i) {
+                bool on = lane < npend;
+                if constexpr (MK) on = on && ((pok >> i) & 1);
+                list_offer(mine + (size_t)i * k, k, ps[i], pid, on, lane);
+            }
             npend = 0;
         };
 
@@ -197,6 +221,8 @@ __global__ __launch_bounds__(kThreads) void maxsim_search_kernel(const typename 
                 }
                 kb = 0;
                 if (rbase + 16 >= len) {   // wave-uniform: the document's last group
+                    int ok = 1;            // masked: bit i set when query i of the pass admits the document
+                    if constexpr (MK) ok = admit_bits<NQ>(aw, NQ, id);
 #pragma unroll
                     for (int i = 0; i < NQ; ++i) {
                         // doc_score<QTq> of the query's maxima (maxsim_common.h) written out, the
@@ -218,10 +244,21 @@ __global__ __launch_bounds__(kThreads) void maxsim_search_kernel(const typename 
                         ps[i] = lane == npend ? s0 : ps[i];
                     }
                     pid = lane == npend ? id : pid;
-                    ++npend;
+                    if constexpr (MK) {
+                        pok = lane == npend ? ok : pok;
+                        npend += ok != 0;   // no query admits it: the lane is taken again
+                    } else {
+                        ++npend;
+                    }
                     ++id;
                     len = len_next;
                     len_next = tab[min(id + 1, n_docs - 1)].y;
+                    if constexpr (MK) {
+#pragma unroll
+                        for (int i = 0; i < NQ; ++i) aw[i] = an[i];
+                        // wave-uniform: the document behind the one that opens starts a word
+                        if (((id + 1) & 31) == 0 && id + 1 < n_docs) admit_words<NQ>(m, NQ, id + 1, an);
+                    }
                     rbase = 0;
                 } else {
                     rbase += 16;
@@ -333,21 +370,23 @@ bool with_pass(int qtq, int nq, F &&f)
     return fits;
 }
 
-template <int ST>
+template <int ST, class... Mask>
 hipError_t allow_lds_all()
 {
     hipError_t e = hipSuccess;
     for (int qtq = 1; qtq <= 4; ++qtq)
         for (int nq = 1; nq <= 4 / qtq && e == hipSuccess; ++nq)
             with_pass(qtq, nq, [&](auto a, auto b) {
-                e = allow_lds((const void *)maxsim_search_kernel<decltype(a)::value, decltype(b)::value, ST>);
+                e = allow_lds((const void *)maxsim_search_kernel<decltype(a)::value, decltype(b)::value, ST, Mask...>);
             });
     return e;
 }
 
-template <int ST>
+// mask: none (the unmasked kernels) or the call's SearchMask
+template <int ST, class... Mask>
 int launch_all(const void *store, const float *scales, const void *table, int n_docs, int G, int w, const float *d_q,
-               int B, int Lq, int k, void *scratch, float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg, int *ran_wg)
+               int B, int Lq, int k, void *scratch, float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg, int *ran_wg,
+               Mask... mask)
 {
     const int QTq = (Lq + 15) / 16, per_pass = 4 / QTq;
     for (int b0 = 0; b0 < B; b0 += per_pass) {
@@ -358,8 +397,10 @@ int launch_all(const void *store, const float *scales, const void *table, int n_
         const float *Q = d_q + (size_t)b0 * Lq * w;
         Hit *part = (Hit *)scratch;
         const bool fits = with_pass(QTq, nq, [&](auto a, auto b) {
-            maxsim_search_kernel<decltype(a)::value, decltype(b)::value, ST><<<(unsigned)P, kThreads, lds, s>>>(
-                (const typename Store<ST>::Block *)store, scales, (const int2 *)table, n_docs, G, Q, Lq, w, k, part);
+            // (the pass's own filters: a shared filter has stride 0)
+            maxsim_search_kernel<decltype(a)::value, decltype(b)::value, ST, Mask...><<<(unsigned)P, kThreads, lds, s>>>(
+                (const typename Store<ST>::Block *)store, scales, (const int2 *)table, n_docs, G, Q, Lq, w, k, part,
+                pass_mask(mask, b0)...);
         });
         if (!fits) return -1;
         if (hipGetLastError() != hipSuccess) return -3;
@@ -389,6 +430,8 @@ int maxsim_search_prepare_device()
 {
     hipError_t e = allow_lds_all<SEARCH_F16>();
     if (e == hipSuccess) e = allow_lds_all<SEARCH_I8>();
+    if (e == hipSuccess) e = allow_lds_all<SEARCH_F16, SearchMask>();
+    if (e == hipSuccess) e = allow_lds_all<SEARCH_I8, SearchMask>();
     return e == hipSuccess ? 0 : -1;
 }
 
@@ -401,12 +444,20 @@ size_t maxsim_search_scratch_bytes()
 
 int launch_maxsim_search(const void *store, const float *scales, int storage, const void *d_table, int n_docs,
                          int64_t used_groups, int w, const float *d_q, int B, int Lq, int k, void *scratch,
-                         float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg, int *ran_wg)
+                         float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg, int *ran_wg, const SearchMask *mask)
 {
     if (B < 1 || Lq < 1 || Lq > 64 || k < 1 || k > 128 || n_docs < 0 || used_groups < 0 || used_groups > 0x7ffffff0ll ||
         w % 64 || w < 64 || w > 1024 || !scratch)
         return -1;
     if ((storage != SEARCH_F16 && storage != SEARCH_I8) || (storage == SEARCH_I8 && !scales)) return -1;
+    if (mask) {
+        if (!mask->tomb) return -1;
+        if (storage == SEARCH_I8)
+            return launch_all<SEARCH_I8>(store, scales, d_table, n_docs, (int)used_groups, w, d_q, B, Lq, k, scratch,
+                                         d_scores, d_ids, s, max_wg, ran_wg, *mask);
+        return launch_all<SEARCH_F16>(store, nullptr, d_table, n_docs, (int)used_groups, w, d_q, B, Lq, k, scratch, d_scores,
+                                      d_ids, s, max_wg, ran_wg, *mask);
+    }
     if (storage == SEARCH_I8)
         return launch_all<SEARCH_I8>(store, scales, d_table, n_docs, (int)used_groups, w, d_q, B, Lq, k, scratch, d_scores,
                                      d_ids, s, max_wg, ran_wg);

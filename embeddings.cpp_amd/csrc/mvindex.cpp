@@ -47,6 +47,14 @@ struct bertx_mvindex {
     // test hook (bertx_test_mvindex_grid): a positive grid_cap bounds the workgroups of every scan
     // launched for this store; last_grid: the scan kernel's workgroups at the latest such launch
     int grid_cap = 0, last_grid = 0;
+    // the tombstones (index_mask.hip): bit d % 32 of word d / 32 is 1 once document d was
+    // removed; `removed`: some remove was accepted since creation or the last clear, so the
+    // scans and the scorers take their masked instantiations.  last_masked (test hook
+    // bertx_test_mvindex_last_masked): the latest scan or scorer launch was a masked one
+    uint32_t *tomb = nullptr;
+    int64_t tomb_words = 0;
+    bool removed = false;
+    int last_masked = 0;
     void *search_scratch = nullptr;        // the partial lists of the full-scan search (maxsim_search_scratch_bytes)
     // centroid codes (set_centroids; all null / 0 before): the C centroids packed as one
     // document of their own buffer, their f32 (int8), one code per token slot, the table of
@@ -85,7 +93,7 @@ struct bertx_mvindex {
                         (void *)st_ids, (void *)st_tok, search_scratch, cent, (void *)cent_u, (void *)codes,
                         (void *)tscratch, (void *)cand_approx, (void *)cand_exact, (void *)cand_ids, (void *)cent_entry,
                         (void *)res_bits, (void *)res_u, (void *)res_cuts, (void *)res_wts, (void *)res_pair, stage_img,
-                        (void *)stage_tab})
+                        (void *)stage_tab, (void *)tomb})
             if (p) (void)hipFree(p);
         if (h_table) (void)hipHostFree(h_table);
         if (h_src) (void)hipHostFree(h_src);
@@ -270,18 +278,36 @@ int32_t add_device_locked(bertx_mvindex &mv, const float *d_rows, const int32_t 
 
 // The scorer of the store's kind; the caller orders the stream.  (On a residual store without
 // documents every id is out of range, and neither codes nor centroids are read.)
+// Once a document was removed the masked scorers run, with the store's tombstones: a deleted
+// id scores as one outside [0, docs).
 int32_t score_launch(bertx_mvindex &mv, const float *d_q, int32_t Lq, const int32_t *d_ids, int32_t n, float *d_out,
                      hipStream_t s)
 {
+    const uint32_t *tomb = mv.removed ? mv.tomb : nullptr;
+    mv.last_masked = tomb != nullptr;
     if (mv.storage == BERTX_INDEX_I8)
         return launch_maxsim_i8(mv.store, mv.scales, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s,
-                                mv.grid_cap, &mv.last_grid);
+                                mv.grid_cap, &mv.last_grid, tomb);
     if (const int nb = res_nbits(mv))
         return launch_maxsim_res(mv.res_bits, mv.res_u, mv.codes, mv.cent, mv.res_pair, nb, mv.table, (int)mv.n_docs, mv.w,
-                                 d_q, Lq, d_ids, n, d_out, s, mv.grid_cap, &mv.last_grid);
+                                 d_q, Lq, d_ids, n, d_out, s, mv.grid_cap, &mv.last_grid, tomb);
     return launch_maxsim(mv.store, mv.table, (int)mv.n_docs, mv.w, d_q, Lq, d_ids, n, d_out, s, mv.grid_cap,
-                         &mv.last_grid);
+                         &mv.last_grid, tomb);
 }
+
+// The mask of a scan (mv locked): none while nothing was removed and no filter is given, which
+// launches the unmasked kernels with the arguments they always had; else the store's
+// tombstones with the call's filters (not read on an empty store).
+struct ScanMask {
+    SearchMask m;
+    bool on;
+    ScanMask(bertx_mvindex &mv, const Filters &f)
+        : m{mv.tomb, mv.n_docs > 0 ? f.d : nullptr, f.stride}, on(mv.removed || f.d)
+    {
+        mv.last_masked = on;
+    }
+    const SearchMask *get() const { return on ? &m : nullptr; }
+};
 
 int32_t score_device_locked(bertx_mvindex &mv, const float *d_q, int32_t Lq, const int32_t *d_ids, int32_t n,
                             float *d_out, hipStream_t s)
@@ -299,13 +325,23 @@ bool search_args_ok(const char *who, int32_t B, int32_t Lq, int32_t k)
 }
 
 int32_t search_device_locked(bertx_mvindex &mv, const float *d_q, int32_t B, int32_t Lq, int32_t k, float *d_scores,
-                             int32_t *d_ids, hipStream_t s)
+                             int32_t *d_ids, hipStream_t s, const Filters &f = Filters())
 {
     if (!d_q || !d_scores || !d_ids || !search_args_ok("bertx_mvindex_search", B, Lq, k)) return -1;
     if (full_scan_refused(mv, "bertx_mvindex_search")) return -1;
     Ordered o(mv.ord, s);
+    const ScanMask mask(mv, f);
     return launch_maxsim_search(mv.store, mv.scales, mv.storage, mv.table, (int)mv.n_docs, mv.used_slots / 16, mv.w, d_q, B,
-                                Lq, k, mv.search_scratch, d_scores, d_ids, s, mv.grid_cap, &mv.last_grid);
+                                Lq, k, mv.search_scratch, d_scores, d_ids, s, mv.grid_cap, &mv.last_grid, mask.get());
+}
+
+int32_t remove_device_locked(bertx_mvindex &mv, const int32_t *d_ids, int32_t n, hipStream_t s)
+{
+    if (!d_ids || n < 1) return -1;
+    Ordered o(mv.ord, s);
+    const int rc = launch_index_remove(d_ids, n, mv.n_docs, mv.tomb, s);
+    if (rc == 0) mv.removed = true;
+    return rc;
 }
 
 // The query already on the device (mv.st_q or a caller's buffer on the store's stream):
@@ -484,16 +520,18 @@ bool pruned_args_ok(const bertx_mvindex &mv, const char *who, int32_t B, int32_t
 // The candidate lists of B queries, floor(4 / ceil(Lq / 16)) per pass; the caller orders the
 // stream.
 int32_t candidates_launch(bertx_mvindex &mv, const float *d_q, int32_t B, int32_t Lq, int32_t n_cand, float *d_approx,
-                          int32_t *d_ids, hipStream_t s)
+                          int32_t *d_ids, hipStream_t s, const Filters &f)
 {
     const int32_t per_pass = 4 / ((Lq + 15) / 16);
+    const ScanMask mask(mv, f);
     for (int32_t b0 = 0; b0 < B; b0 += per_pass) {
         int form = 0;
+        const SearchMask pm = pass_mask(mask.m, b0);
         const int32_t rc = launch_maxsim_candidates(mv.codes, mv.table, (int)mv.n_docs, mv.used_slots / 16, cent_kind(mv), mv.w,
                                                     mv.cent, mv.cent_u, mv.C, d_q + (size_t)b0 * Lq * mv.w,
                                                     std::min(per_pass, B - b0), Lq, n_cand, mv.tscratch, mv.search_scratch,
                                                     d_approx + (size_t)b0 * n_cand, d_ids + (size_t)b0 * n_cand, 3, &form, s,
-                                                    mv.grid_cap, &mv.last_grid);
+                                                    mv.grid_cap, &mv.last_grid, mask.on ? &pm : nullptr);
         if (rc != 0) return rc;
         g_approx_forms.fetch_or(form);
     }
@@ -501,24 +539,26 @@ int32_t candidates_launch(bertx_mvindex &mv, const float *d_q, int32_t B, int32_
 }
 
 int32_t candidates_device_locked(bertx_mvindex &mv, const float *d_q, int32_t B, int32_t Lq, int32_t n_cand,
-                                 float *d_approx, int32_t *d_ids, hipStream_t s)
+                                 float *d_approx, int32_t *d_ids, hipStream_t s, const Filters &f = Filters())
 {
     if (!d_q || !d_approx || !d_ids || !pruned_args_ok(mv, "bertx_mvindex_candidates", B, Lq, 1, n_cand)) return -1;
     Ordered o(mv.ord, s);
-    return candidates_launch(mv, d_q, B, Lq, n_cand, d_approx, d_ids, s);
+    return candidates_launch(mv, d_q, B, Lq, n_cand, d_approx, d_ids, s, f);
 }
 
-// kCandQueries queries at a time through the store's candidate scratch: their candidates,
-// the scorer over each query's candidate ids (a fill id -1 scores -inf), the k best.
+// kCandQueries queries at a time through the store's candidate scratch: their candidates
+// (admissible documents only: the tombstones and the filters limit them), the scorer over each
+// query's candidate ids (a fill id -1 scores -inf; the rerank takes the store's tombstones and
+// no filter, which no candidate could fail), the k best.
 int32_t search_pruned_device_locked(bertx_mvindex &mv, const float *d_q, int32_t B, int32_t Lq, int32_t k, int32_t n_cand,
-                                    float *d_scores, int32_t *d_ids, hipStream_t s)
+                                    float *d_scores, int32_t *d_ids, hipStream_t s, const Filters &f = Filters())
 {
     if (!d_q || !d_scores || !d_ids || !pruned_args_ok(mv, "bertx_mvindex_search_pruned", B, Lq, k, n_cand)) return -1;
     Ordered o(mv.ord, s);
     for (int32_t c0 = 0; c0 < B; c0 += kCandQueries) {
         const int32_t m = std::min(kCandQueries, B - c0);
         const float *Q = d_q + (size_t)c0 * Lq * mv.w;
-        int32_t rc = candidates_launch(mv, Q, m, Lq, n_cand, mv.cand_approx, mv.cand_ids, s);
+        int32_t rc = candidates_launch(mv, Q, m, Lq, n_cand, mv.cand_approx, mv.cand_ids, s, f.from(c0));
         for (int32_t b = 0; b < m && rc == 0; ++b) {
             const float *qb = Q + (size_t)b * Lq * mv.w;
             const int32_t *ib = mv.cand_ids + (size_t)b * n_cand;
@@ -948,6 +988,7 @@ bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t c
     const size_t slots16 = (size_t)((cap_slots + 15) / 16) * 16;
     const bool i8 = storage == BERTX_INDEX_I8;
     const int nb = res_nbits(*mv);
+    mv->tomb_words = index_mask_words(cap_docs);
     // a residual store keeps no rows: w nb / 8 bytes of bits and one f32 per slot, and the codec
     const size_t store_bytes = nb ? slots16 * (size_t)w * nb / 8 + slots16 * 4 : slots16 * (size_t)w * (i8 ? 1 : 2);
     const bool ok = maxsim_prepare_device() == 0 && maxsim_search_prepare_device() == 0 &&
@@ -971,7 +1012,10 @@ bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t c
                     hipMalloc((void **)&mv->st_q, (size_t)kMaxLq * w * 4) == hipSuccess &&
                     hipMalloc((void **)&mv->st_out, (size_t)kStageIds * 4) == hipSuccess &&
                     hipMalloc((void **)&mv->st_ids, (size_t)kStageIds * 4) == hipSuccess &&
-                    hipMalloc((void **)&mv->st_tok, (size_t)(kMaxLq + 3) * 4) == hipSuccess;
+                    hipMalloc((void **)&mv->st_tok, (size_t)(kMaxLq + 3) * 4) == hipSuccess &&
+                    hipMalloc((void **)&mv->tomb, (size_t)mv->tomb_words * 4) == hipSuccess &&
+                    hipMemsetAsync(mv->tomb, 0, (size_t)mv->tomb_words * 4, mv->stream) == hipSuccess &&
+                    hipStreamSynchronize(mv->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         errorf("bertx_mvindex_create: device %d could not allocate %zu bytes of token rows (+ %lld table entries)\n",
@@ -1027,6 +1071,12 @@ int32_t bertx_mvindex_clear(struct bertx_mvindex *mv)
     // the host images' entries are about to be reused: no copy of them may be in flight
     // (the embedding index keeps no such images and does not wait)
     HIP_RC(mv->ord.wait());
+    if (mv->removed) {
+        // the tombstones back to zero, ordered behind every operation so far
+        emb::Ordered o(mv->ord, mv->stream);
+        HIP_RC(hipMemsetAsync(mv->tomb, 0, (size_t)mv->tomb_words * 4, mv->stream));
+        mv->removed = false;
+    }
     mv->n_docs = 0;
     mv->used_slots = 0;
     return 0;
@@ -1241,40 +1291,123 @@ int32_t bertx_mvindex_score_text_colbert(struct bertx_mvindex *mv, struct bert_c
     }
 }
 
-int32_t bertx_mvindex_search_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq, int32_t k,
-                                    float *d_scores, int32_t *d_ids, void *stream)
+int32_t bertx_mvindex_search_filtered_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq, int32_t k,
+                                             const uint32_t *d_filters, int32_t n_filters, int32_t words, float *d_scores,
+                                             int32_t *d_ids, void *stream)
 {
     if (!mv) return -1;
     std::lock_guard<std::mutex> lk(mv->mu);
+    if (!emb::filters_fit(mv->n_docs, d_filters, n_filters, words, B)) return -1;
     DeviceGuard g(mv->ordinal);
     HIP_RC(g.status());
-    return emb::search_device_locked(*mv, d_q, B, Lq, k, d_scores, d_ids, stream ? (hipStream_t)stream : mv->stream);
+    return emb::search_device_locked(*mv, d_q, B, Lq, k, d_scores, d_ids, stream ? (hipStream_t)stream : mv->stream,
+                                     emb::filters_of(d_filters, n_filters, words));
+}
+
+int32_t bertx_mvindex_search_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq, int32_t k,
+                                    float *d_scores, int32_t *d_ids, void *stream)
+{
+    return bertx_mvindex_search_filtered_device(mv, d_q, B, Lq, k, nullptr, 0, 0, d_scores, d_ids, stream);
+}
+
+int32_t bertx_mvindex_search_filtered(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t k,
+                                      const uint32_t *filters, int32_t n_filters, int32_t words, float *scores, int32_t *ids)
+{
+    if (!mv || !q || !scores || !ids || !emb::search_args_ok("bertx_mvindex_search", B, Lq, k)) return -1;
+    if (emb::full_scan_refused(*mv, "bertx_mvindex_search")) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    if (!emb::filters_fit(mv->n_docs, filters, n_filters, words, B)) return -1;
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    emb::DevBuf fbuf;   // (freed after the call's synchronise)
+    try {
+        HIP_RC(emb::stage_filters(mv->stream, filters, n_filters, words, fbuf));
+        const emb::Filters f = emb::filters_of((const uint32_t *)fbuf.p, n_filters, words);
+        return emb::queries_to_host(*mv, q, B, Lq, k, [&](const float *dq, float *ds, int32_t *di) {
+            return emb::search_device_locked(*mv, dq, B, Lq, k, ds, di, mv->stream, f);
+        }, scores, ids);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_mvindex_search: out of host memory\n");
+        return -1;
+    }
 }
 
 int32_t bertx_mvindex_search(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t k, float *scores,
                              int32_t *ids)
 {
-    if (!mv || !q || !scores || !ids || !emb::search_args_ok("bertx_mvindex_search", B, Lq, k)) return -1;
-    if (emb::full_scan_refused(*mv, "bertx_mvindex_search")) return -1;
+    return bertx_mvindex_search_filtered(mv, q, B, Lq, k, nullptr, 0, 0, scores, ids);
+}
+
+int32_t bertx_mvindex_remove_device(struct bertx_mvindex *mv, const int32_t *d_ids, int32_t n, void *stream)
+{
+    if (!mv) return -1;
     std::lock_guard<std::mutex> lk(mv->mu);
     DeviceGuard g(mv->ordinal);
     HIP_RC(g.status());
-    try {
-        const size_t nq = (size_t)B * Lq * mv->w, nr = (size_t)B * k;
-        std::vector<float> hs(nr);
-        std::vector<int32_t> hi(nr);
-        emb::DevBuf d_q;
-        HIP_RC(hipMalloc(&d_q.p, nq * 4));
-        HIP_RC(hipMemcpyAsync(d_q.p, q, nq * 4, hipMemcpyHostToDevice, mv->stream));
-        const int32_t rc = emb::search_to_host(*mv, (const float *)d_q.p, B, Lq, k, hs.data(), hi.data());
+    return emb::remove_device_locked(*mv, d_ids, n, stream ? (hipStream_t)stream : mv->stream);
+}
+
+int32_t bertx_mvindex_remove(struct bertx_mvindex *mv, const int32_t *ids, int32_t n)
+{
+    if (!mv || !ids || n < 1) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    for (int32_t i = 0; i < n; i += emb::kStageIds) {
+        const int32_t m = std::min(emb::kStageIds, n - i);
+        HIP_RC(hipMemcpyAsync(mv->st_ids, ids + i, (size_t)m * 4, hipMemcpyHostToDevice, mv->stream));
+        const int32_t rc = emb::remove_device_locked(*mv, mv->st_ids, m, mv->stream);
         if (rc != 0) return rc;
-        std::memcpy(scores, hs.data(), nr * 4);
-        std::memcpy(ids, hi.data(), nr * 4);
-        return 0;
+        HIP_RC(hipStreamSynchronize(mv->stream));   // the staging buffer is reused
+    }
+    return 0;
+}
+
+int32_t bertx_mvindex_live(struct bertx_mvindex *mv)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    int32_t dead = 0;
+    {
+        emb::Ordered o(mv->ord, mv->stream);
+        const int rc = emb::launch_index_count_deleted(mv->tomb, mv->n_docs, mv->st_ids, mv->stream);
+        if (rc != 0) return rc;
+        HIP_RC(hipMemcpyAsync(&dead, mv->st_ids, 4, hipMemcpyDeviceToHost, mv->stream));
+    }
+    HIP_RC(hipStreamSynchronize(mv->stream));
+    return (int32_t)mv->n_docs - dead;
+}
+
+int32_t bertx_mvindex_deleted(struct bertx_mvindex *mv, int32_t first, int32_t n, uint8_t *out)
+{
+    if (!mv || !out || first < 0 || n < 1) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    if ((int64_t)first + n > mv->n_docs) return -1;
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    try {
+        // the caller's output is written only once every chunk has succeeded
+        std::vector<uint8_t> flags((size_t)n);
+        constexpr int32_t kChunk = emb::kStageIds * 4;   // bytes of the id staging buffer, one flag each
+        for (int32_t i = 0; i < n; i += kChunk) {
+            const int32_t m = std::min(kChunk, n - i);
+            {
+                emb::Ordered o(mv->ord, mv->stream);
+                const int rc = emb::launch_index_deleted_flags(mv->tomb, (int64_t)first + i, m, (uint8_t *)mv->st_ids,
+                                                               mv->stream);
+                if (rc != 0) return rc;
+                HIP_RC(hipMemcpyAsync(flags.data() + i, mv->st_ids, (size_t)m, hipMemcpyDeviceToHost, mv->stream));
+            }
+            HIP_RC(hipStreamSynchronize(mv->stream));
+        }
+        std::memcpy(out, flags.data(), flags.size());
     } catch (const std::bad_alloc &) {
-        emb::errorf("bertx_mvindex_search: out of host memory\n");
+        emb::errorf("bertx_mvindex_deleted: out of host memory\n");
         return -1;
     }
+    return 0;
 }
 
 int32_t bertx_mvindex_search_texts(struct bertx_mvindex *mv, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
@@ -1607,27 +1740,48 @@ int32_t bertx_test_mvindex_last_grid(struct bertx_mvindex *mv)
     return mv->last_grid;
 }
 
-int32_t bertx_mvindex_candidates_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq, int32_t n_cand,
-                                        float *d_approx, int32_t *d_ids, void *stream)
+int32_t bertx_test_mvindex_last_masked(struct bertx_mvindex *mv)
 {
     if (!mv) return -1;
     std::lock_guard<std::mutex> lk(mv->mu);
-    DeviceGuard g(mv->ordinal);
-    HIP_RC(g.status());
-    return emb::candidates_device_locked(*mv, d_q, B, Lq, n_cand, d_approx, d_ids, stream ? (hipStream_t)stream : mv->stream);
+    return mv->last_masked;
 }
 
-int32_t bertx_mvindex_candidates(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t n_cand,
-                                 float *approx, int32_t *ids)
+int32_t bertx_mvindex_candidates_filtered_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq,
+                                                 int32_t n_cand, const uint32_t *d_filters, int32_t n_filters, int32_t words,
+                                                 float *d_approx, int32_t *d_ids, void *stream)
+{
+    if (!mv) return -1;
+    std::lock_guard<std::mutex> lk(mv->mu);
+    if (!emb::filters_fit(mv->n_docs, d_filters, n_filters, words, B)) return -1;
+    DeviceGuard g(mv->ordinal);
+    HIP_RC(g.status());
+    return emb::candidates_device_locked(*mv, d_q, B, Lq, n_cand, d_approx, d_ids, stream ? (hipStream_t)stream : mv->stream,
+                                         emb::filters_of(d_filters, n_filters, words));
+}
+
+int32_t bertx_mvindex_candidates_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq, int32_t n_cand,
+                                        float *d_approx, int32_t *d_ids, void *stream)
+{
+    return bertx_mvindex_candidates_filtered_device(mv, d_q, B, Lq, n_cand, nullptr, 0, 0, d_approx, d_ids, stream);
+}
+
+int32_t bertx_mvindex_candidates_filtered(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t n_cand,
+                                          const uint32_t *filters, int32_t n_filters, int32_t words, float *approx,
+                                          int32_t *ids)
 {
     if (!mv || !q || !approx || !ids) return -1;
     std::lock_guard<std::mutex> lk(mv->mu);
     if (!emb::pruned_args_ok(*mv, "bertx_mvindex_candidates", B, Lq, 1, n_cand)) return -1;
+    if (!emb::filters_fit(mv->n_docs, filters, n_filters, words, B)) return -1;
     DeviceGuard g(mv->ordinal);
     HIP_RC(g.status());
+    emb::DevBuf fbuf;   // (freed after the call's synchronise)
     try {
+        HIP_RC(emb::stage_filters(mv->stream, filters, n_filters, words, fbuf));
+        const emb::Filters f = emb::filters_of((const uint32_t *)fbuf.p, n_filters, words);
         return emb::queries_to_host(*mv, q, B, Lq, n_cand, [&](const float *dq, float *ds, int32_t *di) {
-            return emb::candidates_device_locked(*mv, dq, B, Lq, n_cand, ds, di, mv->stream);
+            return emb::candidates_device_locked(*mv, dq, B, Lq, n_cand, ds, di, mv->stream, f);
         }, approx, ids);
     } catch (const std::bad_alloc &) {
         emb::errorf("bertx_mvindex_candidates: out of host memory\n");
@@ -1635,33 +1789,59 @@ int32_t bertx_mvindex_candidates(struct bertx_mvindex *mv, const float *q, int32
     }
 }
 
-int32_t bertx_mvindex_search_pruned_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq, int32_t k,
-                                           int32_t n_cand, float *d_scores, int32_t *d_ids, void *stream)
+int32_t bertx_mvindex_candidates(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t n_cand,
+                                 float *approx, int32_t *ids)
+{
+    return bertx_mvindex_candidates_filtered(mv, q, B, Lq, n_cand, nullptr, 0, 0, approx, ids);
+}
+
+int32_t bertx_mvindex_search_pruned_filtered_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq,
+                                                    int32_t k, int32_t n_cand, const uint32_t *d_filters, int32_t n_filters,
+                                                    int32_t words, float *d_scores, int32_t *d_ids, void *stream)
 {
     if (!mv) return -1;
     std::lock_guard<std::mutex> lk(mv->mu);
+    if (!emb::filters_fit(mv->n_docs, d_filters, n_filters, words, B)) return -1;
     DeviceGuard g(mv->ordinal);
     HIP_RC(g.status());
     return emb::search_pruned_device_locked(*mv, d_q, B, Lq, k, n_cand, d_scores, d_ids,
-                                            stream ? (hipStream_t)stream : mv->stream);
+                                            stream ? (hipStream_t)stream : mv->stream,
+                                            emb::filters_of(d_filters, n_filters, words));
 }
 
-int32_t bertx_mvindex_search_pruned(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t k,
-                                    int32_t n_cand, float *scores, int32_t *ids)
+int32_t bertx_mvindex_search_pruned_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq, int32_t k,
+                                           int32_t n_cand, float *d_scores, int32_t *d_ids, void *stream)
+{
+    return bertx_mvindex_search_pruned_filtered_device(mv, d_q, B, Lq, k, n_cand, nullptr, 0, 0, d_scores, d_ids, stream);
+}
+
+int32_t bertx_mvindex_search_pruned_filtered(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t k,
+                                             int32_t n_cand, const uint32_t *filters, int32_t n_filters, int32_t words,
+                                             float *scores, int32_t *ids)
 {
     if (!mv || !q || !scores || !ids) return -1;
     std::lock_guard<std::mutex> lk(mv->mu);
     if (!emb::pruned_args_ok(*mv, "bertx_mvindex_search_pruned", B, Lq, k, n_cand)) return -1;
+    if (!emb::filters_fit(mv->n_docs, filters, n_filters, words, B)) return -1;
     DeviceGuard g(mv->ordinal);
     HIP_RC(g.status());
+    emb::DevBuf fbuf;   // (freed after the call's synchronise)
     try {
+        HIP_RC(emb::stage_filters(mv->stream, filters, n_filters, words, fbuf));
+        const emb::Filters f = emb::filters_of((const uint32_t *)fbuf.p, n_filters, words);
         return emb::queries_to_host(*mv, q, B, Lq, k, [&](const float *dq, float *ds, int32_t *di) {
-            return emb::search_pruned_device_locked(*mv, dq, B, Lq, k, n_cand, ds, di, mv->stream);
+            return emb::search_pruned_device_locked(*mv, dq, B, Lq, k, n_cand, ds, di, mv->stream, f);
         }, scores, ids);
     } catch (const std::bad_alloc &) {
         emb::errorf("bertx_mvindex_search_pruned: out of host memory\n");
         return -1;
     }
+}
+
+int32_t bertx_mvindex_search_pruned(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t k,
+                                    int32_t n_cand, float *scores, int32_t *ids)
+{
+    return bertx_mvindex_search_pruned_filtered(mv, q, B, Lq, k, n_cand, nullptr, 0, 0, scores, ids);
 }
 
 int32_t bertx_mvindex_search_pruned_texts(struct bertx_mvindex *mv, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
@@ -1821,11 +2001,12 @@ struct MaxsimBench {
 // B == 0: the scorer over n_cand candidates; B >= 1: the full-scan search of B queries for
 // the k best.  C > 0 (with B >= 1): C hash-chosen stored rows become the centroids and
 // avg_us[3] gets the table kernels, the scans with their selections, and the whole pruned
-// search of n_cand candidates.
+// search of n_cand candidates.  pattern (with B >= 1): the mask of bertx_bench_maxsim_masked.
 int32_t bench_store(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t B, int32_t k,
-                    int32_t storage, int32_t iters, float *avg_us, int32_t C = 0)
+                    int32_t storage, int32_t iters, float *avg_us, int32_t C = 0, int32_t pattern = 0)
 {
     using namespace emb;
+    if (pattern < 0 || pattern > 5 || (pattern && B < 1)) return -1;
     if (n_docs < 1 || doc_len < 0 || doc_len > 4096 || n_cand < 1 || iters < 1 || !avg_us || hip_device_count() == 0)
         return -1;
     if (B > 0 && !search_args_ok("bertx_bench_maxsim_search", B, Lq, k)) return -1;
@@ -1840,29 +2021,56 @@ int32_t bench_store(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int3
         const float *Q = (const float *)F.q.p;
         float *out = (float *)F.out.p;
         int32_t *oid = (int32_t *)F.oid.p;
+        // the mask: nf filters of `words` words on the device, or a hashed sixteenth removed
+        const int32_t words = (n_docs + 31) / 32, nf = pattern == 2 ? B : pattern >= 1 && pattern <= 4 ? 1 : 0;
+        auto sixteenth = [](int32_t i) {
+            uint32_t h = (uint32_t)i * 2654435761u + 4242u;
+            h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
+            return (h & 15u) == 0;
+        };
+        DevBuf filt;
+        if (nf) {
+            std::vector<uint32_t> fw((size_t)nf * words, pattern <= 2 ? ~0u : 0u);
+            for (int32_t i = 0; i < n_docs; ++i)
+                if ((pattern == 3 && sixteenth(i)) || (pattern == 4 && i < n_docs / 16)) fw[(size_t)(i >> 5)] |= 1u << (i & 31);
+            HIP_RC(hipMalloc(&filt.p, fw.size() * 4));
+            HIP_RC(hipMemcpy(filt.p, fw.data(), fw.size() * 4, hipMemcpyHostToDevice));
+        }
+        if (pattern == 5) {
+            std::vector<int32_t> gone;
+            for (int32_t i = 0; i < n_docs; ++i)
+                if (sixteenth(i)) gone.push_back(i);
+            if (!gone.empty() && bertx_mvindex_remove(F.mv, gone.data(), (int32_t)gone.size()) != 0) return -1;
+        }
+        const uint32_t *df = (const uint32_t *)filt.p;
         if (C > 0) {
             std::vector<float> cent;
             if (F.pick_centroids(F.mv, C, cent) != 0 || bertx_mvindex_set_centroids(F.mv, cent.data(), C) != 0) return -1;
             HIP_RC(F.mv->ord.wait());
             bertx_mvindex &mv = *F.mv;
             const int32_t per_pass = 4 / ((Lq + 15) / 16);
+            const SearchMask sm{mv.tomb, df, nf > 1 ? words : 0};
             auto stage = [&](int st) -> int32_t {
                 for (int32_t b0 = 0; b0 < B; b0 += per_pass) {
+                    const SearchMask pm = pass_mask(sm, b0);
                     const int32_t rc = launch_maxsim_candidates(
                         mv.codes, mv.table, (int)mv.n_docs, mv.used_slots / 16, mv.storage, mv.w, mv.cent, mv.cent_u, mv.C,
                         Q + (size_t)b0 * Lq * w, std::min(per_pass, B - b0), Lq, n_cand, mv.tscratch, mv.search_scratch,
-                        out + (size_t)b0 * n_cand, oid + (size_t)b0 * n_cand, st, nullptr, F.s);
+                        out + (size_t)b0 * n_cand, oid + (size_t)b0 * n_cand, st, nullptr, F.s, 0, nullptr,
+                        pattern ? &pm : nullptr);
                     if (rc != 0) return rc;
                 }
                 return 0;
             };
             if (F.timed([&] { return stage(1); }, avg_us) != 0) return -1;
             if (F.timed([&] { return stage(2); }, avg_us + 1) != 0) return -1;
-            return F.timed([&] { return bertx_mvindex_search_pruned_device(F.mv, Q, B, Lq, k, n_cand, out, oid, F.s); },
-                           avg_us + 2);
+            return F.timed([&] {
+                return bertx_mvindex_search_pruned_filtered_device(F.mv, Q, B, Lq, k, n_cand, df, nf, nf ? words : 0, out, oid,
+                                                                   F.s);
+            }, avg_us + 2);
         }
         return F.timed([&] {
-            if (B > 0) return bertx_mvindex_search_device(F.mv, Q, B, Lq, k, out, oid, F.s);
+            if (B > 0) return bertx_mvindex_search_filtered_device(F.mv, Q, B, Lq, k, df, nf, nf ? words : 0, out, oid, F.s);
             return bertx_mvindex_score_device(F.mv, Q, Lq, (const int32_t *)F.id.p, n_cand, out, F.s);
         }, avg_us);
     } catch (const std::exception &ex) {
@@ -1941,6 +2149,13 @@ int32_t bertx_bench_maxsim_pruned(int32_t w, int32_t n_docs, int32_t doc_len, in
 {
     if (B < 1 || C < 1) return -1;
     return bench_store(w, n_docs, doc_len, Lq, n_cand, B, k, storage, iters, avg_us, C);
+}
+
+int32_t bertx_bench_maxsim_masked(int32_t w, int32_t n_docs, int32_t doc_len, int32_t C, int32_t Lq, int32_t B, int32_t k,
+                                  int32_t n_cand, int32_t storage, int32_t pattern, int32_t iters, float *avg_us)
+{
+    if (B < 1 || C < 0) return -1;
+    return bench_store(w, n_docs, doc_len, Lq, C > 0 ? n_cand : 1, B, k, storage, iters, avg_us, C, pattern);
 }
 
 int32_t bertx_bench_maxsim(int32_t w, int32_t n_docs, int32_t doc_len, int32_t Lq, int32_t n_cand, int32_t iters,

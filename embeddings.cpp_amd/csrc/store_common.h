@@ -52,6 +52,47 @@ struct DevBuf {
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
+// The filters of one search (device memory): none (d null, n 0), one for every query
+// (stride 0) or one per query, `stride` words apart.  A mask packs 32 units (rows of the
+// embedding index, documents of the token store) to a uint32_t word.
+struct Filters {
+    const uint32_t *d = nullptr;
+    int64_t stride = 0;
+    Filters from(int64_t query) const
+    {
+        Filters f = *this;
+        if (f.d) f.d += (size_t)query * (size_t)stride;
+        return f;
+    }
+};
+
+// What a filtered search accepts over a store of n units (the store locked): no filter as
+// (NULL, 0), else 1 or B filters of at least ceil(n / 32) words.
+inline bool filters_fit(int64_t n, const void *filters, int32_t n_filters, int32_t words, int32_t B)
+{
+    if (!filters || n_filters == 0) return !filters && n_filters == 0;
+    return (n_filters == 1 || n_filters == B) && (int64_t)words >= (n + 31) / 32;
+}
+
+inline Filters filters_of(const uint32_t *d_filters, int32_t n_filters, int32_t words)
+{
+    Filters f;
+    f.d = d_filters;
+    f.stride = n_filters > 1 ? words : 0;
+    return f;
+}
+
+// The filters of a host call, uint32 [n_filters][words], staged in a device buffer of the
+// call's own (the store locked, its device current); the copy is ordered on the store's stream.
+inline hipError_t stage_filters(hipStream_t stream, const uint32_t *filters, int32_t n_filters, int32_t words, DevBuf &buf)
+{
+    if (!filters) return hipSuccess;
+    const size_t bytes = (size_t)n_filters * (size_t)words * 4;
+    hipError_t e = hipMalloc(&buf.p, bytes > 4 ? bytes : 4);
+    if (e == hipSuccess && bytes) e = hipMemcpyAsync(buf.p, filters, bytes, hipMemcpyHostToDevice, stream);
+    return e;
+}
+
 // The unpackers.  image: a host copy of whole 16-row groups of width w, of which the
 // first holds row image_first (a multiple of 16); rows first .. first + n - 1 of it go to
 // out [n][w].  An int8 store's scales stay with the caller (the two stores index them

@@ -11,6 +11,11 @@
 // (bertx_index_remove; with -R from both indexes) and prints `deleted N`, N being the change
 // of bertx_index_live; later queries no longer return them.  With -a there is no embedding
 // index: the line is answered with a message and ignored.
+// A stdin line `:drop ID [ID ...]` removes those documents from the token store (-l or -L,
+// with or without -a; bertx_mvindex_remove) and prints `dropped N`, N being the change of
+// bertx_mvindex_live: the full scan and the pruned search no longer return them, and as
+// second-stage candidates they score -inf and are not printed.  Without a token store the
+// line is answered with `no token store: nothing dropped` and ignored.
 // -s: how the index stores its rows (bertx_index_create_ex): f16, the default, or int8
 // with one scale per row, half the bytes and a less precise first stage, or binary: a row
 // as its sign bits, one sixteenth of the bytes, searched by Hamming distance; the printed
@@ -59,6 +64,7 @@
 #include "bert_hip.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -280,6 +286,29 @@ int main(int argc, char **argv)
             std::fflush(stdout);
             continue;
         }
+        if (q.compare(0, 5, ":drop") == 0 && (q.size() == 5 || q[5] == ' ' || q[5] == '\t')) {
+            if (!mv) {
+                std::printf("no token store: nothing dropped\n");
+                std::fflush(stdout);
+                continue;
+            }
+            std::vector<int32_t> drop;
+            const char *p = q.c_str() + 5;
+            for (char *end = nullptr;; p = end) {
+                const long v = std::strtol(p, &end, 10);
+                if (end == p) break;
+                drop.push_back(v < 0 || v > 0x7fffffffl ? -1 : (int32_t)v);
+            }
+            const int32_t before = bertx_mvindex_live(mv);
+            if (!drop.empty() && bertx_mvindex_remove(mv, drop.data(), (int32_t)drop.size()) != 0) {
+                std::fprintf(stderr, "search: dropping failed\n");
+                rc = 1;
+                break;
+            }
+            std::printf("dropped %d\n", before - bertx_mvindex_live(mv));
+            std::fflush(stdout);
+            continue;
+        }
         const char *qp = q.c_str();
         if (all) {
             // the full scan: the k best of every stored document by MaxSim, selected on the GPU
@@ -307,7 +336,8 @@ int main(int argc, char **argv)
             break;
         }
         if (mv) {
-            // the candidates re-scored by MaxSim (a -1 fill slot scores -inf and sorts last)
+            // the candidates re-scored by MaxSim (a -1 fill slot scores -inf and sorts last, as
+            // does a document dropped from the token store, which is not printed)
             std::vector<float> ms((size_t)kq);
             if ((colbert ? bertx_mvindex_score_text_colbert(mv, rctx, qp, query_maxlen, ids.data(), kq, ms.data())
                          : bertx_mvindex_score_text(mv, ctx, qp, ids.data(), kq, ms.data())) != 0) {
@@ -322,6 +352,7 @@ int main(int argc, char **argv)
             });
             for (int j = 0; j < k && ids[(size_t)ord[(size_t)j]] >= 0; ++j) {
                 const int c = ord[(size_t)j];
+                if (ms[(size_t)c] == -INFINITY) break;
                 std::printf("%d\t%d\t%.4f\t%s\n", j + 1, ids[(size_t)c], ms[(size_t)c], texts[(size_t)ids[(size_t)c]].c_str());
             }
             std::fflush(stdout);

@@ -528,8 +528,8 @@ BERT_API int32_t bertx_tokenize_batch(struct bert_ctx *ctx, int32_t n_threads, i
  *
  * Not provided: an index sharded over several GPUs, compaction (reclaiming deleted rows'
  * bytes or renumbering), skipping the loads of fully masked groups, a gather path for very
- * selective filters, masks on the token store, saving and loading (the mask layout above is
- * what a file would carry), f32 storage, f16 queries against int8 rows, 4-bit storage,
+ * selective filters, saving and loading (the mask layout above is what a file would carry;
+ * the token store's masks: "Deleting documents and filtered search" below), f32 storage, f16 queries against int8 rows, 4-bit storage,
  * binary rows against unbinarized queries (asymmetric scores), a fine copy kept in host
  * memory.
  */
@@ -889,9 +889,65 @@ BERT_API int32_t bertx_index_search_rescored_filtered_device(struct bertx_index 
  * query for the 10 best of min(n_cand, 128) candidates; each the average of `iters` calls
  * after 3.
  *
+ * Deleting documents and filtered search.  The embedding index's section word for word, a
+ * document in the place of a row.  Two masks over document ids, both packed 32 documents to a
+ * uint32_t word: document i is bit i % 32 of word i / 32 (np.packbits(x, bitorder="little")
+ * viewed as uint32).  Tombstones belong to the store, lie on its device, cover capacity_docs
+ * and are allocated and zeroed at creation; bit 1 = deleted.  Filters are the caller's, per
+ * call; bit 1 = the document may be returned.  A document is admissible for query b iff
+ * id < docs, its tombstone is 0 and, when a filter is given, its bit in query b's filter is 1.
+ * bertx_mvindex_remove / _remove_device (ids int32[n], host / device; n >= 1, anything else a
+ * negative error with nothing changed): sets the tombstones of the listed ids and returns 0.
+ * Ids outside [0, docs), docs being the document count when the call is made, are ignored;
+ * repeated ids are harmless; the bits are set by atomic OR, so no order matters.  The device
+ * form is asynchronous, allocates nothing, never synchronises, can be captured, and is
+ * ordered as bertx_mvindex_add_device is.  Ids are never reused: bertx_mvindex_docs and
+ * _token_slots do not change, and _doc, _doc_len, _doc_i8, _doc_codes and _doc_residual still
+ * return a deleted document's stored values.  bertx_mvindex_clear also zeroes the tombstones
+ * (ordered on the store's stream), so a clear followed by adds starts clean.
+ * bertx_mvindex_live: docs minus the deleted documents in [0, docs); a host call that
+ * synchronises.  bertx_mvindex_deleted: out uint8[n] = 0 or 1 for documents first .. first +
+ * n - 1; -1 on a bad range with the output untouched.
+ * bertx_mvindex_search_filtered / _device(mv, q, B, Lq, k, filters, n_filters, words, scores,
+ * ids[, stream]): bertx_mvindex_search over the admissible documents.  filters
+ * uint32[n_filters][words] (host / device); n_filters is 1 (one filter for every query) or B
+ * (query b uses filter b); words >= ceil(docs / 32) is also the stride between filters; bits
+ * of documents >= docs are ignored, whatever they hold.  filters == NULL with n_filters == 0
+ * is exactly bertx_mvindex_search.  The result is the k best admissible documents with the
+ * scorer's score bits, the same order (score descending, id ascending) and the same (-inf,
+ * -1) fill when fewer than k documents are admissible; a deleted or filtered document never
+ * appears, not even as (-inf, id).  Every refusal (a null pointer, n_filters not 0, 1 or B,
+ * too few words, a filter pointer without a count or the reverse, and the refusals of
+ * _search) returns a negative error with the outputs untouched.  The device form allocates
+ * nothing and can be captured; the host form allocates and frees a staging buffer for the
+ * filters per call.  The filter is read when the kernel runs: a captured search sees the bits
+ * the buffer holds at replay.  A filter is not read while the store is empty.
+ * bertx_mvindex_candidates_filtered / _device and bertx_mvindex_search_pruned_filtered /
+ * _device take the same three filter arguments, for all four storage kinds: the candidates are
+ * the n_cand best admissible documents by (approx, ascending id), and the pruned search is
+ * literally the composition stated under "Pruned search" with that as its first line; the
+ * exact stage takes the store's tombstones.  With n_cand >= the number of admissible documents
+ * it equals _search_filtered, bit for bit.
+ * On a store with deletions the entries above follow: _search, _candidates, _search_pruned,
+ * their device forms and the text forms (_search_texts, _search_texts_colbert,
+ * _search_pruned_texts) return admissible documents only; _score / _score_device /
+ * _score_text (and _score_text_colbert) give -inf for a deleted id, exactly as for an id
+ * outside [0, docs), on the f16, int8 and residual scorers alike.  Training ignores
+ * tombstones: _train_centroids, _train_residual_buckets and _set_centroids keep numbering and
+ * coding every stored token row, deleted documents' rows included, so their contracts above
+ * stay true word for word.
+ * A store from which nothing was removed since creation or the last clear, searched without a
+ * filter, launches the kernels it launched before masks existed, with the same arguments: the
+ * masked kernels are other instantiations, chosen at launch time by a host flag that any
+ * accepted remove sets and clear resets (a graph captured before the first removal keeps
+ * launching the unmasked kernels).
+ *
  * Not provided: int8 queries against f16 rows; the full scan of a residual store, 1-bit
  * codes; candidate lists longer than 128; per-query lengths on the device; sharding over
- * GPUs; deleting, saving and loading.  (ColBERT checkpoints: "Projection" below.)
+ * GPUs; compaction (reclaiming deleted documents' slots or renumbering); skipping the loads of
+ * masked documents; a gather path for very selective filters (bertx_mvindex_score over listed
+ * ids already serves those); filtered text forms in C; saving and loading.  (ColBERT
+ * checkpoints: "Projection" below.)
  */
 enum { BERTX_INDEX_RES2 = 4, BERTX_INDEX_RES4 = 5 };   /* token stores only: "Residual codes" above */
 struct bertx_mvindex;
@@ -959,6 +1015,39 @@ BERT_API int32_t bertx_mvindex_train_residual_buckets(struct bertx_mvindex *src,
 BERT_API int32_t bertx_mvindex_doc_residual(struct bertx_mvindex *mv, int32_t id, uint16_t *codes, uint8_t *bits, float *u);
 BERT_API int32_t bertx_bench_maxsim_res(int32_t w, int32_t n_docs, int32_t doc_len, int32_t C, int32_t Lq, int32_t n_cand,
                                         int32_t storage, int32_t iters, float *avg_us);
+/* "Deleting documents and filtered search" above. */
+BERT_API int32_t bertx_mvindex_remove(struct bertx_mvindex *mv, const int32_t *ids, int32_t n);
+BERT_API int32_t bertx_mvindex_remove_device(struct bertx_mvindex *mv, const int32_t *d_ids, int32_t n, void *stream);
+BERT_API int32_t bertx_mvindex_live(struct bertx_mvindex *mv);
+BERT_API int32_t bertx_mvindex_deleted(struct bertx_mvindex *mv, int32_t first, int32_t n, uint8_t *out);
+BERT_API int32_t bertx_mvindex_search_filtered(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq, int32_t k,
+                                               const uint32_t *filters, int32_t n_filters, int32_t words, float *scores,
+                                               int32_t *ids);
+BERT_API int32_t bertx_mvindex_search_filtered_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq,
+                                                      int32_t k, const uint32_t *d_filters, int32_t n_filters,
+                                                      int32_t words, float *d_scores, int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_mvindex_candidates_filtered(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq,
+                                                   int32_t n_cand, const uint32_t *filters, int32_t n_filters,
+                                                   int32_t words, float *approx, int32_t *ids);
+BERT_API int32_t bertx_mvindex_candidates_filtered_device(struct bertx_mvindex *mv, const float *d_q, int32_t B, int32_t Lq,
+                                                          int32_t n_cand, const uint32_t *d_filters, int32_t n_filters,
+                                                          int32_t words, float *d_approx, int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_mvindex_search_pruned_filtered(struct bertx_mvindex *mv, const float *q, int32_t B, int32_t Lq,
+                                                      int32_t k, int32_t n_cand, const uint32_t *filters, int32_t n_filters,
+                                                      int32_t words, float *scores, int32_t *ids);
+BERT_API int32_t bertx_mvindex_search_pruned_filtered_device(struct bertx_mvindex *mv, const float *d_q, int32_t B,
+                                                             int32_t Lq, int32_t k, int32_t n_cand,
+                                                             const uint32_t *d_filters, int32_t n_filters, int32_t words,
+                                                             float *d_scores, int32_t *d_ids, void *stream);
+/* bertx_bench_maxsim_masked: bertx_bench_maxsim_search (C == 0; avg_us[0]) or
+ * bertx_bench_maxsim_pruned (C > 0; avg_us[0 .. 2]) of the same store under a mask pattern:
+ * 0 none (the unmasked kernels); 1 one all-ones filter for every query; 2 an all-ones filter
+ * per query; 3 a shared filter that admits a hashed 1 / 16 of the documents; 4 a shared
+ * filter that admits the contiguous first 1 / 16; 5 no filter, a hashed 1 / 16 of the
+ * documents removed.  -1 for another pattern. */
+BERT_API int32_t bertx_bench_maxsim_masked(int32_t w, int32_t n_docs, int32_t doc_len, int32_t C, int32_t Lq, int32_t B,
+                                           int32_t k, int32_t n_cand, int32_t storage, int32_t pattern, int32_t iters,
+                                           float *avg_us);
 /* Test hooks: which table placement the candidate scans took; the host half of training
  * (kmeans_update.h): one update in place, returning the centroids without a member; the
  * sample rule, out3 = {stride, start, n_sample}. */
@@ -973,9 +1062,13 @@ BERT_API int32_t bertx_test_approx_ran(int32_t reset);
  * A capped scan returns what the uncapped one returns, bit for bit: a score depends on the
  * query and the document alone.
  * bertx_test_mvindex_last_grid: the workgroups of the scan kernel (not of the selection
- * behind it) at the store's most recent scan launch, 0 before the first. */
+ * behind it) at the store's most recent scan launch, 0 before the first.
+ * bertx_test_mvindex_last_masked: 1 if the store's most recent scan or scorer launch was a
+ * masked instantiation ("Deleting documents and filtered search"), 0 otherwise, including
+ * before the first launch. */
 BERT_API int32_t bertx_test_mvindex_grid(struct bertx_mvindex *mv, int32_t max_wg);
 BERT_API int32_t bertx_test_mvindex_last_grid(struct bertx_mvindex *mv);
+BERT_API int32_t bertx_test_mvindex_last_masked(struct bertx_mvindex *mv);
 BERT_API int32_t bertx_test_kmeans_update(const float *sample, const uint16_t *codes, int32_t n, int32_t w, int32_t C,
                                           float *cent);
 BERT_API int32_t bertx_test_kmeans_sample(int64_t T, uint32_t seed, int64_t *out3);
