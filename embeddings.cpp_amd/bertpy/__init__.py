@@ -418,6 +418,21 @@ def load_lib(path=None):
         L.bertx_bench_attention_kv.argtypes = [c_i32] * 7 + [c_f32p]
     except AttributeError:
         pass
+    try:   # (SPLADE sparse term weights: the masked-LM head records and their entries; absent from older BERT_LIB builds)
+        L.bertx_convert_hf_mlm.restype = c_i32
+        L.bertx_convert_hf_mlm.argtypes = [ctypes.c_char_p, ctypes.c_char_p, c_i32]
+        L.bertx_sparse_width.restype = c_i32
+        L.bertx_sparse_width.argtypes = [vp]
+        L.bertx_forward_sparse.restype = c_i32
+        L.bertx_forward_sparse.argtypes = [vp, c_i32, c_i32, ctypes.POINTER(c_i32p), c_i32p, ctypes.POINTER(c_f32p)]
+        L.bertx_forward_sparse_device.restype = c_i32
+        L.bertx_forward_sparse_device.argtypes = [vp, c_i32, vp, vp, vp, c_i32, c_i32, c_i32, vp, vp]
+        L.bertx_test_sparse.restype = c_i32
+        L.bertx_test_sparse.argtypes = [c_i32, vp, c_i32, c_i32, vp, vp, vp, vp, vp, vp, c_i32, vp, vp, c_i32, vp, c_i32]
+        L.bertx_bench_sparse.restype = c_i32
+        L.bertx_bench_sparse.argtypes = [c_i32] * 5 + [c_f32p]
+    except AttributeError:
+        pass
     L.bertx_bench_gemm.restype = c_i32
     L.bertx_bench_gemm.argtypes = [c_i32] * 7 + [c_f32p]
     L.bertx_bench_attention.restype = c_i32
@@ -571,6 +586,40 @@ class BertModel:
             return self._forward_rows(self.lib.bertx_forward_project_kv, "bertx_forward_project_kv", ids_list,
                                       self.proj_width, n_keys)
         return self._forward_rows(self.lib.bertx_forward_project, "bertx_forward_project", ids_list, self.proj_width)
+
+    # -- SPLADE checkpoints: files with the masked-LM head records --
+    @property
+    def sparse_width(self):
+        """Terms per sparse row (n_vocab) of a file with the masked-LM head, 0 for a file without one."""
+        return int(self.lib.bertx_sparse_width(self.ctx))
+
+    def forward_sparse(self, ids_list):
+        """SPLADE term weights: an [n][n_vocab] f32 array, row i the weights of ids_list[i]."""
+        n = len(ids_list)
+        lens = np.fromiter((len(x) for x in ids_list), np.int32, n)
+        flat = np.ascontiguousarray((np.concatenate(ids_list) if n else np.zeros(0)).astype(np.int32, copy=False))
+        out = np.zeros((n, max(self.sparse_width, 1)), np.float32)
+        offs = np.zeros(n, np.uintp)
+        if n > 1:
+            np.cumsum(lens[:-1], out=offs[1:])
+        tp = (flat.ctypes.data + 4 * offs).astype(np.uintp)
+        op = (out.ctypes.data + out.strides[0] * np.arange(n, dtype=np.uintp)).astype(np.uintp)
+        rc = self.lib.bertx_forward_sparse(self.ctx, self.N_THREADS, n, tp.ctypes.data_as(ctypes.POINTER(c_i32p)),
+                                           _as_i32p(lens), op.ctypes.data_as(ctypes.POINTER(c_f32p)))
+        if rc != 0:
+            raise RuntimeError("bertx_forward_sparse failed (%d)" % rc)
+        return out
+
+    def encode_sparse(self, texts, top=None):
+        """Per text the (term id, weight) pairs with weight > 0 by descending weight (equal weights by
+        id), the best `top`; selected on the host from the dense rows."""
+        rows = self.forward_sparse([np.asarray(self.tokenize(t)[0], np.int32) for t in texts])
+        out = []
+        for w in rows:
+            order = np.argsort(-w, kind="stable")
+            order = order[w[order] > 0][:top]
+            out.append([(int(i), float(w[i])) for i in order])
+        return out
 
     def encode(self, sentences, batch_size=16):
         input_is_string = isinstance(sentences, str)
@@ -1359,6 +1408,25 @@ def append_head(src, dst, tensors):
     with open(dst, "wb") as f:
         f.write(raw)
         for name, _ in HEAD_NAMES:
+            _write_tensor(f, name, tensors[name], ftype)
+    return dst
+
+
+MLM_NAMES = ["cls.predictions.transform.dense.weight", "cls.predictions.transform.dense.bias",
+             "cls.predictions.transform.LayerNorm.weight", "cls.predictions.transform.LayerNorm.bias",
+             "cls.predictions.bias"]
+
+
+def append_mlm_head(src, dst, tensors, names=MLM_NAMES):
+    """Copy the f32 / f16 model file src to dst followed by the masked-LM head records (MLM_NAMES)
+    from tensors; quantize the result with bertx_quantize_file for the q formats."""
+    with open(src, "rb") as f:
+        raw = f.read()
+    ftype = struct.unpack_from("<i", raw, 4 + 6 * 4)[0]
+    assert ftype in (0, 1), "append_mlm_head needs an f32 or f16 file"
+    with open(dst, "wb") as f:
+        f.write(raw)
+        for name in names:
             _write_tensor(f, name, tensors[name], ftype)
     return dst
 

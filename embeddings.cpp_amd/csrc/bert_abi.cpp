@@ -90,6 +90,7 @@ struct bert_ctx {
     int pool = 0;       // BERTX_POOL_MEAN / BERTX_POOL_CLS (bertx_set_pooling), mirrored on every replica
     int n_labels = 0;   // logits per sentence of the file's classification head; 0: none (bertx_n_labels)
     int proj_dim = 0;   // rows of the file's ColBERT projection; 0: none (bertx_proj_dim)
+    bool sparse = false;   // the file carries the masked-LM head (bertx_sparse_width)
     // whether a ColBERT query's [MASK] rows are attention keys (bertx_set_mask_keys).  One value
     // for the context: the replicas hold no copy, the counts travel with each forward.
     std::atomic<int> mask_keys{1};
@@ -400,6 +401,7 @@ static bert_ctx *load_context(const char *fname, int act_mode)
     ctx->act_mode = emb::act_mode_effective(m.hp.ftype, act_mode);
     ctx->n_labels = m.n_labels;
     ctx->proj_dim = m.proj_dim;
+    ctx->sparse = m.sparse;
     if (act_mode == 1 && ctx->act_mode == 0)
         emb::infof("bert_load_from_file: q8 activations asked for a file of ftype %d: the reference has no q8 "
                    "arithmetic for f16 / f32 files, running the default mode\n", m.hp.ftype);
@@ -687,12 +689,17 @@ int32_t bertx_forward_tokens_device(struct bert_ctx *ctx, int32_t slot, const in
                      true);
 }
 
-// The per-token host forms: every token's final-LayerNorm row, or (proj) its projection.
+// The per-token host forms: every token's final-LayerNorm row, or (proj) its projection;
+// sparse: per sentence its n_vocab term weights, computed from all its token rows.
 // n_keys (or null): sentence i's key count, which travels with it into its chunk.
 static int32_t forward_rows(struct bert_ctx *ctx, int32_t n, bert_vocab_id **batch_tokens, int32_t *n_tokens,
-                            float **out, bool proj, const int32_t *n_keys = nullptr)
+                            float **out, bool proj, const int32_t *n_keys = nullptr, bool sparse = false)
 {
     if (!ctx || n < 0 || (n > 0 && (!batch_tokens || !n_tokens || !out))) return -1;
+    if (sparse && !ctx->sparse) {
+        emb::errorf("libbert: this model file has no masked-LM head (cls.predictions.*)\n");
+        return -6;
+    }
     if (proj && ctx->proj_dim <= 0) {
         emb::errorf("libbert: this model file has no projection (linear.weight)\n");
         return -6;
@@ -735,7 +742,7 @@ static int32_t forward_rows(struct bert_ctx *ctx, int32_t n, bert_vocab_id **bat
                 if (n_keys) kp.push_back(n_keys[i]);
             }
             rc = D.forward_host(tp.data(), lp.data(), (int)tp.size(), op.data(), true, nullptr, false, proj,
-                                n_keys ? kp.data() : nullptr);
+                                n_keys ? kp.data() : nullptr, sparse);
         }
     } catch (...) {
         rc = -1;
@@ -771,6 +778,30 @@ int32_t bertx_forward_project_kv(struct bert_ctx *ctx, int32_t n, bert_vocab_id 
                                  const int32_t *n_keys, float **out)
 {
     return forward_rows(ctx, n, batch_tokens, n_tokens, out, true, n_keys);
+}
+
+int32_t bertx_forward_sparse(struct bert_ctx *ctx, int32_t n_threads, int32_t n, bert_vocab_id **batch_tokens,
+                             int32_t *n_tokens, float **out)
+{
+    (void)n_threads;   // (one replica runs the call, as bertx_forward_tokens)
+    return forward_rows(ctx, n, batch_tokens, n_tokens, out, false, nullptr, true);
+}
+
+int32_t bertx_sparse_width(struct bert_ctx *ctx) { return ctx && ctx->sparse ? ctx->hp.n_vocab : 0; }
+
+int32_t bertx_forward_sparse_device(struct bert_ctx *ctx, int32_t slot, const int32_t *d_ids, const int32_t *d_types,
+                                    const int32_t *d_cu, int32_t n_seqs, int32_t max_len, int32_t total_tokens,
+                                    float *d_out, void *stream)
+{
+    if (!ctx || slot < 0 || slot >= (int32_t)ctx->devices.size()) return -1;
+    if (!ctx->sparse) return -6;
+    return bertx_forward_device_ex(ctx, slot, d_ids, d_types, d_cu, n_seqs, max_len, total_tokens, BERTX_OUT_SPARSE, d_out,
+                                   stream);
+}
+
+int32_t bertx_convert_hf_mlm(const char *dir_model, const char *fname_out, int32_t ftype)
+{
+    return emb::convert_hf_dir(dir_model, fname_out, ftype, false, false, true);
 }
 
 int32_t bertx_proj_dim(struct bert_ctx *ctx) { return ctx ? ctx->proj_dim : 0; }
@@ -896,9 +927,11 @@ int32_t bertx_forward_device_ex(struct bert_ctx *ctx, int32_t slot, const int32_
 {
     if (slot < 0 || slot >= (int32_t)ctx->devices.size()) return -1;
     if (out_kind != BERTX_OUT_POOLED && out_kind != BERTX_OUT_TOKENS && out_kind != BERTX_OUT_LOGITS &&
-        out_kind != BERTX_OUT_PROJ)
+        out_kind != BERTX_OUT_PROJ && out_kind != BERTX_OUT_SPARSE)
         return -1;
     if (out_kind == BERTX_OUT_LOGITS && ctx->n_labels <= 0) return -6;
+    // (as for the projection below: without the masked-LM head there is no fifth kind)
+    if (out_kind == BERTX_OUT_SPARSE && !ctx->sparse) return -1;
     // (a file without the projection record has no fourth output kind: -1 as before the
     // record existed; the entries that exist only for the projection answer -6)
     if (out_kind == BERTX_OUT_PROJ && ctx->proj_dim <= 0) return -1;
@@ -916,7 +949,8 @@ int32_t bertx_forward_device_kv(struct bert_ctx *ctx, int32_t slot, const int32_
                                 float *d_out, void *stream)
 {
     if (!ctx || slot < 0 || slot >= (int32_t)ctx->devices.size()) return -1;
-    if (out_kind != BERTX_OUT_TOKENS && out_kind != BERTX_OUT_PROJ) return -1;
+    if (out_kind != BERTX_OUT_TOKENS && out_kind != BERTX_OUT_PROJ && !(out_kind == BERTX_OUT_SPARSE && ctx->sparse))
+        return -1;
     const bool mapped = out_kind == BERTX_OUT_PROJ && d_rows != nullptr;
     if (mapped && n_rows < 0) return -1;
     if (out_kind == BERTX_OUT_PROJ && ctx->proj_dim <= 0) return -6;

@@ -283,7 +283,7 @@ template <typename T> void put(std::string &o, const T &v) { o.append((const cha
 
 }  // namespace
 
-int convert_hf_dir(const std::string &dir, const std::string &fname_out, int ftype, bool head, bool colbert)
+int convert_hf_dir(const std::string &dir, const std::string &fname_out, int ftype, bool head, bool colbert, bool mlm)
 {
     if (ftype < 0 || ftype > 1) {
         errorf("Invalid ftype: %d\n", ftype);
@@ -468,6 +468,53 @@ int convert_hf_dir(const std::string &dir, const std::string &fname_out, int fty
                 infof("convert: --colbert: this checkpoint was trained with attend_to_mask_tokens = false; encode its "
                       "queries with BERT_MASK_KEYS=0 (bertx_set_mask_keys(ctx, 0), search -M), else [MASK] rows are keys\n");
         }
+    }
+    if (mlm) {
+        // the masked-LM head behind everything else; its decoder is the word table (tied)
+        const int64_t d = hp[2], V = hp[0];
+        const char *tw = "cls.predictions.transform.dense.weight", *tb = "cls.predictions.transform.dense.bias";
+        const char *lw = "cls.predictions.transform.LayerNorm.weight", *lb = "cls.predictions.transform.LayerNorm.bias";
+        for (const char *n : {tw, tb, lw, lb})
+            if (!byname.count(n)) {
+                errorf("convert: --mlm: checkpoint lacks tensor '%s' (not a BertForMaskedLM checkpoint)\n", n);
+                return 1;
+            }
+        const char *bn = byname.count("cls.predictions.bias") ? "cls.predictions.bias" : "cls.predictions.decoder.bias";
+        if (!byname.count(bn)) {
+            errorf("convert: --mlm: checkpoint lacks tensor 'cls.predictions.bias'\n");
+            return 1;
+        }
+        const auto dw = byname.find("cls.predictions.decoder.weight");
+        const StTensor &word = *byname["embeddings.word_embeddings.weight"];
+        if (dw != byname.end() && (dw->second->data.size() != word.data.size() ||
+                                   std::memcmp(dw->second->data.data(), word.data.data(), word.data.size() * 4) != 0)) {
+            errorf("convert: --mlm: cls.predictions.decoder.weight differs from embeddings.word_embeddings.weight; "
+                   "untied decoders are not supported\n");
+            return 1;
+        }
+        const StTensor &w = *byname[tw], &b = *byname[tb], &g = *byname[lw], &be = *byname[lb], &vb = *byname[bn];
+        if ((int64_t)w.data.size() != d * d || (int64_t)b.data.size() != d || (int64_t)g.data.size() != d ||
+            (int64_t)be.data.size() != d || (int64_t)vb.data.size() != V) {
+            errorf("convert: --mlm: the head's shapes do not fit hidden_size %d and vocab_size %d\n", (int)d, (int)V);
+            return 1;
+        }
+        auto rec = [&](const char *n, const StTensor &t, int nd, int64_t e0, int64_t e1, bool half) {
+            put(o, (int32_t)nd);
+            put(o, (int32_t)std::strlen(n));
+            put(o, (int32_t)(half ? 1 : 0));
+            put(o, (int32_t)e0);
+            if (nd == 2) put(o, (int32_t)e1);
+            o += n;
+            if (half)
+                for (float v : t.data) put(o, f32_to_f16(v));
+            else
+                o.append((const char *)t.data.data(), t.data.size() * 4);
+        };
+        rec(tw, w, 2, d, d, ftype == 1);
+        rec(tb, b, 1, d, 1, false);
+        rec(lw, g, 1, d, 1, false);
+        rec(lb, be, 1, d, 1, false);
+        rec("cls.predictions.bias", vb, 1, V, 1, false);
     }
     FILE *f = std::fopen(fname_out.c_str(), "wb");
     if (!f) {

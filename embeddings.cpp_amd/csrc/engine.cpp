@@ -46,6 +46,22 @@ void build_proj_image(const float *W, int dim, int d, std::vector<uint8_t> &byte
         }
 }
 
+void build_rows_image(int rows, int pad, int d, const std::function<void(int, float *)> &row, std::vector<uint8_t> &bytes)
+{
+    const size_t NT = ((size_t)rows + pad - 1) / pad * pad / 16;
+    bytes.assign(NT * 16 * (size_t)d * 2, 0);   // (f16 +0: the padding rows)
+    uint16_t *o = (uint16_t *)bytes.data();
+    std::vector<float> x((size_t)d);
+    for (int j = 0; j < rows; ++j) {
+        row(j, x.data());
+        const size_t t = (size_t)j / 16, f = (size_t)j % 16;
+        for (int k = 0; k < d; ++k) {
+            const size_t kb = (size_t)k / 32, g = (size_t)(k % 32) / 8, e = (size_t)k % 8;
+            o[((kb * NT + t) * 64 + 16 * g + f) * 8 + e] = f32_to_f16(x[(size_t)k]);
+        }
+    }
+}
+
 bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bool pin, int act_mode)
 {
     try {
@@ -140,6 +156,22 @@ bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bo
             build_proj_image(w32.data(), m.proj_dim, d, p.bytes);
             img.proj_dim = m.proj_dim;
             img.proj = add(std::move(p));
+        }
+        // the masked-LM head: two f16 images for every chain, from the library's own
+        // dequantized rows -- the transform weight, and the word table as the decoder
+        if (m.sparse) {
+            auto image = [&](const HostTensor &t, int pad) {
+                Piece p;
+                build_rows_image(t.ne1, pad, d, [&](int r, float *x) {
+                    dequant_row(t.fmt, t.bytes.data() + fmt_row_bytes(t.fmt, d) * (size_t)r, x, d);
+                }, p.bytes);
+                return add(std::move(p));
+            };
+            img.sparse = true;
+            img.mlm_w = image(m.mlm_w, 64);
+            img.mlm_e = image(m.word, kSparseVocabTile);
+            img.mlm_b = vec(m.mlm_b); img.mlm_ln_w = vec(m.mlm_ln_w); img.mlm_ln_b = vec(m.mlm_ln_b);
+            img.mlm_bias = vec(m.mlm_bias);
         }
         img.layers.assign((size_t)hp.n_layer, ModelImage::Layer());
         for (int l = 0; l < hp.n_layer; ++l) {
@@ -324,6 +356,10 @@ void Device::bind(const ModelImage &img)
     head_wc_ = (const float *)P(img.head_wc); head_bc_ = (const float *)P(img.head_bc);
     proj_dim_ = img.proj_dim;
     proj_w_ = P(img.proj);
+    sparse_ = img.sparse;
+    mlm_w_ = P(img.mlm_w); mlm_e_ = P(img.mlm_e);
+    mlm_b_ = (const float *)P(img.mlm_b); mlm_ln_w_ = (const float *)P(img.mlm_ln_w);
+    mlm_ln_b_ = (const float *)P(img.mlm_ln_b); mlm_bias_ = (const float *)P(img.mlm_bias);
     auto mk_lin = [&](const ModelImage::Lin &x) {
         DevWeight w;
         w.fmt = wfmt_ == FMT_F32 ? FMT_F16 : wfmt_; w.N = x.N; w.K = x.K;

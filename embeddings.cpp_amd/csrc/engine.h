@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -94,6 +95,10 @@ struct ModelImage {
     // the ColBERT projection (files that carry one): build_proj_image of the dequantized rows
     size_t proj = kNone;
     int proj_dim = 0;
+    // the masked-LM head (files that carry one; SPLADE): the transform weight and the
+    // decoder (the word table) as build_rows_image f16 images, the f32 vectors beside them
+    size_t mlm_w = kNone, mlm_e = kNone, mlm_b = kNone, mlm_ln_w = kNone, mlm_ln_b = kNone, mlm_bias = kNone;
+    bool sparse = false;
     std::vector<Layer> layers;
     // piece i: bytes [off[i], off[i] + len[i]) of the image (len 0: absent plane)
     std::vector<size_t> off, len;
@@ -124,6 +129,10 @@ bool build_model_image(const HostModel &m, ModelImage &img, std::string &err, bo
 // SEARCH_F16 block order: block (kb, t) of 16 features x 32 k at (kb * width / 16 + t)
 // KiB, lane 16g + f = feature 16t + f, elements 32kb + 8g .. + 7.
 void build_proj_image(const float *W, int dim, int d, std::vector<uint8_t> &bytes);
+// The same block order for any row count (sparse.hip's two images): `rows` rows of d
+// values, row j from row(j, dst) as f32, rounded to f16, zero-padded to a multiple of
+// `pad` rows (a multiple of 16).
+void build_rows_image(int rows, int pad, int d, const std::function<void(int, float *)> &row, std::vector<uint8_t> &bytes);
 // The activation mode a file of format `ftype` runs when `act_mode` is asked for:
 // 1 only for q4_0 / q4_1 / q8_0 (f16 and f32 files have no q8 arithmetic in the reference).
 inline int act_mode_effective(int ftype, int act_mode)
@@ -180,13 +189,16 @@ public:
     // [n_seqs] on this GPU, sentence b's first d_keys[b] rows are the keys and values of
     // its attention, 1 <= d_keys[b] <= its length (trusted); every row stays a query and
     // an output row.  Those kinds never run the pruned last layer.
-    enum OutKind : int { KIND_POOLED = 0, KIND_TOKENS = 1, KIND_LOGITS = 2, KIND_PROJ = 3 };
+    // KIND_SPARSE: d_out is float[n_seqs][n_vocab], the SPLADE term weights of every
+    // sentence (bert_hip.h "Sparse"); -6 on a file without the masked-LM head.  Never pruned.
+    enum OutKind : int { KIND_POOLED = 0, KIND_TOKENS = 1, KIND_LOGITS = 2, KIND_PROJ = 3, KIND_SPARSE = 4 };
     int forward_ex(const int32_t *d_ids, const int32_t *d_types, const int32_t *d_cu, int n_seqs, int max_len,
                    int total_tokens, int out_kind, float *d_out, hipStream_t s, double len2_sum = -1.0,
                    const int32_t *d_rows = nullptr, int n_rows = 0, const int32_t *d_keys = nullptr);
     int n_labels() const { return n_labels_; }
     int proj_dim() const { return proj_dim_; }
     int proj_width() const { return proj_width_of(proj_dim_); }
+    int sparse_width() const { return sparse_ ? hp_.n_vocab : 0; }
 
     // Host-driven forward: packs tokens, H2D, forward, D2H, synchronous.
     // tokens[i] has lens[i] ids; out[i] receives n_embd floats, or with tok_out
@@ -195,9 +207,10 @@ public:
     // n_labels logits of sentence i instead.  proj (with tok_out): out[i] receives
     // lens[i] x proj_width floats, the projected rows (KIND_PROJ).  keys (with tok_out;
     // null: none): keys[i] is sentence i's key count, 1 .. lens[i] (checked by the caller).
+    // sparse (with tok_out): out[i] receives the n_vocab term weights of sentence i (KIND_SPARSE).
     int forward_host(const int32_t *const *tokens, const int32_t *lens, int n, float *const *out, bool tok_out = false,
                      const int32_t *const *types = nullptr, bool logits = false, bool proj = false,
-                     const int32_t *keys = nullptr);
+                     const int32_t *keys = nullptr, bool sparse = false);
 
     // Pooling of the sentence embeddings (bert_hip.h): BERTX_POOL_MEAN / BERTX_POOL_CLS,
     // and whether CLS pooling runs the last layer on the sentences' first rows only
@@ -244,7 +257,7 @@ private:
         }
     };
     // what the launch sequence ends in (and, for CLS and the logits, how its last layer runs)
-    enum OutMode : int { OUT_MEAN = 0, OUT_CLS, OUT_CLS_PRUNED, OUT_TOKENS, OUT_LOGITS, OUT_LOGITS_PRUNED, OUT_PROJ };
+    enum OutMode : int { OUT_MEAN = 0, OUT_CLS, OUT_CLS_PRUNED, OUT_TOKENS, OUT_LOGITS, OUT_LOGITS_PRUNED, OUT_PROJ, OUT_SPARSE };
     bool pruned_last() const { return out_mode_ == OUT_CLS_PRUNED || out_mode_ == OUT_LOGITS_PRUNED; }
     struct GraphEntry { GraphKey key; hipGraphExec_t exec; };
     int forward_ordered(const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out,
@@ -274,6 +287,8 @@ private:
     int chain_f16(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out);
     int layer_tail(Launcher &run, const DevLayer &L, int l, const RowSet &r, const float *&gz, const float *&bz);
     int head(Launcher &run, int n_seqs, float *d_out);
+    int sparse_head(Launcher &run, const uint16_t *z, const float2 *st, const float *gz, const float *bz, const float *x32,
+                    uint16_t *h, const int32_t *d_cu, int n_seqs, int T, float *d_out);
     int chain_32(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, int n_seqs, int max_len, int T, float *d_out);
     void drop_graphs();
     void bind(const ModelImage &img);   // device pointers of the image's planes
@@ -303,6 +318,10 @@ private:
     int n_labels_ = 0;
     const void *proj_w_ = nullptr;   // the projector's weight image (null / 0: the file has none)
     int proj_dim_ = 0;
+    // the masked-LM head (sparse_ false: the file has none)
+    const void *mlm_w_ = nullptr, *mlm_e_ = nullptr;
+    const float *mlm_b_ = nullptr, *mlm_ln_w_ = nullptr, *mlm_ln_b_ = nullptr, *mlm_bias_ = nullptr;
+    bool sparse_ = false;
 
     // workspace
     int64_t cap_tokens_ = 0, cap_seqs_ = 0, cap_pool_ = 0;   // cap_pool_: pool partial rows (seqs x chunks)

@@ -80,11 +80,14 @@ int Device::forward_ex(const int32_t *d_ids, const int32_t *d_types, const int32
                        int out_kind, float *d_out, hipStream_t s, double len2_sum, const int32_t *d_rows, int n_rows,
                        const int32_t *d_keys)
 {
-    if (out_kind != KIND_POOLED && out_kind != KIND_TOKENS && out_kind != KIND_LOGITS && out_kind != KIND_PROJ) return -1;
+    if (out_kind != KIND_POOLED && out_kind != KIND_TOKENS && out_kind != KIND_LOGITS && out_kind != KIND_PROJ &&
+        out_kind != KIND_SPARSE)
+        return -1;
     // key counts come with the per-token outputs only (which never take the pruned last layer)
-    if (d_keys && out_kind != KIND_TOKENS && out_kind != KIND_PROJ) return -1;
+    if (d_keys && out_kind != KIND_TOKENS && out_kind != KIND_PROJ && out_kind != KIND_SPARSE) return -1;
     if (out_kind == KIND_LOGITS && n_labels_ <= 0) return -6;
     if (out_kind == KIND_PROJ && proj_dim_ <= 0) return -6;
+    if (out_kind == KIND_SPARSE && !sparse_) return -6;
     const bool mapped = out_kind == KIND_PROJ && d_rows != nullptr;
     if (mapped && n_rows < 0) return -1;
     map_ = mapped ? d_rows : nullptr;
@@ -92,6 +95,7 @@ int Device::forward_ex(const int32_t *d_ids, const int32_t *d_types, const int32
     const bool can_prune = prune_ && !f32_ && !q8_;
     out_mode_ = out_kind == KIND_TOKENS   ? OUT_TOKENS
                 : out_kind == KIND_PROJ   ? OUT_PROJ
+                : out_kind == KIND_SPARSE ? OUT_SPARSE
                 : out_kind == KIND_LOGITS ? (can_prune ? OUT_LOGITS_PRUNED : OUT_LOGITS)
                 : pool_ != 1              ? OUT_MEAN
                                           : can_prune ? OUT_CLS_PRUNED : OUT_CLS;
@@ -240,6 +244,8 @@ int Device::chain_f16(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, 
         }, Out{"project", "", -1, d_out, (size_t)n_out * width, 0});
         return ok ? 0 : -1;
     }
+    if (out_mode_ == OUT_SPARSE)   // (att_ is free behind the last layer: the transform's h rows)
+        return sparse_head(run, z_, st_, gz, bz, nullptr, att_, d_cu, n_seqs, T, d_out);
     const Out out{"pool_l2", "", -1, d_out, (out_mode_ == OUT_TOKENS ? (size_t)T : (size_t)n_seqs) * d, 0};
     if (out_mode_ == OUT_MEAN) {
         run.run(K_POOL_L2, t * d * 2.0 + t * 8.0 + (double)n_seqs * d * 4.0,
@@ -254,6 +260,22 @@ int Device::chain_f16(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, 
         }, out);
     }
     return 0;
+}
+
+// The masked-LM head with its max-pool (sparse.hip), timed in the output-stage class by
+// its FLOP-free traffic: the source rows, h written and read, both images once, the output.
+int Device::sparse_head(Launcher &run, const uint16_t *z, const float2 *st, const float *gz, const float *bz,
+                        const float *x32, uint16_t *h, const int32_t *d_cu, int n_seqs, int T, float *d_out)
+{
+    const int d = hp_.n_embd, V = hp_.n_vocab;
+    const double t = (double)T;
+    bool ok = run.run(K_POOL_L2, t * d * (x32 ? 4.0 : 2.0) + t * d * 2.0 + (double)d * d * 2.0, [&] {
+        return launch_sparse_transform(z, st, gz, bz, x32, d, mlm_w_, mlm_b_, mlm_ln_w_, mlm_ln_b_, T, h, run.s);
+    }, Launcher::Out{"sparse_transform", "", -1, h, (size_t)T * d});
+    ok = ok && run.run(K_POOL_L2, t * d * 2.0 + (double)V * d * 2.0 + (double)n_seqs * V * 12.0, [&] {
+        return launch_sparse_decoder(h, T, d, mlm_e_, V, mlm_bias_, d_cu, n_seqs, d_out, run.s);
+    }, Launcher::Out{"sparse_decoder", "", -1, d_out, (size_t)n_seqs * V, 0});
+    return ok ? 0 : -1;
 }
 
 // The classification head on head_x_ (the sentences' final-LayerNorm [CLS] rows): the
@@ -387,6 +409,8 @@ int Device::chain_32(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, i
         }, Out{"project", "", -1, d_out, (size_t)n_out * width, 0});
         return ok ? 0 : -1;
     }
+    if (out_mode_ == OUT_SPARSE)   // (att32_ is free behind the last layer: the transform's h rows)
+        return sparse_head(run, nullptr, nullptr, nullptr, nullptr, x32_, (uint16_t *)att32_, d_cu, n_seqs, T, d_out);
     if (out_mode_ == OUT_MEAN)
         ok = run.run(K_POOL_L2, t * d * 4.0 + (double)n_seqs * d * 4.0,
                      [&] { launch_f32_pool(x32_, d_cu, n_seqs, d, d_out, s, exact); }, Out{"pool_l2", "", -1, d_out, nd, 0});
@@ -400,10 +424,11 @@ int Device::chain_32(Launcher &run, const int32_t *d_ids, const int32_t *d_cu, i
 }
 
 int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int n, float *const *out, bool tok_out,
-                         const int32_t *const *types, bool logits, bool proj, const int32_t *keys)
+                         const int32_t *const *types, bool logits, bool proj, const int32_t *keys, bool sparse)
 {
     if (!ok_) return -3;
     if (keys && !tok_out) return -1;
+    if (sparse && (!sparse_ || !tok_out || proj)) return sparse_ ? -1 : -6;
     if (logits && n_labels_ <= 0) return -6;
     if (proj && proj_dim_ <= 0) return -6;
     if (n <= 0) return 0;
@@ -439,20 +464,29 @@ int Device::forward_host(const int32_t *const *tokens, const int32_t *lens, int 
     if (tok_out) {
         // per-token output: a device buffer of its own, grown on demand, and plain
         // copies into the caller's buffers (not a hot path)
-        if (T > cap_tok_out_) {
+        // (the sparse output, n rows of n_vocab floats, in the same buffer: counted in its rows)
+        const size_t tw_max = std::max(d, (size_t)proj_width()), V = (size_t)hp_.n_vocab;
+        const int64_t need = sparse ? (int64_t)(((size_t)n * V + tw_max - 1) / tw_max) : T;
+        if (need > cap_tok_out_) {
             HIP_RC(hipStreamSynchronize(stream_));
             if (tok_out_) { (void)hipFree(tok_out_); tok_out_ = nullptr; }
             cap_tok_out_ = 0;
             drop_graphs();   // captured token forwards hold the old pointer
-            const int64_t cap = (int64_t)align_up((size_t)T, 4096);
-            HIP_RC(hipMalloc((void **)&tok_out_, sizeof(float) * std::max(d, (size_t)proj_width()) * (size_t)cap));
+            const int64_t cap = (int64_t)align_up((size_t)need, 4096);
+            HIP_RC(hipMalloc((void **)&tok_out_, sizeof(float) * tw_max * (size_t)cap));
             cap_tok_out_ = cap;
         }
         const size_t tw = proj ? (size_t)proj_width() : d;   // floats per row of this output
-        const int rc = forward_ex(d_ids_, dty, d_cu_, n, max_len, (int)T, proj ? KIND_PROJ : KIND_TOKENS, tok_out_, stream_,
-                                  len2, nullptr, 0, keys ? d_keys_ : nullptr);
+        const int rc = forward_ex(d_ids_, dty, d_cu_, n, max_len, (int)T,
+                                  sparse ? KIND_SPARSE : proj ? KIND_PROJ : KIND_TOKENS, tok_out_, stream_, len2, nullptr, 0,
+                                  keys ? d_keys_ : nullptr);
         if (rc != 0) return rc;
         HIP_RC(hipStreamSynchronize(stream_));
+        if (sparse) {
+            for (int i = 0; i < n; ++i)
+                HIP_RC(hipMemcpy(out[i], tok_out_ + V * (size_t)i, sizeof(float) * V, hipMemcpyDeviceToHost));
+            return 0;
+        }
         for (int i = 0; i < n; ++i)
             HIP_RC(hipMemcpy(out[i], tok_out_ + tw * (size_t)h_cu_[i], sizeof(float) * tw * (size_t)lens[i],
                              hipMemcpyDeviceToHost));

@@ -1201,3 +1201,128 @@ extern "C" int32_t bertx_bench_project(int32_t d, int32_t dim, int32_t T, int32_
         return -1;
     }
 }
+
+// The sparse head's two images from plain f32 rows, as the engine builds them at load.
+static void sparse_hook_image(const float *W, int rows, int pad, int d, std::vector<uint8_t> &img)
+{
+    emb::build_rows_image(rows, pad, d, [&](int r, float *x) { std::memcpy(x, W + (size_t)r * d, (size_t)d * 4); }, img);
+}
+
+extern "C" int32_t bertx_test_sparse(int32_t mode, const float *x, int32_t T, int32_t d, const float *Wt, const float *bt,
+                                     const float *gamma, const float *beta, const uint16_t *h_in, const float *E,
+                                     int32_t V, const float *b, const int32_t *cu, int32_t n_seqs, void *out,
+                                     int32_t out_rows)
+{
+    using namespace emb;
+    const bool tf = mode == 0 || mode == 2, dec = mode == 1 || mode == 2;
+    if (mode < 0 || mode > 2 || T <= 0 || !hook_width_ok(d) || !out || hip_device_count() == 0) return -1;
+    if (tf && (!x || !Wt || !bt || !gamma || !beta)) return -1;
+    if (mode == 1 && !h_in) return -1;
+    if (dec && (!E || !b || V < 1 || !hook_cu_ok(cu, n_seqs, T) || cu[n_seqs] != T)) return -1;
+    if (out_rows < (dec ? n_seqs : T)) return -1;
+    constexpr size_t GUARD = 16;   // rows of NaN bits behind the caller's out_rows
+    const size_t row_bytes = dec ? (size_t)V * 4 : (size_t)d * 2;
+    std::vector<uint8_t> wimg, eimg;
+    if (tf) sparse_hook_image(Wt, d, 64, d, wimg);
+    if (dec) sparse_hook_image(E, V, kSparseVocabTile, d, eimg);
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const float *dx = tf ? (const float *)B.up(x, (size_t)T * d * 4, 0) : nullptr;
+    const void *dw = tf ? B.up(wimg.data(), wimg.size(), 0) : nullptr;
+    const float *dbt = tf ? (const float *)B.up(bt, (size_t)d * 4, 0) : nullptr;
+    const float *dga = tf ? (const float *)B.up(gamma, (size_t)d * 4, 0) : nullptr;
+    const float *dbe = tf ? (const float *)B.up(beta, (size_t)d * 4, 0) : nullptr;
+    const void *de = dec ? B.up(eimg.data(), eimg.size(), 0) : nullptr;
+    const float *db = dec ? (const float *)B.up(b, (size_t)V * 4, 0) : nullptr;
+    const int32_t *dcu = dec ? (const int32_t *)B.up(cu, ((size_t)n_seqs + 1) * 4, 0) : nullptr;
+    const size_t ob = (size_t)out_rows * row_bytes, gb = GUARD * row_bytes;
+    void *dout = B.up(out, ob, ob + gb);
+    // h: the output itself (mode 0), the caller's rows (mode 1) or a buffer between the stages
+    uint16_t *dh = mode == 0 ? (uint16_t *)dout : (uint16_t *)B.up(mode == 1 ? h_in : nullptr, mode == 1 ? (size_t)T * d * 2 : 0,
+                                                                   (size_t)T * d * 2);
+    if (B.bad) return -1;
+    HIP_RC(hipMemset((char *)dout + ob, 0xff, gb));
+    int lrc = 0;
+    if (tf) lrc = launch_sparse_transform(nullptr, nullptr, nullptr, nullptr, dx, d, dw, dbt, dga, dbe, T, dh, nullptr);
+    if (dec && lrc == 0) lrc = launch_sparse_decoder(dh, T, d, de, V, db, dcu, n_seqs, (float *)dout, nullptr);
+    if (const int rc = hook_finish()) return rc;
+    if (lrc != 0) return -1;
+    HIP_RC(hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost));
+    std::vector<uint8_t> gd(gb);
+    HIP_RC(hipMemcpy(gd.data(), (char *)dout + ob, gb, hipMemcpyDeviceToHost));
+    for (const uint8_t v : gd) if (v != 0xffu) return -5;
+    return 0;
+}
+
+// Sparse head micro-benchmark (bert_hip.h): device 0, no context, the f16-chain source
+// form; avg_us[0] the transform, avg_us[1] the decoder (fill, GEMM + max, log1p).
+extern "C" int32_t bertx_bench_sparse(int32_t d, int32_t V, int32_t n_seqs, int32_t len, int32_t iters, float *avg_us)
+{
+    using namespace emb;
+    if (!hook_width_ok(d) || V < 1 || n_seqs < 1 || len < 1 || iters < 1 || !avg_us || hip_device_count() == 0 ||
+        (int64_t)n_seqs * len > (1 << 24))
+        return -1;
+    try {
+        auto h01 = [](uint32_t x) {
+            x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+            return (float)(x >> 8) * (1.0f / 16777216.0f);
+        };
+        const int T = n_seqs * len;
+        std::vector<uint16_t> z((size_t)T * d);
+        for (size_t i = 0; i < z.size(); ++i) z[i] = f32_to_f16(4.0f * h01((uint32_t)i + 1u) - 2.0f);
+        std::vector<float> st((size_t)T * 2), gam((size_t)d), bet((size_t)d), bias((size_t)V);
+        for (int t = 0; t < T; ++t) { st[2 * (size_t)t] = 0.1f * h01(77u + (uint32_t)t); st[2 * (size_t)t + 1] = 0.5f + h01(991u + (uint32_t)t); }
+        for (int k = 0; k < d; ++k) { gam[(size_t)k] = 0.75f + 0.5f * h01(5u + (uint32_t)k); bet[(size_t)k] = 0.2f * h01(3001u + (uint32_t)k) - 0.1f; }
+        for (int v = 0; v < V; ++v) bias[(size_t)v] = 0.2f * h01(40503u + (uint32_t)v) - 0.1f;
+        std::vector<int32_t> cu((size_t)n_seqs + 1);
+        for (int i = 0; i <= n_seqs; ++i) cu[(size_t)i] = i * len;
+        const float ws = 2.0f / std::sqrt((float)d);
+        auto hashed = [&](uint32_t salt) {
+            return [=](int r, float *x) {
+                for (int k = 0; k < d; ++k) x[k] = ws * (h01(salt + (uint32_t)r * (uint32_t)d + (uint32_t)k) - 0.5f);
+            };
+        };
+        std::vector<uint8_t> wimg, eimg;
+        build_rows_image(d, 64, d, hashed(0x9e3779b9u), wimg);
+        build_rows_image(V, kSparseVocabTile, d, hashed(0x85ebca6bu), eimg);
+        DeviceGuard guard(0);
+        HIP_RC(guard.status());
+        HookBufs B;
+        const uint16_t *dz = (const uint16_t *)B.up(z.data(), z.size() * 2, 0);
+        const float2 *dst = (const float2 *)B.up(st.data(), st.size() * 4, 0);
+        const float *dg = (const float *)B.up(gam.data(), gam.size() * 4, 0), *db = (const float *)B.up(bet.data(), bet.size() * 4, 0);
+        const float *dbias = (const float *)B.up(bias.data(), bias.size() * 4, 0);
+        const int32_t *dcu = (const int32_t *)B.up(cu.data(), cu.size() * 4, 0);
+        const void *dw = B.up(wimg.data(), wimg.size(), 0), *de = B.up(eimg.data(), eimg.size(), 0);
+        uint16_t *dh = (uint16_t *)B.up(nullptr, 0, (size_t)T * d * 2);
+        float *dout = (float *)B.up(nullptr, 0, (size_t)n_seqs * V * 4);
+        if (B.bad) return -1;
+        struct Str {
+            hipStream_t s = nullptr;
+            ~Str() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+        } E;
+        HIP_RC(hipStreamCreateWithFlags(&E.s, hipStreamNonBlocking));
+        EventPair ev;
+        HIP_RC(ev.create());
+        // (the transform's LayerNorm and bias vectors: the hashed gamma / beta serve for all)
+        auto tf = [&] { return launch_sparse_transform(dz, dst, dg, db, nullptr, d, dw, db, dg, db, T, dh, E.s); };
+        auto dc = [&] { return launch_sparse_decoder(dh, T, d, de, V, dbias, dcu, n_seqs, dout, E.s); };
+        for (int stage = 0; stage < 2; ++stage) {
+            for (int i = 0; i < 3; ++i)
+                if ((stage ? dc() : tf()) != 0) return -1;
+            HIP_RC(hipEventRecord(ev.a, E.s));
+            for (int i = 0; i < iters; ++i)
+                if ((stage ? dc() : tf()) != 0) return -1;
+            HIP_RC(hipEventRecord(ev.b, E.s));
+            HIP_RC(hipEventSynchronize(ev.b));
+            float ms = 0.f;
+            HIP_RC(hipEventElapsedTime(&ms, ev.a, ev.b));
+            avg_us[stage] = ms * 1000.f / (float)iters;
+        }
+        return 0;
+    } catch (const std::exception &ex) {
+        emb::errorf("bertx_bench_sparse: %s\n", ex.what());
+        return -1;
+    }
+}

@@ -79,6 +79,12 @@ struct HostModel {
     // the optional ColBERT projection linear.weight [dim][d] in the header ftype, no bias
     HostTensor proj_w;
     int32_t proj_dim = 0;           // 0: the file has no projection
+    // the optional masked-LM head of SPLADE checkpoints (all five records or none):
+    // cls.predictions.transform.dense.weight [d][d] in the header ftype, its bias, the
+    // transform's LayerNorm weight and bias [d] and cls.predictions.bias [n_vocab], f32;
+    // the decoder weight is the word-embedding table
+    HostTensor mlm_w, mlm_b, mlm_ln_w, mlm_ln_b, mlm_bias;
+    bool sparse = false;            // the file has the five records
     size_t total_bytes = 0;
     int n_tensors = 0;
 };
@@ -109,7 +115,10 @@ int quantize_file(const char *in, const char *out, int itype, bool verbose);
 // colbert: followed by the projection record linear.weight (HF_ColBERT checkpoints:
 // encoder tensors bert.*, the projection un-prefixed), refused without it, with a
 // linear.bias or with a shape the loader would refuse
+// mlm: followed by the five masked-LM head records of a BertForMaskedLM checkpoint
+// (cls.predictions.*; SPLADE), refused without the transform or with a decoder weight
+// that is not the word-embedding table
 int convert_hf_dir(const std::string &dir, const std::string &fname_out, int ftype, bool head = false,
-                   bool colbert = false);
+                   bool colbert = false, bool mlm = false);
 
 }  // namespace emb

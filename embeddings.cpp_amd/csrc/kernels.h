@@ -447,6 +447,24 @@ int launch_project(const uint16_t *z, const float2 *stats, const float *ln_w, co
                    int32_t d, const void *wimg, int32_t dim, const int32_t *d_rows, int32_t n_out, float *out,
                    hipStream_t s);
 
+// ---- SPLADE sparse term weights (sparse.hip; the arithmetic: bert_hip.h "Sparse") ----
+// The decoder image's rows are padded with zeros to whole vocab tiles of this many terms.
+constexpr int kSparseVocabTile = 128;
+// The transform: h f16 [T][d] = f16(LayerNorm(gelu_erf(x Wt^T + bt)) * gamma + beta), the
+// source row given as for launch_project (z with stats / ln_w / ln_b, or x32).  wimg:
+// Wt [d][d] as build_rows_image (engine.h) lays it out with pad 64.  Only rows 0 .. T - 1
+// are read and stored.  d % 64 == 0, 64 <= d <= 1024, T >= 1; -1 otherwise, -3 refused.
+int launch_sparse_transform(const uint16_t *z, const float2 *stats, const float *ln_w, const float *ln_b,
+                            const float *x32, int32_t d, const void *wimg, const float *bt, const float *gamma,
+                            const float *beta, int32_t T, uint16_t *h, hipStream_t s);
+// The decoder with its fused segmented max: out f32 [n_seqs][V], out[s][v] =
+// log1pf(max(+0, max over rows cu[s] .. cu[s + 1] - 1 of (h_row . E_v) + bias_v)).  eimg: E
+// [V][d] as build_rows_image with pad kSparseVocabTile; cu int32 [n_seqs + 1] on the
+// device, ascending from 0 to T.  Three launches: a +0 fill of out, the GEMM with atomicMax
+// on the bits of the positive results, log1pf in place.  Same shape rules, V >= 1.
+int launch_sparse_decoder(const uint16_t *h, int32_t T, int32_t d, const void *eimg, int32_t V, const float *bias,
+                          const int32_t *cu, int32_t n_seqs, float *out, hipStream_t s);
+
 // Diagnostics: *cnt += number of non-finite values in p[0..n) (f32, or f16 if f16).
 void launch_count_nonfinite(const void *p, size_t n, int f16, unsigned *cnt, hipStream_t s);
 

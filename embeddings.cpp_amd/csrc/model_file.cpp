@@ -140,6 +140,12 @@ HostTensor *slot(HostModel &m, const std::string &name, int32_t &e0, int32_t &e1
     // the optional head; e1 = -1: the classifier's row count is the file's (n_labels)
     if (name == "pooler.dense.bias") { e0 = d; return &m.pool_b; }
     if (name == "classifier.bias") { e0 = -1; return &m.cls_b; }
+    // the optional masked-LM head (SPLADE)
+    if (name == "cls.predictions.transform.dense.bias") { e0 = d; return &m.mlm_b; }
+    if (name == "cls.predictions.transform.LayerNorm.weight") { e0 = d; return &m.mlm_ln_w; }
+    if (name == "cls.predictions.transform.LayerNorm.bias") { e0 = d; return &m.mlm_ln_b; }
+    if (name == "cls.predictions.bias") { e0 = m.hp.n_vocab; return &m.mlm_bias; }
+    if (name == "cls.predictions.transform.dense.weight") { vec = false; e0 = d; e1 = d; return &m.mlm_w; }
     if (name == "pooler.dense.weight") { vec = false; e0 = d; e1 = d; return &m.pool_w; }
     if (name == "classifier.weight") { vec = false; e0 = d; e1 = -1; return &m.cls_w; }
     // the optional ColBERT projection; e1 = -1: the row count is the file's (dim)
@@ -278,6 +284,15 @@ bool load_model_file(const char *path, HostModel &m, std::string &err, bool verb
         m.n_labels = m.cls_w.ne1;
         if (verbose) std::printf("bert_load_from_file: n_labels = %d\n", m.n_labels);
     }
+    const int n_mlm_recs = (int)m.mlm_w.present() + m.mlm_b.present() + m.mlm_ln_w.present() + m.mlm_ln_b.present() +
+                           m.mlm_bias.present();
+    if (n_mlm_recs != 0 && n_mlm_recs != 5) {
+        err = "incomplete masked-LM head: cls.predictions.transform.dense.weight and .bias, "
+              "cls.predictions.transform.LayerNorm.weight and .bias and cls.predictions.bias come together or not at all";
+        return false;
+    }
+    m.sparse = n_mlm_recs == 5;
+    if (m.sparse && verbose) std::printf("bert_load_from_file: sparse_width = %d\n", m.hp.n_vocab);
     if (m.proj_w.present()) {
         m.proj_dim = m.proj_w.ne1;
         if (verbose) std::printf("bert_load_from_file: proj_dim = %d\n", m.proj_dim);

@@ -7,6 +7,8 @@
 // cross-encoder reranker): the same file followed by the pooler and classifier records.
 //   convert dir-model ftype --colbert   an HF_ColBERT checkpoint (encoder tensors bert.*,
 // the un-prefixed linear.weight): the same file followed by the projection record.
+//   convert dir-model ftype --mlm   a BertForMaskedLM checkpoint (SPLADE, neural-sparse):
+// the same file followed by the masked-LM head's five records (the decoder stays tied).
 #include "bert_hip.h"
 
 #include <cstdio>
@@ -33,8 +35,10 @@ int main(int argc, char **argv)
     }
     const bool head = argc > 3 && std::string(argv[3]) == "--head";
     const bool colbert = argc > 3 && std::string(argv[3]) == "--colbert";
+    const bool mlm = argc > 3 && std::string(argv[3]) == "--mlm";
     const int rc = head      ? bertx_convert_hf_head(dir.c_str(), out.c_str(), ftype)
                    : colbert ? bertx_convert_hf_colbert(dir.c_str(), out.c_str(), ftype)
+                   : mlm     ? bertx_convert_hf_mlm(dir.c_str(), out.c_str(), ftype)
                              : bertx_convert_hf(dir.c_str(), out.c_str(), ftype);
     if (rc != 0) return 1;
     std::printf("Done. Output file: %s\n\n", out.c_str());

@@ -1331,6 +1331,90 @@ BERT_API int32_t bertx_test_attention_f32_kv(const float *qkv, const int32_t *cu
 BERT_API int32_t bertx_bench_attention_kv(int32_t n_seqs, int32_t len, int32_t n_keys, int32_t n_head, int32_t dh,
                                           int32_t variant, int32_t iters, float *avg_us);
 
+/*
+ * Sparse: SPLADE term weights (learned sparse retrieval; naver/splade-*, the OpenSearch
+ * neural-sparse family): BertForMaskedLM checkpoints on the WordPiece vocabulary.  A
+ * sentence's representation is one non-negative weight per vocabulary term,
+ *   w[s][v] = log(1 + relu(max over the sentence's tokens t of logit[t][v])),
+ * the masked-LM head's logits max-pooled over all the sentence's rows ([CLS] and [SEP]
+ * included, as SPLADE's attention-mask product does).
+ *
+ * Model file.  Five optional records, all or none (a partial set is a load error):
+ * cls.predictions.transform.dense.weight, ne = {n_embd, n_embd}, in the header ftype like
+ * any 2-D weight (bertx_quantize_file quantizes it by its general rule);
+ * cls.predictions.transform.dense.bias, cls.predictions.transform.LayerNorm.weight and
+ * .bias, ne = {n_embd}, and cls.predictions.bias, ne = {n_vocab}, f32.  The decoder weight
+ * is the word-embedding record (tied) and is not stored again.  A file without the
+ * records loads and runs exactly as before.  bertx_convert_hf_mlm (convert DIR FTYPE
+ * --mlm) is bertx_convert_hf followed by the records from a BertForMaskedLM directory
+ * (cls.predictions.decoder.bias is read where cls.predictions.bias is absent); it refuses
+ * (message, non-zero) a checkpoint without the transform and one whose
+ * cls.predictions.decoder.weight is present and not byte-equal to the word embeddings.
+ * bertx_sparse_width: n_vocab for a file with the records, else 0; works on
+ * tokenizer-only contexts.  At load every replica holds two f16 images beside the model:
+ * the transform weight (2 n_embd^2 bytes) and the decoder, the word table dequantized by
+ * the library's own rule and rounded to f16, rows padded with zeros to a multiple of 128
+ * (2 n_embd 128 ceil(n_vocab / 128) bytes: 47 MB at n_embd 768, n_vocab 30,522).
+ *
+ * Arithmetic, every named operation rounded once to f32, nearest even, for every token
+ * row of a sentence:
+ *   x     = the row's final-LayerNorm values, the bits BERTX_OUT_TOKENS gives for that row
+ *   a_k   = f16(x_k)
+ *   u_j   = (sum_k a_k f16(Wt_jk)) + bt_j; the sum f32 from 0 in ascending blocks of 32 k
+ *           (v_mfma_f32_16x16x32_f16; the order inside a block is the instruction's)
+ *   g_j   = (0.5 u_j) * (1 + erff(u_j * 0.70710678f))     (HF's hidden_act "gelu")
+ *   mean  = (sum_j g_j) / d;  c_j = g_j - mean;  var = (sum_j c_j c_j) / d;
+ *   rstd  = 1 / sqrt(var + 1e-5) (sqrt, then the division); both sums in one fixed order
+ *           that depends on d only
+ *   h_j   = f16(((c_j * rstd) * gamma_j) + beta_j)
+ *   l_v   = sum_k h_k f16(E_vk), f32 as above;  E the word table
+ *   m_v   = (max over the sentence's rows of l_v) + b_v
+ *   w_v   = log1pf(m_v > 0 ? m_v : +0)
+ * log1p and the relu are applied once per (sentence, term), after the max: both are
+ * monotone, so this is SPLADE-max exactly.  The same arithmetic runs under all three
+ * chains.  A sentence's weights depend on its own ids and types only, bit for bit: not
+ * on its place in the batch, the other sentences or n_seqs.
+ *
+ * BERTX_OUT_SPARSE (bertx_forward_device_ex, bertx_forward_device_kv): d_out is
+ * float[n_seqs][n_vocab].  All token rows are needed: it follows no pooling mode and is
+ * never pruned.  Asynchronous and capturable like the other kinds.  On a file without the
+ * records these two entries know no such kind and return -1, as they did before the
+ * records existed; the entries that exist only for the sparse output return -6 there:
+ * bertx_forward_sparse_device (bertx_forward_device_ex with BERTX_OUT_SPARSE) and
+ * bertx_forward_sparse, the host form with the routing, chunking, replicas and refusals
+ * of bertx_forward_tokens; out[i] receives float[n_vocab]; on a refusal out is untouched
+ * (n_threads is accepted for symmetry and unused).
+ *
+ * bertx_test_sparse (parity hook; host buffers, device 0, the rules of the row-kernel
+ * hooks).  mode 0, the transform: x f32 [T][d], Wt f32 [d][d], bt, gamma, beta f32 [d];
+ * out = h f16 [out_rows][d], out_rows >= T.  mode 1, the decoder: h_in f16 [T][d], E f32
+ * [V][d], b f32 [V], cu int32 [n_seqs + 1] (0 ascending to T); out = w f32
+ * [out_rows][V], out_rows >= n_seqs.  mode 2: both, from x.  Arguments a mode does not
+ * use may be NULL / 0.  The device output starts as the caller's bytes and is copied back
+ * whole, with guard rows of NaN bits behind it; -5: a guard row was written; -1: a shape
+ * the kernels refuse or too few out_rows.
+ * bertx_bench_sparse (device 0, no context): n_seqs sentences of len tokens of hashed
+ * data; avg_us[0] the transform's, avg_us[1] the decoder's average device time over
+ * `iters` launches after 3 warm-up launches.
+ *
+ * Not provided: an inverted index or a sparse search (the rows leave the library dense),
+ * untied decoders, the `search` tool, RoBERTa / XLM-R vocabularies (bge-m3's sparse
+ * head), top-n selection on the device.
+ */
+enum { BERTX_OUT_SPARSE = 4 };
+BERT_API int32_t bertx_convert_hf_mlm(const char *dir_model, const char *fname_out, int32_t ftype);
+BERT_API int32_t bertx_sparse_width(struct bert_ctx *ctx);
+BERT_API int32_t bertx_forward_sparse(struct bert_ctx *ctx, int32_t n_threads, int32_t n, bert_vocab_id **batch_tokens,
+                                      int32_t *n_tokens, float **out);
+BERT_API int32_t bertx_forward_sparse_device(struct bert_ctx *ctx, int32_t slot, const int32_t *d_ids,
+                                             const int32_t *d_types, const int32_t *d_cu, int32_t n_seqs,
+                                             int32_t max_len, int32_t total_tokens, float *d_out, void *stream);
+BERT_API int32_t bertx_test_sparse(int32_t mode, const float *x, int32_t T, int32_t d, const float *Wt, const float *bt,
+                                   const float *gamma, const float *beta, const uint16_t *h_in, const float *E,
+                                   int32_t V, const float *b, const int32_t *cu, int32_t n_seqs, void *out,
+                                   int32_t out_rows);
+BERT_API int32_t bertx_bench_sparse(int32_t d, int32_t V, int32_t n_seqs, int32_t len, int32_t iters, float *avg_us);
+
 BERT_API const char *bertx_version(void);
 
 #ifdef __cplusplus
