@@ -433,6 +433,46 @@ def load_lib(path=None):
         L.bertx_bench_sparse.argtypes = [c_i32] * 5 + [c_f32p]
     except AttributeError:
         pass
+    try:   # (the sparse index: device top-n selection and the fused scan; absent from older BERT_LIB builds)
+        L.bertx_spindex_create.restype = vp
+        L.bertx_spindex_create.argtypes = [vp, c_i32, c_i32, c_i32, c_i32, ctypes.c_int64]
+        L.bertx_spindex_free.restype = None
+        L.bertx_spindex_free.argtypes = [vp]
+        for fn in (L.bertx_spindex_clear, L.bertx_spindex_docs, L.bertx_spindex_capacity_docs, L.bertx_spindex_vocab,
+                   L.bertx_spindex_top, L.bertx_test_spindex_last_grid):
+            fn.restype = c_i32
+            fn.argtypes = [vp]
+        for fn in (L.bertx_spindex_postings, L.bertx_spindex_capacity_postings):
+            fn.restype = ctypes.c_int64
+            fn.argtypes = [vp]
+        L.bertx_spindex_add_device.restype = c_i32
+        L.bertx_spindex_add_device.argtypes = [vp, vp, c_i32, vp]
+        L.bertx_spindex_add.restype = c_i32
+        L.bertx_spindex_add.argtypes = [vp, vp, c_i32]
+        L.bertx_spindex_add_postings.restype = c_i32
+        L.bertx_spindex_add_postings.argtypes = [vp, vp, vp, vp, c_i32]
+        L.bertx_spindex_add_texts.restype = c_i32
+        L.bertx_spindex_add_texts.argtypes = [vp, vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p)]
+        L.bertx_spindex_doc_len.restype = c_i32
+        L.bertx_spindex_doc_len.argtypes = [vp, c_i32]
+        L.bertx_spindex_doc.restype = c_i32
+        L.bertx_spindex_doc.argtypes = [vp, c_i32, vp, vp]
+        L.bertx_spindex_search_device.restype = c_i32
+        L.bertx_spindex_search_device.argtypes = [vp, vp, c_i32, c_i32, vp, vp, vp]
+        L.bertx_spindex_search.restype = c_i32
+        L.bertx_spindex_search.argtypes = [vp, vp, c_i32, c_i32, vp, vp]
+        L.bertx_spindex_search_texts.restype = c_i32
+        L.bertx_spindex_search_texts.argtypes = [vp, vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p), c_i32, vp, vp]
+        L.bertx_forward_sparse_top.restype = c_i32
+        L.bertx_forward_sparse_top.argtypes = [vp, c_i32, c_i32, ctypes.POINTER(c_i32p), c_i32p, c_i32, vp, vp, vp]
+        L.bertx_test_sparse_select.restype = c_i32
+        L.bertx_test_sparse_select.argtypes = [vp, c_i32, c_i32, c_i32, vp, vp, vp]
+        L.bertx_test_spindex_grid.restype = c_i32
+        L.bertx_test_spindex_grid.argtypes = [vp, c_i32]
+        L.bertx_bench_spindex.restype = c_i32
+        L.bertx_bench_spindex.argtypes = [c_i32] * 6 + [c_f32p]
+    except AttributeError:
+        pass
     L.bertx_bench_gemm.restype = c_i32
     L.bertx_bench_gemm.argtypes = [c_i32] * 7 + [c_f32p]
     L.bertx_bench_attention.restype = c_i32
@@ -609,6 +649,22 @@ class BertModel:
         if rc != 0:
             raise RuntimeError("bertx_forward_sparse failed (%d)" % rc)
         return out
+
+    def forward_sparse_top(self, ids_list, n, slot=0):
+        """The n largest term weights of every sentence, selected on the device (bert_hip.h
+        "Sparse index"): (terms int32 [len(ids_list)][n], weights f32 [..][n], counts int32 [..]); a
+        row's terms ascend, slots past its count hold (-1, 0).  Only these leave the device."""
+        m = len(ids_list)
+        arrs = [np.ascontiguousarray(a, np.int32) for a in ids_list]
+        lens = np.array([len(a) for a in arrs], np.int32)
+        tp = (c_i32p * m)(*[a.ctypes.data_as(c_i32p) for a in arrs])
+        terms, weights = np.zeros((m, n), np.int32), np.zeros((m, n), np.float32)
+        counts = np.zeros(m, np.int32)
+        rc = self.lib.bertx_forward_sparse_top(self.ctx, slot, m, tp, lens.ctypes.data_as(c_i32p), n, terms.ctypes.data,
+                                               weights.ctypes.data, counts.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("bertx_forward_sparse_top failed (%d)" % rc)
+        return terms, weights, counts
 
     def encode_sparse(self, texts, top=None):
         """Per text the (term id, weight) pairs with weight > 0 by descending weight (equal weights by
@@ -1358,6 +1414,99 @@ class BertTokenIndex:
 
 HEAD_NAMES = [("pooler.dense.weight", "dd"), ("pooler.dense.bias", "d"), ("classifier.weight", "cd"),
               ("classifier.bias", "c")]
+
+
+class BertSparseIndex:
+    """A device-resident index of sparse documents with a fused top-k search (bertx_spindex_*):
+    a document keeps the n_top largest of its sparse_width term weights as (term, f16 weight)
+    postings; ids are the insertion order.  bert_hip.h "Sparse index" gives the layout and the
+    arithmetic of a score."""
+
+    def __init__(self, model, capacity_docs, capacity_postings, n_top=256, slot=0, n_vocab=None):
+        self.model = model
+        self.lib = model.lib
+        self.n_vocab = int(n_vocab or model.sparse_width)
+        self.n_top = n_top
+        self.sp = self.lib.bertx_spindex_create(model.ctx, slot, self.n_vocab, n_top, capacity_docs, capacity_postings)
+        if not self.sp:
+            raise RuntimeError("bertx_spindex_create failed")
+
+    def __del__(self):
+        if getattr(self, "sp", None):
+            self.lib.bertx_spindex_free(self.sp)
+            self.sp = None
+
+    def __len__(self):
+        return int(self.lib.bertx_spindex_docs(self.sp))
+
+    def postings(self):
+        return int(self.lib.bertx_spindex_postings(self.sp))
+
+    def clear(self):
+        self.lib.bertx_spindex_clear(self.sp)
+
+    def _dense(self, a):
+        a = np.ascontiguousarray(np.asarray(a, np.float32))
+        if a.ndim == 1:
+            a = a[None, :]
+        if a.ndim != 2 or a.shape[1] != self.n_vocab:
+            raise ValueError("expected rows of %d terms, got shape %r" % (self.n_vocab, a.shape))
+        return a
+
+    @staticmethod
+    def _checked(rc, name):
+        if rc < 0:
+            raise RuntimeError("%s failed (%d)" % (name, rc))
+        return rc
+
+    def add(self, rows):
+        """Append dense f32 rows [n][n_vocab], selected and packed on the device; returns the first new id."""
+        a = self._dense(rows)
+        return self._checked(self.lib.bertx_spindex_add(self.sp, a.ctypes.data, a.shape[0]), "bertx_spindex_add")
+
+    def add_postings(self, docs):
+        """Append documents given as (terms, weights) pairs, terms ascending; returns the first new id."""
+        lens = np.array([len(t) for t, _ in docs], np.int32)
+        terms = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int32) for t, _ in docs] + [np.zeros(0, np.int32)]))
+        wts = np.ascontiguousarray(np.concatenate([np.asarray(w, np.float32) for _, w in docs] + [np.zeros(0, np.float32)]))
+        return self._checked(self.lib.bertx_spindex_add_postings(self.sp, terms.ctypes.data, wts.ctypes.data,
+                                                                 lens.ctypes.data, len(docs)), "bertx_spindex_add_postings")
+
+    def add_texts(self, texts):
+        return self._checked(self.lib.bertx_spindex_add_texts(self.sp, self.model.ctx, self.model.N_THREADS, len(texts),
+                                                              BertIndex._texts(texts)), "bertx_spindex_add_texts")
+
+    def doc(self, i):
+        """(terms int32 [len], weights f32 [len]) of document i, the weights as stored (f16 values)."""
+        terms, wts = np.zeros(self.n_top, np.int32), np.zeros(self.n_top, np.float32)
+        n = self._checked(self.lib.bertx_spindex_doc(self.sp, i, terms.ctypes.data, wts.ctypes.data), "bertx_spindex_doc")
+        return terms[:n].copy(), wts[:n].copy()
+
+    def search(self, queries, k):
+        """(scores f32 [B][k], ids int32 [B][k]); queries: dense [B][n_vocab] (or one row), or a list
+        of lists of (term, weight) pairs, densified here.  Any B: 64 queries per call of the library."""
+        if isinstance(queries, (list, tuple)) and len(queries) and isinstance(queries[0], (list, tuple)):
+            q = np.zeros((len(queries), self.n_vocab), np.float32)
+            for b, pairs in enumerate(queries):
+                for t, w in pairs:
+                    q[b, t] = w
+        else:
+            q = self._dense(queries)
+        B = q.shape[0]
+        scores, ids = np.zeros((B, k), np.float32), np.zeros((B, k), np.int32)
+        for b in range(0, B, 64):
+            m = min(64, B - b)
+            self._checked(-abs(self.lib.bertx_spindex_search(self.sp, q[b:].ctypes.data, m, k, scores[b:].ctypes.data,
+                                                             ids[b:].ctypes.data)), "bertx_spindex_search")
+        return scores, ids
+
+    def search_texts(self, texts, k):
+        n = len(texts)
+        scores, ids = np.zeros((n, k), np.float32), np.zeros((n, k), np.int32)
+        self._checked(-abs(self.lib.bertx_spindex_search_texts(self.sp, self.model.ctx, self.model.N_THREADS, n,
+                                                               BertIndex._texts(texts), k, scores.ctypes.data,
+                                                               ids.ctypes.data)), "bertx_spindex_search_texts")
+        return scores, ids
 
 
 def tensor_names(n_layer, head=False):

@@ -1326,3 +1326,96 @@ extern "C" int32_t bertx_bench_sparse(int32_t d, int32_t V, int32_t n_seqs, int3
         return -1;
     }
 }
+
+// Selection parity hook (bert_hip.h "Sparse index"): host buffers, device 0; the three
+// outputs start as NaN bits with guard rows of NaN bits behind them.
+extern "C" int32_t bertx_test_sparse_select(const float *rows, int32_t S, int32_t V, int32_t n, int32_t *terms,
+                                            float *weights, int32_t *count)
+{
+    using namespace emb;
+    if (!rows || !terms || !weights || !count || S < 1 || V < 1 || n < 1 || hip_device_count() == 0) return -1;
+    constexpr size_t GUARD = 16;   // rows of NaN bits behind the S rows of each output
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs B;
+    const float *dr = (const float *)B.up(rows, (size_t)S * V * 4, 0);
+    const size_t ob = (size_t)S * n * 4, gb = GUARD * n * 4, cb = (size_t)S * 4, cg = GUARD * 4;
+    int32_t *dt = (int32_t *)B.up_ff(nullptr, 0, ob + gb);
+    float *dw = (float *)B.up_ff(nullptr, 0, ob + gb);
+    int32_t *dc = (int32_t *)B.up_ff(nullptr, 0, cb + cg);
+    if (B.bad) return -1;
+    const int lrc = launch_sparse_select(dr, S, V, n, dt, dw, dc, nullptr);
+    if (const int rc = hook_finish()) return rc;
+    if (lrc != 0) return -1;
+    HIP_RC(hipMemcpy(terms, dt, ob, hipMemcpyDeviceToHost));
+    HIP_RC(hipMemcpy(weights, dw, ob, hipMemcpyDeviceToHost));
+    HIP_RC(hipMemcpy(count, dc, cb, hipMemcpyDeviceToHost));
+    std::vector<uint8_t> gd(2 * gb + cg);
+    HIP_RC(hipMemcpy(gd.data(), (char *)dt + ob, gb, hipMemcpyDeviceToHost));
+    HIP_RC(hipMemcpy(gd.data() + gb, (char *)dw + ob, gb, hipMemcpyDeviceToHost));
+    HIP_RC(hipMemcpy(gd.data() + 2 * gb, (char *)dc + cb, cg, hipMemcpyDeviceToHost));
+    for (const uint8_t v : gd) if (v != 0xffu) return -5;
+    return 0;
+}
+
+// Sparse index micro-benchmark (bert_hip.h): device 0, no context.  n_docs documents of
+// doc_len postings each, selected from dense rows of hashed values (launch_unit_rows: about
+// half of a row's V values are positive), 1,024 rows per chunk.  avg_us[0]: the selection of
+// one chunk; avg_us[1]: its pack and append; avg_us[2]: one search of B hashed queries.
+extern "C" int32_t bertx_bench_spindex(int32_t V, int32_t n_docs, int32_t doc_len, int32_t B, int32_t k, int32_t iters,
+                                       float *avg_us)
+{
+    using namespace emb;
+    if (V < 1 || V > 65536 || n_docs < 1 || doc_len < 1 || doc_len > 1024 || 2 * doc_len > V || B < 1 || B > 64 || k < 1 ||
+        k > 128 || iters < 1 || !avg_us || hip_device_count() == 0)
+        return -1;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    if (sparse_scan_prepare_device() != 0) return -1;
+    const int chunk = std::min<int>(kSparseAddRows, n_docs);
+    const size_t units = (size_t)n_docs * ((size_t)(doc_len + 15) / 16);
+    HookBufs H;
+    float *rows = (float *)H.up(nullptr, 0, (size_t)chunk * V * 4);
+    int32_t *terms = (int32_t *)H.up(nullptr, 0, (size_t)chunk * doc_len * 4), *count = (int32_t *)H.up(nullptr, 0, (size_t)chunk * 4);
+    float *wts = (float *)H.up(nullptr, 0, (size_t)chunk * doc_len * 4);
+    uint32_t *store = (uint32_t *)H.up(nullptr, 0, units * 64);
+    int32_t *table = (int32_t *)H.up(nullptr, 0, (size_t)n_docs * 8), *used = (int32_t *)H.up(nullptr, 0, 16);
+    float *q = (float *)H.up(nullptr, 0, (size_t)B * V * 4), *sc = (float *)H.up(nullptr, 0, (size_t)B * k * 4);
+    int32_t *ids = (int32_t *)H.up(nullptr, 0, (size_t)B * k * 4);
+    void *qtab = H.up(nullptr, 0, sparse_scan_table_bytes(V)), *part = H.up(nullptr, 0, sparse_scan_partial_bytes());
+    if (H.bad) return -1;
+    struct Str {
+        hipStream_t s = nullptr;
+        ~Str() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    } E;
+    HIP_RC(hipStreamCreateWithFlags(&E.s, hipStreamNonBlocking));
+    EventPair ev;
+    HIP_RC(ev.create());
+    auto select = [&](int m) { return launch_sparse_select(rows, m, V, doc_len, terms, wts, count, E.s); };
+    auto pack = [&](int m, int64_t first) { return launch_sparse_pack(terms, wts, count, m, doc_len, table + 2 * first, used, store, E.s); };
+    auto timed = [&](int stage, float *us) -> int {
+        for (int i = -3; i < iters; ++i) {
+            if (i == 0) HIP_RC(hipEventRecord(ev.a, E.s));
+            int rc = 0;
+            if (stage == 0) rc = select(chunk);
+            if (stage == 1) rc = hipMemsetAsync(used, 0, 4, E.s) == hipSuccess ? pack(chunk, 0) : -1;
+            if (stage == 2) rc = launch_sparse_scan(store, table, used, n_docs, V, q, B, k, qtab, part, sc, ids, E.s);
+            if (rc != 0) return -1;
+        }
+        HIP_RC(hipEventRecord(ev.b, E.s));
+        HIP_RC(hipEventSynchronize(ev.b));
+        float ms = 0.f;
+        HIP_RC(hipEventElapsedTime(&ms, ev.a, ev.b));
+        *us = ms * 1000.f / (float)iters;
+        return 0;
+    };
+    if (launch_unit_rows(rows, chunk, V, 777u, E.s) != 0 || launch_unit_rows(q, B, V, 4242u, E.s) != 0) return -1;
+    if (timed(0, &avg_us[0]) != 0 || timed(1, &avg_us[1]) != 0) return -1;
+    HIP_RC(hipMemsetAsync(used, 0, 4, E.s));
+    for (int64_t i = 0; i < n_docs; i += chunk) {
+        const int m = (int)std::min<int64_t>(chunk, n_docs - i);
+        if (launch_unit_rows(rows, m, V, 12345u + (uint32_t)i, E.s) != 0 || select(m) != 0 || pack(m, i) != 0) return -1;
+    }
+    if (timed(2, &avg_us[2]) != 0) return -1;
+    return hook_finish();
+}

@@ -465,6 +465,33 @@ int launch_sparse_transform(const uint16_t *z, const float2 *stats, const float 
 int launch_sparse_decoder(const uint16_t *h, int32_t T, int32_t d, const void *eimg, int32_t V, const float *bias,
                           const int32_t *cu, int32_t n_seqs, float *out, hipStream_t s);
 
+// ---- the sparse index (sparse_select.hip, sparse_scan.hip, spindex.cpp; the layout and the
+// arithmetic: bert_hip.h "Sparse index") ----
+// Per row of d_rows f32 [S][V] (non-negative) the min(n, weights > 0) terms of largest weight,
+// equal weights by ascending term, in ascending term: d_terms int32 [S][n], d_weights f32
+// [S][n] (the input's bits), d_count int32 [S]; slots past the count hold (-1, +0).  One
+// workgroup per row, no global atomics.  1 <= V <= 65536, 1 <= n <= 1024; -1 otherwise.
+int launch_sparse_select(const float *d_rows, int S, int V, int n, int32_t *d_terms, float *d_weights, int32_t *d_count,
+                         hipStream_t s);
+// The m <= kSparseAddRows documents a selection left in d_terms / d_weights / d_count, appended:
+// d_table (the first new document's entry) receives (first unit, postings) per document, the
+// units counted from d_used[0], which advances; the postings go to `store`, padded to units.
+constexpr int kSparseAddRows = 1024;
+int launch_sparse_pack(const int32_t *d_terms, const float *d_weights, const int32_t *d_count, int m, int n,
+                       void *d_table, int32_t *d_used, uint32_t *store, hipStream_t s);
+// The scan.  Queries of one pass (2 where two f16 tables of V terms fit in LDS beside the
+// lists, else 1), the bytes of the passes' tables (qtab) and of the workgroups' lists (partial).
+int sparse_scan_prepare_device();
+int sparse_scan_pair(int V, int k);
+size_t sparse_scan_table_bytes(int V);
+size_t sparse_scan_partial_bytes();
+// d_scores / d_ids [B][k]: per dense query f32 [V] the k best documents, launch_search's result
+// contract.  One table kernel, then per pass the scan and launch_search_merge.  max_wg, ran_wg
+// as on launch_maxsim.  1 <= B <= 64, 1 <= k <= 128; -1 otherwise, -3: launch refused.
+int launch_sparse_scan(const uint32_t *store, const void *d_table, const int32_t *d_used, int n_docs, int V,
+                       const float *d_queries, int B, int k, void *qtab, void *partial, float *d_scores, int32_t *d_ids,
+                       hipStream_t s, int max_wg = 0, int *ran_wg = nullptr);
+
 // Diagnostics: *cnt += number of non-finite values in p[0..n) (f32, or f16 if f16).
 void launch_count_nonfinite(const void *p, size_t n, int f16, unsigned *cnt, hipStream_t s);
 

@@ -1,0 +1,611 @@
+// The sparse index (bert_hip.h bertx_spindex_*): an append-only, device-
+// resident set of sparse documents and the fused top-k scan over it.  A document is a run
+// of postings (uint32 = term | f16 weight << 16, ascending term) padded to whole units of 16;
+// the documents lie contiguous in id order and a device table holds (first unit, postings)
+// per document.  Dense rows become documents on the device: top-n selection, f16 rounding,
+// padding and the offsets (a prefix sum of the counts the host never sees).  The host knows
+// the used units only as an upper bound and asks the device when the bound stops an add.
+// The ordering rules are the other two stores' (store_common.h).
+#include "bert.h"
+#include "bert_hip.h"
+
+#include "chunk_rule.h"
+#include "engine.h"
+#include "hip_check.h"
+#include "kernels.h"
+#include "store_common.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <vector>
+
+namespace {
+constexpr int kStage = 64;   // dense rows of the host forms' staging (an add chunk, a search's queries)
+}
+
+struct bertx_spindex {
+    int ordinal = 0;
+    int V = 0, n_top = 0;
+    int64_t cap_docs = 0, cap_units = 0;
+    int64_t n_docs = 0, used_bound = 0;    // used_bound >= the device's used units (d_used)
+    uint32_t *store = nullptr;             // cap_units * 16 postings
+    int32_t *table = nullptr;              // device: (first unit, postings) per document
+    int32_t *d_used = nullptr;             // device: the used units
+    // the selection's output for one chunk of kSparseAddRows rows
+    int32_t *sel_terms = nullptr, *sel_count = nullptr;
+    float *sel_weights = nullptr;
+    float *st_rows = nullptr;              // f32 [kStage][V]
+    float *st_scores = nullptr;            // [64][128]
+    int32_t *st_ids = nullptr;
+    void *qtab = nullptr, *partial = nullptr;
+    int grid_cap = 0, last_grid = 0;       // bertx_test_spindex_grid
+    hipStream_t stream = nullptr;
+    emb::StoreOrder ord;
+    std::mutex mu;
+    ~bertx_spindex()
+    {
+        emb::DeviceGuard g(ordinal);
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (ord.done) (void)ord.wait();
+        for (void *p : {(void *)store, (void *)table, (void *)d_used, (void *)sel_terms, (void *)sel_count,
+                        (void *)sel_weights, (void *)st_rows, (void *)st_scores, (void *)st_ids, qtab, partial})
+            if (p) (void)hipFree(p);
+        if (ord.done) (void)hipEventDestroy(ord.done);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace emb {
+namespace {
+
+int64_t units_of(int64_t postings) { return (postings + 15) / 16; }
+
+// The device's used units (the store locked, its device current); waits for the store.
+int32_t read_used(bertx_spindex &sp, int64_t *used)
+{
+    HIP_RC(sp.ord.wait());
+    int32_t u = 0;
+    HIP_RC(hipMemcpy(&u, sp.d_used, 4, hipMemcpyDeviceToHost));
+    *used = sp.used_bound = u;
+    return 0;
+}
+
+// Room for n more documents of at most `worst` units in all: by the bound, else by the
+// device's own count.
+int32_t room_for(bertx_spindex &sp, const char *who, int64_t n, int64_t worst)
+{
+    if (sp.n_docs + n > sp.cap_docs) {
+        errorf("%s: %lld documents do not fit (%lld of %lld used)\n", who, (long long)n, (long long)sp.n_docs,
+               (long long)sp.cap_docs);
+        return -2;
+    }
+    if (sp.used_bound + worst <= sp.cap_units) return 0;
+    int64_t used = 0;
+    if (const int32_t rc = read_used(sp, &used)) return rc;
+    if (used + worst <= sp.cap_units) return 0;
+    errorf("%s: up to %lld postings do not fit (%lld of %lld used)\n", who, (long long)worst * 16, (long long)used * 16,
+           (long long)sp.cap_units * 16);
+    return -2;
+}
+
+// n dense rows on the device -> documents n_docs .. n_docs + n - 1, on s.  Returns the first new id.
+int32_t add_device_locked(bertx_spindex &sp, const float *d_rows, int32_t n, hipStream_t s, const char *who)
+{
+    if (!d_rows || n < 1) return -1;
+    const int64_t worst = (int64_t)n * units_of(sp.n_top);
+    if (const int32_t rc = room_for(sp, who, n, worst)) return rc;
+    int rc = 0;
+    {
+        Ordered o(sp.ord, s);
+        for (int32_t i = 0; i < n && rc == 0; i += kSparseAddRows) {
+            const int m = std::min<int32_t>(kSparseAddRows, n - i);
+            rc = launch_sparse_select(d_rows + (size_t)i * sp.V, m, sp.V, sp.n_top, sp.sel_terms, sp.sel_weights,
+                                      sp.sel_count, s);
+            if (rc == 0)
+                rc = launch_sparse_pack(sp.sel_terms, sp.sel_weights, sp.sel_count, m, sp.n_top,
+                                        sp.table + 2 * (size_t)(sp.n_docs + i), sp.d_used, sp.store, s);
+        }
+    }
+    if (rc != 0) {
+        errorf("%s: device %d refused a launch (%d)\n", who, sp.ordinal, rc);
+        return rc;
+    }
+    const int32_t first = (int32_t)sp.n_docs;
+    sp.n_docs += n;
+    sp.used_bound += worst;
+    return first;
+}
+
+int32_t search_device_locked(bertx_spindex &sp, const float *d_q, int32_t B, int32_t k, float *d_scores, int32_t *d_ids,
+                             hipStream_t s)
+{
+    if (!d_q || !d_scores || !d_ids || B < 1 || B > 64 || k < 1 || k > 128) {
+        errorf("bertx_spindex_search: B = %d, k = %d are not in 1 <= B <= 64, 1 <= k <= 128\n", B, k);
+        return -1;
+    }
+    Ordered o(sp.ord, s);
+    return launch_sparse_scan(sp.store, sp.table, sp.d_used, (int)sp.n_docs, sp.V, d_q, B, k, sp.qtab, sp.partial, d_scores,
+                              d_ids, s, sp.grid_cap, &sp.last_grid);
+}
+
+// B dense queries on the device, on the store's stream -> host results.
+int32_t search_to_host(bertx_spindex &sp, const float *d_q, int32_t B, int32_t k, float *scores, int32_t *ids)
+{
+    const int32_t rc = search_device_locked(sp, d_q, B, k, sp.st_scores, sp.st_ids, sp.stream);
+    if (rc != 0) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(sp.stream);
+        return rc;
+    }
+    HIP_RC(hipMemcpyAsync(scores, sp.st_scores, (size_t)B * k * 4, hipMemcpyDeviceToHost, sp.stream));
+    HIP_RC(hipMemcpyAsync(ids, sp.st_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, sp.stream));
+    HIP_RC(hipStreamSynchronize(sp.stream));
+    return 0;
+}
+
+// The refusals of the text forms: -6 a file without the MLM records, -1 another vocabulary or
+// no replica on the store's device.
+int32_t text_ctx_ok(bertx_spindex *sp, struct bert_ctx *ctx, const char *who, int32_t *slot)
+{
+    if (!sp || !ctx) return -1;
+    if (bertx_sparse_width(ctx) <= 0) {
+        errorf("%s: this model file has no masked-LM head (cls.predictions.*)\n", who);
+        return -6;
+    }
+    if (bertx_num_devices(ctx) == 0 || bertx_sparse_width(ctx) != sp->V) {
+        errorf("%s: the context gives rows of %d terms, the store holds %d\n", who, bertx_sparse_width(ctx), sp->V);
+        return -1;
+    }
+    for (int32_t s = 0; s < bertx_num_devices(ctx); ++s)
+        if (bertx_device_ordinal(ctx, s) == sp->ordinal) {
+            *slot = s;
+            return 0;
+        }
+    errorf("%s: the context has no replica on the store's device %d\n", who, sp->ordinal);
+    return -1;
+}
+
+struct Texts {
+    std::vector<int32_t> ids, lens;
+    size_t stride = 0;
+};
+
+int32_t tokenize(struct bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts, Texts &t)
+{
+    t.stride = (size_t)bert_n_max_tokens(ctx);
+    t.ids.resize((size_t)n * t.stride);
+    t.lens.resize((size_t)n);
+    return bertx_tokenize_batch(ctx, n_threads, n, texts, (int32_t)t.stride, t.ids.data(), t.lens.data()) != 0 ? -1 : 0;
+}
+
+// Texts i0 .. i1 - 1 (at most kStage) through one sparse forward on `stream` into d_out f32
+// [i1 - i0][n_vocab]; d_tok: the call's device buffer of ids and offsets, grown as needed.
+int32_t forward_chunk(hipStream_t stream, float *d_out, struct bert_ctx *ctx, int32_t slot, const Texts &t, size_t i0,
+                      size_t i1, std::vector<int32_t> &flat, DevBuf &d_tok, size_t *cap)
+{
+    flat.clear();
+    std::vector<int32_t> cu(1, 0);
+    int32_t max_len = 0;
+    for (size_t i = i0; i < i1; ++i) {
+        const int32_t *p = t.ids.data() + i * t.stride, len = t.lens[i];
+        flat.insert(flat.end(), p, p + len);
+        cu.push_back((int32_t)flat.size());
+        max_len = std::max(max_len, len);
+    }
+    const size_t tok = flat.size(), seqs = i1 - i0;
+    flat.insert(flat.end(), cu.begin(), cu.end());
+    if (flat.size() > *cap) {
+        if (d_tok.p) {
+            HIP_RC(hipStreamSynchronize(stream));
+            (void)hipFree(d_tok.p);
+            d_tok.p = nullptr;
+        }
+        HIP_RC(hipMalloc(&d_tok.p, flat.size() * 4));
+        *cap = flat.size();
+    }
+    if (bertx_reserve(ctx, slot, (int32_t)tok, (int32_t)seqs) != 0) return -1;
+    HIP_RC(hipMemcpyAsync(d_tok.p, flat.data(), flat.size() * 4, hipMemcpyHostToDevice, stream));
+    HIP_RC(hipStreamSynchronize(stream));   // flat is pageable and reused
+    const int32_t *d = (const int32_t *)d_tok.p;
+    return bertx_forward_sparse_device(ctx, slot, d, nullptr, d + tok, (int32_t)seqs, max_len, (int32_t)tok, d_out,
+                                       stream);
+}
+
+bertx_spindex *spindex_create_on(int ordinal, int V, int n_top, int64_t cap_docs, int64_t cap_postings)
+{
+    if (V < 1 || V > 65536 || n_top < 1 || n_top > 1024) {
+        errorf("bertx_spindex_create: n_vocab %d / n_top %d are not in 1 .. 65536 / 1 .. 1024\n", V, n_top);
+        return nullptr;
+    }
+    if (cap_docs < 1 || cap_docs > 0x7ffffff0ll || cap_postings < 16 || cap_postings > (0x7ffffff0ll << 4)) {
+        errorf("bertx_spindex_create: capacity of %lld documents / %lld postings is not in 1 .. 2^31 - 16 / "
+               "16 .. 2^35 - 256\n", (long long)cap_docs, (long long)cap_postings);
+        return nullptr;
+    }
+    DeviceGuard g(ordinal);
+    if (!g.ok()) {
+        errorf("bertx_spindex_create: cannot select device %d\n", ordinal);
+        return nullptr;
+    }
+    bertx_spindex *sp = new (std::nothrow) bertx_spindex();
+    if (!sp) return nullptr;
+    sp->ordinal = ordinal;
+    sp->V = V;
+    sp->n_top = n_top;
+    sp->cap_docs = cap_docs;
+    sp->cap_units = units_of(cap_postings);
+    const size_t sel = (size_t)kSparseAddRows * n_top * 4;
+    const bool ok = sparse_scan_prepare_device() == 0 &&
+                    hipStreamCreateWithFlags(&sp->stream, hipStreamNonBlocking) == hipSuccess &&
+                    hipEventCreateWithFlags(&sp->ord.done, hipEventDisableTiming) == hipSuccess &&
+                    hipMalloc((void **)&sp->store, (size_t)sp->cap_units * 64) == hipSuccess &&
+                    hipMalloc((void **)&sp->table, (size_t)cap_docs * 8) == hipSuccess &&
+                    hipMalloc((void **)&sp->d_used, 16) == hipSuccess &&
+                    hipMalloc((void **)&sp->sel_terms, sel) == hipSuccess &&
+                    hipMalloc((void **)&sp->sel_weights, sel) == hipSuccess &&
+                    hipMalloc((void **)&sp->sel_count, (size_t)kSparseAddRows * 4) == hipSuccess &&
+                    hipMalloc((void **)&sp->st_rows, (size_t)kStage * V * 4) == hipSuccess &&
+                    hipMalloc((void **)&sp->st_scores, 64 * 128 * 4) == hipSuccess &&
+                    hipMalloc((void **)&sp->st_ids, 64 * 128 * 4) == hipSuccess &&
+                    hipMalloc(&sp->qtab, sparse_scan_table_bytes(V)) == hipSuccess &&
+                    hipMalloc(&sp->partial, sparse_scan_partial_bytes()) == hipSuccess &&
+                    hipMemsetAsync(sp->d_used, 0, 16, sp->stream) == hipSuccess &&
+                    hipStreamSynchronize(sp->stream) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        errorf("bertx_spindex_create: device %d could not allocate %zu bytes of postings (+ %lld table entries)\n", ordinal,
+               (size_t)sp->cap_units * 64, (long long)cap_docs);
+        delete sp;
+        return nullptr;
+    }
+    return sp;
+}
+
+}  // namespace
+}  // namespace emb
+
+using emb::DeviceGuard;
+
+extern "C" {
+
+struct bertx_spindex *bertx_spindex_create(struct bert_ctx *ctx, int32_t slot, int32_t n_vocab, int32_t n_top,
+                                           int32_t capacity_docs, int64_t capacity_postings)
+{
+    if (!ctx || bertx_num_devices(ctx) == 0) {
+        emb::errorf("bertx_spindex_create: no context with a device to hold a sparse index\n");
+        return nullptr;
+    }
+    const int ordinal = bertx_device_ordinal(ctx, slot);
+    if (ordinal < 0) {
+        emb::errorf("bertx_spindex_create: slot %d is not one of the context's %d device(s)\n", slot,
+                    bertx_num_devices(ctx));
+        return nullptr;
+    }
+    return emb::spindex_create_on(ordinal, n_vocab, n_top, capacity_docs, capacity_postings);
+}
+
+void bertx_spindex_free(struct bertx_spindex *sp) { delete sp; }
+
+int32_t bertx_spindex_clear(struct bertx_spindex *sp)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    {
+        emb::Ordered o(sp->ord, sp->stream);
+        HIP_RC(hipMemsetAsync(sp->d_used, 0, 4, sp->stream));
+    }
+    sp->n_docs = 0;
+    sp->used_bound = 0;
+    return 0;
+}
+
+int32_t bertx_spindex_docs(struct bertx_spindex *sp)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    return (int32_t)sp->n_docs;
+}
+
+int64_t bertx_spindex_postings(struct bertx_spindex *sp)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    int64_t used = 0;
+    if (emb::read_used(*sp, &used) != 0) return -1;
+    return used * 16;
+}
+
+int32_t bertx_spindex_capacity_docs(struct bertx_spindex *sp) { return sp ? (int32_t)sp->cap_docs : -1; }
+int64_t bertx_spindex_capacity_postings(struct bertx_spindex *sp) { return sp ? sp->cap_units * 16 : -1; }
+int32_t bertx_spindex_vocab(struct bertx_spindex *sp) { return sp ? sp->V : -1; }
+int32_t bertx_spindex_top(struct bertx_spindex *sp) { return sp ? sp->n_top : -1; }
+
+int32_t bertx_spindex_add_device(struct bertx_spindex *sp, const float *d_rows, int32_t n, void *stream)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    return emb::add_device_locked(*sp, d_rows, n, stream ? (hipStream_t)stream : sp->stream, "bertx_spindex_add_device");
+}
+
+int32_t bertx_spindex_add(struct bertx_spindex *sp, const float *rows, int32_t n)
+{
+    if (!sp || !rows || n < 1) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    if (const int32_t rc = emb::room_for(*sp, "bertx_spindex_add", n, (int64_t)n * emb::units_of(sp->n_top))) return rc;
+    const int32_t first = (int32_t)sp->n_docs;
+    for (int32_t i = 0; i < n; i += kStage) {
+        const int32_t m = std::min<int32_t>(kStage, n - i);
+        {
+            emb::Ordered o(sp->ord, sp->stream);
+            HIP_RC(hipMemcpyAsync(sp->st_rows, rows + (size_t)i * sp->V, (size_t)m * sp->V * 4, hipMemcpyHostToDevice,
+                                  sp->stream));
+        }
+        const int32_t rc = emb::add_device_locked(*sp, sp->st_rows, m, sp->stream, "bertx_spindex_add");
+        if (hipStreamSynchronize(sp->stream) != hipSuccess || rc < 0) {   // the staging buffer is reused
+            (void)hipGetLastError();
+            return rc < 0 ? rc : -1;
+        }
+    }
+    return first;
+}
+
+int32_t bertx_spindex_add_postings(struct bertx_spindex *sp, const int32_t *terms, const float *weights,
+                                   const int32_t *lens, int32_t n)
+{
+    if (!sp || !lens || n < 1) return -1;
+    int64_t total = 0, units = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        if (lens[i] < 0 || lens[i] > sp->n_top) {
+            emb::errorf("bertx_spindex_add_postings: document %d has %d postings, not 0 .. n_top = %d\n", i, lens[i], sp->n_top);
+            return -1;
+        }
+        total += lens[i];
+        units += emb::units_of(lens[i]);
+    }
+    if (total > 0 && (!terms || !weights)) return -1;
+    // the postings as the device packs them
+    std::vector<uint32_t> img((size_t)units * 16, 0u);
+    std::vector<int32_t> tab((size_t)n * 2);
+    int64_t j0 = 0, u0 = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        for (int32_t j = 0; j < lens[i]; ++j) {
+            const int32_t t = terms[j0 + j];
+            const float w = weights[j0 + j];
+            const uint16_t h = std::isfinite(w) && w >= 0.f ? emb::f32_to_f16(w) : (uint16_t)0x7c00;
+            if (t < 0 || t >= sp->V || (j > 0 && t <= terms[j0 + j - 1]) || h >= 0x7c00) {
+                emb::errorf("bertx_spindex_add_postings: document %d, posting %d: terms ascend without repeats below "
+                            "n_vocab = %d, weights are finite in f16 and not negative\n", i, j, sp->V);
+                return -1;
+            }
+            img[(size_t)u0 * 16 + (size_t)j] = (uint32_t)t | (uint32_t)h << 16;
+        }
+        tab[2 * (size_t)i] = (int32_t)u0;   // relative to the call's first unit
+        tab[2 * (size_t)i + 1] = lens[i];
+        j0 += lens[i];
+        u0 += emb::units_of(lens[i]);
+    }
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    if (const int32_t rc = emb::room_for(*sp, "bertx_spindex_add_postings", n, units)) return rc;
+    int64_t used = 0;
+    if (emb::read_used(*sp, &used) != 0) return -1;   // a host form: the exact offset, read from the device
+    for (int32_t i = 0; i < n; ++i) tab[2 * (size_t)i] += (int32_t)used;
+    const int32_t new_used = (int32_t)(used + units);
+    {
+        emb::Ordered o(sp->ord, sp->stream);
+        if (units) HIP_RC(hipMemcpyAsync(sp->store + (size_t)used * 16, img.data(), img.size() * 4, hipMemcpyHostToDevice, sp->stream));
+        HIP_RC(hipMemcpyAsync(sp->table + 2 * (size_t)sp->n_docs, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, sp->stream));
+        HIP_RC(hipMemcpyAsync(sp->d_used, &new_used, 4, hipMemcpyHostToDevice, sp->stream));
+    }
+    HIP_RC(hipStreamSynchronize(sp->stream));   // the images are pageable and leave scope
+    const int32_t first = (int32_t)sp->n_docs;
+    sp->n_docs += n;
+    sp->used_bound = new_used;
+    return first;
+}
+
+int32_t bertx_spindex_doc_len(struct bertx_spindex *sp, int32_t id)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (id < 0 || id >= sp->n_docs) return -1;
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    HIP_RC(sp->ord.wait());
+    int32_t e[2] = {0, 0};
+    HIP_RC(hipMemcpy(e, sp->table + 2 * (size_t)id, 8, hipMemcpyDeviceToHost));
+    return e[1];
+}
+
+int32_t bertx_spindex_doc(struct bertx_spindex *sp, int32_t id, int32_t *terms, float *weights)
+{
+    if (!sp || !terms || !weights) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (id < 0 || id >= sp->n_docs) return -1;
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    HIP_RC(sp->ord.wait());
+    int32_t e[2] = {0, 0};
+    HIP_RC(hipMemcpy(e, sp->table + 2 * (size_t)id, 8, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> p((size_t)e[1]);
+    if (e[1]) HIP_RC(hipMemcpy(p.data(), sp->store + (size_t)e[0] * 16, p.size() * 4, hipMemcpyDeviceToHost));
+    for (int32_t j = 0; j < e[1]; ++j) {
+        terms[j] = (int32_t)(p[(size_t)j] & 0xffffu);
+        weights[j] = emb::f16_to_f32((uint16_t)(p[(size_t)j] >> 16));
+    }
+    return e[1];
+}
+
+int32_t bertx_spindex_search_device(struct bertx_spindex *sp, const float *d_queries, int32_t B, int32_t k, float *d_scores,
+                                    int32_t *d_ids, void *stream)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    return emb::search_device_locked(*sp, d_queries, B, k, d_scores, d_ids, stream ? (hipStream_t)stream : sp->stream);
+}
+
+int32_t bertx_spindex_search(struct bertx_spindex *sp, const float *queries, int32_t B, int32_t k, float *scores,
+                             int32_t *ids)
+{
+    if (!sp || !queries || !scores || !ids || B < 1 || B > kStage) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    {
+        emb::Ordered o(sp->ord, sp->stream);
+        HIP_RC(hipMemcpyAsync(sp->st_rows, queries, (size_t)B * sp->V * 4, hipMemcpyHostToDevice, sp->stream));
+    }
+    HIP_RC(hipStreamSynchronize(sp->stream));   // the caller's rows are pageable
+    return emb::search_to_host(*sp, sp->st_rows, B, k, scores, ids);
+}
+
+int32_t bertx_spindex_add_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                const char **texts)
+{
+    int32_t slot = -1;
+    if (const int32_t rc = emb::text_ctx_ok(sp, ctx, "bertx_spindex_add_texts", &slot)) return rc;
+    if (!texts || n < 1) return -1;
+    emb::Texts t;
+    if (emb::tokenize(ctx, n_threads, n, texts, t) != 0) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    if (const int32_t rc = emb::room_for(*sp, "bertx_spindex_add_texts", n, (int64_t)n * emb::units_of(sp->n_top))) return rc;
+    const int32_t first = (int32_t)sp->n_docs;
+    std::vector<int32_t> flat;
+    emb::DevBuf d_tok;
+    size_t cap = 0;
+    for (size_t i = 0; i < (size_t)n;) {
+        const size_t e = emb::chunk_end([&](size_t j) { return t.lens[j]; }, i, (size_t)n, emb::kChunkTokens, kStage);
+        int32_t rc = 0;
+        {
+            emb::Ordered o(sp->ord, sp->stream);
+            rc = emb::forward_chunk(sp->stream, sp->st_rows, ctx, slot, t, i, e, flat, d_tok, &cap);
+        }
+        if (rc == 0) rc = emb::add_device_locked(*sp, sp->st_rows, (int32_t)(e - i), sp->stream, "bertx_spindex_add_texts");
+        if (hipStreamSynchronize(sp->stream) != hipSuccess || rc < 0) {   // st_rows is reused by the next chunk
+            (void)hipGetLastError();
+            emb::errorf("bertx_spindex_add_texts: device %d failed while adding (%d)\n", sp->ordinal, rc);
+            return rc < 0 ? rc : -1;
+        }
+        i = e;
+    }
+    return first;
+}
+
+int32_t bertx_spindex_search_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                   const char **texts, int32_t k, float *scores, int32_t *ids)
+{
+    int32_t slot = -1;
+    if (const int32_t rc = emb::text_ctx_ok(sp, ctx, "bertx_spindex_search_texts", &slot)) return rc;
+    if (!texts || !scores || !ids || n < 1 || k < 1 || k > 128) return -1;
+    emb::Texts t;
+    if (emb::tokenize(ctx, n_threads, n, texts, t) != 0) return -1;
+    std::vector<float> hs((size_t)n * k);
+    std::vector<int32_t> hi((size_t)n * k);
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    std::vector<int32_t> flat;
+    emb::DevBuf d_tok;
+    size_t cap = 0;
+    for (size_t i = 0; i < (size_t)n;) {
+        const size_t e = emb::chunk_end([&](size_t j) { return t.lens[j]; }, i, (size_t)n, emb::kChunkTokens, kStage);
+        int32_t rc = 0;
+        {
+            emb::Ordered o(sp->ord, sp->stream);
+            rc = emb::forward_chunk(sp->stream, sp->st_rows, ctx, slot, t, i, e, flat, d_tok, &cap);
+        }
+        if (rc == 0) rc = emb::search_to_host(*sp, sp->st_rows, (int32_t)(e - i), k, hs.data() + i * k, hi.data() + i * k);
+        if (rc != 0) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(sp->stream);
+            return rc < 0 ? rc : -1;
+        }
+        i = e;
+    }
+    std::memcpy(scores, hs.data(), hs.size() * 4);
+    std::memcpy(ids, hi.data(), hi.size() * 4);
+    return 0;
+}
+
+int32_t bertx_forward_sparse_top(struct bert_ctx *ctx, int32_t slot, int32_t n, bert_vocab_id **batch_tokens,
+                                 int32_t *n_tokens, int32_t n_top, int32_t *terms, float *weights, int32_t *counts)
+{
+    if (!ctx || !batch_tokens || !n_tokens || !terms || !weights || !counts || n < 1 || n_top < 1 || n_top > 1024) return -1;
+    const int32_t V = bertx_sparse_width(ctx);
+    if (V <= 0) {
+        emb::errorf("bertx_forward_sparse_top: this model file has no masked-LM head (cls.predictions.*)\n");
+        return -6;
+    }
+    const int ordinal = bertx_num_devices(ctx) > 0 ? bertx_device_ordinal(ctx, slot) : -1;
+    if (ordinal < 0 || V > 65536) return -1;
+    emb::Texts t;
+    t.lens.assign(n_tokens, n_tokens + n);
+    for (int32_t i = 0; i < n; ++i) {
+        if (n_tokens[i] < 1 || n_tokens[i] > bert_n_max_tokens(ctx)) return -1;
+        t.stride = std::max(t.stride, (size_t)n_tokens[i]);
+    }
+    t.ids.assign((size_t)n * t.stride, 0);
+    for (int32_t i = 0; i < n; ++i) std::memcpy(t.ids.data() + (size_t)i * t.stride, batch_tokens[i], (size_t)n_tokens[i] * 4);
+    DeviceGuard g(ordinal);
+    HIP_RC(g.status());
+    struct Str {
+        hipStream_t s = nullptr;
+        ~Str() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    } S;
+    HIP_RC(hipStreamCreateWithFlags(&S.s, hipStreamNonBlocking));
+    emb::DevBuf d_tok, d_rows, d_t, d_w, d_c;
+    HIP_RC(hipMalloc(&d_rows.p, (size_t)kStage * V * 4));
+    HIP_RC(hipMalloc(&d_t.p, (size_t)kStage * n_top * 4));
+    HIP_RC(hipMalloc(&d_w.p, (size_t)kStage * n_top * 4));
+    HIP_RC(hipMalloc(&d_c.p, (size_t)kStage * 4));
+    std::vector<int32_t> flat;
+    size_t cap = 0;
+    for (size_t i = 0; i < (size_t)n;) {
+        const size_t e = emb::chunk_end([&](size_t j) { return t.lens[j]; }, i, (size_t)n, emb::kChunkTokens, kStage);
+        const int m = (int)(e - i);
+        int32_t rc = emb::forward_chunk(S.s, (float *)d_rows.p, ctx, slot, t, i, e, flat, d_tok, &cap);
+        if (rc == 0)
+            rc = emb::launch_sparse_select((const float *)d_rows.p, m, V, n_top, (int32_t *)d_t.p, (float *)d_w.p,
+                                           (int32_t *)d_c.p, S.s);
+        if (rc != 0) return rc < 0 ? rc : -1;
+        HIP_RC(hipMemcpyAsync(terms + i * n_top, d_t.p, (size_t)m * n_top * 4, hipMemcpyDeviceToHost, S.s));
+        HIP_RC(hipMemcpyAsync(weights + i * n_top, d_w.p, (size_t)m * n_top * 4, hipMemcpyDeviceToHost, S.s));
+        HIP_RC(hipMemcpyAsync(counts + i, d_c.p, (size_t)m * 4, hipMemcpyDeviceToHost, S.s));
+        HIP_RC(hipStreamSynchronize(S.s));
+        i = e;
+    }
+    return 0;
+}
+
+int32_t bertx_test_spindex_grid(struct bertx_spindex *sp, int32_t max_wg)
+{
+    if (!sp || max_wg < 0) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    sp->grid_cap = max_wg;
+    return 0;
+}
+
+int32_t bertx_test_spindex_last_grid(struct bertx_spindex *sp)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    return sp->last_grid;
+}
+
+}  // extern "C"

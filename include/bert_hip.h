@@ -1397,9 +1397,9 @@ BERT_API int32_t bertx_bench_attention_kv(int32_t n_seqs, int32_t len, int32_t n
  * data; avg_us[0] the transform's, avg_us[1] the decoder's average device time over
  * `iters` launches after 3 warm-up launches.
  *
- * Not provided: an inverted index or a sparse search (the rows leave the library dense),
- * untied decoders, the `search` tool, RoBERTa / XLM-R vocabularies (bge-m3's sparse
- * head), top-n selection on the device.
+ * Not provided: untied decoders, the `search` tool, RoBERTa / XLM-R vocabularies (bge-m3's
+ * sparse head).  Searching the rows and top-n selection on the device: "Sparse index" below
+ * (a document-major scan of stored postings, not inverted lists).
  */
 enum { BERTX_OUT_SPARSE = 4 };
 BERT_API int32_t bertx_convert_hf_mlm(const char *dir_model, const char *fname_out, int32_t ftype);
@@ -1414,6 +1414,121 @@ BERT_API int32_t bertx_test_sparse(int32_t mode, const float *x, int32_t T, int3
                                    int32_t V, const float *b, const int32_t *cu, int32_t n_seqs, void *out,
                                    int32_t out_rows);
 BERT_API int32_t bertx_bench_sparse(int32_t d, int32_t V, int32_t n_seqs, int32_t len, int32_t iters, float *avg_us);
+
+/*
+ * Sparse index: a device-resident, append-only store of sparse documents and a fused
+ * top-k search over it; the sparse counterpart of bertx_index_* and bertx_mvindex_*.
+ *
+ * bertx_spindex_create(ctx, slot, n_vocab, n_top, capacity_docs, capacity_postings): a store
+ * on the replica's device for rows of n_vocab terms (1 .. 65,536) of which a document keeps
+ * at most n_top (1 .. 1,024).  NULL with a message on bad arguments or a failed allocation.
+ *
+ * Layout.  A document is a run of postings, one uint32 each: the term id in the low 16
+ * bits, the weight's f16 bits (round to nearest even) in the high 16; ascending term, padded
+ * with (term 0, +0) to a multiple of 16 postings (64 B).  Documents lie one behind the other
+ * in the order of arrival, which is their id; a second device array holds (first unit of 16
+ * postings, posting count) per document.  A document with no positive weight has count 0.
+ * 4 bytes per posting: a 128-term document takes 512 B.
+ *
+ * Selection (bertx_spindex_add_device / _add / _add_texts; bertx_test_sparse_select).  Dense
+ * f32 rows [n][n_vocab] of non-negative weights, BERTX_OUT_SPARSE's output.  Per row the
+ * min(n_top, number of weights > 0) terms of largest weight, equal weights by ascending
+ * term id, kept in ascending term id.  Exact: non-negative floats order as their unsigned
+ * bits, and a radix select over the bits (11 + 11 + 10) finds the threshold; -0, negative
+ * values and NaNs with the sign bit set count as "not > 0".  Selection, f16 rounding, padding
+ * and the document offsets (a prefix sum of the counts) all run on the device: the host never
+ * sees the counts, checks the capacity by the worst case of n * ceil16(n_top) postings
+ * against an upper bound of the used postings, and asks the device for the exact figure
+ * (a synchronisation) only when the bound refuses.  Weights of 65,520 and above would round
+ * to f16 infinity: the caller keeps them below (log1p outputs are).  _add_device is
+ * asynchronous on `stream` (NULL: the store's); all adds return the first new id, -2 when
+ * the documents or the postings do not fit, -1 on other errors.
+ * bertx_spindex_add_postings: n documents encoded elsewhere, document i's lens[i] (term,
+ * weight) pairs consecutive in terms / weights.  Refused (-1, nothing added): terms not
+ * strictly ascending, a term >= n_vocab, a weight that is negative, not finite or not finite
+ * as f16, lens[i] > n_top.  Stores the f16 rounding of what it is given.
+ * bertx_spindex_add_texts: tokenizes, runs the sparse forward into a device buffer on the
+ * store's stream, 64 texts per forward, and adds from there; -6 on a file without the MLM
+ * records, -1 when the context's n_vocab is not the store's or it has no replica on the
+ * store's device.
+ * bertx_forward_sparse_top(ctx, slot, n, batch_tokens, n_tokens, n_top, terms, weights,
+ * counts): the sparse forward of n tokenized sentences on replica `slot` followed by the
+ * selection, without a store; only terms int32 [n][n_top], weights f32 [n][n_top] (the
+ * forward's bits) and counts int32 [n] leave the device, slots past a count (-1, +0).
+ * -6 on a file without the MLM records.
+ * _doc_len(id): the posting count; _doc(id, terms, weights): the postings, weights as the f32
+ * value of the stored f16, returns the count (the buffers hold at least _top entries).
+ * _postings: the used postings, padding included (asks the device).  _clear empties the store.
+ *
+ * Search.  bertx_spindex_search_device(sp, d_queries, B, k, d_scores, d_ids, stream): dense
+ * f32 queries [B][n_vocab], 1 <= B <= 64, 1 <= k <= 128; d_scores f32 [B][k], d_ids int32
+ * [B][k]: per query the k best documents, higher score first, equal scores by ascending id,
+ * (-inf, -1) where the store has fewer than k documents (bertx_index_search's result
+ * contract).  Asynchronous, capturable, allocates nothing.  bertx_spindex_search is the host
+ * form, bertx_spindex_search_texts the text form (any n; refusals as _add_texts).
+ * Arithmetic of one (query, document) score, every operation f32, round to nearest even:
+ *   qh[v]  = f16(q[v])
+ *   s_l    = sum over the document's postings j with j mod 16 == l, in ascending j, from +0,
+ *            of qh[term_j] * w_j      (w_j the stored f16; the product is exact in f32)
+ *   score  = the 16 sub-sums folded 8, 4, 2, 1 apart: t_l = s_l + s_(l + 8) for l < 8,
+ *            u_l = t_l + t_(l + 4) for l < 4, v_l = u_l + u_(l + 2) for l < 2, v_0 + v_1
+ * The order depends on the document's posting count alone: not on its id, its place in the
+ * store, the batch, k or B.  Padding postings add qh[0] * +0, which changes no bit for
+ * finite queries; queries with non-finite values are outside the contract.  A document of
+ * count 0 scores +0.
+ * The scan is document-major: it streams every stored posting once per pass of two queries
+ * (one where n_vocab is too large for two f16 tables in LDS), keeps the k best in LDS and
+ * merges the workgroups' lists; B > 2 is a sequence of passes.
+ *
+ * bertx_test_sparse_select (parity hook; host buffers, device 0): rows f32 [S][V] ->
+ * terms int32 [S][n], weights f32 [S][n] (the input's bits), count int32 [S]; slots past a
+ * row's count hold (-1, +0).  Guard rows of NaN bits lie behind the three device outputs;
+ * -5: one was written.  bertx_test_spindex_grid(sp, max_wg): max_wg > 0 bounds the scan's
+ * workgroups (the tests' way to many documents per wave), 0 lifts the bound;
+ * bertx_test_spindex_last_grid: the workgroups of the latest scan.
+ * bertx_bench_spindex (device 0, no context): n_docs documents of doc_len postings selected
+ * from dense rows of hashed values; avg_us[0] the selection of 1,024 rows (fewer if n_docs
+ * is), avg_us[1] their pack and append, avg_us[2] one search of B hashed queries; averages
+ * of `iters` launches after 3 warm-up launches.
+ *
+ * Not provided: inverted lists and any dynamic pruning (WAND, block-max); int8 or impact-
+ * quantized weights; deletion and filters; scoring listed ids; a mode of the `search` tool;
+ * saving and loading; vocabularies above 65,536 terms.
+ */
+struct bertx_spindex;
+BERT_API struct bertx_spindex *bertx_spindex_create(struct bert_ctx *ctx, int32_t slot, int32_t n_vocab, int32_t n_top,
+                                                    int32_t capacity_docs, int64_t capacity_postings);
+BERT_API void bertx_spindex_free(struct bertx_spindex *sp);
+BERT_API int32_t bertx_spindex_clear(struct bertx_spindex *sp);
+BERT_API int32_t bertx_spindex_docs(struct bertx_spindex *sp);
+BERT_API int64_t bertx_spindex_postings(struct bertx_spindex *sp);
+BERT_API int32_t bertx_spindex_capacity_docs(struct bertx_spindex *sp);
+BERT_API int64_t bertx_spindex_capacity_postings(struct bertx_spindex *sp);
+BERT_API int32_t bertx_spindex_vocab(struct bertx_spindex *sp);
+BERT_API int32_t bertx_spindex_top(struct bertx_spindex *sp);
+BERT_API int32_t bertx_spindex_add_device(struct bertx_spindex *sp, const float *d_rows, int32_t n, void *stream);
+BERT_API int32_t bertx_spindex_add(struct bertx_spindex *sp, const float *rows, int32_t n);
+BERT_API int32_t bertx_spindex_add_postings(struct bertx_spindex *sp, const int32_t *terms, const float *weights,
+                                            const int32_t *lens, int32_t n);
+BERT_API int32_t bertx_spindex_add_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                         const char **texts);
+BERT_API int32_t bertx_spindex_doc_len(struct bertx_spindex *sp, int32_t id);
+BERT_API int32_t bertx_spindex_doc(struct bertx_spindex *sp, int32_t id, int32_t *terms, float *weights);
+BERT_API int32_t bertx_spindex_search_device(struct bertx_spindex *sp, const float *d_queries, int32_t B, int32_t k,
+                                             float *d_scores, int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_spindex_search(struct bertx_spindex *sp, const float *queries, int32_t B, int32_t k, float *scores,
+                                      int32_t *ids);
+BERT_API int32_t bertx_spindex_search_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                            const char **texts, int32_t k, float *scores, int32_t *ids);
+BERT_API int32_t bertx_forward_sparse_top(struct bert_ctx *ctx, int32_t slot, int32_t n, bert_vocab_id **batch_tokens,
+                                          int32_t *n_tokens, int32_t n_top, int32_t *terms, float *weights,
+                                          int32_t *counts);
+BERT_API int32_t bertx_test_sparse_select(const float *rows, int32_t S, int32_t V, int32_t n, int32_t *terms,
+                                          float *weights, int32_t *count);
+BERT_API int32_t bertx_test_spindex_grid(struct bertx_spindex *sp, int32_t max_wg);
+BERT_API int32_t bertx_test_spindex_last_grid(struct bertx_spindex *sp);
+BERT_API int32_t bertx_bench_spindex(int32_t V, int32_t n_docs, int32_t doc_len, int32_t B, int32_t k, int32_t iters,
+                                     float *avg_us);
 
 BERT_API const char *bertx_version(void);
 

@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""The sparse index: the selection, the pack and the fused scan.
+
+Every figure is the median of R rounds with its min-max spread; a round is one
+bertx_bench_spindex call (3 warm-up launches, then `iters` timed launches between two device
+events per stage).  V 30,522, 128 postings per document (512 stored bytes), k 10.
+
+Per point (n_docs, B): the scan's microseconds and its stored bytes per second, beside
+bertx_bench_search_ex's f16 scan of the same number of stored bytes in the same process (d 256:
+512 bytes per row, the same n_docs rows); the selection's microseconds per row beside the time
+of reading the row's V * 4 bytes once at that dense scan's byte rate; the pack and append per row.
+One JSON line per point into --out.
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "embeddings.cpp_amd"))
+
+import bertpy  # noqa: E402
+
+V, DOC_LEN, K, DENSE_D = 30522, 128, 10, 256
+
+
+def spread(t):
+    return {"median": round(statistics.median(t), 2), "min": round(min(t), 2), "max": round(max(t), 2)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--docs", type=int, nargs="+", default=[1 << 20, 1 << 23])
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 2, 64])
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "spindex_bench.jsonl"))
+    a = ap.parse_args()
+    lib = bertpy.load_lib()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "a") as f:
+        for n_docs in a.docs:
+            for B in a.batches:
+                iters = 20 if B <= 2 else 3
+                sel, pack, scan, dense = [], [], [], []
+                us3, us = (ctypes.c_float * 3)(), ctypes.c_float()
+                for _ in range(a.rounds):
+                    assert lib.bertx_bench_spindex(V, n_docs, DOC_LEN, B, K, iters, us3) == 0
+                    sel.append(us3[0])
+                    pack.append(us3[1])
+                    scan.append(us3[2])
+                    assert lib.bertx_bench_search_ex(DENSE_D, n_docs, B, K, 0, iters, ctypes.byref(us)) == 0
+                    dense.append(us.value)
+                rows = min(1024, n_docs)
+                stored = n_docs * DOC_LEN * 4
+                rec = {"V": V, "n_docs": n_docs, "doc_len": DOC_LEN, "B": B, "k": K, "rounds": a.rounds, "iters": iters,
+                       "stored_bytes": stored, "select_us": spread(sel), "pack_us": spread(pack), "scan_us": spread(scan),
+                       "dense_f16_scan_us": spread(dense), "select_rows": rows}
+                rec["scan_GBps"] = round(stored / (rec["scan_us"]["median"] * 1e-6) / 1e9, 1)
+                rec["dense_GBps"] = round(stored / (rec["dense_f16_scan_us"]["median"] * 1e-6) / 1e9, 1)
+                rec["scan_of_dense"] = round(rec["scan_GBps"] / rec["dense_GBps"], 3)
+                rec["select_us_per_row"] = round(rec["select_us"]["median"] / rows, 3)
+                rec["row_read_once_us"] = round(V * 4 / (rec["dense_GBps"] * 1e9) * 1e6, 3)
+                rec["pack_us_per_row"] = round(rec["pack_us"]["median"] / rows, 4)
+                rec["time"] = time.strftime("%Y-%m-%dT%H:%M:%S")
+                f.write(json.dumps(rec) + "\n")
+                f.flush()
+                print(json.dumps(rec), flush=True)
+
+
+if __name__ == "__main__":
+    main()
