@@ -467,6 +467,19 @@ def load_lib(path=None):
         L.bertx_forward_sparse_top.argtypes = [vp, c_i32, c_i32, ctypes.POINTER(c_i32p), c_i32p, c_i32, vp, vp, vp]
         L.bertx_test_sparse_select.restype = c_i32
         L.bertx_test_sparse_select.argtypes = [vp, c_i32, c_i32, c_i32, vp, vp, vp]
+        L.bertx_spindex_search_sparse_device.restype = c_i32
+        L.bertx_spindex_search_sparse_device.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, vp, vp, vp]
+        L.bertx_spindex_search_sparse.restype = c_i32
+        L.bertx_spindex_search_sparse.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, vp, vp]
+        L.bertx_spindex_search_texts_top.restype = c_i32
+        L.bertx_spindex_search_texts_top.argtypes = [vp, vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p), c_i32, c_i32,
+                                                     vp, vp]
+        L.bertx_spindex_batch_queries.restype = c_i32
+        L.bertx_spindex_batch_queries.argtypes = [vp, c_i32, c_i32]
+        L.bertx_test_spindex_last_passes.restype = c_i32
+        L.bertx_test_spindex_last_passes.argtypes = [vp]
+        L.bertx_bench_spindex_batch.restype = c_i32
+        L.bertx_bench_spindex_batch.argtypes = [c_i32] * 7 + [c_f32p]
         L.bertx_test_spindex_grid.restype = c_i32
         L.bertx_test_spindex_grid.argtypes = [vp, c_i32]
         L.bertx_bench_spindex.restype = c_i32
@@ -1500,12 +1513,45 @@ class BertSparseIndex:
                                                              ids[b:].ctypes.data)), "bertx_spindex_search")
         return scores, ids
 
-    def search_texts(self, texts, k):
+    def search_sparse(self, terms, weights=None, k=10):
+        """(scores f32 [B][k], ids int32 [B][k]) of sparse queries: terms int32 [B][q_top] and weights
+        f32 [B][q_top] with -1 in the empty slots (forward_sparse_top's output), or, weights None, a list
+        of lists of (term, weight) pairs, padded here.  The bits of search() on the densified queries,
+        32, 16, 8 or 4 queries per pass over the store.  Any B: 64 queries per call of the library."""
+        if weights is None:
+            q_top = max([len(p) for p in terms] + [1])
+            t, w = np.full((len(terms), q_top), -1, np.int32), np.zeros((len(terms), q_top), np.float32)
+            for b, pairs in enumerate(terms):
+                for j, (term, wt) in enumerate(pairs):
+                    t[b, j], w[b, j] = term, wt
+        else:
+            t = np.ascontiguousarray(np.asarray(terms, np.int32))
+            w = np.ascontiguousarray(np.asarray(weights, np.float32))
+            if t.ndim == 1:
+                t, w = t[None, :], w[None, :]
+            if t.ndim != 2 or t.shape != w.shape:
+                raise ValueError("expected terms and weights of one shape [B][q_top], got %r and %r" % (t.shape, w.shape))
+        B, q_top = t.shape
+        scores, ids = np.zeros((B, k), np.float32), np.zeros((B, k), np.int32)
+        for b in range(0, B, 64):
+            m = min(64, B - b)
+            self._checked(-abs(self.lib.bertx_spindex_search_sparse(self.sp, t[b:].ctypes.data, w[b:].ctypes.data, m, q_top,
+                                                                    k, scores[b:].ctypes.data, ids[b:].ctypes.data)),
+                          "bertx_spindex_search_sparse")
+        return scores, ids
+
+    def search_texts(self, texts, k, q_top=None):
+        """q_top: the queries cut to their q_top largest weights on the device and searched sparse."""
         n = len(texts)
         scores, ids = np.zeros((n, k), np.float32), np.zeros((n, k), np.int32)
-        self._checked(-abs(self.lib.bertx_spindex_search_texts(self.sp, self.model.ctx, self.model.N_THREADS, n,
-                                                               BertIndex._texts(texts), k, scores.ctypes.data,
-                                                               ids.ctypes.data)), "bertx_spindex_search_texts")
+        if q_top is None:
+            rc = self.lib.bertx_spindex_search_texts(self.sp, self.model.ctx, self.model.N_THREADS, n,
+                                                     BertIndex._texts(texts), k, scores.ctypes.data, ids.ctypes.data)
+        else:
+            rc = self.lib.bertx_spindex_search_texts_top(self.sp, self.model.ctx, self.model.N_THREADS, n,
+                                                         BertIndex._texts(texts), q_top, k, scores.ctypes.data,
+                                                         ids.ctypes.data)
+        self._checked(-abs(rc), "bertx_spindex_search_texts")
         return scores, ids
 
 

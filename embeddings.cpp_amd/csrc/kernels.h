@@ -491,6 +491,26 @@ size_t sparse_scan_partial_bytes();
 int launch_sparse_scan(const uint32_t *store, const void *d_table, const int32_t *d_used, int n_docs, int V,
                        const float *d_queries, int B, int k, void *qtab, void *partial, float *d_scores, int32_t *d_ids,
                        hipStream_t s, int max_wg = 0, int *ran_wg = nullptr);
+// The batched scan of sparse queries (sparse_batch.hip).  Queries of one pass: the largest of
+// 32, 16, 8, 4 whose image (a rank dictionary over V and f16 weights [min(NQ q_top, V)][NQ]),
+// lists and staging tile fit in LDS, 0 when none does or an argument is out of range; the
+// bytes of the passes' images and of the workgroups' lists.
+int sparse_batch_prepare_device();
+int sparse_batch_queries(int V, int q_top, int k);
+size_t sparse_batch_image_bytes();
+size_t sparse_batch_partial_bytes();
+// The passes' images alone (the first launch of launch_sparse_scan_batch).
+int launch_sparse_batch_image(const int32_t *d_terms, const float *d_weights, int B, int q_top, int V, int k, void *images,
+                              hipStream_t s);
+// launch_sparse_scan's result for the queries d_terms int32 [B][q_top], d_weights f32 [B][q_top]
+// (a term outside 0 .. V - 1 is an empty slot; a query's terms are distinct, else the highest
+// slot of a term wins): the bits of the dense form on q[b][term] = weight.  One image kernel,
+// then per pass of sparse_batch_queries queries the scan and launch_search_merge.  Same limits
+// and 1 <= q_top <= 1024; -1 otherwise, -3: launch refused.
+int launch_sparse_scan_batch(const uint32_t *store, const void *d_table, const int32_t *d_used, int n_docs, int V,
+                             const int32_t *d_terms, const float *d_weights, int B, int q_top, int k, void *images,
+                             void *partial, float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg = 0,
+                             int *ran_wg = nullptr);
 
 // Diagnostics: *cnt += number of non-finite values in p[0..n) (f32, or f16 if f16).
 void launch_count_nonfinite(const void *p, size_t n, int f16, unsigned *cnt, hipStream_t s);

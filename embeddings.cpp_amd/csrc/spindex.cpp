@@ -41,7 +41,12 @@ struct bertx_spindex {
     float *st_scores = nullptr;            // [64][128]
     int32_t *st_ids = nullptr;
     void *qtab = nullptr, *partial = nullptr;
+    // sparse queries: the host forms' staging int32 / f32 [kStage][1024], the passes' images
+    int32_t *st_qterms = nullptr;
+    float *st_qweights = nullptr;
+    void *qimage = nullptr;
     int grid_cap = 0, last_grid = 0;       // bertx_test_spindex_grid
+    int last_passes = 0;                   // bertx_test_spindex_last_passes
     hipStream_t stream = nullptr;
     emb::StoreOrder ord;
     std::mutex mu;
@@ -51,7 +56,8 @@ struct bertx_spindex {
         if (stream) (void)hipStreamSynchronize(stream);
         if (ord.done) (void)ord.wait();
         for (void *p : {(void *)store, (void *)table, (void *)d_used, (void *)sel_terms, (void *)sel_count,
-                        (void *)sel_weights, (void *)st_rows, (void *)st_scores, (void *)st_ids, qtab, partial})
+                        (void *)sel_weights, (void *)st_rows, (void *)st_scores, (void *)st_ids, qtab, partial,
+                        (void *)st_qterms, (void *)st_qweights, qimage})
             if (p) (void)hipFree(p);
         if (ord.done) (void)hipEventDestroy(ord.done);
         if (stream) (void)hipStreamDestroy(stream);
@@ -127,14 +133,31 @@ int32_t search_device_locked(bertx_spindex &sp, const float *d_q, int32_t B, int
         return -1;
     }
     Ordered o(sp.ord, s);
+    const int NQ = sparse_scan_pair(sp.V, k);
+    sp.last_passes = (B + NQ - 1) / NQ;
     return launch_sparse_scan(sp.store, sp.table, sp.d_used, (int)sp.n_docs, sp.V, d_q, B, k, sp.qtab, sp.partial, d_scores,
                               d_ids, s, sp.grid_cap, &sp.last_grid);
 }
 
-// B dense queries on the device, on the store's stream -> host results.
-int32_t search_to_host(bertx_spindex &sp, const float *d_q, int32_t B, int32_t k, float *scores, int32_t *ids)
+int32_t search_sparse_device_locked(bertx_spindex &sp, const int32_t *d_terms, const float *d_weights, int32_t B,
+                                    int32_t q_top, int32_t k, float *d_scores, int32_t *d_ids, hipStream_t s)
 {
-    const int32_t rc = search_device_locked(sp, d_q, B, k, sp.st_scores, sp.st_ids, sp.stream);
+    const int NQ = sparse_batch_queries(sp.V, q_top, k);
+    if (!d_terms || !d_weights || !d_scores || !d_ids || B < 1 || B > 64 || NQ == 0) {
+        errorf("bertx_spindex_search_sparse: B = %d, q_top = %d, k = %d are not in 1 <= B <= 64, 1 <= q_top <= 1024, "
+               "1 <= k <= 128 with four queries' image in LDS\n", B, q_top, k);
+        return -1;
+    }
+    Ordered o(sp.ord, s);
+    sp.last_passes = (B + NQ - 1) / NQ;
+    return launch_sparse_scan_batch(sp.store, sp.table, sp.d_used, (int)sp.n_docs, sp.V, d_terms, d_weights, B, q_top, k,
+                                    sp.qimage, sp.partial, d_scores, d_ids, s, sp.grid_cap, &sp.last_grid);
+}
+
+// The results of a search launched on the store's stream into st_scores / st_ids (rc: its
+// return value) -> the host.
+int32_t results_to_host(bertx_spindex &sp, int32_t rc, int32_t B, int32_t k, float *scores, int32_t *ids)
+{
     if (rc != 0) {
         (void)hipGetLastError();
         (void)hipStreamSynchronize(sp.stream);
@@ -144,6 +167,12 @@ int32_t search_to_host(bertx_spindex &sp, const float *d_q, int32_t B, int32_t k
     HIP_RC(hipMemcpyAsync(ids, sp.st_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, sp.stream));
     HIP_RC(hipStreamSynchronize(sp.stream));
     return 0;
+}
+
+// B dense queries on the device, on the store's stream -> host results.
+int32_t search_to_host(bertx_spindex &sp, const float *d_q, int32_t B, int32_t k, float *scores, int32_t *ids)
+{
+    return results_to_host(sp, search_device_locked(sp, d_q, B, k, sp.st_scores, sp.st_ids, sp.stream), B, k, scores, ids);
 }
 
 // The refusals of the text forms: -6 a file without the MLM records, -1 another vocabulary or
@@ -238,7 +267,8 @@ bertx_spindex *spindex_create_on(int ordinal, int V, int n_top, int64_t cap_docs
     sp->cap_docs = cap_docs;
     sp->cap_units = units_of(cap_postings);
     const size_t sel = (size_t)kSparseAddRows * n_top * 4;
-    const bool ok = sparse_scan_prepare_device() == 0 &&
+    const size_t stq = (size_t)kStage * 1024 * 4;
+    const bool ok = sparse_scan_prepare_device() == 0 && sparse_batch_prepare_device() == 0 &&
                     hipStreamCreateWithFlags(&sp->stream, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&sp->ord.done, hipEventDisableTiming) == hipSuccess &&
                     hipMalloc((void **)&sp->store, (size_t)sp->cap_units * 64) == hipSuccess &&
@@ -251,7 +281,10 @@ bertx_spindex *spindex_create_on(int ordinal, int V, int n_top, int64_t cap_docs
                     hipMalloc((void **)&sp->st_scores, 64 * 128 * 4) == hipSuccess &&
                     hipMalloc((void **)&sp->st_ids, 64 * 128 * 4) == hipSuccess &&
                     hipMalloc(&sp->qtab, sparse_scan_table_bytes(V)) == hipSuccess &&
-                    hipMalloc(&sp->partial, sparse_scan_partial_bytes()) == hipSuccess &&
+                    hipMalloc(&sp->partial, std::max(sparse_scan_partial_bytes(), sparse_batch_partial_bytes())) == hipSuccess &&
+                    hipMalloc((void **)&sp->st_qterms, stq) == hipSuccess &&
+                    hipMalloc((void **)&sp->st_qweights, stq) == hipSuccess &&
+                    hipMalloc(&sp->qimage, sparse_batch_image_bytes()) == hipSuccess &&
                     hipMemsetAsync(sp->d_used, 0, 16, sp->stream) == hipSuccess &&
                     hipStreamSynchronize(sp->stream) == hipSuccess;
     if (!ok) {
@@ -507,11 +540,55 @@ int32_t bertx_spindex_add_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, 
     return first;
 }
 
-int32_t bertx_spindex_search_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
-                                   const char **texts, int32_t k, float *scores, int32_t *ids)
+int32_t bertx_spindex_search_sparse_device(struct bertx_spindex *sp, const int32_t *d_terms, const float *d_weights,
+                                           int32_t B, int32_t q_top, int32_t k, float *d_scores, int32_t *d_ids, void *stream)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    return emb::search_sparse_device_locked(*sp, d_terms, d_weights, B, q_top, k, d_scores, d_ids,
+                                            stream ? (hipStream_t)stream : sp->stream);
+}
+
+int32_t bertx_spindex_search_sparse(struct bertx_spindex *sp, const int32_t *terms, const float *weights, int32_t B,
+                                    int32_t q_top, int32_t k, float *scores, int32_t *ids)
+{
+    if (!sp || !terms || !weights || !scores || !ids || B < 1 || B > kStage || q_top < 1 || q_top > 1024) return -1;
+    std::vector<int32_t> seen((size_t)sp->V, -1);   // the query that last held the term
+    for (int32_t b = 0; b < B; ++b)
+        for (int32_t j = 0; j < q_top; ++j) {
+            const int32_t t = terms[(size_t)b * q_top + j];
+            if (t < 0) continue;   // an empty slot
+            if (t >= sp->V || seen[(size_t)t] == b || !std::isfinite(weights[(size_t)b * q_top + j])) {
+                emb::errorf("bertx_spindex_search_sparse: query %d, slot %d: terms are below n_vocab = %d and distinct "
+                            "within a query, weights are finite\n", b, j, sp->V);
+                return -1;
+            }
+            seen[(size_t)t] = b;
+        }
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    {
+        emb::Ordered o(sp->ord, sp->stream);
+        HIP_RC(hipMemcpyAsync(sp->st_qterms, terms, (size_t)B * q_top * 4, hipMemcpyHostToDevice, sp->stream));
+        HIP_RC(hipMemcpyAsync(sp->st_qweights, weights, (size_t)B * q_top * 4, hipMemcpyHostToDevice, sp->stream));
+    }
+    HIP_RC(hipStreamSynchronize(sp->stream));   // the caller's arrays are pageable
+    const int32_t rc = emb::search_sparse_device_locked(*sp, sp->st_qterms, sp->st_qweights, B, q_top, k, sp->st_scores,
+                                                        sp->st_ids, sp->stream);
+    return emb::results_to_host(*sp, rc, B, k, scores, ids);
+}
+
+namespace {
+// The text searches: q_top == 0 searches the forward's dense rows, q_top > 0 selects the
+// q_top largest weights of each row on the device and searches those.
+int32_t search_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts,
+                     int32_t q_top, int32_t k, float *scores, int32_t *ids, const char *who)
 {
     int32_t slot = -1;
-    if (const int32_t rc = emb::text_ctx_ok(sp, ctx, "bertx_spindex_search_texts", &slot)) return rc;
+    if (const int32_t rc = emb::text_ctx_ok(sp, ctx, who, &slot)) return rc;
     if (!texts || !scores || !ids || n < 1 || k < 1 || k > 128) return -1;
     emb::Texts t;
     if (emb::tokenize(ctx, n_threads, n, texts, t) != 0) return -1;
@@ -525,12 +602,21 @@ int32_t bertx_spindex_search_texts(struct bertx_spindex *sp, struct bert_ctx *ct
     size_t cap = 0;
     for (size_t i = 0; i < (size_t)n;) {
         const size_t e = emb::chunk_end([&](size_t j) { return t.lens[j]; }, i, (size_t)n, emb::kChunkTokens, kStage);
+        const int32_t m = (int32_t)(e - i);
         int32_t rc = 0;
         {
             emb::Ordered o(sp->ord, sp->stream);
             rc = emb::forward_chunk(sp->stream, sp->st_rows, ctx, slot, t, i, e, flat, d_tok, &cap);
+            if (rc == 0 && q_top > 0)
+                rc = emb::launch_sparse_select(sp->st_rows, m, sp->V, q_top, sp->st_qterms, sp->st_qweights, sp->sel_count,
+                                               sp->stream);
         }
-        if (rc == 0) rc = emb::search_to_host(*sp, sp->st_rows, (int32_t)(e - i), k, hs.data() + i * k, hi.data() + i * k);
+        if (rc == 0 && q_top > 0)
+            rc = emb::results_to_host(*sp, emb::search_sparse_device_locked(*sp, sp->st_qterms, sp->st_qweights, m, q_top, k,
+                                                                            sp->st_scores, sp->st_ids, sp->stream),
+                                      m, k, hs.data() + i * k, hi.data() + i * k);
+        else if (rc == 0)
+            rc = emb::search_to_host(*sp, sp->st_rows, m, k, hs.data() + i * k, hi.data() + i * k);
         if (rc != 0) {
             (void)hipGetLastError();
             (void)hipStreamSynchronize(sp->stream);
@@ -541,6 +627,25 @@ int32_t bertx_spindex_search_texts(struct bertx_spindex *sp, struct bert_ctx *ct
     std::memcpy(scores, hs.data(), hs.size() * 4);
     std::memcpy(ids, hi.data(), hi.size() * 4);
     return 0;
+}
+}  // namespace
+
+int32_t bertx_spindex_search_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                   const char **texts, int32_t k, float *scores, int32_t *ids)
+{
+    return search_texts(sp, ctx, n_threads, n, texts, 0, k, scores, ids, "bertx_spindex_search_texts");
+}
+
+int32_t bertx_spindex_search_texts_top(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                       const char **texts, int32_t q_top, int32_t k, float *scores, int32_t *ids)
+{
+    if (q_top < 1 || q_top > 1024) return -1;
+    return search_texts(sp, ctx, n_threads, n, texts, q_top, k, scores, ids, "bertx_spindex_search_texts_top");
+}
+
+int32_t bertx_spindex_batch_queries(struct bertx_spindex *sp, int32_t q_top, int32_t k)
+{
+    return sp ? emb::sparse_batch_queries(sp->V, q_top, k) : 0;
 }
 
 int32_t bertx_forward_sparse_top(struct bert_ctx *ctx, int32_t slot, int32_t n, bert_vocab_id **batch_tokens,
@@ -606,6 +711,13 @@ int32_t bertx_test_spindex_last_grid(struct bertx_spindex *sp)
     if (!sp) return -1;
     std::lock_guard<std::mutex> lk(sp->mu);
     return sp->last_grid;
+}
+
+int32_t bertx_test_spindex_last_passes(struct bertx_spindex *sp)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    return sp->last_passes;
 }
 
 }  // extern "C"

@@ -1476,20 +1476,51 @@ BERT_API int32_t bertx_bench_sparse(int32_t d, int32_t V, int32_t n_seqs, int32_
  * store, the batch, k or B.  Padding postings add qh[0] * +0, which changes no bit for
  * finite queries; queries with non-finite values are outside the contract.  A document of
  * count 0 scores +0.
- * The scan is document-major: it streams every stored posting once per pass of two queries
- * (one where n_vocab is too large for two f16 tables in LDS), keeps the k best in LDS and
- * merges the workgroups' lists; B > 2 is a sequence of passes.
+ * The scan is document-major: it streams every stored posting once per pass, keeps the k
+ * best in LDS and merges the workgroups' lists.  A pass of the dense-query search holds two
+ * queries (one where n_vocab is too large for two f16 tables in LDS), so B > 2 is a sequence
+ * of ceil(B / 2) passes; a pass of the sparse-query search below holds 32, 16, 8 or 4.
+ *
+ * Sparse queries.  bertx_spindex_search_sparse_device(sp, d_terms, d_weights, B, q_top, k,
+ * d_scores, d_ids, stream): d_terms int32 [B][q_top], d_weights f32 [B][q_top], the layout
+ * bertx_forward_sparse_top returns; a slot with a term below 0 (or >= n_vocab) is empty, so
+ * no counts are passed.  1 <= B <= 64, 1 <= q_top <= 1,024, 1 <= k <= 128.  The result is
+ * bertx_spindex_search_device's on the densified queries (q[b][term] = weight, 0 elsewhere):
+ * the same ids and the same score bits, because a posting whose term the query lacks adds +-0
+ * to a sub-sum that is never -0, and the postings that are added keep their lane, order and
+ * fold.  A query's terms are distinct: the device form trusts this, and of a repeated term the
+ * weight in the highest slot counts.  Asynchronous, capturable, allocates nothing.  A pass
+ * holds NQ = bertx_spindex_batch_queries(sp, q_top, k) queries, the largest of 32, 16, 8, 4
+ * whose image (8 bytes per 32 terms of n_vocab and f16 weights [min(NQ q_top, n_vocab)][NQ]),
+ * lists and staging tile fit in LDS (0: not even 4 do, and the search returns -1); B > NQ is
+ * ceil(B / NQ) passes.  bertx_spindex_search_sparse is the host form; it refuses (-1) a term
+ * >= n_vocab, a term repeated within a query and a non-finite weight.
+ * bertx_spindex_search_texts_top(sp, ctx, n_threads, n, texts, q_top, k, scores, ids): the
+ * sparse forward, the selection of the q_top largest weights per query and the sparse-query
+ * search, all on the device, 64 texts per forward.  Equal to bertx_spindex_search_texts when
+ * every query has at most q_top positive weights; otherwise the search of the query cut to
+ * its q_top largest weights (the selection's rule above).
+ * Which to use (DESIGN.md 9i-3 has the measured rows; one MI355X, n_vocab 30,522, 1 M
+ * documents of 128 postings, queries of 32 terms, k 10, dense-query / sparse-query search):
+ * B 1 362 / 414 us, B 2 387 / 418 us, B 16 3,091 / 453 us, B 64 12,339 / 997 us.  The
+ * dense-query search for one or two queries, the sparse-query search from a handful up: at 64
+ * queries of 32 terms it takes 2 passes over the store where the dense-query search takes 32.
  *
  * bertx_test_sparse_select (parity hook; host buffers, device 0): rows f32 [S][V] ->
  * terms int32 [S][n], weights f32 [S][n] (the input's bits), count int32 [S]; slots past a
  * row's count hold (-1, +0).  Guard rows of NaN bits lie behind the three device outputs;
  * -5: one was written.  bertx_test_spindex_grid(sp, max_wg): max_wg > 0 bounds the scan's
  * workgroups (the tests' way to many documents per wave), 0 lifts the bound;
- * bertx_test_spindex_last_grid: the workgroups of the latest scan.
+ * bertx_test_spindex_last_grid: the workgroups of the latest scan;
+ * bertx_test_spindex_last_passes: the scan launches of the latest search of either kind.
  * bertx_bench_spindex (device 0, no context): n_docs documents of doc_len postings selected
  * from dense rows of hashed values; avg_us[0] the selection of 1,024 rows (fewer if n_docs
  * is), avg_us[1] their pack and append, avg_us[2] one search of B hashed queries; averages
  * of `iters` launches after 3 warm-up launches.
+ * bertx_bench_spindex_batch(V, n_docs, doc_len, B, q_len, k, iters, avg_us): the same store
+ * and B queries of q_len terms selected from hashed rows as the documents are; avg_us[0] the
+ * query-image kernel, avg_us[1] the whole sparse-query search, avg_us[2]
+ * bertx_spindex_search_device's scan of the same queries densified.
  *
  * Not provided: inverted lists and any dynamic pruning (WAND, block-max); int8 or impact-
  * quantized weights; deletion and filters; scoring listed ids; a mode of the `search` tool;
@@ -1520,6 +1551,15 @@ BERT_API int32_t bertx_spindex_search(struct bertx_spindex *sp, const float *que
                                       int32_t *ids);
 BERT_API int32_t bertx_spindex_search_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
                                             const char **texts, int32_t k, float *scores, int32_t *ids);
+BERT_API int32_t bertx_spindex_search_sparse_device(struct bertx_spindex *sp, const int32_t *d_terms,
+                                                    const float *d_weights, int32_t B, int32_t q_top, int32_t k,
+                                                    float *d_scores, int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_spindex_search_sparse(struct bertx_spindex *sp, const int32_t *terms, const float *weights,
+                                             int32_t B, int32_t q_top, int32_t k, float *scores, int32_t *ids);
+BERT_API int32_t bertx_spindex_search_texts_top(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads,
+                                                int32_t n, const char **texts, int32_t q_top, int32_t k, float *scores,
+                                                int32_t *ids);
+BERT_API int32_t bertx_spindex_batch_queries(struct bertx_spindex *sp, int32_t q_top, int32_t k);
 BERT_API int32_t bertx_forward_sparse_top(struct bert_ctx *ctx, int32_t slot, int32_t n, bert_vocab_id **batch_tokens,
                                           int32_t *n_tokens, int32_t n_top, int32_t *terms, float *weights,
                                           int32_t *counts);
@@ -1527,8 +1567,11 @@ BERT_API int32_t bertx_test_sparse_select(const float *rows, int32_t S, int32_t 
                                           float *weights, int32_t *count);
 BERT_API int32_t bertx_test_spindex_grid(struct bertx_spindex *sp, int32_t max_wg);
 BERT_API int32_t bertx_test_spindex_last_grid(struct bertx_spindex *sp);
+BERT_API int32_t bertx_test_spindex_last_passes(struct bertx_spindex *sp);
 BERT_API int32_t bertx_bench_spindex(int32_t V, int32_t n_docs, int32_t doc_len, int32_t B, int32_t k, int32_t iters,
                                      float *avg_us);
+BERT_API int32_t bertx_bench_spindex_batch(int32_t V, int32_t n_docs, int32_t doc_len, int32_t B, int32_t q_len,
+                                           int32_t k, int32_t iters, float *avg_us);
 
 BERT_API const char *bertx_version(void);
 

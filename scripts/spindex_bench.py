@@ -10,6 +10,10 @@ bertx_bench_search_ex's f16 scan of the same number of stored bytes in the same 
 512 bytes per row, the same n_docs rows); the selection's microseconds per row beside the time
 of reading the row's V * 4 bytes once at that dense scan's byte rate; the pack and append per row.
 One JSON line per point into --out.
+
+--batch-leg measures bertx_bench_spindex_batch instead: per point (n_docs, B) the
+query-image kernel, the whole sparse-query search of B queries of --q-len terms and the dense-query
+search of the same queries densified, in the same process and round.
 """
 import argparse
 import ctypes
@@ -36,12 +40,33 @@ def main():
     ap.add_argument("--docs", type=int, nargs="+", default=[1 << 20, 1 << 23])
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 2, 64])
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--batch-leg", action="store_true")
+    ap.add_argument("--q-len", type=int, default=32)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "spindex_bench.jsonl"))
     a = ap.parse_args()
     lib = bertpy.load_lib()
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "a") as f:
-        for n_docs in a.docs:
+        for n_docs in a.docs if a.batch_leg else []:
+            for B in a.batches:
+                iters = 20 if B <= 2 else 5
+                image, sparse, dense = [], [], []
+                us3 = (ctypes.c_float * 3)()
+                for _ in range(a.rounds):
+                    assert lib.bertx_bench_spindex_batch(V, n_docs, DOC_LEN, B, a.q_len, K, iters, us3) == 0
+                    image.append(us3[0])
+                    sparse.append(us3[1])
+                    dense.append(us3[2])
+                rec = {"leg": "batch", "V": V, "n_docs": n_docs, "doc_len": DOC_LEN, "B": B, "q_len": a.q_len, "k": K,
+                       "rounds": a.rounds, "iters": iters, "image_us": spread(image), "sparse_query_us": spread(sparse),
+                       "dense_query_us": spread(dense)}
+                rec["dense_of_sparse"] = round(rec["dense_query_us"]["median"] / rec["sparse_query_us"]["median"], 2)
+                rec["slowest_sparse_beats_fastest_dense"] = max(sparse) < min(dense)
+                rec["time"] = time.strftime("%Y-%m-%dT%H:%M:%S")
+                f.write(json.dumps(rec) + "\n")
+                f.flush()
+                print(json.dumps(rec), flush=True)
+        for n_docs in [] if a.batch_leg else a.docs:
             for B in a.batches:
                 iters = 20 if B <= 2 else 3
                 sel, pack, scan, dense = [], [], [], []
