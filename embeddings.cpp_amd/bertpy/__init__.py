@@ -484,6 +484,21 @@ def load_lib(path=None):
         L.bertx_test_spindex_grid.argtypes = [vp, c_i32]
         L.bertx_bench_spindex.restype = c_i32
         L.bertx_bench_spindex.argtypes = [c_i32] * 6 + [c_f32p]
+        for fn in (L.bertx_spindex_build_inverted, L.bertx_spindex_inverted_docs, L.bertx_spindex_inv_block):
+            fn.restype = c_i32
+            fn.argtypes = [vp]
+        L.bertx_spindex_inverted_bytes.restype = ctypes.c_int64
+        L.bertx_spindex_inverted_bytes.argtypes = [vp]
+        L.bertx_spindex_search_inverted_device.restype = c_i32
+        L.bertx_spindex_search_inverted_device.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, vp, vp, vp]
+        L.bertx_spindex_search_inverted.restype = c_i32
+        L.bertx_spindex_search_inverted.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, vp, vp]
+        L.bertx_spindex_search_texts_inverted.restype = c_i32
+        L.bertx_spindex_search_texts_inverted.argtypes = L.bertx_spindex_search_texts_top.argtypes
+        L.bertx_test_spindex_inv_block.restype = c_i32
+        L.bertx_test_spindex_inv_block.argtypes = [vp, c_i32]
+        L.bertx_bench_spindex_inverted.restype = c_i32
+        L.bertx_bench_spindex_inverted.argtypes = [c_i32] * 8 + [c_f32p]
     except AttributeError:
         pass
     L.bertx_bench_gemm.restype = c_i32
@@ -1518,6 +1533,23 @@ class BertSparseIndex:
         f32 [B][q_top] with -1 in the empty slots (forward_sparse_top's output), or, weights None, a list
         of lists of (term, weight) pairs, padded here.  The bits of search() on the densified queries,
         32, 16, 8 or 4 queries per pass over the store.  Any B: 64 queries per call of the library."""
+        return self._search_pairs(self.lib.bertx_spindex_search_sparse, "bertx_spindex_search_sparse", terms, weights, k)
+
+    def build_inverted(self):
+        """Inverts the documents added since the last build (block-local term lists, on the device)."""
+        self._checked(self.lib.bertx_spindex_build_inverted(self.sp), "bertx_spindex_build_inverted")
+
+    @property
+    def inverted_docs(self):
+        return int(self.lib.bertx_spindex_inverted_docs(self.sp))
+
+    def search_inverted(self, terms, weights=None, k=10):
+        """search_sparse's arguments and result contract over the inverted lists, which are built first
+        when stale: only the lists the queries name are read.  The score adds the query's terms in slot
+        order (bert_hip.h "Inverted lists"), so its bits are not search_sparse's."""
+        return self._search_pairs(self.lib.bertx_spindex_search_inverted, "bertx_spindex_search_inverted", terms, weights, k)
+
+    def _search_pairs(self, fn, name, terms, weights, k):
         if weights is None:
             q_top = max([len(p) for p in terms] + [1])
             t, w = np.full((len(terms), q_top), -1, np.int32), np.zeros((len(terms), q_top), np.float32)
@@ -1535,16 +1567,22 @@ class BertSparseIndex:
         scores, ids = np.zeros((B, k), np.float32), np.zeros((B, k), np.int32)
         for b in range(0, B, 64):
             m = min(64, B - b)
-            self._checked(-abs(self.lib.bertx_spindex_search_sparse(self.sp, t[b:].ctypes.data, w[b:].ctypes.data, m, q_top,
-                                                                    k, scores[b:].ctypes.data, ids[b:].ctypes.data)),
-                          "bertx_spindex_search_sparse")
+            self._checked(-abs(fn(self.sp, t[b:].ctypes.data, w[b:].ctypes.data, m, q_top, k, scores[b:].ctypes.data,
+                               ids[b:].ctypes.data)), name)
         return scores, ids
 
-    def search_texts(self, texts, k, q_top=None):
-        """q_top: the queries cut to their q_top largest weights on the device and searched sparse."""
+    def search_texts(self, texts, k, q_top=None, inverted=False):
+        """q_top: the queries cut to their q_top largest weights on the device and searched sparse;
+        inverted (with q_top): over the inverted lists, built first when stale."""
         n = len(texts)
         scores, ids = np.zeros((n, k), np.float32), np.zeros((n, k), np.int32)
-        if q_top is None:
+        if inverted:
+            if q_top is None:
+                raise ValueError("search_texts(inverted=True) needs q_top")
+            rc = self.lib.bertx_spindex_search_texts_inverted(self.sp, self.model.ctx, self.model.N_THREADS, n,
+                                                              BertIndex._texts(texts), q_top, k, scores.ctypes.data,
+                                                              ids.ctypes.data)
+        elif q_top is None:
             rc = self.lib.bertx_spindex_search_texts(self.sp, self.model.ctx, self.model.N_THREADS, n,
                                                      BertIndex._texts(texts), k, scores.ctypes.data, ids.ctypes.data)
         else:

@@ -1490,3 +1490,82 @@ extern "C" int32_t bertx_bench_spindex_batch(int32_t V, int32_t n_docs, int32_t 
     }
     return hook_finish();
 }
+
+// The inverted search beside the two document-major searches (bert_hip.h): device 0, no
+// context, bertx_bench_spindex_batch's store and queries.  skew 1: the documents' and the
+// queries' rows get heavy terms before the selection (launch_sparse_skew_rows: 16 terms held
+// by 50 %, 37.5 %, 28 %, ... of the documents; every query holds the first four).
+// avg_us[0]: the build of the whole image; avg_us[1]: the inverted search; avg_us[2]: the
+// sparse-query search; avg_us[3]: the dense-query search of the same queries densified.
+extern "C" int32_t bertx_bench_spindex_inverted(int32_t V, int32_t n_docs, int32_t doc_len, int32_t B, int32_t q_len,
+                                                int32_t k, int32_t skew, int32_t iters, float *avg_us)
+{
+    using namespace emb;
+    if (V < 4 * kSparseHeavyTerms || V > 65536 || n_docs < 1 || doc_len < 1 || doc_len > 1024 || 2 * doc_len > V || B < 1 ||
+        B > 64 || sparse_batch_queries(V, q_len, k) == 0 || 2 * q_len > V || skew < 0 || skew > 1 || iters < 1 || !avg_us ||
+        hip_device_count() == 0)
+        return -1;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    if (sparse_scan_prepare_device() != 0 || sparse_batch_prepare_device() != 0 || sparse_inv_prepare_device() != 0) return -1;
+    const int chunk = std::min<int>(kSparseAddRows, n_docs);
+    const size_t units = (size_t)n_docs * ((size_t)(doc_len + 15) / 16);
+    HookBufs H;
+    float *rows = (float *)H.up(nullptr, 0, (size_t)std::max(chunk, B) * V * 4);
+    int32_t *terms = (int32_t *)H.up(nullptr, 0, (size_t)chunk * doc_len * 4), *count = (int32_t *)H.up(nullptr, 0, (size_t)chunk * 4);
+    float *wts = (float *)H.up(nullptr, 0, (size_t)chunk * doc_len * 4);
+    uint32_t *store = (uint32_t *)H.up(nullptr, 0, units * 64), *inv = (uint32_t *)H.up(nullptr, 0, units * 64);
+    uint32_t *inv_rows = (uint32_t *)H.up(nullptr, 0, sparse_inv_rows_bytes(n_docs, V, kSparseInvBlock));
+    int32_t *table = (int32_t *)H.up(nullptr, 0, (size_t)n_docs * 8), *used = (int32_t *)H.up(nullptr, 0, 16);
+    int32_t *qt = (int32_t *)H.up(nullptr, 0, (size_t)B * q_len * 4), *qc = (int32_t *)H.up(nullptr, 0, (size_t)B * 4);
+    float *qw = (float *)H.up(nullptr, 0, (size_t)B * q_len * 4), *sc = (float *)H.up(nullptr, 0, (size_t)B * k * 4);
+    int32_t *ids = (int32_t *)H.up(nullptr, 0, (size_t)B * k * 4);
+    void *qtab = H.up(nullptr, 0, sparse_scan_table_bytes(V)), *img = H.up(nullptr, 0, sparse_batch_image_bytes());
+    void *part = H.up(nullptr, 0, std::max({sparse_scan_partial_bytes(), sparse_batch_partial_bytes(), sparse_inv_partial_bytes()}));
+    if (H.bad) return -1;
+    struct Str {
+        hipStream_t s = nullptr;
+        ~Str() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    } E;
+    HIP_RC(hipStreamCreateWithFlags(&E.s, hipStreamNonBlocking));
+    EventPair ev;
+    HIP_RC(ev.create());
+    for (int64_t i = 0; i < n_docs; i += chunk) {
+        const int m = (int)std::min<int64_t>(chunk, n_docs - i);
+        if (launch_unit_rows(rows, m, V, 12345u + (uint32_t)i, E.s) != 0 ||
+            (skew && launch_sparse_skew_rows(rows, m, V, 99u + (uint32_t)i, 0, E.s) != 0) ||
+            launch_sparse_select(rows, m, V, doc_len, terms, wts, count, E.s) != 0 ||
+            launch_sparse_pack(terms, wts, count, m, doc_len, table + 2 * i, used, store, E.s) != 0)
+            return -1;
+    }
+    if (launch_unit_rows(rows, B, V, 4242u, E.s) != 0 || (skew && launch_sparse_skew_rows(rows, B, V, 0u, 4, E.s) != 0) ||
+        launch_sparse_select(rows, B, V, q_len, qt, qw, qc, E.s) != 0)
+        return -1;
+    // the same queries dense: the selected weights at their terms, zero elsewhere
+    std::vector<int32_t> ht((size_t)B * q_len);
+    std::vector<float> hw((size_t)B * q_len), dense((size_t)B * V, 0.f);
+    HIP_RC(hipStreamSynchronize(E.s));
+    HIP_RC(hipMemcpy(ht.data(), qt, ht.size() * 4, hipMemcpyDeviceToHost));
+    HIP_RC(hipMemcpy(hw.data(), qw, hw.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < ht.size(); ++i)
+        if (ht[i] >= 0) dense[i / (size_t)q_len * V + (size_t)ht[i]] = hw[i];
+    HIP_RC(hipMemcpy(rows, dense.data(), dense.size() * 4, hipMemcpyHostToDevice));
+    for (int stage = 0; stage < 4; ++stage) {
+        const int n = stage == 0 ? std::min(iters, 3) : iters;   // a build is milliseconds
+        for (int i = stage == 0 ? -1 : -3; i < n; ++i) {
+            if (i == 0) HIP_RC(hipEventRecord(ev.a, E.s));
+            int rc = 0;
+            if (stage == 0) rc = launch_sparse_invert(store, table, 0, n_docs, V, kSparseInvBlock, inv_rows, inv, E.s);
+            if (stage == 1) rc = launch_sparse_inv_search(inv, inv_rows, table, n_docs, V, kSparseInvBlock, qt, qw, B, q_len, k, part, sc, ids, E.s);
+            if (stage == 2) rc = launch_sparse_scan_batch(store, table, used, n_docs, V, qt, qw, B, q_len, k, img, part, sc, ids, E.s);
+            if (stage == 3) rc = launch_sparse_scan(store, table, used, n_docs, V, rows, B, k, qtab, part, sc, ids, E.s);
+            if (rc != 0) return -1;
+        }
+        HIP_RC(hipEventRecord(ev.b, E.s));
+        HIP_RC(hipEventSynchronize(ev.b));
+        float ms = 0.f;
+        HIP_RC(hipEventElapsedTime(&ms, ev.a, ev.b));
+        avg_us[stage] = ms * 1000.f / (float)n;
+    }
+    return hook_finish();
+}

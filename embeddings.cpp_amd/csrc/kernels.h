@@ -511,6 +511,35 @@ int launch_sparse_scan_batch(const uint32_t *store, const void *d_table, const i
                              const int32_t *d_terms, const float *d_weights, int B, int q_top, int k, void *images,
                              void *partial, float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg = 0,
                              int *ran_wg = nullptr);
+// Block-local inverted lists and the term-major search (sparse_invert.hip).  A block is
+// inv_block consecutive documents (a multiple of 64, at most 65,536; the default below keeps
+// 64 KiB of f32 accumulators in LDS); rows: uint32 [blocks][V + 1], the lists' offsets from the
+// block's first posting; inv: the postings regrouped by term, uint32 = id within the block |
+// f16 weight bits << 16, block b's at posting 16 table[b inv_block].x, the order within a list
+// free.  sparse_inv_rows_bytes: the rows of a store of cap_docs documents.
+constexpr int kSparseInvBlock = 16384;
+int sparse_inv_prepare_device();
+size_t sparse_inv_rows_bytes(int64_t cap_docs, int V, int inv_block);
+size_t sparse_inv_partial_bytes();
+// The image of the blocks that hold documents d0 .. d1 - 1 (d0 a block's first document),
+// built on the device: zero, count, prefix, fill.  -1 on bad arguments, -3: launch refused.
+int launch_sparse_invert(const uint32_t *store, const void *d_table, int d0, int d1, int V, int inv_block, uint32_t *rows,
+                         uint32_t *inv, hipStream_t s);
+// The search's launch rule: the workgroups per query (*ran_wg too) and the LDS bytes of one.
+int sparse_inv_grid(int n_docs, int inv_block, int B, int q_top, int k, int max_wg, int *ran_wg, size_t *lds);
+// launch_sparse_scan_batch's arguments and result contract over the inverted image of all
+// n_docs documents; the score is s = +0, then s = fmaf(f16(weight_i), w, s) over the query's
+// slots i in slot order whose term the document holds (w the stored f16): not the document-
+// major scans' bits, which fold 16 sub-sums.  One search kernel and launch_search_merge.
+int launch_sparse_inv_search(const uint32_t *inv, const uint32_t *rows, const void *d_table, int n_docs, int V,
+                             int inv_block, const int32_t *d_terms, const float *d_weights, int B, int q_top, int k,
+                             void *partial, float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg = 0,
+                             int *ran_wg = nullptr);
+// Benches: heavy term j < kSparseHeavyTerms set in d_rows f32 [n][V] at weight 2 + j / 8, in a
+// share 1/2 (3/4)^j of the rows (all_of == 0), or the first all_of heavy terms in every row.
+constexpr int kSparseHeavyTerms = 16;
+constexpr int sparse_bench_heavy_term(int j, int V) { return (j + 1) * (V / (kSparseHeavyTerms + 1)); }
+int launch_sparse_skew_rows(float *d_rows, int n, int V, uint32_t seed, int all_of, hipStream_t s);
 
 // Diagnostics: *cnt += number of non-finite values in p[0..n) (f32, or f16 if f16).
 void launch_count_nonfinite(const void *p, size_t n, int f16, unsigned *cnt, hipStream_t s);

@@ -5,7 +5,9 @@
 // per document.  Dense rows become documents on the device: top-n selection, f16 rounding,
 // padding and the offsets (a prefix sum of the counts the host never sees).  The host knows
 // the used units only as an upper bound and asks the device when the bound stops an add.
-// The ordering rules are the other two stores' (store_common.h).
+// The ordering rules are the other two stores' (store_common.h).  Beside the forward store an
+// inverted image (block-local term lists) is built on request and covers
+// inverted_docs documents; the inverted search refuses to run while that is not all of them.
 #include "bert.h"
 #include "bert_hip.h"
 
@@ -47,6 +49,11 @@ struct bertx_spindex {
     void *qimage = nullptr;
     int grid_cap = 0, last_grid = 0;       // bertx_test_spindex_grid
     int last_passes = 0;                   // bertx_test_spindex_last_passes
+    // the inverted image (sparse_invert.hip), allocated by the first build
+    int inv_block = emb::kSparseInvBlock;
+    int64_t inverted_docs = 0;
+    uint32_t *inv = nullptr, *inv_rows = nullptr;   // cap_units * 16 postings; offset rows of every block
+    size_t inv_rows_bytes = 0;
     hipStream_t stream = nullptr;
     emb::StoreOrder ord;
     std::mutex mu;
@@ -57,7 +64,7 @@ struct bertx_spindex {
         if (ord.done) (void)ord.wait();
         for (void *p : {(void *)store, (void *)table, (void *)d_used, (void *)sel_terms, (void *)sel_count,
                         (void *)sel_weights, (void *)st_rows, (void *)st_scores, (void *)st_ids, qtab, partial,
-                        (void *)st_qterms, (void *)st_qweights, qimage})
+                        (void *)st_qterms, (void *)st_qweights, qimage, (void *)inv, (void *)inv_rows})
             if (p) (void)hipFree(p);
         if (ord.done) (void)hipEventDestroy(ord.done);
         if (stream) (void)hipStreamDestroy(stream);
@@ -152,6 +159,60 @@ int32_t search_sparse_device_locked(bertx_spindex &sp, const int32_t *d_terms, c
     sp.last_passes = (B + NQ - 1) / NQ;
     return launch_sparse_scan_batch(sp.store, sp.table, sp.d_used, (int)sp.n_docs, sp.V, d_terms, d_weights, B, q_top, k,
                                     sp.qimage, sp.partial, d_scores, d_ids, s, sp.grid_cap, &sp.last_grid);
+}
+
+// Inverts the blocks that are not yet inverted, or have grown, on s.  The first call
+// allocates the image for the store's whole capacity.
+int32_t build_inverted_locked(bertx_spindex &sp, hipStream_t s)
+{
+    if (sp.inverted_docs == sp.n_docs) return 0;
+    const size_t need = sparse_inv_rows_bytes(sp.cap_docs, sp.V, sp.inv_block);
+    if (!sp.inv || sp.inv_rows_bytes < need) {
+        HIP_RC(sp.ord.wait());   // inv_block changes only while nothing is inverted: no row is lost
+        if (sp.inv_rows) (void)hipFree(sp.inv_rows);
+        sp.inv_rows = nullptr;
+        sp.inv_rows_bytes = 0;
+        if (hipMalloc((void **)&sp.inv_rows, need) != hipSuccess ||
+            (!sp.inv && hipMalloc((void **)&sp.inv, (size_t)sp.cap_units * 64) != hipSuccess)) {
+            (void)hipGetLastError();
+            errorf("bertx_spindex_build_inverted: device %d could not allocate %zu bytes\n", sp.ordinal,
+                   need + (size_t)sp.cap_units * 64);
+            return -2;
+        }
+        sp.inv_rows_bytes = need;
+    }
+    const int64_t d0 = sp.inverted_docs / sp.inv_block * sp.inv_block;
+    Ordered o(sp.ord, s);
+    const int rc = launch_sparse_invert(sp.store, sp.table, (int)d0, (int)sp.n_docs, sp.V, sp.inv_block, sp.inv_rows, sp.inv, s);
+    if (rc != 0) {
+        errorf("bertx_spindex_build_inverted: device %d refused a launch (%d)\n", sp.ordinal, rc);
+        return rc;
+    }
+    sp.inverted_docs = sp.n_docs;
+    return 0;
+}
+
+int32_t search_inverted_device_locked(bertx_spindex &sp, const int32_t *d_terms, const float *d_weights, int32_t B,
+                                      int32_t q_top, int32_t k, float *d_scores, int32_t *d_ids, hipStream_t s)
+{
+    if (!d_terms || !d_weights || !d_scores || !d_ids || B < 1 || B > 64 || q_top < 1 || q_top > 1024 || k < 1 || k > 128) {
+        errorf("bertx_spindex_search_inverted: B = %d, q_top = %d, k = %d are not in 1 <= B <= 64, 1 <= q_top <= 1024, "
+               "1 <= k <= 128\n", B, q_top, k);
+        return -1;
+    }
+    if (sp.inverted_docs != sp.n_docs) {
+        errorf("bertx_spindex_search_inverted: %lld of %lld documents are inverted; call bertx_spindex_build_inverted\n",
+               (long long)sp.inverted_docs, (long long)sp.n_docs);
+        return -1;
+    }
+    Ordered o(sp.ord, s);
+    sp.last_passes = 1;
+    if (sp.n_docs == 0) {   // nothing was ever built: the scan of an empty store gives the fill
+        return launch_sparse_scan_batch(sp.store, sp.table, sp.d_used, 0, sp.V, d_terms, d_weights, B, q_top, k, sp.qimage,
+                                        sp.partial, d_scores, d_ids, s, sp.grid_cap, &sp.last_grid);
+    }
+    return launch_sparse_inv_search(sp.inv, sp.inv_rows, sp.table, (int)sp.n_docs, sp.V, sp.inv_block, d_terms, d_weights, B,
+                                    q_top, k, sp.partial, d_scores, d_ids, s, sp.grid_cap, &sp.last_grid);
 }
 
 // The results of a search launched on the store's stream into st_scores / st_ids (rc: its
@@ -269,6 +330,7 @@ bertx_spindex *spindex_create_on(int ordinal, int V, int n_top, int64_t cap_docs
     const size_t sel = (size_t)kSparseAddRows * n_top * 4;
     const size_t stq = (size_t)kStage * 1024 * 4;
     const bool ok = sparse_scan_prepare_device() == 0 && sparse_batch_prepare_device() == 0 &&
+                    sparse_inv_prepare_device() == 0 &&
                     hipStreamCreateWithFlags(&sp->stream, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&sp->ord.done, hipEventDisableTiming) == hipSuccess &&
                     hipMalloc((void **)&sp->store, (size_t)sp->cap_units * 64) == hipSuccess &&
@@ -281,7 +343,8 @@ bertx_spindex *spindex_create_on(int ordinal, int V, int n_top, int64_t cap_docs
                     hipMalloc((void **)&sp->st_scores, 64 * 128 * 4) == hipSuccess &&
                     hipMalloc((void **)&sp->st_ids, 64 * 128 * 4) == hipSuccess &&
                     hipMalloc(&sp->qtab, sparse_scan_table_bytes(V)) == hipSuccess &&
-                    hipMalloc(&sp->partial, std::max(sparse_scan_partial_bytes(), sparse_batch_partial_bytes())) == hipSuccess &&
+                    hipMalloc(&sp->partial, std::max({sparse_scan_partial_bytes(), sparse_batch_partial_bytes(),
+                                                     sparse_inv_partial_bytes()})) == hipSuccess &&
                     hipMalloc((void **)&sp->st_qterms, stq) == hipSuccess &&
                     hipMalloc((void **)&sp->st_qweights, stq) == hipSuccess &&
                     hipMalloc(&sp->qimage, sparse_batch_image_bytes()) == hipSuccess &&
@@ -334,6 +397,7 @@ int32_t bertx_spindex_clear(struct bertx_spindex *sp)
     }
     sp->n_docs = 0;
     sp->used_bound = 0;
+    sp->inverted_docs = 0;
     return 0;
 }
 
@@ -551,8 +615,11 @@ int32_t bertx_spindex_search_sparse_device(struct bertx_spindex *sp, const int32
                                             stream ? (hipStream_t)stream : sp->stream);
 }
 
-int32_t bertx_spindex_search_sparse(struct bertx_spindex *sp, const int32_t *terms, const float *weights, int32_t B,
-                                    int32_t q_top, int32_t k, float *scores, int32_t *ids)
+namespace {
+// The host forms of the two sparse-query searches: the refusals, the staging, the search
+// (inverted: over the inverted lists, built first when stale) and the results.
+int32_t search_sparse_host(struct bertx_spindex *sp, const int32_t *terms, const float *weights, int32_t B, int32_t q_top,
+                           int32_t k, float *scores, int32_t *ids, bool inverted)
 {
     if (!sp || !terms || !weights || !scores || !ids || B < 1 || B > kStage || q_top < 1 || q_top > 1024) return -1;
     std::vector<int32_t> seen((size_t)sp->V, -1);   // the query that last held the term
@@ -576,16 +643,83 @@ int32_t bertx_spindex_search_sparse(struct bertx_spindex *sp, const int32_t *ter
         HIP_RC(hipMemcpyAsync(sp->st_qweights, weights, (size_t)B * q_top * 4, hipMemcpyHostToDevice, sp->stream));
     }
     HIP_RC(hipStreamSynchronize(sp->stream));   // the caller's arrays are pageable
-    const int32_t rc = emb::search_sparse_device_locked(*sp, sp->st_qterms, sp->st_qweights, B, q_top, k, sp->st_scores,
-                                                        sp->st_ids, sp->stream);
+    int32_t rc = inverted ? emb::build_inverted_locked(*sp, sp->stream) : 0;
+    if (rc == 0)
+        rc = (inverted ? emb::search_inverted_device_locked : emb::search_sparse_device_locked)(
+            *sp, sp->st_qterms, sp->st_qweights, B, q_top, k, sp->st_scores, sp->st_ids, sp->stream);
     return emb::results_to_host(*sp, rc, B, k, scores, ids);
+}
+}  // namespace
+
+int32_t bertx_spindex_search_sparse(struct bertx_spindex *sp, const int32_t *terms, const float *weights, int32_t B,
+                                    int32_t q_top, int32_t k, float *scores, int32_t *ids)
+{
+    return search_sparse_host(sp, terms, weights, B, q_top, k, scores, ids, false);
+}
+
+int32_t bertx_spindex_search_inverted(struct bertx_spindex *sp, const int32_t *terms, const float *weights, int32_t B,
+                                      int32_t q_top, int32_t k, float *scores, int32_t *ids)
+{
+    return search_sparse_host(sp, terms, weights, B, q_top, k, scores, ids, true);
+}
+
+int32_t bertx_spindex_search_inverted_device(struct bertx_spindex *sp, const int32_t *d_terms, const float *d_weights,
+                                             int32_t B, int32_t q_top, int32_t k, float *d_scores, int32_t *d_ids,
+                                             void *stream)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    return emb::search_inverted_device_locked(*sp, d_terms, d_weights, B, q_top, k, d_scores, d_ids,
+                                              stream ? (hipStream_t)stream : sp->stream);
+}
+
+int32_t bertx_spindex_build_inverted(struct bertx_spindex *sp)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    return emb::build_inverted_locked(*sp, sp->stream);
+}
+
+int32_t bertx_spindex_inverted_docs(struct bertx_spindex *sp)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    return (int32_t)sp->inverted_docs;
+}
+
+int32_t bertx_spindex_inv_block(struct bertx_spindex *sp)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    return sp->inv_block;
+}
+
+int64_t bertx_spindex_inverted_bytes(struct bertx_spindex *sp)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    return sp->inv ? (int64_t)((size_t)sp->cap_units * 64 + sp->inv_rows_bytes) : 0;
+}
+
+int32_t bertx_test_spindex_inv_block(struct bertx_spindex *sp, int32_t docs)
+{
+    if (!sp || docs < 64 || docs > emb::kSparseInvBlock || docs % 64 != 0) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (sp->inverted_docs != 0) return -1;
+    sp->inv_block = docs;
+    return 0;
 }
 
 namespace {
 // The text searches: q_top == 0 searches the forward's dense rows, q_top > 0 selects the
-// q_top largest weights of each row on the device and searches those.
+// q_top largest weights of each row on the device and searches those (inverted: over the
+// inverted lists, built first when stale).
 int32_t search_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts,
-                     int32_t q_top, int32_t k, float *scores, int32_t *ids, const char *who)
+                     int32_t q_top, int32_t k, float *scores, int32_t *ids, const char *who, bool inverted = false)
 {
     int32_t slot = -1;
     if (const int32_t rc = emb::text_ctx_ok(sp, ctx, who, &slot)) return rc;
@@ -600,6 +734,9 @@ int32_t search_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_t
     std::vector<int32_t> flat;
     emb::DevBuf d_tok;
     size_t cap = 0;
+    if (inverted)
+        if (const int32_t rc = emb::build_inverted_locked(*sp, sp->stream)) return rc;
+    const auto sparse_search = inverted ? emb::search_inverted_device_locked : emb::search_sparse_device_locked;
     for (size_t i = 0; i < (size_t)n;) {
         const size_t e = emb::chunk_end([&](size_t j) { return t.lens[j]; }, i, (size_t)n, emb::kChunkTokens, kStage);
         const int32_t m = (int32_t)(e - i);
@@ -612,8 +749,8 @@ int32_t search_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_t
                                                sp->stream);
         }
         if (rc == 0 && q_top > 0)
-            rc = emb::results_to_host(*sp, emb::search_sparse_device_locked(*sp, sp->st_qterms, sp->st_qweights, m, q_top, k,
-                                                                            sp->st_scores, sp->st_ids, sp->stream),
+            rc = emb::results_to_host(*sp, sparse_search(*sp, sp->st_qterms, sp->st_qweights, m, q_top, k, sp->st_scores,
+                                                         sp->st_ids, sp->stream),
                                       m, k, hs.data() + i * k, hi.data() + i * k);
         else if (rc == 0)
             rc = emb::search_to_host(*sp, sp->st_rows, m, k, hs.data() + i * k, hi.data() + i * k);
@@ -641,6 +778,13 @@ int32_t bertx_spindex_search_texts_top(struct bertx_spindex *sp, struct bert_ctx
 {
     if (q_top < 1 || q_top > 1024) return -1;
     return search_texts(sp, ctx, n_threads, n, texts, q_top, k, scores, ids, "bertx_spindex_search_texts_top");
+}
+
+int32_t bertx_spindex_search_texts_inverted(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                            const char **texts, int32_t q_top, int32_t k, float *scores, int32_t *ids)
+{
+    if (q_top < 1 || q_top > 1024) return -1;
+    return search_texts(sp, ctx, n_threads, n, texts, q_top, k, scores, ids, "bertx_spindex_search_texts_inverted", true);
 }
 
 int32_t bertx_spindex_batch_queries(struct bertx_spindex *sp, int32_t q_top, int32_t k)

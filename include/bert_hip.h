@@ -1500,11 +1500,45 @@ BERT_API int32_t bertx_bench_sparse(int32_t d, int32_t V, int32_t n_seqs, int32_
  * search, all on the device, 64 texts per forward.  Equal to bertx_spindex_search_texts when
  * every query has at most q_top positive weights; otherwise the search of the query cut to
  * its q_top largest weights (the selection's rule above).
- * Which to use (DESIGN.md 9i-3 has the measured rows; one MI355X, n_vocab 30,522, 1 M
- * documents of 128 postings, queries of 32 terms, k 10, dense-query / sparse-query search):
- * B 1 362 / 414 us, B 2 387 / 418 us, B 16 3,091 / 453 us, B 64 12,339 / 997 us.  The
- * dense-query search for one or two queries, the sparse-query search from a handful up: at 64
- * queries of 32 terms it takes 2 passes over the store where the dense-query search takes 32.
+ *
+ * Inverted lists.  The two searches above stream every stored posting; the inverted search reads
+ * only the lists the queries name.  A block is bertx_spindex_inv_block(sp) consecutive documents
+ * (16,384; at most 65,536, the local id's 16 bits).  Its inverted image is an offset row uint32
+ * [n_vocab + 1] and the block's postings regrouped by term, one uint32 each: the document's id
+ * within the block in the low 16 bits, the stored f16 weight bits unchanged in the high 16; padding
+ * postings are not copied.  The order within a list is unspecified: no score bit depends on it,
+ * because a document occurs at most once in a list.
+ * bertx_spindex_build_inverted(sp) inverts what is not yet inverted, on the device and on the
+ * store's stream: every complete block once, a partial last block again when it has grown.  The
+ * first build allocates the image for the store's whole capacity, as many posting bytes again plus
+ * (n_vocab + 1) * 4 bytes per block (bertx_spindex_inverted_bytes; 0 before); -2 when that fails.
+ * Later builds and all searches allocate nothing.  bertx_spindex_inverted_docs: the documents the
+ * image covers; _clear resets it to 0.
+ * bertx_spindex_search_inverted_device(sp, d_terms, d_weights, B, q_top, k, d_scores, d_ids,
+ * stream): the query layout, the limits (B <= 64, q_top <= 1,024, k <= 128) and the result contract
+ * of bertx_spindex_search_sparse_device; documents that share no term with a query score +0 and
+ * take part like any other.  A query's terms are distinct (the device form trusts this).
+ * Asynchronous, capturable, allocates nothing.  -1 with a message when inverted_docs != docs: a
+ * stale image is never searched.  Arithmetic of one (query, document) score, f32:
+ *   s = +0; for the query's slots i in slot order whose term the document holds:
+ *       s = fmaf(f16(weight_i), w, s)      (w the stored f16; the product is exact in f32, so
+ *                                           each step rounds once)
+ * The order is the query's slot order; it does not depend on the document, the block, the block
+ * size, B, k or the grid.  These are NOT the bits of the two document-major searches, which fold
+ * 16 sub-sums; where every partial sum is exactly representable the three agree bit for bit.
+ * bertx_spindex_search_inverted is the host form, with bertx_spindex_search_sparse's refusals; it
+ * builds first when the image is stale.  bertx_spindex_search_texts_inverted(sp, ctx, n_threads,
+ * n, texts, q_top, k, scores, ids): the sparse forward, the selection, the build if stale and
+ * the inverted search, as bertx_spindex_search_texts_top.
+ *
+ * Which to use (DESIGN.md 9i-4 has the measured rows; one MI355X, n_vocab 30,522, 1 M
+ * documents of 128 postings, queries of 32 hashed-uniform terms, k 10, dense-query /
+ * sparse-query / inverted search): B 1 360 / 415 / 80 us, B 2 387 / 422 / 82 us, B 16 3,094 /
+ * 457 / 163 us, B 64 12,351 / 998 / 362 us; over 8 M documents B 1 2,392 / 2,740 / 182 us.
+ * With heavy terms in documents and queries (ten times the postings per query) the inverted
+ * search takes 95 us at B 1 and 656 us at B 64.  The inverted search wherever its image (the
+ * posting bytes again, 11 ms of build per million documents) is affordable; without it the
+ * dense-query search for one or two queries and the sparse-query search from a handful up.
  *
  * bertx_test_sparse_select (parity hook; host buffers, device 0): rows f32 [S][V] ->
  * terms int32 [S][n], weights f32 [S][n] (the input's bits), count int32 [S]; slots past a
@@ -1521,10 +1555,18 @@ BERT_API int32_t bertx_bench_sparse(int32_t d, int32_t V, int32_t n_seqs, int32_
  * and B queries of q_len terms selected from hashed rows as the documents are; avg_us[0] the
  * query-image kernel, avg_us[1] the whole sparse-query search, avg_us[2]
  * bertx_spindex_search_device's scan of the same queries densified.
+ * bertx_test_spindex_grid's bound also caps the inverted search's workgroups per query, and
+ * _last_grid reports the capped count.  bertx_test_spindex_inv_block(sp, docs): the block size,
+ * a multiple of 64 up to the default, only while nothing is inverted (-1 otherwise).
+ * bertx_bench_spindex_inverted(V, n_docs, doc_len, B, q_len, k, skew, iters, avg_us): the same
+ * store and queries; skew 1 plants 16 heavy terms before the selection, term j in a share
+ * 1/2 (3/4)^j of the documents and the first four in every query.  avg_us[0] the build of the
+ * whole image, avg_us[1] the inverted search, avg_us[2] the sparse-query search, avg_us[3] the
+ * dense-query search.
  *
- * Not provided: inverted lists and any dynamic pruning (WAND, block-max); int8 or impact-
- * quantized weights; deletion and filters; scoring listed ids; a mode of the `search` tool;
- * saving and loading; vocabularies above 65,536 terms.
+ * Not provided: dynamic pruning (WAND, block-max); int8 or impact-quantized weights; deletion
+ * and filters; scoring listed ids; a mode of the `search` tool; saving and loading; an inverted
+ * image without the forward store; vocabularies above 65,536 terms.
  */
 struct bertx_spindex;
 BERT_API struct bertx_spindex *bertx_spindex_create(struct bert_ctx *ctx, int32_t slot, int32_t n_vocab, int32_t n_top,
@@ -1560,6 +1602,21 @@ BERT_API int32_t bertx_spindex_search_texts_top(struct bertx_spindex *sp, struct
                                                 int32_t n, const char **texts, int32_t q_top, int32_t k, float *scores,
                                                 int32_t *ids);
 BERT_API int32_t bertx_spindex_batch_queries(struct bertx_spindex *sp, int32_t q_top, int32_t k);
+BERT_API int32_t bertx_spindex_build_inverted(struct bertx_spindex *sp);
+BERT_API int32_t bertx_spindex_inverted_docs(struct bertx_spindex *sp);
+BERT_API int64_t bertx_spindex_inverted_bytes(struct bertx_spindex *sp);
+BERT_API int32_t bertx_spindex_inv_block(struct bertx_spindex *sp);
+BERT_API int32_t bertx_spindex_search_inverted_device(struct bertx_spindex *sp, const int32_t *d_terms,
+                                                      const float *d_weights, int32_t B, int32_t q_top, int32_t k,
+                                                      float *d_scores, int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_spindex_search_inverted(struct bertx_spindex *sp, const int32_t *terms, const float *weights,
+                                               int32_t B, int32_t q_top, int32_t k, float *scores, int32_t *ids);
+BERT_API int32_t bertx_spindex_search_texts_inverted(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads,
+                                                     int32_t n, const char **texts, int32_t q_top, int32_t k,
+                                                     float *scores, int32_t *ids);
+BERT_API int32_t bertx_test_spindex_inv_block(struct bertx_spindex *sp, int32_t docs);
+BERT_API int32_t bertx_bench_spindex_inverted(int32_t V, int32_t n_docs, int32_t doc_len, int32_t B, int32_t q_len,
+                                              int32_t k, int32_t skew, int32_t iters, float *avg_us);
 BERT_API int32_t bertx_forward_sparse_top(struct bert_ctx *ctx, int32_t slot, int32_t n, bert_vocab_id **batch_tokens,
                                           int32_t *n_tokens, int32_t n_top, int32_t *terms, float *weights,
                                           int32_t *counts);

@@ -14,6 +14,10 @@ One JSON line per point into --out.
 --batch-leg measures bertx_bench_spindex_batch instead: per point (n_docs, B) the
 query-image kernel, the whole sparse-query search of B queries of --q-len terms and the dense-query
 search of the same queries densified, in the same process and round.
+
+--inverted-leg measures bertx_bench_spindex_inverted: per point (n_docs, B, skew) the
+build of the inverted image, the inverted search, the sparse-query search and the dense-query search
+of the same queries, in the same process and round; skew 1 plants heavy terms in documents and queries.
 """
 import argparse
 import ctypes
@@ -41,12 +45,34 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 2, 64])
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--batch-leg", action="store_true")
+    ap.add_argument("--inverted-leg", action="store_true")
+    ap.add_argument("--skews", type=int, nargs="+", default=[0, 1])
     ap.add_argument("--q-len", type=int, default=32)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "spindex_bench.jsonl"))
     a = ap.parse_args()
     lib = bertpy.load_lib()
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "a") as f:
+        for n_docs, B, skew in [(n, B, s) for n in a.docs for B in a.batches for s in a.skews] if a.inverted_leg else []:
+            iters = 20 if B <= 2 else 5
+            legs = {"build_us": [], "inverted_us": [], "sparse_query_us": [], "dense_query_us": []}
+            us4 = (ctypes.c_float * 4)()
+            for _ in range(a.rounds):
+                assert lib.bertx_bench_spindex_inverted(V, n_docs, DOC_LEN, B, a.q_len, K, skew, iters, us4) == 0
+                for name, us in zip(legs, us4):
+                    legs[name].append(us)
+            rec = {"leg": "inverted", "V": V, "n_docs": n_docs, "doc_len": DOC_LEN, "B": B, "q_len": a.q_len, "k": K,
+                   "skew": skew, "rounds": a.rounds, "iters": iters, **{name: spread(t) for name, t in legs.items()}}
+            rec["build_us_per_million_docs"] = round(rec["build_us"]["median"] * 1e6 / n_docs, 1)
+            rec["inverted_bytes_added"] = n_docs * DOC_LEN * 4 + -(-n_docs // 16384) * (V + 1) * 4
+            rec["slowest_inverted_beats_fastest_dense"] = max(legs["inverted_us"]) < min(legs["dense_query_us"])
+            rec["slowest_inverted_beats_fastest_sparse"] = max(legs["inverted_us"]) < min(legs["sparse_query_us"])
+            rec["time"] = time.strftime("%Y-%m-%dT%H:%M:%S")
+            f.write(json.dumps(rec) + "\n")
+            f.flush()
+            print(json.dumps(rec), flush=True)
+        if a.inverted_leg:
+            return
         for n_docs in a.docs if a.batch_leg else []:
             for B in a.batches:
                 iters = 20 if B <= 2 else 5
