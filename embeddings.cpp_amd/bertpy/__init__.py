@@ -499,6 +499,27 @@ def load_lib(path=None):
         L.bertx_test_spindex_inv_block.argtypes = [vp, c_i32]
         L.bertx_bench_spindex_inverted.restype = c_i32
         L.bertx_bench_spindex_inverted.argtypes = [c_i32] * 8 + [c_f32p]
+        L.bertx_spindex_remove.restype = c_i32
+        L.bertx_spindex_remove.argtypes = [vp, vp, c_i32]
+        L.bertx_spindex_remove_device.restype = c_i32
+        L.bertx_spindex_remove_device.argtypes = [vp, vp, c_i32, vp]
+        for fn in (L.bertx_spindex_live, L.bertx_test_spindex_last_masked):
+            fn.restype = c_i32
+            fn.argtypes = [vp]
+        L.bertx_spindex_deleted.restype = c_i32
+        L.bertx_spindex_deleted.argtypes = [vp, c_i32, c_i32, vp]
+        L.bertx_spindex_search_filtered.restype = c_i32
+        L.bertx_spindex_search_filtered.argtypes = [vp, vp, c_i32, c_i32, vp, c_i32, c_i32, vp, vp]
+        L.bertx_spindex_search_filtered_device.restype = c_i32
+        L.bertx_spindex_search_filtered_device.argtypes = [vp, vp, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp]
+        for fn in (L.bertx_spindex_search_sparse_filtered, L.bertx_spindex_search_inverted_filtered):
+            fn.restype = c_i32
+            fn.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, vp]
+        for fn in (L.bertx_spindex_search_sparse_filtered_device, L.bertx_spindex_search_inverted_filtered_device):
+            fn.restype = c_i32
+            fn.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp]
+        L.bertx_bench_spindex_masked.restype = c_i32
+        L.bertx_bench_spindex_masked.argtypes = [c_i32] * 8 + [c_f32p]
     except AttributeError:
         pass
     L.bertx_bench_gemm.restype = c_i32
@@ -1473,6 +1494,33 @@ class BertSparseIndex:
     def clear(self):
         self.lib.bertx_spindex_clear(self.sp)
 
+    _allow = BertIndex._allow
+
+    def remove(self, ids):
+        """Delete the listed documents: no search returns them again, their ids are not reused,
+        len() and postings() do not change, doc() still answers and the inverted lists need no
+        rebuild.  Ids outside the store are ignored, repeats are harmless."""
+        a = np.ascontiguousarray(np.asarray(ids, np.int32).ravel())
+        self._checked(-abs(self.lib.bertx_spindex_remove(self.sp, a.ctypes.data, a.size)), "bertx_spindex_remove")
+
+    def live(self):
+        """len() minus the deleted documents."""
+        return int(self.lib.bertx_spindex_live(self.sp))
+
+    def deleted(self, first, n):
+        """bool [n]: whether documents first .. first + n - 1 are deleted."""
+        out = np.zeros(n, np.uint8)
+        if n and self.lib.bertx_spindex_deleted(self.sp, first, n, out.ctypes.data) != 0:
+            raise RuntimeError("bertx_spindex_deleted failed")
+        return out.astype(bool)
+
+    @staticmethod
+    def _filter_args(f, nf, words, b):
+        """The (filters, n_filters, words) of the library call that starts at query b."""
+        if f is None:
+            return None, 0, 0
+        return (f[b:] if nf > 1 else f).ctypes.data, nf if nf <= 1 else min(64, nf - b), words
+
     def _dense(self, a):
         a = np.ascontiguousarray(np.asarray(a, np.float32))
         if a.ndim == 1:
@@ -1510,9 +1558,11 @@ class BertSparseIndex:
         n = self._checked(self.lib.bertx_spindex_doc(self.sp, i, terms.ctypes.data, wts.ctypes.data), "bertx_spindex_doc")
         return terms[:n].copy(), wts[:n].copy()
 
-    def search(self, queries, k):
+    def search(self, queries, k, allow=None):
         """(scores f32 [B][k], ids int32 [B][k]); queries: dense [B][n_vocab] (or one row), or a list
-        of lists of (term, weight) pairs, densified here.  Any B: 64 queries per call of the library."""
+        of lists of (term, weight) pairs, densified here.  Any B: 64 queries per call of the library.
+        Deleted documents are never returned; allow (pack_allow: bool [docs], [B][docs] for one filter
+        per query, or packed uint32 words) limits the search to the documents it marks."""
         if isinstance(queries, (list, tuple)) and len(queries) and isinstance(queries[0], (list, tuple)):
             q = np.zeros((len(queries), self.n_vocab), np.float32)
             for b, pairs in enumerate(queries):
@@ -1522,18 +1572,22 @@ class BertSparseIndex:
             q = self._dense(queries)
         B = q.shape[0]
         scores, ids = np.zeros((B, k), np.float32), np.zeros((B, k), np.int32)
+        f, nf, words = self._allow(allow, B)
         for b in range(0, B, 64):
             m = min(64, B - b)
-            self._checked(-abs(self.lib.bertx_spindex_search(self.sp, q[b:].ctypes.data, m, k, scores[b:].ctypes.data,
-                                                             ids[b:].ctypes.data)), "bertx_spindex_search")
+            fp, n, w = self._filter_args(f, nf, words, b)
+            self._checked(-abs(self.lib.bertx_spindex_search_filtered(self.sp, q[b:].ctypes.data, m, k, fp, n, w,
+                                                                      scores[b:].ctypes.data, ids[b:].ctypes.data)),
+                          "bertx_spindex_search")
         return scores, ids
 
-    def search_sparse(self, terms, weights=None, k=10):
+    def search_sparse(self, terms, weights=None, k=10, allow=None):
         """(scores f32 [B][k], ids int32 [B][k]) of sparse queries: terms int32 [B][q_top] and weights
         f32 [B][q_top] with -1 in the empty slots (forward_sparse_top's output), or, weights None, a list
         of lists of (term, weight) pairs, padded here.  The bits of search() on the densified queries,
         32, 16, 8 or 4 queries per pass over the store.  Any B: 64 queries per call of the library."""
-        return self._search_pairs(self.lib.bertx_spindex_search_sparse, "bertx_spindex_search_sparse", terms, weights, k)
+        return self._search_pairs(self.lib.bertx_spindex_search_sparse_filtered, "bertx_spindex_search_sparse", terms,
+                                  weights, k, allow)
 
     def build_inverted(self):
         """Inverts the documents added since the last build (block-local term lists, on the device)."""
@@ -1543,13 +1597,14 @@ class BertSparseIndex:
     def inverted_docs(self):
         return int(self.lib.bertx_spindex_inverted_docs(self.sp))
 
-    def search_inverted(self, terms, weights=None, k=10):
+    def search_inverted(self, terms, weights=None, k=10, allow=None):
         """search_sparse's arguments and result contract over the inverted lists, which are built first
         when stale: only the lists the queries name are read.  The score adds the query's terms in slot
         order (bert_hip.h "Inverted lists"), so its bits are not search_sparse's."""
-        return self._search_pairs(self.lib.bertx_spindex_search_inverted, "bertx_spindex_search_inverted", terms, weights, k)
+        return self._search_pairs(self.lib.bertx_spindex_search_inverted_filtered, "bertx_spindex_search_inverted", terms,
+                                  weights, k, allow)
 
-    def _search_pairs(self, fn, name, terms, weights, k):
+    def _search_pairs(self, fn, name, terms, weights, k, allow=None):
         if weights is None:
             q_top = max([len(p) for p in terms] + [1])
             t, w = np.full((len(terms), q_top), -1, np.int32), np.zeros((len(terms), q_top), np.float32)
@@ -1565,20 +1620,30 @@ class BertSparseIndex:
                 raise ValueError("expected terms and weights of one shape [B][q_top], got %r and %r" % (t.shape, w.shape))
         B, q_top = t.shape
         scores, ids = np.zeros((B, k), np.float32), np.zeros((B, k), np.int32)
+        f, nf, words = self._allow(allow, B)
         for b in range(0, B, 64):
             m = min(64, B - b)
-            self._checked(-abs(fn(self.sp, t[b:].ctypes.data, w[b:].ctypes.data, m, q_top, k, scores[b:].ctypes.data,
-                               ids[b:].ctypes.data)), name)
+            fp, n, fw = self._filter_args(f, nf, words, b)
+            self._checked(-abs(fn(self.sp, t[b:].ctypes.data, w[b:].ctypes.data, m, q_top, k, fp, n, fw,
+                               scores[b:].ctypes.data, ids[b:].ctypes.data)), name)
         return scores, ids
 
-    def search_texts(self, texts, k, q_top=None, inverted=False):
+    def search_texts(self, texts, k, q_top=None, inverted=False, allow=None):
         """q_top: the queries cut to their q_top largest weights on the device and searched sparse;
-        inverted (with q_top): over the inverted lists, built first when stale."""
+        inverted (with q_top): over the inverted lists, built first when stale.  allow (as in
+        search()): the queries' weights come back from the device (forward_sparse / _top) and go
+        through the filtered search of the same kind, which returns the same bits."""
         n = len(texts)
+        if inverted and q_top is None:
+            raise ValueError("search_texts(inverted=True) needs q_top")
+        if allow is not None:
+            toks = [np.asarray(self.model.tokenize(t)[0], np.int32) for t in texts]
+            if q_top is None:
+                return self.search(self.model.forward_sparse(toks), k, allow)
+            terms, wts, _ = self.model.forward_sparse_top(toks, q_top)
+            return (self.search_inverted if inverted else self.search_sparse)(terms, wts, k, allow)
         scores, ids = np.zeros((n, k), np.float32), np.zeros((n, k), np.int32)
         if inverted:
-            if q_top is None:
-                raise ValueError("search_texts(inverted=True) needs q_top")
             rc = self.lib.bertx_spindex_search_texts_inverted(self.sp, self.model.ctx, self.model.N_THREADS, n,
                                                               BertIndex._texts(texts), q_top, k, scores.ctypes.data,
                                                               ids.ctypes.data)

@@ -1569,3 +1569,93 @@ extern "C" int32_t bertx_bench_spindex_inverted(int32_t V, int32_t n_docs, int32
     }
     return hook_finish();
 }
+
+// The three searches under a mask (bert_hip.h "Sparse index", "Deleting documents and filtered
+// search"): device 0, no context, bertx_bench_spindex_inverted's store and
+// queries without skew, built once.  Pattern 0: no mask, the unmasked kernels; 1: an all-ones
+// filter; 2: one document in two removed by a hash of the id; 3: a filter that admits the
+// contiguous sixteenth of the ids from n_docs / 2 on.  us [4][3][reps]: per pattern the inverted,
+// the sparse-query and the dense-query search, each sample the average of `iters` launches after
+// 3; the patterns alternate within a repetition, so drift falls on all of them alike.
+extern "C" int32_t bertx_bench_spindex_masked(int32_t V, int32_t n_docs, int32_t doc_len, int32_t B, int32_t q_len,
+                                              int32_t k, int32_t iters, int32_t reps, float *us)
+{
+    using namespace emb;
+    if (V < 1 || V > 65536 || n_docs < 16 || doc_len < 1 || doc_len > 1024 || 2 * doc_len > V || B < 1 || B > 64 ||
+        sparse_batch_queries(V, q_len, k) == 0 || 2 * q_len > V || iters < 1 || reps < 1 || !us || hip_device_count() == 0)
+        return -1;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    if (sparse_scan_prepare_device() != 0 || sparse_batch_prepare_device() != 0 || sparse_inv_prepare_device() != 0) return -1;
+    const int chunk = std::min<int>(kSparseAddRows, n_docs);
+    const size_t units = (size_t)n_docs * ((size_t)(doc_len + 15) / 16), words = (size_t)index_mask_words(n_docs);
+    // the masks: no tombstones, the hashed half, all ones, the sixteenth
+    std::vector<uint32_t> half(words, 0u), ones(words, 0xffffffffu), tenant(words, 0u);
+    for (int64_t i = 0; i < n_docs; ++i) {
+        uint32_t h = (uint32_t)i * 0x9e3779b1u;
+        h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15;
+        if (h & 1u) half[(size_t)(i >> 5)] |= 1u << (i & 31);
+        if (i >= n_docs / 2 && i < n_docs / 2 + n_docs / 16) tenant[(size_t)(i >> 5)] |= 1u << (i & 31);
+    }
+    HookBufs H;
+    float *rows = (float *)H.up(nullptr, 0, (size_t)std::max(chunk, B) * V * 4);
+    int32_t *terms = (int32_t *)H.up(nullptr, 0, (size_t)chunk * doc_len * 4), *count = (int32_t *)H.up(nullptr, 0, (size_t)chunk * 4);
+    float *wts = (float *)H.up(nullptr, 0, (size_t)chunk * doc_len * 4);
+    uint32_t *store = (uint32_t *)H.up(nullptr, 0, units * 64), *inv = (uint32_t *)H.up(nullptr, 0, units * 64);
+    uint32_t *inv_rows = (uint32_t *)H.up(nullptr, 0, sparse_inv_rows_bytes(n_docs, V, kSparseInvBlock));
+    int32_t *table = (int32_t *)H.up(nullptr, 0, (size_t)n_docs * 8), *used = (int32_t *)H.up(nullptr, 0, 16);
+    int32_t *qt = (int32_t *)H.up(nullptr, 0, (size_t)B * q_len * 4), *qc = (int32_t *)H.up(nullptr, 0, (size_t)B * 4);
+    float *qw = (float *)H.up(nullptr, 0, (size_t)B * q_len * 4), *sc = (float *)H.up(nullptr, 0, (size_t)B * k * 4);
+    int32_t *ids = (int32_t *)H.up(nullptr, 0, (size_t)B * k * 4);
+    void *qtab = H.up(nullptr, 0, sparse_scan_table_bytes(V)), *img = H.up(nullptr, 0, sparse_batch_image_bytes());
+    void *part = H.up(nullptr, 0, std::max({sparse_scan_partial_bytes(), sparse_batch_partial_bytes(), sparse_inv_partial_bytes()}));
+    const uint32_t *d_none = (const uint32_t *)H.up(nullptr, 0, words * 4), *d_half = (const uint32_t *)H.up(half.data(), words * 4, 0);
+    const uint32_t *d_ones = (const uint32_t *)H.up(ones.data(), words * 4, 0), *d_tenant = (const uint32_t *)H.up(tenant.data(), words * 4, 0);
+    if (H.bad) return -1;
+    const SearchMask masks[4] = {{nullptr, nullptr, 0}, {d_none, d_ones, 0}, {d_half, nullptr, 0}, {d_none, d_tenant, 0}};
+    struct Str {
+        hipStream_t s = nullptr;
+        ~Str() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    } E;
+    HIP_RC(hipStreamCreateWithFlags(&E.s, hipStreamNonBlocking));
+    EventPair ev;
+    HIP_RC(ev.create());
+    for (int64_t i = 0; i < n_docs; i += chunk) {
+        const int m = (int)std::min<int64_t>(chunk, n_docs - i);
+        if (launch_unit_rows(rows, m, V, 12345u + (uint32_t)i, E.s) != 0 ||
+            launch_sparse_select(rows, m, V, doc_len, terms, wts, count, E.s) != 0 ||
+            launch_sparse_pack(terms, wts, count, m, doc_len, table + 2 * i, used, store, E.s) != 0)
+            return -1;
+    }
+    if (launch_unit_rows(rows, B, V, 4242u, E.s) != 0 || launch_sparse_select(rows, B, V, q_len, qt, qw, qc, E.s) != 0 ||
+        launch_sparse_invert(store, table, 0, n_docs, V, kSparseInvBlock, inv_rows, inv, E.s) != 0)
+        return -1;
+    // the same queries dense: the selected weights at their terms, zero elsewhere
+    std::vector<int32_t> ht((size_t)B * q_len);
+    std::vector<float> hw((size_t)B * q_len), dense((size_t)B * V, 0.f);
+    HIP_RC(hipStreamSynchronize(E.s));
+    HIP_RC(hipMemcpy(ht.data(), qt, ht.size() * 4, hipMemcpyDeviceToHost));
+    HIP_RC(hipMemcpy(hw.data(), qw, hw.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < ht.size(); ++i)
+        if (ht[i] >= 0) dense[i / (size_t)q_len * V + (size_t)ht[i]] = hw[i];
+    HIP_RC(hipMemcpy(rows, dense.data(), dense.size() * 4, hipMemcpyHostToDevice));
+    for (int r = 0; r < reps; ++r)
+        for (int pat = 0; pat < 4; ++pat)
+            for (int stage = 0; stage < 3; ++stage) {
+                const SearchMask *mk = pat == 0 ? nullptr : &masks[pat];
+                for (int i = -3; i < iters; ++i) {
+                    if (i == 0) HIP_RC(hipEventRecord(ev.a, E.s));
+                    int rc = 0;
+                    if (stage == 0) rc = launch_sparse_inv_search(inv, inv_rows, table, n_docs, V, kSparseInvBlock, qt, qw, B, q_len, k, part, sc, ids, E.s, 0, nullptr, mk);
+                    if (stage == 1) rc = launch_sparse_scan_batch(store, table, used, n_docs, V, qt, qw, B, q_len, k, img, part, sc, ids, E.s, 0, nullptr, mk);
+                    if (stage == 2) rc = launch_sparse_scan(store, table, used, n_docs, V, rows, B, k, qtab, part, sc, ids, E.s, 0, nullptr, mk);
+                    if (rc != 0) return -1;
+                }
+                HIP_RC(hipEventRecord(ev.b, E.s));
+                HIP_RC(hipEventSynchronize(ev.b));
+                float ms = 0.f;
+                HIP_RC(hipEventElapsedTime(&ms, ev.a, ev.b));
+                us[((size_t)pat * 3 + stage) * reps + r] = ms * 1000.f / (float)iters;
+            }
+    return hook_finish();
+}

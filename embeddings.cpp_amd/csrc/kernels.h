@@ -488,9 +488,14 @@ size_t sparse_scan_partial_bytes();
 // d_scores / d_ids [B][k]: per dense query f32 [V] the k best documents, launch_search's result
 // contract.  One table kernel, then per pass the scan and launch_search_merge.  max_wg, ran_wg
 // as on launch_maxsim.  1 <= B <= 64, 1 <= k <= 128; -1 otherwise, -3: launch refused.
+// mask (here and on the two searches below; may be null): a SearchMask over documents, tomb the
+// store's tombstones, filt the call's filters (null: none; stride 0: one for every query); the
+// masked kernels offer a document only when it is admissible as well (bert_hip.h "Sparse index",
+// "Deleting documents and filtered search").  null launches the unmasked instantiations with
+// the arguments above and nothing else.
 int launch_sparse_scan(const uint32_t *store, const void *d_table, const int32_t *d_used, int n_docs, int V,
                        const float *d_queries, int B, int k, void *qtab, void *partial, float *d_scores, int32_t *d_ids,
-                       hipStream_t s, int max_wg = 0, int *ran_wg = nullptr);
+                       hipStream_t s, int max_wg = 0, int *ran_wg = nullptr, const SearchMask *mask = nullptr);
 // The batched scan of sparse queries (sparse_batch.hip).  Queries of one pass: the largest of
 // 32, 16, 8, 4 whose image (a rank dictionary over V and f16 weights [min(NQ q_top, V)][NQ]),
 // lists and staging tile fit in LDS, 0 when none does or an argument is out of range; the
@@ -510,7 +515,7 @@ int launch_sparse_batch_image(const int32_t *d_terms, const float *d_weights, in
 int launch_sparse_scan_batch(const uint32_t *store, const void *d_table, const int32_t *d_used, int n_docs, int V,
                              const int32_t *d_terms, const float *d_weights, int B, int q_top, int k, void *images,
                              void *partial, float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg = 0,
-                             int *ran_wg = nullptr);
+                             int *ran_wg = nullptr, const SearchMask *mask = nullptr);
 // Block-local inverted lists and the term-major search (sparse_invert.hip).  A block is
 // inv_block consecutive documents (a multiple of 64, at most 65,536; the default below keeps
 // 64 KiB of f32 accumulators in LDS); rows: uint32 [blocks][V + 1], the lists' offsets from the
@@ -525,8 +530,10 @@ size_t sparse_inv_partial_bytes();
 // built on the device: zero, count, prefix, fill.  -1 on bad arguments, -3: launch refused.
 int launch_sparse_invert(const uint32_t *store, const void *d_table, int d0, int d1, int V, int inv_block, uint32_t *rows,
                          uint32_t *inv, hipStream_t s);
-// The search's launch rule: the workgroups per query (*ran_wg too) and the LDS bytes of one.
-int sparse_inv_grid(int n_docs, int inv_block, int B, int q_top, int k, int max_wg, int *ran_wg, size_t *lds);
+// The search's launch rule: the workgroups per query (*ran_wg too) and the LDS bytes of one
+// (masked: with the block's inv_block / 32 admit words).
+int sparse_inv_grid(int n_docs, int inv_block, int B, int q_top, int k, int max_wg, int *ran_wg, size_t *lds,
+                    bool masked = false);
 // launch_sparse_scan_batch's arguments and result contract over the inverted image of all
 // n_docs documents; the score is s = +0, then s = fmaf(f16(weight_i), w, s) over the query's
 // slots i in slot order whose term the document holds (w the stored f16): not the document-
@@ -534,7 +541,7 @@ int sparse_inv_grid(int n_docs, int inv_block, int B, int q_top, int k, int max_
 int launch_sparse_inv_search(const uint32_t *inv, const uint32_t *rows, const void *d_table, int n_docs, int V,
                              int inv_block, const int32_t *d_terms, const float *d_weights, int B, int q_top, int k,
                              void *partial, float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg = 0,
-                             int *ran_wg = nullptr);
+                             int *ran_wg = nullptr, const SearchMask *mask = nullptr);
 // Benches: heavy term j < kSparseHeavyTerms set in d_rows f32 [n][V] at weight 2 + j / 8, in a
 // share 1/2 (3/4)^j of the rows (all_of == 0), or the first all_of heavy terms in every row.
 constexpr int kSparseHeavyTerms = 16;

@@ -32,6 +32,15 @@
 // to the lists of queries w, w + 16, ...; a second barrier carries every wave's "documents
 // left" flag, and the loop ends when none has.  (A workgroup OR by flags in the dynamic LDS:
 // the library reduction's static words would not fit beside a full 160 KiB.)
+//
+// Mask: nothing, the unmasked kernel, whose arguments end at partial; or one SearchMask over
+// documents (filt at the pass's first filter), the masked kernel.  The part of
+// the mask the pass's queries share, the tombstones and a filter given once for all queries, is
+// tested where a quarter closes a document, from a word the quarter keeps for the 32 documents
+// around its current one: a document it rejects takes no staging slot, writes nothing and is
+// never offered, and the slots count the admitted documents only.  Filters given per query
+// cannot be tested there, since a staged document serves every query; wave w, offering for
+// query i, gathers the word of each staged id from query i's filter and gates its offer.
 #include "device_common.h"
 #include "kernels.h"
 #include "maxsim_common.h"
@@ -159,13 +168,21 @@ __device__ __forceinline__ int fold_halving(float (&a)[NQ], int l16)
 }
 
 // nq <= NQ: the queries of this pass that exist.  partial: [nq][gridDim.x][k].
-template <int NQ>
+template <int NQ, class... Mask>
 __global__ __launch_bounds__(kThreads) void sparse_scan_batch_kernel(const uint32_t *__restrict__ store,
                                                                      const int2 *__restrict__ table,
                                                                      const int32_t *__restrict__ d_used, int n_docs,
                                                                      const char *__restrict__ image, int dict16,
-                                                                     int w16, int nq, int k, Hit *__restrict__ partial)
+                                                                     int w16, int nq, int k, Hit *__restrict__ partial,
+                                                                     Mask... mask)
 {
+    constexpr bool MK = sizeof...(Mask) != 0;
+    SearchMask m{nullptr, nullptr, 0};
+    if constexpr (MK) m = first_mask(mask...);
+    // the filter every query of the pass shares (tested with the tombstones where a document
+    // closes), and whether each query has its own (tested at the offer)
+    const uint32_t *shared_filt = m.stride == 0 ? m.filt : nullptr;
+    const bool own_filt = m.filt && m.stride != 0;
     extern __shared__ uint4 smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l16 = lane & 15;
     const uint2 *dict = (const uint2 *)smem;
@@ -204,6 +221,15 @@ __global__ __launch_bounds__(kThreads) void sparse_scan_batch_kernel(const uint3
     float acc[NQ];
 #pragma unroll
     for (int i = 0; i < NQ; ++i) acc[i] = 0.f;
+    // masked: the shared admit word of documents 32 (doc / 32) .. + 31, reloaded when doc crosses
+    // a multiple of 32
+    auto shared_admit = [&](int d) {
+        const uint32_t live = ~m.tomb[d >> 5];
+        return shared_filt ? live & shared_filt[d >> 5] : live;
+    };
+    uint32_t adm = 0u;
+    if constexpr (MK)
+        if (doc < dend) adm = shared_admit(doc);
 
     bool any = true;
     while (any) {
@@ -235,26 +261,37 @@ __global__ __launch_bounds__(kThreads) void sparse_scan_batch_kernel(const uint3
                 --rem;
             }
             const bool fin = active && rem == 0;
-            const unsigned long long closing = __ballot(fin && l16 == 0);
-            if (closing) {
-                float s[NQ];
+            // take: the quarter closes a document that is staged (masked: an admitted one)
+            bool take = fin;
+            if constexpr (MK) take = fin && ((adm >> (doc & 31)) & 1u);
+            const unsigned long long closing = __ballot(take && l16 == 0);
+            unsigned long long ending = closing;   // the quarters that close a document, staged or not
+            if constexpr (MK) ending = __ballot(fin);
+            if (ending) {
+                if (closing) {
+                    float s[NQ];
 #pragma unroll
-                for (int i = 0; i < NQ; ++i) s[i] = acc[i];
-                const int first = fold_halving<NQ>(s, l16);
-                if (fin) {
-                    const int slot = wv * kDepth + cnt + __popcll(closing & ((1ull << (lane & 48)) - 1ull));
-                    if constexpr (NQ >= 16) {
+                    for (int i = 0; i < NQ; ++i) s[i] = acc[i];
+                    const int first = fold_halving<NQ>(s, l16);
+                    if (take) {
+                        const int slot = wv * kDepth + cnt + __popcll(closing & ((1ull << (lane & 48)) - 1ull));
+                        if constexpr (NQ >= 16) {
 #pragma unroll
-                        for (int j = 0; j < NQ / 16; ++j) st_s[(first + j) * kSlots + slot] = s[j];
-                    } else {
-                        if ((l16 & (16 / NQ - 1)) == 0) st_s[first * kSlots + slot] = s[0];
+                            for (int j = 0; j < NQ / 16; ++j) st_s[(first + j) * kSlots + slot] = s[j];
+                        } else {
+                            if ((l16 & (16 / NQ - 1)) == 0) st_s[first * kSlots + slot] = s[0];
+                        }
+                        if (l16 == 0) st_id[slot] = doc;
                     }
-                    if (l16 == 0) st_id[slot] = doc;
+                }
+                if (fin) {
                     ++doc;
                     rem = (nxt + 15) >> 4;
                     nxt = table[min(doc + 1, n_docs - 1)].y;
 #pragma unroll
                     for (int i = 0; i < NQ; ++i) acc[i] = 0.f;
+                    if constexpr (MK)
+                        if ((doc & 31) == 0 && doc < dend) adm = shared_admit(doc);
                 }
                 cnt += __popcll(closing);
             }
@@ -265,7 +302,13 @@ __global__ __launch_bounds__(kThreads) void sparse_scan_batch_kernel(const uint3
 #pragma unroll
             for (int g = 0; g < kSlots / 64; ++g) {
                 const int slot = 64 * g + lane;
-                const bool valid = (slot & (kDepth - 1)) < st_cnt[slot / kDepth];
+                bool valid = (slot & (kDepth - 1)) < st_cnt[slot / kDepth];
+                if constexpr (MK) {
+                    if (own_filt && valid) {   // query i's own filter: the word of the staged id
+                        const int32_t id = st_id[slot];
+                        valid = (m.filt[(int64_t)i * m.stride + (id >> 5)] >> (id & 31)) & 1u;
+                    }
+                }
                 if (__ballot(valid)) list_offer(lists + (size_t)i * k, k, st_s[i * kSlots + slot], st_id[slot], valid, lane);
             }
         }
@@ -280,24 +323,45 @@ __global__ __launch_bounds__(kThreads) void sparse_scan_batch_kernel(const uint3
         for (int j = lane; j < k; j += 64) partial[((size_t)i * gridDim.x + blockIdx.x) * k + j] = lists[(size_t)i * k + j];
 }
 
-template <int NQ>
+// mask: none (the unmasked kernel) or the pass's SearchMask
+template <int NQ, class... Mask>
 void launch_pass(int P, size_t lds, hipStream_t s, const uint32_t *store, const void *d_table, const int32_t *d_used,
-                 int n_docs, const char *image, int V, int q_top, int nq, int k, void *partial)
+                 int n_docs, const char *image, int V, int q_top, int nq, int k, void *partial, Mask... mask)
 {
-    sparse_scan_batch_kernel<NQ><<<(unsigned)P, kThreads, lds, s>>>(store, (const int2 *)d_table, d_used, n_docs, image,
-                                                                    (int)(dict_bytes(V) / 16),
-                                                                    (int)(w_bytes(V, q_top, NQ) / 16), nq, k,
-                                                                    (Hit *)partial);
+    sparse_scan_batch_kernel<NQ, Mask...><<<(unsigned)P, kThreads, lds, s>>>(
+        store, (const int2 *)d_table, d_used, n_docs, image, (int)(dict_bytes(V) / 16),
+        (int)(w_bytes(V, q_top, NQ) / 16), nq, k, (Hit *)partial, mask...);
+}
+
+template <class... Mask>
+void launch_pass_of(int NQ, int P, size_t lds, hipStream_t s, const uint32_t *store, const void *d_table,
+                    const int32_t *d_used, int n_docs, const char *image, int V, int q_top, int nq, int k, void *partial,
+                    Mask... mask)
+{
+    switch (NQ) {
+    case 32: launch_pass<32>(P, lds, s, store, d_table, d_used, n_docs, image, V, q_top, nq, k, partial, mask...); break;
+    case 16: launch_pass<16>(P, lds, s, store, d_table, d_used, n_docs, image, V, q_top, nq, k, partial, mask...); break;
+    case 8: launch_pass<8>(P, lds, s, store, d_table, d_used, n_docs, image, V, q_top, nq, k, partial, mask...); break;
+    default: launch_pass<4>(P, lds, s, store, d_table, d_used, n_docs, image, V, q_top, nq, k, partial, mask...); break;
+    }
+}
+
+template <class... Mask>
+hipError_t allow_lds_all()
+{
+    hipError_t e = allow_lds((const void *)sparse_scan_batch_kernel<32, Mask...>);
+    if (e == hipSuccess) e = allow_lds((const void *)sparse_scan_batch_kernel<16, Mask...>);
+    if (e == hipSuccess) e = allow_lds((const void *)sparse_scan_batch_kernel<8, Mask...>);
+    if (e == hipSuccess) e = allow_lds((const void *)sparse_scan_batch_kernel<4, Mask...>);
+    return e;
 }
 
 }  // namespace
 
 int sparse_batch_prepare_device()
 {
-    hipError_t e = allow_lds((const void *)sparse_scan_batch_kernel<32>);
-    if (e == hipSuccess) e = allow_lds((const void *)sparse_scan_batch_kernel<16>);
-    if (e == hipSuccess) e = allow_lds((const void *)sparse_scan_batch_kernel<8>);
-    if (e == hipSuccess) e = allow_lds((const void *)sparse_scan_batch_kernel<4>);
+    hipError_t e = allow_lds_all<>();
+    if (e == hipSuccess) e = allow_lds_all<SearchMask>();
     return e == hipSuccess ? 0 : -1;
 }
 
@@ -327,7 +391,8 @@ int launch_sparse_batch_image(const int32_t *d_terms, const float *d_weights, in
 
 int launch_sparse_scan_batch(const uint32_t *store, const void *d_table, const int32_t *d_used, int n_docs, int V,
                              const int32_t *d_terms, const float *d_weights, int B, int q_top, int k, void *images,
-                             void *partial, float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg, int *ran_wg)
+                             void *partial, float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg, int *ran_wg,
+                             const SearchMask *mask)
 {
     if (!store || !d_table || !d_used || !partial || !d_scores || !d_ids || n_docs < 0) return -1;
     const int NQ = sparse_batch_queries(V, q_top, k);
@@ -339,12 +404,11 @@ int launch_sparse_scan_batch(const uint32_t *store, const void *d_table, const i
     for (int p = 0; p * NQ < B; ++p) {
         const int nq = std::min(NQ, B - p * NQ);
         const char *img = (const char *)images + (size_t)p * ib;
-        switch (NQ) {
-        case 32: launch_pass<32>(P, lds, s, store, d_table, d_used, n_docs, img, V, q_top, nq, k, partial); break;
-        case 16: launch_pass<16>(P, lds, s, store, d_table, d_used, n_docs, img, V, q_top, nq, k, partial); break;
-        case 8: launch_pass<8>(P, lds, s, store, d_table, d_used, n_docs, img, V, q_top, nq, k, partial); break;
-        default: launch_pass<4>(P, lds, s, store, d_table, d_used, n_docs, img, V, q_top, nq, k, partial); break;
-        }
+        if (mask)
+            launch_pass_of(NQ, P, lds, s, store, d_table, d_used, n_docs, img, V, q_top, nq, k, partial,
+                           pass_mask(*mask, (int64_t)p * NQ));
+        else
+            launch_pass_of(NQ, P, lds, s, store, d_table, d_used, n_docs, img, V, q_top, nq, k, partial);
         if (hipGetLastError() != hipSuccess) return -3;
         const int rc = launch_search_merge(partial, nq, P, k, d_scores + (size_t)p * NQ * k, d_ids + (size_t)p * NQ * k, s);
         if (rc != 0) return rc;

@@ -36,6 +36,14 @@
 //      63 of every 1,024, by list_offer.
 // After the last block wave 0 folds the other waves' lists into its own and writes the
 // workgroup's list; launch_search_merge merges the P lists of each query.
+//
+// Mask: nothing, the unmasked kernel, whose arguments end at partial; or one SearchMask over
+// documents, the masked kernel.  Per (block, query), before step 1, the
+// workgroup loads the block's inv_block / 32 admit words into LDS (~tombstones & the query's
+// filter, the bits at and above n_docs cleared; a block starts on a multiple of 64 documents, so
+// its words are whole) and ORs them over the workgroup through one flag per wave.  A block with
+// no admissible document is skipped there: no offset row, no staging, no accumulation, no offers.
+// Otherwise step 5 offers a document only when its bit is set; a wave's 64 documents are two words.
 #include "device_common.h"
 #include "kernels.h"
 #include "maxsim_common.h"
@@ -50,15 +58,17 @@ constexpr int kStagePost = kPerThread * kThreads;    // postings of the staging 
 constexpr int kBuildThreads = 256;
 
 // LDS words in front of the lists: acc [inv_block] | stage [kStagePost] | cum [q_top + 1] |
-// start [q_top] | qw [q_top] | the scan's wave totals [kWaves], rounded to the lists' 8 bytes.  (No
-// static LDS: the kernel's dynamic limit is the whole 160 KiB.)
-__host__ __device__ inline int inv_lists_word(int inv_block, int q_top)
+// start [q_top] | qw [q_top] | the scan's wave totals [kWaves] | masked: the block's admit words
+// [inv_block / 32] and the waves' "some document is admissible" flags [kWaves] |, rounded to the
+// lists' 8 bytes.  (No static LDS: the kernel's dynamic limit is the whole 160 KiB.)
+__host__ __device__ inline int inv_admit_word(int inv_block, int q_top) { return inv_block + kStagePost + 3 * q_top + kWaves + 1; }
+__host__ __device__ inline int inv_lists_word(int inv_block, int q_top, bool masked)
 {
-    return (inv_block + kStagePost + 3 * q_top + kWaves + 2) & ~1;
+    return (inv_admit_word(inv_block, q_top) + (masked ? inv_block / 32 + kWaves : 0) + 1) & ~1;
 }
-inline size_t inv_lds_bytes(int inv_block, int q_top, int k)
+inline size_t inv_lds_bytes(int inv_block, int q_top, int k, bool masked)
 {
-    return (size_t)inv_lists_word(inv_block, q_top) * 4 + (size_t)kWaves * k * sizeof(Hit);
+    return (size_t)inv_lists_word(inv_block, q_top, masked) * 4 + (size_t)kWaves * k * sizeof(Hit);
 }
 
 __global__ __launch_bounds__(kBuildThreads) void inv_zero_kernel(uint32_t *__restrict__ p, size_t n)
@@ -132,13 +142,17 @@ __global__ __launch_bounds__(kThreads) void inv_prefix_kernel(uint32_t *__restri
 }
 
 // Workgroup (x, query): blocks x, x + gridDim.x, ...  partial: [B][gridDim.x][k].
+template <class... Mask>
 __global__ __launch_bounds__(kThreads) void sparse_inv_search_kernel(const uint32_t *__restrict__ inv,
                                                                      const uint32_t *__restrict__ rows,
                                                                      const int2 *__restrict__ table, int n_docs, int V,
                                                                      int inv_block, const int32_t *__restrict__ terms,
                                                                      const float *__restrict__ weights, int q_top, int k,
-                                                                     Hit *__restrict__ partial)
+                                                                     Hit *__restrict__ partial, Mask... mask)
 {
+    constexpr bool MK = sizeof...(Mask) != 0;
+    SearchMask m{nullptr, nullptr, 0};
+    if constexpr (MK) m = first_mask(mask...);
     extern __shared__ uint4 smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, q = blockIdx.y, P = gridDim.x;
     float *acc = (float *)smem;                              // [inv_block]
@@ -147,7 +161,9 @@ __global__ __launch_bounds__(kThreads) void sparse_inv_search_kernel(const uint3
     uint32_t *start = cum + q_top + 1;                       // [q_top]
     float *qw = (float *)(start + q_top);                    // [q_top]
     uint32_t *wave_tot = (uint32_t *)(qw + q_top);           // [kWaves]
-    Hit *lists = (Hit *)((uint32_t *)smem + inv_lists_word(inv_block, q_top));   // [kWaves][k]
+    uint32_t *adm = (uint32_t *)smem + inv_admit_word(inv_block, q_top);   // masked: [inv_block / 32]
+    uint32_t *wave_any = adm + (inv_block >> 5);                           // masked: [kWaves]
+    Hit *lists = (Hit *)((uint32_t *)smem + inv_lists_word(inv_block, q_top, MK));   // [kWaves][k]
     Hit *mine = lists + (size_t)wv * k;
 
     // this thread's slot of the query: a term outside 0 .. V - 1 is an empty slot
@@ -162,6 +178,30 @@ __global__ __launch_bounds__(kThreads) void sparse_inv_search_kernel(const uint3
     const int n_blocks = (n_docs + inv_block - 1) / inv_block;
     for (int b = blockIdx.x; b < n_blocks; b += P) {
         const int doc0 = b * inv_block, nb = min(inv_block, n_docs - doc0);
+        if constexpr (MK) {
+            // the block's admit words, and whether any document of the block is admissible
+            const uint32_t *tomb = m.tomb + (doc0 >> 5);
+            const uint32_t *filt = m.filt ? m.filt + (int64_t)q * m.stride + (doc0 >> 5) : nullptr;
+            uint32_t some = 0u;
+            for (int i = tid; i < inv_block >> 5; i += kThreads) {
+                const int left = nb - 32 * i;   // the block's documents from this word on
+                uint32_t a = 0u;
+                if (left > 0) {
+                    a = filt ? ~tomb[i] & filt[i] : ~tomb[i];
+                    if (left < 32) a &= (1u << left) - 1u;
+                }
+                adm[i] = a;
+                some |= a;
+            }
+            if (lane == 0) wave_any[wv] = 0u;   // (a wave's own flag: in order with the write below)
+            if (__ballot(some != 0u) && lane == 0) wave_any[wv] = 1u;
+            lds_barrier();
+            const bool skip = __ballot(wave_any[lane & (kWaves - 1)] != 0u) == 0;
+            if (skip) {
+                lds_barrier();   // every wave has read the flags before the next block's are written
+                continue;
+            }
+        }
         for (int i = tid; i < (nb + 3) >> 2; i += kThreads) ((float4 *)acc)[i] = float4{0.f, 0.f, 0.f, 0.f};
         const uint32_t *row = rows + (size_t)b * (size_t)(V + 1);
         uint32_t s0 = 0, len = 0;
@@ -218,8 +258,9 @@ __global__ __launch_bounds__(kThreads) void sparse_inv_search_kernel(const uint3
 
         for (int i0 = wv * 64; i0 < nb; i0 += kThreads) {
             const int i = i0 + lane;
-            const bool valid = i < nb;
-            list_offer(mine, k, valid ? acc[i] : 0.f, doc0 + i, valid, lane);
+            bool valid = i < nb;
+            if constexpr (MK) valid = valid && ((adm[i >> 5] >> (i & 31)) & 1u);
+            list_offer(mine, k, i < nb ? acc[i] : 0.f, doc0 + i, valid, lane);
         }
         lds_barrier();   // the next block's zeros and tables follow the offers
     }
@@ -257,7 +298,12 @@ __global__ __launch_bounds__(kBuildThreads) void skew_rows_kernel(float *__restr
 
 }  // namespace
 
-int sparse_inv_prepare_device() { return allow_lds((const void *)sparse_inv_search_kernel) == hipSuccess ? 0 : -1; }
+int sparse_inv_prepare_device()
+{
+    hipError_t e = allow_lds((const void *)sparse_inv_search_kernel<>);
+    if (e == hipSuccess) e = allow_lds((const void *)sparse_inv_search_kernel<SearchMask>);
+    return e == hipSuccess ? 0 : -1;
+}
 
 size_t sparse_inv_rows_bytes(int64_t cap_docs, int V, int inv_block)
 {
@@ -266,9 +312,9 @@ size_t sparse_inv_rows_bytes(int64_t cap_docs, int V, int inv_block)
 
 // A workgroup per (block, query) while the device has room for them: as many workgroups as
 // its LDS holds, shared among the B queries, never more per query than blocks.
-int sparse_inv_grid(int n_docs, int inv_block, int B, int q_top, int k, int max_wg, int *ran_wg, size_t *lds)
+int sparse_inv_grid(int n_docs, int inv_block, int B, int q_top, int k, int max_wg, int *ran_wg, size_t *lds, bool masked)
 {
-    *lds = inv_lds_bytes(inv_block, q_top, k);
+    *lds = inv_lds_bytes(inv_block, q_top, k, masked);
     const int64_t blocks = ((int64_t)n_docs + inv_block - 1) / inv_block;
     const int64_t room = std::max<int64_t>(1, wg_per_cu(*lds) * device_cu_count() / B);
     return capped_grid(std::min(blocks, room), max_wg, ran_wg);
@@ -303,17 +349,22 @@ int launch_sparse_invert(const uint32_t *store, const void *d_table, int d0, int
 
 int launch_sparse_inv_search(const uint32_t *inv, const uint32_t *rows, const void *d_table, int n_docs, int V,
                              int inv_block, const int32_t *d_terms, const float *d_weights, int B, int q_top, int k,
-                             void *partial, float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg, int *ran_wg)
+                             void *partial, float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg, int *ran_wg,
+                             const SearchMask *mask)
 {
     if (!inv || !rows || !d_table || !d_terms || !d_weights || !partial || !d_scores || !d_ids || n_docs < 0 || V < 1 ||
         V > 65536 || inv_block < 64 || inv_block > 65536 || inv_block % 64 != 0 || B < 1 || B > 64 || q_top < 1 ||
         q_top > 1024 || k < 1 || k > 128)
         return -1;
     size_t lds = 0;
-    const int P = sparse_inv_grid(n_docs, inv_block, B, q_top, k, max_wg, ran_wg, &lds);
+    const int P = sparse_inv_grid(n_docs, inv_block, B, q_top, k, max_wg, ran_wg, &lds, mask != nullptr);
     if (lds > (size_t)kLdsBudget || (size_t)B * P * 128 * sizeof(Hit) > sparse_inv_partial_bytes()) return -1;
-    sparse_inv_search_kernel<<<dim3((unsigned)P, (unsigned)B), kThreads, lds, s>>>(
-        inv, rows, (const int2 *)d_table, n_docs, V, inv_block, d_terms, d_weights, q_top, k, (Hit *)partial);
+    if (mask)
+        sparse_inv_search_kernel<SearchMask><<<dim3((unsigned)P, (unsigned)B), kThreads, lds, s>>>(
+            inv, rows, (const int2 *)d_table, n_docs, V, inv_block, d_terms, d_weights, q_top, k, (Hit *)partial, *mask);
+    else
+        sparse_inv_search_kernel<><<<dim3((unsigned)P, (unsigned)B), kThreads, lds, s>>>(
+            inv, rows, (const int2 *)d_table, n_docs, V, inv_block, d_terms, d_weights, q_top, k, (Hit *)partial);
     if (hipGetLastError() != hipSuccess) return -3;
     return launch_search_merge(partial, B, P, k, d_scores, d_ids, s);
 }

@@ -27,6 +27,14 @@
 // offers (score, id) to the wave's own list of the query (list_offer is a whole-wave
 // operation).  At the end wave 0 folds the other waves' lists into its own and writes
 // the workgroup's list; launch_search_merge merges the workgroups' lists.
+//
+// Mask: nothing, the unmasked kernel, whose arguments end at partial; or one SearchMask over
+// documents (filt at the pass's first filter), the masked kernel.  A quarter
+// keeps the admit words of the 32 documents around its current one in registers, ~tombstones &
+// filter: one word when the pass's queries share a filter or have none, one per query when the
+// filters are per query.  The words are loaded at the quarter's first document and again only
+// when the document crosses a multiple of 32; a document's bit gates the `valid` of its offer,
+// per query.  The postings are streamed and the scores computed as ever.
 #include "device_common.h"
 #include "kernels.h"
 #include "maxsim_common.h"
@@ -56,14 +64,32 @@ __global__ __launch_bounds__(256) void sparse_qtable_kernel(const float *__restr
     }
 }
 
-// nq <= NQ: the queries of this pass that exist.  partial: [nq][gridDim.x][k].
+// The admit words of the 32 documents around `doc` (< n_docs) for the queries i < nq of the pass:
+// a query that does not exist reads no filter, queries that share a filter read it once.
 template <int NQ>
+__device__ __forceinline__ void load_admit(const SearchMask &m, int nq, int doc, uint32_t (&adm)[NQ])
+{
+    const uint32_t live = ~m.tomb[doc >> 5];
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+        adm[i] = live;
+        if (!m.filt || i >= nq) continue;
+        if (i == 0 || m.stride != 0) adm[i] = live & m.filt[(int64_t)i * m.stride + (doc >> 5)];
+        else adm[i] = adm[0];
+    }
+}
+
+// nq <= NQ: the queries of this pass that exist.  partial: [nq][gridDim.x][k].
+template <int NQ, class... Mask>
 __global__ __launch_bounds__(kThreads) void sparse_scan_kernel(const uint32_t *__restrict__ store,
                                                                const int2 *__restrict__ table,
                                                                const int32_t *__restrict__ d_used, int n_docs,
                                                                const uint4 *__restrict__ qtab, int tab16, int nq, int k,
-                                                               Hit *__restrict__ partial)
+                                                               Hit *__restrict__ partial, Mask... mask)
 {
+    constexpr bool MK = sizeof...(Mask) != 0;
+    SearchMask m{nullptr, nullptr, 0};
+    if constexpr (MK) m = first_mask(mask...);
     extern __shared__ uint4 smem[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l16 = lane & 15;
     Hit *lists = (Hit *)(smem + tab16);              // [wave][NQ][k]
@@ -92,6 +118,11 @@ __global__ __launch_bounds__(kThreads) void sparse_scan_kernel(const uint32_t *_
     float acc[NQ];
 #pragma unroll
     for (int i = 0; i < NQ; ++i) acc[i] = 0.f;
+    uint32_t adm[NQ];   // masked: the admit words of documents 32 (doc / 32) .. + 31
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) adm[i] = 0u;
+    if constexpr (MK)
+        if (doc < dend) load_admit<NQ>(m, nq, doc, adm);
 
     while (__ballot(doc < dend)) {
         const bool active = doc < dend, has = active && rem > 0;
@@ -120,12 +151,17 @@ __global__ __launch_bounds__(kThreads) void sparse_scan_kernel(const uint32_t *_
                 for (int o = 8; o >= 1; o >>= 1) s[i] = __fadd_rn(s[i], __shfl_xor(s[i], o, 64));
             }
 #pragma unroll
-            for (int i = 0; i < NQ; ++i)
-                if (i < nq) list_offer(mine + (size_t)i * k, k, s[i], doc, fin && l16 == 0, lane);
+            for (int i = 0; i < NQ; ++i) {
+                bool ok = fin && l16 == 0;
+                if constexpr (MK) ok = ok && ((adm[i] >> (doc & 31)) & 1u);
+                if (i < nq) list_offer(mine + (size_t)i * k, k, s[i], doc, ok, lane);
+            }
             if (fin) {
                 ++doc;
                 rem = (nxt + 15) >> 4;
                 nxt = table[min(doc + 1, n_docs - 1)].y;
+                if constexpr (MK)
+                    if ((doc & 31) == 0 && doc < dend) load_admit<NQ>(m, nq, doc, adm);
 #pragma unroll
                 for (int i = 0; i < NQ; ++i) acc[i] = 0.f;
             }
@@ -155,6 +191,8 @@ int sparse_scan_prepare_device()
 {
     hipError_t e = allow_lds((const void *)sparse_scan_kernel<1>);
     if (e == hipSuccess) e = allow_lds((const void *)sparse_scan_kernel<2>);
+    if (e == hipSuccess) e = allow_lds((const void *)sparse_scan_kernel<1, SearchMask>);
+    if (e == hipSuccess) e = allow_lds((const void *)sparse_scan_kernel<2, SearchMask>);
     return e == hipSuccess ? 0 : -1;
 }
 
@@ -166,7 +204,7 @@ size_t sparse_scan_partial_bytes() { return (size_t)2 * scan_max_lists() * 128 *
 
 int launch_sparse_scan(const uint32_t *store, const void *d_table, const int32_t *d_used, int n_docs, int V,
                        const float *d_queries, int B, int k, void *qtab, void *partial, float *d_scores, int32_t *d_ids,
-                       hipStream_t s, int max_wg, int *ran_wg)
+                       hipStream_t s, int max_wg, int *ran_wg, const SearchMask *mask)
 {
     if (!store || !d_table || !d_used || !d_queries || !qtab || !partial || !d_scores || !d_ids || n_docs < 0 || V < 1 ||
         V > 65536 || B < 1 || B > 64 || k < 1 || k > 128)
@@ -184,7 +222,15 @@ int launch_sparse_scan(const uint32_t *store, const void *d_table, const int32_t
     for (int p = 0; p < passes; ++p) {
         const int nq = std::min(NQ, B - p * NQ);
         const uint4 *tab = (const uint4 *)((const char *)qtab + (size_t)p * tb);
-        if (NQ == 2)
+        if (mask) {
+            const SearchMask pm = pass_mask(*mask, (int64_t)p * NQ);
+            if (NQ == 2)
+                sparse_scan_kernel<2, SearchMask><<<(unsigned)P, kThreads, lds, s>>>(
+                    store, (const int2 *)d_table, d_used, n_docs, tab, (int)(tb / 16), nq, k, (Hit *)partial, pm);
+            else
+                sparse_scan_kernel<1, SearchMask><<<(unsigned)P, kThreads, lds, s>>>(
+                    store, (const int2 *)d_table, d_used, n_docs, tab, (int)(tb / 16), nq, k, (Hit *)partial, pm);
+        } else if (NQ == 2)
             sparse_scan_kernel<2><<<(unsigned)P, kThreads, lds, s>>>(store, (const int2 *)d_table, d_used, n_docs, tab,
                                                                      (int)(tb / 16), nq, k, (Hit *)partial);
         else

@@ -8,6 +8,8 @@
 // The ordering rules are the other two stores' (store_common.h).  Beside the forward store an
 // inverted image (block-local term lists) is built on request and covers
 // inverted_docs documents; the inverted search refuses to run while that is not all of them.
+// Tombstones (index_mask.hip) and the callers' filters limit every search to the admissible
+// documents (bert_hip.h "Sparse index", "Deleting documents and filtered search").
 #include "bert.h"
 #include "bert_hip.h"
 
@@ -54,6 +56,14 @@ struct bertx_spindex {
     int64_t inverted_docs = 0;
     uint32_t *inv = nullptr, *inv_rows = nullptr;   // cap_units * 16 postings; offset rows of every block
     size_t inv_rows_bytes = 0;
+    // the tombstones (index_mask.hip): bit d % 32 of word d / 32 is 1 once document d was
+    // removed; `removed`: some remove was accepted since creation or the last clear, so the
+    // searches take their masked instantiations.  last_masked (test hook
+    // bertx_test_spindex_last_masked): the latest scan launch was a masked one
+    uint32_t *tomb = nullptr;
+    int64_t tomb_words = 0;
+    bool removed = false;
+    int last_masked = 0;
     hipStream_t stream = nullptr;
     emb::StoreOrder ord;
     std::mutex mu;
@@ -64,7 +74,8 @@ struct bertx_spindex {
         if (ord.done) (void)ord.wait();
         for (void *p : {(void *)store, (void *)table, (void *)d_used, (void *)sel_terms, (void *)sel_count,
                         (void *)sel_weights, (void *)st_rows, (void *)st_scores, (void *)st_ids, qtab, partial,
-                        (void *)st_qterms, (void *)st_qweights, qimage, (void *)inv, (void *)inv_rows})
+                        (void *)st_qterms, (void *)st_qweights, qimage, (void *)inv, (void *)inv_rows,
+                        (void *)tomb})
             if (p) (void)hipFree(p);
         if (ord.done) (void)hipEventDestroy(ord.done);
         if (stream) (void)hipStreamDestroy(stream);
@@ -132,8 +143,33 @@ int32_t add_device_locked(bertx_spindex &sp, const float *d_rows, int32_t n, hip
     return first;
 }
 
+// The mask of a search (sp locked): none while nothing was removed and no filter is given, which
+// launches the unmasked kernels with the arguments they always had; else the store's
+// tombstones with the call's filters (not read on an empty store).
+struct ScanMask {
+    SearchMask m;
+    bool on;
+    ScanMask(bertx_spindex &sp, const Filters &f)
+        : m{sp.tomb, sp.n_docs > 0 ? f.d : nullptr, f.stride}, on(sp.removed || f.d)
+    {
+        sp.last_masked = on;
+    }
+    const SearchMask *get() const { return on ? &m : nullptr; }
+};
+
+constexpr int32_t kStageIds = 64 * 128;   // int32 entries of st_ids, the staging of remove / deleted
+
+int32_t remove_device_locked(bertx_spindex &sp, const int32_t *d_ids, int32_t n, hipStream_t s)
+{
+    if (!d_ids || n < 1) return -1;
+    Ordered o(sp.ord, s);
+    const int rc = launch_index_remove(d_ids, n, sp.n_docs, sp.tomb, s);
+    if (rc == 0) sp.removed = true;
+    return rc;
+}
+
 int32_t search_device_locked(bertx_spindex &sp, const float *d_q, int32_t B, int32_t k, float *d_scores, int32_t *d_ids,
-                             hipStream_t s)
+                             hipStream_t s, const Filters &f = Filters())
 {
     if (!d_q || !d_scores || !d_ids || B < 1 || B > 64 || k < 1 || k > 128) {
         errorf("bertx_spindex_search: B = %d, k = %d are not in 1 <= B <= 64, 1 <= k <= 128\n", B, k);
@@ -142,12 +178,14 @@ int32_t search_device_locked(bertx_spindex &sp, const float *d_q, int32_t B, int
     Ordered o(sp.ord, s);
     const int NQ = sparse_scan_pair(sp.V, k);
     sp.last_passes = (B + NQ - 1) / NQ;
+    const ScanMask mask(sp, f);
     return launch_sparse_scan(sp.store, sp.table, sp.d_used, (int)sp.n_docs, sp.V, d_q, B, k, sp.qtab, sp.partial, d_scores,
-                              d_ids, s, sp.grid_cap, &sp.last_grid);
+                              d_ids, s, sp.grid_cap, &sp.last_grid, mask.get());
 }
 
 int32_t search_sparse_device_locked(bertx_spindex &sp, const int32_t *d_terms, const float *d_weights, int32_t B,
-                                    int32_t q_top, int32_t k, float *d_scores, int32_t *d_ids, hipStream_t s)
+                                    int32_t q_top, int32_t k, float *d_scores, int32_t *d_ids, hipStream_t s,
+                                    const Filters &f = Filters())
 {
     const int NQ = sparse_batch_queries(sp.V, q_top, k);
     if (!d_terms || !d_weights || !d_scores || !d_ids || B < 1 || B > 64 || NQ == 0) {
@@ -157,8 +195,9 @@ int32_t search_sparse_device_locked(bertx_spindex &sp, const int32_t *d_terms, c
     }
     Ordered o(sp.ord, s);
     sp.last_passes = (B + NQ - 1) / NQ;
+    const ScanMask mask(sp, f);
     return launch_sparse_scan_batch(sp.store, sp.table, sp.d_used, (int)sp.n_docs, sp.V, d_terms, d_weights, B, q_top, k,
-                                    sp.qimage, sp.partial, d_scores, d_ids, s, sp.grid_cap, &sp.last_grid);
+                                    sp.qimage, sp.partial, d_scores, d_ids, s, sp.grid_cap, &sp.last_grid, mask.get());
 }
 
 // Inverts the blocks that are not yet inverted, or have grown, on s.  The first call
@@ -193,7 +232,8 @@ int32_t build_inverted_locked(bertx_spindex &sp, hipStream_t s)
 }
 
 int32_t search_inverted_device_locked(bertx_spindex &sp, const int32_t *d_terms, const float *d_weights, int32_t B,
-                                      int32_t q_top, int32_t k, float *d_scores, int32_t *d_ids, hipStream_t s)
+                                      int32_t q_top, int32_t k, float *d_scores, int32_t *d_ids, hipStream_t s,
+                                      const Filters &f = Filters())
 {
     if (!d_terms || !d_weights || !d_scores || !d_ids || B < 1 || B > 64 || q_top < 1 || q_top > 1024 || k < 1 || k > 128) {
         errorf("bertx_spindex_search_inverted: B = %d, q_top = %d, k = %d are not in 1 <= B <= 64, 1 <= q_top <= 1024, "
@@ -207,12 +247,13 @@ int32_t search_inverted_device_locked(bertx_spindex &sp, const int32_t *d_terms,
     }
     Ordered o(sp.ord, s);
     sp.last_passes = 1;
+    const ScanMask mask(sp, f);
     if (sp.n_docs == 0) {   // nothing was ever built: the scan of an empty store gives the fill
         return launch_sparse_scan_batch(sp.store, sp.table, sp.d_used, 0, sp.V, d_terms, d_weights, B, q_top, k, sp.qimage,
-                                        sp.partial, d_scores, d_ids, s, sp.grid_cap, &sp.last_grid);
+                                        sp.partial, d_scores, d_ids, s, sp.grid_cap, &sp.last_grid, mask.get());
     }
     return launch_sparse_inv_search(sp.inv, sp.inv_rows, sp.table, (int)sp.n_docs, sp.V, sp.inv_block, d_terms, d_weights, B,
-                                    q_top, k, sp.partial, d_scores, d_ids, s, sp.grid_cap, &sp.last_grid);
+                                    q_top, k, sp.partial, d_scores, d_ids, s, sp.grid_cap, &sp.last_grid, mask.get());
 }
 
 // The results of a search launched on the store's stream into st_scores / st_ids (rc: its
@@ -231,9 +272,10 @@ int32_t results_to_host(bertx_spindex &sp, int32_t rc, int32_t B, int32_t k, flo
 }
 
 // B dense queries on the device, on the store's stream -> host results.
-int32_t search_to_host(bertx_spindex &sp, const float *d_q, int32_t B, int32_t k, float *scores, int32_t *ids)
+int32_t search_to_host(bertx_spindex &sp, const float *d_q, int32_t B, int32_t k, float *scores, int32_t *ids,
+                       const Filters &f = Filters())
 {
-    return results_to_host(sp, search_device_locked(sp, d_q, B, k, sp.st_scores, sp.st_ids, sp.stream), B, k, scores, ids);
+    return results_to_host(sp, search_device_locked(sp, d_q, B, k, sp.st_scores, sp.st_ids, sp.stream, f), B, k, scores, ids);
 }
 
 // The refusals of the text forms: -6 a file without the MLM records, -1 another vocabulary or
@@ -327,6 +369,7 @@ bertx_spindex *spindex_create_on(int ordinal, int V, int n_top, int64_t cap_docs
     sp->n_top = n_top;
     sp->cap_docs = cap_docs;
     sp->cap_units = units_of(cap_postings);
+    sp->tomb_words = index_mask_words(cap_docs);
     const size_t sel = (size_t)kSparseAddRows * n_top * 4;
     const size_t stq = (size_t)kStage * 1024 * 4;
     const bool ok = sparse_scan_prepare_device() == 0 && sparse_batch_prepare_device() == 0 &&
@@ -348,6 +391,8 @@ bertx_spindex *spindex_create_on(int ordinal, int V, int n_top, int64_t cap_docs
                     hipMalloc((void **)&sp->st_qterms, stq) == hipSuccess &&
                     hipMalloc((void **)&sp->st_qweights, stq) == hipSuccess &&
                     hipMalloc(&sp->qimage, sparse_batch_image_bytes()) == hipSuccess &&
+                    hipMalloc((void **)&sp->tomb, (size_t)sp->tomb_words * 4) == hipSuccess &&
+                    hipMemsetAsync(sp->tomb, 0, (size_t)sp->tomb_words * 4, sp->stream) == hipSuccess &&
                     hipMemsetAsync(sp->d_used, 0, 16, sp->stream) == hipSuccess &&
                     hipStreamSynchronize(sp->stream) == hipSuccess;
     if (!ok) {
@@ -394,6 +439,10 @@ int32_t bertx_spindex_clear(struct bertx_spindex *sp)
     {
         emb::Ordered o(sp->ord, sp->stream);
         HIP_RC(hipMemsetAsync(sp->d_used, 0, 4, sp->stream));
+        if (sp->removed) {   // the tombstones back to zero, ordered behind every operation so far
+            HIP_RC(hipMemsetAsync(sp->tomb, 0, (size_t)sp->tomb_words * 4, sp->stream));
+            sp->removed = false;
+        }
     }
     sp->n_docs = 0;
     sp->used_bound = 0;
@@ -545,29 +594,117 @@ int32_t bertx_spindex_doc(struct bertx_spindex *sp, int32_t id, int32_t *terms, 
     return e[1];
 }
 
-int32_t bertx_spindex_search_device(struct bertx_spindex *sp, const float *d_queries, int32_t B, int32_t k, float *d_scores,
-                                    int32_t *d_ids, void *stream)
+int32_t bertx_spindex_search_filtered_device(struct bertx_spindex *sp, const float *d_queries, int32_t B, int32_t k,
+                                             const uint32_t *d_filters, int32_t n_filters, int32_t words, float *d_scores,
+                                             int32_t *d_ids, void *stream)
 {
     if (!sp) return -1;
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (!emb::filters_fit(sp->n_docs, d_filters, n_filters, words, B)) return -1;
     DeviceGuard g(sp->ordinal);
     HIP_RC(g.status());
-    return emb::search_device_locked(*sp, d_queries, B, k, d_scores, d_ids, stream ? (hipStream_t)stream : sp->stream);
+    return emb::search_device_locked(*sp, d_queries, B, k, d_scores, d_ids, stream ? (hipStream_t)stream : sp->stream,
+                                     emb::filters_of(d_filters, n_filters, words));
+}
+
+int32_t bertx_spindex_search_device(struct bertx_spindex *sp, const float *d_queries, int32_t B, int32_t k, float *d_scores,
+                                    int32_t *d_ids, void *stream)
+{
+    return bertx_spindex_search_filtered_device(sp, d_queries, B, k, nullptr, 0, 0, d_scores, d_ids, stream);
+}
+
+int32_t bertx_spindex_search_filtered(struct bertx_spindex *sp, const float *queries, int32_t B, int32_t k,
+                                      const uint32_t *filters, int32_t n_filters, int32_t words, float *scores, int32_t *ids)
+{
+    if (!sp || !queries || !scores || !ids || B < 1 || B > kStage) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (!emb::filters_fit(sp->n_docs, filters, n_filters, words, B)) return -1;
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    emb::DevBuf fbuf;   // (freed after the call's synchronise)
+    {
+        emb::Ordered o(sp->ord, sp->stream);
+        HIP_RC(hipMemcpyAsync(sp->st_rows, queries, (size_t)B * sp->V * 4, hipMemcpyHostToDevice, sp->stream));
+        HIP_RC(emb::stage_filters(sp->stream, filters, n_filters, words, fbuf));
+    }
+    HIP_RC(hipStreamSynchronize(sp->stream));   // the caller's rows are pageable
+    return emb::search_to_host(*sp, sp->st_rows, B, k, scores, ids,
+                               emb::filters_of((const uint32_t *)fbuf.p, n_filters, words));
 }
 
 int32_t bertx_spindex_search(struct bertx_spindex *sp, const float *queries, int32_t B, int32_t k, float *scores,
                              int32_t *ids)
 {
-    if (!sp || !queries || !scores || !ids || B < 1 || B > kStage) return -1;
+    return bertx_spindex_search_filtered(sp, queries, B, k, nullptr, 0, 0, scores, ids);
+}
+
+int32_t bertx_spindex_remove_device(struct bertx_spindex *sp, const int32_t *d_ids, int32_t n, void *stream)
+{
+    if (!sp) return -1;
     std::lock_guard<std::mutex> lk(sp->mu);
     DeviceGuard g(sp->ordinal);
     HIP_RC(g.status());
+    return emb::remove_device_locked(*sp, d_ids, n, stream ? (hipStream_t)stream : sp->stream);
+}
+
+int32_t bertx_spindex_remove(struct bertx_spindex *sp, const int32_t *ids, int32_t n)
+{
+    if (!sp || !ids || n < 1) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    for (int32_t i = 0; i < n; i += emb::kStageIds) {
+        const int32_t m = std::min(emb::kStageIds, n - i);
+        {
+            emb::Ordered o(sp->ord, sp->stream);
+            HIP_RC(hipMemcpyAsync(sp->st_ids, ids + i, (size_t)m * 4, hipMemcpyHostToDevice, sp->stream));
+        }
+        const int32_t rc = emb::remove_device_locked(*sp, sp->st_ids, m, sp->stream);
+        if (rc != 0) return rc;
+        HIP_RC(hipStreamSynchronize(sp->stream));   // the staging buffer is reused
+    }
+    return 0;
+}
+
+int32_t bertx_spindex_live(struct bertx_spindex *sp)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    int32_t dead = 0;
     {
         emb::Ordered o(sp->ord, sp->stream);
-        HIP_RC(hipMemcpyAsync(sp->st_rows, queries, (size_t)B * sp->V * 4, hipMemcpyHostToDevice, sp->stream));
+        const int rc = emb::launch_index_count_deleted(sp->tomb, sp->n_docs, sp->st_ids, sp->stream);
+        if (rc != 0) return rc;
+        HIP_RC(hipMemcpyAsync(&dead, sp->st_ids, 4, hipMemcpyDeviceToHost, sp->stream));
     }
-    HIP_RC(hipStreamSynchronize(sp->stream));   // the caller's rows are pageable
-    return emb::search_to_host(*sp, sp->st_rows, B, k, scores, ids);
+    HIP_RC(hipStreamSynchronize(sp->stream));
+    return (int32_t)sp->n_docs - dead;
+}
+
+int32_t bertx_spindex_deleted(struct bertx_spindex *sp, int32_t first, int32_t n, uint8_t *out)
+{
+    if (!sp || !out || first < 0 || n < 1) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if ((int64_t)first + n > sp->n_docs) return -1;
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    // the caller's output is written only once every chunk has succeeded
+    std::vector<uint8_t> flags((size_t)n);
+    constexpr int32_t kChunk = emb::kStageIds * 4;   // bytes of the id staging buffer, one flag each
+    for (int32_t i = 0; i < n; i += kChunk) {
+        const int32_t m = std::min(kChunk, n - i);
+        {
+            emb::Ordered o(sp->ord, sp->stream);
+            const int rc = emb::launch_index_deleted_flags(sp->tomb, (int64_t)first + i, m, (uint8_t *)sp->st_ids, sp->stream);
+            if (rc != 0) return rc;
+            HIP_RC(hipMemcpyAsync(flags.data() + i, sp->st_ids, (size_t)m, hipMemcpyDeviceToHost, sp->stream));
+        }
+        HIP_RC(hipStreamSynchronize(sp->stream));
+    }
+    std::memcpy(out, flags.data(), flags.size());
+    return 0;
 }
 
 int32_t bertx_spindex_add_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
@@ -604,22 +741,34 @@ int32_t bertx_spindex_add_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, 
     return first;
 }
 
-int32_t bertx_spindex_search_sparse_device(struct bertx_spindex *sp, const int32_t *d_terms, const float *d_weights,
-                                           int32_t B, int32_t q_top, int32_t k, float *d_scores, int32_t *d_ids, void *stream)
+int32_t bertx_spindex_search_sparse_filtered_device(struct bertx_spindex *sp, const int32_t *d_terms,
+                                                    const float *d_weights, int32_t B, int32_t q_top, int32_t k,
+                                                    const uint32_t *d_filters, int32_t n_filters, int32_t words,
+                                                    float *d_scores, int32_t *d_ids, void *stream)
 {
     if (!sp) return -1;
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (!emb::filters_fit(sp->n_docs, d_filters, n_filters, words, B)) return -1;
     DeviceGuard g(sp->ordinal);
     HIP_RC(g.status());
     return emb::search_sparse_device_locked(*sp, d_terms, d_weights, B, q_top, k, d_scores, d_ids,
-                                            stream ? (hipStream_t)stream : sp->stream);
+                                            stream ? (hipStream_t)stream : sp->stream,
+                                            emb::filters_of(d_filters, n_filters, words));
+}
+
+int32_t bertx_spindex_search_sparse_device(struct bertx_spindex *sp, const int32_t *d_terms, const float *d_weights,
+                                           int32_t B, int32_t q_top, int32_t k, float *d_scores, int32_t *d_ids, void *stream)
+{
+    return bertx_spindex_search_sparse_filtered_device(sp, d_terms, d_weights, B, q_top, k, nullptr, 0, 0, d_scores, d_ids,
+                                                       stream);
 }
 
 namespace {
 // The host forms of the two sparse-query searches: the refusals, the staging, the search
 // (inverted: over the inverted lists, built first when stale) and the results.
 int32_t search_sparse_host(struct bertx_spindex *sp, const int32_t *terms, const float *weights, int32_t B, int32_t q_top,
-                           int32_t k, float *scores, int32_t *ids, bool inverted)
+                           int32_t k, const uint32_t *filters, int32_t n_filters, int32_t words, float *scores, int32_t *ids,
+                           bool inverted)
 {
     if (!sp || !terms || !weights || !scores || !ids || B < 1 || B > kStage || q_top < 1 || q_top > 1024) return -1;
     std::vector<int32_t> seen((size_t)sp->V, -1);   // the query that last held the term
@@ -635,44 +784,73 @@ int32_t search_sparse_host(struct bertx_spindex *sp, const int32_t *terms, const
             seen[(size_t)t] = b;
         }
     std::lock_guard<std::mutex> lk(sp->mu);
+    if (!emb::filters_fit(sp->n_docs, filters, n_filters, words, B)) return -1;
     DeviceGuard g(sp->ordinal);
     HIP_RC(g.status());
+    emb::DevBuf fbuf;   // (freed after the call's synchronise)
     {
         emb::Ordered o(sp->ord, sp->stream);
         HIP_RC(hipMemcpyAsync(sp->st_qterms, terms, (size_t)B * q_top * 4, hipMemcpyHostToDevice, sp->stream));
         HIP_RC(hipMemcpyAsync(sp->st_qweights, weights, (size_t)B * q_top * 4, hipMemcpyHostToDevice, sp->stream));
+        HIP_RC(emb::stage_filters(sp->stream, filters, n_filters, words, fbuf));
     }
     HIP_RC(hipStreamSynchronize(sp->stream));   // the caller's arrays are pageable
+    const emb::Filters f = emb::filters_of((const uint32_t *)fbuf.p, n_filters, words);
     int32_t rc = inverted ? emb::build_inverted_locked(*sp, sp->stream) : 0;
     if (rc == 0)
         rc = (inverted ? emb::search_inverted_device_locked : emb::search_sparse_device_locked)(
-            *sp, sp->st_qterms, sp->st_qweights, B, q_top, k, sp->st_scores, sp->st_ids, sp->stream);
+            *sp, sp->st_qterms, sp->st_qweights, B, q_top, k, sp->st_scores, sp->st_ids, sp->stream, f);
     return emb::results_to_host(*sp, rc, B, k, scores, ids);
 }
 }  // namespace
 
+int32_t bertx_spindex_search_sparse_filtered(struct bertx_spindex *sp, const int32_t *terms, const float *weights, int32_t B,
+                                             int32_t q_top, int32_t k, const uint32_t *filters, int32_t n_filters,
+                                             int32_t words, float *scores, int32_t *ids)
+{
+    return search_sparse_host(sp, terms, weights, B, q_top, k, filters, n_filters, words, scores, ids, false);
+}
+
 int32_t bertx_spindex_search_sparse(struct bertx_spindex *sp, const int32_t *terms, const float *weights, int32_t B,
                                     int32_t q_top, int32_t k, float *scores, int32_t *ids)
 {
-    return search_sparse_host(sp, terms, weights, B, q_top, k, scores, ids, false);
+    return search_sparse_host(sp, terms, weights, B, q_top, k, nullptr, 0, 0, scores, ids, false);
+}
+
+int32_t bertx_spindex_search_inverted_filtered(struct bertx_spindex *sp, const int32_t *terms, const float *weights,
+                                               int32_t B, int32_t q_top, int32_t k, const uint32_t *filters,
+                                               int32_t n_filters, int32_t words, float *scores, int32_t *ids)
+{
+    return search_sparse_host(sp, terms, weights, B, q_top, k, filters, n_filters, words, scores, ids, true);
 }
 
 int32_t bertx_spindex_search_inverted(struct bertx_spindex *sp, const int32_t *terms, const float *weights, int32_t B,
                                       int32_t q_top, int32_t k, float *scores, int32_t *ids)
 {
-    return search_sparse_host(sp, terms, weights, B, q_top, k, scores, ids, true);
+    return search_sparse_host(sp, terms, weights, B, q_top, k, nullptr, 0, 0, scores, ids, true);
+}
+
+int32_t bertx_spindex_search_inverted_filtered_device(struct bertx_spindex *sp, const int32_t *d_terms,
+                                                      const float *d_weights, int32_t B, int32_t q_top, int32_t k,
+                                                      const uint32_t *d_filters, int32_t n_filters, int32_t words,
+                                                      float *d_scores, int32_t *d_ids, void *stream)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    if (!emb::filters_fit(sp->n_docs, d_filters, n_filters, words, B)) return -1;
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    return emb::search_inverted_device_locked(*sp, d_terms, d_weights, B, q_top, k, d_scores, d_ids,
+                                              stream ? (hipStream_t)stream : sp->stream,
+                                              emb::filters_of(d_filters, n_filters, words));
 }
 
 int32_t bertx_spindex_search_inverted_device(struct bertx_spindex *sp, const int32_t *d_terms, const float *d_weights,
                                              int32_t B, int32_t q_top, int32_t k, float *d_scores, int32_t *d_ids,
                                              void *stream)
 {
-    if (!sp) return -1;
-    std::lock_guard<std::mutex> lk(sp->mu);
-    DeviceGuard g(sp->ordinal);
-    HIP_RC(g.status());
-    return emb::search_inverted_device_locked(*sp, d_terms, d_weights, B, q_top, k, d_scores, d_ids,
-                                              stream ? (hipStream_t)stream : sp->stream);
+    return bertx_spindex_search_inverted_filtered_device(sp, d_terms, d_weights, B, q_top, k, nullptr, 0, 0, d_scores, d_ids,
+                                                         stream);
 }
 
 int32_t bertx_spindex_build_inverted(struct bertx_spindex *sp)
@@ -750,7 +928,7 @@ int32_t search_texts(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_t
         }
         if (rc == 0 && q_top > 0)
             rc = emb::results_to_host(*sp, sparse_search(*sp, sp->st_qterms, sp->st_qweights, m, q_top, k, sp->st_scores,
-                                                         sp->st_ids, sp->stream),
+                                                         sp->st_ids, sp->stream, emb::Filters()),
                                       m, k, hs.data() + i * k, hi.data() + i * k);
         else if (rc == 0)
             rc = emb::search_to_host(*sp, sp->st_rows, m, k, hs.data() + i * k, hi.data() + i * k);
@@ -862,6 +1040,13 @@ int32_t bertx_test_spindex_last_passes(struct bertx_spindex *sp)
     if (!sp) return -1;
     std::lock_guard<std::mutex> lk(sp->mu);
     return sp->last_passes;
+}
+
+int32_t bertx_test_spindex_last_masked(struct bertx_spindex *sp)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    return sp->last_masked;
 }
 
 }  // extern "C"

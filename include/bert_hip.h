@@ -1540,6 +1540,54 @@ BERT_API int32_t bertx_bench_sparse(int32_t d, int32_t V, int32_t n_seqs, int32_
  * posting bytes again, 11 ms of build per million documents) is affordable; without it the
  * dense-query search for one or two queries and the sparse-query search from a handful up.
  *
+ * Deleting documents and filtered search.  The token store's section word for word, a sparse
+ * document in the place of a document.  Two masks over document ids, both packed 32 documents
+ * to a uint32_t word: document i is bit i % 32 of word i / 32 (np.packbits(x,
+ * bitorder="little") viewed as uint32).  Tombstones belong to the store, lie on its device,
+ * cover capacity_docs and are allocated and zeroed at creation; bit 1 = deleted.  Filters are
+ * the caller's, per call; bit 1 = the document may be returned.  A document is admissible for
+ * query b iff id < docs, its tombstone is 0 and, when a filter is given, its bit in query b's
+ * filter is 1.
+ * bertx_spindex_remove / _remove_device (ids int32[n], host / device; n >= 1, anything else a
+ * negative error with nothing changed): sets the tombstones of the listed ids and returns 0.
+ * Ids outside [0, docs), docs being the document count when the call is made, are ignored;
+ * repeated ids are harmless; the bits are set by atomic OR, so no order matters.  The device
+ * form is asynchronous, allocates nothing, never synchronises, can be captured, and is
+ * ordered as bertx_spindex_add_device is.  Ids are never reused: bertx_spindex_docs and
+ * _postings do not change, and _doc_len and _doc still return a deleted document's stored
+ * values.  bertx_spindex_clear also zeroes the tombstones (ordered on the store's stream), so a
+ * clear followed by adds starts clean.  The inverted image is untouched by a removal:
+ * bertx_spindex_inverted_docs does not change and no rebuild is needed.
+ * bertx_spindex_live: docs minus the deleted documents in [0, docs); a host call that
+ * synchronises.  bertx_spindex_deleted: out uint8[n] = 0 or 1 for documents first .. first +
+ * n - 1; -1 on a bad range with the output untouched.
+ * bertx_spindex_search_filtered / _device, bertx_spindex_search_sparse_filtered / _device and
+ * bertx_spindex_search_inverted_filtered / _device: the unfiltered entry's argument list with
+ * (filters, n_filters, words) in front of the outputs, and its search over the admissible
+ * documents.  filters uint32[n_filters][words] (host / device); n_filters is 1 (one filter for
+ * every query) or B (query b uses filter b); words >= ceil(docs / 32) is also the stride
+ * between filters; bits of documents >= docs are ignored, whatever they hold.  filters == NULL
+ * with n_filters == 0 is exactly the unfiltered entry.  The result is the k best admissible
+ * documents with that search's own score bits, the same order (score descending, id ascending)
+ * and the same (-inf, -1) fill when fewer than k documents are admissible; a deleted or
+ * filtered document never appears, not even as (-inf, id).  Documents that share no term with
+ * the query still score +0 and take part if admissible.  Every refusal (a null pointer,
+ * n_filters not 0, 1 or B, too few words, a filter pointer without a count or the reverse, and
+ * the refusals of the unfiltered entry, the inverted search's stale image among them) returns
+ * a negative error with the outputs untouched.  The device forms allocate nothing and can be
+ * captured; the host forms allocate and free a staging buffer for the filters per call.  The
+ * filter is read when the kernel runs: a captured search sees the bits the buffer holds at
+ * replay.  A filter is not read while the store is empty.
+ * On a store with deletions the entries above follow: _search, _search_sparse,
+ * _search_inverted, their device forms and the text forms (_search_texts, _search_texts_top,
+ * _search_texts_inverted) return admissible documents only.
+ * A store from which nothing was removed since creation or the last clear, searched without a
+ * filter, launches the kernels it launched before masks existed, with the same arguments: the
+ * masked kernels are other instantiations, chosen at launch time by a host flag that any
+ * accepted remove sets and clear resets (a graph captured before the first removal keeps
+ * launching the unmasked kernels).  The inverted search also skips a whole block that holds no
+ * admissible document for the query before any of its lists is fetched.
+ *
  * bertx_test_sparse_select (parity hook; host buffers, device 0): rows f32 [S][V] ->
  * terms int32 [S][n], weights f32 [S][n] (the input's bits), count int32 [S]; slots past a
  * row's count hold (-1, +0).  Guard rows of NaN bits lie behind the three device outputs;
@@ -1563,10 +1611,20 @@ BERT_API int32_t bertx_bench_sparse(int32_t d, int32_t V, int32_t n_seqs, int32_
  * 1/2 (3/4)^j of the documents and the first four in every query.  avg_us[0] the build of the
  * whole image, avg_us[1] the inverted search, avg_us[2] the sparse-query search, avg_us[3] the
  * dense-query search.
+ * bertx_test_spindex_last_masked(sp): 1 when the store's most recent scan launch was a masked
+ * instantiation ("Deleting documents and filtered search"), 0 otherwise.
+ * bertx_bench_spindex_masked(V, n_docs, doc_len, B, q_len, k, iters, reps, us): the same store
+ * and queries (no skew), built once, under four masks; pattern 0 no mask (the unmasked
+ * kernels), 1 an all-ones filter, 2 one document in two removed by a hash of the id, 3 a filter
+ * that admits one contiguous sixteenth of the ids.  us [4][3][reps]: per pattern the inverted,
+ * the sparse-query and the dense-query search, each sample the average of `iters` launches
+ * after 3 warm-up launches.
  *
- * Not provided: dynamic pruning (WAND, block-max); int8 or impact-quantized weights; deletion
- * and filters; scoring listed ids; a mode of the `search` tool; saving and loading; an inverted
- * image without the forward store; vocabularies above 65,536 terms.
+ * Not provided: dynamic pruning (WAND, block-max); int8 or impact-quantized weights; compaction
+ * (reclaiming deleted documents' postings or renumbering); skipping the posting loads of masked
+ * documents in the two document-major scans; saving the masks; scoring listed ids; a mode of
+ * the `search` tool; saving and loading; an inverted image without the forward store;
+ * vocabularies above 65,536 terms.
  */
 struct bertx_spindex;
 BERT_API struct bertx_spindex *bertx_spindex_create(struct bert_ctx *ctx, int32_t slot, int32_t n_vocab, int32_t n_top,
@@ -1614,6 +1672,35 @@ BERT_API int32_t bertx_spindex_search_inverted(struct bertx_spindex *sp, const i
 BERT_API int32_t bertx_spindex_search_texts_inverted(struct bertx_spindex *sp, struct bert_ctx *ctx, int32_t n_threads,
                                                      int32_t n, const char **texts, int32_t q_top, int32_t k,
                                                      float *scores, int32_t *ids);
+BERT_API int32_t bertx_spindex_remove(struct bertx_spindex *sp, const int32_t *ids, int32_t n);
+BERT_API int32_t bertx_spindex_remove_device(struct bertx_spindex *sp, const int32_t *d_ids, int32_t n, void *stream);
+BERT_API int32_t bertx_spindex_live(struct bertx_spindex *sp);
+BERT_API int32_t bertx_spindex_deleted(struct bertx_spindex *sp, int32_t first, int32_t n, uint8_t *out);
+BERT_API int32_t bertx_spindex_search_filtered(struct bertx_spindex *sp, const float *queries, int32_t B, int32_t k,
+                                               const uint32_t *filters, int32_t n_filters, int32_t words, float *scores,
+                                               int32_t *ids);
+BERT_API int32_t bertx_spindex_search_filtered_device(struct bertx_spindex *sp, const float *d_queries, int32_t B,
+                                                      int32_t k, const uint32_t *d_filters, int32_t n_filters,
+                                                      int32_t words, float *d_scores, int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_spindex_search_sparse_filtered(struct bertx_spindex *sp, const int32_t *terms, const float *weights,
+                                                      int32_t B, int32_t q_top, int32_t k, const uint32_t *filters,
+                                                      int32_t n_filters, int32_t words, float *scores, int32_t *ids);
+BERT_API int32_t bertx_spindex_search_sparse_filtered_device(struct bertx_spindex *sp, const int32_t *d_terms,
+                                                             const float *d_weights, int32_t B, int32_t q_top, int32_t k,
+                                                             const uint32_t *d_filters, int32_t n_filters, int32_t words,
+                                                             float *d_scores, int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_spindex_search_inverted_filtered(struct bertx_spindex *sp, const int32_t *terms,
+                                                        const float *weights, int32_t B, int32_t q_top, int32_t k,
+                                                        const uint32_t *filters, int32_t n_filters, int32_t words,
+                                                        float *scores, int32_t *ids);
+BERT_API int32_t bertx_spindex_search_inverted_filtered_device(struct bertx_spindex *sp, const int32_t *d_terms,
+                                                               const float *d_weights, int32_t B, int32_t q_top,
+                                                               int32_t k, const uint32_t *d_filters, int32_t n_filters,
+                                                               int32_t words, float *d_scores, int32_t *d_ids,
+                                                               void *stream);
+BERT_API int32_t bertx_test_spindex_last_masked(struct bertx_spindex *sp);
+BERT_API int32_t bertx_bench_spindex_masked(int32_t V, int32_t n_docs, int32_t doc_len, int32_t B, int32_t q_len,
+                                            int32_t k, int32_t iters, int32_t reps, float *us);
 BERT_API int32_t bertx_test_spindex_inv_block(struct bertx_spindex *sp, int32_t docs);
 BERT_API int32_t bertx_bench_spindex_inverted(int32_t V, int32_t n_docs, int32_t doc_len, int32_t B, int32_t q_len,
                                               int32_t k, int32_t skew, int32_t iters, float *avg_us);
