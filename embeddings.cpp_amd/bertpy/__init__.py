@@ -520,6 +520,19 @@ def load_lib(path=None):
             fn.argtypes = [vp, vp, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp]
         L.bertx_bench_spindex_masked.restype = c_i32
         L.bertx_bench_spindex_masked.argtypes = [c_i32] * 8 + [c_f32p]
+        L.bertx_spindex_score_ids.restype = c_i32
+        L.bertx_spindex_score_ids.argtypes = [vp, vp, vp, c_i32, c_i32, vp, c_i32, vp]
+        L.bertx_spindex_score_ids_device.restype = c_i32
+        L.bertx_spindex_score_ids_device.argtypes = [vp, vp, vp, c_i32, c_i32, vp, c_i32, vp, vp]
+        hybrid = [c_i32] * 5 + [ctypes.c_float] * 2 + [vp, vp]   # B, q_top, k, n_cand, mode, a, b, scores, ids
+        L.bertx_hybrid_search.restype = c_i32
+        L.bertx_hybrid_search.argtypes = [vp] * 5 + hybrid
+        L.bertx_hybrid_search_device.restype = c_i32
+        L.bertx_hybrid_search_device.argtypes = [vp] * 5 + hybrid + [vp]
+        L.bertx_hybrid_search_texts.restype = c_i32
+        L.bertx_hybrid_search_texts.argtypes = [vp] * 4 + [c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p)] + hybrid[1:]
+        L.bertx_bench_hybrid.restype = c_i32
+        L.bertx_bench_hybrid.argtypes = [c_i32] * 11 + [c_f32p]
     except AttributeError:
         pass
     L.bertx_bench_gemm.restype = c_i32
@@ -1604,7 +1617,9 @@ class BertSparseIndex:
         return self._search_pairs(self.lib.bertx_spindex_search_inverted_filtered, "bertx_spindex_search_inverted", terms,
                                   weights, k, allow)
 
-    def _search_pairs(self, fn, name, terms, weights, k, allow=None):
+    @staticmethod
+    def _pairs(terms, weights):
+        """terms int32 [B][q_top], weights f32 [B][q_top] of either query form of search_sparse."""
         if weights is None:
             q_top = max([len(p) for p in terms] + [1])
             t, w = np.full((len(terms), q_top), -1, np.int32), np.zeros((len(terms), q_top), np.float32)
@@ -1618,6 +1633,10 @@ class BertSparseIndex:
                 t, w = t[None, :], w[None, :]
             if t.ndim != 2 or t.shape != w.shape:
                 raise ValueError("expected terms and weights of one shape [B][q_top], got %r and %r" % (t.shape, w.shape))
+        return t, w
+
+    def _search_pairs(self, fn, name, terms, weights, k, allow=None):
+        t, w = self._pairs(terms, weights)
         B, q_top = t.shape
         scores, ids = np.zeros((B, k), np.float32), np.zeros((B, k), np.int32)
         f, nf, words = self._allow(allow, B)
@@ -1626,6 +1645,68 @@ class BertSparseIndex:
             fp, n, fw = self._filter_args(f, nf, words, b)
             self._checked(-abs(fn(self.sp, t[b:].ctypes.data, w[b:].ctypes.data, m, q_top, k, fp, n, fw,
                                scores[b:].ctypes.data, ids[b:].ctypes.data)), name)
+        return scores, ids
+
+    def score_ids(self, terms, weights, ids):
+        """scores f32 [B][n]: the score of (sparse query b, document ids[b][j]) with the bits
+        search_sparse() / search() give that pair, -inf for an id outside the store or a deleted
+        document (a search's -1 fill included); queries as in search_sparse, B <= 64, n <= 128."""
+        t, w = self._pairs(terms, weights)
+        ids = np.ascontiguousarray(np.asarray(ids, np.int32))
+        if ids.ndim == 1:
+            ids = ids[None, :]
+        if ids.ndim != 2 or ids.shape[0] != t.shape[0]:
+            raise ValueError("expected ids of shape (%d, n), got %r" % (t.shape[0], ids.shape))
+        scores = np.zeros(ids.shape, np.float32)
+        self._checked(-abs(self.lib.bertx_spindex_score_ids(self.sp, t.ctypes.data, w.ctypes.data, t.shape[0], t.shape[1],
+                                                            ids.ctypes.data, ids.shape[1], scores.ctypes.data)),
+                      "bertx_spindex_score_ids")
+        return scores
+
+    @staticmethod
+    def _fusion(k, n_cand, fusion, a, inverted):
+        """(n_cand, mode, a) of a hybrid call: n_cand defaults to min(64, 4 k),
+        reciprocal-rank fusion's a to 60, linear fusion's to 1."""
+        if fusion not in ("linear", "rrf"):
+            raise ValueError("fusion is 'linear' or 'rrf', got %r" % (fusion,))
+        if n_cand is None:
+            n_cand = min(64, 4 * k)
+        if a is None:
+            a = 60.0 if fusion == "rrf" else 1.0
+        return n_cand, (1 if fusion == "rrf" else 0) | (16 if inverted else 0), a
+
+    def search_hybrid(self, index, queries, terms, weights, k, n_cand=None, fusion="linear", a=None, b=1.0, inverted=False):
+        """(fused scores f32 [B][k], ids int32 [B][k]): `index` (a BertIndex whose rows were added in
+        the order of this store's documents) and this store each find n_cand candidates for their
+        form of the queries (dense [B][dim]; sparse as in search_sparse, over the inverted lists
+        when inverted), the union is scored by both and fused: "linear" a * dense + b * sparse,
+        "rrf" 1 / (a + position) summed over the lists that hold the id (a defaults to 60).
+        bert_hip.h "Hybrid search" states the result through search() and score_ids().  k <= 2 n_cand
+        <= 128.  Any B: 64 queries per call of the library."""
+        q = index._rows(queries)
+        t, w = self._pairs(terms, weights)
+        if t.shape[0] != q.shape[0]:
+            raise ValueError("%d dense and %d sparse queries" % (q.shape[0], t.shape[0]))
+        n_cand, mode, a = self._fusion(k, n_cand, fusion, a, inverted)
+        B, q_top = t.shape
+        scores, ids = np.zeros((B, k), np.float32), np.zeros((B, k), np.int32)
+        for i in range(0, B, 64):
+            self._checked(-abs(self.lib.bertx_hybrid_search(index.idx, self.sp, q[i:].ctypes.data, t[i:].ctypes.data,
+                                                            w[i:].ctypes.data, min(64, B - i), q_top, k, n_cand, mode, a, b,
+                                                            scores[i:].ctypes.data, ids[i:].ctypes.data)),
+                          "bertx_hybrid_search")
+        return scores, ids
+
+    def search_hybrid_texts(self, index, dense_model, texts, k, q_top, n_cand=None, fusion="linear", a=None, b=1.0,
+                            inverted=False):
+        """search_hybrid of texts: dense_model encodes the dense queries, this store's model the sparse
+        ones, cut to their q_top largest weights on the device."""
+        n_cand, mode, a = self._fusion(k, n_cand, fusion, a, inverted)
+        scores, ids = np.zeros((len(texts), k), np.float32), np.zeros((len(texts), k), np.int32)
+        rc = self.lib.bertx_hybrid_search_texts(index.idx, dense_model.ctx, self.sp, self.model.ctx, self.model.N_THREADS,
+                                                len(texts), BertIndex._texts(texts), q_top, k, n_cand, mode, a, b,
+                                                scores.ctypes.data, ids.ctypes.data)
+        self._checked(-abs(rc), "bertx_hybrid_search_texts")
         return scores, ids
 
     def search_texts(self, texts, k, q_top=None, inverted=False, allow=None):

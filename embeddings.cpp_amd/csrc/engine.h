@@ -16,6 +16,7 @@
 
 struct bertx_index;
 struct bertx_mvindex;
+struct bertx_spindex;
 
 namespace emb {
 
@@ -389,5 +390,9 @@ int hip_device_count();
 // (bertx_mvindex_create_ex, the MaxSim bench); storage BERTX_INDEX_F16 or _I8.  NULL
 // after a message.
 ::bertx_mvindex *mvindex_create_on(int ordinal, int w, int64_t cap_docs, int64_t cap_slots, int storage);
+
+// A sparse index (spindex.cpp, bert_hip.h bertx_spindex_*) on device `ordinal`, without a
+// context (bertx_spindex_create, the hybrid bench).  NULL after a message.
+::bertx_spindex *spindex_create_on(int ordinal, int V, int n_top, int64_t cap_docs, int64_t cap_postings);
 
 }  // namespace emb

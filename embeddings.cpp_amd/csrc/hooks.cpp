@@ -1659,3 +1659,83 @@ extern "C" int32_t bertx_bench_spindex_masked(int32_t V, int32_t n_docs, int32_t
             }
     return hook_finish();
 }
+
+// The hybrid search beside its stages (bert_hip.h "Hybrid search"): device 0, no
+// context, bertx_bench_spindex_masked's documents and queries in a sparse index (inverted) beside
+// an f16 embedding index of n_docs hashed unit rows of width d.  us [7][reps]: the dense search
+// for n_cand, the sparse-query search, the inverted search, the hybrid call with mode's fusion
+// over the former and over the latter, bertx_spindex_score_ids_device and
+// bertx_index_score_ids_device at n = 2 n_cand live ids; each sample the average of `iters` calls
+// after 3, the legs alternating within a repetition.  BERTX_HYBRID_INVERTED in mode is ignored.
+extern "C" int32_t bertx_bench_hybrid(int32_t V, int32_t d, int32_t n_docs, int32_t doc_len, int32_t B, int32_t q_len,
+                                      int32_t k, int32_t n_cand, int32_t mode, int32_t iters, int32_t reps, float *us)
+{
+    using namespace emb;
+    const int32_t fusion = mode & ~BERTX_HYBRID_INVERTED;
+    if (V < 1 || V > 65536 || n_docs < 2 * n_cand || doc_len < 1 || doc_len > 1024 || 2 * doc_len > V || B < 1 || B > 64 ||
+        n_cand < 1 || n_cand > 64 || k < 1 || k > 2 * n_cand || sparse_batch_queries(V, q_len, n_cand) == 0 || 2 * q_len > V ||
+        (fusion != BERTX_FUSE_LINEAR && fusion != BERTX_FUSE_RRF) || iters < 1 || reps < 1 || !us || hip_device_count() == 0)
+        return -1;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    struct Stores {
+        bertx_index *ix = nullptr;
+        bertx_spindex *sp = nullptr;
+        ~Stores() { bertx_index_free(ix); bertx_spindex_free(sp); }
+    } S;
+    S.ix = index_create_on(0, d, n_docs, BERTX_INDEX_F16);
+    S.sp = spindex_create_on(0, V, doc_len, n_docs, (int64_t)n_docs * ((doc_len + 15) / 16 * 16));
+    if (!S.ix || !S.sp) return -1;
+    const int chunk = std::min<int>(kSparseAddRows, n_docs), n2 = 2 * n_cand;
+    HookBufs H;
+    float *rows = (float *)H.up(nullptr, 0, (size_t)std::max(chunk, B) * std::max(V, d) * 4);
+    float *dq = (float *)H.up(nullptr, 0, (size_t)B * d * 4), *qw = (float *)H.up(nullptr, 0, (size_t)B * q_len * 4);
+    int32_t *qt = (int32_t *)H.up(nullptr, 0, (size_t)B * q_len * 4), *qc = (int32_t *)H.up(nullptr, 0, (size_t)B * 4);
+    float *sc = (float *)H.up(nullptr, 0, (size_t)B * 128 * 4), *sc2 = (float *)H.up(nullptr, 0, (size_t)B * 128 * 4);
+    int32_t *ids = (int32_t *)H.up(nullptr, 0, (size_t)B * 128 * 4), *ids2 = (int32_t *)H.up(nullptr, 0, (size_t)B * 128 * 4);
+    if (H.bad) return -1;
+    struct Str {
+        hipStream_t s = nullptr;
+        ~Str() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    } E;
+    HIP_RC(hipStreamCreateWithFlags(&E.s, hipStreamNonBlocking));
+    EventPair ev;
+    HIP_RC(ev.create());
+    for (int64_t i = 0; i < n_docs; i += chunk) {
+        const int m = (int)std::min<int64_t>(chunk, n_docs - i);
+        if (launch_unit_rows(rows, m, V, 12345u + (uint32_t)i, E.s) != 0 || bertx_spindex_add_device(S.sp, rows, m, E.s) < 0 ||
+            launch_unit_rows(rows, m, d, 54321u + (uint32_t)i, E.s) != 0 || bertx_index_add_device(S.ix, rows, m, E.s) < 0)
+            return -1;
+    }
+    if (launch_unit_rows(rows, B, V, 4242u, E.s) != 0 || launch_sparse_select(rows, B, V, q_len, qt, qw, qc, E.s) != 0 ||
+        launch_unit_rows(dq, B, d, 777u, E.s) != 0)
+        return -1;
+    HIP_RC(hipStreamSynchronize(E.s));
+    // the inverted image, the hybrid call's scratch (its first call allocates) and 2 n_cand live ids per query
+    if (bertx_spindex_build_inverted(S.sp) != 0 ||
+        bertx_hybrid_search_device(S.ix, S.sp, dq, qt, qw, B, q_len, k, n_cand, fusion, 1.f, 1.f, sc, ids, E.s) != 0 ||
+        bertx_index_search_device(S.ix, dq, B, n2, sc2, ids2, E.s) != 0)
+        return -1;
+    for (int r = 0; r < reps; ++r)
+        for (int leg = 0; leg < 7; ++leg) {
+            for (int i = -3; i < iters; ++i) {
+                if (i == 0) HIP_RC(hipEventRecord(ev.a, E.s));
+                int rc = 0;
+                if (leg == 0) rc = bertx_index_search_device(S.ix, dq, B, n_cand, sc, ids, E.s);
+                if (leg == 1) rc = bertx_spindex_search_sparse_device(S.sp, qt, qw, B, q_len, n_cand, sc, ids, E.s);
+                if (leg == 2) rc = bertx_spindex_search_inverted_device(S.sp, qt, qw, B, q_len, n_cand, sc, ids, E.s);
+                if (leg == 3 || leg == 4)
+                    rc = bertx_hybrid_search_device(S.ix, S.sp, dq, qt, qw, B, q_len, k, n_cand,
+                                                    fusion | (leg == 4 ? BERTX_HYBRID_INVERTED : 0), 1.f, 1.f, sc, ids, E.s);
+                if (leg == 5) rc = bertx_spindex_score_ids_device(S.sp, qt, qw, B, q_len, ids2, n2, sc, E.s);
+                if (leg == 6) rc = bertx_index_score_ids_device(S.ix, dq, B, ids2, n2, sc, E.s);
+                if (rc != 0) return -1;
+            }
+            HIP_RC(hipEventRecord(ev.b, E.s));
+            HIP_RC(hipEventSynchronize(ev.b));
+            float ms = 0.f;
+            HIP_RC(hipEventElapsedTime(&ms, ev.a, ev.b));
+            us[(size_t)leg * reps + r] = ms * 1000.f / (float)iters;
+        }
+    return hook_finish();
+}

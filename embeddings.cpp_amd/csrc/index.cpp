@@ -196,6 +196,8 @@ int32_t search_rescored_device_locked(bertx_index &coarse, bertx_index &fine, co
 
 }  // namespace
 
+int index_ordinal(const bertx_index *ix) { return ix->ordinal; }
+
 bertx_index *index_create_on(int ordinal, int d, int64_t capacity, int storage)
 {
     if (!kind_known(storage)) {

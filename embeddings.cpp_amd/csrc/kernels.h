@@ -542,6 +542,24 @@ int launch_sparse_inv_search(const uint32_t *inv, const uint32_t *rows, const vo
                              int inv_block, const int32_t *d_terms, const float *d_weights, int B, int q_top, int k,
                              void *partial, float *d_scores, int32_t *d_ids, hipStream_t s, int max_wg = 0,
                              int *ran_wg = nullptr, const SearchMask *mask = nullptr);
+// Scores of listed documents (sparse_gather.hip): d_scores f32 [B][n] = the score of (query b of
+// d_terms / d_weights [B][q_top], document d_ids[b][j]) with the bits launch_sparse_scan_batch
+// gives that pair, -inf for an id outside [0, n_docs) or, tomb given (the store's tombstones;
+// null launches the instantiation without the test), one whose bit is 1.  One launch.
+// 1 <= B <= 64, 1 <= q_top <= 1024, 1 <= n <= 128; -1 otherwise, -3: launch refused.
+int launch_sparse_score_ids(const uint32_t *store, const void *d_table, int n_docs, int V, const int32_t *d_terms,
+                            const float *d_weights, int B, int q_top, const int32_t *d_ids, int n, float *d_scores,
+                            hipStream_t s, const uint32_t *tomb = nullptr);
+// The hybrid search's two kernels (hybrid.hip; bert_hip.h "Hybrid search"), one wave per query.
+// Union: cd / cs int32 [B][n_cand] (-1 the fill, the ids of one list distinct) -> U int32
+// [B][2 n_cand] the distinct ids >= 0 ascending, then -1; rd / rs: the id's 1-based position in
+// cd / cs, 0 for none.  Fuse: the k <= 2 n_cand best (f, id) of U, f from the scorers' sd / ss
+// f32 [B][2 n_cand] (linear: a sd + b ss, each operation rounded; an id either scores -inf is
+// the fill) or, rrf, from rd / rs (1 / (a + position), summed).  1 <= n_cand <= 64.
+int launch_hybrid_union(const int32_t *cd, const int32_t *cs, int B, int n_cand, int32_t *U, int32_t *rd, int32_t *rs,
+                        hipStream_t s);
+int launch_hybrid_fuse(const int32_t *U, const int32_t *rd, const int32_t *rs, const float *sd, const float *ss, int B,
+                       int n_cand, int k, bool rrf, float a, float b, float *d_scores, int32_t *d_ids, hipStream_t s);
 // Benches: heavy term j < kSparseHeavyTerms set in d_rows f32 [n][V] at weight 2 + j / 8, in a
 // share 1/2 (3/4)^j of the rows (all_of == 0), or the first all_of heavy terms in every row.
 constexpr int kSparseHeavyTerms = 16;

@@ -10,6 +10,9 @@
 // inverted_docs documents; the inverted search refuses to run while that is not all of them.
 // Tombstones (index_mask.hip) and the callers' filters limit every search to the admissible
 // documents (bert_hip.h "Sparse index", "Deleting documents and filtered search").
+// Listed documents are scored by a gather (sparse_gather.hip), and the hybrid search (bert_hip.h
+// "Hybrid search") stacks that scorer, the embedding index's and the two first
+// stages around the union and fusion kernels (hybrid.hip); its scratch belongs to this store.
 #include "bert.h"
 #include "bert_hip.h"
 
@@ -64,6 +67,9 @@ struct bertx_spindex {
     int64_t tomb_words = 0;
     bool removed = false;
     int last_masked = 0;
+    // the hybrid search's scratch, allocated by the first hybrid call: cd, cs, U, rd, rs, sd, ss,
+    // [64][128] words each
+    int32_t *hyb = nullptr;
     hipStream_t stream = nullptr;
     emb::StoreOrder ord;
     std::mutex mu;
@@ -75,7 +81,7 @@ struct bertx_spindex {
         for (void *p : {(void *)store, (void *)table, (void *)d_used, (void *)sel_terms, (void *)sel_count,
                         (void *)sel_weights, (void *)st_rows, (void *)st_scores, (void *)st_ids, qtab, partial,
                         (void *)st_qterms, (void *)st_qweights, qimage, (void *)inv, (void *)inv_rows,
-                        (void *)tomb})
+                        (void *)tomb, (void *)hyb})
             if (p) (void)hipFree(p);
         if (ord.done) (void)hipEventDestroy(ord.done);
         if (stream) (void)hipStreamDestroy(stream);
@@ -256,6 +262,72 @@ int32_t search_inverted_device_locked(bertx_spindex &sp, const int32_t *d_terms,
                                     q_top, k, sp.partial, d_scores, d_ids, s, sp.grid_cap, &sp.last_grid, mask.get());
 }
 
+// The scorer of listed documents on s: a deleted document as an id the store does not hold.
+int32_t score_ids_device_locked(bertx_spindex &sp, const int32_t *d_terms, const float *d_weights, int32_t B, int32_t q_top,
+                                const int32_t *d_ids, int32_t n, float *d_scores, hipStream_t s)
+{
+    if (!d_terms || !d_weights || !d_ids || !d_scores || B < 1 || B > 64 || q_top < 1 || q_top > 1024 || n < 1 || n > 128) {
+        errorf("bertx_spindex_score_ids: B = %d, q_top = %d, n = %d are not in 1 <= B <= 64, 1 <= q_top <= 1024, "
+               "1 <= n <= 128\n", B, q_top, n);
+        return -1;
+    }
+    Ordered o(sp.ord, s);
+    sp.last_masked = sp.removed;
+    return launch_sparse_score_ids(sp.store, sp.table, (int)sp.n_docs, sp.V, d_terms, d_weights, B, q_top, d_ids, n,
+                                   d_scores, s, sp.removed ? sp.tomb : nullptr);
+}
+
+constexpr size_t kHybWords = 64 * 128;   // words of one of the hybrid search's seven buffers
+
+// The hybrid search on s (sp locked, its device current; ix is locked by each of its entries):
+// every refusal comes before the first launch.
+int32_t hybrid_device_locked(bertx_index *ix, bertx_spindex &sp, const float *d_q, const int32_t *d_terms,
+                             const float *d_weights, int32_t B, int32_t q_top, int32_t k, int32_t n_cand, int32_t mode,
+                             float a, float b, float *d_scores, int32_t *d_ids, hipStream_t s)
+{
+    const int32_t fusion = mode & ~BERTX_HYBRID_INVERTED;
+    const bool inverted = (mode & BERTX_HYBRID_INVERTED) != 0, rrf = fusion == BERTX_FUSE_RRF;
+    if (!ix || !d_q || !d_terms || !d_weights || !d_scores || !d_ids || B < 1 || B > 64 || q_top < 1 || q_top > 1024 ||
+        n_cand < 1 || n_cand > 64 || k < 1 || k > 2 * n_cand || (fusion != BERTX_FUSE_LINEAR && !rrf) ||
+        (!inverted && sparse_batch_queries(sp.V, q_top, n_cand) == 0)) {
+        errorf("bertx_hybrid_search: B = %d, q_top = %d, k = %d, n_cand = %d, mode = %d are not in 1 <= B <= 64, "
+               "1 <= q_top <= 1024, 1 <= n_cand <= 64, 1 <= k <= 2 n_cand, BERTX_FUSE_LINEAR or _RRF\n", B, q_top, k, n_cand,
+               mode);
+        return -1;
+    }
+    if (index_ordinal(ix) != sp.ordinal) {
+        errorf("bertx_hybrid_search: the embedding index lies on device %d, the sparse index on device %d\n",
+               index_ordinal(ix), sp.ordinal);
+        return -1;
+    }
+    if (inverted && sp.inverted_docs != sp.n_docs) {
+        errorf("bertx_hybrid_search: %lld of %lld documents are inverted; call bertx_spindex_build_inverted\n",
+               (long long)sp.inverted_docs, (long long)sp.n_docs);
+        return -1;
+    }
+    if (!sp.hyb) {
+        if (capturing(s) || hipMalloc((void **)&sp.hyb, 7 * kHybWords * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            sp.hyb = nullptr;
+            errorf("bertx_hybrid_search: the first call on a sparse index allocates %zu bytes and cannot be captured\n",
+                   7 * kHybWords * 4);
+            return -2;
+        }
+    }
+    int32_t *cd = sp.hyb, *cs = cd + kHybWords, *U = cs + kHybWords, *rd = U + kHybWords, *rs = rd + kHybWords;
+    float *sd = (float *)(rs + kHybWords), *ss = sd + kHybWords;   // (first the stages' own scores)
+    Ordered o(sp.ord, s);
+    int32_t rc = bertx_index_search_device(ix, d_q, B, n_cand, sd, cd, s);
+    if (rc == 0)
+        rc = (inverted ? search_inverted_device_locked : search_sparse_device_locked)(sp, d_terms, d_weights, B, q_top, n_cand,
+                                                                                      ss, cs, s, Filters());
+    if (rc == 0) rc = launch_hybrid_union(cd, cs, B, n_cand, U, rd, rs, s);
+    if (rc == 0 && !rrf) rc = bertx_index_score_ids_device(ix, d_q, B, U, 2 * n_cand, sd, s);
+    if (rc == 0 && !rrf) rc = score_ids_device_locked(sp, d_terms, d_weights, B, q_top, U, 2 * n_cand, ss, s);
+    if (rc == 0) rc = launch_hybrid_fuse(U, rd, rs, sd, ss, B, n_cand, k, rrf, a, b, d_scores, d_ids, s);
+    return rc;
+}
+
 // The results of a search launched on the store's stream into st_scores / st_ids (rc: its
 // return value) -> the host.
 int32_t results_to_host(bertx_spindex &sp, int32_t rc, int32_t B, int32_t k, float *scores, int32_t *ids)
@@ -346,6 +418,8 @@ int32_t forward_chunk(hipStream_t stream, float *d_out, struct bert_ctx *ctx, in
                                        stream);
 }
 
+}  // namespace
+
 bertx_spindex *spindex_create_on(int ordinal, int V, int n_top, int64_t cap_docs, int64_t cap_postings)
 {
     if (V < 1 || V > 65536 || n_top < 1 || n_top > 1024) {
@@ -405,7 +479,6 @@ bertx_spindex *spindex_create_on(int ordinal, int V, int n_top, int64_t cap_docs
     return sp;
 }
 
-}  // namespace
 }  // namespace emb
 
 using emb::DeviceGuard;
@@ -764,25 +837,40 @@ int32_t bertx_spindex_search_sparse_device(struct bertx_spindex *sp, const int32
 }
 
 namespace {
+// What the host forms accept as sparse queries; a message otherwise.
+bool queries_ok(int32_t V, const int32_t *terms, const float *weights, int32_t B, int32_t q_top)
+{
+    if (!terms || !weights || B < 1 || B > kStage || q_top < 1 || q_top > 1024) return false;
+    std::vector<int32_t> seen((size_t)V, -1);   // the query that last held the term
+    for (int32_t b = 0; b < B; ++b)
+        for (int32_t j = 0; j < q_top; ++j) {
+            const int32_t t = terms[(size_t)b * q_top + j];
+            if (t < 0) continue;   // an empty slot
+            if (t >= V || seen[(size_t)t] == b || !std::isfinite(weights[(size_t)b * q_top + j])) {
+                emb::errorf("bertx_spindex_search_sparse: query %d, slot %d: terms are below n_vocab = %d and distinct "
+                            "within a query, weights are finite\n", b, j, V);
+                return false;
+            }
+            seen[(size_t)t] = b;
+        }
+    return true;
+}
+
+// The sparse queries of a host form into the staging buffers, on the store's stream (sp locked; the
+// caller orders the copies and synchronises before its arrays leave scope).
+hipError_t stage_queries(struct bertx_spindex *sp, const int32_t *terms, const float *weights, int32_t B, int32_t q_top)
+{
+    const hipError_t e = hipMemcpyAsync(sp->st_qterms, terms, (size_t)B * q_top * 4, hipMemcpyHostToDevice, sp->stream);
+    return e != hipSuccess ? e : hipMemcpyAsync(sp->st_qweights, weights, (size_t)B * q_top * 4, hipMemcpyHostToDevice, sp->stream);
+}
+
 // The host forms of the two sparse-query searches: the refusals, the staging, the search
 // (inverted: over the inverted lists, built first when stale) and the results.
 int32_t search_sparse_host(struct bertx_spindex *sp, const int32_t *terms, const float *weights, int32_t B, int32_t q_top,
                            int32_t k, const uint32_t *filters, int32_t n_filters, int32_t words, float *scores, int32_t *ids,
                            bool inverted)
 {
-    if (!sp || !terms || !weights || !scores || !ids || B < 1 || B > kStage || q_top < 1 || q_top > 1024) return -1;
-    std::vector<int32_t> seen((size_t)sp->V, -1);   // the query that last held the term
-    for (int32_t b = 0; b < B; ++b)
-        for (int32_t j = 0; j < q_top; ++j) {
-            const int32_t t = terms[(size_t)b * q_top + j];
-            if (t < 0) continue;   // an empty slot
-            if (t >= sp->V || seen[(size_t)t] == b || !std::isfinite(weights[(size_t)b * q_top + j])) {
-                emb::errorf("bertx_spindex_search_sparse: query %d, slot %d: terms are below n_vocab = %d and distinct "
-                            "within a query, weights are finite\n", b, j, sp->V);
-                return -1;
-            }
-            seen[(size_t)t] = b;
-        }
+    if (!sp || !scores || !ids || !queries_ok(sp->V, terms, weights, B, q_top)) return -1;
     std::lock_guard<std::mutex> lk(sp->mu);
     if (!emb::filters_fit(sp->n_docs, filters, n_filters, words, B)) return -1;
     DeviceGuard g(sp->ordinal);
@@ -790,8 +878,7 @@ int32_t search_sparse_host(struct bertx_spindex *sp, const int32_t *terms, const
     emb::DevBuf fbuf;   // (freed after the call's synchronise)
     {
         emb::Ordered o(sp->ord, sp->stream);
-        HIP_RC(hipMemcpyAsync(sp->st_qterms, terms, (size_t)B * q_top * 4, hipMemcpyHostToDevice, sp->stream));
-        HIP_RC(hipMemcpyAsync(sp->st_qweights, weights, (size_t)B * q_top * 4, hipMemcpyHostToDevice, sp->stream));
+        HIP_RC(stage_queries(sp, terms, weights, B, q_top));
         HIP_RC(emb::stage_filters(sp->stream, filters, n_filters, words, fbuf));
     }
     HIP_RC(hipStreamSynchronize(sp->stream));   // the caller's arrays are pageable
@@ -851,6 +938,150 @@ int32_t bertx_spindex_search_inverted_device(struct bertx_spindex *sp, const int
 {
     return bertx_spindex_search_inverted_filtered_device(sp, d_terms, d_weights, B, q_top, k, nullptr, 0, 0, d_scores, d_ids,
                                                          stream);
+}
+
+int32_t bertx_spindex_score_ids_device(struct bertx_spindex *sp, const int32_t *d_terms, const float *d_weights, int32_t B,
+                                       int32_t q_top, const int32_t *d_ids, int32_t n, float *d_scores, void *stream)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    return emb::score_ids_device_locked(*sp, d_terms, d_weights, B, q_top, d_ids, n, d_scores,
+                                        stream ? (hipStream_t)stream : sp->stream);
+}
+
+int32_t bertx_spindex_score_ids(struct bertx_spindex *sp, const int32_t *terms, const float *weights, int32_t B,
+                                int32_t q_top, const int32_t *ids, int32_t n, float *scores)
+{
+    if (!sp || !ids || !scores || n < 1 || n > 128 || !queries_ok(sp->V, terms, weights, B, q_top)) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    {
+        emb::Ordered o(sp->ord, sp->stream);
+        HIP_RC(stage_queries(sp, terms, weights, B, q_top));
+        HIP_RC(hipMemcpyAsync(sp->st_ids, ids, (size_t)B * n * 4, hipMemcpyHostToDevice, sp->stream));
+    }
+    HIP_RC(hipStreamSynchronize(sp->stream));
+    const int32_t rc = emb::score_ids_device_locked(*sp, sp->st_qterms, sp->st_qweights, B, q_top, sp->st_ids, n,
+                                                    sp->st_scores, sp->stream);
+    if (rc == 0) HIP_RC(hipMemcpyAsync(scores, sp->st_scores, (size_t)B * n * 4, hipMemcpyDeviceToHost, sp->stream));
+    HIP_RC(hipStreamSynchronize(sp->stream));
+    return rc;
+}
+
+int32_t bertx_hybrid_search_device(struct bertx_index *ix, struct bertx_spindex *sp, const float *d_queries,
+                                   const int32_t *d_terms, const float *d_weights, int32_t B, int32_t q_top, int32_t k,
+                                   int32_t n_cand, int32_t mode, float a, float b, float *d_scores, int32_t *d_ids,
+                                   void *stream)
+{
+    if (!sp) return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    return emb::hybrid_device_locked(ix, *sp, d_queries, d_terms, d_weights, B, q_top, k, n_cand, mode, a, b, d_scores, d_ids,
+                                     stream ? (hipStream_t)stream : sp->stream);
+}
+
+namespace {
+// The host form's second half (sp locked, the sparse queries staged): the dense queries f32 [B][d]
+// to a buffer of the call's own, the search on the store's stream, the results.
+int32_t hybrid_to_host(struct bertx_index *ix, struct bertx_spindex *sp, const float *queries, int32_t B, int32_t q_top,
+                       int32_t k, int32_t n_cand, int32_t mode, float a, float b, float *scores, int32_t *ids)
+{
+    const size_t qbytes = (size_t)B * (size_t)bertx_index_dim(ix) * 4;
+    emb::DevBuf d_q;   // (freed after the call's synchronise)
+    HIP_RC(hipMalloc(&d_q.p, qbytes));
+    HIP_RC(hipMemcpyAsync(d_q.p, queries, qbytes, hipMemcpyHostToDevice, sp->stream));
+    HIP_RC(hipStreamSynchronize(sp->stream));   // the caller's rows are pageable
+    int32_t rc = (mode & BERTX_HYBRID_INVERTED) ? emb::build_inverted_locked(*sp, sp->stream) : 0;
+    if (rc == 0)
+        rc = emb::hybrid_device_locked(ix, *sp, (const float *)d_q.p, sp->st_qterms, sp->st_qweights, B, q_top, k, n_cand,
+                                       mode, a, b, sp->st_scores, sp->st_ids, sp->stream);
+    return emb::results_to_host(*sp, rc, B, k, scores, ids);
+}
+}  // namespace
+
+int32_t bertx_hybrid_search(struct bertx_index *ix, struct bertx_spindex *sp, const float *queries, const int32_t *terms,
+                            const float *weights, int32_t B, int32_t q_top, int32_t k, int32_t n_cand, int32_t mode,
+                            float a, float b, float *scores, int32_t *ids)
+{
+    if (!ix || !sp || !queries || !scores || !ids || n_cand < 1 || n_cand > 64 || k < 1 || k > 2 * n_cand ||
+        !queries_ok(sp->V, terms, weights, B, q_top))
+        return -1;
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    {
+        emb::Ordered o(sp->ord, sp->stream);
+        HIP_RC(stage_queries(sp, terms, weights, B, q_top));
+    }
+    return hybrid_to_host(ix, sp, queries, B, q_top, k, n_cand, mode, a, b, scores, ids);
+}
+
+int32_t bertx_hybrid_search_texts(struct bertx_index *ix, struct bert_ctx *ctx_dense, struct bertx_spindex *sp,
+                                  struct bert_ctx *ctx_sparse, int32_t n_threads, int32_t n, const char **texts,
+                                  int32_t q_top, int32_t k, int32_t n_cand, int32_t mode, float a, float b, float *scores,
+                                  int32_t *ids)
+{
+    int32_t slot = -1;
+    if (const int32_t rc = emb::text_ctx_ok(sp, ctx_sparse, "bertx_hybrid_search_texts", &slot)) return rc;
+    if (!ix || !ctx_dense || !texts || !scores || !ids || n < 1 || q_top < 1 || q_top > 1024 || n_cand < 1 || n_cand > 64 ||
+        k < 1 || k > 2 * n_cand)
+        return -1;
+    const int32_t d = bertx_index_dim(ix);
+    if (bertx_num_devices(ctx_dense) == 0 || bert_n_embd(ctx_dense) != d) {
+        emb::errorf("bertx_hybrid_search_texts: the dense context cannot produce rows of width %d\n", d);
+        return -1;
+    }
+    // the dense rows as bertx_index_search_texts makes them: one batch, refused as a whole
+    std::vector<float> rows((size_t)n * d, 0.f);
+    std::vector<float *> ptr((size_t)n);
+    for (int32_t i = 0; i < n; ++i) {
+        ptr[(size_t)i] = rows.data() + (size_t)i * d;
+        *ptr[(size_t)i] = std::nanf("");
+    }
+    bert_encode_batch(ctx_dense, n_threads, n, n, texts, ptr.data());
+    for (int32_t i = 0; i < n; ++i)
+        if (std::isnan(*ptr[(size_t)i])) {
+            emb::errorf("bertx_hybrid_search_texts: the encoder refused the texts; nothing was searched\n");
+            return -4;
+        }
+    emb::Texts t;
+    if (emb::tokenize(ctx_sparse, n_threads, n, texts, t) != 0) return -1;
+    std::vector<float> hs((size_t)n * k);
+    std::vector<int32_t> hi((size_t)n * k);
+    std::lock_guard<std::mutex> lk(sp->mu);
+    DeviceGuard g(sp->ordinal);
+    HIP_RC(g.status());
+    std::vector<int32_t> flat;
+    emb::DevBuf d_tok;
+    size_t cap = 0;
+    for (size_t i = 0; i < (size_t)n;) {
+        const size_t e = emb::chunk_end([&](size_t j) { return t.lens[j]; }, i, (size_t)n, emb::kChunkTokens, kStage);
+        const int32_t m = (int32_t)(e - i);
+        int32_t rc = 0;
+        {
+            emb::Ordered o(sp->ord, sp->stream);
+            rc = emb::forward_chunk(sp->stream, sp->st_rows, ctx_sparse, slot, t, i, e, flat, d_tok, &cap);
+            if (rc == 0)
+                rc = emb::launch_sparse_select(sp->st_rows, m, sp->V, q_top, sp->st_qterms, sp->st_qweights, sp->sel_count,
+                                               sp->stream);
+        }
+        if (rc == 0)
+            rc = hybrid_to_host(ix, sp, rows.data() + i * d, m, q_top, k, n_cand, mode, a, b, hs.data() + i * k,
+                                hi.data() + i * k);
+        if (rc != 0) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(sp->stream);
+            return rc < 0 ? rc : -1;
+        }
+        i = e;
+    }
+    std::memcpy(scores, hs.data(), hs.size() * 4);
+    std::memcpy(ids, hi.data(), hi.size() * 4);
+    return 0;
 }
 
 int32_t bertx_spindex_build_inverted(struct bertx_spindex *sp)

@@ -7,7 +7,13 @@
 
 #include <hip/hip_runtime.h>
 
+struct bertx_index;
+
 namespace emb {
+
+// The device of an embedding index (index.cpp), for the hybrid search, which pairs it with a
+// sparse index (spindex.cpp).
+int index_ordinal(const bertx_index *ix);
 
 inline bool capturing(hipStream_t s)
 {

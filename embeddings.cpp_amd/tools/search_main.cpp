@@ -4,11 +4,11 @@
 //
 // usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8|binary [-R f16|int8 [-B N]]]
 //               [-r RERANK_MODEL [-c N] | -l [-c N | -a [-C N [-c N]]] | -L COLBERT_MODEL [-M] [-c N | -a [-C N [-c N]]]]
-//               [-S f16|int8|res2|res4]
+//               [-S f16|int8|res2|res4] [-H MLM_MODEL [-q Q_TOP] [-c N] [-F linear|rrf] [-w A,B]]
 // One text per line of CORPUS.txt; queries from stdin, one per line, `q` or EOF ends.
 // Per hit one line: rank<TAB>id<TAB>score<TAB>text.
 // A stdin line `:del ID [ID ...]` removes those rows from the embedding index
-// (bertx_index_remove; with -R from both indexes) and prints `deleted N`, N being the change
+// (bertx_index_remove; with -R from both indexes, with -H from the sparse index too) and prints `deleted N`, N being the change
 // of bertx_index_live; later queries no longer return them.  With -a there is no embedding
 // index: the line is answered with a message and ignored.
 // A stdin line `:drop ID [ID ...]` removes those documents from the token store (-l or -L,
@@ -60,6 +60,16 @@
 // gets those centroids (read back with bertx_mvindex_centroid) and buckets, the corpus is
 // added to it, the f16 store is freed, and the queries go through the pruned search.
 // -S res* without -C is a usage error.
+// -H MLM_MODEL: hybrid dense + sparse search instead of a second stage.  MLM_MODEL is a model file
+// with the masked-LM records (SPLADE); a sparse index of the corpus (bertx_spindex_*, 128 terms per
+// text) is kept beside the embedding index and inverted after indexing, and every query goes
+// through bertx_hybrid_search_texts with the inverted search as the sparse first stage: each store
+// finds -c candidates (default min(64, 4 k), at least k / 2, at most 64), the query's sparse form is
+// cut to its -q largest weights (default 32, 1 .. 1024), and the union is fused as -F says:
+// linear, the default, A * dense + B * sparse, or rrf, 1 / (A + position) summed over both lists.
+// -w A,B: the two weights (default 1,1; rrf: A defaults to 60, B is ignored).  The printed score
+// is the fused one.  `:del` removes from both stores.  -H with -r, -l, -L, -a or -R, and -q, -F
+// or -w without -H, are usage errors.
 #include "bert.h"
 #include "bert_hip.h"
 
@@ -79,6 +89,8 @@ int main(int argc, char **argv)
     int k = 3, threads = 4, cand = 0, cents = 0, storage = BERTX_INDEX_F16, mv_storage = -1, res_storage = -1;
     int fine_storage = -1, bin_cand = 0;
     bool late = false, all = false, no_mask_keys = false;
+    const char *mlm = nullptr, *weights = nullptr;
+    int q_top = 0, fuse = -1;
     for (int i = 1; i < argc; ++i) {
         const bool has = i + 1 < argc;
         if (!std::strcmp(argv[i], "-m") && has) model = argv[++i];
@@ -105,25 +117,42 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "-a")) all = true;
         else if (!std::strcmp(argv[i], "-M")) no_mask_keys = true;
         else if (!std::strcmp(argv[i], "-L") && has) colbert = argv[++i];
+        else if (!std::strcmp(argv[i], "-H") && has) mlm = argv[++i];
+        else if (!std::strcmp(argv[i], "-q") && has) { q_top = std::atoi(argv[++i]); if (q_top < 1) q_top = -1; }
+        else if (!std::strcmp(argv[i], "-F") && has && !std::strcmp(argv[i + 1], "linear")) { fuse = BERTX_FUSE_LINEAR; ++i; }
+        else if (!std::strcmp(argv[i], "-F") && has && !std::strcmp(argv[i + 1], "rrf")) { fuse = BERTX_FUSE_RRF; ++i; }
+        else if (!std::strcmp(argv[i], "-w") && has) weights = argv[++i];
         else { model = nullptr; break; }
     }
     const bool second = rerank || late || colbert;
     const bool bad_all = (all && ((!late && !colbert) || (cand != 0 && cents == 0))) || (cents != 0 && !all) || cents < 0 ||
                          cents % 16 || cents > 65536;
     if (second && (!all || cents) && cand == 0) cand = std::min(128, 4 * k);
+    // -H: the fusion, its two weights and the candidates per side
+    float wa = fuse == BERTX_FUSE_RRF ? 60.f : 1.f, wb = 1.f;
+    bool bad_hybrid = (!mlm && (q_top != 0 || fuse >= 0 || weights)) || (mlm && (second || all || fine_storage >= 0)) || q_top < 0 ||
+                      q_top > 1024 || (weights && std::sscanf(weights, "%f,%f", &wa, &wb) != 2);
+    if (mlm) {
+        if (q_top == 0) q_top = 32;
+        if (fuse < 0) fuse = BERTX_FUSE_LINEAR;
+        if (cand == 0) cand = std::min(64, 4 * k);
+        bad_hybrid = bad_hybrid || cand < 1 || cand > 64 || k > 2 * cand;
+    }
     // the rescored first stage: what it is asked for (K) and how many binary candidates it takes
     const int first_k = second && !all ? cand : k;
     const bool bad_bin = ((fine_storage >= 0 || bin_cand != 0) && (storage != BERTX_INDEX_BIN || all)) ||
                          (bin_cand != 0 && fine_storage < 0);
     if (fine_storage >= 0 && bin_cand == 0) bin_cand = std::min(128, 4 * first_k);
-    if (bad_bin || (fine_storage >= 0 && (bin_cand < first_k || bin_cand > 128)) || bad_all || !model || !corpus || k < 1 || k > 128 || threads < 1 || (int)(rerank != nullptr) + late + (colbert != nullptr) > 1 ||
-        (second && (!all || cents) ? cand < k || cand > 128 : cand != 0) || (mv_storage >= 0 && !late && !colbert) ||
+    if (bad_hybrid || bad_bin || (fine_storage >= 0 && (bin_cand < first_k || bin_cand > 128)) || bad_all || !model || !corpus || k < 1 || k > 128 || threads < 1 || (int)(rerank != nullptr) + late + (colbert != nullptr) > 1 ||
+        (second && (!all || cents) ? cand < k || cand > 128 : !mlm && cand != 0) || (mv_storage >= 0 && !late && !colbert) ||
         (no_mask_keys && !colbert) || (res_storage >= 0 && cents == 0)) {
         std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads] "
                              "[-s f16|int8|binary [-R f16|int8 (rescore the binary candidates) [-B N (K..128, default 4 K)]]] "
                              "[-r RERANK_MODEL [-c N (k..128, default 4 k)] | -l [-c N | -a [-C CENTROIDS [-c N]]] | "
                              "-L COLBERT_MODEL [-M] [-c N | -a [-C CENTROIDS [-c N]]]] "
-                             "[-S f16|int8 (the token store of -l / -L) | res2|res4 (with -a -C)]\n",
+                             "[-S f16|int8 (the token store of -l / -L) | res2|res4 (with -a -C)] "
+                             "[-H MLM_MODEL (hybrid dense + sparse) [-q Q_TOP (1..1024, default 32)] [-c N (1..64, k <= 2 N)] "
+                             "[-F linear|rrf] [-w A,B]]\n",
                      argv[0]);
         return 2;
     }
@@ -181,6 +210,23 @@ int main(int argc, char **argv)
         bert_free(ctx);
         return 1;
     }
+    // -H: the masked-LM model and the sparse index beside the embedding index
+    bert_ctx *hctx = nullptr;
+    bertx_spindex *sp = nullptr;
+    if (mlm) {
+        constexpr int32_t n_top = 128;
+        hctx = bert_load_from_file(mlm);
+        if (hctx && bertx_sparse_width(hctx) > 0)
+            sp = bertx_spindex_create(hctx, 0, bertx_sparse_width(hctx), n_top, (int32_t)texts.size(), (int64_t)texts.size() * n_top);
+        if (!sp) {
+            std::fprintf(stderr, "search: '%s' %s\n", mlm,
+                         !hctx ? "cannot be loaded" : bertx_sparse_width(hctx) > 0 ? "gives no sparse index" : "has no masked-LM head");
+            if (hctx) bert_free(hctx);
+            bertx_index_free(idx);
+            bert_free(ctx);
+            return 1;
+        }
+    }
     bertx_mvindex *mv = nullptr;
     if (late) {
         // the store's size: every text's token count, as bert_tokenize counts it
@@ -222,6 +268,9 @@ int main(int argc, char **argv)
                        (fine && bertx_index_add_texts(fine, ctx, threads, (int32_t)p.size(), p.data()) < 0))) {
                 std::fprintf(stderr, "search: indexing failed at text %zu\n", i);
                 rc = 1;
+            } else if (sp && bertx_spindex_add_texts(sp, hctx, threads, (int32_t)p.size(), p.data()) < 0) {
+                std::fprintf(stderr, "search: sparse indexing failed at text %zu\n", i);
+                rc = 1;
             } else if (to && (colbert ? bertx_mvindex_add_texts_colbert(to, rctx, threads, (int32_t)p.size(), p.data(), doc_maxlen)
                                       : bertx_mvindex_add_texts(to, ctx, threads, (int32_t)p.size(), p.data())) < 0) {
                 std::fprintf(stderr, "search: token indexing failed at text %zu\n", i);
@@ -230,6 +279,10 @@ int main(int argc, char **argv)
         }
     };
     add_corpus(idx, mv);
+    if (rc == 0 && sp && bertx_spindex_build_inverted(sp) != 0) {
+        std::fprintf(stderr, "search: inverting the sparse index failed\n");
+        rc = 1;
+    }
     if (rc == 0 && cents && bertx_mvindex_train_centroids(mv, cents, 8, 0) != 0) {
         std::fprintf(stderr, "search: training %d centroids failed\n", cents);
         rc = 1;
@@ -277,7 +330,8 @@ int main(int argc, char **argv)
             }
             const int32_t before = bertx_index_live(idx);
             if (!del.empty() && (bertx_index_remove(idx, del.data(), (int32_t)del.size()) != 0 ||
-                                 (fine && bertx_index_remove(fine, del.data(), (int32_t)del.size()) != 0))) {
+                                 (fine && bertx_index_remove(fine, del.data(), (int32_t)del.size()) != 0) ||
+                                 (sp && bertx_spindex_remove(sp, del.data(), (int32_t)del.size()) != 0))) {
                 std::fprintf(stderr, "search: deleting failed\n");
                 rc = 1;
                 break;
@@ -321,6 +375,19 @@ int main(int argc, char **argv)
                           : bertx_mvindex_search_texts(mv, ctx, threads, 1, &qp, k, scores.data(), ids.data());
             if (qrc != 0) {
                 std::fprintf(stderr, "search: late-interaction search failed\n");
+                rc = 1;
+                break;
+            }
+            for (int j = 0; j < k && ids[(size_t)j] >= 0; ++j)
+                std::printf("%d\t%d\t%.4f\t%s\n", j + 1, ids[(size_t)j], scores[(size_t)j], texts[(size_t)ids[(size_t)j]].c_str());
+            std::fflush(stdout);
+            continue;
+        }
+        if (sp) {
+            // the hybrid search: the k best of both stores' candidates by the fused score
+            if (bertx_hybrid_search_texts(idx, ctx, sp, hctx, threads, 1, &qp, q_top, k, cand, fuse | BERTX_HYBRID_INVERTED, wa,
+                                          wb, scores.data(), ids.data()) != 0) {
+                std::fprintf(stderr, "search: hybrid search failed\n");
                 rc = 1;
                 break;
             }
@@ -388,6 +455,8 @@ int main(int argc, char **argv)
             std::printf("%d\t%d\t%.4f\t%s\n", j + 1, ids[(size_t)j], scores[(size_t)j], texts[(size_t)ids[(size_t)j]].c_str());
         std::fflush(stdout);
     }
+    bertx_spindex_free(sp);
+    if (hctx) bert_free(hctx);
     bertx_mvindex_free(mv);
     bertx_index_free(fine);
     bertx_index_free(idx);

@@ -1588,6 +1588,72 @@ BERT_API int32_t bertx_bench_sparse(int32_t d, int32_t V, int32_t n_seqs, int32_
  * launching the unmasked kernels).  The inverted search also skips a whole block that holds no
  * admissible document for the query before any of its lists is fetched.
  *
+ * Listed documents.  bertx_spindex_score_ids_device(sp, d_terms, d_weights, B, q_top, d_ids, n,
+ * d_scores, stream): queries in the layout of bertx_spindex_search_sparse_device (int32 / f32
+ * [B][q_top]; a term outside 0 .. n_vocab - 1 is an empty slot, of a repeated term the highest
+ * slot counts), 1 <= B <= 64, 1 <= q_top <= 1,024; d_ids int32 [B][n], 1 <= n <= 128; d_scores f32
+ * [B][n].  scores[b][j] carries exactly the bits bertx_spindex_search_sparse (and so
+ * bertx_spindex_search on the densified query) gives the pair (query b, document ids[b][j]): the
+ * document-major arithmetic above, 16 sub-sums folded 8, 4, 2, 1 apart, not the inverted search's.
+ * -inf for an id outside [0, docs) and for a deleted document; so the id output of a search, -1
+ * fill and repeated ids included, can be passed as it is (bertx_index_score_ids's rule).  One
+ * kernel, a gather: a quarter-wave per listed document, the query as a rank dictionary in LDS
+ * (DESIGN.md 9i-6).  Asynchronous, capturable, allocates nothing, ordered as the searches are.
+ * Refusals return a negative error with the output untouched.  bertx_spindex_score_ids is the host
+ * form; it also refuses what bertx_spindex_search_sparse refuses (a term >= n_vocab, a term repeated
+ * within a query, a non-finite weight).  A store from which nothing was removed launches the
+ * instantiation without the tombstone test (bertx_test_spindex_last_masked reports this launch too).
+ *
+ * Hybrid search: the embedding index and the sparse index stacked.  bertx_hybrid_search_device(ix,
+ * sp, d_queries, d_terms, d_weights, B, q_top, k, n_cand, mode, a, b, d_scores, d_ids, stream):
+ * ix an embedding index of any storage kind with queries f32 [B][dim], sp a sparse index on the
+ * same GPU with the sparse queries int32 / f32 [B][q_top]; ids correspond by insertion order, and
+ * keeping the two stores in step is the caller's job, as in the rescored search.  1 <= B <= 64,
+ * 1 <= n_cand <= 64, 1 <= k <= 2 n_cand; mode is BERTX_FUSE_LINEAR or BERTX_FUSE_RRF, with
+ * BERTX_HYBRID_INVERTED ORed in for the inverted search as the sparse first stage (a stale image
+ * is refused as bertx_spindex_search_inverted_device refuses it), else
+ * bertx_spindex_search_sparse_device is.  The result, stated through the entries above, bit for bit:
+ *   cd = the ids of bertx_index_search(ix, queries, n_cand)                    [B][n_cand]
+ *   cs = the ids of the chosen sparse search(sp, terms, weights, n_cand)       [B][n_cand]
+ *   U  = per query the distinct ids >= 0 of cd and cs, ascending, -1 fill      [B][2 n_cand]
+ *   LINEAR: sd = bertx_index_score_ids(ix, queries, U), ss = bertx_spindex_score_ids(sp, terms,
+ *           weights, U); f = fadd(fmul(a, sd), fmul(b, ss)); a pair with sd or ss = -inf is fill
+ *   RRF:    rd, rs = the 1-based position of the id in cd / cs;
+ *           f = fadd(in cd ? fdiv(1, fadd(a, rd)) : +0, in cs ? fdiv(1, fadd(a, rs)) : +0); b is ignored
+ *   result: the k best (f, id), f descending, equal f by ascending id, the fill (-inf, -1) last.
+ * fadd, fmul and fdiv are single f32 operations rounded to nearest even, never contracted into an
+ * FMA (np.float32 arithmetic restates them); a, b and the stages' scores are finite: the order of a
+ * NaN fused score (inf - inf, 0 * inf) is outside the contract (it ranks as -inf does, in front of
+ * the fill); the linear ss are the document-major bits even when
+ * the inverted search chose the candidates.  With (a, b) = (0, 1), finite scores and n_cand >= docs
+ * LINEAR is the sparse search's own result, with (1, 0) the dense search's.  Tombstones of either
+ * store act through the stages: each search returns live candidates only, and a candidate the other
+ * store has deleted scores -inf and becomes fill (LINEAR; RRF never asks the scorers).  Seven
+ * launches (RRF five): the two searches, hybrid_union_kernel, the two scorers, hybrid_fuse_kernel.
+ * The first hybrid call on a sparse index allocates the call's scratch (seven buffers of [64][128]
+ * words) and cannot be captured (-2 on a capturing stream); later calls allocate nothing, never
+ * synchronise and can be captured.  Two concurrent calls on one sp are serialised; the call is
+ * ordered behind the earlier operations on both stores.  Refusals (a null pointer, a limit, an
+ * unknown mode, stores on different GPUs, a stale image with the inverted bit) return a negative
+ * error with the outputs untouched.  bertx_hybrid_search is the host form: bertx_spindex_search_sparse's
+ * refusals as well, and with the inverted bit it builds the image first when stale, as
+ * bertx_spindex_search_inverted does.  bertx_hybrid_search_texts(ix, ctx_dense, sp, ctx_sparse,
+ * n_threads, n, texts, q_top, k, n_cand, mode, a, b, scores, ids), any n: the dense rows as
+ * bertx_index_search_texts makes them, the sparse queries as bertx_spindex_search_texts_top does
+ * (the sparse forward and the selection of the q_top largest weights on the device), 64 texts per
+ * hybrid call.  build/bin/search -H MLM_MODEL [-q q_top] [-c n_cand] [-F linear|rrf] [-w a,b] keeps
+ * a sparse index of the corpus beside the embedding index, inverted after indexing, and answers
+ * every query with this entry (the inverted first stage); `:del` removes from both stores.
+ * Not provided for the hybrid entry: per-call filters, more than 64 candidates per
+ * side, more than two lists, weights per query.
+ * bertx_bench_hybrid(V, d, n_docs, doc_len, B, q_len, k, n_cand, mode, iters, reps, us) (device 0,
+ * no context): bertx_bench_spindex_masked's documents and queries (no skew) in a sparse index,
+ * inverted, beside an f16 embedding index of n_docs hashed unit rows of width d.  us [7][reps]: the
+ * dense search for n_cand, the sparse-query search, the inverted search, the hybrid call with
+ * mode's fusion over the former and over the latter (BERTX_HYBRID_INVERTED in mode is ignored),
+ * bertx_spindex_score_ids_device and bertx_index_score_ids_device at n = 2 n_cand live ids; the
+ * legs alternate within a repetition, each sample the average of `iters` calls after 3 warm-up calls.
+ *
  * bertx_test_sparse_select (parity hook; host buffers, device 0): rows f32 [S][V] ->
  * terms int32 [S][n], weights f32 [S][n] (the input's bits), count int32 [S]; slots past a
  * row's count hold (-1, +0).  Guard rows of NaN bits lie behind the three device outputs;
@@ -1622,9 +1688,8 @@ BERT_API int32_t bertx_bench_sparse(int32_t d, int32_t V, int32_t n_seqs, int32_
  *
  * Not provided: dynamic pruning (WAND, block-max); int8 or impact-quantized weights; compaction
  * (reclaiming deleted documents' postings or renumbering); skipping the posting loads of masked
- * documents in the two document-major scans; saving the masks; scoring listed ids; a mode of
- * the `search` tool; saving and loading; an inverted image without the forward store;
- * vocabularies above 65,536 terms.
+ * documents in the two document-major scans; saving the masks; saving and loading; an inverted
+ * image without the forward store; vocabularies above 65,536 terms.
  */
 struct bertx_spindex;
 BERT_API struct bertx_spindex *bertx_spindex_create(struct bert_ctx *ctx, int32_t slot, int32_t n_vocab, int32_t n_top,
@@ -1698,6 +1763,25 @@ BERT_API int32_t bertx_spindex_search_inverted_filtered_device(struct bertx_spin
                                                                int32_t k, const uint32_t *d_filters, int32_t n_filters,
                                                                int32_t words, float *d_scores, int32_t *d_ids,
                                                                void *stream);
+BERT_API int32_t bertx_spindex_score_ids(struct bertx_spindex *sp, const int32_t *terms, const float *weights, int32_t B,
+                                         int32_t q_top, const int32_t *ids, int32_t n, float *scores);
+BERT_API int32_t bertx_spindex_score_ids_device(struct bertx_spindex *sp, const int32_t *d_terms, const float *d_weights,
+                                                int32_t B, int32_t q_top, const int32_t *d_ids, int32_t n,
+                                                float *d_scores, void *stream);
+enum { BERTX_FUSE_LINEAR = 0, BERTX_FUSE_RRF = 1, BERTX_HYBRID_INVERTED = 16 };
+BERT_API int32_t bertx_hybrid_search_device(struct bertx_index *ix, struct bertx_spindex *sp, const float *d_queries,
+                                            const int32_t *d_terms, const float *d_weights, int32_t B, int32_t q_top,
+                                            int32_t k, int32_t n_cand, int32_t mode, float a, float b, float *d_scores,
+                                            int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_hybrid_search(struct bertx_index *ix, struct bertx_spindex *sp, const float *queries,
+                                     const int32_t *terms, const float *weights, int32_t B, int32_t q_top, int32_t k,
+                                     int32_t n_cand, int32_t mode, float a, float b, float *scores, int32_t *ids);
+BERT_API int32_t bertx_hybrid_search_texts(struct bertx_index *ix, struct bert_ctx *ctx_dense, struct bertx_spindex *sp,
+                                           struct bert_ctx *ctx_sparse, int32_t n_threads, int32_t n, const char **texts,
+                                           int32_t q_top, int32_t k, int32_t n_cand, int32_t mode, float a, float b,
+                                           float *scores, int32_t *ids);
+BERT_API int32_t bertx_bench_hybrid(int32_t V, int32_t d, int32_t n_docs, int32_t doc_len, int32_t B, int32_t q_len,
+                                    int32_t k, int32_t n_cand, int32_t mode, int32_t iters, int32_t reps, float *us);
 BERT_API int32_t bertx_test_spindex_last_masked(struct bertx_spindex *sp);
 BERT_API int32_t bertx_bench_spindex_masked(int32_t V, int32_t n_docs, int32_t doc_len, int32_t B, int32_t q_len,
                                             int32_t k, int32_t iters, int32_t reps, float *us);
