@@ -223,6 +223,31 @@ def load_lib(path=None):
         L.bertx_bench_search_rescored.argtypes = [c_i32] * 7 + [c_f32p]
     except AttributeError:
         pass
+    try:   # (lists and the probed search: absent from older BERT_LIB builds)
+        L.bertx_index_set_lists.restype = c_i32
+        L.bertx_index_set_lists.argtypes = [vp, vp, c_i32]
+        L.bertx_index_train_lists.restype = c_i32
+        L.bertx_index_train_lists.argtypes = [vp, c_i32, c_i32, ctypes.c_uint32]
+        for name in ("bertx_index_build_lists", "bertx_index_lists", "bertx_index_listed_rows"):
+            getattr(L, name).restype = c_i32
+            getattr(L, name).argtypes = [vp]
+        L.bertx_index_lists_bytes.restype = ctypes.c_int64
+        L.bertx_index_lists_bytes.argtypes = [vp]
+        L.bertx_index_list_centroid.restype = c_i32
+        L.bertx_index_list_centroid.argtypes = [vp, c_i32, vp]
+        L.bertx_index_row_lists.restype = c_i32
+        L.bertx_index_row_lists.argtypes = [vp, c_i32, c_i32, vp]
+        L.bertx_index_search_probed.restype = c_i32
+        L.bertx_index_search_probed.argtypes = [vp, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, vp]
+        L.bertx_index_search_probed_device.restype = c_i32
+        L.bertx_index_search_probed_device.argtypes = [vp, vp, c_i32, c_i32, c_i32, vp, c_i32, c_i32, vp, vp, vp]
+        L.bertx_index_search_probed_texts.restype = c_i32
+        L.bertx_index_search_probed_texts.argtypes = [vp, vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_char_p), c_i32, c_i32,
+                                                      vp, vp]
+        L.bertx_bench_search_lists.restype = c_i32
+        L.bertx_bench_search_lists.argtypes = [c_i32] * 6 + [vp, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp]
+    except AttributeError:
+        pass
     try:   # (cross-encoder reranking: absent from older BERT_LIB builds)
         L.bertx_convert_hf_head.restype = c_i32
         L.bertx_convert_hf_head.argtypes = [ctypes.c_char_p, ctypes.c_char_p, c_i32]
@@ -1010,28 +1035,80 @@ class BertIndex:
         (documents)."""
         return pack_allow(allow, B, len(self))
 
-    def search(self, queries, k, allow=None):
+    def search(self, queries, k, allow=None, n_probe=None):
         """(scores f32 [B][k], ids i32 [B][k]) of the k best rows per query, best first.  Deleted
         rows are never returned; allow (bool [size], or [B][size] for one filter per query)
-        limits the search to the rows it marks."""
+        limits the search to the rows it marks.  n_probe: the probed search over the lists of the
+        n_probe centroids nearest to each query (set_lists / train_lists first)."""
         q = self._rows(queries)
         scores = np.zeros((q.shape[0], k), np.float32)
         ids = np.zeros((q.shape[0], k), np.int32)
         f, nf, words = self._allow(allow, q.shape[0])
-        rc = self.lib.bertx_index_search_filtered(self.idx, q.ctypes.data, q.shape[0], k, None if f is None else f.ctypes.data,
-                                                  nf, words, scores.ctypes.data, ids.ctypes.data)
+        fp = None if f is None else f.ctypes.data
+        if n_probe is None:
+            rc = self.lib.bertx_index_search_filtered(self.idx, q.ctypes.data, q.shape[0], k, fp, nf, words,
+                                                      scores.ctypes.data, ids.ctypes.data)
+        else:
+            rc = self.lib.bertx_index_search_probed(self.idx, q.ctypes.data, q.shape[0], k, n_probe, fp, nf, words,
+                                                    scores.ctypes.data, ids.ctypes.data)
         if rc != 0:
             raise RuntimeError("bertx_index_search failed (%d)" % rc)
         return scores, ids
 
-    def search_texts(self, texts, k):
+    def search_texts(self, texts, k, n_probe=None):
         scores = np.zeros((len(texts), k), np.float32)
         ids = np.zeros((len(texts), k), np.int32)
-        rc = self.lib.bertx_index_search_texts(self.idx, self.model.ctx, self.model.N_THREADS, len(texts),
-                                               self._texts(texts), k, scores.ctypes.data, ids.ctypes.data)
+        if n_probe is None:
+            rc = self.lib.bertx_index_search_texts(self.idx, self.model.ctx, self.model.N_THREADS, len(texts),
+                                                   self._texts(texts), k, scores.ctypes.data, ids.ctypes.data)
+        else:
+            rc = self.lib.bertx_index_search_probed_texts(self.idx, self.model.ctx, self.model.N_THREADS, len(texts),
+                                                          self._texts(texts), k, n_probe, scores.ctypes.data, ids.ctypes.data)
         if rc != 0:
             raise RuntimeError("bertx_index_search_texts failed (%d)" % rc)
         return scores, ids
+
+    def set_lists(self, cent):
+        """Cluster the stored rows by their nearest of the centroids cent f32 [C][dim] (kept as
+        f16) and lay out the clustered image that search(n_probe=) reads; bert_hip.h "Lists and
+        probed search"."""
+        c = self._rows(cent)
+        rc = self.lib.bertx_index_set_lists(self.idx, c.ctypes.data, c.shape[0])
+        if rc != 0:
+            raise RuntimeError("bertx_index_set_lists failed (%d)" % rc)
+
+    def train_lists(self, C, iters=8, seed=0):
+        """set_lists with C centroids trained on the stored rows (reproducible k-means)."""
+        rc = self.lib.bertx_index_train_lists(self.idx, C, iters, seed)
+        if rc != 0:
+            raise RuntimeError("bertx_index_train_lists failed (%d)" % rc)
+
+    def build_lists(self):
+        """Cover the rows added since the lists were last built."""
+        rc = self.lib.bertx_index_build_lists(self.idx)
+        if rc != 0:
+            raise RuntimeError("bertx_index_build_lists failed (%d)" % rc)
+
+    def n_lists(self):
+        return int(self.lib.bertx_index_lists(self.idx))
+
+    def listed_rows(self):
+        return int(self.lib.bertx_index_listed_rows(self.idx))
+
+    def list_centroid(self, c):
+        """The stored f16 values of centroid c as f32 [dim]."""
+        out = np.zeros(self.dim, np.float32)
+        if self.lib.bertx_index_list_centroid(self.idx, c, out.ctypes.data) != 0:
+            raise RuntimeError("bertx_index_list_centroid failed")
+        return out
+
+    def row_lists(self, first=0, n=None):
+        """int32 [n]: the list of each of rows first .. first + n - 1 (default: all covered rows)."""
+        n = self.listed_rows() - first if n is None else n
+        out = np.zeros(n, np.int32)
+        if n and self.lib.bertx_index_row_lists(self.idx, first, n, out.ctypes.data) != 0:
+            raise RuntimeError("bertx_index_row_lists failed")
+        return out
 
     def rows(self, first, n):
         """The stored rows first .. first + n - 1 as f32 [n][dim]: the exact f16 values, or

@@ -7,6 +7,7 @@
 #include "repack.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -654,6 +655,89 @@ extern "C" int32_t bertx_bench_search_ex(int32_t d, int32_t N, int32_t B, int32_
     float ms = 0.f;
     HIP_RC(hipEventElapsedTime(&ms, ev.a, ev.b));
     *avg_us = ms * 1000.f / (float)iters;
+    return 0;
+}
+
+// The flat and the probed search over one synthetic index, in one process (bert_hip.h).  The
+// rows are planted: C unit centroids of hashed values, row r = centroid r % C + 0.5 x a unit row
+// of hashed values; query b = centroid (7919 b + 13) % C + 0.5 x another unit row.  Every round
+// times `iters` flat searches and then `iters` probed searches per n_probe, so the two alternate.
+extern "C" int32_t bertx_bench_search_lists(int32_t d, int32_t N, int32_t B, int32_t k, int32_t storage, int32_t C,
+                                            const int32_t *n_probes, int32_t n_np, int32_t rounds, int32_t iters,
+                                            float *flat_us, float *probed_us, float *recall, double *build_ms,
+                                            int64_t *image_bytes)
+{
+    using namespace emb;
+    if (N <= 0 || B <= 0 || iters <= 0 || rounds <= 0 || k < 1 || k > 128 || C < 1 || C > 65536 || !n_probes || n_np < 1 ||
+        !flat_us || !probed_us || !recall || !build_ms || !image_bytes || hip_device_count() == 0 ||
+        (storage != BERTX_INDEX_F16 && storage != BERTX_INDEX_I8))
+        return -1;
+    DeviceGuard guard(0);
+    HIP_RC(guard.status());
+    HookBufs bufs;
+    IndexHolder H;
+    StreamHolder S;   // destroyed (after a synchronise) before the index and the buffers
+    HIP_RC(hipStreamCreateWithFlags(&S.s, hipStreamNonBlocking));
+    H.ix = index_create_on(0, d, N, storage);
+    if (!H.ix) return -1;
+    const int64_t chunk = std::min<int64_t>(kFill, N);
+    float *rows = (float *)bufs.up(nullptr, 0, (size_t)chunk * d * 4);
+    float *cent = (float *)bufs.up(nullptr, 0, (size_t)C * d * 4);
+    float *q = (float *)bufs.up(nullptr, 0, (size_t)B * d * 4);
+    float *sc = (float *)bufs.up(nullptr, 0, (size_t)B * 128 * 4);
+    int32_t *id = (int32_t *)bufs.up(nullptr, 0, (size_t)B * 128 * 4);
+    if (bufs.bad || launch_unit_rows(cent, C, d, 4242u, S.s) != 0) return -1;
+    for (int64_t i = 0; i < N; i += chunk) {
+        const int64_t m = std::min<int64_t>(chunk, N - i);
+        if (launch_unit_rows(rows, m, d, 12345u + (uint32_t)i, S.s) != 0 ||
+            launch_plant_rows(rows, m, d, cent, C, 1, i % C, 0.5f, S.s) != 0 ||
+            bertx_index_add_device(H.ix, rows, (int32_t)m, S.s) < 0)
+            return -1;
+    }
+    if (launch_unit_rows(q, B, d, 777u, S.s) != 0 || launch_plant_rows(q, B, d, cent, C, 7919, 13, 0.5f, S.s) != 0) return -1;
+    std::vector<float> hcent((size_t)C * d);
+    HIP_RC(hipMemcpyAsync(hcent.data(), cent, hcent.size() * 4, hipMemcpyDeviceToHost, S.s));
+    HIP_RC(hipStreamSynchronize(S.s));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (bertx_index_set_lists(H.ix, hcent.data(), C) != 0) return -1;   // (returns after a synchronise)
+    *build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *image_bytes = bertx_index_lists_bytes(H.ix);
+
+    auto call = [&](int what) -> int32_t {   // -1: the flat search; else the probed one with n_probes[what]
+        if (what < 0) return bertx_index_search_device(H.ix, q, B, k, sc, id, S.s);
+        return bertx_index_search_probed_device(H.ix, q, B, k, n_probes[what], nullptr, 0, 0, sc, id, S.s);
+    };
+    // recall of the probed ids against the flat ones, and the warm-up of every shape
+    std::vector<int32_t> flat_ids((size_t)B * k), got((size_t)B * k);
+    for (int what = -1; what < n_np; ++what) {
+        for (int i = 0; i < 3; ++i)
+            if (call(what) != 0) return -1;
+        HIP_RC(hipMemcpyAsync(what < 0 ? flat_ids.data() : got.data(), id, (size_t)B * k * 4, hipMemcpyDeviceToHost, S.s));
+        HIP_RC(hipStreamSynchronize(S.s));
+        if (what < 0) continue;
+        int64_t hit = 0, all = 0;
+        for (int b = 0; b < B; ++b)
+            for (int j = 0; j < k; ++j) {
+                const int32_t want = flat_ids[(size_t)b * k + j];
+                if (want < 0) continue;
+                ++all;
+                hit += std::count(got.begin() + (size_t)b * k, got.begin() + (size_t)(b + 1) * k, want) > 0;
+            }
+        recall[what] = all ? (float)hit / (float)all : 1.f;
+    }
+    EventPair ev;
+    HIP_RC(ev.create());
+    for (int r = 0; r < rounds; ++r)
+        for (int what = -1; what < n_np; ++what) {
+            HIP_RC(hipEventRecord(ev.a, S.s));
+            for (int i = 0; i < iters; ++i)
+                if (call(what) != 0) return -1;
+            HIP_RC(hipEventRecord(ev.b, S.s));
+            HIP_RC(hipEventSynchronize(ev.b));
+            float ms = 0.f;
+            HIP_RC(hipEventElapsedTime(&ms, ev.a, ev.b));
+            (what < 0 ? flat_us[r] : probed_us[(size_t)what * rounds + r]) = ms * 1000.f / (float)iters;
+        }
     return 0;
 }
 

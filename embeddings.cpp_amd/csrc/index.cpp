@@ -10,6 +10,7 @@
 
 #include "engine.h"
 #include "hip_check.h"
+#include "kmeans_update.h"
 #include "store_common.h"
 
 #include <algorithm>
@@ -41,6 +42,20 @@ struct bertx_index {
     // staging of the host forms, kStage rows or queries at a time
     float *st_rows = nullptr, *st_scores = nullptr;
     int32_t *st_ids = nullptr;
+    // the lists (search_lists.hip; bert_hip.h "Lists and probed search"), n_lists == 0: none.
+    // The clustered image covers rows [0, listed) in list_groups of its list_cap_groups groups.
+    int32_t n_lists = 0;
+    int64_t listed = 0, list_groups = 0, list_cap_groups = 0;
+    void *cent = nullptr, *cent_scratch = nullptr;      // the centroids' f16 image, their search's partial lists
+    uint32_t *goff = nullptr, *lcount = nullptr;        // [n_lists + 1] in groups, [n_lists]
+    void *probe_partial = nullptr;                      // [64][min(n_lists, 128)][128] pairs
+    int32_t *row_list = nullptr;                        // [cap]: the list of every covered row
+    void *limage = nullptr;                             // the clustered image, its scales and row ids
+    float *lscales = nullptr;
+    int32_t *slot_id = nullptr;
+    int32_t *probe_ids = nullptr, *item_n = nullptr;    // one pass of the probed search: [64][128] each
+    float *probe_scores = nullptr;
+    uint32_t *pair_sorted = nullptr;
     hipStream_t stream = nullptr;
     emb::StoreOrder ord;
     std::mutex mu;
@@ -50,6 +65,10 @@ struct bertx_index {
         // (no wait for ord.done, unlike the token store: an operation in flight on a caller's
         // stream reads device memory only, and hipFree waits for the device itself)
         if (stream) (void)hipStreamSynchronize(stream);
+        for (void *p : {cent, cent_scratch, (void *)goff, (void *)lcount, probe_partial, (void *)row_list, limage,
+                        (void *)lscales, (void *)slot_id, (void *)probe_ids, (void *)item_n, (void *)probe_scores,
+                        (void *)pair_sorted})
+            if (p) (void)hipFree(p);
         if (rows) (void)hipFree(rows);
         if (scales) (void)hipFree(scales);
         if (tomb) (void)hipFree(tomb);
@@ -194,6 +213,188 @@ int32_t search_rescored_device_locked(bertx_index &coarse, bertx_index &fine, co
     return 0;
 }
 
+// ---- lists and the probed search (bert_hip.h "Lists and probed search") ----
+constexpr int kMaxLists = 65536, kMaxProbe = 128, kProbePass = 64;
+
+bool lists_kind_ok(const bertx_index &ix, const char *who)
+{
+    if (ix.storage != BERTX_INDEX_BIN) return true;
+    errorf("%s: a binary index keeps no lists\n", who);
+    return false;
+}
+
+// hipMalloc into an owned buffer; false (and no HIP error left behind) when it fails
+bool dev_alloc(DevBuf &b, size_t bytes)
+{
+    if (hipMalloc(&b.p, bytes ? bytes : 4) == hipSuccess) return true;
+    (void)hipGetLastError();
+    b.p = nullptr;
+    return false;
+}
+
+// new takes old's place; old's memory is freed when `fresh` goes out of scope
+template <class T> void install(T *&field, DevBuf &fresh)
+{
+    void *old = (void *)field;
+    field = (T *)fresh.p;
+    fresh.p = old;
+}
+
+// Every operation in flight on the index has finished (before buffers it may read are freed).
+int32_t lists_quiesce(bertx_index &ix)
+{
+    HIP_RC(ix.ord.wait());
+    HIP_RC(hipStreamSynchronize(ix.stream));
+    return 0;
+}
+
+struct ImageBufs {
+    DevBuf image, scales, ids;
+    int64_t groups = 0;
+    bool alloc(const bertx_index &ix, int64_t n_rows, int C)
+    {
+        groups = lists_max_groups(n_rows, C);
+        const size_t slots = (size_t)groups * 16;
+        return dev_alloc(image, slots * (size_t)ix.d * (ix.storage == BERTX_INDEX_I8 ? 1 : 2)) && dev_alloc(ids, slots * 4) &&
+               (ix.storage != BERTX_INDEX_I8 || dev_alloc(scales, slots * 4));
+    }
+    void install_in(bertx_index &ix)
+    {
+        install(ix.limage, image);
+        install(ix.lscales, scales);
+        install(ix.slot_id, ids);
+        ix.list_cap_groups = groups;
+    }
+};
+
+// Covers rows [listed, n) (idx locked, its device current, lists set): their lists by the
+// centroid search, kStage rows at a time through the row staging buffer, then the layout of
+// the whole image; nothing to do when every row is covered, unless the lists are new.  -2 with
+// nothing changed when a larger image cannot be allocated.
+int32_t build_lists_locked(bertx_index &ix, bool fresh_lists = false)
+{
+    if (!fresh_lists && ix.listed == ix.n && ix.limage) return 0;
+    if (!ix.limage || lists_max_groups(ix.n, ix.n_lists) > ix.list_cap_groups) {
+        ImageBufs fresh;
+        if (!fresh.alloc(ix, ix.n, ix.n_lists)) {
+            errorf("bertx_index_build_lists: device %d could not allocate the image of %lld rows in %d lists\n", ix.ordinal,
+                   (long long)ix.n, ix.n_lists);
+            return -2;
+        }
+        const int32_t rc = lists_quiesce(ix);
+        if (rc != 0) return rc;
+        fresh.install_in(ix);   // (the covered rows keep their lists; the whole image is laid out below)
+    }
+    uint32_t total = 0;
+    {
+        Ordered o(ix.ord, ix.stream);
+        for (int64_t r0 = ix.listed; r0 < ix.n; r0 += kStage) {
+            const int m = (int)std::min<int64_t>(kStage, ix.n - r0);
+            int rc = launch_index_widen(ix.rows, ix.scales, ix.storage, r0, m, ix.d, ix.st_rows, ix.stream);
+            if (rc == 0)
+                rc = launch_search(ix.cent, nullptr, SEARCH_F16, ix.n_lists, ix.d, ix.st_rows, m, 1, ix.cent_scratch, ix.st_scores,
+                                   ix.row_list + r0, ix.stream);
+            if (rc != 0) return rc;
+        }
+        const int rc = launch_lists_layout(ix.rows, ix.scales, ix.storage, ix.n, ix.d, ix.row_list, ix.n_lists, ix.lcount, ix.goff,
+                                           ix.limage, ix.lscales, ix.slot_id, ix.list_cap_groups, ix.stream);
+        if (rc != 0) return rc;
+        HIP_RC(hipMemcpyAsync(&total, ix.goff + ix.n_lists, 4, hipMemcpyDeviceToHost, ix.stream));
+    }
+    HIP_RC(hipStreamSynchronize(ix.stream));
+    ix.list_groups = total;
+    ix.listed = ix.n;
+    return 0;
+}
+
+int32_t set_lists_locked(bertx_index &ix, const float *cent, int32_t C)
+{
+    if (!lists_kind_ok(ix, "bertx_index_set_lists")) return -1;
+    if (!cent || C < 1 || C > kMaxLists) {
+        errorf("bertx_index_set_lists: C = %d is not in 1 .. %d\n", C, kMaxLists);
+        return -1;
+    }
+    // everything the new lists need, before anything of the old ones is touched
+    DevBuf ncent, nscratch, ngoff, ncount, npartial, nrow, nids, nitem, nscores, nsorted;
+    ImageBufs img;
+    const bool need_img = !ix.limage || lists_max_groups(ix.n, C) > ix.list_cap_groups;
+    const bool ok = dev_alloc(ncent, (size_t)((C + 15) / 16) * 16 * ix.d * 2) &&
+                    dev_alloc(nscratch, (size_t)64 * (size_t)search_max_workgroups(C) * kMaxK * 8) &&
+                    dev_alloc(ngoff, (size_t)(C + 1) * 4) && dev_alloc(ncount, (size_t)C * 4) &&
+                    dev_alloc(npartial, probed_partial_bytes(C)) && (ix.row_list || dev_alloc(nrow, (size_t)ix.cap * 4)) &&
+                    (ix.probe_ids || (dev_alloc(nids, (size_t)kProbePass * kMaxProbe * 4) &&
+                                      dev_alloc(nitem, (size_t)kProbePass * kMaxProbe * 4) &&
+                                      dev_alloc(nscores, (size_t)kProbePass * kMaxProbe * 4) &&
+                                      dev_alloc(nsorted, (size_t)kProbePass * kMaxProbe * 4))) &&
+                    (!need_img || img.alloc(ix, ix.n, C));
+    if (!ok) {
+        errorf("bertx_index_set_lists: device %d could not allocate %d lists over %lld rows\n", ix.ordinal, C, (long long)ix.n);
+        return -2;
+    }
+    for (int32_t c0 = 0; c0 < C; c0 += kStage) {
+        const int32_t m = std::min(kStage, C - c0);
+        HIP_RC(hipMemcpyAsync(ix.st_rows, cent + (size_t)c0 * ix.d, (size_t)m * ix.d * 4, hipMemcpyHostToDevice, ix.stream));
+        const int rc = launch_index_add(ix.st_rows, m, ix.d, c0, SEARCH_F16, ncent.p, nullptr, ix.stream);
+        if (rc != 0) return rc;
+        HIP_RC(hipStreamSynchronize(ix.stream));   // the staging buffer is reused
+    }
+    const int32_t rc = lists_quiesce(ix);
+    if (rc != 0) return rc;
+    install(ix.cent, ncent);
+    install(ix.cent_scratch, nscratch);
+    install(ix.goff, ngoff);
+    install(ix.lcount, ncount);
+    install(ix.probe_partial, npartial);
+    if (!ix.row_list) install(ix.row_list, nrow);
+    if (!ix.probe_ids) {
+        install(ix.probe_ids, nids);
+        install(ix.item_n, nitem);
+        install(ix.probe_scores, nscores);
+        install(ix.pair_sorted, nsorted);
+    }
+    if (need_img) img.install_in(ix);
+    ix.n_lists = C;
+    ix.listed = 0;
+    ix.list_groups = 0;
+    return build_lists_locked(ix, true);   // (an empty index too: the offsets must be written)
+}
+
+// The probed search on s (idx locked, its device current): passes of 64 queries, each the
+// centroid search for the probes and launch_search_probed over the clustered image.
+int32_t search_probed_device_locked(bertx_index &ix, const float *d_q, int32_t B, int32_t k, int32_t n_probe, float *d_scores,
+                                    int32_t *d_ids, hipStream_t s, const Filters &f)
+{
+    if (!d_q || !d_scores || !d_ids || B < 1 || k < 1 || k > kMaxK) return -1;
+    if (ix.n_lists == 0) {
+        errorf("bertx_index_search_probed: the index has no lists (bertx_index_set_lists / _train_lists)\n");
+        return -1;
+    }
+    if (n_probe < 1 || n_probe > std::min(ix.n_lists, kMaxProbe)) {
+        errorf("bertx_index_search_probed: n_probe = %d is not in 1 .. %d\n", n_probe, std::min(ix.n_lists, kMaxProbe));
+        return -1;
+    }
+    if (ix.listed != ix.n) {
+        errorf("bertx_index_search_probed: the lists cover %lld of %lld rows (bertx_index_build_lists)\n", (long long)ix.listed,
+               (long long)ix.n);
+        return -1;
+    }
+    Ordered o(ix.ord, s);
+    for (int32_t b0 = 0; b0 < B; b0 += kProbePass) {
+        const int32_t nq = std::min(kProbePass, B - b0);
+        const float *q = d_q + (size_t)b0 * ix.d;
+        int rc = launch_search(ix.cent, nullptr, SEARCH_F16, ix.n_lists, ix.d, q, nq, n_probe, ix.cent_scratch, ix.probe_scores,
+                               ix.probe_ids, s);
+        if (rc != 0) return rc;
+        const Filters fp = f.from(b0);
+        const SearchMask mask{ix.tomb, fp.d, fp.stride};
+        rc = launch_search_probed(ix.limage, ix.lscales, ix.slot_id, ix.goff, ix.storage, ix.n_lists, ix.d, q, nq, k, n_probe,
+                                  ix.probe_ids, ix.pair_sorted, ix.item_n, ix.probe_partial, d_scores + (size_t)b0 * k,
+                                  d_ids + (size_t)b0 * k, s, ix.removed || f.d ? &mask : nullptr);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
 }  // namespace
 
 int index_ordinal(const bertx_index *ix) { return ix->ordinal; }
@@ -304,6 +505,10 @@ int32_t bertx_index_clear(struct bertx_index *idx)
         idx->removed = false;
     }
     idx->n = 0;
+    // the lists go with the rows (their buffers stay until the next set_lists or the index's end)
+    idx->n_lists = 0;
+    idx->listed = 0;
+    idx->list_groups = 0;
     return 0;
 }
 
@@ -720,6 +925,219 @@ int32_t bertx_index_deleted(struct bertx_index *idx, int32_t first, int32_t n, u
     return 0;
 }
 
+// ---- lists and the probed search ----
+
+int32_t bertx_index_set_lists(struct bertx_index *idx, const float *cent, int32_t C)
+{
+    if (!idx) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    return emb::set_lists_locked(*idx, cent, C);
+}
+
+int32_t bertx_index_build_lists(struct bertx_index *idx)
+{
+    if (!idx) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (!emb::lists_kind_ok(*idx, "bertx_index_build_lists")) return -1;
+    if (idx->n_lists == 0) {
+        emb::errorf("bertx_index_build_lists: the index has no lists\n");
+        return -1;
+    }
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    return emb::build_lists_locked(*idx);
+}
+
+int32_t bertx_index_lists(struct bertx_index *idx)
+{
+    if (!idx) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    return idx->n_lists;
+}
+
+int32_t bertx_index_listed_rows(struct bertx_index *idx)
+{
+    if (!idx) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    return idx->n_lists ? (int32_t)idx->listed : 0;
+}
+
+int64_t bertx_index_lists_bytes(struct bertx_index *idx)
+{
+    if (!idx) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (idx->n_lists == 0) return 0;
+    const int64_t slot_bytes = (int64_t)idx->d * (idx->storage == BERTX_INDEX_I8 ? 1 : 2) + 4 + (idx->storage == BERTX_INDEX_I8 ? 4 : 0);
+    return idx->list_groups * 16 * slot_bytes;
+}
+
+int32_t bertx_index_list_centroid(struct bertx_index *idx, int32_t c, float *out)
+{
+    if (!idx || !out) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (c < 0 || c >= idx->n_lists) return -1;
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    try {
+        const size_t group_halfs = (size_t)16 * idx->d;
+        std::vector<uint16_t> raw(group_halfs);
+        HIP_RC(idx->ord.wait());
+        HIP_RC(hipMemcpy(raw.data(), (const uint16_t *)idx->cent + (size_t)(c / 16) * group_halfs, group_halfs * 2,
+                         hipMemcpyDeviceToHost));
+        emb::unpack_f16_rows(raw.data(), c / 16 * 16, c, 1, idx->d, out);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_index_list_centroid: out of host memory\n");
+        return -1;
+    }
+    return 0;
+}
+
+int32_t bertx_index_row_lists(struct bertx_index *idx, int32_t first, int32_t n, int32_t *out)
+{
+    if (!idx || !out || first < 0 || n < 1) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (idx->n_lists == 0 || (int64_t)first + n > idx->listed) return -1;
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    try {
+        // the caller's output is written only once the copy has succeeded
+        std::vector<int32_t> h((size_t)n);
+        HIP_RC(idx->ord.wait());
+        HIP_RC(hipMemcpy(h.data(), idx->row_list + first, (size_t)n * 4, hipMemcpyDeviceToHost));
+        std::memcpy(out, h.data(), h.size() * 4);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_index_row_lists: out of host memory\n");
+        return -1;
+    }
+    return 0;
+}
+
+// The stored rows first, first + stride, ... (n of them) widened into out [n][d] (idx locked,
+// its device current): bertx_index_rows' values, kStage consecutive rows at a time.
+static int32_t sample_rows(struct bertx_index *idx, const emb::KmeansSample &sm, float *out)
+{
+    const int d = idx->d;
+    std::vector<float> chunk((size_t)emb::kStage * d);
+    int64_t have0 = -1;   // the first row the chunk holds
+    for (int64_t i = 0; i < sm.n; ++i) {
+        const int64_t r = sm.start + i * sm.stride;
+        if (have0 < 0 || r >= have0 + emb::kStage) {
+            have0 = r;
+            const int m = (int)std::min<int64_t>(emb::kStage, idx->n - r);
+            {
+                emb::Ordered o(idx->ord, idx->stream);
+                const int rc = emb::launch_index_widen(idx->rows, idx->scales, idx->storage, r, m, d, idx->st_rows, idx->stream);
+                if (rc != 0) return rc;
+                HIP_RC(hipMemcpyAsync(chunk.data(), idx->st_rows, (size_t)m * d * 4, hipMemcpyDeviceToHost, idx->stream));
+            }
+            HIP_RC(hipStreamSynchronize(idx->stream));
+        }
+        std::memcpy(out + (size_t)i * d, chunk.data() + (size_t)(r - have0) * d, (size_t)d * 4);
+    }
+    return 0;
+}
+
+int32_t bertx_index_train_lists(struct bertx_index *idx, int32_t C, int32_t iters, uint32_t seed)
+{
+    if (!idx) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (!emb::lists_kind_ok(*idx, "bertx_index_train_lists")) return -1;
+    if (C < 1 || C > emb::kMaxLists || iters < 0 || idx->n < 1) {
+        emb::errorf("bertx_index_train_lists: C = %d, iters = %d, %lld rows: nothing to train\n", C, iters, (long long)idx->n);
+        return -1;
+    }
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    try {
+        const int d = idx->d;
+        const emb::KmeansSample sm = emb::kmeans_sample(idx->n, seed);
+        if (C > sm.n) {
+            emb::errorf("bertx_index_train_lists: C = %d exceeds the sample of %lld rows\n", C, (long long)sm.n);
+            return -1;
+        }
+        std::vector<float> sample((size_t)sm.n * d), cent((size_t)C * d);
+        int32_t rc = sample_rows(idx, sm, sample.data());
+        if (rc != 0) return rc;
+        for (int64_t c = 0; c < C; ++c)
+            std::memcpy(cent.data() + (size_t)c * d, sample.data() + (size_t)emb::kmeans_initial_row(c, sm.n, C) * d, (size_t)d * 4);
+        std::vector<int32_t> all((size_t)idx->n);
+        std::vector<uint16_t> codes((size_t)sm.n);
+        for (int32_t it = 0; it < iters; ++it) {
+            rc = emb::set_lists_locked(*idx, cent.data(), C);
+            if (rc != 0) return rc;
+            HIP_RC(idx->ord.wait());
+            HIP_RC(hipMemcpy(all.data(), idx->row_list, all.size() * 4, hipMemcpyDeviceToHost));
+            // (a row without a list, whose scores were not numbers, takes part in no centroid)
+            for (int64_t j = 0; j < sm.n; ++j) codes[(size_t)j] = (uint16_t)std::min<uint32_t>((uint32_t)all[(size_t)(sm.start + j * sm.stride)], 0xffffu);
+            (void)emb::kmeans_update(sample.data(), codes.data(), sm.n, d, C, cent.data());
+        }
+        return emb::set_lists_locked(*idx, cent.data(), C);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_index_train_lists: out of host memory\n");
+        return -1;
+    }
+}
+
+int32_t bertx_index_search_probed_device(struct bertx_index *idx, const float *d_queries, int32_t B, int32_t k,
+                                         int32_t n_probe, const uint32_t *d_filters, int32_t n_filters, int32_t words,
+                                         float *d_scores, int32_t *d_ids, void *stream)
+{
+    if (!idx) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (!emb::lists_kind_ok(*idx, "bertx_index_search_probed")) return -1;
+    if (!emb::filters_ok(*idx, d_filters, n_filters, words, B)) return -1;
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    return emb::search_probed_device_locked(*idx, d_queries, B, k, n_probe, d_scores, d_ids,
+                                            stream ? (hipStream_t)stream : idx->stream,
+                                            emb::filters_of(d_filters, n_filters, words));
+}
+
+int32_t bertx_index_search_probed(struct bertx_index *idx, const float *queries, int32_t B, int32_t k, int32_t n_probe,
+                                  const uint32_t *filters, int32_t n_filters, int32_t words, float *scores, int32_t *ids)
+{
+    if (!idx || !queries || !scores || !ids || B < 1 || k < 1 || k > emb::kMaxK) return -1;
+    std::lock_guard<std::mutex> lk(idx->mu);
+    if (!emb::lists_kind_ok(*idx, "bertx_index_search_probed")) return -1;
+    if (!emb::filters_ok(*idx, filters, n_filters, words, B)) return -1;
+    DeviceGuard g(idx->ordinal);
+    HIP_RC(g.status());
+    if (idx->n_lists && idx->listed != idx->n) {   // the host form covers the new rows first
+        const int32_t rc = emb::build_lists_locked(*idx);
+        if (rc != 0) return rc;
+    }
+    emb::DevBuf fbuf;   // (freed after the last chunk's synchronise)
+    try {
+        const int32_t frc = stage_filters(idx, filters, n_filters, words, fbuf);
+        if (frc != 0) return frc;
+        const emb::Filters f = emb::filters_of((const uint32_t *)fbuf.p, n_filters, words);
+        // the caller's outputs are written only once every chunk has succeeded
+        std::vector<float> hs((size_t)B * k);
+        std::vector<int32_t> hi((size_t)B * k);
+        for (int32_t i = 0; i < B; i += emb::kStage) {
+            const int32_t m = std::min(emb::kStage, B - i);
+            HIP_RC(hipMemcpyAsync(idx->st_rows, queries + (size_t)i * idx->d, (size_t)m * idx->d * 4, hipMemcpyHostToDevice,
+                                  idx->stream));
+            const int32_t rc = emb::search_probed_device_locked(*idx, idx->st_rows, m, k, n_probe, idx->st_scores, idx->st_ids,
+                                                                idx->stream, f.from(i));
+            if (rc != 0) return rc;
+            HIP_RC(hipMemcpyAsync(hs.data() + (size_t)i * k, idx->st_scores, (size_t)m * k * 4, hipMemcpyDeviceToHost,
+                                  idx->stream));
+            HIP_RC(hipMemcpyAsync(hi.data() + (size_t)i * k, idx->st_ids, (size_t)m * k * 4, hipMemcpyDeviceToHost,
+                                  idx->stream));
+            HIP_RC(hipStreamSynchronize(idx->stream));
+        }
+        std::memcpy(scores, hs.data(), hs.size() * 4);
+        std::memcpy(ids, hi.data(), hi.size() * 4);
+    } catch (const std::bad_alloc &) {
+        emb::errorf("bertx_index_search_probed: out of host memory\n");
+        return -1;
+    }
+    return 0;
+}
+
 // texts -> rows through bert_encode_batch as one batch (it refuses the whole call
 // when any input is longer than n_max_tokens and then writes nothing: the NaN
 // planted in every row's first element is still there)
@@ -773,6 +1191,20 @@ int32_t bertx_index_search_texts(struct bertx_index *idx, struct bert_ctx *ctx, 
         return rc != 0 ? rc : bertx_index_search(idx, rows.data(), n, k, scores, ids);
     } catch (const std::exception &ex) {
         emb::errorf("bertx_index_search_texts: %s\n", ex.what());
+        return -1;
+    }
+}
+
+int32_t bertx_index_search_probed_texts(struct bertx_index *idx, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                        const char **texts, int32_t k, int32_t n_probe, float *scores, int32_t *ids)
+{
+    try {
+        if (!scores || !ids || k < 1 || k > emb::kMaxK) return -1;
+        std::vector<float> rows;
+        const int32_t rc = encode_texts(idx, ctx, n_threads, n, texts, rows, "bertx_index_search_probed_texts");
+        return rc != 0 ? rc : bertx_index_search_probed(idx, rows.data(), n, k, n_probe, nullptr, 0, 0, scores, ids);
+    } catch (const std::exception &ex) {
+        emb::errorf("bertx_index_search_probed_texts: %s\n", ex.what());
         return -1;
     }
 }

@@ -271,6 +271,33 @@ int launch_search_merge(const void *partial, int nq, int P, int k, float *d_scor
 // Benches: out f32 [n][d] (device) = unit rows of hashed values.
 int launch_unit_rows(float *d_out, int64_t n, int d, uint32_t seed, hipStream_t s);
 
+// ---- lists and the probed search of the embedding index (search_lists.hip; bert_hip.h
+// "Lists and probed search"), SEARCH_F16 and SEARCH_I8 ----
+// Rows first .. first + n - 1 of the flat image widened to d_out f32 [n][d]: bertx_index_rows' values.
+int launch_index_widen(const void *corpus, const float *scales, int storage, int64_t first, int n, int d, float *d_out,
+                       hipStream_t s);
+// The most 16-row groups the clustered image of n_rows rows in C lists takes (every list
+// padded up), and the bytes of the probed search's per-(query, probe) lists.
+int64_t lists_max_groups(int64_t n_rows, int C);
+size_t probed_partial_bytes(int C);
+// Lays the clustered image out: row_list int32 [n_rows] (a value outside [0, C) puts the row in
+// no list) -> goff uint32 [C + 1] in groups, image (fragment order, the padding zeros), the int8
+// image's scales, slot_id int32 [16 cap_groups] (-1 in the padding).  count uint32 [C] is scratch.
+// cap_groups >= lists_max_groups(n_rows, C) is what the three image buffers hold.
+int launch_lists_layout(const void *corpus, const float *scales, int storage, int64_t n_rows, int d,
+                        const int32_t *row_list, int C, uint32_t *count, uint32_t *goff, void *image, float *img_scales,
+                        int32_t *slot_id, int64_t cap_groups, hipStream_t s);
+// One pass of nq <= 64 queries over the lists probe_ids int32 [nq][n_probe] names (-1: none):
+// the pair sort, the scan, launch_search_merge.  sorted uint32 / item_n int32 [nq n_probe] and
+// partial (probed_partial_bytes) are scratch.  mask as launch_search's, looked up by row id.
+int launch_search_probed(const void *image, const float *img_scales, const int32_t *slot_id, const uint32_t *goff,
+                         int storage, int C, int d, const float *d_queries, int nq, int k, int n_probe,
+                         const int32_t *probe_ids, uint32_t *sorted, int32_t *item_n, void *partial, float *d_scores,
+                         int32_t *d_ids, hipStream_t s, const SearchMask *mask = nullptr);
+// Benches: d_rows [n][d] = d_rows * noise + the centroid (r step + shift) % C of d_cent f32 [C][d].
+int launch_plant_rows(float *d_rows, int64_t n, int d, const float *d_cent, int C, int64_t step, int64_t shift, float noise,
+                      hipStream_t s);
+
 // ---- binary storage of the embedding index (search_bin.hip; the layout, the binarizer
 // and the score: bin_bits.h; the contract: bert_hip.h "Binary storage") ----
 enum { SEARCH_BIN = 8 };   // = BERTX_INDEX_BIN

@@ -2,7 +2,7 @@
 // corpus, then print the k closest texts of every query) with the corpus resident on
 // the GPU and the search fused there (bertx_index_*).
 //
-// usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8|binary [-R f16|int8 [-B N]]]
+// usage: search -m MODEL -f CORPUS.txt [-k 3] [-t threads] [-s f16|int8|binary [-R f16|int8 [-B N]]] [-P LISTS[,N_PROBE]]
 //               [-r RERANK_MODEL [-c N] | -l [-c N | -a [-C N [-c N]]] | -L COLBERT_MODEL [-M] [-c N | -a [-C N [-c N]]]]
 //               [-S f16|int8|res2|res4] [-H MLM_MODEL [-q Q_TOP] [-c N] [-F linear|rrf] [-w A,B]]
 // One text per line of CORPUS.txt; queries from stdin, one per line, `q` or EOF ends.
@@ -70,6 +70,11 @@
 // -w A,B: the two weights (default 1,1; rrf: A defaults to 60, B is ignored).  The printed score
 // is the fused one.  `:del` removes from both stores.  -H with -r, -l, -L, -a or -R, and -q, -F
 // or -w without -H, are usage errors.
+// -P C[,N_PROBE]: lists and the probed search (bert_hip.h "Lists and probed search"): after indexing,
+// C lists (1 .. 65536, at most the corpus' texts) are trained over the stored rows
+// (bertx_index_train_lists, 8 iterations) and every first-stage query goes through
+// bertx_index_search_probed_texts over the N_PROBE lists nearest to it (1 .. min(C, 128), default
+// min(C, 8)).  -P with -s binary, -a or -H is a usage error.
 #include "bert.h"
 #include "bert_hip.h"
 
@@ -91,6 +96,7 @@ int main(int argc, char **argv)
     bool late = false, all = false, no_mask_keys = false;
     const char *mlm = nullptr, *weights = nullptr;
     int q_top = 0, fuse = -1;
+    int lists = 0, n_probe = 0;
     for (int i = 1; i < argc; ++i) {
         const bool has = i + 1 < argc;
         if (!std::strcmp(argv[i], "-m") && has) model = argv[++i];
@@ -122,6 +128,9 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "-F") && has && !std::strcmp(argv[i + 1], "linear")) { fuse = BERTX_FUSE_LINEAR; ++i; }
         else if (!std::strcmp(argv[i], "-F") && has && !std::strcmp(argv[i + 1], "rrf")) { fuse = BERTX_FUSE_RRF; ++i; }
         else if (!std::strcmp(argv[i], "-w") && has) weights = argv[++i];
+        else if (!std::strcmp(argv[i], "-P") && has) {
+            if (std::sscanf(argv[++i], "%d,%d", &lists, &n_probe) < 1 || lists < 1) lists = -1;
+        }
         else { model = nullptr; break; }
     }
     const bool second = rerank || late || colbert;
@@ -143,7 +152,10 @@ int main(int argc, char **argv)
     const bool bad_bin = ((fine_storage >= 0 || bin_cand != 0) && (storage != BERTX_INDEX_BIN || all)) ||
                          (bin_cand != 0 && fine_storage < 0);
     if (fine_storage >= 0 && bin_cand == 0) bin_cand = std::min(128, 4 * first_k);
-    if (bad_hybrid || bad_bin || (fine_storage >= 0 && (bin_cand < first_k || bin_cand > 128)) || bad_all || !model || !corpus || k < 1 || k > 128 || threads < 1 || (int)(rerank != nullptr) + late + (colbert != nullptr) > 1 ||
+    if (lists > 0 && n_probe == 0) n_probe = std::min(lists, 8);
+    const bool bad_lists = lists < 0 || lists > 65536 || (lists > 0 && (n_probe < 1 || n_probe > std::min(lists, 128) ||
+                                                                        storage == BERTX_INDEX_BIN || all || mlm));
+    if (bad_lists || bad_hybrid || bad_bin || (fine_storage >= 0 && (bin_cand < first_k || bin_cand > 128)) || bad_all || !model || !corpus || k < 1 || k > 128 || threads < 1 || (int)(rerank != nullptr) + late + (colbert != nullptr) > 1 ||
         (second && (!all || cents) ? cand < k || cand > 128 : !mlm && cand != 0) || (mv_storage >= 0 && !late && !colbert) ||
         (no_mask_keys && !colbert) || (res_storage >= 0 && cents == 0)) {
         std::fprintf(stderr, "usage: %s -m MODEL -f CORPUS.txt [-k 3 (1..128)] [-t threads] "
@@ -152,7 +164,9 @@ int main(int argc, char **argv)
                              "-L COLBERT_MODEL [-M] [-c N | -a [-C CENTROIDS [-c N]]]] "
                              "[-S f16|int8 (the token store of -l / -L) | res2|res4 (with -a -C)] "
                              "[-H MLM_MODEL (hybrid dense + sparse) [-q Q_TOP (1..1024, default 32)] [-c N (1..64, k <= 2 N)] "
-                             "[-F linear|rrf] [-w A,B]]\n",
+                             "[-F linear|rrf] [-w A,B]] "
+                             "[-P LISTS[,N_PROBE] (probed search over LISTS trained lists, N_PROBE 1..min(LISTS,128), "
+                             "default min(LISTS,8); not with -s binary, -a, -H)]\n",
                      argv[0]);
         return 2;
     }
@@ -283,6 +297,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "search: inverting the sparse index failed\n");
         rc = 1;
     }
+    if (rc == 0 && lists && bertx_index_train_lists(idx, lists, 8, 0) != 0) {
+        std::fprintf(stderr, "search: training %d lists failed\n", lists);
+        rc = 1;
+    }
     if (rc == 0 && cents && bertx_mvindex_train_centroids(mv, cents, 8, 0) != 0) {
         std::fprintf(stderr, "search: training %d centroids failed\n", cents);
         rc = 1;
@@ -397,7 +415,8 @@ int main(int argc, char **argv)
             continue;
         }
         if ((fine ? bertx_index_search_rescored_texts(idx, fine, ctx, threads, 1, &qp, kq, bin_cand, scores.data(), ids.data())
-                  : bertx_index_search_texts(idx, ctx, threads, 1, &qp, kq, scores.data(), ids.data())) != 0) {
+                  : lists ? bertx_index_search_probed_texts(idx, ctx, threads, 1, &qp, kq, n_probe, scores.data(), ids.data())
+                          : bertx_index_search_texts(idx, ctx, threads, 1, &qp, kq, scores.data(), ids.data())) != 0) {
             std::fprintf(stderr, "search: query failed\n");
             rc = 1;
             break;

@@ -532,6 +532,56 @@ BERT_API int32_t bertx_tokenize_batch(struct bert_ctx *ctx, int32_t n_threads, i
  * the token store's masks: "Deleting documents and filtered search" below), f32 storage, f16 queries against int8 rows, 4-bit storage,
  * binary rows against unbinarized queries (asymmetric scores), a fine copy kept in host
  * memory.
+ *
+ * Lists and probed search (inverted-file lists, IVF; f16 and int8 indexes; a BERTX_INDEX_BIN
+ * index refuses every entry of this section with -1 and a message).  The rows are clustered by
+ * their nearest centroid and a search reads only the lists of the n_probe centroids nearest to
+ * the query.  Every result is stated through the entries above and equals them bit for bit.
+ * bertx_index_set_lists(idx, cent float[C][d] on the host, C), 1 <= C <= 65,536: the centroids
+ * are kept as an f16 image, whatever the index's kind, with the bits an f16 index given the same
+ * rows would hold.  With CI an f16 bertx_index that holds cent in order, every stored row r gets
+ *   list(r) = ids[0] of bertx_index_search(CI, bertx_index_rows(idx, r), k = 1)
+ * (the query is the row's widened stored values; ties go to the lower centroid by the search's
+ * ordering rule; a row none of whose scores is a number has list -1 and is in no list), and a
+ * clustered copy of the rows is laid out: every list contiguous in the search kernel's fragment
+ * order and padded to whole 16-row groups, with each slot's row id (and int8 scale) beside it.
+ * A second call replaces the lists; bertx_index_clear drops them.  bertx_index_lists returns C,
+ * or 0; bertx_index_list_centroid(idx, c, out float[d]) the stored f16 values of centroid c,
+ * widened; bertx_index_row_lists(idx, first, n, out int32[n]) the lists of rows first ..
+ * first + n - 1 (covered rows only, else -1 with the output untouched); bertx_index_listed_rows
+ * the number of rows the image covers; bertx_index_lists_bytes the bytes of the image in use
+ * (rows, ids and scales of every group, the padding included).
+ * bertx_index_build_lists covers the rows added since the last build with the same centroids:
+ * it assigns the new rows and lays the whole image out again.  The first build and every growth
+ * allocate; an allocation failure returns -2 and leaves the previous state intact (for
+ * bertx_index_set_lists too).  Both calls are host calls that synchronise.
+ * bertx_index_train_lists(idx, C, iters, seed) is bertx_mvindex_train_centroids' rule ("Centroid
+ * codes" below) word for word with stored rows in place of token rows: the sample is rows
+ * start, start + stride, ... of all `size` rows (tombstones are ignored), the initial centroid c
+ * is sample row floor(c n_sample / C), each iteration is a bertx_index_set_lists, the sample's
+ * lists, and the f64 update on the host (a centroid without a member keeps its row); a final
+ * bertx_index_set_lists leaves the index listed.  -1 when C is out of range or above n_sample,
+ * on an empty index, or for iters < 0.
+ * bertx_index_search_probed_device(idx, d_queries, B, k, n_probe, d_filters, n_filters, words,
+ * d_scores, d_ids, stream), 1 <= n_probe <= min(C, 128), 1 <= k <= 128, B >= 1:
+ *   probes(b) = the ids of bertx_index_search(CI, query b, n_probe)
+ *   result(b) = bertx_index_search_filtered(idx, query b, k,
+ *                  filter = {r : list(r) in probes(b)} AND the caller's filter, if any)
+ * bit for bit: scores, ids, order (score descending, id ascending) and (-inf, -1) fill.
+ * Tombstones and the caller's filter follow "Deleting rows and filtered search": n_filters is 0,
+ * 1 or B, with the same refusals.  With n_probe = C the result is bertx_index_search_filtered's.
+ * The call is asynchronous, capturable and allocates nothing (its scratch is sized when the
+ * lists are set); it is ordered as a search is, and two calls on one index are serialised.  It
+ * returns -1 after a message when listed_rows != size: a stale image is never searched.
+ * bertx_index_search_probed is the host form: it builds first when the image is stale and
+ * stages the filters as bertx_index_search_filtered does.  bertx_index_search_probed_texts
+ * encodes as bertx_index_search_texts does.
+ * An index without lists does exactly what it did before; search, score_ids, the rescored and
+ * the hybrid entries never read the lists and launch the kernels they launched before.
+ * Not provided: lists on a binary index; probing as the coarse stage of the rescored or the
+ * hybrid search; inserting into the image without laying it out again; splitting one long list
+ * over several workgroups (a list is scanned by one workgroup per 16 queries that probe it);
+ * product quantization.
  */
 enum { BERTX_INDEX_F16 = 0, BERTX_INDEX_I8 = 1 };
 enum { BERTX_INDEX_BIN = 8 };   /* the embedding index only: "Binary storage" above */
@@ -588,6 +638,23 @@ BERT_API int32_t bertx_index_search_rescored_filtered_device(struct bertx_index 
                                                              const float *d_queries, int32_t B, int32_t k, int32_t n_cand,
                                                              const uint32_t *d_filters, int32_t n_filters, int32_t words,
                                                              float *d_scores, int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_index_set_lists(struct bertx_index *idx, const float *cent, int32_t C);
+BERT_API int32_t bertx_index_train_lists(struct bertx_index *idx, int32_t C, int32_t iters, uint32_t seed);
+BERT_API int32_t bertx_index_build_lists(struct bertx_index *idx);
+BERT_API int32_t bertx_index_lists(struct bertx_index *idx);
+BERT_API int32_t bertx_index_list_centroid(struct bertx_index *idx, int32_t c, float *out);
+BERT_API int32_t bertx_index_row_lists(struct bertx_index *idx, int32_t first, int32_t n, int32_t *out);
+BERT_API int32_t bertx_index_listed_rows(struct bertx_index *idx);
+BERT_API int64_t bertx_index_lists_bytes(struct bertx_index *idx);
+BERT_API int32_t bertx_index_search_probed(struct bertx_index *idx, const float *queries, int32_t B, int32_t k,
+                                           int32_t n_probe, const uint32_t *filters, int32_t n_filters, int32_t words,
+                                           float *scores, int32_t *ids);
+BERT_API int32_t bertx_index_search_probed_device(struct bertx_index *idx, const float *d_queries, int32_t B, int32_t k,
+                                                  int32_t n_probe, const uint32_t *d_filters, int32_t n_filters,
+                                                  int32_t words, float *d_scores, int32_t *d_ids, void *stream);
+BERT_API int32_t bertx_index_search_probed_texts(struct bertx_index *idx, struct bert_ctx *ctx, int32_t n_threads, int32_t n,
+                                                 const char **texts, int32_t k, int32_t n_probe, float *scores,
+                                                 int32_t *ids);
 
 /*
  * Token store: late interaction (ColBERT's MaxSim) over per-token vectors.  An
@@ -1165,6 +1232,21 @@ BERT_API int32_t bertx_bench_search_add_rate(int32_t d, int32_t N, double *add_r
 BERT_API int32_t bertx_bench_search_ex(int32_t d, int32_t N, int32_t B, int32_t k, int32_t storage, int32_t iters,
                                        float *avg_us);
 BERT_API int32_t bertx_bench_search_add_rate_ex(int32_t d, int32_t N, int32_t storage, double *add_rows_per_s);
+/*
+ * The flat and the probed search ("Lists and probed search") on the same synthetic index in one
+ * process.  Planted data: C unit centroids of hashed values; row r = centroid r % C + 0.5 x a unit
+ * row of hashed values; query b = centroid (7919 b + 13) % C + 0.5 x another unit row; the lists
+ * are bertx_index_set_lists of those centroids.  After 3 warm-up calls of every form, each of
+ * `rounds` rounds times `iters` calls of bertx_index_search_device (flat_us[round]) and then of
+ * bertx_index_search_probed_device for every n_probes[i] (probed_us[i][round]), average device
+ * time per call.  recall[i]: the share of the flat search's k ids that the probed search with
+ * n_probes[i] returns, on this synthetic set.  build_ms: the host time of bertx_index_set_lists
+ * (assignment and layout); image_bytes: bertx_index_lists_bytes.
+ */
+BERT_API int32_t bertx_bench_search_lists(int32_t d, int32_t N, int32_t B, int32_t k, int32_t storage, int32_t C,
+                                          const int32_t *n_probes, int32_t n_np, int32_t rounds, int32_t iters,
+                                          float *flat_us, float *probed_us, float *recall, double *build_ms,
+                                          int64_t *image_bytes);
 /*
  * The two-stage search on the same data: a binary index and an index of kind `fine`
  * (BERTX_INDEX_F16 or _I8) of the same N rows.  avg_us[0]: bertx_index_search_rescored_device
